@@ -6,10 +6,14 @@ followed by the forward recursion for PER_GPU_BATCH independent, DISTINCT ANYmal
 instances (nv=18, 4 point contacts, N=40 -> 47 grids with 2 lifts + 2 impacts; randomised
 stage data and initial state directions, generated in HBM), inputs resident in HBM.
 One process per GPU; instances are sharded across ranks with no data-path collective
-(weak scaling: fixed work per GPU); after the timed region the step directions are
-all-gathered over RCCL (the one real exchange step) to validate the multi-GPU path.
+(weak scaling: fixed work per GPU).
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...); --dump-outputs DIR also writes what the last timed
+step computed.  --full adds everything else this file measures after the timed steps: the roofline
+block, the RCCL all-gather of the step directions (the one real exchange step) and the
+strong-scaling block with --gpus N > 1, the SQP iteration, the other BASELINE configurations and the
+CPU baseline, with the full record in --detail-out (see DESIGN.md "Measurement" for every field).
 """
 import argparse
 import json
@@ -27,6 +31,9 @@ PER_GPU_BATCH = 4096
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 F64_MFMA_PEAK_TFLOPS = 78.6  # MI355X spec sheet, dense fp64 matrix (= the fp64 vector rate)
 PROFILE_ROUND = "r06"
+DUMP_INSTANCES = 32        # --dump-outputs: instances sampled (a fixed seed) from the batch, ~32 MB of records
+DUMP_SEED = 20260917
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def kernel_source_hash():
@@ -462,7 +469,8 @@ def compact_line(res):
     for k in ("rccl_gather_ok", "rccl_gather_c_abi_ok", "gather_backend", "dry_run", "gather_ok"):
         if k in res:
             out[k] = res[k]
-    out["detail"] = res.get("detail_file")
+    if "detail_file" in res:
+        out["detail"] = res["detail_file"]
     line = json.dumps(out, allow_nan=False, separators=(",", ":"))
     if len(line) > COMPACT_LIMIT:   # never let the line outgrow the driver's tail again: shed the optional blocks
         for k in ("other_configs", "sqp_phase_ms", "roofline_expand", "roofline_condense"):
@@ -488,18 +496,66 @@ def _finite(o):
 
 
 def emit(res, detail_path):
-    """Write the full record to `detail_path` (best effort) and print the compact line as the LAST line of stdout."""
+    """Write the full record to `detail_path` (best effort; None: no file) and print the compact line as the LAST line of
+    stdout."""
     res = _finite(res)
     try:
-        os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-        with open(detail_path, "w") as f:
-            json.dump(res, f, allow_nan=False)
-            f.write("\n")
-        res["detail_file"] = os.path.relpath(detail_path, ROOT)
+        if detail_path is not None:
+            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+            with open(detail_path, "w") as f:
+                json.dump(res, f, allow_nan=False)
+                f.write("\n")
+            res["detail_file"] = os.path.relpath(detail_path, ROOT)
     except OSError as e:
         res["detail_file"] = "not written: %r" % (e,)
     sys.stdout.flush()
     print(compact_line(res), flush=True)
+
+
+def headline_record(args, world, batch, grids, dt, bad):
+    """The contract keys of the headline line: what a plain run prints, and what --full extends."""
+    return {
+        "metric": "riccati_sweeps_per_sec",
+        "value": world * batch * args.steps / dt,
+        "unit": "sweeps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "anymal_trot_N40 (nv=18,nu=12, 47 grids: 2 lifts + 2 impacts, "
+                               "switching constraints ns=6), %d DISTINCT OCP instances per GPU (randomised "
+                               "stage data and dx0), backward+forward Riccati sweep" % batch,
+                   "per_gpu_batch": batch, "stages": len(grids),
+                   "parallelism": "instances sharded, dp%d" % world, "backward_waves": args.waves},
+        "status_nonzero_instances": bad,
+    }
+
+
+def dump_outputs(out_dir, ctx, dir_t):
+    """--dump-outputs: the records the timed sweep hands its caller (the step directions, in the caller's tensor, and the
+    Riccati factorisation in the context's buffer) as they stand after the last timed step, for DUMP_INSTANCES instances
+    drawn with a fixed seed; one <dir|ric>_<field>.npy of shape [instances, stages, rows(, cols)] per record field."""
+    import torch
+    from robotoc_amd.types import BUF_RIC, Records
+    L, batch, n = ctx.L, dir_t.shape[0], ctx.nstages
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(batch, min(batch, DUMP_INSTANCES), replace=False))
+    recs = {"dir": dir_t[torch.from_numpy(idx).to(dir_t.device)].cpu().numpy(),
+            "ric": np.stack([ctx.download(BUF_RIC, (n, L.ric.stride), offset=int(b) * n * L.ric.stride) for b in idx])}
+    arrays = {}
+    for which, buf in recs.items():
+        R = Records(L, which)
+        for name in R.names:
+            arrays["%s_%s" % (which, name)] = np.ascontiguousarray(R.f(buf, name), dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sqp_single_instance(dims, grids, device):
@@ -819,13 +875,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)   # (the clock settles over the first ~8 launches: profiles/r03_dvfs_probe.txt)
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="instances per GPU")
     ap.add_argument("--waves", type=int, default=0, help="backward-kernel waves per instance (0=default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sqp", action="store_true", help="skip the SQP-iteration phase timing")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE.json configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sqp", action="store_true", help="with --full: skip the SQP-iteration phase timing")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE.json configurations")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="file the full (20+ KB) record goes to; stdout carries only the compact line")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / gather plumbing only, no GPU work (tests/test_bench_launcher.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, everything else this file measures: the roofline block (role-split kernel, "
+                         "copy / stream bandwidth probes, committed counter passes), the RCCL gather check and the strong-scaling "
+                         "block (--gpus N > 1), the SQP iteration, the other BASELINE configurations, the CPU baseline, and the "
+                         "full record in --detail-out.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (direction and Riccati records of a fixed sample of %d "
+                         "instances, one float64 .npy per field) into DIR" % DUMP_INSTANCES)
     args = ap.parse_args()
 
     # `python bench.py --gpus N` launches its N ranks itself (one process per GPU under torch.distributed.run); when the
@@ -910,6 +974,7 @@ def main():
     sync_all()
     # HIP events on the launch stream (the stream handed to ctx.set_stream above) INSIDE the timed
     # region, so that the kernel times reported under `roofline` are those of exactly the launches `ms_per_step` covers
+    # (recorded with and without --full: both time the same loop)
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -920,13 +985,22 @@ def main():
         ev[k][2].record(stream)
     sync_all()
     dt = time.perf_counter() - t0
-    ms_b = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
-    ms_f = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     bad = int((ctx.status() != 0).sum())
+    if args.dump_outputs and rank == 0:   # rank 0's instances: the same inputs as a one-GPU run's
+        dump_outputs(args.dump_outputs, ctx, dir_t)
+    if not args.full:
+        if rank == 0:
+            emit(headline_record(args, world, batch, grids, dt, bad), None)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    ms_b = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
+    ms_f = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
     # the role-split kernel (the default up to round 4; what RTOC_OPT_BACKWARD_REGISTER = 0 runs) on the same records, for the record
     ms_b_rs = None
     if args.waves == 0:
@@ -1452,8 +1526,6 @@ def main():
             others["icub_jump_sto_example_N130"] = {"error": repr(e)}
 
     if rank == 0:
-        total_sweeps = world * batch * args.steps
-        value = total_sweeps / dt
         bytes_b = algorithmic_bytes(L, grids, batch, "backward")
         bytes_f = algorithmic_bytes(L, grids, batch, "forward")
         fl_b = backward_flops(L, grids, batch)
@@ -1461,24 +1533,9 @@ def main():
         from robotoc_amd.types import OPT_BACKWARD_REGISTER
         kname = ("riccati_backward_rv_kernel" if args.waves == 0 and ctx.get_option(OPT_BACKWARD_REGISTER) else
                  "riccati_backward_rs4_kernel" if args.waves in (0, 8) else "riccati_backward_kernel")
-        res = {
-            "metric": "riccati_sweeps_per_sec",
-            "value": value,
-            "unit": "sweeps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "anymal_trot_N40 (nv=18,nu=12, 47 grids: 2 lifts + 2 impacts, "
-                                   "switching constraints ns=6), %d DISTINCT OCP instances per GPU (randomised "
-                                   "stage data and dx0), backward+forward Riccati sweep" % batch,
-                       "per_gpu_batch": batch, "distinct_instances_per_gpu": distinct, "stages": len(grids),
-                       "parallelism": "instances sharded, dp%d" % world, "backward_waves": args.waves},
+        res = headline_record(args, world, batch, grids, dt, bad)
+        res["config"]["distinct_instances_per_gpu"] = distinct
+        res.update({
             "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS,
                          "traffic": pmc_traffic(kname) if batch == PER_GPU_BATCH else None,
@@ -1503,8 +1560,7 @@ def main():
                          "forward_frac": bytes_f / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBS,
                          "forward_algorithmic_bytes_per_launch": bytes_f,
                          "forward_traffic": pmc_traffic("riccati_forward_kernel") if batch == PER_GPU_BATCH else None},
-            "status_nonzero_instances": bad,
-        }
+        })
         if sqp is not None:
             res["sqp_iteration"] = sqp
             if world == 1:

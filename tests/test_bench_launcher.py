@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,7 +43,7 @@ def test_bench_refuses_a_rank_count_that_is_not_gpus():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_device():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--no-sqp", "--no-configs"],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--full", "--no-cpu-baseline", "--no-sqp", "--no-configs"],
              {"RTOC_BENCH_BACKEND": "gloo", "RTOC_BENCH_ONE_DEVICE": "1"})
     assert r["n_gpus"] == 2 and r["rccl_gather_ok"] is True and r["status_nonzero_instances"] == 0
     assert r["value"] > 0 and r["config"]["per_gpu_batch"] == 64
@@ -53,6 +54,33 @@ def test_bench_two_ranks_on_one_device():
     ss = r["strong_scaling"]
     assert ss["total_instances"] == 64 and ss["per_gpu_batch"] == 32 and ss["value"] > 0
     assert ss["backward_kernel_ms"] + ss["forward_kernel_ms"] <= ss["ms_per_step"] * 1.001
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """Without --full the run times exactly --steps steps and prints the contract keys only; --dump-outputs writes what the last
+    timed step computed for a fixed sample of instances, float64, within 64 MB, the same from run to run."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        runs.append((_run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64", "--dump-outputs", str(out)]), out))
+    r = runs[0][0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 3 and r["status_nonzero_instances"] == 0 and r["config"]["per_gpu_batch"] == 64
+    assert abs(r["value"] - 64 / (r["ms_per_step"] * 1e-3)) <= 1e-4 * r["value"]
+    for k in ("roofline", "cpu_baseline", "sqp_iters_per_sec", "other_configs", "detail"):
+        assert k not in r, k
+    files = sorted(os.listdir(runs[0][1]))
+    assert files == sorted(os.listdir(runs[1][1])) and {"dir_dx.npy", "dir_du.npy", "ric_P.npy", "ric_K.npy"} <= set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(runs[0][1] / f), np.load(runs[1][1] / f)
+        assert a.dtype == np.float64 and a.shape[:2] == (32, 47), (f, a.dtype, a.shape)
+        assert np.isfinite(a).all() and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.abs(np.load(runs[0][1] / "dir_du.npy")).max() > 0
 
 
 def test_compact_line_of_a_full_record_fits_the_drivers_tail():

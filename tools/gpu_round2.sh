@@ -12,14 +12,14 @@ rocminfo 2>/dev/null | grep -E "Marketing Name|Compute Unit|Max Clock" | head -8
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 1500 python -m pytest tests -m gpu -q -x --durations=8 ${PYTEST_ARGS:-} 2>&1 | tail -40 > $OUT/pytest_gpu.log
 fi
-timeout 900 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   export TMPDIR=/tmp
   cd /tmp
-  B="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-}"
+  B="python $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline ${BENCH_ARGS:-}"
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o stats -- $B > $OUT/prof_stats.log 2>&1
   if [ "${SKIP_PMC:-0}" != "1" ]; then
-    B3="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+    B3="python $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-}"
     timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_fetch -o fetch -- $B3 > $OUT/prof_fetch.log 2>&1
     timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write -o write -- $B3 > $OUT/prof_write.log 2>&1
     timeout 900 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT/prof_sq1 -o sq1 -- $B3 > $OUT/prof_sq1.log 2>&1

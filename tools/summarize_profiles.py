@@ -10,7 +10,7 @@ DST = os.environ.get("RTOC_PROFILE_OUT", os.path.join(R, "profiles"))
 os.makedirs(DST, exist_ok=True)
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 note = sys.argv[2] if len(sys.argv) > 2 else ""
-lines = ["# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline   (%s)" % note,
+lines = ["# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline   (%s)" % note,
          "# counter passes: rocprofv3 --pmc <set> -- python tools/pmc_driver.py 3   (tools/gpu_pmc2.sh; same kernels, same sizes, no torch in the process)",
          "# Name, Calls, TotalDurationNs, AverageNs, Percentage, MinNs, MaxNs, StdDev"]
 for r in csv.DictReader(open(os.path.join(OUT, "prof_stats", "stats_kernel_stats.csv"))):
