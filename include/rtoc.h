@@ -143,8 +143,10 @@ enum rtoc_option {
                               * verifies the structured rows of every record it factorises -- they are in its LDS anyway --
                               * and sets RTOC_STAT_FXX_UNSTRUCTURED on an instance that breaks the shape; the iCub-size
                               * shapes' register-wide kernel never loads those rows, so on a bound buffer the device check
-                              * runs again before every backward recursion (one pass over the top halves: ~8 % of that
-                              * recursion; rtoc_upload-ed buffers are checked once per upload).  Mode 2 switches both off. */
+                              * runs again in every call that runs a backward recursion (rtoc_riccati_backward,
+                              * rtoc_riccati_sweep however many RTOC_OPT_SWEEP_CHUNKS, rtoc_newton_iteration, ...: one pass
+                              * over the top halves, ~8 % of that recursion; rtoc_upload-ed buffers are checked once per
+                              * upload).  The call decides the kernel once, for all of its chunks.  Mode 2 switches both off. */
   RTOC_OPT_GRAPH = 9, /* 1: rtoc_riccati_sweep and rtoc_newton_iteration replay their launch sequence from a captured
                       * hipGraph (captured on the second call after any change of grid, options, buffers, rows or
                       * cones; arguments kkt_tol / tau are part of the key).  For the single-OCP latency path, whose
@@ -176,7 +178,7 @@ enum rtoc_option {
                       * register-wide kernel (riccati_backward_rw.hpp, nx = 64: one wavefront per instance and SIMD, P+ in 16 accumulator
                       * tiles; riccati_backward_rw2.hpp, nx = 70: two wavefronts per instance, P+ in 25 tiles in each, the stage split
                       * between them by role and by column tiles; the dense rows of a STRUCTURED Fxx staged in LDS; checked on the device
-                      * like RTOC_OPT_FXX_STRUCTURE -- on a bound record buffer before every recursion unless that option is 2;
+                      * like RTOC_OPT_FXX_STRUCTURE -- on a bound record buffer in every call unless that option is 2;
                       * switching-constraint grid points as one-stage launches of the tile-split kernel): with 1 on batches of more
                       * instances than the device has compute units (below that the tile-split kernel's four waves per instance
                       * finish a horizon sooner), with 2 on every batch.  Elsewhere, and with 0, the role-split / tile-split
@@ -244,7 +246,9 @@ int rtoc_get_option(rtoc_ctx* ctx, int option, int64_t* value);
 /* Host <-> HBM transfers of whole buffers (count in doubles, from the buffer start +offset). */
 int rtoc_upload(rtoc_ctx* ctx, int buffer, size_t offset, const double* host, size_t count);
 int rtoc_download(rtoc_ctx* ctx, int buffer, size_t offset, double* host, size_t count);
-/* Device pointer / element count of a buffer (for zero-copy interop and RCCL). */
+/* Device pointer / element count of a buffer (for zero-copy interop and RCCL).  Once rtoc_device_ptr has handed out
+ * RTOC_BUF_KKT, the context treats that buffer as written by the caller for the rest of its life, like a bound one
+ * (RTOC_OPT_FXX_STRUCTURE). */
 void* rtoc_device_ptr(rtoc_ctx* ctx, int buffer);
 size_t rtoc_buffer_count(const rtoc_ctx* ctx, int buffer);
 /* Replace a buffer by caller-owned device memory of at least rtoc_buffer_count doubles. */

@@ -53,8 +53,8 @@ static const std::vector<KernelSet>& kernel_table() {
 }
 
 // Shapes beyond the compiled-in table: librtoc_shape_<nv>_<nu>_<ns>.so next to this library (or in $RTOC_SHAPE_DIR),
-// built by `make -C robotoc_amd/csrc plugin SHAPE=nv:nu:ns:nw0:nw1`; with RTOC_SHAPE_JIT=1 rtoc_create builds it itself
-// (hipcc + the source directory this library was built from must be present; ~1 min, once).
+// built by `make -C robotoc_amd/csrc plugin SHAPE=nv:nu:ns:nw0:nw1`; with RTOC_SHAPE_JIT=1 rtoc_create builds it itself, next to
+// this library wherever it lives now (hipcc + the source directory this library was built from must be present; ~1 min, once).
 #include <mutex>
 static std::vector<KernelSet>& plugin_table() {
   static std::vector<KernelSet> t;
@@ -87,9 +87,10 @@ static const KernelSet* load_plugin(const rtoc_dims* d) {
   if (!h && jit && jit[0] == '1') {
     // tile-split wave counts by state dimension, like the compiled-in shapes: one / three waves up to 36, four beyond
     const int nx = 2 * d->nv, nw0 = nx <= 36 ? 1 : 4, nw1 = nx <= 36 ? 3 : (nx > 64 ? 5 : 4);
-    char cmd[1024];
-    snprintf(cmd, sizeof cmd, "make -s -C '%s' plugin SHAPE=%d:%d:%d:%d:%d >/dev/null 2>&1", RTOC_CSRC_DIR, d->nv, d->nu, d->ns_max, nw0, nw1);
-    if (system(cmd) == 0) h = dlopen((std::string(RTOC_CSRC_DIR) + "/../" + name).c_str(), RTLD_NOW | RTLD_LOCAL);
+    char shape[96];
+    snprintf(shape, sizeof shape, "SHAPE=%d:%d:%d:%d:%d", d->nv, d->nu, d->ns_max, nw0, nw1);
+    const std::string cmd = std::string("make -s -C '") + RTOC_CSRC_DIR + "' plugin " + shape + " PLUGIN_DIR='" + library_dir() + "' >/dev/null 2>&1";
+    if (system(cmd.c_str()) == 0) h = dlopen((library_dir() + "/" + name).c_str(), RTLD_NOW | RTLD_LOCAL);
   }
 #endif
   if (!h) return nullptr;
@@ -144,6 +145,13 @@ static hipError_t set_linearize_lds(const rtoc_robot_model& m, int nlevels, int 
 
 // ---- context --------------------------------------------------------------------------
 #define RTOC_MAX_CHUNK_EVENTS 16
+// the backward recursion of one public call, as plan_backward decides it
+enum BwdPath { BWD_SCAN, BWD_RV, BWD_RW, BWD_TILE };
+struct BwdPlan {
+  BwdPath path;   // horizon scan, register-resident, register-wide (iCub-size shapes), tile-split / role-split
+  bwd_fn kern;    // the kernel of the path (scan: its policy kernel; register-wide: the one between the one-stage launches)
+  int check_fxx;  // BwdArgs::check_fxx of the register-resident kernel: verify the structured rows as it goes
+};
 struct rtoc_ctx {
   rtoc_dims dims;
   rtoc_layout L;
@@ -154,7 +162,6 @@ struct rtoc_ctx {
   size_t count[RTOC_NUM_BUFFERS];
   bool owned[RTOC_NUM_BUFFERS];
   bool kkt_exposed;    // rtoc_device_ptr(RTOC_BUF_KKT) was handed out: the caller can rewrite the records without the runtime seeing it
-  bool capturing;      // inside run_graphed's stream capture (nothing that synchronises may run)
   rtoc_grid* d_grid;
   rtoc_box_row* d_rows;
   rtoc_box_row* h_rows;  // host copies (stage dump)
@@ -182,7 +189,7 @@ struct rtoc_ctx {
   int* d_stage_list;   // [max_stages] grid points 0 .. nstages - 2: the contact ones first (n_stage_contact), then the impact ones
   int n_stage_contact, n_stage_impact;
   int fxx_state;       // auto mode cache: 0 unknown (re-check before the next backward recursion), 1 every Fxx structured, 2 not
-  int fxx_last;        // the last check's answer (1 / 2; 0 never checked): the kernel choice baked into captured graphs
+  BwdPlan bwd_plan;    // the last plan_backward's answer: the backward kernel baked into captured graphs
   unsigned long long graph_replays;  // hipGraphLaunch count of RTOC_OPT_GRAPH (rtoc_graph_replay_count)
   int* d_fxx_flag;
   double* d_sto;       // rtoc_sto_eval_kkt staging: lt, diag(Qtt), squared error
@@ -370,13 +377,13 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   c->device = device;
   c->max_dts0 = 0.1;  // RiccatiRecursion(ocp, max_dts0 = 0.1), riccati_recursion.hpp:35
   c->bwd_variant = (ks->nvariants >= 3) ? ks->nvariants - 1 : 0;  // role-split kernel where it exists
-  c->bwd_register = 1;   // ... and the register-resident kernel wherever it applies (rv_applies, rw_applies)
+  c->bwd_register = 1;   // ... and the register-resident kernel wherever it applies (plan_backward)
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
     c->num_cus = cus;
   }
-  c->cond_register = 1;  // likewise the condensation (cond_rv_applies)
+  c->cond_register = 1;  // likewise the condensation (cond_register_applies)
   if (const char* e = getenv("RTOC_CONDENSE_REGISTER")) c->cond_register = (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
   HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
@@ -418,25 +425,20 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   HIP_TRY(hipMalloc((void**)&c->d_stage_list, sizeof(int) * max_stages));
   HIP_TRY(hipMalloc((void**)&c->d_status, sizeof(uint32_t) * batch));
   HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t) * batch, c->stream));
+  // dynamic LDS beyond the default limit: every kernel a launch may name (nullptr: not in this shape's kernel set)
+  const struct { const void* f; int bytes; } lds[] = {
+      {(const void*)ks->bwd_sa, ks->bwd_lds[3]},        {(const void*)ks->bwd_rv, ks->bwd_rv_lds},
+      {(const void*)ks->bwd_rv_sa, ks->bwd_rv_lds},     {(const void*)ks->bwd_rv_sto, ks->bwd_rv_lds},
+      {(const void*)ks->bwd_rw, ks->bwd_rw_lds},        {(const void*)ks->cond, ks->cond_lds},
+      {(const void*)ks->cond_split, ks->cond_split_lds}, {(const void*)ks->mjt, ks->mjt_lds},
+      {(const void*)ks->expd, ks->expd_lds},            {(const void*)ks->scan_elt, ks->scan_elt_lds},
+      {(const void*)ks->scan_comb, ks->scan_comb_lds},  {(const void*)ks->fscan_elt, ks->fscan_lds},
+      {(const void*)ks->fscan_comb, ks->fscan_lds},     {(const void*)ks->sto_prep, ks->sto_prep_lds},
+      {(const void*)ks->sto_vec, ks->sto_vec_lds}};
   for (int v = 0; v < ks->nvariants; ++v)
-    HIP_TRY(hipFuncSetAttribute((const void*)ks->bwd[v], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ks->bwd_lds[v]));
-  if (ks->bwd_sa)
-    HIP_TRY(hipFuncSetAttribute((const void*)ks->bwd_sa, hipFuncAttributeMaxDynamicSharedMemorySize, ks->bwd_lds[3]));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->cond, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ks->cond_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->cond_split, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ks->cond_split_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->mjt, hipFuncAttributeMaxDynamicSharedMemorySize, ks->mjt_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->expd, hipFuncAttributeMaxDynamicSharedMemorySize, ks->expd_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->scan_elt, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ks->scan_elt_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->scan_comb, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              ks->scan_comb_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->fscan_elt, hipFuncAttributeMaxDynamicSharedMemorySize, ks->fscan_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->fscan_comb, hipFuncAttributeMaxDynamicSharedMemorySize, ks->fscan_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->sto_prep, hipFuncAttributeMaxDynamicSharedMemorySize, ks->sto_prep_lds));
-  HIP_TRY(hipFuncSetAttribute((const void*)ks->sto_vec, hipFuncAttributeMaxDynamicSharedMemorySize, ks->sto_vec_lds));
+    HIP_TRY(hipFuncSetAttribute((const void*)ks->bwd[v], hipFuncAttributeMaxDynamicSharedMemorySize, ks->bwd_lds[v]));
+  for (const auto& k : lds)
+    if (k.f) HIP_TRY(hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -956,7 +958,26 @@ static int ensure_scan_buffers(rtoc_ctx* c) {
   return RTOC_OK;
 }
 
-static int launch_backward_scan(rtoc_ctx* c, int first, int end, hipStream_t stream) {
+// the arguments every backward launch shares (the register-resident and register-wide paths run only without
+// RTOC_OPT_WRITEBACK_KKT: writeback is set on the tile-split and scan paths alone)
+static BwdArgs bwd_args(const rtoc_ctx* c, int first, int end) {
+  BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.kkt = c->buf[RTOC_BUF_KKT];
+  a.kkt_rw = c->buf[RTOC_BUF_KKT];
+  a.ric = c->buf[RTOC_BUF_RIC];
+  a.grid = c->d_grid;
+  a.status = c->d_status;
+  a.prof = c->d_prof;
+  a.nstages = c->nstages;
+  a.batch = end;
+  a.first = first;
+  a.writeback = c->writeback;
+  a.max_dts0 = c->max_dts0;
+  return a;
+}
+
+static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
   const KernelSet* ks = c->ks;
   int rc0 = ensure_scan_buffers(c);
   if (rc0) return rc0;
@@ -981,19 +1002,8 @@ static int launch_backward_scan(rtoc_ctx* c, int first, int end, hipStream_t str
     hipLaunchKernelGGL(ks->scan_comb, dim3(n - d, nb, 2), dim3(ks->scan_comb_threads), ks->scan_comb_lds, stream, s);
     cur ^= 1;
   }
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
+  BwdArgs a = bwd_args(c, first, end);
   a.prof = nullptr;
-  a.nstages = n;
-  a.batch = end;
-  a.first = first;
-  a.writeback = c->writeback;
-  a.max_dts0 = c->max_dts0;
   a.scan_ps = c->d_scan[2];
   a.scan_ps_stride = ks->scan_ps_stride;
   a.scan_ps_soff = ks->scan_ps_soff;
@@ -1011,7 +1021,7 @@ static int launch_backward_scan(rtoc_ctx* c, int first, int end, hipStream_t str
     if (!ride) hipLaunchKernelGGL(ks->sto_prep, dim3(n - 1, nb), dim3(SCAN_STO_PREP_NT), ks->sto_prep_lds, stream, t);
   }
   a.sto_scr = ride ? c->d_scan_sto : nullptr;
-  hipLaunchKernelGGL(ks->bwd[v], dim3(nb, ride ? 2 * n - 1 : n), dim3(64 * ks->bwd_waves[v]), ks->bwd_lds[v], stream, a);
+  hipLaunchKernelGGL(p.kern, dim3(nb, ride ? 2 * n - 1 : n), dim3(64 * ks->bwd_waves[v]), ks->bwd_lds[v], stream, a);
   if (sto) hipLaunchKernelGGL(ks->sto_vec, dim3(nb), dim3(ks->sto_vec_threads), ks->sto_vec_lds, stream, t);   // s, k, m, the STO quantities
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -1036,92 +1046,73 @@ static int check_fxx(rtoc_ctx* c) {
   int bad = 1;
   HIP_TRY(hipMemcpyAsync(&bad, c->d_fxx_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // the kernel choice of the backward recursion is part of a captured graph: a new epoch only when the ANSWER changes, not
-  // whenever the records were re-uploaded (the documented loop re-linearises and uploads before every iteration)
-  if (c->fxx_last != (bad ? 2 : 1)) c->epoch++;
-  c->fxx_state = c->fxx_last = bad ? 2 : 1;
+  c->fxx_state = bad ? 2 : 1;
   return RTOC_OK;
 }
-// does the backward recursion of this context have a structure-exploiting kernel to choose? (quadruped shapes: the structured forms of
-// the role-split / register-resident kernels; iCub-size shapes: riccati_backward_rw_kernel, which exists in the structured form only)
-static bool rw_configured(const rtoc_ctx* c);
-static bool fxx_structured(rtoc_ctx* c) {
-  if (!((c->ks->bwd_sa && c->bwd_variant == 3) || rw_configured(c))) return false;  // no structured kernel for this shape / variant: nothing to check
-  if (c->fxx_mode == 1) return false;
-  if (c->fxx_mode == 2) return true;
-  if (c->fxx_state == 0 && check_fxx(c) != RTOC_OK) return false;
-  return c->fxx_state == 1;
+
+// The backward recursion of one public call: the horizon scan (RTOC_OPT_BACKWARD_SCAN), else (RTOC_OPT_BACKWARD_REGISTER) the
+// register-resident kernel (riccati_backward_rv.hpp, one launch per horizon; on grids with switching-time optimisation its STO form,
+// structured Fxx only), else on the iCub-size shapes the register-wide kernel (riccati_backward_rw.hpp, structured Fxx only; with 1
+// on batches of more instances than CUs -- below that the tile-split kernel's four waves per instance finish a horizon sooner --,
+// with 2 always), else the tile-split / role-split kernel.  The only code that checks the records (it synchronises) or resets
+// fxx_state: the entry points call it once, before any capture, and hand the plan to the launchers.
+static int plan_backward(rtoc_ctx* c, BwdPlan* out) {
+  const KernelSet* ks = c->ks;
+  // the register kernels: the default variant only (an explicit RTOC_OPT_BACKWARD_WAVES keeps its kernel)
+  const bool reg = c->bwd_register && c->h_grid && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback &&
+                   c->bwd_variant == ((ks->nvariants >= 3) ? ks->nvariants - 1 : 0);
+  const bool sto = reg && grid_has_sto(c);
+  const bool rw = reg && ks->bwd_rw && !sto && (c->bwd_register >= 2 || c->batch > c->num_cus);
+  // the caller may have rewritten the records since the runtime last saw them (a bound buffer, or its pointer handed out)
+  const bool rewritable = c->fxx_mode == 0 && (!c->owned[RTOC_BUF_KKT] || c->kkt_exposed);
+  int rc = RTOC_OK;
+  auto structured = [&]() {   // a structured kernel to choose, and the records have the structure
+    if (!((ks->bwd_sa && c->bwd_variant == 3) || rw) || c->fxx_mode == 1) return false;
+    if (c->fxx_mode == 2) return true;
+    if (c->fxx_state == 0 && rc == RTOC_OK) rc = check_fxx(c);
+    return c->fxx_state == 1;
+  };
+  BwdPlan p = {BWD_TILE, nullptr, 0};
+  if (scan_applies(c)) {
+    p = {BWD_SCAN, ks->bwd[ks->scan_policy_variant], 0};
+  } else if (reg && ks->bwd_rv && (!sto || (ks->bwd_rv_sto && structured()))) {
+    p.path = BWD_RV;
+    p.kern = sto ? ks->bwd_rv_sto : (ks->bwd_rv_sa && structured()) ? ks->bwd_rv_sa : ks->bwd_rv;
+    // a rewritable buffer may have changed since the check that chose the structured form: the kernel verifies as it goes
+    p.check_fxx = (p.kern != ks->bwd_rv && rewritable) ? 1 : 0;
+  } else {
+    // the register-wide kernel never loads the structured rows of Fxx, so it cannot verify them: check them for every call
+    if (rw && rewritable) c->fxx_state = 0;
+    const bool s = structured();
+    p.path = (rw && s) ? BWD_RW : BWD_TILE;
+    p.kern = (rw && s) ? ks->bwd_rw : s ? ks->bwd_sa : ks->bwd[c->bwd_variant];
+  }
+  if (rc) return rc;
+  // the plan is part of a captured graph: a new epoch when it changes, not whenever the records are checked again
+  if (p.path != c->bwd_plan.path || p.kern != c->bwd_plan.kern || p.check_fxx != c->bwd_plan.check_fxx) c->epoch++;
+  c->bwd_plan = *out = p;
+  return RTOC_OK;
 }
 
-// RTOC_OPT_BACKWARD_REGISTER: the register-resident kernel (riccati_backward_rv.hpp), one launch for the whole horizon.
-static bool rv_applies(rtoc_ctx* c) {
-  if (!(c->bwd_register && c->ks->bwd_rv && c->h_grid && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback &&
-        c->bwd_variant == ((c->ks->nvariants >= 3) ? c->ks->nvariants - 1 : 0)))   // (an explicit RTOC_OPT_BACKWARD_WAVES keeps its kernel)
-    return false;
-  // grids with switching-time optimisation: the STO instantiation, which exists in the structured-Fxx form only
-  if (grid_has_sto(c)) return c->ks->bwd_rv_sto && fxx_structured(c);
-  return true;
-}
-static int launch_backward_rv(rtoc_ctx* c, int first, int end, hipStream_t stream) {
-  const KernelSet* ks = c->ks;
-  const int N = c->nstages - 1, nb = end - first;
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
-  a.nstages = c->nstages;
-  a.batch = end;
-  a.first = first;
-  a.max_dts0 = c->max_dts0;
-  a.prof = c->d_prof;
+static int launch_backward_rv(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
+  const int N = c->nstages - 1;
+  BwdArgs a = bwd_args(c, first, end);
   // one launch for the whole horizon: regular, lift, impact and switching-constraint grid points are all the kernel's own
   a.seg_hi = N - 1;
   a.seg_lo = 0;
+  a.check_fxx = p.check_fxx;
 #ifdef RTOC_RV_DEBUG_MASK
   if (const char* e = getenv("RTOC_RV_DEBUG")) a.scan_ps_soff = atoi(e);
 #endif
-  const bool sto = grid_has_sto(c);
-  const bwd_fn kern = sto ? ks->bwd_rv_sto : ((ks->bwd_rv_sa && fxx_structured(c)) ? ks->bwd_rv_sa : ks->bwd_rv);   // RTOC_OPT_FXX_STRUCTURE, as for the role-split kernel
-  // a bound buffer may have been rewritten since the device check that chose the structured form: the kernel verifies as it goes
-  a.check_fxx = (kern != ks->bwd_rv && c->fxx_mode == 0 && (!c->owned[RTOC_BUF_KKT] || c->kkt_exposed)) ? 1 : 0;
-  if (N >= 1) hipLaunchKernelGGL(kern, dim3(nb), dim3(64), ks->bwd_rv_lds, stream, a);
+  if (N >= 1) hipLaunchKernelGGL(p.kern, dim3(end - first), dim3(64), c->ks->bwd_rv_lds, stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
 
-// RTOC_OPT_BACKWARD_REGISTER on the iCub-size shapes: the register-wide kernel (riccati_backward_rw.hpp; one wave per instance and
-// SIMD, structured Fxx).  1 (default): batches that fill the machine -- below one instance per CU the tile-split kernel's four waves
-// per instance finish a horizon sooner --, 2: always.  Switching-constraint grid points are one-stage launches of the tile-split
-// kernel between the segments (P+ / s+ through the Riccati records).
-static bool rw_configured(const rtoc_ctx* c) {
-  return c->bwd_register && c->ks->bwd_rw && c->h_grid && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback && !grid_has_sto(c) &&
-         c->bwd_variant == ((c->ks->nvariants >= 3) ? c->ks->nvariants - 1 : 0) && (c->bwd_register >= 2 || c->batch > c->num_cus);
-}
-static bool rw_applies(rtoc_ctx* c) {
-  if (!rw_configured(c)) return false;
-  // the kernel never loads the structured rows of Fxx, so it cannot verify them: on a bound buffer (the caller may have rewritten the
-  // records since the last check) the device check runs again before every recursion, unless the caller asserts the structure
-  if (c->fxx_mode == 0 && (!c->owned[RTOC_BUF_KKT] || c->kkt_exposed) && !c->capturing) c->fxx_state = 0;
-  return fxx_structured(c);
-}
-static int launch_backward_rw(rtoc_ctx* c, int first, int end, hipStream_t stream) {
+static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
   const KernelSet* ks = c->ks;
   const int N = c->nstages - 1, nb = end - first;
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
-  a.nstages = c->nstages;
-  a.batch = end;
-  a.first = first;
-  a.max_dts0 = c->max_dts0;
-  a.prof = c->d_prof;
+  BwdArgs a = bwd_args(c, first, end);
   const int v1 = ks->scan_policy_variant;
   auto constrained = [&](int st) { return c->h_grid[st].type != RTOC_GRID_IMPACT && c->h_grid[st].dims > 0; };
   auto one_stage = [&](int st) {   // tile-split kernel, grid point st only (st == N: the terminal record)
@@ -1144,38 +1135,30 @@ static int launch_backward_rw(rtoc_ctx* c, int first, int end, hipStream_t strea
     while (lo > 0 && !constrained(lo - 1)) --lo;
     a.seg_hi = hi;
     a.seg_lo = lo;
-    hipLaunchKernelGGL(ks->bwd_rw, dim3(nb), dim3(ks->bwd_rw_threads), ks->bwd_rw_lds, stream, a);
+    hipLaunchKernelGGL(p.kern, dim3(nb), dim3(ks->bwd_rw_threads), ks->bwd_rw_lds, stream, a);
     hi = lo - 1;
   }
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
 
-static int launch_backward_range(rtoc_ctx* c, int first, int end, hipStream_t stream) {
-  if (scan_applies(c)) return launch_backward_scan(c, first, end, stream);
-  if (rv_applies(c)) return launch_backward_rv(c, first, end, stream);
-  if (rw_applies(c)) return launch_backward_rw(c, first, end, stream);
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
-  a.prof = c->d_prof;
-  a.nstages = c->nstages;
-  a.batch = end;
-  a.first = first;
-  a.writeback = c->writeback;
-  a.max_dts0 = c->max_dts0;
-  const int v = c->bwd_variant;
-  const int ni = c->ks->bwd_inst[v];
-  const bwd_fn kern = fxx_structured(c) ? c->ks->bwd_sa : c->ks->bwd[v];
-  hipLaunchKernelGGL(kern, dim3((end - first + ni - 1) / ni), dim3(64 * c->ks->bwd_waves[v]), c->ks->bwd_lds[v], stream, a);
+static int launch_backward_tile(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
+  const int v = c->bwd_variant, ni = c->ks->bwd_inst[v];
+  const BwdArgs a = bwd_args(c, first, end);
+  hipLaunchKernelGGL(p.kern, dim3((end - first + ni - 1) / ni), dim3(64 * c->ks->bwd_waves[v]), c->ks->bwd_lds[v], stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
-static int launch_backward(rtoc_ctx* c) { return launch_backward_range(c, 0, c->batch, c->stream); }
+
+static int launch_backward_range(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
+  switch (p.path) {
+    case BWD_SCAN: return launch_backward_scan(c, p, first, end, stream);
+    case BWD_RV: return launch_backward_rv(c, p, first, end, stream);
+    case BWD_RW: return launch_backward_rw(c, p, first, end, stream);
+    default: return launch_backward_tile(c, p, first, end, stream);
+  }
+}
+static int launch_backward(rtoc_ctx* c, const BwdPlan& p) { return launch_backward_range(c, p, 0, c->batch, c->stream); }
 
 // Forward recursion as a prefix scan of the closed-loop maps (riccati_scan.hpp): maps of all grid points,
 // log2 composition levels (dx of every grid point), then du / dlmdgmm / dxi of all grid points at once.
@@ -1233,10 +1216,10 @@ static int launch_forward(rtoc_ctx* c) { return launch_forward_range(c, 0, c->ba
 // forward recursion of chunk i (HBM-bound, a few small waves per CU) runs under the backward
 // recursion of chunk i+1 (MFMA / LDS-bound, leaves most of the HBM bandwidth idle).  Results are
 // those of rtoc_riccati_backward followed by rtoc_riccati_forward.
-static int launch_sweep(rtoc_ctx* c) {
+static int launch_sweep(rtoc_ctx* c, const BwdPlan& p) {
   const int nch = (c->sweep_chunks > 0) ? c->sweep_chunks : 1;
-  if (nch == 1 || scan_applies(c)) {  // the scan's element buffers are not chunked
-    int rc = launch_backward(c);
+  if (nch == 1 || p.path == BWD_SCAN) {  // the scan's element buffers are not chunked
+    int rc = launch_backward(c, p);
     return rc ? rc : launch_forward(c);
   }
   const int per = (((c->batch + nch - 1) / nch) + 3) & ~3;  // whole 4-instance workgroups
@@ -1244,7 +1227,7 @@ static int launch_sweep(rtoc_ctx* c) {
   HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
   for (int i = 0; i * per < c->batch; ++i) {
     const int first = i * per, end = (first + per < c->batch) ? first + per : c->batch;
-    int rc = launch_backward_range(c, first, end, c->stream);
+    int rc = launch_backward_range(c, p, first, end, c->stream);
     if (rc) return rc;
     hipEvent_t e = c->ev_chunk[i % RTOC_MAX_CHUNK_EVENTS];
     HIP_TRY(hipEventRecord(e, c->stream));
@@ -1265,7 +1248,7 @@ static int launch_sweep(rtoc_ctx* c) {
 static bool cond_rv_fuses_cones(const rtoc_ctx* c) {
   return c->cone_contacts > 0 && c->cone_rows == RTOC_FRICTION_ROWS && c->cone_dim == 3 && c->ks->cond_fuses_cones && c->ks->cond_rv_cones;
 }
-static bool cond_rv_applies(const rtoc_ctx* c) {
+static bool cond_register_applies(const rtoc_ctx* c) {
   if (!c->cond_register || !c->ks->cond_rv || c->condense_split || c->keep_qaf) return false;
   if (c->cone_contacts > 0 && !cond_rv_fuses_cones(c) && c->cond_register < 2) return false;
   return c->n_stage_contact + c->n_stage_impact == c->nstages - 1;
@@ -1297,7 +1280,7 @@ static int launch_condense(rtoc_ctx* c) {
   a.cone_rows = 0;
   a.keep_qaf = c->keep_qaf;
   a.dt_inst = c->sto_on ? c->d_dt : nullptr;
-  const bool rv = cond_rv_applies(c);
+  const bool rv = cond_register_applies(c);
   if ((rv ? cond_rv_fuses_cones(c) : (c->condense_split || c->ks->cond_fuses_cones)) && c->cone_contacts > 0) {  // the cone rows ride with the MJtJinv kernel / in wave 1 of the fused kernel / inside condense_rv_kernel
     if (!c->buf[RTOC_BUF_CONE] || !c->buf[RTOC_BUF_CON]) return RTOC_ERR_NOT_READY;
     const bool wrench = c->cone_rows == RTOC_WRENCH_ROWS;
@@ -1455,7 +1438,7 @@ int rtoc_compute_initial_state_direction(rtoc_ctx* c) {
 int rtoc_condense(rtoc_ctx* c) {
   CHECK_READY(c);
   int rc = RTOC_OK;
-  if (c->cone_contacts > 0 && (cond_rv_applies(c) ? !cond_rv_fuses_cones(c) : (!c->condense_split && !c->ks->cond_fuses_cones)))
+  if (c->cone_contacts > 0 && (cond_register_applies(c) ? !cond_rv_fuses_cones(c) : (!c->condense_split && !c->ks->cond_fuses_cones)))
     rc = launch_cones(c, 0, 0.0);  // Constraints::condenseSlackAndDual first
   if (!rc) rc = launch_condense(c);
   if (!rc && c->buf[RTOC_BUF_SE3] && c->dims.np == 6) rc = launch_state_correction(c, 0);
@@ -1464,7 +1447,9 @@ int rtoc_condense(rtoc_ctx* c) {
 
 int rtoc_riccati_backward(rtoc_ctx* c) {
   CHECK_READY(c);
-  return launch_backward(c);
+  BwdPlan p;
+  int rc = plan_backward(c, &p);
+  return rc ? rc : launch_backward(c, p);
 }
 
 int rtoc_riccati_forward(rtoc_ctx* c) {
@@ -1472,16 +1457,14 @@ int rtoc_riccati_forward(rtoc_ctx* c) {
   return launch_forward(c);
 }
 
-// RTOC_OPT_GRAPH: run `body` (a sequence of kernel launches on c->stream, no allocation, no synchronisation) from a
-// captured hipGraph.  The first call at a given configuration epoch runs it plainly (lazy allocations happen there),
+// RTOC_OPT_GRAPH: run `body` (a sequence of kernel launches on c->stream, no allocation, no synchronisation; its backward plan
+// resolved by the caller) from a captured hipGraph.  The first call at a given configuration epoch runs it plainly (lazy allocations happen there),
 // the second captures and instantiates, later calls are one hipGraphLaunch -- a single-OCP Newton iteration is ~25
 // small kernels, whose launch gaps are a third of its latency.
 extern "C++" {
 template <class Body>
 static int run_graphed(rtoc_ctx* c, rtoc_ctx::GraphSlot* g, double p0, double p1, Body body) {
   if (!c->use_graph) return body();
-  (void)rw_applies(c);      // (bound buffers of the iCub-size shapes: the re-check of every recursion, see rw_applies)
-  (void)fxx_structured(c);  // may check the records (synchronises): before, never inside, a capture
   if (g->exec && g->epoch == c->epoch && g->p0 == p0 && g->p1 == p1) {
     HIP_TRY(hipGraphLaunch(g->exec, c->stream));
     c->graph_replays++;
@@ -1499,9 +1482,7 @@ static int run_graphed(rtoc_ctx* c, rtoc_ctx::GraphSlot* g, double p0, double p1
   }
   hipGraph_t graph = nullptr;
   HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-  c->capturing = true;
   const int rc = body();
-  c->capturing = false;
   const hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc || e != hipSuccess || !graph) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -1532,7 +1513,9 @@ int rtoc_graph_replay_count(rtoc_ctx* c, unsigned long long* out) {
 
 int rtoc_riccati_sweep(rtoc_ctx* c) {
   CHECK_READY(c);
-  return run_graphed(c, &c->g_sweep, 0.0, 0.0, [&]() { return launch_sweep(c); });
+  BwdPlan p;
+  int rc = plan_backward(c, &p);
+  return rc ? rc : run_graphed(c, &c->g_sweep, 0.0, 0.0, [&]() { return launch_sweep(c, p); });
 }
 
 static int launch_fill(rtoc_ctx* c, double dt) {
@@ -1576,9 +1559,10 @@ int rtoc_unconstr_backward(rtoc_ctx* c, double dt) {
   CHECK_READY(c);
   if (c->dims.nu != c->dims.nv || !(dt > 0.0)) return RTOC_ERR_BAD_ARG;
   if (unconstr_structured(c)) return launch_unconstr_riccati(c, dt, false);
+  BwdPlan p;
   int rc = launch_fill(c, dt);
-  if (rc) return rc;
-  return launch_backward(c);
+  if (!rc) rc = plan_backward(c, &p);
+  return rc ? rc : launch_backward(c, p);
 }
 
 static int launch_unconstr_dynamics(rtoc_ctx* c, bool expand, double dt) {
@@ -1819,13 +1803,15 @@ int rtoc_time_phase(rtoc_ctx* c, int phase, int reps, float* ms) {
   if (!ms || reps < 1 || phase < 0 || phase > 8) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   for (int r = 0; r < reps; ++r) {
-    int rc = RTOC_OK;
+    BwdPlan p;
+    int rc = (phase == 0 || phase == 4) ? plan_backward(c, &p) : RTOC_OK;
+    if (rc) return rc;
     switch (phase) {
-      case 0: rc = launch_backward(c); break;
+      case 0: rc = launch_backward(c, p); break;
       case 1: rc = launch_forward(c); break;
       case 2: rc = rtoc_condense(c); break;      // incl. cone rows / state-equation correction if set
       case 3: rc = rtoc_expand(c, 0.995); break;
-      case 4: rc = launch_sweep(c); break;
+      case 4: rc = launch_sweep(c, p); break;
       case 5: rc = rtoc_update(c); break;
       case 6: rc = rtoc_newton_iteration(c, 0.0, 0.995); break;  // the whole iteration as one launch sequence
       case 7: rc = rtoc_linearize_contact_dynamics(c, 0); break;
@@ -2192,9 +2178,7 @@ static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   a.dt_inst = c->sto_on ? c->d_dt : nullptr;
   hipLaunchKernelGGL(state_equation_lin_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  if (zeroed && c->fxx_last != 1) c->epoch++;  // the kernel choice of the backward recursion is part of a captured graph
   c->fxx_state = zeroed ? 1 : 0;
-  if (zeroed) c->fxx_last = 1;
   return RTOC_OK;
 }
 
@@ -3130,13 +3114,13 @@ __global__ void mask_converged_kernel(double* steps, const double* kkterr, int* 
   }
 }
 
-static int newton_iteration_body(rtoc_ctx* c, double kkt_tol, double tau) {
+static int newton_iteration_body(rtoc_ctx* c, const BwdPlan& p, double kkt_tol, double tau) {
   HIP_TRY(hipMemsetAsync(c->d_nconv, 0, sizeof(int), c->stream));
   int rc = launch_kkt_error(c);  // on the freshly linearised (pre-condensation) records
   if (!rc && c->ls_on) rc = launch_eval_ocp(c, c->d_eval);   // dms_.getEval(): cost + barrier, violation of the current iterate
   if (!rc) rc = rtoc_condense(c);
   if (!rc && c->sto_on) STO_LAUNCH(sto_eval_kkt_dev_kernel, c);   // sto_.evalKKT (ocp_solver.cpp:119); KKTError() gains the STO term
-  if (!rc) rc = launch_sweep(c);
+  if (!rc) rc = launch_sweep(c, p);
   if (!rc) rc = rtoc_expand(c, tau);  // directions + fraction-to-boundary step sizes, on the device
   if (rc) return rc;
   if (c->sto_on) STO_LAUNCH(sto_step_sizes_kernel, c);             // sto_.computeStepSizes, min with the stages' steps (:128-132)
@@ -3157,11 +3141,14 @@ int rtoc_newton_iteration(rtoc_ctx* c, double kkt_tol, double tau) {
   CHECK_READY(c);
   if (!(kkt_tol >= 0.0) || !(tau > 0.0 && tau <= 1.0)) return RTOC_ERR_BAD_ARG;
   if (!c->d_nconv) HIP_TRY(hipMalloc((void**)&c->d_nconv, sizeof(int)));
+  BwdPlan p;
+  int rc = plan_backward(c, &p);   // (the condensation ahead of the sweep leaves the rows of Fxx the check reads as they are)
+  if (rc) return rc;
   if (c->ls_on) {   // the backtracking loop synchronises with the host: no graph replay
-    int rc = ensure_line_search(c);
-    return rc ? rc : newton_iteration_body(c, kkt_tol, tau);
+    rc = ensure_line_search(c);
+    return rc ? rc : newton_iteration_body(c, p, kkt_tol, tau);
   }
-  return run_graphed(c, &c->g_newton, kkt_tol, tau, [&]() { return newton_iteration_body(c, kkt_tol, tau); });
+  return run_graphed(c, &c->g_newton, kkt_tol, tau, [&]() { return newton_iteration_body(c, p, kkt_tol, tau); });
 }
 
 int rtoc_converged_count(rtoc_ctx* c, int* host_count) {

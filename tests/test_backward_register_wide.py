@@ -280,3 +280,64 @@ def test_register_wide_kernel_rechecks_a_bound_buffer_before_every_recursion(ora
         assert not torch.equal(auto[3].view(torch.int64), wide[3].view(torch.int64))
     finally:
         ctx.close()
+
+
+def test_register_wide_bound_sweep_decides_the_kernel_once_for_all_chunks():
+    """Bound record buffers (RTOC_OPT_FXX_STRUCTURE = 0) and a sweep pipelined over three chunks of instances: the backward kernel
+    is decided once per call, for every chunk.  (a) The chunked sweep equals the unchunked one bit for bit.  (b) After a stray entry
+    is written in place into a structured row of one Fxx, EVERY instance of the chunked sweep equals the tile-split kernel's bit for
+    bit (the register-wide kernel's bits differ from those in every chunk).  (c) The same as a replayed HIP graph, no option
+    changed between the steps: the replays pick up the rewrite, then the restore."""
+    import torch
+    from robotoc_amd import capi
+    dims, grids, _ = pr.config_icub_jump(nv=32)
+    batch, n = 12, len(grids)   # three chunks of four instances (whole 4-instance workgroups)
+    ctx = capi.Context(dims, n, batch, 0)
+    try:
+        L = ctx.L
+        ctx.set_grid(grids)
+        ctx.set_fxx_structure(0)
+        kkt = torch.from_numpy(pr.make_kkt_batch(L, grids, batch, mode="dynamics")).to("cuda:0")
+        dx0 = torch.from_numpy(pr.make_dx0(L, batch)).to("cuda:0")
+        ric = torch.zeros((batch, n, L.ric.stride), dtype=torch.float64, device="cuda:0")
+        d = torch.zeros((batch, n, L.dir.stride), dtype=torch.float64, device="cuda:0")
+        for b_, t_ in ((BUF_KKT, kkt), (BUF_DX0, dx0), (BUF_RIC, ric), (BUF_DIR, d)):
+            ctx.bind(b_, t_.data_ptr())
+        torch.cuda.synchronize()
+        nx, o = 2 * dims.nv, L.kkt.off[0]
+        stray = (3, 12, o + 20 + 5 * nx)   # an entry of a structured row of Fxx
+        kept = float(kkt[stray])
+
+        def run(reps=1, value=kept):
+            kkt[stray] = value
+            for _ in range(reps):
+                ric.fill_(float("nan"))   # poison: every field compared must be written by this call
+                torch.cuda.synchronize()
+                ctx.riccati_sweep()
+                ctx.sync()
+            assert (ctx.status() == 0).all()
+            return ric.clone().view(torch.int64), d.clone().view(torch.int64)
+
+        def same(x, y, b):
+            return torch.equal(x[0][b], y[0][b]) and torch.equal(x[1][b], y[1][b])
+
+        ctx.set_backward_register(2)
+        wide = run()
+        ctx.set_backward_register(0)
+        dense = run()
+        dense_rewritten = run(value=-0.5)
+        for ch in (range(0, 4), range(4, 8), range(8, 12)):   # the two kernels' bits differ in every chunk: (b) tells which ran
+            assert any(not same(wide, dense, b) for b in ch), ch
+        ctx.set_backward_register(2)
+        ctx.set_sweep_chunks(3)
+        for graph in (False, True):
+            ctx.set_graph(graph)
+            for step, value, want in (("chunked", kept, wide), ("rewritten", -0.5, dense_rewritten), ("restored", kept, wide)):
+                replays = ctx.graph_replay_count()
+                got = run(4 if graph else 1, value)   # graph: warm-up, capture, replays
+                for b in range(batch):
+                    assert same(got, want, b), "graph=%s, %s: instance %d" % (graph, step, b)
+                if graph:
+                    assert ctx.graph_replay_count() - replays >= 2, step
+    finally:
+        ctx.close()
