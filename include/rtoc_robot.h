@@ -103,6 +103,52 @@ int rtoc_linearize_contact_dynamics(rtoc_ctx* ctx, int augment_residual);
  * rtoc_set_robot_model, rtoc_set_contact_schedule, rtoc_set_configuration_cost, rtoc_set_initial_state. */
 int rtoc_contact_eval_kkt(rtoc_ctx* ctx);
 
+/* ---- task-space cost components evaluated by rtoc_contact_eval_kkt beside the ConfigurationSpaceCost ----
+ * TaskSpace3DCost (src/cost/task_space_3d_cost.cpp: the world position of a frame) and CoMCost (src/cost/com_cost.cpp: the
+ * centre of mass), each with a constant reference (set_const_ref) or a periodic one: PeriodicSwingFootRef
+ * (src/cost/periodic_swing_foot_ref.cpp) / PeriodicCoMRef (src/cost/periodic_com_ref.cpp), evaluated on the device from the
+ * grid time (isActive / updateRef, the reference's loops).  Per active term: diff = x(q) - x_ref(t),
+ * lq += s J^T W diff, Qqq += s J^T W J (Gauss-Newton), the cost value s/2 sum W diff^2 into what evalOCP sums; s = dt on
+ * intermediate / lift grids with `weight`, 1 on impact grids with `weight_impact` and on the terminal grid with
+ * `weight_terminal`; on intermediate / lift grids also hx += J^T W diff and h += 1/2 sum W diff^2 (the STO sensitivities).
+ * A term whose weight of the grid's kind is zero is off there, as in the reference (enable_cost_).
+ * A frame term needs only the frame's origin in its parent joint's frame: the world-aligned linear Jacobian does not depend
+ * on the frame's rotation. */
+#define RTOC_TASK_FRAME_3D 0       /* TaskSpace3DCost                                                   */
+#define RTOC_TASK_COM 1            /* CoMCost                                                           */
+#define RTOC_REF_CONST 0           /* set_const_ref: x0 is the reference, always active                 */
+#define RTOC_REF_PERIODIC_FOOT 1   /* PeriodicSwingFootRef(x3d0 = x0, step_length = rate, step_height, t0,
+                                    *   period_swing = period_active, period_stance = period_inactive, is_first_step_half) */
+#define RTOC_REF_PERIODIC_COM 2    /* PeriodicCoMRef(com_ref0 = x0, vcom_ref = rate, t0, period_active, period_inactive,
+                                    *   is_first_move_half)                                              */
+#define RTOC_MAX_TASK_COSTS 8
+typedef struct rtoc_task_cost {
+  int kind, ref_kind;
+  int frame_parent;            /* RTOC_TASK_FRAME_3D: joint the frame is attached to                   */
+  int first_half;              /* is_first_step_half / is_first_move_half                              */
+  double frame_p[3];           /* frame origin in that joint's frame                                   */
+  double weight[3], weight_terminal[3], weight_impact[3];
+  double x0[3];                /* const ref / x3d0 / com_ref0                                          */
+  double rate[3];              /* step_length (foot) / vcom_ref (CoM)                                  */
+  double step_height, t0, period_active, period_inactive;   /* swing | stance, active | inactive       */
+} rtoc_task_cost;
+/* terms[nterms] shared by the batch (per_instance = 0) or terms[batch][nterms] (per_instance = 1: every instance its own
+ * references).  RTOC_ERR_BAD_ARG: nterms outside [0, RTOC_MAX_TASK_COSTS], a negative weight, a frame parent outside the
+ * model's joints, a non-positive period of a periodic reference, an unknown kind / ref_kind; needs rtoc_set_robot_model.
+ * nterms = 0 (terms may be NULL) removes the terms: rtoc_contact_eval_kkt then launches exactly what it launched before.
+ * The terms belong to the contact path: with terms set, rtoc_unconstr_eval_kkt (and what calls it) returns RTOC_ERR_BAD_ARG.
+ * The kernel takes the subtree of a joint as the joints after it in the table down to the next one no deeper, which holds
+ * because rtoc_set_robot_model only accepts depth-first ordered tables. */
+int rtoc_set_task_costs(rtoc_ctx* ctx, const rtoc_task_cost* terms, int nterms, int per_instance);
+/* GridInfo::t of every grid point of a fixed grid (t[nstages], shared by the batch): what the periodic references read.
+ * With switching-time optimisation (rtoc_sto_set_problem) the times come from the device instead: correctTimeSteps
+ * (time_discretization.cpp:186-222) per instance, prev_event_time + (j - prev_event_stage) dt, the event time on impact grids,
+ * t + T on the terminal one.  rtoc_get_grid_times: the times rtoc_contact_eval_kkt uses, host_out[count <= batch][nstages]. */
+/* rtoc_set_grid forgets the times of a fixed grid: set them again after it, or rtoc_contact_eval_kkt returns
+ * RTOC_ERR_NOT_READY while terms are set. */
+int rtoc_set_grid_times(rtoc_ctx* ctx, const double* t, int nstages);
+int rtoc_get_grid_times(rtoc_ctx* ctx, double* host_out, int count);
+
 /* ---- inequality rows of the contact path evaluated on the device (the Constraints object of examples/anymal/trot.cpp:
  * six joint-limit components + FrictionCone) ----
  * Joint limits: the rows of rtoc_set_constraint_rows with their bounds from rtoc_set_constraint_bounds.  Friction cones: the

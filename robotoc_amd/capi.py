@@ -36,6 +36,7 @@ EXPORTS = [
     "rtoc_sto_get_event_times", "rtoc_sto_get_time_steps", "rtoc_sto_get_constraint_data", "rtoc_sto_get_kkt_terms",
     "rtoc_sto_set_slack_dual", "rtoc_contact_eval_ocp", "rtoc_set_line_search", "rtoc_contact_line_search",
     "rtoc_bandwidth_probe", "rtoc_get_option",
+    "rtoc_set_task_costs", "rtoc_set_grid_times", "rtoc_get_grid_times",
 ]
 
 
@@ -172,6 +173,9 @@ def lib():
         L.rtoc_contact_line_search.argtypes = [vp, C.POINTER(C.c_int)]
         L.rtoc_error_string.argtypes = [C.c_int]
         L.rtoc_error_string.restype = C.c_char_p
+        L.rtoc_set_task_costs.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.rtoc_set_grid_times.argtypes = [vp, dp, C.c_int]
+        L.rtoc_get_grid_times.argtypes = [vp, dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -529,6 +533,31 @@ class Context:
 
     def contact_eval_kkt(self):
         _chk(lib().rtoc_contact_eval_kkt(self._h))
+
+    def set_task_costs(self, terms, per_instance=False):
+        """rtoc_set_task_costs: `terms` = a list of robotoc_amd.costs.TaskSpace3DCost / CoMCost (or TaskCost structs) shared by
+        the batch, with per_instance a list of `batch` such lists; None or [] removes the terms"""
+        from .costs import TaskCost
+        if not terms:
+            _chk(lib().rtoc_set_task_costs(self._h, None, 0, 0))
+            return
+        rows = [t for inst in terms for t in inst] if per_instance else list(terms)
+        n = len(rows) // self.batch if per_instance else len(rows)
+        if per_instance and any(len(inst) != n for inst in terms):
+            raise ValueError("every instance needs the same number of terms")
+        arr = (TaskCost * len(rows))(*[t if isinstance(t, TaskCost) else t.to_struct() for t in rows])
+        _chk(lib().rtoc_set_task_costs(self._h, C.cast(arr, C.c_void_p), n, 1 if per_instance else 0))
+
+    def set_grid_times(self, t):
+        """rtoc_set_grid_times: GridInfo::t of every grid point of a fixed grid"""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        _chk(lib().rtoc_set_grid_times(self._h, _dp(t), t.size))
+
+    def grid_times(self):
+        """rtoc_get_grid_times: [batch, nstages] grid times as rtoc_contact_eval_kkt uses them"""
+        out = np.zeros((self.batch, self.nstages))
+        _chk(lib().rtoc_get_grid_times(self._h, _dp(out), self.batch))
+        return out
 
     def contact_update_solution(self, fraction_to_boundary_rule=0.995, want_kkt_error=True):
         out = np.zeros(self.batch) if want_kkt_error else None

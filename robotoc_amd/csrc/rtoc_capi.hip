@@ -20,6 +20,7 @@
 #include "switching_constraint_lin.hpp"
 #include "contact_constraints.hpp"
 #include "contact_eval_kkt.hpp"
+#include "task_space_cost.hpp"
 #include "sto.hpp"
 
 using namespace rtoc;
@@ -247,6 +248,12 @@ struct rtoc_ctx {
   double* d_sto_cost;   // [2][batch][nev] STO cost gradient / Hessian diagonal handed over by the host, or nullptr
   double* d_sto_out;    // [2][batch][nev] + [batch]: lt, Qtt diagonal as scattered, squared STO KKT term
   double* d_costval;    // [batch][max_stages] cost values of the last rtoc_contact_eval_kkt (rtoc_contact_eval_ocp)
+  // task-space cost components (rtoc_set_task_costs; task_space_cost.hpp)
+  rtoc_task_cost* d_tasks;   // [ntasks] or [batch][ntasks]
+  int ntasks, tasks_per_instance;
+  double* d_gt;              // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
+  std::vector<double>* h_gt; // host copy of the same, its size = the grid it belongs to
+  double* d_gt_inst;         // [batch][max_stages] per-instance grid times written by sto_time_steps_kernel, or nullptr
   // filter line search on the device (rtoc_set_line_search, rtoc_contact_line_search)
   int ls_on;
   double ls_rate, ls_min_step, ls_cost_rate, ls_viol_rate;
@@ -504,6 +511,10 @@ int rtoc_destroy(rtoc_ctx* c) {
   if (c->d_sto_cost) (void)hipFree(c->d_sto_cost);
   if (c->d_sto_out) (void)hipFree(c->d_sto_out);
   if (c->d_costval) (void)hipFree(c->d_costval);
+  if (c->d_tasks) (void)hipFree(c->d_tasks);
+  if (c->d_gt) (void)hipFree(c->d_gt);
+  if (c->d_gt_inst) (void)hipFree(c->d_gt_inst);
+  delete c->h_gt;
   if (c->d_eval) (void)hipFree(c->d_eval);
   if (c->d_eval_part) (void)hipFree(c->d_eval_part);
   if (c->d_sol_trial) (void)hipFree(c->d_sol_trial);
@@ -609,6 +620,16 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
     dup((void**)&n->d_sto_cost, c->d_sto_cost, sizeof(double) * 2 * ne);
     dup((void**)&n->d_sto_out, c->d_sto_out, sizeof(double) * (2 * ne + c->batch));
   }
+  if (c->ntasks > 0) {
+    n->ntasks = c->ntasks, n->tasks_per_instance = c->tasks_per_instance;
+    dup((void**)&n->d_tasks, c->d_tasks, sizeof(rtoc_task_cost) * c->ntasks * (c->tasks_per_instance ? c->batch : 1));
+  }
+  dup((void**)&n->d_gt, c->d_gt, sizeof(double) * c->max_stages);
+  if (c->h_gt && !rc) {
+    n->h_gt = new (std::nothrow) std::vector<double>(*c->h_gt);
+    if (!n->h_gt) rc = RTOC_ERR_HIP;
+  }
+  if (c->d_gt_inst && c->sto_on) dup((void**)&n->d_gt_inst, c->d_gt_inst, sizeof(double) * c->batch * c->max_stages);
   for (int b = 0; !rc && e == hipSuccess && b < RTOC_NUM_BUFFERS; ++b) {
     if (!c->buf[b]) continue;
     if (!n->buf[b]) {
@@ -673,6 +694,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
       if (grid[i].type == RTOC_GRID_IMPACT || grid[i].type == RTOC_GRID_LIFT) ++nev;
     if (nev != c->sto_nev) c->sto_on = 0;   // rtoc_sto_set_problem again
   }
+  if (c->h_gt) c->h_gt->clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
   return RTOC_OK;
 }
 
@@ -848,6 +870,7 @@ static StoDevArgs sto_args(rtoc_ctx* c) {
   a.grid = c->d_grid;
   a.ts = c->d_ts;
   a.dt_inst = c->d_dt;
+  a.t_inst = c->d_gt_inst;
   a.con = c->d_sto_con;
   a.min_dwell = c->d_min_dwell;
   a.cost_lt = c->d_sto_cost;
@@ -2237,6 +2260,7 @@ int rtoc_unconstr_init_constraints(rtoc_ctx* c) {
 int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   CHECK_READY(c);
   if (!(dt > 0.0) || c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
+  if (c->ntasks > 0) return RTOC_ERR_BAD_ARG;   // task-space costs are evaluated on the contact path only
   if (!c->h_model || !c->d_cost || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
   int rc = ensure_buffer(c, RTOC_BUF_KKT);
@@ -2484,6 +2508,109 @@ static int launch_switching_constraint(rtoc_ctx* c) {
   return RTOC_OK;
 }
 
+// ---- TaskSpace3DCost / CoMCost (task_space_cost.hpp) ----
+static bool task_cost_valid(const rtoc_task_cost& t, int njoints) {
+  if (t.kind != RTOC_TASK_FRAME_3D && t.kind != RTOC_TASK_COM) return false;
+  if (t.ref_kind != RTOC_REF_CONST && t.ref_kind != RTOC_REF_PERIODIC_FOOT && t.ref_kind != RTOC_REF_PERIODIC_COM) return false;
+  if (t.kind == RTOC_TASK_FRAME_3D && (t.frame_parent < 0 || t.frame_parent >= njoints)) return false;
+  for (int k = 0; k < 3; ++k)   // set_weight / set_weight_terminal / set_weight_impact: elements must be non-negative
+    if (!(t.weight[k] >= 0.0) || !(t.weight_terminal[k] >= 0.0) || !(t.weight_impact[k] >= 0.0)) return false;
+  if (t.ref_kind != RTOC_REF_CONST && (!(t.period_active > 0.0) || !(t.period_inactive >= 0.0))) return false;
+  return true;
+}
+
+int rtoc_set_task_costs(rtoc_ctx* c, const rtoc_task_cost* terms, int nterms, int per_instance) {
+  if (!c || nterms < 0 || nterms > RTOC_MAX_TASK_COSTS || (nterms > 0 && !terms)) return RTOC_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  if (nterms == 0) {
+    if (c->ntasks > 0) c->epoch++;   // the kernel leaves the captured launch sequence
+    c->ntasks = 0;
+    return RTOC_OK;
+  }
+  if (!c->h_model) return RTOC_ERR_NOT_READY;
+  if (c->dims.nv > 64) return RTOC_ERR_UNSUPPORTED_DIMS;
+  const size_t n = (size_t)nterms * (per_instance ? c->batch : 1);
+  for (size_t i = 0; i < n; ++i)
+    if (!task_cost_valid(terms[i], c->h_model->m.njoints)) return RTOC_ERR_BAD_ARG;
+  const size_t cap = sizeof(rtoc_task_cost) * RTOC_MAX_TASK_COSTS * c->batch;
+  if (!c->d_tasks) HIP_TRY(hipMalloc((void**)&c->d_tasks, cap));
+  HIP_TRY(hipMemcpyAsync(c->d_tasks, terms, sizeof(rtoc_task_cost) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->ntasks = nterms, c->tasks_per_instance = per_instance ? 1 : 0;
+  c->epoch++;   // launch parameters baked into captured graphs
+  return RTOC_OK;
+}
+
+int rtoc_set_grid_times(rtoc_ctx* c, const double* t, int nstages) {
+  if (!c || !t || nstages < 2 || nstages > c->max_stages) return RTOC_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->d_gt) {
+    HIP_TRY(hipMalloc((void**)&c->d_gt, sizeof(double) * c->max_stages));
+    c->epoch++;
+  }
+  if (!c->h_gt) c->h_gt = new (std::nothrow) std::vector<double>();
+  if (!c->h_gt) return RTOC_ERR_HIP;
+  c->h_gt->assign(t, t + nstages);
+  HIP_TRY(hipMemcpyAsync(c->d_gt, t, sizeof(double) * nstages, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RTOC_OK;
+}
+
+// per-instance grid times of a switching-time problem: kept by sto_time_steps_kernel once this buffer exists
+static int ensure_grid_times_inst(rtoc_ctx* c) {
+  if (c->d_gt_inst) return RTOC_OK;
+  HIP_TRY(hipMalloc((void**)&c->d_gt_inst, sizeof(double) * c->batch * c->max_stages));
+  c->epoch++;   // sto_time_steps_kernel's arguments changed
+  return RTOC_OK;
+}
+
+int rtoc_get_grid_times(rtoc_ctx* c, double* host_out, int count) {
+  CHECK_READY(c);
+  if (!host_out || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
+  if (c->sto_on) {
+    int rc = ensure_grid_times_inst(c);
+    if (rc) return rc;
+    STO_LAUNCH(sto_time_steps_kernel, c);
+    HIP_TRY(hipMemcpyAsync(host_out, c->d_gt_inst, sizeof(double) * count * c->nstages, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTOC_OK;
+  }
+  if (!c->h_gt || (int)c->h_gt->size() != c->nstages) return RTOC_ERR_NOT_READY;
+  for (int b = 0; b < count; ++b) memcpy(host_out + (size_t)b * c->nstages, c->h_gt->data(), sizeof(double) * c->nstages);
+  return RTOC_OK;
+}
+
+static int launch_task_costs(rtoc_ctx* c) {
+  if (!c->h_model || !c->d_model || !c->d_tasks) return RTOC_ERR_NOT_READY;
+  if (!c->sto_on && (!c->h_gt || (int)c->h_gt->size() != c->nstages)) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
+  if (c->sto_on && !c->d_gt_inst) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
+  TaskCostArgs a;
+  a.sol = c->buf[RTOC_BUF_SOL];
+  a.kkt = c->buf[RTOC_BUF_KKT];
+  a.cost_out = c->d_costval;
+  a.grid = c->d_grid;
+  a.model = c->d_model;
+  a.terms = c->d_tasks;
+  a.t_fixed = c->sto_on ? nullptr : c->d_gt;
+  a.t_inst = c->sto_on ? c->d_gt_inst : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
+  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.o_q = c->L.sol.off[RTOC_SOL_Q];
+  a.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_hx = c->L.kkt.off[RTOC_KKT_HX];
+  a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
+  // the 16-byte row pairs of Qqq need an even record stride and column length and an even field offset
+  if ((a.kkt_stride | a.o_qxx) & 1) return RTOC_ERR_BAD_ARG;
+  const long long items = (long long)c->batch * c->nstages;
+  const size_t lds1 = sizeof(double) * task_cost_lds_doubles(c->h_model->m.njoints, c->ntasks, c->dims.nv);
+  if (c->dims.nv <= 32) {
+    hipLaunchKernelGGL(task_space_cost_kernel<2>, dim3((unsigned)((items + 1) / 2)), dim3(64), 2 * lds1, c->stream, a);
+  } else {
+    hipLaunchKernelGGL(task_space_cost_kernel<1>, dim3((unsigned)items), dim3(64), lds1, c->stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return RTOC_OK;
+}
+
 int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   CHECK_READY(c);
   if (!c->h_model || !c->d_active || !c->d_cost || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
@@ -2493,6 +2620,11 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   c->ls_unconstr_dt = 0.0;
+  // the periodic references of the task-space costs read the per-instance grid times that the time steps below then write
+  if (c->sto_on && c->ntasks > 0) {
+    rc = ensure_grid_times_inst(c);
+    if (rc) return rc;
+  }
   // PhaseBased discretisation: time_discretization_.correctTimeSteps(contact_sequence_, t) ahead of evalKKT (ocp_solver.cpp:115-117)
   if (c->sto_on) STO_LAUNCH(sto_time_steps_kernel, c);
   if (!c->d_costval) HIP_TRY(hipMalloc((void**)&c->d_costval, sizeof(double) * c->batch * c->max_stages));
@@ -2550,6 +2682,14 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   }
   hipLaunchKernelGGL(contact_cost_kernel, dim3((c->batch * c->nstages + COST_GP - 1) / COST_GP), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
+  // TaskSpace3DCost / CoMCost: added to what the configuration cost stored, ahead of the constraints and the dynamics
+  if (c->ntasks > 0) {
+    rc = launch_task_costs(c);
+    if (rc) {
+      c->vals_fresh = 0;
+      return rc;
+    }
+  }
   // constraints_->linearizeConstraints (intermediate_stage.cpp:109-110, impact_stage.cpp:95-96) of the rows evaluated here
   if (c->nrows > 0 && c->d_bounds && c->buf[RTOC_BUF_CON]) rc = launch_ubox(c, UBOX_LINEARIZE, true);
   if (!rc && device_cones_on(c) && c->buf[RTOC_BUF_CON]) rc = launch_contact_cones(c, CC_LINEARIZE);

@@ -35,6 +35,7 @@ struct StoDevArgs {
   const rtoc_grid* grid;
   double* ts;               // [batch][nev] event times
   double* dt_inst;          // [batch][nstages]
+  double* t_inst;           // [batch][nstages] grid times (GridInfo::t), or nullptr: not kept
   double* con;              // [batch][RTOC_STO_CON_STRIDE]
   const double* min_dwell;  // [nev + 1]
   const double* cost_lt;    // [batch][nev] or nullptr
@@ -59,13 +60,17 @@ __device__ __forceinline__ void sto_dwell_times(const StoDevArgs& a, const doubl
   dwell[a.nev] = a.t0 + a.T - prev;
 }
 
-// TimeDiscretization::correctTimeSteps (time_discretization.cpp:179-221), dt only (grid times are read by nothing on the device)
+// TimeDiscretization::correctTimeSteps (time_discretization.cpp:179-221): dt, and with a.t_inst (the periodic references of
+// task_space_cost.hpp read them) the grid times by the reference's formulas, prev_event_time + (j - prev_event_stage) * dt
 static __global__ void sto_time_steps_kernel(StoDevArgs a) {
+  // no fused multiply-adds: prev_event_time + (j - prev_event_stage) * dt rounded twice, as the reference's host code rounds it
+#pragma clang fp contract(off)
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.batch) return;
   const int N = a.nstages - 1;
   const double* ts = a.ts + (size_t)b * a.nev;
   double* dt = a.dt_inst + (size_t)b * a.nstages;
+  double* const tg = a.t_inst ? a.t_inst + (size_t)b * a.nstages : nullptr;
   int prev_stage = 0, e = 0;
   double prev_t = a.t0;
   for (int i = 0; i < N; ++i) {
@@ -74,6 +79,10 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
       const double te = e < a.nev ? ts[e] : prev_t;
       const double d = (te - prev_t) / (double)a.grid[i - 1].num_grids_in_phase;
       for (int j = prev_stage; j <= i - 1; ++j) dt[j] = d;
+      if (tg) {
+        for (int j = prev_stage; j <= i - 1; ++j) tg[j] = prev_t + (j - prev_stage) * d;
+        tg[i] = te;
+      }
       dt[i] = 0.0;
       prev_t = te;
       prev_stage = i + 1;
@@ -83,15 +92,20 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
       const double te = e < a.nev ? ts[e] : prev_t;
       const double d = (te - prev_t) / (double)a.grid[i].num_grids_in_phase;
       for (int j = prev_stage; j <= i; ++j) dt[j] = d;
+      if (tg)
+        for (int j = prev_stage; j <= i; ++j) tg[j] = prev_t + (j - prev_stage) * d;
       prev_t = te;
       prev_stage = i + 1;
       ++e;
     } else if (tn == RTOC_GRID_TERMINAL) {
       const double d = (a.t0 + a.T - prev_t) / (double)a.grid[i].num_grids_in_phase;
       for (int j = prev_stage; j <= i; ++j) dt[j] = d;
+      if (tg)
+        for (int j = prev_stage; j <= i; ++j) tg[j] = prev_t + (j - prev_stage) * d;
     }
   }
   dt[N] = 0.0;
+  if (tg) tg[N] = a.t0 + a.T;
 }
 
 // SwitchingTimeOptimization::initConstraints -> STOConstraints::setSlackAndDual (sto_constraints.cpp:148-172)

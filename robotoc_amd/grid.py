@@ -36,9 +36,10 @@ class ContactSequence:
         return [e for e in self.events if e.kind == "lift"]
 
 
-def discretize(N, T, t, cs: ContactSequence, phase_based=False) -> List[Grid]:
+def discretize(N, T, t, cs: ContactSequence, phase_based=False, times=False):
     """TimeDiscretization::discretize (time_discretization.cpp:43-181) followed, if
-    ``phase_based``, by correctTimeSteps (:184-262).  Returns num_grids+1 Grid structs."""
+    ``phase_based``, by correctTimeSteps (:184-262).  Returns num_grids+1 Grid structs, with ``times``
+    also GridInfo::t of every grid point (what the periodic references of robotoc_amd.costs read)."""
     impacts, lifts = cs.impacts(), cs.lifts()
     nmax = N + len(lifts) + 2 * len(impacts) + 2
     g = [dict(type=GRID_INTERMEDIATE, t=0.0, dt=0.0, phase=0, impact_index=-1, lift_index=-1,
@@ -180,6 +181,8 @@ def discretize(N, T, t, cs: ContactSequence, phase_based=False) -> List[Grid]:
         ts = -1 if gi["type"] == GRID_IMPACT else i
         out.append(Grid(gi["type"], int(gi["sto"]), int(gi["sto_next"]), int(gi["sc"]), dimf, dims,
                         gi["ngp"], ts, gi["dt"]))
+    if times:
+        return out, [g[i]["t"] for i in range(num + 1)]
     return out
 
 

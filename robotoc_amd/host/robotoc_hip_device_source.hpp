@@ -11,6 +11,7 @@
 
 #include "../../include/rtoc_robot.h"
 #include "robotoc_hip_solver.hpp"
+#include "robotoc_hip_task_costs.hpp"
 
 namespace robotoc {
 
@@ -24,6 +25,14 @@ class ConfigurationCostSource : public StageDataSource {
     if (active.size() != grid.size() || contact_positions.size() != grid.size() * static_cast<size_t>(model.ncontacts) * 3)
       throw std::invalid_argument("[ConfigurationCostSource] one contact mask and ncontacts positions per grid point");
   }
+  // The same with TaskSpace3DCost / CoMCost components beside the ConfigurationSpaceCost (the cost function's other
+  // components, evaluated on the device by rtoc_contact_eval_kkt); their periodic references read GridInfo::t of `grid`.
+  ConfigurationCostSource(const rtoc_robot_model& model, const rtoc_configuration_cost& cost,
+                          const std::vector<std::shared_ptr<TaskCostComponent>>& task_costs, const std::vector<GridInfo>& grid,
+                          const std::vector<unsigned>& active, const std::vector<double>& contact_positions, const Solution& s0)
+      : ConfigurationCostSource(model, cost, grid, active, contact_positions, s0) {
+    setTaskCosts(task_costs);
+  }
   // The same OCP described like the reference describes it: contact sequence + horizon (OCP::contact_sequence, T, N) instead of
   // a ready-made grid, optionally with STOConstraints (an OCP with an STO problem: PhaseBased discretisation, ocp_solver.cpp:46-48).
   // The source then owns the discretisation: OCPSolver::discretize(t) re-runs TimeDiscretization::discretize at the sequence's
@@ -35,6 +44,15 @@ class ConfigurationCostSource : public StageDataSource {
     if (N <= 0) throw std::out_of_range("[OCPSolver] invalid argument: ocp.N must be positive!");
     if (contact_sequence.numContacts() != model.ncontacts) throw std::invalid_argument("[ConfigurationCostSource] the contact sequence is for another robot");
     discretize(0.0);
+  }
+  // the task-space components of the cost (before the solver is constructed); empty: the configuration cost alone
+  void setTaskCosts(const std::vector<std::shared_ptr<TaskCostComponent>>& task_costs) {
+    if (task_costs.size() > static_cast<size_t>(RTOC_MAX_TASK_COSTS)) throw std::invalid_argument("[ConfigurationCostSource] at most RTOC_MAX_TASK_COSTS task-space costs");
+    tasks_.clear();
+    for (const auto& c : task_costs) {
+      if (!c) throw std::invalid_argument("[ConfigurationCostSource] null task-space cost");
+      tasks_.push_back(c->term());
+    }
   }
   ContactSequence* contactSequence() override { return cs_.get(); }
   const STOConstraints* stoConstraints() const override { return sto_.get(); }
@@ -95,6 +113,7 @@ class ConfigurationCostSource : public StageDataSource {
   void configure(rtoc_ctx* ctx) override {
     chk(rtoc_set_robot_model(ctx, &model_), "rtoc_set_robot_model");
     chk(rtoc_set_configuration_cost(ctx, &cost_), "rtoc_set_configuration_cost");
+    if (!tasks_.empty()) chk(rtoc_set_task_costs(ctx, tasks_.data(), static_cast<int>(tasks_.size()), 0), "rtoc_set_task_costs");
     if (!rows_.empty()) {
       chk(rtoc_set_constraint_rows(ctx, rows_.data(), static_cast<int>(rows_.size())), "rtoc_set_constraint_rows");
       chk(rtoc_set_constraint_bounds(ctx, bounds_.data(), static_cast<int>(bounds_.size()), barrier_, ftb_), "rtoc_set_constraint_bounds");
@@ -120,6 +139,11 @@ class ConfigurationCostSource : public StageDataSource {
   }
   void linearize(rtoc_ctx* ctx, const Solution&) override {
     schedule(ctx);
+    if (!tasks_.empty()) {   // GridInfo::t of the grid in force (rtoc_set_grid forgets them; with STO the device keeps its own)
+      std::vector<double> t(td_.size());
+      for (int i = 0; i < td_.size(); ++i) t[i] = td_[i].t;
+      chk(rtoc_set_grid_times(ctx, t.data(), td_.size()), "rtoc_set_grid_times");
+    }
     chk(rtoc_contact_eval_kkt(ctx), "rtoc_contact_eval_kkt");
   }
   // computed on the device with the linearisation (state_equation.cpp:99-109, Fqq_prev_inv correction included)
@@ -146,6 +170,7 @@ class ConfigurationCostSource : public StageDataSource {
   std::vector<double> cpos_;
   std::vector<double> crot_;   // [grid point][contact][9] or empty (surface contacts: ContactSequence rotations)
   Solution s0_;
+  std::vector<rtoc_task_cost> tasks_;
   std::vector<rtoc_box_row> rows_;
   std::vector<double> bounds_, mu_;
   bool impact_cone_ = false;

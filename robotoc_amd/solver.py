@@ -144,9 +144,10 @@ def interpolate_configuration(q1, q2, alpha, floating):
 class OCPSolver:
     def __init__(self, model, plan: ContactPlan, T, N, cost, joint_limits=None, friction_coefficients=None, barrier_param=1.0e-3,
                  fraction_to_boundary_rule=0.995, sto_constraints: Optional[STOConstraints] = None, options: Optional[SolverOptions] = None,
-                 batch=1, device=0, impact_cones=False):
+                 batch=1, device=0, impact_cones=False, task_costs=None):
         """cost: keyword arguments of capi.Context.set_configuration_cost; joint_limits: (q_min, q_max, v_max, u_max) over the
-        actuated joints or None; friction_coefficients: per contact or None."""
+        actuated joints or None; friction_coefficients: per contact or None; task_costs: robotoc_amd.costs.TaskSpace3DCost /
+        CoMCost components added to the configuration cost (a list shared by the batch) or None."""
         self.model, self.plan, self.T, self.N = model, plan, float(T), int(N)
         self.options = options or SolverOptions()
         self.sto = sto_constraints
@@ -164,6 +165,9 @@ class OCPSolver:
         c = self.ctx
         c.set_robot_model(model)
         c.set_configuration_cost(**cost)
+        self.task_costs = list(task_costs) if task_costs else None
+        if self.task_costs:
+            c.set_task_costs(self.task_costs)
         c.set_max_dts0(self.options.max_dts_riccati)
         c.set_backward_scan({"auto": "auto", "on": True, "off": False}[self.options.horizon_scan])
         self.tau = fraction_to_boundary_rule
@@ -199,7 +203,10 @@ class OCPSolver:
         of the mean event times; every instance gets its own time steps from its own event times (rtoc_sto_set_problem)."""
         self.t0 = float(t)
         cs = self._sequence(self.event_times.mean(axis=0))
-        grids = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None)
+        if self.task_costs:
+            grids, times = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None, times=True)
+        else:
+            grids = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None)
         nev = sum(1 for g in grids if g.type in (GRID_IMPACT, GRID_LIFT))
         if len(grids) > self.max_stages or nev != len(self.plan.events):
             raise RuntimeError("the discretisation has %d grid points with %d events, the context was sized for %d with %d (an event left the horizon?)"
@@ -207,6 +214,8 @@ class OCPSolver:
         self.grids = grids
         c = self.ctx
         c.set_grid(grids)
+        if self.task_costs:
+            c.set_grid_times(times)   # the periodic references' GridInfo::t (with STO the device keeps its own per instance)
         self.masks = contact_masks(grids, self.plan.phase_masks, self.plan.impact_masks())
         pos, phase = np.zeros((len(grids), self.nc, 3)), 0
         for i, g in enumerate(grids):
