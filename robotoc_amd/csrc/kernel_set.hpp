@@ -144,7 +144,7 @@ inline KernelSet make_set() {
   }
   constexpr int NWF = (2 * NV + NU + 63) / 64;
   if constexpr (NWF == 1)
-    k.fwd = riccati_forward_kernel<NV, NU, NS, 1>;
+    k.fwd = riccati_forward_kernel<NV, NU, NS>;
   else
     k.fwd = riccati_forward_mw_kernel<NV, NU, NS, NWF>;
   k.fwd_threads = 64 * NWF;

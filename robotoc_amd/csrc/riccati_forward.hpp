@@ -6,26 +6,17 @@
 // computeSwitchingTimeDirection, computeCostateDirection (x2),
 // computeLagrangeMultiplierDirection.
 //
-// The forward pass is a chain of mat-vecs (about 0.24 flop/byte): HBM-bound.  One
-// workgroup of NWF wavefronts per OCP instance; thread t < NX owns row t of Fxx and P,
-// threads NX..NX+NU-1 own a row of K.  For a fixed column j consecutive threads read
-// consecutive doubles of Fxx / P (coalesced); the per-instance chain dependency is only
-// through the NX-vector dx kept in LDS, many instances per CU hide the load latency.
+// The forward pass is a chain of mat-vecs (about 0.24 flop/byte): HBM-bound, and bound by the NUMBER and width of its
+// load instructions more than by its bytes.  riccati_forward_kernel (2 NV + NU <= 64): one wave per instance, lanes as
+// row pairs x column groups, every matrix read with 16-byte loads (864 B per instruction for ANYmal, 32 vector-memory
+// reads per grid point against the former row walk's ~87), partial sums reduced through LDS in a fixed order, Fxx of
+// the next grid point in flight across the serial tail of this one.  riccati_forward_mw_kernel (iCub): several waves,
+// thread t < NX owns row t of Fxx and P, threads NX..NX+NU-1 a row of K.
 #pragma once
 #include "device_utils.hpp"
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-#ifndef FWD_UNROLL
-#define FWD_UNROLL 18
-#endif
-#ifndef FWD_REST_PARTS
-#define FWD_REST_PARTS 2  // the remaining columns are walked in this many load batches
-#endif
-#ifndef FWD_HEAD
-#define FWD_HEAD 8  // columns of the next stage requested ahead of the tail of this one
-#endif
 
 struct FwdArgs {
   const double* kkt;
@@ -36,6 +27,27 @@ struct FwdArgs {
   int nstages;
   int batch;  // instances [first, batch) are processed by this launch
   int first;
+};
+
+#ifndef FWD_PREFETCH
+#define FWD_PREFETCH 12  // Fxx loads of grid point st + 1 requested ahead of the tail of st (all of them for ANYmal)
+#endif
+#ifndef FWD_WAVES_PER_SIMD
+// 2: a register budget of 256 VGPRs.  ANYmal takes 218 (no scratch), so eight waves per CU; the 7:7:x and 12:6:6 shapes
+// take 118-120 and still run sixteen.  Capped at 128, ANYmal spills 58-84 VGPRs whatever the prefetch depth (0, 6, 12).
+#define FWD_WAVES_PER_SIMD 2
+#endif
+
+template <int NV, int NU>
+struct FwdPairCfg {
+  static constexpr int NX = 2 * NV;
+  static constexpr int G = 64 / NV;               // column groups: lane l = c * NV + p, l < G * NV
+  static constexpr int TX = (NX + G - 1) / G;     // 16-B loads per NX x NX matrix (Fxx, P): column G t + c in load t
+  static constexpr int TXP = (TX + 1) & ~1;       // row of the permuted dx copy, a whole number of 16-B reads
+  static constexpr int TK = (NU + G - 1) / G;     // 16-B loads of K (row u = G t + c in load t)
+  static constexpr int NVP = (NV + 1) & ~1;       // row of the K partials
+  static constexpr int NF = NV * NU, NFP = (NF + 1) & ~1;
+  static constexpr int TF = (NFP + 127) / 128;    // 16-B loads of Fvu, a flat copy (an odd NF reads one double of padding)
 };
 
 // Hand-over of dx / du / dts between the threads of an instance goes through LDS only: one wavefront needs no barrier
@@ -49,23 +61,44 @@ __device__ __forceinline__ void fwd_sync() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int NV, int NU, int NS, int NWF>
-__global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a) {
-  constexpr int NX = 2 * NV, NT = 64 * NWF;
-  constexpr bool MFOLD = NS > 0 && NX + NU + NS <= NT;  // the rows of M have threads of their own
-  static_assert(NX + NU <= NT, "one thread per row of [Fxx;K]");
-  __shared__ double sDx[2][NX + 8];
+// One wave per instance (2 NV + NU <= 64).  Lane l = c * NV + p (l < G * NV, G = floor(64 / NV)) owns row pair p and
+// column group c: in load t it reads rows 2p, 2p+1 of column G t + c -- 16 contiguous, aligned bytes, since the leading
+// dimension NX = 2 NV is even and fields are 64-B aligned -- so ONE global_load_dwordx4 covers G whole columns (ANYmal:
+// 3 columns = 864 B on 54 lanes).  Fxx and P take ceil(NX / G) loads each, K (row-major = K^T column-major, the same
+// map with u = G t + c) ceil(NU / G), Fvu a flat copy of ceil(NV NU / 128) loads into LDS; ANYmal: 12 + 12 + 4 + 2 + 2
+// vector loads per grid point against the row walk's ~87.  The lane's operands dx[G t + c] are one ds_read_b128 per two
+// loads from a permuted copy of dx in LDS.  Partial sums go through LDS and are reduced in a fixed order (over c for
+// Fxx dx and P dx, over p for K dx), so results repeat bit for bit.  The Fxx loads of grid point st + 1 are issued
+// before the tail of st (K dx -> du -> Fvu du -> dx+): all instances reach that tail together, and without requests in
+// flight across it the memory system idles once per grid point.  Lanes past G * NV repeat group 0's addresses and drop
+// their sums; a column or K row past the matrix is clamped to a live one and its product is not accumulated.
+template <int NV, int NU, int NS>
+__global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel(FwdArgs a) {
+  using C = FwdPairCfg<NV, NU>;
+  constexpr int NX = C::NX, G = C::G, TX = C::TX, TXP = C::TXP, TK = C::TK, NVP = C::NVP, NF = C::NF, TF = C::TF;
+  constexpr int PF = FWD_PREFETCH < TX ? FWD_PREFETCH : TX;  // Fxx loads of grid point st + 1 issued ahead of the tail of st
+  static_assert(NX + NU <= 64, "one lane per row of [Fxx; K] in the reductions");
+  __shared__ __attribute__((aligned(16))) double sDx[2][NX + 8];   // dx in natural order
+  __shared__ __attribute__((aligned(16))) double sXp[2][G * TXP];  // dx permuted: [c][t] = dx[G t + c], 0 past NX
+  // partial sums; the last row of each takes the sums that are dropped, so that every lane writes (a branch around the
+  // writes lets the compiler sink the products, and with them every register the loads landed in, into it)
+  __shared__ __attribute__((aligned(16))) double sPa[G + 1][NX];    // Fxx dx, partial over column group c
+  __shared__ __attribute__((aligned(16))) double sPp[G + 1][NX];    // P dx, the same
+  __shared__ __attribute__((aligned(16))) double sPk[NU + 1][NVP];  // K dx, partial over row pair p
+  __shared__ __attribute__((aligned(16))) double sF[TF * 128];      // Fvu of the grid point, column-major
   __shared__ double sDu[NU + 8];
+  __shared__ double sDt[NX];  // dtsdx of an impact grid point with sto_next, requested ahead like the other riders
   __shared__ double sRed[8];
   extern __shared__ int sGridTab[];  // [nstages] (dynamic): type | sto << 4 | sto_next << 5 | switching_constraint << 6 | dims << 8
   const int tid = threadIdx.x;
   const int b = a.first + blockIdx.x;
   if (b >= a.batch) return;
-  for (int st = tid; st < a.nstages; st += NT) {
+  for (int st = tid; st < a.nstages; st += 64) {
     const rtoc_grid* gp = a.grid + st;
     sGridTab[st] = (gp->type & 15) | ((gp->sto != 0) << 4) | ((gp->sto_next != 0) << 5) |
                    ((gp->switching_constraint != 0) << 6) | (gp->dims << 8);
   }
+  for (int e = tid; e < 2 * G * TXP; e += 64) (&sXp[0][0])[e] = 0.0;
   const int N = a.nstages - 1;
   constexpr rtoc_layout SL = StaticLayout<NV, NU, NS>::make();
   constexpr rtoc_record_layout KL = SL.kkt, RL = SL.ric, DL = SL.dir;
@@ -73,9 +106,21 @@ __global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a)
   const double* rb = a.ric + (size_t)b * a.nstages * RL.stride;
   double* db = a.dir + (size_t)b * a.nstages * DL.stride;
 
-  if (tid < NX) {
+  // lane roles: (p, c) in the loads and partial sums; row tid < NX, row NX + u of K in the reductions and the outputs
+  const bool lg = tid < G * NV;
+  const int p = lg ? tid % NV : tid - G * NV;
+  const int c = lg ? tid / NV : 0;
+  const int cw = lg ? c : G;  // row of sPa / sPp this lane writes
+  const bool xrow = tid < NX;
+  const int r = xrow ? tid : NX - 1;
+  const bool kl = tid >= NX && tid < NX + NU;
+  const int u = kl ? tid - NX : 0;
+  const int pos = (r % G) * TXP + r / G;  // place of dx[r] in the permuted copy
+  __syncthreads();
+  if (xrow) {
     const double v = a.dx0 ? a.dx0[(size_t)b * NX + tid] : db[DL.off[RTOC_DIR_DX] + tid];
     sDx[0][tid] = v;
+    sXp[0][pos] = v;
     if (a.dx0) db[DL.off[RTOC_DIR_DX] + tid] = v;
   }
   __syncthreads();
@@ -94,51 +139,27 @@ __global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a)
       __syncthreads();
     }
   }
+  // offset of the lane's 16 bytes in load t of an NX x NX matrix (Fxx, P) and of K, and whether its product counts.  Only
+  // the last load of a matrix whose order G does not divide can run past it; it is clamped into the matrix, and the
+  // other addresses stay lane base + t x immediate.
+  const int lo = c * NX + 2 * p;
+  auto moff = [&](int t) { return (NX % G == 0 || t < TX - 1 || G * t + c < NX) ? lo + t * (G * NX) : (NX - 1) * NX + 2 * p; };
+  auto live = [&](int t) { return NX % G == 0 || t < TX - 1 || G * t + c < NX; };
+  auto koff = [&](int t) { return (NU % G == 0 || t < TK - 1 || G * t + c < NU) ? lo + t * (G * NX) : (NU - 1) * NX + 2 * p; };
+  auto klive = [&](int t) { return NU % G == 0 || t < TK - 1 || G * t + c < NU; };
+  // Fx[r] | k[u] and s[r]: one 8-B load each
+  auto vec_ptr = [&](int st) {
+    return xrow ? kb + (size_t)st * KL.stride + KL.off[RTOC_KKT_FX] + tid : rb + (size_t)st * RL.stride + RL.off[RTOC_RIC_KV] + u;
+  };
+  auto s_ptr = [&](int st) { return rb + (size_t)st * RL.stride + RL.off[RTOC_RIC_S] + r; };
+  d2 fa[TX];
+  double vec, sv;
+#pragma unroll
+  for (int t = 0; t < PF; ++t) fa[t] = *(const d2*)(kb + KL.off[RTOC_KKT_FXX] + moff(t));
+  vec = *vec_ptr(0);
+  sv = *s_ptr(0);
   int cur = 0;
   struct GridBits { int type, sto, sto_next, switching_constraint, dims; };
-  // ---- Row walks.  Every HBM read of a stage that does not depend on dx: the rows of Fxx / P (threads < NX), of K
-  //      (threads NX..NX+NU-1) and of M (the NS threads behind them, switching-constraint stages) share the SAME two load
-  //      instructions per column -- a divergent branch per role used to serialise them into ~13 dependent round trips per
-  //      stage --, Fx / k / m and s ride along.  Threads without a role read element 0 of a live field; nothing consumes
-  //      what they load.  The first FWD_HEAD columns (and the two vectors) of stage st + 1 are requested BEFORE the tail
-  //      of stage st (du -> LDS -> dx+ -> LDS, stores): all 4096 instances run in step, so without that the memory system
-  //      idles during the tail of every stage (tools/probes/read_bw_probe.hip: the walks alone stream at 5.6 TB/s). ----
-  struct StageRows {
-    const double *pa, *pp, *pv, *ps;
-    int sa;
-  };
-  auto stage_rows = [&](int st) {
-    const int gb = __builtin_amdgcn_readfirstlane(sGridTab[st]);
-    const bool imp = (gb & 15) == RTOC_GRID_IMPACT;
-    const bool xrow = tid < NX;
-    const bool krow = !imp && tid >= NX && tid < NX + NU;
-    const bool mrow = MFOLD && ((gb >> 6) & 1) && tid >= NX + NU && tid < NX + NU + (gb >> 8);
-    const int u = krow ? tid - NX : 0;
-    const int m = mrow ? tid - NX - NU : 0;
-    const int t = xrow ? tid : 0;
-    const double* kr = kb + (size_t)st * KL.stride;
-    const double* rr = rb + (size_t)st * RL.stride;
-    StageRows r;
-    r.pa = xrow ? kr + KL.off[RTOC_KKT_FXX] + tid
-                : (mrow ? rr + RL.off[RTOC_RIC_M] + m : rr + RL.off[RTOC_RIC_K] + (size_t)u * NX);
-    r.sa = xrow ? NX : (mrow ? NS : 1);
-    r.pp = rr + RL.off[RTOC_RIC_P] + t;
-    r.pv = xrow ? kr + KL.off[RTOC_KKT_FX] + tid : (mrow ? rr + RL.off[RTOC_RIC_MV] + m : rr + RL.off[RTOC_RIC_KV] + u);
-    r.ps = rr + RL.off[RTOC_RIC_S] + t;
-    return r;
-  };
-  constexpr int H = NX < FWD_HEAD ? NX : FWD_HEAD;
-  double ha[H], hp[H], vec, sv;
-  {
-    const StageRows r0 = stage_rows(0);
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-      ha[j] = r0.pa[j * r0.sa];
-      hp[j] = r0.pp[j * NX];
-    }
-    vec = *r0.pv;  // Fx[t] | k[u] | m[m]
-    sv = *r0.ps;
-  }
   for (int st = 0; st < N; ++st) {
     // grid descriptor from the LDS table: a global read here waits, on gfx9's single vector-memory counter, for the
     // acknowledgement of the previous stage's stores as well -- a write round trip per stage with nothing else in flight
@@ -150,7 +171,7 @@ __global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a)
     const double* rr = rb + (size_t)st * RL.stride;
     double* dr = db + (size_t)st * DL.stride;
     const double* dx = sDx[cur];
-    double* dxn = sDx[cur ^ 1];
+    const double* xp = sXp[cur];
 
     if (impact || lift) {
       dts = dtsn;  // d[i].dts = d[i-1].dts_next
@@ -158,114 +179,166 @@ __global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a)
       if (lift && sto_next) {
         if (tid == 0) {
           double acc = 0.0;
+          #pragma unroll 4
           for (int k = 0; k < NX; ++k) acc += rr[RL.off[RTOC_RIC_DTSDX] + k] * dx[k];
           acc += rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTS0];
           if (sto) acc += rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTSDTS] * dts;
           sRed[0] = acc;
         }
-        fwd_sync<NWF>();
+        fwd_sync<1>();
         dtsn = sRed[0];
-        fwd_sync<NWF>();
+        fwd_sync<1>();
       }
     }
 
-    const bool xrow = tid < NX;
-    const bool krow = !impact && tid >= NX && tid < NX + NU;
-    const bool mrow = MFOLD && g.switching_constraint && tid >= NX + NU && tid < NX + NU + g.dims;
-    const int u = krow ? tid - NX : 0;
-    const int m = mrow ? tid - NX - NU : 0;
-    const StageRows r = stage_rows(st);
-    double bv[NU];
-    double acc_a = 0.0, acc_p = 0.0;
+    // ---- the requests of this grid point not made ahead: the rest of Fxx, K, Fvu (read on impact grid points too, and
+    //      dropped), P ----
+    d2 fk[TK], ff[TF], fp[TX];
 #pragma unroll
-    for (int j = 0; j < H; ++j) {  // the head, in flight since the previous stage
-      const double x = dx[j];
-      acc_a += ha[j] * x;
-      acc_p += hp[j] * x;
-    }
-#pragma unroll((NX - H + FWD_REST_PARTS - 1) / FWD_REST_PARTS > 0 ? (NX - H + FWD_REST_PARTS - 1) / FWD_REST_PARTS : 1)
-    for (int j = H; j < NX; ++j) {
-      const double x = dx[j];
-      acc_a += r.pa[j * r.sa] * x;
-      acc_p += r.pp[j * NX] * x;
-    }
-    {  // the row of Fvu, needed by the tail: behind the last column, in front of the next head
-      const double* Bv = kr + KL.off[RTOC_KKT_FVU] + ((tid >= NV && tid < NX) ? tid - NV : 0);
+    for (int t = PF; t < TX; ++t) fa[t] = *(const d2*)(kr + KL.off[RTOC_KKT_FXX] + moff(t));
 #pragma unroll
-      for (int c = 0; c < NU; ++c) bv[c] = Bv[c * NV];
-    }
-    double vec_n, sv_n;
-    {
-      const StageRows rn = stage_rows(st + 1);  // st + 1 <= N: the terminal records exist, what is read there is dropped
+    for (int t = 0; t < TK; ++t) fk[t] = *(const d2*)(rr + RL.off[RTOC_RIC_K] + koff(t));
 #pragma unroll
-      for (int j = 0; j < H; ++j) {
-        ha[j] = rn.pa[j * rn.sa];
-        hp[j] = rn.pp[j * NX];
+    for (int i = 0; i < TF; ++i) {
+      const int e = 2 * (64 * i + tid);
+      ff[i] = *(const d2*)(kr + KL.off[RTOC_KKT_FVU] + (e < NF ? e : 0));
+    }
+    // the STO riders (T | Ffx, W | Psi, Phi) and the dtsdx of an impact grid point: requested here, AHEAD of the Fxx loads of
+    // st + 1, since gfx9 has one vector-memory counter: a load issued behind the prefetch waits for all of it
+    double rd1 = 0.0, rd2 = 0.0, rd3 = 0.0, rdt = 0.0, rs0 = 0.0, rss = 0.0;
+    if (sto) {
+      rd1 = xrow ? kr[KL.off[RTOC_KKT_FFX] + tid] : rr[RL.off[RTOC_RIC_T] + u];
+      rd2 = xrow ? rr[RL.off[RTOC_RIC_PSI] + tid] : rr[RL.off[RTOC_RIC_W] + u];
+      rd3 = rr[RL.off[RTOC_RIC_PHI] + r];
+    }
+    if (impact && sto_next) {
+      rdt = rr[RL.off[RTOC_RIC_DTSDX] + r];
+      rs0 = rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTS0];
+      rss = rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTSDTS];
+    }
+    d2 x[TXP / 2];
+#pragma unroll
+    for (int i = 0; i < TXP / 2; ++i) x[i] = *(const d2*)(xp + c * TXP + 2 * i);
+    const d2 xq = *(const d2*)(dx + 2 * p);
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < TX; ++t) {
+      const double xt = x[t / 2][t % 2];
+      if (live(t)) {
+        a0 += fa[t].x * xt;
+        a1 += fa[t].y * xt;
       }
-      vec_n = *rn.pv;
-      sv_n = *rn.ps;
     }
-    if (krow) {
-      double du = acc_a + vec;
+    // P is requested only once Fxx has been consumed: this bounds the registers the loads of a grid point hold at once
+    // (the scheduler otherwise hoists every load of the stage to its top)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < TX; ++t) fp[t] = *(const d2*)(rr + RL.off[RTOC_RIC_P] + moff(t));
+    double pk[TK];
+#pragma unroll
+    for (int t = 0; t < TK; ++t) pk[t] = fk[t].x * xq.x + fk[t].y * xq.y;
+#pragma unroll
+    for (int i = 0; i < TF; ++i) *(d2*)(sF + 2 * (64 * i + tid)) = ff[i];
+    double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < TX; ++t) {
+      const double xt = x[t / 2][t % 2];
+      if (live(t)) {
+        q0 += fp[t].x * xt;
+        q1 += fp[t].y * xt;
+      }
+    }
+    // ---- the Fxx loads and the two vectors of grid point st + 1, in flight across the tail of this one
+    //      (st + 1 <= N: the terminal records exist, what is read there is dropped) ----
+    double vec_n, sv_n;
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      const double* kn = kb + (size_t)(st + 1) * KL.stride;
+#pragma unroll
+      for (int t = 0; t < PF; ++t) fa[t] = *(const d2*)(kn + KL.off[RTOC_KKT_FXX] + moff(t));
+      vec_n = *vec_ptr(st + 1);
+      sv_n = *s_ptr(st + 1);
+    }
+    // ---- partial sums -> LDS -> row sums, in a fixed order ----
+    {
+      d2 va = {a0, a1}, vp = {q0, q1};
+      *(d2*)(&sPa[cw][2 * p]) = va;
+      *(d2*)(&sPp[cw][2 * p]) = vp;
+#pragma unroll
+      for (int t = 0; t < TK; ++t) sPk[lg && klive(t) ? G * t + c : NU][p] = pk[t];
+    }
+    fwd_sync<1>();
+    double acc_a = sPa[0][r], acc_p = sPp[0][r];
+#pragma unroll
+    for (int cc = 1; cc < G; ++cc) {
+      acc_a += sPa[cc][r];
+      acc_p += sPp[cc][r];
+    }
+    double kd = 0.0;
+#pragma unroll 3
+    for (int i = 0; i < NVP / 2; ++i) {
+      const d2 w = *(const d2*)(&sPk[u][2 * i]);
+      kd += w.x;
+      if (2 * i + 1 < NV) kd += w.y;
+    }
+    if (kl && !impact) {
+      double du = kd + vec;
       if (sto) {
-        du += rr[RL.off[RTOC_RIC_T] + u] * (dtsn - dts);
-        if (sto_next) du -= rr[RL.off[RTOC_RIC_W] + u] * dtsn;
+        du += rd1 * (dtsn - dts);
+        if (sto_next) du -= rd2 * dtsn;
       }
       sDu[u] = du;
       dr[DL.off[RTOC_DIR_DU] + u] = du;
     }
-    fwd_sync<NWF>();
+    fwd_sync<1>();
+    double* dxn = sDx[cur ^ 1];
     if (xrow) {
       double v = vec + acc_a;
       if (!impact) {
         if (tid >= NV) {
-#pragma unroll
-          for (int c = 0; c < NU; ++c) v += bv[c] * sDu[c];
+#pragma unroll 4
+          for (int cc = 0; cc < NU; ++cc) v += sF[cc * NV + tid - NV] * sDu[cc];
         }
-        if (sto) v += kr[KL.off[RTOC_KKT_FFX] + tid] * (dtsn - dts);
+        if (sto) v += rd1 * (dtsn - dts);
       }
       dxn[tid] = v;
+      if (impact && sto_next) sDt[tid] = rdt;
+      sXp[cur ^ 1][pos] = v;
       (dr + DL.stride)[DL.off[RTOC_DIR_DX] + tid] = v;
     }
     if (impact && sto_next) {
       // riccati_recursion.cpp:101-107: dts_next of d[i+1] from sto_policy_[i] and dx[i+1]
-      fwd_sync<NWF>();
+      fwd_sync<1>();
       if (tid == 0) {
         double acc = 0.0;
-        for (int k = 0; k < NX; ++k) acc += rr[RL.off[RTOC_RIC_DTSDX] + k] * dxn[k];
-        acc += rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTS0];
-        if (sto) acc += rr[RL.off[RTOC_RIC_SCAL] + RTOC_RIC_SCAL_DTSDTS] * dts;
+        #pragma unroll 4
+        for (int k = 0; k < NX; ++k) acc += sDt[k] * dxn[k];
+        acc += rs0;
+        if (sto) acc += rss * dts;
         sRed[0] = acc;
       }
-      fwd_sync<NWF>();
+      fwd_sync<1>();
       dtsn = sRed[0];
     }
     // ---- costate (riccati_factorizer.cpp:243-262) ----
-    if (tid < NX) {
+    if (xrow) {
       double lam = acc_p - sv;
       if (sto) {
         if (impact) {
-          lam -= rr[RL.off[RTOC_RIC_PHI] + tid] * dtsn;
+          lam -= rd3 * dtsn;
         } else {
-          lam += rr[RL.off[RTOC_RIC_PSI] + tid] * (dtsn - dts);
-          if (sto_next) lam -= rr[RL.off[RTOC_RIC_PHI] + tid] * dtsn;
+          lam += rd2 * (dtsn - dts);
+          if (sto_next) lam -= rd3 * dtsn;
         }
       }
       dr[DL.off[RTOC_DIR_DLMDGMM] + tid] = lam;
     }
-    // ---- switching-constraint multiplier (:265-277) ----
-    if constexpr (MFOLD) {
-      if (mrow) {
-        double acc = acc_a + vec;
-        if (sto) {
-          acc += rr[RL.off[RTOC_RIC_MT] + m] * (dtsn - dts);
-          if (sto_next) acc -= rr[RL.off[RTOC_RIC_MTN] + m] * dtsn;
-        }
-        dr[DL.off[RTOC_DIR_DXI] + m] = acc;
-      }
-    } else if (NS > 0 && g.switching_constraint && tid < g.dims) {
+    // ---- switching-constraint multiplier (:265-277): two grid points of a trot, a plain row walk (its loads, like those of
+    //      the dtsdx walk of a lift grid point with sto_next, wait for the prefetch: rare grid points) ----
+    if (NS > 0 && g.switching_constraint && tid < g.dims) {
       const double* M = rr + RL.off[RTOC_RIC_M] + tid;
       double acc = 0.0;
+      #pragma unroll 4
       for (int j = 0; j < NX; ++j) acc += M[j * NS] * dx[j];
       acc += rr[RL.off[RTOC_RIC_MV] + tid];
       if (sto) {
@@ -278,23 +351,39 @@ __global__ __launch_bounds__(64 * NWF, 4) void riccati_forward_kernel(FwdArgs a)
       dr[DL.off[RTOC_DIR_DTS] + 0] = dts;
       dr[DL.off[RTOC_DIR_DTS] + 1] = dtsn;
     }
-    fwd_sync<NWF>();
+    fwd_sync<1>();
     cur ^= 1;
     vec = vec_n;
     sv = sv_n;
   }
-  // terminal costate (riccati_recursion.cpp:128-130)
+  // terminal costate (riccati_recursion.cpp:128-130): P dx - s with the same map (the Fxx / Fx requested ahead are dropped)
   {
     const double* rr = rb + (size_t)N * RL.stride;
     double* dr = db + (size_t)N * DL.stride;
-    const double* dx = sDx[cur];
-    if (tid < NX) {
-      const double* P = rr + RL.off[RTOC_RIC_P] + tid;
-      double acc = 0.0;
-#pragma unroll FWD_UNROLL
-      for (int j = 0; j < NX; ++j) acc += P[j * NX] * dx[j];
-      dr[DL.off[RTOC_DIR_DLMDGMM] + tid] = acc - rr[RL.off[RTOC_RIC_S] + tid];
+    const double* xp = sXp[cur];
+    d2 fp[TX], x[TXP / 2];
+#pragma unroll
+    for (int t = 0; t < TX; ++t) fp[t] = *(const d2*)(rr + RL.off[RTOC_RIC_P] + moff(t));
+#pragma unroll
+    for (int i = 0; i < TXP / 2; ++i) x[i] = *(const d2*)(xp + c * TXP + 2 * i);
+    double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < TX; ++t) {
+      const double xt = x[t / 2][t % 2];
+      if (live(t)) {
+        q0 += fp[t].x * xt;
+        q1 += fp[t].y * xt;
+      }
     }
+    {
+      d2 vp = {q0, q1};
+      *(d2*)(&sPp[cw][2 * p]) = vp;
+    }
+    fwd_sync<1>();
+    double acc_p = sPp[0][r];
+#pragma unroll
+    for (int cc = 1; cc < G; ++cc) acc_p += sPp[cc][r];
+    if (xrow) dr[DL.off[RTOC_DIR_DLMDGMM] + tid] = acc_p - sv;
     if (tid == 0) {
       dr[DL.off[RTOC_DIR_DTS] + 0] = dts;
       dr[DL.off[RTOC_DIR_DTS] + 1] = dtsn;
@@ -377,7 +466,7 @@ __global__ __launch_bounds__(64 * NWF) void riccati_forward_mw_kernel(FwdArgs a)
     if (tid < NX) {
       const double* A = kr + KL.off[RTOC_KKT_FXX] + tid;
       const double* P = rr + RL.off[RTOC_RIC_P] + tid;
-#pragma unroll FWD_UNROLL
+#pragma unroll 18
       for (int j = 0; j < NX; ++j) {
         const double x = dx[j];
         acc_a += A[j * NX] * x;
