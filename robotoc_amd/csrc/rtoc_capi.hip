@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -13,6 +14,7 @@
 
 #include "../../include/rtoc.h"
 #include "../../include/rtoc_robot.h"
+#include "device_buffer.hpp"
 #include "kernel_set.hpp"
 #include "rigid_body.hpp"
 #include "unconstr_constraints.hpp"
@@ -149,125 +151,147 @@ static hipError_t set_linearize_lds(const rtoc_robot_model& m, int nlevels, int 
 // the backward recursion of one public call, as plan_backward decides it
 enum BwdPath { BWD_SCAN, BWD_RV, BWD_RW, BWD_TILE };
 struct BwdPlan {
-  BwdPath path;   // horizon scan, register-resident, register-wide (iCub-size shapes), tile-split / role-split
-  bwd_fn kern;    // the kernel of the path (scan: its policy kernel; register-wide: the one between the one-stage launches)
-  int check_fxx;  // BwdArgs::check_fxx of the register-resident kernel: verify the structured rows as it goes
+  BwdPath path = BWD_SCAN;  // horizon scan, register-resident, register-wide (iCub-size shapes), tile-split / role-split
+  bwd_fn kern = nullptr;    // the kernel of the path (scan: its policy kernel; register-wide: the one between the one-stage launches)
+  int check_fxx = 0;        // BwdArgs::check_fxx of the register-resident kernel: verify the structured rows as it goes
 };
-struct rtoc_ctx {
-  rtoc_dims dims;
-  rtoc_layout L;
-  const KernelSet* ks;
-  int max_stages, nstages, batch, device;
-  hipStream_t own_stream, stream;
-  double* buf[RTOC_NUM_BUFFERS];
-  size_t count[RTOC_NUM_BUFFERS];
-  bool owned[RTOC_NUM_BUFFERS];
-  bool kkt_exposed;    // rtoc_device_ptr(RTOC_BUF_KKT) was handed out: the caller can rewrite the records without the runtime seeing it
-  rtoc_grid* d_grid;
-  rtoc_box_row* d_rows;
-  rtoc_box_row* h_rows;  // host copies (stage dump)
-  rtoc_grid* h_grid;
-  int* d_nconv;  // instances found converged by the last rtoc_newton_iteration
-  int* d_pair;   // first two rows of every primal entry, packed (int4 per entry)
-  int* d_entry;  // CSR over the primal entries (q_0..,v_0..,u_0..): [ne+1] offsets, then [nrows] row ids
-  int nrows;
-  uint32_t* d_status;
-  long long* d_prof;
-  int writeback;
-  double max_dts0;
-  double contact_inv_damping;
-  int bwd_variant;
-  hipEvent_t ev0, ev1;
-  hipStream_t stream2;  // forward half of the pipelined sweep
-  hipEvent_t ev_fork, ev_join, ev_chunk[RTOC_MAX_CHUNK_EVENTS];
-  int sweep_chunks;
-  int condense_split;  // 1: MJtJinv in its own kernel ahead of the condensation
-  int keep_qaf;        // RTOC_OPT_CONDENSE_KEEP_QAF
-  int fxx_mode;        // RTOC_OPT_FXX_STRUCTURE: 0 auto, 1 dense, 2 caller asserts the structure
-  int bwd_register;    // RTOC_OPT_BACKWARD_REGISTER: the register-resident backward kernel where it applies
-  int num_cus;         // compute units of the device (the register-wide iCub kernel runs where the batch fills them)
-  int cond_register;   // RTOC_OPT_CONDENSE_REGISTER: the register-chained condensation of the contact grid points where it applies
-  int* d_stage_list;   // [max_stages] grid points 0 .. nstages - 2: the contact ones first (n_stage_contact), then the impact ones
-  int n_stage_contact, n_stage_impact;
-  int fxx_state;       // auto mode cache: 0 unknown (re-check before the next backward recursion), 1 every Fxx structured, 2 not
-  BwdPlan bwd_plan;    // the last plan_backward's answer: the backward kernel baked into captured graphs
-  unsigned long long graph_replays;  // hipGraphLaunch count of RTOC_OPT_GRAPH (rtoc_graph_replay_count)
-  int* d_fxx_flag;
-  double* d_sto;       // rtoc_sto_eval_kkt staging: lt, diag(Qtt), squared error
-  // RTOC_OPT_GRAPH: launch sequences replayed from captured hipGraphs
-  int use_graph;
-  int exact_transport;  // RTOC_OPT_SWITCHING_TRANSPORT
-  int unconstr_dense;   // RTOC_OPT_UNCONSTR_DENSE
-  int exact_cone_jacobian;  // RTOC_OPT_CONE_JACOBIAN
-  int impact_cones;     // RTOC_OPT_IMPACT_CONES (default 1, rtoc_create)
-  double* d_mu;         // rtoc_set_friction_coefficients
-  int n_mu;             // how many of its RTOC_MAX_CONTACTS entries the caller set
-  double* d_wcone;      // rtoc_set_wrench_cone_params: [RTOC_MAX_CONTACTS][17 x 6]
-  double *d_vals, *d_vals2;  // rbd_values_kernel -> linearize_contact_dynamics_kernel<.., PRE>: [batch * max_stages][njoints][64]
-  size_t vals_cap;
-  int vals_fresh;       // the values in d_vals belong to the iterate in RTOC_BUF_SOL (consumed by the next launch_linearize)
-  int linearize_fused;  // RTOC_OPT_LINEARIZE_FUSED
-  int lin_dpp;          // RTOC_OPT_LINEARIZE_DOFS_PER_PASS (0 = per model)
-  unsigned long long epoch;  // bumped by everything that changes a launch parameter baked into a captured graph
-  struct GraphSlot {
-    hipGraphExec_t exec;
-    unsigned long long epoch, warm_epoch;
-    double p0, p1;
-    bool warm;
-  } g_sweep, g_newton;
-  size_t sto_cap;
-  int cone_contacts, cone_dim;  // friction / wrench cones: max contacts (0 = off), force components per contact
-  int cone_rows;                // PDIPM rows per contact: 5 friction cone, 17 contact wrench cone
-  double* d_kkterr;             // [batch]
-  int backward_scan;            // RTOC_OPT_BACKWARD_SCAN
-  double* d_scan[3];            // element ping-pong buffers, value records (allocated on first use)
-  double* d_scan_sto;           // riccati_scan_sto.hpp: per grid point At, P+ Fx, P+ fx, factors of G
-  // rigid-body model (rtoc_set_robot_model) and contact schedule (rtoc_set_contact_schedule)
-  rbd::DevModel* d_model;
-  rbd::DevModel* h_model;
-  unsigned* d_active;
-  double* d_cpos;
-  double* d_crot;
-  bool has_cpos, has_crot;
-  // rtoc_line_search_filter: filters [batch][CAP][2], sizes [batch], staging (cost, violation | mask, accepted)
-  double* d_cost;      // rtoc_set_configuration_cost: 9 nv doubles
-  double* d_bounds;    // rtoc_set_constraint_bounds: [nrows]
-  double barrier, ftb_rule;
-  double* d_x0;        // rtoc_set_initial_state: [batch][2 nv]
-  double* d_filter;
-  int* d_nfilter;
-  double* d_ls_in;
-  int* d_ls_flags;
-  // switching-time optimisation on the device (rtoc_sto_set_problem; sto.hpp)
-  int sto_on, sto_nev;
-  double sto_t0, sto_T, sto_barrier, sto_tau, sto_reg;
-  double* d_ts;         // [batch][nev] event times of every instance
-  double* d_dt;         // [batch][max_stages] time steps of every instance (grid_dt)
-  double* d_sto_con;    // [batch][RTOC_STO_CON_STRIDE] dwell-time rows
-  double* d_min_dwell;  // [RTOC_STO_MAX_EVENTS + 1]
-  double* d_sto_cost;   // [2][batch][nev] STO cost gradient / Hessian diagonal handed over by the host, or nullptr
-  double* d_sto_out;    // [2][batch][nev] + [batch]: lt, Qtt diagonal as scattered, squared STO KKT term
-  double* d_costval;    // [batch][max_stages] cost values of the last rtoc_contact_eval_kkt (rtoc_contact_eval_ocp)
-  // task-space cost components (rtoc_set_task_costs; task_space_cost.hpp)
-  rtoc_task_cost* d_tasks;   // [ntasks] or [batch][ntasks]
-  int ntasks, tasks_per_instance;
-  double* d_gt;              // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
-  std::vector<double>* h_gt; // host copy of the same, its size = the grid it belongs to
-  double* d_gt_inst;         // [batch][max_stages] per-instance grid times written by sto_time_steps_kernel, or nullptr
+// Streams and events of a context.  A base of rtoc_ctx, so that it is destroyed after every member: device memory is freed
+// first, streams and events go last.
+struct CtxStreams {
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream2 = nullptr;  // forward half of the pipelined sweep
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_chunk[RTOC_MAX_CHUNK_EVENTS] = {};
+  CtxStreams() = default;
+  CtxStreams(const CtxStreams&) = delete;
+  CtxStreams& operator=(const CtxStreams&) = delete;
+  ~CtxStreams() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    if (stream2) (void)hipStreamDestroy(stream2);
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    for (hipEvent_t e : ev_chunk)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+// The scalar settings rtoc_clone hands to the new context in one assignment (a base of rtoc_ctx: c->writeback etc.)
+struct CtxOptions {
+  int writeback = 0;
+  double max_dts0 = 0.1;  // RiccatiRecursion(ocp, max_dts0 = 0.1), riccati_recursion.hpp:35
+  double contact_inv_damping = 0.0;
+  int bwd_variant = 0;
+  int sweep_chunks = 1;         // measured on MI355X: chunked pipelining does not pay (forward waves do not fit next to the backward waves)
+  int condense_split = 0;       // 1: MJtJinv in its own kernel ahead of the condensation
+  int keep_qaf = 0;             // RTOC_OPT_CONDENSE_KEEP_QAF
+  int fxx_mode = 0;             // RTOC_OPT_FXX_STRUCTURE: 0 auto, 1 dense, 2 caller asserts the structure
+  int bwd_register = 1;         // RTOC_OPT_BACKWARD_REGISTER: the register-resident backward kernel where it applies (plan_backward)
+  int cond_register = 1;        // RTOC_OPT_CONDENSE_REGISTER: the register-chained condensation of the contact grid points where it applies
+  int use_graph = 0;            // RTOC_OPT_GRAPH: launch sequences replayed from captured hipGraphs
+  int exact_transport = 0;      // RTOC_OPT_SWITCHING_TRANSPORT
+  int unconstr_dense = 0;       // RTOC_OPT_UNCONSTR_DENSE
+  int exact_cone_jacobian = 0;  // RTOC_OPT_CONE_JACOBIAN
+  int impact_cones = 1;         // RTOC_OPT_IMPACT_CONES
+  int linearize_fused = 0;      // RTOC_OPT_LINEARIZE_FUSED
+  int lin_dpp = 0;              // RTOC_OPT_LINEARIZE_DOFS_PER_PASS (0 = per model)
+  double barrier = 0.0, ftb_rule = 0.0;
+  int n_mu = 0;                 // how many of d_mu's RTOC_MAX_CONTACTS entries the caller set
+  bool has_cpos = false, has_crot = false;
   // filter line search on the device (rtoc_set_line_search, rtoc_contact_line_search)
-  int ls_on;
-  double ls_rate, ls_min_step, ls_cost_rate, ls_viol_rate;
-  int ls_method;        // 0 LineSearchMethod::Filter, 1 MeritBacktracking (rtoc_set_line_search_method)
-  double ls_armijo, ls_margin, ls_eps;
-  double* d_ls_merit;   // [batch] penalty parameter + [batch] directional derivative
-  double ls_unconstr_dt;   // > 0: the last evalKKT was rtoc_unconstr_eval_kkt(dt) -- trial iterates of the line search are evaluated by it
-  double* d_eval;       // [2][2][batch]: (cost + barrier | violation) of the current iterate, of the trial iterate
-  double* d_eval_part;  // [batch][max_stages][2]
-  double* d_sol_trial;  // trial iterate: SplitSolution records, constraint records, steps
-  double* d_con_trial;
-  double* d_ls_steps;   // [batch][2] trial steps + [batch] alpha
-  int* d_ls_active;     // [batch] active flags + [1] counter
-  int ls_trials;        // trial evaluations of the last line search
+  int ls_on = 0;
+  double ls_rate = 0.0, ls_min_step = 0.0, ls_cost_rate = 0.0, ls_viol_rate = 0.0;
+  int ls_method = 0;  // 0 LineSearchMethod::Filter, 1 MeritBacktracking (rtoc_set_line_search_method)
+  double ls_armijo = 0.0, ls_margin = 0.0, ls_eps = 0.0;
+};
+struct GraphSlot {
+  hipGraphExec_t exec = nullptr;
+  unsigned long long epoch = 0, warm_epoch = 0;
+  double p0 = 0.0, p1 = 0.0;
+  bool warm = false;
+  ~GraphSlot() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+  }
+};
+struct rtoc_ctx : CtxStreams, CtxOptions {
+  rtoc_dims dims = {};
+  rtoc_layout L = {};
+  const KernelSet* ks = nullptr;
+  int max_stages = 0, nstages = 0, batch = 0, device = 0;
+  hipStream_t stream = nullptr;  // own_stream, or the caller's (rtoc_set_stream)
+  DevBuf<double> buf[RTOC_NUM_BUFFERS];
+  size_t want[RTOC_NUM_BUFFERS] = {};  // doubles of a buffer at max_stages (rtoc_buffer_count), allocated or not
+  bool kkt_exposed = false;  // rtoc_device_ptr(RTOC_BUF_KKT) was handed out: the caller can rewrite the records without the runtime seeing it
+  DevBuf<rtoc_grid> d_grid;
+  DevBuf<rtoc_box_row> d_rows;
+  std::vector<rtoc_box_row> h_rows;  // host copies (stage dump, rtoc_clone)
+  std::vector<rtoc_grid> h_grid;
+  DevBuf<int> d_nconv;  // instances found converged by the last rtoc_newton_iteration
+  DevBuf<int> d_pair;   // first two rows of every primal entry, packed (int4 per entry)
+  DevBuf<int> d_entry;  // CSR over the primal entries (q_0..,v_0..,u_0..): [ne+1] offsets, then [nrows] row ids
+  int nrows = 0;
+  DevBuf<uint32_t> d_status;
+  DevBuf<long long> d_prof;
+  int num_cus = 0;               // compute units of the device (the register-wide iCub kernel runs where the batch fills them)
+  DevBuf<int> d_stage_list;      // [max_stages] grid points 0 .. nstages - 2: the contact ones first (n_stage_contact), then the impact ones
+  int n_stage_contact = 0, n_stage_impact = 0;
+  int fxx_state = 0;             // auto mode cache: 0 unknown (re-check before the next backward recursion), 1 every Fxx structured, 2 not
+  BwdPlan bwd_plan;              // the last plan_backward's answer: the backward kernel baked into captured graphs
+  unsigned long long graph_replays = 0;  // hipGraphLaunch count of RTOC_OPT_GRAPH (rtoc_graph_replay_count)
+  DevBuf<int> d_fxx_flag;
+  DevBuf<double> d_sto;          // rtoc_sto_eval_kkt staging: lt, diag(Qtt), squared error
+  DevBuf<double> d_mu;           // rtoc_set_friction_coefficients
+  DevBuf<double> d_wcone;        // rtoc_set_wrench_cone_params: [RTOC_MAX_CONTACTS][17 x 6]
+  DevBuf<double> d_vals, d_vals2;  // rbd_values_kernel -> linearize_contact_dynamics_kernel<.., PRE>: [batch * max_stages][njoints][64]
+  int vals_fresh = 0;            // the values in d_vals belong to the iterate in RTOC_BUF_SOL (consumed by the next launch_linearize)
+  unsigned long long epoch = 0;  // bumped by everything that changes a launch parameter baked into a captured graph
+  int cone_contacts = 0, cone_dim = 0;  // friction / wrench cones: max contacts (0 = off), force components per contact
+  int cone_rows = 0;                    // PDIPM rows per contact: 5 friction cone, 17 contact wrench cone
+  DevBuf<double> d_kkterr;              // [batch] + [batch][max_stages] partial sums
+  int backward_scan = 0;                // RTOC_OPT_BACKWARD_SCAN
+  DevBuf<double> d_scan[3];             // element ping-pong buffers, value records (allocated on first use)
+  DevBuf<double> d_scan_sto;            // riccati_scan_sto.hpp: per grid point At, P+ Fx, P+ fx, factors of G
+  // rigid-body model (rtoc_set_robot_model) and contact schedule (rtoc_set_contact_schedule)
+  DevBuf<rbd::DevModel> d_model;
+  std::unique_ptr<rbd::DevModel> h_model;
+  DevBuf<unsigned> d_active;
+  DevBuf<double> d_cpos;
+  DevBuf<double> d_crot;
+  // rtoc_line_search_filter: filters [batch][CAP][2], sizes [batch], staging (cost, violation | mask, accepted)
+  DevBuf<double> d_cost;      // rtoc_set_configuration_cost: 12 (nv + 1) doubles
+  DevBuf<double> d_bounds;    // rtoc_set_constraint_bounds: [nc_max]
+  DevBuf<double> d_x0;        // rtoc_set_initial_state: [batch][nq + nv]
+  DevBuf<double> d_filter;
+  DevBuf<int> d_nfilter;
+  DevBuf<double> d_ls_in;
+  DevBuf<int> d_ls_flags;
+  // switching-time optimisation on the device (rtoc_sto_set_problem; sto.hpp)
+  int sto_on = 0, sto_nev = 0;
+  double sto_t0 = 0.0, sto_T = 0.0, sto_barrier = 0.0, sto_tau = 0.0, sto_reg = 0.0;
+  DevBuf<double> d_ts;         // [batch][nev] event times of every instance
+  DevBuf<double> d_dt;         // [batch][max_stages] time steps of every instance (grid_dt)
+  DevBuf<double> d_sto_con;    // [batch][RTOC_STO_CON_STRIDE] dwell-time rows
+  DevBuf<double> d_min_dwell;  // [RTOC_STO_MAX_EVENTS + 1]
+  DevBuf<double> d_sto_cost;   // [2][batch][nev] STO cost gradient / Hessian diagonal handed over by the host, or unallocated
+  DevBuf<double> d_sto_out;    // [2][batch][nev] + [batch]: lt, Qtt diagonal as scattered, squared STO KKT term
+  DevBuf<double> d_costval;    // [batch][max_stages] cost values of the last rtoc_contact_eval_kkt (rtoc_contact_eval_ocp)
+  // task-space cost components (rtoc_set_task_costs; task_space_cost.hpp)
+  DevBuf<rtoc_task_cost> d_tasks;  // capacity [batch][RTOC_MAX_TASK_COSTS]; in use [ntasks] or [batch][ntasks]
+  int ntasks = 0, tasks_per_instance = 0;
+  DevBuf<double> d_gt;             // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
+  std::vector<double> h_gt;        // host copy of the same, its size = the grid it belongs to (empty: none)
+  DevBuf<double> d_gt_inst;        // [batch][max_stages] per-instance grid times written by sto_time_steps_kernel, or unallocated
+  DevBuf<double> d_ls_merit;   // [batch] penalty parameter + [batch] directional derivative
+  double ls_unconstr_dt = 0.0; // > 0: the last evalKKT was rtoc_unconstr_eval_kkt(dt) -- trial iterates of the line search are evaluated by it
+  DevBuf<double> d_eval;       // [2][2][batch]: (cost + barrier | violation) of the current iterate, of the trial iterate
+  DevBuf<double> d_eval_part;  // [batch][max_stages][2]
+  DevBuf<double> d_sol_trial;  // trial iterate: SplitSolution records, constraint records, steps
+  DevBuf<double> d_con_trial;
+  DevBuf<double> d_ls_steps;   // [batch][2] trial steps + [batch] alpha
+  DevBuf<int> d_ls_active;     // [batch] active flags + [1] counter
+  int ls_trials = 0;           // trial evaluations of the last line search
+  // RTOC_OPT_GRAPH: the captured launch sequences.  Declared last: destroyed before the memory their nodes name is freed
+  GraphSlot g_sweep, g_newton;
 };
 
 extern "C" {
@@ -309,21 +333,21 @@ int rtoc_bandwidth_probe(int device, size_t bytes, double* read_gbs, double* cop
   if (bytes < per * 1024) return RTOC_ERR_BAD_ARG;             // RTOC_BANDWIDTH_PROBE_MIN_BYTES: one trip of every wave (512 MiB)
   HIP_TRY(hipSetDevice(device));
   const size_t chunks = (bytes / 1024) / per * per;
-  char *src = nullptr, *dst = nullptr;
-  double* sink = nullptr;
+  DevBuf<char> src, dst;
+  DevBuf<double> sink;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc((void**)&src, chunks * 1024);
-  if (e == hipSuccess) e = hipMalloc((void**)&dst, chunks * 1024);
-  if (e == hipSuccess) e = hipMalloc((void**)&sink, sizeof(double) * blocks * 4);
-  if (e == hipSuccess) e = hipMemset(src, 0, chunks * 1024);
+  hipError_t e = src.reserve(chunks * 1024);
+  if (e == hipSuccess) e = dst.reserve(chunks * 1024);
+  if (e == hipSuccess) e = sink.reserve((size_t)blocks * 4);
+  if (e == hipSuccess) e = hipMemset(src.p, 0, chunks * 1024);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
   double best[2] = {0.0, 0.0};
   for (int mode = 0; mode < 2 && e == hipSuccess; ++mode)
     for (int rep = 0; rep < 6 && e == hipSuccess; ++rep) {   // the first launch warms up
       (void)hipEventRecord(e0, nullptr);
-      if (mode == 0) hipLaunchKernelGGL((stream_probe_kernel<8, false>), dim3(blocks), dim3(256), 0, nullptr, src, dst, chunks, sink);
-      else hipLaunchKernelGGL((stream_probe_kernel<8, true>), dim3(blocks), dim3(256), 0, nullptr, src, dst, chunks, sink);
+      if (mode == 0) hipLaunchKernelGGL((stream_probe_kernel<8, false>), dim3(blocks), dim3(256), 0, nullptr, src.p, dst.p, chunks, sink.p);
+      else hipLaunchKernelGGL((stream_probe_kernel<8, true>), dim3(blocks), dim3(256), 0, nullptr, src.p, dst.p, chunks, sink.p);
       (void)hipEventRecord(e1, nullptr);
       e = hipEventSynchronize(e1);
       float ms = 0.f;
@@ -333,9 +357,6 @@ int rtoc_bandwidth_probe(int device, size_t bytes, double* read_gbs, double* cop
     }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (src) (void)hipFree(src);
-  if (dst) (void)hipFree(dst);
-  if (sink) (void)hipFree(sink);
   if (e != hipSuccess) {
     ctx_set_err(e, __LINE__);
     return RTOC_ERR_HIP;
@@ -363,9 +384,31 @@ const char* rtoc_error_string(int code) {
   }
 }
 
+// doubles of buffer b that the kernels index on a horizon of `stages` grid points: max_stages gives what is allocated
+// (rtoc_buffer_count), nstages what a stage dump holds
+static size_t buffer_count(const rtoc_ctx* c, int b, int stages) {
+  const size_t per = (size_t)c->batch * stages;
+  switch (b) {
+    case RTOC_BUF_KKT: return per * c->L.kkt.stride;
+    case RTOC_BUF_RIC: return per * c->L.ric.stride;
+    case RTOC_BUF_DIR: return per * c->L.dir.stride;
+    case RTOC_BUF_CDD: return per * c->L.cdd.stride;
+    case RTOC_BUF_CON: return per * c->L.con.stride;
+    case RTOC_BUF_DX0: return (size_t)c->batch * c->L.nx;
+    case RTOC_BUF_STEP: return (size_t)c->batch * 2;
+    case RTOC_BUF_SE3: return per * RTOC_SE3_STRIDE;
+    case RTOC_BUF_CONE:   // none until rtoc_set_friction_cones / rtoc_set_wrench_cones
+      if (c->cone_contacts <= 0) return 0;
+      return per * (c->cone_rows == RTOC_WRENCH_ROWS ? rtoc_wrench_cone_stride(c->cone_contacts)
+                                                     : rtoc_cone_stride(c->dims.nv, c->cone_contacts));
+    case RTOC_BUF_SOL: return per * c->L.sol.stride;
+    default: return 0;
+  }
+}
+
 int rtoc_destroy(rtoc_ctx* c);
 // everything of rtoc_create that can fail after the context object exists; the caller destroys the
-// half-built context on failure (rtoc_destroy tolerates members that were never created)
+// half-built context on failure (members that were never created are null)
 static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* ks, int max_stages, int batch, int device) {
   c->dims = *dims;
   rtoc_compute_layout(dims, &c->L);
@@ -379,18 +422,14 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   }
   c->ks = ks;
   c->max_stages = max_stages;
-  c->nstages = 0;
   c->batch = batch;
   c->device = device;
-  c->max_dts0 = 0.1;  // RiccatiRecursion(ocp, max_dts0 = 0.1), riccati_recursion.hpp:35
   c->bwd_variant = (ks->nvariants >= 3) ? ks->nvariants - 1 : 0;  // role-split kernel where it exists
-  c->bwd_register = 1;   // ... and the register-resident kernel wherever it applies (plan_backward)
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
     c->num_cus = cus;
   }
-  c->cond_register = 1;  // likewise the condensation (cond_register_applies)
   if (const char* e = getenv("RTOC_CONDENSE_REGISTER")) c->cond_register = (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
   HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
@@ -405,33 +444,17 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   // RTOC_CONDENSE_SPLIT=0|1 in the environment: default of RTOC_OPT_CONDENSE_SPLIT for contexts created afterwards (runs the
   // whole test suite / bench on the other condensation pipeline without touching the callers)
   if (const char* e = getenv("RTOC_CONDENSE_SPLIT")) c->condense_split = (e[0] == '0') ? 0 : 1;
-  c->sweep_chunks = 1;  // measured on MI355X: chunked pipelining does not pay (forward waves do not fit next to the backward waves)
-  const size_t per = (size_t)batch * max_stages;
-  c->count[RTOC_BUF_KKT] = per * c->L.kkt.stride;
-  c->count[RTOC_BUF_RIC] = per * c->L.ric.stride;
-  c->count[RTOC_BUF_DIR] = per * c->L.dir.stride;
-  c->count[RTOC_BUF_CDD] = per * c->L.cdd.stride;
-  c->count[RTOC_BUF_CON] = per * (size_t)c->L.con.stride;
-  c->count[RTOC_BUF_DX0] = (size_t)batch * c->L.nx;
-  c->count[RTOC_BUF_STEP] = (size_t)batch * 2;
-  c->count[RTOC_BUF_SE3] = per * RTOC_SE3_STRIDE;
-  c->count[RTOC_BUF_CONE] = 0;  // sized by rtoc_set_friction_cones
-  c->count[RTOC_BUF_SOL] = per * c->L.sol.stride;
-  for (int i = 0; i < RTOC_NUM_BUFFERS; ++i) {
-    // the CDD / CON buffers are large; they are allocated lazily on first use (upload / bind / condense)
-    c->buf[i] = nullptr;
-    c->owned[i] = false;
-  }
+  for (int b = 0; b < RTOC_NUM_BUFFERS; ++b) c->want[b] = buffer_count(c, b, max_stages);
+  // the CDD / CON buffers are large; they (and SE3, CONE, SOL) are allocated lazily on first use (upload / bind / condense)
   const int eager[] = {RTOC_BUF_KKT, RTOC_BUF_RIC, RTOC_BUF_DIR, RTOC_BUF_DX0, RTOC_BUF_STEP};
   for (int i : eager) {
-    HIP_TRY(hipMalloc((void**)&c->buf[i], c->count[i] * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c->buf[i], 0, c->count[i] * sizeof(double), c->stream));
-    c->owned[i] = true;
+    HIP_TRY(c->buf[i].reserve(c->want[i]));
+    HIP_TRY(hipMemsetAsync(c->buf[i].p, 0, c->want[i] * sizeof(double), c->stream));
   }
-  HIP_TRY(hipMalloc((void**)&c->d_grid, sizeof(rtoc_grid) * max_stages));
-  HIP_TRY(hipMalloc((void**)&c->d_stage_list, sizeof(int) * max_stages));
-  HIP_TRY(hipMalloc((void**)&c->d_status, sizeof(uint32_t) * batch));
-  HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t) * batch, c->stream));
+  HIP_TRY(c->d_grid.reserve(max_stages));
+  HIP_TRY(c->d_stage_list.reserve(max_stages));
+  HIP_TRY(c->d_status.reserve(batch));
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t) * batch, c->stream));
   // dynamic LDS beyond the default limit: every kernel a launch may name (nullptr: not in this shape's kernel set)
   const struct { const void* f; int bytes; } lds[] = {
       {(const void*)ks->bwd_sa, ks->bwd_lds[3]},        {(const void*)ks->bwd_rv, ks->bwd_rv_lds},
@@ -458,9 +481,7 @@ int rtoc_create(const rtoc_dims* dims, int max_stages, int batch, int device, rt
   HIP_TRY(hipSetDevice(device));
   rtoc_ctx* c = new (std::nothrow) rtoc_ctx();
   if (!c) return RTOC_ERR_BAD_ARG;
-  memset(c, 0, sizeof(*c));
   c->device = device;
-  c->impact_cones = 1;
   int rc = create_members(c, dims, ks, max_stages, batch, device);
   if (rc) {
     (void)rtoc_destroy(c);
@@ -470,72 +491,11 @@ int rtoc_create(const rtoc_dims* dims, int max_stages, int batch, int device, rt
   return RTOC_OK;
 }
 
+// the stream drains first; then ~rtoc_ctx: the graph executables, every buffer, and last the streams and events (CtxStreams)
 int rtoc_destroy(rtoc_ctx* c) {
   if (!c) return RTOC_ERR_BAD_ARG;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (int i = 0; i < RTOC_NUM_BUFFERS; ++i)
-    if (c->owned[i] && c->buf[i]) (void)hipFree(c->buf[i]);
-  if (c->d_grid) (void)hipFree(c->d_grid);
-  if (c->d_stage_list) (void)hipFree(c->d_stage_list);
-  if (c->d_rows) (void)hipFree(c->d_rows);
-  free(c->h_rows);
-  free(c->h_grid);
-  if (c->d_kkterr) (void)hipFree(c->d_kkterr);
-  if (c->d_entry) (void)hipFree(c->d_entry);
-  if (c->d_pair) (void)hipFree(c->d_pair);
-  if (c->d_nconv) (void)hipFree(c->d_nconv);
-  if (c->d_fxx_flag) (void)hipFree(c->d_fxx_flag);
-  if (c->d_sto) (void)hipFree(c->d_sto);
-  if (c->g_sweep.exec) (void)hipGraphExecDestroy(c->g_sweep.exec);
-  if (c->g_newton.exec) (void)hipGraphExecDestroy(c->g_newton.exec);
-  if (c->d_status) (void)hipFree(c->d_status);
-  if (c->d_model) (void)hipFree(c->d_model);
-  delete c->h_model;
-  if (c->d_active) (void)hipFree(c->d_active);
-  if (c->d_cost) (void)hipFree(c->d_cost);
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  if (c->d_mu) (void)hipFree(c->d_mu);
-  if (c->d_wcone) (void)hipFree(c->d_wcone);
-  if (c->d_vals) (void)hipFree(c->d_vals);
-  if (c->d_vals2) (void)hipFree(c->d_vals2);
-  if (c->d_x0) (void)hipFree(c->d_x0);
-  if (c->d_filter) (void)hipFree(c->d_filter);
-  if (c->d_nfilter) (void)hipFree(c->d_nfilter);
-  if (c->d_ls_in) (void)hipFree(c->d_ls_in);
-  if (c->d_ls_flags) (void)hipFree(c->d_ls_flags);
-  if (c->d_ts) (void)hipFree(c->d_ts);
-  if (c->d_dt) (void)hipFree(c->d_dt);
-  if (c->d_sto_con) (void)hipFree(c->d_sto_con);
-  if (c->d_min_dwell) (void)hipFree(c->d_min_dwell);
-  if (c->d_sto_cost) (void)hipFree(c->d_sto_cost);
-  if (c->d_sto_out) (void)hipFree(c->d_sto_out);
-  if (c->d_costval) (void)hipFree(c->d_costval);
-  if (c->d_tasks) (void)hipFree(c->d_tasks);
-  if (c->d_gt) (void)hipFree(c->d_gt);
-  if (c->d_gt_inst) (void)hipFree(c->d_gt_inst);
-  delete c->h_gt;
-  if (c->d_eval) (void)hipFree(c->d_eval);
-  if (c->d_eval_part) (void)hipFree(c->d_eval_part);
-  if (c->d_sol_trial) (void)hipFree(c->d_sol_trial);
-  if (c->d_con_trial) (void)hipFree(c->d_con_trial);
-  if (c->d_ls_steps) (void)hipFree(c->d_ls_steps);
-  if (c->d_ls_merit) (void)hipFree(c->d_ls_merit);
-  if (c->d_ls_active) (void)hipFree(c->d_ls_active);
-  if (c->d_cpos) (void)hipFree(c->d_cpos);
-  if (c->d_crot) (void)hipFree(c->d_crot);
-  if (c->d_prof) (void)hipFree(c->d_prof);
-  for (int i = 0; i < 3; ++i)
-    if (c->d_scan[i]) (void)hipFree(c->d_scan[i]);
-  if (c->d_scan_sto) (void)hipFree(c->d_scan_sto);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  for (int i = 0; i < RTOC_MAX_CHUNK_EVENTS; ++i)
-    if (c->ev_chunk[i]) (void)hipEventDestroy(c->ev_chunk[i]);
   delete c;
   return RTOC_OK;
 }
@@ -551,96 +511,65 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
   rtoc_ctx* n = nullptr;
   int rc = rtoc_create(&c->dims, c->max_stages, c->batch, c->device, &n);
   if (rc) return rc;
-  if (c->nstages >= 2 && c->h_grid) rc = rtoc_set_grid(n, c->h_grid, c->nstages);
-  if (!rc && c->nrows > 0 && c->h_rows) rc = rtoc_set_constraint_rows(n, c->h_rows, c->nrows);
+  if (c->nstages >= 2 && !c->h_grid.empty()) rc = rtoc_set_grid(n, c->h_grid.data(), c->nstages);
+  if (!rc && c->nrows > 0 && !c->h_rows.empty()) rc = rtoc_set_constraint_rows(n, c->h_rows.data(), c->nrows);
   if (!rc && c->cone_contacts > 0)
     rc = c->cone_rows == RTOC_WRENCH_ROWS ? rtoc_set_wrench_cones(n, c->cone_contacts)
                                           : rtoc_set_friction_cones(n, c->cone_contacts, c->cone_dim);
   if (!rc) {
-    n->writeback = c->writeback;
-    n->bwd_register = c->bwd_register;
-    n->cond_register = c->cond_register;
-    n->max_dts0 = c->max_dts0;
-    n->contact_inv_damping = c->contact_inv_damping;
-    n->bwd_variant = c->bwd_variant;
-    n->sweep_chunks = c->sweep_chunks;
-    n->condense_split = c->condense_split;
-    n->keep_qaf = c->keep_qaf;
-    n->fxx_mode = c->fxx_mode;
-    n->use_graph = c->use_graph;
-    n->exact_transport = c->exact_transport;
-    n->impact_cones = c->impact_cones;
-    n->unconstr_dense = c->unconstr_dense;
-    n->linearize_fused = c->linearize_fused;
-    n->lin_dpp = c->lin_dpp;
-    n->exact_cone_jacobian = c->exact_cone_jacobian;
-    n->ls_on = c->ls_on, n->ls_rate = c->ls_rate, n->ls_min_step = c->ls_min_step, n->ls_cost_rate = c->ls_cost_rate, n->ls_viol_rate = c->ls_viol_rate;
-    n->ls_method = c->ls_method, n->ls_armijo = c->ls_armijo, n->ls_margin = c->ls_margin, n->ls_eps = c->ls_eps;
+    static_cast<CtxOptions&>(*n) = *c;
     if (c->backward_scan) rc = rtoc_set_option(n, RTOC_OPT_BACKWARD_SCAN, c->backward_scan);
   }
   hipError_t e = hipStreamSynchronize(c->stream);
-  // the rigid-body model, contact schedule, cost, initial states, constraint bounds and line-search filters (rtoc_robot.h)
-  auto dup = [&](void** dst, const void* src, size_t bytes) {
-    if (!src || rc || e != hipSuccess) return;
-    e = hipMalloc(dst, bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyDeviceToDevice, n->stream);
+  // the rigid-body model, contact schedule, cost, initial states, constraint bounds and line-search filters (rtoc_robot.h):
+  // every buffer with the capacity it has in c, whatever part of it is in use
+  auto dup = [&](auto& dst, const auto& src) {
+    if (!rc && e == hipSuccess) e = dst.copy_from(src, n->stream);
   };
   if (!rc && c->h_model) {
-    n->h_model = new (std::nothrow) rbd::DevModel(*c->h_model);
+    n->h_model.reset(new (std::nothrow) rbd::DevModel(*c->h_model));
     if (!n->h_model) rc = RTOC_ERR_HIP;
-    dup((void**)&n->d_model, c->d_model, sizeof(rbd::DevModel));
+    dup(n->d_model, c->d_model);
     if (!rc && e == hipSuccess)
       e = set_linearize_lds(n->h_model->m, n->h_model->nlevels, n->h_model->nbranch, n->h_model->dpp);
   }
-  dup((void**)&n->d_active, c->d_active, sizeof(unsigned) * c->max_stages);
-  dup((void**)&n->d_cpos, c->d_cpos, sizeof(double) * c->max_stages * RTOC_MAX_CONTACTS * 3);
-  dup((void**)&n->d_crot, c->d_crot, sizeof(double) * c->max_stages * RTOC_MAX_CONTACTS * 9);
-  n->has_cpos = c->has_cpos, n->has_crot = c->has_crot;
-  dup((void**)&n->d_cost, c->d_cost, sizeof(double) * 12 * (c->dims.nv + 1));
-  dup((void**)&n->d_x0, c->d_x0, sizeof(double) * c->batch * (2 * c->dims.nv + (c->dims.np == 6 ? 1 : 0)));
-  dup((void**)&n->d_bounds, c->d_bounds, sizeof(double) * c->dims.nc_max);
-  dup((void**)&n->d_mu, c->d_mu, sizeof(double) * RTOC_MAX_CONTACTS);
-  n->n_mu = c->n_mu;
-  dup((void**)&n->d_wcone, c->d_wcone, sizeof(double) * RTOC_MAX_CONTACTS * RTOC_WRENCH_ROWS * 6);
-  n->barrier = c->barrier, n->ftb_rule = c->ftb_rule;
-  if (c->d_filter) {
-    dup((void**)&n->d_filter, c->d_filter, sizeof(double) * 2 * RTOC_LINE_SEARCH_FILTER_CAPACITY * c->batch);
-    dup((void**)&n->d_nfilter, c->d_nfilter, sizeof(int) * c->batch);
-    dup((void**)&n->d_ls_in, c->d_ls_in, sizeof(double) * 2 * c->batch);
-    dup((void**)&n->d_ls_flags, c->d_ls_flags, sizeof(int) * 2 * c->batch);
+  dup(n->d_active, c->d_active);
+  dup(n->d_cpos, c->d_cpos);
+  dup(n->d_crot, c->d_crot);
+  dup(n->d_cost, c->d_cost);
+  dup(n->d_x0, c->d_x0);
+  dup(n->d_bounds, c->d_bounds);
+  dup(n->d_mu, c->d_mu);
+  dup(n->d_wcone, c->d_wcone);
+  if (c->d_filter.p) {
+    dup(n->d_filter, c->d_filter);
+    dup(n->d_nfilter, c->d_nfilter);
+    dup(n->d_ls_in, c->d_ls_in);
+    dup(n->d_ls_flags, c->d_ls_flags);
   }
   if (c->sto_on) {
     n->sto_on = 1, n->sto_nev = c->sto_nev, n->sto_t0 = c->sto_t0, n->sto_T = c->sto_T;
     n->sto_barrier = c->sto_barrier, n->sto_tau = c->sto_tau, n->sto_reg = c->sto_reg;
-    const size_t ne = (size_t)c->batch * (c->sto_nev > 0 ? c->sto_nev : 1);
-    dup((void**)&n->d_ts, c->d_ts, sizeof(double) * ne);
-    dup((void**)&n->d_dt, c->d_dt, sizeof(double) * c->batch * c->max_stages);
-    dup((void**)&n->d_sto_con, c->d_sto_con, sizeof(double) * c->batch * RTOC_STO_CON_STRIDE);
-    dup((void**)&n->d_min_dwell, c->d_min_dwell, sizeof(double) * (RTOC_STO_MAX_EVENTS + 1));
-    dup((void**)&n->d_sto_cost, c->d_sto_cost, sizeof(double) * 2 * ne);
-    dup((void**)&n->d_sto_out, c->d_sto_out, sizeof(double) * (2 * ne + c->batch));
+    dup(n->d_ts, c->d_ts);
+    dup(n->d_dt, c->d_dt);
+    dup(n->d_sto_con, c->d_sto_con);
+    dup(n->d_min_dwell, c->d_min_dwell);
+    dup(n->d_sto_cost, c->d_sto_cost);
+    dup(n->d_sto_out, c->d_sto_out);
+    dup(n->d_gt_inst, c->d_gt_inst);
   }
   if (c->ntasks > 0) {
     n->ntasks = c->ntasks, n->tasks_per_instance = c->tasks_per_instance;
-    dup((void**)&n->d_tasks, c->d_tasks, sizeof(rtoc_task_cost) * c->ntasks * (c->tasks_per_instance ? c->batch : 1));
+    dup(n->d_tasks, c->d_tasks);
   }
-  dup((void**)&n->d_gt, c->d_gt, sizeof(double) * c->max_stages);
-  if (c->h_gt && !rc) {
-    n->h_gt = new (std::nothrow) std::vector<double>(*c->h_gt);
-    if (!n->h_gt) rc = RTOC_ERR_HIP;
+  dup(n->d_gt, c->d_gt);
+  if (!rc) n->h_gt = c->h_gt;
+  for (int b = 0; b < RTOC_NUM_BUFFERS; ++b) {
+    if (!c->buf[b].p) continue;
+    n->want[b] = c->want[b];
+    dup(n->buf[b], c->buf[b]);
   }
-  if (c->d_gt_inst && c->sto_on) dup((void**)&n->d_gt_inst, c->d_gt_inst, sizeof(double) * c->batch * c->max_stages);
-  for (int b = 0; !rc && e == hipSuccess && b < RTOC_NUM_BUFFERS; ++b) {
-    if (!c->buf[b]) continue;
-    if (!n->buf[b]) {
-      n->count[b] = c->count[b];
-      e = hipMalloc((void**)&n->buf[b], n->count[b] * sizeof(double));
-      if (e != hipSuccess) break;
-      n->owned[b] = true;
-    }
-    e = hipMemcpyAsync(n->buf[b], c->buf[b], c->count[b] * sizeof(double), hipMemcpyDeviceToDevice, n->stream);
-  }
-  if (!rc && e == hipSuccess) e = hipMemcpyAsync(n->d_status, c->d_status, sizeof(uint32_t) * c->batch, hipMemcpyDeviceToDevice, n->stream);
+  dup(n->d_status, c->d_status);
   if (!rc && e == hipSuccess) e = hipStreamSynchronize(n->stream);
   if (rc || e != hipSuccess) {
     if (e != hipSuccess) ctx_set_err(e, __LINE__);
@@ -669,7 +598,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
     if (g.type == RTOC_GRID_LIFT && i == 0) return RTOC_ERR_BAD_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(c->d_grid, grid, sizeof(rtoc_grid) * nstages, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_grid.p, grid, sizeof(rtoc_grid) * nstages, hipMemcpyHostToDevice, c->stream));
   {
     // the grid points a condensation launch covers, by kind (condense_rv_kernel takes the contact ones, condense_kernel the impact ones)
     std::vector<int> list;
@@ -679,12 +608,11 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
     for (int i = 0; i + 1 < nstages; ++i)
       if (grid[i].type == RTOC_GRID_IMPACT) list.push_back(i);
     c->n_stage_impact = (int)list.size() - c->n_stage_contact;
-    HIP_TRY(hipMemcpyAsync(c->d_stage_list, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_stage_list.p, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));   // (the pageable source dies with this scope)
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (!c->h_grid) c->h_grid = (rtoc_grid*)malloc(sizeof(rtoc_grid) * c->max_stages);
-  if (c->h_grid) memcpy(c->h_grid, grid, sizeof(rtoc_grid) * nstages);
+  c->h_grid.assign(grid, grid + nstages);
   c->nstages = nstages;
   c->fxx_state = 0;
   c->epoch++;
@@ -694,7 +622,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
       if (grid[i].type == RTOC_GRID_IMPACT || grid[i].type == RTOC_GRID_LIFT) ++nev;
     if (nev != c->sto_nev) c->sto_on = 0;   // rtoc_sto_set_problem again
   }
-  if (c->h_gt) c->h_gt->clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
+  c->h_gt.clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
   return RTOC_OK;
 }
 
@@ -710,7 +638,7 @@ static int ensure_scan_buffers(rtoc_ctx* c);
 
 // (re)plans the passes of the tangent walk for the context's model and sends the model to the device
 static int apply_linearize_plan(rtoc_ctx* c) {
-  rbd::DevModel* h = c->h_model;
+  rbd::DevModel* h = c->h_model.get();
   const int old_dpp = h->dpp;
   rbd::plan_passes(h, c->lin_dpp);
   if (rbd::lin_lds_bytes(h->nlevels, h->nbranch, h->m.njoints, h->m.ncontacts, h->m.nv, h->dpp, false) > 160 * 1024) {
@@ -718,7 +646,7 @@ static int apply_linearize_plan(rtoc_ctx* c) {
     return RTOC_ERR_BAD_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(c->d_model, h, sizeof(rbd::DevModel), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_model.p, h, sizeof(rbd::DevModel), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(set_linearize_lds(h->m, h->nlevels, h->nbranch, h->dpp));
   return RTOC_OK;
@@ -844,14 +772,18 @@ int rtoc_set_option(rtoc_ctx* c, int option, int64_t value) {
 }
 
 static int ensure_buffer(rtoc_ctx* c, int b) {
-  if (c->buf[b]) return RTOC_OK;
+  if (c->buf[b].p) return RTOC_OK;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMalloc((void**)&c->buf[b], c->count[b] * sizeof(double)));
-  HIP_TRY(hipMemsetAsync(c->buf[b], 0, c->count[b] * sizeof(double), c->stream));
-  c->owned[b] = true;
+  HIP_TRY(c->buf[b].reserve(c->want[b]));
+  HIP_TRY(hipMemsetAsync(c->buf[b].p, 0, c->want[b] * sizeof(double), c->stream));
   c->epoch++;
   return RTOC_OK;
 }
+
+// the buffers that more than one entry point allocates on first use
+static hipError_t reserve_active(rtoc_ctx* c, bool* fresh = nullptr) { return c->d_active.reserve(c->max_stages, fresh); }
+static hipError_t reserve_costval(rtoc_ctx* c) { return c->d_costval.reserve((size_t)c->batch * c->max_stages); }
+static hipError_t reserve_kkterr(rtoc_ctx* c) { return c->d_kkterr.reserve((size_t)c->batch * (1 + c->max_stages)); }
 
 // switching-time optimisation on the device (sto.hpp): kernel arguments, one thread per instance
 static int sto_count_events(const rtoc_ctx* c) {
@@ -865,21 +797,21 @@ static StoDevArgs sto_args(rtoc_ctx* c) {
   StoDevArgs a;
   memset(&a, 0, sizeof(a));
   const size_t ne = (size_t)c->batch * (c->sto_nev > 0 ? c->sto_nev : 1);
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.grid = c->d_grid;
-  a.ts = c->d_ts;
-  a.dt_inst = c->d_dt;
-  a.t_inst = c->d_gt_inst;
-  a.con = c->d_sto_con;
-  a.min_dwell = c->d_min_dwell;
-  a.cost_lt = c->d_sto_cost;
-  a.cost_qtt = c->d_sto_cost ? c->d_sto_cost + ne : nullptr;
-  a.lt = c->d_sto_out;
-  a.qtt = c->d_sto_out + ne;
-  a.err = c->d_sto_out + 2 * ne;
-  a.kkterr = c->d_kkterr;
-  a.steps = c->buf[RTOC_BUF_STEP];
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.grid = c->d_grid.p;
+  a.ts = c->d_ts.p;
+  a.dt_inst = c->d_dt.p;
+  a.t_inst = c->d_gt_inst.p;
+  a.con = c->d_sto_con.p;
+  a.min_dwell = c->d_min_dwell.p;
+  a.cost_lt = c->d_sto_cost.p;
+  a.cost_qtt = c->d_sto_cost.p ? c->d_sto_cost.p + ne : nullptr;
+  a.lt = c->d_sto_out.p;
+  a.qtt = c->d_sto_out.p + ne;
+  a.err = c->d_sto_out.p + 2 * ne;
+  a.kkterr = c->d_kkterr.p;
+  a.steps = c->buf[RTOC_BUF_STEP].p;
   a.nstages = c->nstages, a.batch = c->batch, a.nev = c->sto_nev;
   a.kkt_stride = c->L.kkt.stride, a.scal_off = c->L.kkt.off[RTOC_KKT_SCAL];
   a.dir_stride = c->L.dir.stride, a.dts_off = c->L.dir.off[RTOC_DIR_DTS];
@@ -894,11 +826,11 @@ static StoDevArgs sto_args(rtoc_ctx* c) {
 
 int rtoc_upload(rtoc_ctx* c, int buffer, size_t offset, const double* host, size_t count) {
   if (!c || buffer < 0 || buffer >= RTOC_NUM_BUFFERS || !host) return RTOC_ERR_BAD_ARG;
-  if (count > c->count[buffer] || offset > c->count[buffer] - count) return RTOC_ERR_BAD_ARG;
+  if (count > c->want[buffer] || offset > c->want[buffer] - count) return RTOC_ERR_BAD_ARG;
   int rc = ensure_buffer(c, buffer);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(c->buf[buffer] + offset, host, count * sizeof(double), hipMemcpyHostToDevice,
+  HIP_TRY(hipMemcpyAsync(c->buf[buffer].p + offset, host, count * sizeof(double), hipMemcpyHostToDevice,
                          c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (buffer == RTOC_BUF_KKT) c->fxx_state = 0;  // re-checked by the next backward recursion (RTOC_OPT_FXX_STRUCTURE)
@@ -908,9 +840,9 @@ int rtoc_upload(rtoc_ctx* c, int buffer, size_t offset, const double* host, size
 
 int rtoc_download(rtoc_ctx* c, int buffer, size_t offset, double* host, size_t count) {
   if (!c || buffer < 0 || buffer >= RTOC_NUM_BUFFERS || !host) return RTOC_ERR_BAD_ARG;
-  if (count > c->count[buffer] || offset > c->count[buffer] - count || !c->buf[buffer]) return RTOC_ERR_BAD_ARG;
+  if (count > c->want[buffer] || offset > c->want[buffer] - count || !c->buf[buffer].p) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(host, c->buf[buffer] + offset, count * sizeof(double), hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(host, c->buf[buffer].p + offset, count * sizeof(double), hipMemcpyDeviceToHost,
                          c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
@@ -918,7 +850,7 @@ int rtoc_download(rtoc_ctx* c, int buffer, size_t offset, double* host, size_t c
 
 void* rtoc_device_ptr(rtoc_ctx* c, int buffer) {
   if (!c || buffer < 0 || buffer >= RTOC_NUM_BUFFERS) return nullptr;
-  const bool fresh = !c->buf[buffer];
+  const bool fresh = !c->buf[buffer].p;
   if (ensure_buffer(c, buffer)) return nullptr;
   // the zero fill of a lazily allocated buffer runs on the context's stream: it must have landed before a
   // caller writes through the pointer on a stream of its own
@@ -927,24 +859,20 @@ void* rtoc_device_ptr(rtoc_ctx* c, int buffer) {
     c->fxx_state = 0;  // the caller may write through the pointer
     c->kkt_exposed = true;
   }
-  return c->buf[buffer];
+  return c->buf[buffer].p;
 }
 
 size_t rtoc_buffer_count(const rtoc_ctx* c, int buffer) {
   if (!c || buffer < 0 || buffer >= RTOC_NUM_BUFFERS) return 0;
-  return c->count[buffer];
+  return c->want[buffer];
 }
 
 int rtoc_bind(rtoc_ctx* c, int buffer, void* device_ptr) {
   if (!c || buffer < 0 || buffer >= RTOC_NUM_BUFFERS || !device_ptr) return RTOC_ERR_BAD_ARG;
   if (((uintptr_t)device_ptr & 63) != 0) return RTOC_ERR_BAD_ARG;  // records are 64 B aligned
   HIP_TRY(hipSetDevice(c->device));
-  if (c->owned[buffer] && c->buf[buffer]) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipFree(c->buf[buffer]));
-  }
-  c->buf[buffer] = (double*)device_ptr;
-  c->owned[buffer] = false;
+  if (c->buf[buffer].owned && c->buf[buffer].p) HIP_TRY(hipStreamSynchronize(c->stream));   // ahead of the hipFree
+  c->buf[buffer].bind((double*)device_ptr, c->want[buffer]);
   if (buffer == RTOC_BUF_KKT) c->fxx_state = 0;
   c->epoch++;
   return RTOC_OK;
@@ -959,7 +887,7 @@ static bool grid_has_sto(const rtoc_ctx* c) {
 }
 // the backward recursion: every grid (with switching-time optimisation: matrix scan + serial vector pass, riccati_scan_sto.hpp)
 static bool scan_applies(const rtoc_ctx* c) {
-  if (!c->backward_scan || !c->h_grid) return false;
+  if (!c->backward_scan || c->h_grid.empty()) return false;
   if (c->backward_scan == 2 && c->batch > RTOC_SCAN_AUTO_MAX_BATCH) return false;  // auto: latency regime only
   if (c->nstages > SCAN_STO_MAX_STAGES && grid_has_sto(c)) return false;            // the vector pass keeps the grid in LDS
   return true;
@@ -972,12 +900,8 @@ static bool forward_scan_applies(const rtoc_ctx* c) { return scan_applies(c) && 
 static int ensure_scan_buffers(rtoc_ctx* c) {
   const KernelSet* ks = c->ks;
   const size_t per = (size_t)c->batch * c->max_stages;
-  for (int i = 0; i < 3; ++i)
-    if (!c->d_scan[i]) {
-      const size_t n = per * (i < 2 ? ks->scan_elt_stride : ks->scan_ps_stride);
-      HIP_TRY(hipMalloc((void**)&c->d_scan[i], n * sizeof(double)));
-    }
-  if (!c->d_scan_sto && grid_has_sto(c)) HIP_TRY(hipMalloc((void**)&c->d_scan_sto, per * ks->sto_scr_stride * sizeof(double)));  // (grids with STO only)
+  for (int i = 0; i < 3; ++i) HIP_TRY(c->d_scan[i].reserve(per * (i < 2 ? ks->scan_elt_stride : ks->scan_ps_stride)));
+  if (grid_has_sto(c)) HIP_TRY(c->d_scan_sto.reserve(per * ks->sto_scr_stride));  // (grids with STO only)
   return RTOC_OK;
 }
 
@@ -986,12 +910,12 @@ static int ensure_scan_buffers(rtoc_ctx* c) {
 static BwdArgs bwd_args(const rtoc_ctx* c, int first, int end) {
   BwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
-  a.prof = c->d_prof;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.kkt_rw = c->buf[RTOC_BUF_KKT].p;
+  a.ric = c->buf[RTOC_BUF_RIC].p;
+  a.grid = c->d_grid.p;
+  a.status = c->d_status.p;
+  a.prof = c->d_prof.p;
   a.nstages = c->nstages;
   a.batch = end;
   a.first = first;
@@ -1006,12 +930,12 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   if (rc0) return rc0;
   const int n = c->nstages, nb = end - first;
   ScanArgs s;
-  s.kkt = c->buf[RTOC_BUF_KKT];
-  s.grid = c->d_grid;
-  s.status = c->d_status;
-  s.src = c->d_scan[1];
-  s.dst = c->d_scan[0];
-  s.ps = c->d_scan[2];
+  s.kkt = c->buf[RTOC_BUF_KKT].p;
+  s.grid = c->d_grid.p;
+  s.status = c->d_status.p;
+  s.src = c->d_scan[1].p;
+  s.dst = c->d_scan[0].p;
+  s.ps = c->d_scan[2].p;
   s.nstages = n;
   s.batch = end;
   s.first = first;
@@ -1019,15 +943,15 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   hipLaunchKernelGGL(ks->scan_elt, dim3(n, nb), dim3(SCAN_ELT_NT), ks->scan_elt_lds, stream, s);
   int cur = 0;
   for (int d = 1; d < n; d *= 2) {
-    s.src = c->d_scan[cur];
-    s.dst = c->d_scan[cur ^ 1];
+    s.src = c->d_scan[cur].p;
+    s.dst = c->d_scan[cur ^ 1].p;
     s.dist = d;
     hipLaunchKernelGGL(ks->scan_comb, dim3(n - d, nb, 2), dim3(ks->scan_comb_threads), ks->scan_comb_lds, stream, s);
     cur ^= 1;
   }
   BwdArgs a = bwd_args(c, first, end);
   a.prof = nullptr;
-  a.scan_ps = c->d_scan[2];
+  a.scan_ps = c->d_scan[2].p;
   a.scan_ps_stride = ks->scan_ps_stride;
   a.scan_ps_soff = ks->scan_ps_soff;
   const int v = ks->scan_policy_variant;
@@ -1038,12 +962,12 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   // mutated Quu, lu back into the KKT records (RTOC_OPT_WRITEBACK_KKT), which the preparation reads: then it runs first, by itself.
   const bool ride = sto && !c->writeback && ks->sto_prep_lds <= ks->bwd_lds[v];
   if (sto) {
-    t.kkt = c->buf[RTOC_BUF_KKT], t.ric = c->buf[RTOC_BUF_RIC], t.grid = c->d_grid, t.status = c->d_status;
-    t.ps = c->d_scan[2], t.scr = c->d_scan_sto;
-    t.nstages = n, t.batch = end, t.first = first, t.max_dts0 = c->max_dts0, t.prof = c->d_prof;
+    t.kkt = c->buf[RTOC_BUF_KKT].p, t.ric = c->buf[RTOC_BUF_RIC].p, t.grid = c->d_grid.p, t.status = c->d_status.p;
+    t.ps = c->d_scan[2].p, t.scr = c->d_scan_sto.p;
+    t.nstages = n, t.batch = end, t.first = first, t.max_dts0 = c->max_dts0, t.prof = c->d_prof.p;
     if (!ride) hipLaunchKernelGGL(ks->sto_prep, dim3(n - 1, nb), dim3(SCAN_STO_PREP_NT), ks->sto_prep_lds, stream, t);
   }
-  a.sto_scr = ride ? c->d_scan_sto : nullptr;
+  a.sto_scr = ride ? c->d_scan_sto.p : nullptr;
   hipLaunchKernelGGL(p.kern, dim3(nb, ride ? 2 * n - 1 : n), dim3(64 * ks->bwd_waves[v]), ks->bwd_lds[v], stream, a);
   if (sto) hipLaunchKernelGGL(ks->sto_vec, dim3(nb), dim3(ks->sto_vec_threads), ks->sto_vec_lds, stream, t);   // s, k, m, the STO quantities
   HIP_TRY(hipGetLastError());
@@ -1052,12 +976,12 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
 
 // RTOC_OPT_FXX_STRUCTURE: may the structure-exploiting backward kernel run on the resident records?
 static int check_fxx(rtoc_ctx* c) {
-  if (!c->d_fxx_flag) HIP_TRY(hipMalloc((void**)&c->d_fxx_flag, sizeof(int)));
-  HIP_TRY(hipMemsetAsync(c->d_fxx_flag, 0, sizeof(int), c->stream));
+  HIP_TRY(c->d_fxx_flag.reserve(1));
+  HIP_TRY(hipMemsetAsync(c->d_fxx_flag.p, 0, sizeof(int), c->stream));
   FxxCheckArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.grid = c->d_grid;
-  a.flag = c->d_fxx_flag;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.grid = c->d_grid.p;
+  a.flag = c->d_fxx_flag.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.nv = c->dims.nv;
@@ -1067,7 +991,7 @@ static int check_fxx(rtoc_ctx* c) {
   hipLaunchKernelGGL(fxx_structure_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   int bad = 1;
-  HIP_TRY(hipMemcpyAsync(&bad, c->d_fxx_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, c->d_fxx_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->fxx_state = bad ? 2 : 1;
   return RTOC_OK;
@@ -1082,12 +1006,12 @@ static int check_fxx(rtoc_ctx* c) {
 static int plan_backward(rtoc_ctx* c, BwdPlan* out) {
   const KernelSet* ks = c->ks;
   // the register kernels: the default variant only (an explicit RTOC_OPT_BACKWARD_WAVES keeps its kernel)
-  const bool reg = c->bwd_register && c->h_grid && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback &&
+  const bool reg = c->bwd_register && !c->h_grid.empty() && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback &&
                    c->bwd_variant == ((ks->nvariants >= 3) ? ks->nvariants - 1 : 0);
   const bool sto = reg && grid_has_sto(c);
   const bool rw = reg && ks->bwd_rw && !sto && (c->bwd_register >= 2 || c->batch > c->num_cus);
   // the caller may have rewritten the records since the runtime last saw them (a bound buffer, or its pointer handed out)
-  const bool rewritable = c->fxx_mode == 0 && (!c->owned[RTOC_BUF_KKT] || c->kkt_exposed);
+  const bool rewritable = c->fxx_mode == 0 && (!c->buf[RTOC_BUF_KKT].owned || c->kkt_exposed);
   int rc = RTOC_OK;
   auto structured = [&]() {   // a structured kernel to choose, and the records have the structure
     if (!((ks->bwd_sa && c->bwd_variant == 3) || rw) || c->fxx_mode == 1) return false;
@@ -1140,7 +1064,7 @@ static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end,
   auto constrained = [&](int st) { return c->h_grid[st].type != RTOC_GRID_IMPACT && c->h_grid[st].dims > 0; };
   auto one_stage = [&](int st) {   // tile-split kernel, grid point st only (st == N: the terminal record)
     BwdArgs o = a;
-    o.scan_ps = c->buf[RTOC_BUF_RIC] + c->L.ric.off[RTOC_RIC_P];
+    o.scan_ps = c->buf[RTOC_BUF_RIC].p + c->L.ric.off[RTOC_RIC_P];
     o.scan_ps_stride = c->L.ric.stride;
     o.scan_ps_soff = c->L.ric.off[RTOC_RIC_S] - c->L.ric.off[RTOC_RIC_P];
     o.seg_hi = o.seg_lo = st;
@@ -1191,13 +1115,13 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
   if (rc0) return rc0;
   const int n = c->nstages, nb = end - first, N = n - 1;
   FwdScanArgs s;
-  s.kkt = c->buf[RTOC_BUF_KKT];
-  s.ric = c->buf[RTOC_BUF_RIC];
-  s.dir = c->buf[RTOC_BUF_DIR];
-  s.dx0 = c->buf[RTOC_BUF_DX0];
-  s.grid = c->d_grid;
-  s.src = c->d_scan[1];
-  s.dst = c->d_scan[0];
+  s.kkt = c->buf[RTOC_BUF_KKT].p;
+  s.ric = c->buf[RTOC_BUF_RIC].p;
+  s.dir = c->buf[RTOC_BUF_DIR].p;
+  s.dx0 = c->buf[RTOC_BUF_DX0].p;
+  s.grid = c->d_grid.p;
+  s.src = c->d_scan[1].p;
+  s.dst = c->d_scan[0].p;
   s.nstages = n;
   s.batch = end;
   s.first = first;
@@ -1205,8 +1129,8 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
   hipLaunchKernelGGL(ks->fscan_elt, dim3(N, nb), dim3(SCAN_FWD_NT), ks->fscan_lds, stream, s);
   int cur = 0;
   for (int d = 1; d < N; d *= 2) {
-    s.src = c->d_scan[cur];
-    s.dst = c->d_scan[cur ^ 1];
+    s.src = c->d_scan[cur].p;
+    s.dst = c->d_scan[cur ^ 1].p;
     s.dist = d;
     hipLaunchKernelGGL(ks->fscan_comb, dim3(N - d, nb), dim3(SCAN_FWD_NT), ks->fscan_lds, stream, s);
     cur ^= 1;
@@ -1219,11 +1143,11 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
 static int launch_forward_range(rtoc_ctx* c, int first, int end, hipStream_t stream) {
   if (forward_scan_applies(c)) return launch_forward_scan(c, first, end, stream);
   FwdArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.dx0 = c->buf[RTOC_BUF_DX0];
-  a.grid = c->d_grid;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.ric = c->buf[RTOC_BUF_RIC].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.dx0 = c->buf[RTOC_BUF_DX0].p;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages;
   a.batch = end;
   a.first = first;
@@ -1283,18 +1207,18 @@ static int launch_condense(rtoc_ctx* c) {
   CondArgs a;
   a.stage_list = nullptr;
   a.nlist = 0;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.grid = c->d_grid;
-  a.status = c->d_status;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.grid = c->d_grid.p;
+  a.status = c->d_status.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.damping = c->contact_inv_damping;
-  a.prof = c->d_prof;
-  a.con = (c->nrows > 0) ? c->buf[RTOC_BUF_CON] : nullptr;
-  a.rows = c->d_rows;
-  a.entry = c->d_entry;
-  a.pair = reinterpret_cast<const int4*>(c->d_pair);
+  a.prof = c->d_prof.p;
+  a.con = (c->nrows > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
+  a.rows = c->d_rows.p;
+  a.entry = c->d_entry.p;
+  a.pair = reinterpret_cast<const int4*>(c->d_pair.p);
   a.nrows = c->nrows;
   a.nl = c->L.con;
   a.kl = c->L.kkt;
@@ -1302,14 +1226,14 @@ static int launch_condense(rtoc_ctx* c) {
   const int nblocks = c->batch * (c->nstages - 1);
   a.cone_rows = 0;
   a.keep_qaf = c->keep_qaf;
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   const bool rv = cond_register_applies(c);
   if ((rv ? cond_rv_fuses_cones(c) : (c->condense_split || c->ks->cond_fuses_cones)) && c->cone_contacts > 0) {  // the cone rows ride with the MJtJinv kernel / in wave 1 of the fused kernel / inside condense_rv_kernel
-    if (!c->buf[RTOC_BUF_CONE] || !c->buf[RTOC_BUF_CON]) return RTOC_ERR_NOT_READY;
+    if (!c->buf[RTOC_BUF_CONE].p || !c->buf[RTOC_BUF_CON].p) return RTOC_ERR_NOT_READY;
     const bool wrench = c->cone_rows == RTOC_WRENCH_ROWS;
     a.cone_rows = c->cone_rows;
-    a.cone_con = c->buf[RTOC_BUF_CON];
-    a.cone = c->buf[RTOC_BUF_CONE];
+    a.cone_con = c->buf[RTOC_BUF_CON].p;
+    a.cone = c->buf[RTOC_BUF_CONE].p;
     a.cone_contacts = c->cone_contacts;
     a.cone_dim = c->cone_dim;
     a.cone_row0 = c->dims.nc_max - c->cone_rows * c->cone_contacts;
@@ -1318,7 +1242,7 @@ static int launch_condense(rtoc_ctx* c) {
     a.cone_impact = c->impact_cones;
   }
   if (rv) {
-    a.stage_list = c->d_stage_list;
+    a.stage_list = c->d_stage_list.p;
     a.nlist = c->n_stage_contact;
 #ifdef RTOC_CRV_DEBUG_LDS_PAD   // occupancy experiments (debug builds only): extra dynamic LDS per work item, clamped to what a launch accepts
     static const int lds_pad_env = getenv("RTOC_CRV_LDS_PAD") ? atoi(getenv("RTOC_CRV_LDS_PAD")) : 0;
@@ -1331,7 +1255,7 @@ static int launch_condense(rtoc_ctx* c) {
       hipLaunchKernelGGL(a.cone_rows ? c->ks->cond_rv : c->ks->cond_rv_nc, dim3(c->batch * a.nlist), dim3(64), c->ks->cond_rv_lds + lds_pad, c->stream, a);
       HIP_TRY(hipGetLastError());
     }
-    a.stage_list = c->d_stage_list + c->n_stage_contact;
+    a.stage_list = c->d_stage_list.p + c->n_stage_contact;
     a.nlist = c->n_stage_impact;
     if (a.nlist > 0) hipLaunchKernelGGL(c->ks->cond, dim3(c->batch * a.nlist), dim3(c->ks->cond_threads), c->ks->cond_lds, c->stream, a);
   } else if (c->condense_split) {
@@ -1348,23 +1272,23 @@ static int launch_expand(rtoc_ctx* c, double tau) {
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   ExpArgs a;
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.grid = c->d_grid;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.cl = c->L.cdd;
   a.dl = c->L.dir;
   a.tau = tau;
-  a.con = (c->nrows > 0) ? c->buf[RTOC_BUF_CON] : nullptr;
-  a.rows = c->d_rows;
+  a.con = (c->nrows > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
+  a.rows = c->d_rows.p;
   a.nrows = c->nrows;
   a.nl = c->L.con;
-  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP];
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
-  a.prof = c->d_prof;
+  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
+  a.prof = c->d_prof.p;
   hipLaunchKernelGGL(fill_steps_kernel, dim3((2 * c->batch + 255) / 256), dim3(256), 0, c->stream,
-                     c->buf[RTOC_BUF_STEP], 2 * c->batch);
+                     c->buf[RTOC_BUF_STEP].p, 2 * c->batch);
   const int nblocks = c->batch * (c->nstages - 1);
   hipLaunchKernelGGL(c->ks->expd, dim3(nblocks), dim3(c->ks->expd_threads), c->ks->expd_lds, c->stream, a);
   HIP_TRY(hipGetLastError());
@@ -1372,17 +1296,17 @@ static int launch_expand(rtoc_ctx* c, double tau) {
 }
 
 static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 expand, 2 update
-  if (!c->buf[RTOC_BUF_CONE] || !c->buf[RTOC_BUF_CON]) return RTOC_ERR_NOT_READY;
+  if (!c->buf[RTOC_BUF_CONE].p || !c->buf[RTOC_BUF_CON].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   ConeArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = c->buf[RTOC_BUF_CON];
-  a.cone = c->buf[RTOC_BUF_CONE];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.grid = c->d_grid;
-  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP];
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = c->buf[RTOC_BUF_CON].p;
+  a.cone = c->buf[RTOC_BUF_CONE].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.grid = c->d_grid.p;
+  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.max_contacts = c->cone_contacts;
@@ -1416,19 +1340,19 @@ static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 
   HIP_TRY(hipSetDevice((c)->device));
 
 static int launch_state_correction(rtoc_ctx* c, int mode) {
-  if (!c->buf[RTOC_BUF_SE3]) return RTOC_ERR_BAD_ARG;
+  if (!c->buf[RTOC_BUF_SE3].p) return RTOC_ERR_BAD_ARG;
   SeArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.dx0 = c->buf[RTOC_BUF_DX0];
-  a.se3 = c->buf[RTOC_BUF_SE3];
-  a.grid = c->d_grid;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.dx0 = c->buf[RTOC_BUF_DX0].p;
+  a.se3 = c->buf[RTOC_BUF_SE3].p;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.kl = c->L.kkt;
   a.dl = c->L.dir;
   a.nx = c->L.nx;
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   const int nblocks = (mode == 2) ? c->batch : c->batch * c->nstages;
   if (mode == 0)
     hipLaunchKernelGGL(state_correction_kernel<0>, dim3(nblocks), dim3(64), 0, c->stream, a);
@@ -1464,7 +1388,7 @@ int rtoc_condense(rtoc_ctx* c) {
   if (c->cone_contacts > 0 && (cond_register_applies(c) ? !cond_rv_fuses_cones(c) : (!c->condense_split && !c->ks->cond_fuses_cones)))
     rc = launch_cones(c, 0, 0.0);  // Constraints::condenseSlackAndDual first
   if (!rc) rc = launch_condense(c);
-  if (!rc && c->buf[RTOC_BUF_SE3] && c->dims.np == 6) rc = launch_state_correction(c, 0);
+  if (!rc && c->buf[RTOC_BUF_SE3].p && c->dims.np == 6) rc = launch_state_correction(c, 0);
   return rc;
 }
 
@@ -1486,7 +1410,7 @@ int rtoc_riccati_forward(rtoc_ctx* c) {
 // small kernels, whose launch gaps are a third of its latency.
 extern "C++" {
 template <class Body>
-static int run_graphed(rtoc_ctx* c, rtoc_ctx::GraphSlot* g, double p0, double p1, Body body) {
+static int run_graphed(rtoc_ctx* c, GraphSlot* g, double p0, double p1, Body body) {
   if (!c->use_graph) return body();
   if (g->exec && g->epoch == c->epoch && g->p0 == p0 && g->p1 == p1) {
     HIP_TRY(hipGraphLaunch(g->exec, c->stream));
@@ -1543,7 +1467,7 @@ int rtoc_riccati_sweep(rtoc_ctx* c) {
 
 static int launch_fill(rtoc_ctx* c, double dt) {
   FillArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.dt = dt;
@@ -1562,14 +1486,14 @@ static int launch_unconstr_riccati(rtoc_ctx* c, double dt, bool forward) {
   int rc = ensure_buffer(c, RTOC_BUF_RIC);
   if (!rc && forward) rc = ensure_buffer(c, RTOC_BUF_DIR);
   if (rc) return rc;
-  if (!c->buf[RTOC_BUF_KKT]) return RTOC_ERR_NOT_READY;
+  if (!c->buf[RTOC_BUF_KKT].p) return RTOC_ERR_NOT_READY;
   UrArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.kkt_rw = c->buf[RTOC_BUF_KKT];
-  a.ric = c->buf[RTOC_BUF_RIC];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.dx0 = c->buf[RTOC_BUF_DX0];
-  a.status = c->d_status;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.kkt_rw = c->buf[RTOC_BUF_KKT].p;
+  a.ric = c->buf[RTOC_BUF_RIC].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.dx0 = c->buf[RTOC_BUF_DX0].p;
+  a.status = c->d_status.p;
   a.nstages = c->nstages, a.batch = c->batch, a.writeback = c->writeback;
   a.dt = dt;
   a.kl = c->L.kkt, a.rl = c->L.ric, a.dl = c->L.dir;
@@ -1593,9 +1517,9 @@ static int launch_unconstr_dynamics(rtoc_ctx* c, bool expand, double dt) {
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   UdArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.dir = c->buf[RTOC_BUF_DIR];
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.dt = dt;
@@ -1631,7 +1555,7 @@ int rtoc_expand(rtoc_ctx* c, double tau) {
   if (!(tau > 0.0 && tau <= 1.0)) return RTOC_ERR_BAD_ARG;
   int rc = launch_expand(c, tau);
   if (!rc && c->cone_contacts > 0) rc = launch_cones(c, 1, tau);
-  if (!rc && c->buf[RTOC_BUF_SE3] && c->dims.np == 6) rc = launch_state_correction(c, 1);
+  if (!rc && c->buf[RTOC_BUF_SE3].p && c->dims.np == 6) rc = launch_state_correction(c, 1);
   return rc;
 }
 
@@ -1643,10 +1567,10 @@ int rtoc_update(rtoc_ctx* c) {
   }
   if (c->nrows == 0) return RTOC_OK;
   UpdArgs a;
-  a.con = c->buf[RTOC_BUF_CON];
-  a.rows = c->d_rows;
-  a.grid = c->d_grid;
-  a.steps = c->buf[RTOC_BUF_STEP];
+  a.con = c->buf[RTOC_BUF_CON].p;
+  a.rows = c->d_rows.p;
+  a.grid = c->d_grid.p;
+  a.steps = c->buf[RTOC_BUF_STEP].p;
   a.nrows = c->nrows;
   a.nstages = c->nstages;
   a.batch = c->batch;
@@ -1668,11 +1592,8 @@ static int set_cones(rtoc_ctx* c, int max_contacts, int contact_dim, int rows_pe
     return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   const size_t need = (size_t)c->batch * c->max_stages * stride;
-  if (c->buf[RTOC_BUF_CONE] && c->count[RTOC_BUF_CONE] != need) {
-    if (c->owned[RTOC_BUF_CONE]) (void)hipFree(c->buf[RTOC_BUF_CONE]);
-    c->buf[RTOC_BUF_CONE] = nullptr;
-  }
-  c->count[RTOC_BUF_CONE] = need;
+  if (c->want[RTOC_BUF_CONE] != need) c->buf[RTOC_BUF_CONE].release();
+  c->want[RTOC_BUF_CONE] = need;
   int rc = ensure_buffer(c, RTOC_BUF_CONE);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CON);
   if (rc) return rc;
@@ -1732,8 +1653,8 @@ int rtoc_set_constraint_rows(rtoc_ctx* c, const rtoc_box_row* rows, int nrows) {
   if (nrows > 0) {
     int rc = ensure_buffer(c, RTOC_BUF_CON);
     if (rc) return rc;
-    if (!c->d_rows) HIP_TRY(hipMalloc((void**)&c->d_rows, sizeof(rtoc_box_row) * c->dims.nc_max));
-    HIP_TRY(hipMemcpyAsync(c->d_rows, rows, sizeof(rtoc_box_row) * nrows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->d_rows.reserve(c->dims.nc_max));
+    HIP_TRY(hipMemcpyAsync(c->d_rows.p, rows, sizeof(rtoc_box_row) * nrows, hipMemcpyHostToDevice, c->stream));
     // rows grouped by the primal entry they act on (ascending row index inside a group, i.e. the
     // order in which the reference's components touch that entry)
     // primal entries: q (nv), v (nv), u (nu), a (nv)
@@ -1746,9 +1667,8 @@ int rtoc_set_constraint_rows(rtoc_ctx* c, const rtoc_box_row* rows, int nrows) {
     for (int e = 0; e < ne; ++e) csr[e + 1] += csr[e];
     std::vector<int> fill(csr.begin(), csr.begin() + ne);
     for (int r = 0; r < nrows; ++r) csr[ne + 1 + fill[entry_of(rows[r])]++] = r;
-    if (!c->d_entry)
-      HIP_TRY(hipMalloc((void**)&c->d_entry, sizeof(int) * (ne + 1 + c->dims.nc_max)));
-    HIP_TRY(hipMemcpyAsync(c->d_entry, csr.data(), sizeof(int) * csr.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->d_entry.reserve(ne + 1 + c->dims.nc_max));
+    HIP_TRY(hipMemcpyAsync(c->d_entry.p, csr.data(), sizeof(int) * csr.size(), hipMemcpyHostToDevice, c->stream));
     // the first two rows of every entry, packed (condense.hpp)
     std::vector<int> pair(4 * (size_t)ne, -1);
     for (int e = 0; e < ne; ++e)
@@ -1757,14 +1677,11 @@ int rtoc_set_constraint_rows(rtoc_ctx* c, const rtoc_box_row* rows, int nrows) {
         pair[4 * e + k] = r;
         pair[4 * e + 2 + k] = (rows[r].sign & 0xff) | (rows[r].level << 8);
       }
-    if (!c->d_pair) HIP_TRY(hipMalloc((void**)&c->d_pair, sizeof(int) * 4 * ne));
-    HIP_TRY(hipMemcpyAsync(c->d_pair, pair.data(), sizeof(int) * pair.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c->d_pair.reserve(4 * ne));
+    HIP_TRY(hipMemcpyAsync(c->d_pair.p, pair.data(), sizeof(int) * pair.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
-  if (nrows > 0) {
-    if (!c->h_rows) c->h_rows = (rtoc_box_row*)malloc(sizeof(rtoc_box_row) * c->dims.nc_max);
-    if (c->h_rows) memcpy(c->h_rows, rows, sizeof(rtoc_box_row) * nrows);
-  }
+  if (nrows > 0) c->h_rows.assign(rows, rows + nrows);
   c->nrows = nrows;
   c->epoch++;
   return RTOC_OK;
@@ -1781,7 +1698,7 @@ int rtoc_check_fxx_structure(rtoc_ctx* c, int* structured) {
 int rtoc_status(rtoc_ctx* c, uint32_t* host_flags, int count) {
   if (!c || !host_flags || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemcpyAsync(host_flags, c->d_status, sizeof(uint32_t) * count, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(host_flags, c->d_status.p, sizeof(uint32_t) * count, hipMemcpyDeviceToHost,
                          c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
@@ -1790,7 +1707,7 @@ int rtoc_status(rtoc_ctx* c, uint32_t* host_flags, int count) {
 int rtoc_clear_status(rtoc_ctx* c) {
   if (!c) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(uint32_t) * c->batch, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t) * c->batch, c->stream));
   return RTOC_OK;
 }
 
@@ -1800,13 +1717,13 @@ int rtoc_debug_profile(rtoc_ctx* c, long long* host_out) {
   if (!c) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)c->max_stages * 32;
-  if (!c->d_prof) {
-    HIP_TRY(hipMalloc((void**)&c->d_prof, n * sizeof(long long)));
-    HIP_TRY(hipMemsetAsync(c->d_prof, 0, n * sizeof(long long), c->stream));
+  if (!c->d_prof.p) {
+    HIP_TRY(c->d_prof.reserve(n));
+    HIP_TRY(hipMemsetAsync(c->d_prof.p, 0, n * sizeof(long long), c->stream));
     return RTOC_OK;
   }
   if (host_out) {
-    HIP_TRY(hipMemcpyAsync(host_out, c->d_prof, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, c->d_prof.p, n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return RTOC_OK;
@@ -1853,12 +1770,12 @@ int rtoc_time_phase(rtoc_ctx* c, int phase, int reps, float* ms) {
 // ---- SplitSolution::integrate ---------------------------------------------------------------
 int rtoc_integrate_solution(rtoc_ctx* c) {
   CHECK_READY(c);
-  if (!c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   IntArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.steps = c->buf[RTOC_BUF_STEP];
-  a.grid = c->d_grid;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.steps = c->buf[RTOC_BUF_STEP].p;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.nv = c->dims.nv;
@@ -1875,9 +1792,9 @@ int rtoc_integrate_solution(rtoc_ctx* c) {
 
 // ---- rigid-body linearisation (include/rtoc_robot.h) ------------------------------------------
 // The checks of a robot-model table that do not depend on a context, and everything the kernels precompute from it (tree levels,
-// packed constants, the tangent walk's storage plan and passes).  *out: a new DevModel (caller deletes) or nullptr.
-static int build_dev_model(const rtoc_robot_model* m, int forced_dpp, rbd::DevModel** out, int* max_dimf_out) {
-  *out = nullptr;
+// packed constants, the tangent walk's storage plan and passes).  out: a new DevModel, or empty.
+static int build_dev_model(const rtoc_robot_model* m, int forced_dpp, std::unique_ptr<rbd::DevModel>& out, int* max_dimf_out) {
+  out.reset();
   if (!m) return RTOC_ERR_BAD_ARG;
   if (m->njoints < 1 || m->njoints > RTOC_MAX_JOINTS || m->ncontacts < 0 || m->ncontacts > RTOC_MAX_CONTACTS) return RTOC_ERR_BAD_ARG;
   int max_dimf = 0;
@@ -1889,7 +1806,7 @@ static int build_dev_model(const rtoc_robot_model* m, int forced_dpp, rbd::DevMo
   if (max_dimf_out) *max_dimf_out = max_dimf;
   const bool ff = m->type[0] == RTOC_JOINT_FREE_FLYER;
   if (m->nv < 1 || m->nv > RTOC_MAX_JOINTS + 8 || m->nq != m->nv + (ff ? 1 : 0)) return RTOC_ERR_BAD_ARG;
-  rbd::DevModel* h = new (std::nothrow) rbd::DevModel;
+  std::unique_ptr<rbd::DevModel> h(new (std::nothrow) rbd::DevModel);
   if (!h) return RTOC_ERR_HIP;
   h->m = *m;
   // depth-first order: when joint i is visited, the joint open one level up must be its parent
@@ -1911,53 +1828,44 @@ static int build_dev_model(const rtoc_robot_model* m, int forced_dpp, rbd::DevMo
   }
   ok = ok && iq == m->nq && iv == m->nv;
   for (int k = 0; k < m->ncontacts && ok; ++k) ok = m->contact_parent[k] >= 0 && m->contact_parent[k] < m->njoints;
-  if (!ok) {
-    delete h;
-    return RTOC_ERR_BAD_ARG;
-  }
+  if (!ok) return RTOC_ERR_BAD_ARG;
   h->nlevels = nlev;
-  rbd::pack_model(h);
-  if (forced_dpp) rbd::plan_passes(h, forced_dpp);
+  rbd::pack_model(h.get());
+  if (forced_dpp) rbd::plan_passes(h.get(), forced_dpp);
   // (the walk's plan word has four bits for a forward-tangent slot: at most 14 branching bodies on a root-to-leaf path)
-  if (h->nbranch > 14 || rbd::lin_lds_bytes(nlev, h->nbranch, m->njoints, m->ncontacts, m->nv, h->dpp, false) > 160 * 1024) {
-    delete h;
+  if (h->nbranch > 14 || rbd::lin_lds_bytes(nlev, h->nbranch, m->njoints, m->ncontacts, m->nv, h->dpp, false) > 160 * 1024)
     return RTOC_ERR_BAD_ARG;
-  }
-  *out = h;
+  out = std::move(h);
   return RTOC_OK;
 }
 
 int rtoc_robot_model_plan(const rtoc_robot_model* m, int forced_dofs_per_pass, rtoc_linearize_plan* plan, unsigned long long* pass_bodies) {
   if (!plan || forced_dofs_per_pass < 0 || forced_dofs_per_pass > rbd::LIN_MAX_DPP) return RTOC_ERR_BAD_ARG;
-  rbd::DevModel* h = nullptr;
-  const int rc = build_dev_model(m, forced_dofs_per_pass, &h, nullptr);
+  std::unique_ptr<rbd::DevModel> h;
+  const int rc = build_dev_model(m, forced_dofs_per_pass, h, nullptr);
   if (rc) return rc;
   plan->nlevels = h->nlevels, plan->nbranch = h->nbranch, plan->dofs_per_pass = h->dpp, plan->npass = h->npass;
   plan->lds_bytes = (int)rbd::lin_lds_bytes(h->nlevels, h->nbranch, m->njoints, m->ncontacts, m->nv, h->dpp, true);
   if (pass_bodies)
     for (int p = 0; p < RTOC_MAX_JOINTS + 8; ++p) pass_bodies[p] = p < h->npass ? h->pass_bodies[p] : 0ull;
-  delete h;
   return RTOC_OK;
 }
 
 int rtoc_set_robot_model(rtoc_ctx* c, const rtoc_robot_model* m) {
   if (!c || !m) return RTOC_ERR_BAD_ARG;
-  rbd::DevModel* h = nullptr;
+  std::unique_ptr<rbd::DevModel> h;
   int max_dimf = 0;
-  const int brc = build_dev_model(m, c->lin_dpp, &h, &max_dimf);
+  const int brc = build_dev_model(m, c->lin_dpp, h, &max_dimf);
   if (brc) return brc;
   const bool ff = m->type[0] == RTOC_JOINT_FREE_FLYER;
-  if (m->nv != c->dims.nv || max_dimf > c->dims.nf_max || (ff ? m->nv - 6 : m->nv) != c->dims.nu) {
-    delete h;
+  if (m->nv != c->dims.nv || max_dimf > c->dims.nf_max || (ff ? m->nv - 6 : m->nv) != c->dims.nu)
     return RTOC_ERR_BAD_ARG;
-  }
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_model) HIP_TRY(hipMalloc((void**)&c->d_model, sizeof(rbd::DevModel)));
-  delete c->h_model;
-  c->h_model = h;
-  HIP_TRY(hipMemcpyAsync(c->d_model, h, sizeof(rbd::DevModel), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_model.reserve(1));
+  c->h_model = std::move(h);
+  HIP_TRY(hipMemcpyAsync(c->d_model.p, c->h_model.get(), sizeof(rbd::DevModel), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(set_linearize_lds(*m, h->nlevels, h->nbranch, h->dpp));
+  HIP_TRY(set_linearize_lds(*m, c->h_model->nlevels, c->h_model->nbranch, c->h_model->dpp));
   c->epoch++;
   return RTOC_OK;
 }
@@ -1975,14 +1883,14 @@ int rtoc_set_contact_schedule(rtoc_ctx* c, const unsigned* active, const double*
     if (i < c->nstages - 1 && rows != c->h_grid[i].dimf) return RTOC_ERR_BAD_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, sizeof(unsigned) * c->max_stages));
-  if (!c->d_cpos) HIP_TRY(hipMalloc((void**)&c->d_cpos, sizeof(double) * c->max_stages * RTOC_MAX_CONTACTS * 3));
-  if (rotations && !c->d_crot) HIP_TRY(hipMalloc((void**)&c->d_crot, sizeof(double) * c->max_stages * RTOC_MAX_CONTACTS * 9));
-  HIP_TRY(hipMemcpyAsync(c->d_active, active, sizeof(unsigned) * c->nstages, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(reserve_active(c));
+  HIP_TRY(c->d_cpos.reserve((size_t)c->max_stages * RTOC_MAX_CONTACTS * 3));
+  if (rotations) HIP_TRY(c->d_crot.reserve((size_t)c->max_stages * RTOC_MAX_CONTACTS * 9));
+  HIP_TRY(hipMemcpyAsync(c->d_active.p, active, sizeof(unsigned) * c->nstages, hipMemcpyHostToDevice, c->stream));
   if (positions)
-    HIP_TRY(hipMemcpyAsync(c->d_cpos, positions, sizeof(double) * c->nstages * nc * 3, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_cpos.p, positions, sizeof(double) * c->nstages * nc * 3, hipMemcpyHostToDevice, c->stream));
   if (rotations)
-    HIP_TRY(hipMemcpyAsync(c->d_crot, rotations, sizeof(double) * c->nstages * nc * 9, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_crot.p, rotations, sizeof(double) * c->nstages * nc * 9, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->has_cpos = positions != nullptr;
   c->has_crot = rotations != nullptr;
@@ -1999,20 +1907,14 @@ static int ensure_rbd_values(rtoc_ctx* c) {
   bool any_impact = false;
   for (int i = 0; i + 1 < c->nstages; ++i) any_impact = any_impact || c->h_grid[i].type == RTOC_GRID_IMPACT;
   const size_t need = (size_t)c->batch * c->max_stages * m.njoints * rbd::VAL_SLOTS;
-  if (c->vals_cap < need) {
-    if (c->d_vals) (void)hipFree(c->d_vals);
-    if (c->d_vals2) (void)hipFree(c->d_vals2);
-    c->d_vals = c->d_vals2 = nullptr;
-    c->vals_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->d_vals, need * sizeof(double)));
-    c->vals_cap = need;
-  }
-  if (any_impact && !c->d_vals2) HIP_TRY(hipMalloc((void**)&c->d_vals2, c->vals_cap * sizeof(double)));
+  if (c->d_vals.n < need) c->d_vals2.release();   // both grow together: the second one only on grids with an impact
+  HIP_TRY(c->d_vals.grow(need));
+  if (any_impact) HIP_TRY(c->d_vals2.reserve(c->d_vals.n));
   return RTOC_OK;
 }
 
 static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
-  if (!c->h_model || !c->d_active || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!c->h_model || !c->d_active.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   if (c->nstages < 2) return RTOC_OK;
@@ -2022,7 +1924,7 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   rc = ensure_rbd_values(c);
   if (rc) return rc;
   rbd::ValArgs v;
-  v.model = c->d_model, v.sol = c->buf[RTOC_BUF_SOL], v.cdd = c->buf[RTOC_BUF_CDD], v.grid = c->d_grid, v.active = c->d_active;
+  v.model = c->d_model.p, v.sol = c->buf[RTOC_BUF_SOL].p, v.cdd = c->buf[RTOC_BUF_CDD].p, v.grid = c->d_grid.p, v.active = c->d_active.p;
   v.nstages = c->nstages, v.batch = c->batch, v.nv = m.nv, v.njoints = m.njoints, v.ncontacts = m.ncontacts;
   v.nu = m.type[0] == RTOC_JOINT_FREE_FLYER ? m.nv - 6 : m.nv;
   v.nlevels = c->h_model->nlevels, v.unconstr = unconstr ? 1 : 0;
@@ -2032,13 +1934,13 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   v.o_q = c->L.sol.off[RTOC_SOL_Q], v.o_v = c->L.sol.off[RTOC_SOL_V], v.o_a = c->L.sol.off[RTOC_SOL_A];
   v.o_u = c->L.sol.off[RTOC_SOL_U], v.o_f = c->L.sol.off[RTOC_SOL_F], v.o_idc = c->L.cdd.off[RTOC_CDD_IDC];
   v.gx = m.gravity[0], v.gy = m.gravity[1], v.gz = m.gravity[2];
-  v.positions = c->has_cpos ? c->d_cpos : nullptr, v.rotations = c->has_crot ? c->d_crot : nullptr;
+  v.positions = c->has_cpos ? c->d_cpos.p : nullptr, v.rotations = c->has_crot ? c->d_crot.p : nullptr;
   const int G = 64 / v.gs;
   const long long items = (long long)c->batch * (c->nstages - 1);
   const size_t vlds = sizeof(double) * G * m.njoints * rbd::VAL_SLOTS;
   for (int trav = 0; trav < (any_impact ? 2 : 1); ++trav) {
     v.trav = trav;
-    v.vals = trav == 0 ? c->d_vals : c->d_vals2;
+    v.vals = trav == 0 ? c->d_vals.p : c->d_vals2.p;
     v.nsel = 0;
     long long n = items;
     if (trav == 1) {   // the kinematics traversal exists on impact grids only: launch just those (if they fit the list)
@@ -2058,18 +1960,18 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
 }
 
 static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, double scale) {
-  if (!c->h_model || !c->d_active || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
-  if (augment_residual && !c->buf[RTOC_BUF_KKT]) return RTOC_ERR_NOT_READY;
+  if (!c->h_model || !c->d_active.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
+  if (augment_residual && !c->buf[RTOC_BUF_KKT].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   rbd::LinArgs a;
-  a.model = c->d_model;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.grid = c->d_grid;
-  a.active = c->d_active;
-  a.positions = c->has_cpos ? c->d_cpos : nullptr;
-  a.rotations = c->has_crot ? c->d_crot : nullptr;
+  a.model = c->d_model.p;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.grid = c->d_grid.p;
+  a.active = c->d_active.p;
+  a.positions = c->has_cpos ? c->d_cpos.p : nullptr;
+  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.sol_stride = c->L.sol.stride;
@@ -2092,7 +1994,7 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
     a.nu = m.type[0] == RTOC_JOINT_FREE_FLYER ? m.nv - 6 : m.nv;
     a.gx = m.gravity[0], a.gy = m.gravity[1], a.gz = m.gravity[2];
   }
-  a.kkt = augment_residual ? c->buf[RTOC_BUF_KKT] : nullptr;
+  a.kkt = augment_residual ? c->buf[RTOC_BUF_KKT].p : nullptr;
   a.kkt_stride = c->L.kkt.stride;
   a.o_lx = c->L.kkt.off[RTOC_KKT_LX];
   a.o_lu = c->L.kkt.off[RTOC_KKT_LU];
@@ -2115,7 +2017,7 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
       if (rv) return rv;
     }
     c->vals_fresh = 0;
-    a.vals = c->d_vals, a.vals2 = c->d_vals2;
+    a.vals = c->d_vals.p, a.vals2 = c->d_vals2.p;
     if (surf)
       hipLaunchKernelGGL((rbd::linearize_contact_dynamics_kernel<true, true>), dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
     else
@@ -2151,8 +2053,8 @@ int rtoc_set_configuration_cost(rtoc_ctx* c, const rtoc_configuration_cost* cost
       h[(size_t)k * M + i] = src[k][i];
     }
   }
-  if (!c->d_cost) HIP_TRY(hipMalloc((void**)&c->d_cost, sizeof(double) * 12 * M));
-  HIP_TRY(hipMemcpyAsync(c->d_cost, h.data(), sizeof(double) * 12 * M, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_cost.reserve(12 * M));
+  HIP_TRY(hipMemcpyAsync(c->d_cost.p, h.data(), sizeof(double) * 12 * M, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2162,8 +2064,8 @@ int rtoc_set_initial_state(rtoc_ctx* c, const double* x0, int count) {
   HIP_TRY(hipSetDevice(c->device));
   const int nq = c->dims.nv + (c->dims.np == 6 ? 1 : 0);  // a free-flyer base carries a quaternion
   const size_t n = (size_t)c->batch * (nq + c->dims.nv);
-  if (!c->d_x0) HIP_TRY(hipMalloc((void**)&c->d_x0, sizeof(double) * n));
-  HIP_TRY(hipMemcpyAsync(c->d_x0, x0, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_x0.reserve(n));
+  HIP_TRY(hipMemcpyAsync(c->d_x0.p, x0, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2175,7 +2077,7 @@ int rtoc_linearize_state_equation(rtoc_ctx* c) { return launch_state_equation(c,
 // half are written, and the records are known to have the structure RTOC_OPT_FXX_STRUCTURE's check would find
 static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   CHECK_READY(c);
-  if (!c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->dims.np != 0 && c->dims.np != 6) return RTOC_ERR_BAD_ARG;
   int rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
@@ -2183,13 +2085,13 @@ static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   if (!rc && c->dims.np == 6) rc = ensure_buffer(c, RTOC_BUF_SE3);
   if (rc) return rc;
   SeLinArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.x0 = c->d_x0;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.se3 = c->dims.np == 6 ? c->buf[RTOC_BUF_SE3] : nullptr;
-  a.dx0 = c->d_x0 ? c->buf[RTOC_BUF_DX0] : nullptr;
-  a.grid = c->d_grid;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.x0 = c->d_x0.p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.se3 = c->dims.np == 6 ? c->buf[RTOC_BUF_SE3].p : nullptr;
+  a.dx0 = c->d_x0.p ? c->buf[RTOC_BUF_DX0].p : nullptr;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.floating = c->dims.np == 6;
   a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
   a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A];
@@ -2198,7 +2100,7 @@ static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   a.o_hx = c->L.kkt.off[RTOC_KKT_HX], a.o_ffx = c->L.kkt.off[RTOC_KKT_FFX], a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
   a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_ha = c->L.cdd.off[RTOC_CDD_HA];
   a.zeroed = zeroed ? 1 : 0;
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   hipLaunchKernelGGL(state_equation_lin_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fxx_state = zeroed ? 1 : 0;
@@ -2209,8 +2111,8 @@ int rtoc_set_constraint_bounds(rtoc_ctx* c, const double* bounds, int nrows, dou
   if (!c || !bounds || nrows != c->nrows || nrows <= 0) return RTOC_ERR_BAD_ARG;
   if (!(barrier_param > 0.0) || !(fraction_to_boundary_rule > 0.0) || !(fraction_to_boundary_rule < 1.0)) return RTOC_ERR_BAD_ARG;  // constraints.cpp setters
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_bounds) HIP_TRY(hipMalloc((void**)&c->d_bounds, sizeof(double) * c->dims.nc_max));
-  HIP_TRY(hipMemcpyAsync(c->d_bounds, bounds, sizeof(double) * nrows, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_bounds.reserve(c->dims.nc_max));
+  HIP_TRY(hipMemcpyAsync(c->d_bounds.p, bounds, sizeof(double) * nrows, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->barrier = barrier_param;
   c->ftb_rule = fraction_to_boundary_rule;
@@ -2219,16 +2121,16 @@ int rtoc_set_constraint_bounds(rtoc_ctx* c, const double* bounds, int nrows, dou
 
 static int launch_ubox(rtoc_ctx* c, int mode, bool contact = false) {
   UboxArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = c->buf[RTOC_BUF_CON];
-  a.dir = c->buf[RTOC_BUF_DIR];
-  a.rows = c->d_rows;
-  a.entry = c->d_entry;
-  a.bounds = c->d_bounds;
-  a.grid = c->d_grid;
-  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP];
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = c->buf[RTOC_BUF_CON].p;
+  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.rows = c->d_rows.p;
+  a.entry = c->d_entry.p;
+  a.bounds = c->d_bounds.p;
+  a.grid = c->d_grid.p;
+  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
   a.nstages = c->nstages, a.batch = c->batch, a.nrows = c->nrows, a.nv = c->dims.nv, a.nu = c->dims.nu, a.mode = mode;
   a.barrier = c->barrier, a.tau = c->ftb_rule;
   a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
@@ -2245,12 +2147,12 @@ static int launch_ubox(rtoc_ctx* c, int mode, bool contact = false) {
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
-static bool ubox_on(const rtoc_ctx* c) { return c->nrows > 0 && c->d_bounds != nullptr; }
+static bool ubox_on(const rtoc_ctx* c) { return c->nrows > 0 && c->d_bounds.p != nullptr; }
 
 // UnconstrOCPSolver::initConstraints (unconstr_ocp_solver.cpp:91-93): setSlackAndDual of every row at the current iterate
 int rtoc_unconstr_init_constraints(rtoc_ctx* c) {
   CHECK_READY(c);
-  if (!ubox_on(c) || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!ubox_on(c) || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
   int rc = ensure_buffer(c, RTOC_BUF_CON);
   if (rc) return rc;
@@ -2261,23 +2163,22 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   CHECK_READY(c);
   if (!(dt > 0.0) || c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
   if (c->ntasks > 0) return RTOC_ERR_BAD_ARG;   // task-space costs are evaluated on the contact path only
-  if (!c->h_model || !c->d_cost || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!c->h_model || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
   int rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_DX0);
   if (rc) return rc;
-  if (!c->d_active) {  // no contacts: an all-zero schedule
-    HIP_TRY(hipMalloc((void**)&c->d_active, sizeof(unsigned) * c->max_stages));
-    HIP_TRY(hipMemsetAsync(c->d_active, 0, sizeof(unsigned) * c->max_stages, c->stream));
-  }
+  bool fresh = false;
+  HIP_TRY(reserve_active(c, &fresh));
+  if (fresh) HIP_TRY(hipMemsetAsync(c->d_active.p, 0, sizeof(unsigned) * c->max_stages, c->stream));  // no contacts: an all-zero schedule
   rbd::UkArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.cost = c->d_cost;
-  a.x0 = c->d_x0;
-  a.dx0 = c->buf[RTOC_BUF_DX0];
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.cost = c->d_cost.p;
+  a.x0 = c->d_x0.p;
+  a.dx0 = c->buf[RTOC_BUF_DX0].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.nv = c->dims.nv;
@@ -2289,8 +2190,8 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   a.o_fx = c->L.kkt.off[RTOC_KKT_FX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_lu = c->L.kkt.off[RTOC_KKT_LU];
   a.o_qaa = c->L.cdd.off[RTOC_CDD_QAA], a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_mj = c->L.cdd.off[RTOC_CDD_MJTJINV];
   c->ls_unconstr_dt = dt;
-  if (c->ls_on && !c->d_costval) HIP_TRY(hipMalloc((void**)&c->d_costval, sizeof(double) * c->batch * c->max_stages));
-  a.cost_out = c->ls_on ? c->d_costval : nullptr;   // the line search's evalOCP (unconstr_line_search.cpp:56-83)
+  if (c->ls_on) HIP_TRY(reserve_costval(c));
+  a.cost_out = c->ls_on ? c->d_costval.p : nullptr;   // the line search's evalOCP (unconstr_line_search.cpp:56-83)
   hipLaunchKernelGGL(rbd::unconstr_eval_kkt_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fxx_state = 0;
@@ -2301,14 +2202,14 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
 
 // ---- KKT error ------------------------------------------------------------------------------
 static int launch_kkt_error(rtoc_ctx* c) {
-  if (!c->d_kkterr) HIP_TRY(hipMalloc((void**)&c->d_kkterr, sizeof(double) * c->batch * (size_t)(1 + c->max_stages)));
+  HIP_TRY(reserve_kkterr(c));
   KktErrArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON] : nullptr;
-  a.rows = c->d_rows;
-  a.grid = c->d_grid;
-  a.out = c->d_kkterr;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
+  a.rows = c->d_rows.p;
+  a.grid = c->d_grid.p;
+  a.out = c->d_kkterr.p;
   a.nstages = c->nstages;
   a.batch = c->batch;
   a.nrows = c->nrows;
@@ -2324,9 +2225,9 @@ static int launch_kkt_error(rtoc_ctx* c) {
   a.kl = c->L.kkt;
   a.cl = c->L.cdd;
   a.nl = c->L.con;
-  a.partial = c->d_kkterr + c->batch;
+  a.partial = c->d_kkterr.p + c->batch;
   hipLaunchKernelGGL(kkt_error_kernel, dim3(c->nstages, c->batch), dim3(64), 0, c->stream, a);
-  hipLaunchKernelGGL(kkt_error_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a.partial, c->d_kkterr,
+  hipLaunchKernelGGL(kkt_error_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a.partial, c->d_kkterr.p,
                      c->nstages, c->batch);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -2337,7 +2238,7 @@ int rtoc_kkt_error(rtoc_ctx* c, double* host_out, int count) {
   if (!host_out || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
   int rc = launch_kkt_error(c);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(host_out, c->d_kkterr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(host_out, c->d_kkterr.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2359,17 +2260,17 @@ int rtoc_set_friction_coefficients(rtoc_ctx* c, const double* mu, int ncontacts)
   for (int i = 0; i < ncontacts; ++i)
     if (!(mu[i] > 0.0)) return RTOC_ERR_BAD_ARG;   // ContactStatus::setFrictionCoefficient
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_mu) HIP_TRY(hipMalloc((void**)&c->d_mu, sizeof(double) * RTOC_MAX_CONTACTS));
+  HIP_TRY(c->d_mu.reserve(RTOC_MAX_CONTACTS));
   double full[RTOC_MAX_CONTACTS] = {0.0};
   memcpy(full, mu, sizeof(double) * ncontacts);
-  HIP_TRY(hipMemcpyAsync(c->d_mu, full, sizeof(full), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_mu.p, full, sizeof(full), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->n_mu = ncontacts;
   return RTOC_OK;
 }
 
-static bool device_cones_on(const rtoc_ctx* c) { return c->cone_contacts > 0 && c->cone_rows == RTOC_FRICTION_ROWS && c->d_mu != nullptr; }
-static bool device_wrench_on(const rtoc_ctx* c) { return c->cone_contacts > 0 && c->cone_rows == RTOC_WRENCH_ROWS && c->d_wcone != nullptr; }
+static bool device_cones_on(const rtoc_ctx* c) { return c->cone_contacts > 0 && c->cone_rows == RTOC_FRICTION_ROWS && c->d_mu.p != nullptr; }
+static bool device_wrench_on(const rtoc_ctx* c) { return c->cone_contacts > 0 && c->cone_rows == RTOC_WRENCH_ROWS && c->d_wcone.p != nullptr; }
 
 int rtoc_set_wrench_cone_params(rtoc_ctx* c, const double* xy_mu, int ncontacts) {
   if (!c || !xy_mu || ncontacts < 1 || ncontacts > RTOC_MAX_CONTACTS) return RTOC_ERR_BAD_ARG;
@@ -2379,8 +2280,8 @@ int rtoc_set_wrench_cone_params(rtoc_ctx* c, const double* xy_mu, int ncontacts)
     if (rc) return rc;
   }
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_wcone) HIP_TRY(hipMalloc((void**)&c->d_wcone, sizeof(double) * table.size()));
-  HIP_TRY(hipMemcpyAsync(c->d_wcone, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_wcone.reserve(table.size()));
+  HIP_TRY(hipMemcpyAsync(c->d_wcone.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2391,13 +2292,13 @@ static int launch_wrench_cones(rtoc_ctx* c, int mode) {
   for (int k = 0; k < m.ncontacts; ++k)
     if (m.contact_type[k] != RTOC_CONTACT_SURFACE) return RTOC_ERR_BAD_ARG;
   WcArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = c->buf[RTOC_BUF_CON];
-  a.cone = c->buf[RTOC_BUF_CONE];
-  a.table = c->d_wcone;
-  a.grid = c->d_grid;
-  a.active = c->d_active;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = c->buf[RTOC_BUF_CON].p;
+  a.cone = c->buf[RTOC_BUF_CONE].p;
+  a.table = c->d_wcone.p;
+  a.grid = c->d_grid.p;
+  a.active = c->d_active.p;
   a.nstages = c->nstages, a.batch = c->batch, a.ncontacts = m.ncontacts, a.mode = mode;
   a.row0 = c->dims.nc_max - RTOC_WRENCH_ROWS * c->cone_contacts, a.cone_stride = rtoc_wrench_cone_stride(c->cone_contacts);
   a.impact_cones = c->impact_cones;
@@ -2417,16 +2318,16 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
   for (int k = 0; k < m.ncontacts; ++k)
     if ((m.contact_type[k] == RTOC_CONTACT_SURFACE ? 6 : 3) != c->cone_dim) return RTOC_ERR_BAD_ARG;
   CcArgs a;
-  a.model = c->d_model;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = c->buf[RTOC_BUF_CON];
-  a.cone = c->buf[RTOC_BUF_CONE];
-  a.grid = c->d_grid;
-  a.active = c->d_active;
-  a.rotations = c->has_crot ? c->d_crot : nullptr;
-  a.mu = c->d_mu;
+  a.model = c->d_model.p;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = c->buf[RTOC_BUF_CON].p;
+  a.cone = c->buf[RTOC_BUF_CONE].p;
+  a.grid = c->d_grid.p;
+  a.active = c->d_active.p;
+  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
+  a.mu = c->d_mu.p;
   a.nstages = c->nstages, a.batch = c->batch, a.nv = m.nv, a.njoints = m.njoints, a.ncontacts = m.ncontacts;
   a.nlevels = c->h_model->nlevels, a.mode = mode;
   a.contact_dim = c->cone_dim, a.row0 = c->dims.nc_max - RTOC_FRICTION_ROWS * c->cone_contacts;
@@ -2437,10 +2338,10 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
   a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride, a.con_stride = c->L.con.stride;
   a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_f = c->L.sol.off[RTOC_SOL_F], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_lf = c->L.cdd.off[RTOC_CDD_LF];
   a.nl = c->L.con;
-  if (mode == CC_LINEARIZE && c->vals_fresh && c->d_vals) {   // kinematics already there: no tree walk (contact_cone_vals_kernel)
+  if (mode == CC_LINEARIZE && c->vals_fresh && c->d_vals.p) {   // kinematics already there: no tree walk (contact_cone_vals_kernel)
     CvArgs v;
     v.c = a;
-    v.vals = c->d_vals;
+    v.vals = c->d_vals.p;
     hipLaunchKernelGGL(contact_cone_vals_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, v);
     HIP_TRY(hipGetLastError());
     return RTOC_OK;
@@ -2456,13 +2357,13 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
 // the joint-limit rows (those with bounds on the device) and of the friction-cone rows (those with friction coefficients)
 int rtoc_contact_init_constraints(rtoc_ctx* c) {
   CHECK_READY(c);
-  if (!c->buf[RTOC_BUF_SOL] || !(c->barrier > 0.0)) return RTOC_ERR_NOT_READY;
-  const bool rows = c->nrows > 0 && c->d_bounds != nullptr, cones = device_cones_on(c), wrench = device_wrench_on(c);
+  if (!c->buf[RTOC_BUF_SOL].p || !(c->barrier > 0.0)) return RTOC_ERR_NOT_READY;
+  const bool rows = c->nrows > 0 && c->d_bounds.p != nullptr, cones = device_cones_on(c), wrench = device_wrench_on(c);
   if (!rows && !cones && !wrench) return RTOC_ERR_NOT_READY;
-  if ((cones || wrench) && (!c->h_model || !c->d_active)) return RTOC_ERR_NOT_READY;
+  if ((cones || wrench) && (!c->h_model || !c->d_active.p)) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CON);
   if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(c->buf[RTOC_BUF_CON], 0, sizeof(double) * c->count[RTOC_BUF_CON], c->stream));
+  HIP_TRY(hipMemsetAsync(c->buf[RTOC_BUF_CON].p, 0, sizeof(double) * c->want[RTOC_BUF_CON], c->stream));
   if (rows) rc = launch_ubox(c, UBOX_INIT, true);
   if (!rc && cones) rc = launch_contact_cones(c, CC_INIT);
   if (!rc && wrench) rc = launch_wrench_cones(c, CC_INIT);
@@ -2473,14 +2374,14 @@ int rtoc_contact_init_constraints(rtoc_ctx* c) {
 static int launch_switching_constraint(rtoc_ctx* c) {
   const rtoc_robot_model& m = c->h_model->m;
   SwLinArgs a;
-  a.model = c->d_model;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.grid = c->d_grid;
-  a.active = c->d_active;
-  a.positions = c->has_cpos ? c->d_cpos : nullptr;
-  a.rotations = c->has_crot ? c->d_crot : nullptr;
+  a.model = c->d_model.p;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.grid = c->d_grid.p;
+  a.active = c->d_active.p;
+  a.positions = c->has_cpos ? c->d_cpos.p : nullptr;
+  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
   a.nstages = c->nstages, a.batch = c->batch, a.nv = m.nv, a.nq = m.nq, a.njoints = m.njoints, a.ncontacts = m.ncontacts;
   a.nlevels = c->h_model->nlevels, a.floating = m.type[0] == RTOC_JOINT_FREE_FLYER, a.ns_max = c->dims.ns_max;
   a.exact_transport = c->exact_transport;
@@ -2489,7 +2390,7 @@ static int launch_switching_constraint(rtoc_ctx* c) {
   a.o_phix = c->L.kkt.off[RTOC_KKT_PHIX], a.o_phit = c->L.kkt.off[RTOC_KKT_PHIT], a.o_pres = c->L.kkt.off[RTOC_KKT_PRES];
   a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_hx = c->L.kkt.off[RTOC_KKT_HX], a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
   a.o_phia = c->L.cdd.off[RTOC_CDD_PHIA], a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_ha = c->L.cdd.off[RTOC_CDD_HA];
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   for (int i = 0; i < c->nstages; ++i)
     if (c->h_grid[i].switching_constraint && c->h_grid[i].dims > c->dims.ns_max) return RTOC_ERR_BAD_ARG;
   a.nsel = 0;
@@ -2532,9 +2433,8 @@ int rtoc_set_task_costs(rtoc_ctx* c, const rtoc_task_cost* terms, int nterms, in
   const size_t n = (size_t)nterms * (per_instance ? c->batch : 1);
   for (size_t i = 0; i < n; ++i)
     if (!task_cost_valid(terms[i], c->h_model->m.njoints)) return RTOC_ERR_BAD_ARG;
-  const size_t cap = sizeof(rtoc_task_cost) * RTOC_MAX_TASK_COSTS * c->batch;
-  if (!c->d_tasks) HIP_TRY(hipMalloc((void**)&c->d_tasks, cap));
-  HIP_TRY(hipMemcpyAsync(c->d_tasks, terms, sizeof(rtoc_task_cost) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c->d_tasks.reserve((size_t)RTOC_MAX_TASK_COSTS * c->batch));   // full capacity: later calls may set more terms
+  HIP_TRY(hipMemcpyAsync(c->d_tasks.p, terms, sizeof(rtoc_task_cost) * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->ntasks = nterms, c->tasks_per_instance = per_instance ? 1 : 0;
   c->epoch++;   // launch parameters baked into captured graphs
@@ -2544,23 +2444,20 @@ int rtoc_set_task_costs(rtoc_ctx* c, const rtoc_task_cost* terms, int nterms, in
 int rtoc_set_grid_times(rtoc_ctx* c, const double* t, int nstages) {
   if (!c || !t || nstages < 2 || nstages > c->max_stages) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_gt) {
-    HIP_TRY(hipMalloc((void**)&c->d_gt, sizeof(double) * c->max_stages));
-    c->epoch++;
-  }
-  if (!c->h_gt) c->h_gt = new (std::nothrow) std::vector<double>();
-  if (!c->h_gt) return RTOC_ERR_HIP;
-  c->h_gt->assign(t, t + nstages);
-  HIP_TRY(hipMemcpyAsync(c->d_gt, t, sizeof(double) * nstages, hipMemcpyHostToDevice, c->stream));
+  bool fresh = false;
+  HIP_TRY(c->d_gt.reserve(c->max_stages, &fresh));
+  if (fresh) c->epoch++;
+  c->h_gt.assign(t, t + nstages);
+  HIP_TRY(hipMemcpyAsync(c->d_gt.p, t, sizeof(double) * nstages, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
 
 // per-instance grid times of a switching-time problem: kept by sto_time_steps_kernel once this buffer exists
 static int ensure_grid_times_inst(rtoc_ctx* c) {
-  if (c->d_gt_inst) return RTOC_OK;
-  HIP_TRY(hipMalloc((void**)&c->d_gt_inst, sizeof(double) * c->batch * c->max_stages));
-  c->epoch++;   // sto_time_steps_kernel's arguments changed
+  bool fresh = false;
+  HIP_TRY(c->d_gt_inst.reserve((size_t)c->batch * c->max_stages, &fresh));
+  if (fresh) c->epoch++;   // sto_time_steps_kernel's arguments changed
   return RTOC_OK;
 }
 
@@ -2571,29 +2468,29 @@ int rtoc_get_grid_times(rtoc_ctx* c, double* host_out, int count) {
     int rc = ensure_grid_times_inst(c);
     if (rc) return rc;
     STO_LAUNCH(sto_time_steps_kernel, c);
-    HIP_TRY(hipMemcpyAsync(host_out, c->d_gt_inst, sizeof(double) * count * c->nstages, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, c->d_gt_inst.p, sizeof(double) * count * c->nstages, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RTOC_OK;
   }
-  if (!c->h_gt || (int)c->h_gt->size() != c->nstages) return RTOC_ERR_NOT_READY;
-  for (int b = 0; b < count; ++b) memcpy(host_out + (size_t)b * c->nstages, c->h_gt->data(), sizeof(double) * c->nstages);
+  if ((int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;
+  for (int b = 0; b < count; ++b) memcpy(host_out + (size_t)b * c->nstages, c->h_gt.data(), sizeof(double) * c->nstages);
   return RTOC_OK;
 }
 
 static int launch_task_costs(rtoc_ctx* c) {
-  if (!c->h_model || !c->d_model || !c->d_tasks) return RTOC_ERR_NOT_READY;
-  if (!c->sto_on && (!c->h_gt || (int)c->h_gt->size() != c->nstages)) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
-  if (c->sto_on && !c->d_gt_inst) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
+  if (!c->h_model || !c->d_model.p || !c->d_tasks.p) return RTOC_ERR_NOT_READY;
+  if (!c->sto_on && (int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
+  if (c->sto_on && !c->d_gt_inst.p) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
   TaskCostArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cost_out = c->d_costval;
-  a.grid = c->d_grid;
-  a.model = c->d_model;
-  a.terms = c->d_tasks;
-  a.t_fixed = c->sto_on ? nullptr : c->d_gt;
-  a.t_inst = c->sto_on ? c->d_gt_inst : nullptr;
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cost_out = c->d_costval.p;
+  a.grid = c->d_grid.p;
+  a.model = c->d_model.p;
+  a.terms = c->d_tasks.p;
+  a.t_fixed = c->sto_on ? nullptr : c->d_gt.p;
+  a.t_inst = c->sto_on ? c->d_gt_inst.p : nullptr;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
   a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.o_q = c->L.sol.off[RTOC_SOL_Q];
   a.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_hx = c->L.kkt.off[RTOC_KKT_HX];
@@ -2613,7 +2510,7 @@ static int launch_task_costs(rtoc_ctx* c) {
 
 int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   CHECK_READY(c);
-  if (!c->h_model || !c->d_active || !c->d_cost || !c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+  if (!c->h_model || !c->d_active.p || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   bool switching = false;
   for (int i = 0; i < c->nstages; ++i) switching = switching || c->h_grid[i].switching_constraint;
   int rc = ensure_buffer(c, RTOC_BUF_KKT);
@@ -2627,27 +2524,27 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   }
   // PhaseBased discretisation: time_discretization_.correctTimeSteps(contact_sequence_, t) ahead of evalKKT (ocp_solver.cpp:115-117)
   if (c->sto_on) STO_LAUNCH(sto_time_steps_kernel, c);
-  if (!c->d_costval) HIP_TRY(hipMalloc((void**)&c->d_costval, sizeof(double) * c->batch * c->max_stages));
+  HIP_TRY(reserve_costval(c));
   CostArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL];
-  a.cost = c->d_cost;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.grid = c->d_grid;
+  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.cost = c->d_cost.p;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.grid = c->d_grid.p;
   a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.nu = c->dims.nu;
   a.nf_max = c->dims.nf_max, a.ns_max = c->dims.ns_max, a.floating = c->dims.np == 6;
   a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
   a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A], a.o_u = c->L.sol.off[RTOC_SOL_U];
   a.kl = c->L.kkt, a.cl = c->L.cdd;
-  a.dt_inst = c->sto_on ? c->d_dt : nullptr;
-  a.cost_out = c->d_costval;
+  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
+  a.cost_out = c->d_costval.p;
   {
     // setZero of the KKT records (+ the constant diagonals of the cost) as one stream on the context's second stream (rtoc_riccati_sweep's), BESIDE
     // the values pre-pass of the rigid-body linearisation (lanes = bodies; writes its scratch and RTOC_CDD_IDC, which nothing
     // here zeroes): the one is bound by HBM writes, the other by latency -- 1.1 ms each per 4096 x 47 grid points, one after the
     // other on one stream.  The cost kernel and everything behind it wait for both.
     InitArgs ia;
-    ia.kkt = c->buf[RTOC_BUF_KKT], ia.cost = c->d_cost, ia.grid = c->d_grid, ia.dt_inst = a.dt_inst;
+    ia.kkt = c->buf[RTOC_BUF_KKT].p, ia.cost = c->d_cost.p, ia.grid = c->d_grid.p, ia.dt_inst = a.dt_inst;
     ia.nstages = c->nstages, ia.batch = c->batch, ia.nv = c->dims.nv, ia.nu = c->dims.nu, ia.floating = a.floating;
     ia.kkt_stride = c->L.kkt.stride, ia.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], ia.o_quu = c->L.kkt.off[RTOC_KKT_QUU], ia.o_fxx = c->L.kkt.off[RTOC_KKT_FXX];
     const long long nrec = (long long)c->batch * c->nstages;
@@ -2691,9 +2588,9 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
     }
   }
   // constraints_->linearizeConstraints (intermediate_stage.cpp:109-110, impact_stage.cpp:95-96) of the rows evaluated here
-  if (c->nrows > 0 && c->d_bounds && c->buf[RTOC_BUF_CON]) rc = launch_ubox(c, UBOX_LINEARIZE, true);
-  if (!rc && device_cones_on(c) && c->buf[RTOC_BUF_CON]) rc = launch_contact_cones(c, CC_LINEARIZE);
-  if (!rc && device_wrench_on(c) && c->buf[RTOC_BUF_CON]) rc = launch_wrench_cones(c, CC_LINEARIZE);
+  if (c->nrows > 0 && c->d_bounds.p && c->buf[RTOC_BUF_CON].p) rc = launch_ubox(c, UBOX_LINEARIZE, true);
+  if (!rc && device_cones_on(c) && c->buf[RTOC_BUF_CON].p) rc = launch_contact_cones(c, CC_LINEARIZE);
+  if (!rc && device_wrench_on(c) && c->buf[RTOC_BUF_CON].p) rc = launch_wrench_cones(c, CC_LINEARIZE);
   if (!rc) rc = launch_state_equation(c, true);
   if (!rc) rc = launch_linearize(c, 1, false, 1.0);
   if (!rc && switching) rc = launch_switching_constraint(c);
@@ -2746,7 +2643,7 @@ int rtoc_contact_update_solution(rtoc_ctx* c, double tau, double* host_kkt_error
   if (!rc) rc = rtoc_newton_iteration(c, 0.0, tau);  // KKT error, condensation, sweep, expansion, steps, update, integrate
   if (rc) return rc;
   if (count > 0) {
-    HIP_TRY(hipMemcpyAsync(host_kkt_error, c->d_kkterr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_kkt_error, c->d_kkterr.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return RTOC_OK;
@@ -2765,7 +2662,7 @@ int rtoc_unconstr_update_solution(rtoc_ctx* c, double dt, double* host_kkt_error
   if (!rc) rc = launch_kkt_error(c);                  // performance_index.kkt_error (pre-condensation, like :74-75)
   if (!rc && c->ls_on) {                              // dms_.getEval() of the iterate: what UnconstrLineSearch::computeStepSize reads first
     rc = ensure_line_search(c);
-    if (!rc) rc = launch_eval_ocp(c, c->d_eval);
+    if (!rc) rc = launch_eval_ocp(c, c->d_eval.p);
   }
   if (!rc && rows) rc = launch_ubox(c, UBOX_CONDENSE);  // constraints_->condenseSlackAndDual (:76-77), ahead of the dynamics
   if (!rc) rc = rtoc_unconstr_condense(c);
@@ -2775,7 +2672,7 @@ int rtoc_unconstr_update_solution(rtoc_ctx* c, double dt, double* host_kkt_error
   if (rc) return rc;
   rc = ensure_buffer(c, RTOC_BUF_STEP);
   if (rc) return rc;
-  hipLaunchKernelGGL(fill_steps_kernel, dim3((2 * c->batch + 255) / 256), dim3(256), 0, c->stream, c->buf[RTOC_BUF_STEP], 2 * c->batch);
+  hipLaunchKernelGGL(fill_steps_kernel, dim3((2 * c->batch + 255) / 256), dim3(256), 0, c->stream, c->buf[RTOC_BUF_STEP].p, 2 * c->batch);
   HIP_TRY(hipGetLastError());
   if (rows) rc = launch_ubox(c, UBOX_EXPAND);         // expandSlackAndDual + maxSlack/DualStepSize (:80-97)
   // line_search_.computeStepSize (unconstr_ocp_solver.cpp:107-111, unconstr_line_search.cpp:37-67): the filter's backtracking loop of
@@ -2786,7 +2683,7 @@ int rtoc_unconstr_update_solution(rtoc_ctx* c, double dt, double* host_kkt_error
   rc = rtoc_integrate_solution(c);
   if (rc) return rc;
   if (count > 0) {
-    HIP_TRY(hipMemcpyAsync(host_kkt_error, c->d_kkterr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_kkt_error, c->d_kkterr.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return RTOC_OK;
@@ -2797,22 +2694,17 @@ int rtoc_sto_eval_kkt(rtoc_ctx* c, const double* host_lt, const double* host_qtt
   CHECK_READY(c);
   if (nev < 0 || nev > 31 || count < 0 || count > c->batch || (nev > 0 && (!host_lt || !host_qtt))) return RTOC_ERR_BAD_ARG;
   const size_t n = (size_t)c->batch * (nev > 0 ? nev : 1);
-  if (c->sto_cap < n) {
-    if (c->d_sto) (void)hipFree(c->d_sto);
-    c->d_sto = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_sto, (2 * n + c->batch) * sizeof(double)));
-    c->sto_cap = n;
-  }
-  double* d_lt = c->d_sto;
-  double* d_qtt = c->d_sto + n;
-  double* d_err = c->d_sto + 2 * n;
+  HIP_TRY(c->d_sto.grow(2 * n + c->batch));
+  double* d_lt = c->d_sto.p;
+  double* d_qtt = c->d_sto.p + n;
+  double* d_err = c->d_sto.p + 2 * n;
   if (nev > 0) {
     HIP_TRY(hipMemcpyAsync(d_lt, host_lt, (size_t)c->batch * nev * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_qtt, host_qtt, (size_t)c->batch * nev * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
   StoArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.grid = c->d_grid;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.grid = c->d_grid.p;
   a.lt = d_lt;
   a.qtt = d_qtt;
   a.err = d_err;
@@ -2840,7 +2732,7 @@ int rtoc_sto_set_problem(rtoc_ctx* c, double t0, double T, const double* event_t
   }
   if (num_events < 0 || num_events > RTOC_STO_MAX_EVENTS || !event_times || !min_dwell_times || !(T > 0.0)) return RTOC_ERR_BAD_ARG;
   if (!(barrier_param > 0.0) || !(fraction_to_boundary_rule > 0.0) || !(fraction_to_boundary_rule < 1.0)) return RTOC_ERR_BAD_ARG;  // sto_constraints.cpp:44-59
-  if (!c->h_grid || num_events != sto_count_events(c)) return RTOC_ERR_BAD_ARG;
+  if (c->h_grid.empty() || num_events != sto_count_events(c)) return RTOC_ERR_BAD_ARG;
   for (int p = 0; p <= num_events; ++p)
     if (!(min_dwell_times[p] >= 0.0)) return RTOC_ERR_BAD_ARG;  // :38-43
   const size_t ne = (size_t)c->batch * num_events;
@@ -2852,21 +2744,18 @@ int rtoc_sto_set_problem(rtoc_ctx* c, double t0, double T, const double* event_t
       if (!(te > prev) || !(te < t0 + T)) return RTOC_ERR_BAD_ARG;  // events ordered, inside the horizon
       ts[(size_t)b * num_events + e] = te;
     }
-  if (c->sto_nev != num_events) {
-    for (double** p : {&c->d_ts, &c->d_sto_cost, &c->d_sto_out})
-      if (*p) (void)hipFree(*p), *p = nullptr;
-  }
-  if (!c->d_ts) HIP_TRY(hipMalloc((void**)&c->d_ts, sizeof(double) * ne));
-  if (!c->d_sto_out) HIP_TRY(hipMalloc((void**)&c->d_sto_out, sizeof(double) * (2 * ne + c->batch)));
-  if (!c->d_dt) HIP_TRY(hipMalloc((void**)&c->d_dt, sizeof(double) * c->batch * c->max_stages));
-  if (!c->d_sto_con) HIP_TRY(hipMalloc((void**)&c->d_sto_con, sizeof(double) * c->batch * RTOC_STO_CON_STRIDE));
-  if (!c->d_min_dwell) HIP_TRY(hipMalloc((void**)&c->d_min_dwell, sizeof(double) * (RTOC_STO_MAX_EVENTS + 1)));
-  if (!c->d_kkterr) HIP_TRY(hipMalloc((void**)&c->d_kkterr, sizeof(double) * c->batch * (size_t)(1 + c->max_stages)));
+  if (c->sto_nev != num_events) c->d_sto_cost.release();   // (d_ts and d_sto_out are resized below)
+  HIP_TRY(c->d_ts.reserve(ne));
+  HIP_TRY(c->d_sto_out.reserve(2 * ne + c->batch));
+  HIP_TRY(c->d_dt.reserve((size_t)c->batch * c->max_stages));
+  HIP_TRY(c->d_sto_con.reserve((size_t)c->batch * RTOC_STO_CON_STRIDE));
+  HIP_TRY(c->d_min_dwell.reserve(RTOC_STO_MAX_EVENTS + 1));
+  HIP_TRY(reserve_kkterr(c));
   int rc = ensure_buffer(c, RTOC_BUF_STEP);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_ts, ts.data(), sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_min_dwell, min_dwell_times, sizeof(double) * (num_events + 1), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_sto_con, 0, sizeof(double) * c->batch * RTOC_STO_CON_STRIDE, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_ts.p, ts.data(), sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_min_dwell.p, min_dwell_times, sizeof(double) * (num_events + 1), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_sto_con.p, 0, sizeof(double) * c->batch * RTOC_STO_CON_STRIDE, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->sto_on = 1, c->sto_nev = num_events, c->sto_t0 = t0, c->sto_T = T;
   c->sto_barrier = barrier_param, c->sto_tau = fraction_to_boundary_rule;
@@ -2887,17 +2776,15 @@ int rtoc_sto_set_cost_terms(rtoc_ctx* c, const double* lt, const double* qtt_dia
   if (!c->sto_on || (!lt) != (!qtt_diag)) return RTOC_ERR_BAD_ARG;
   const size_t ne = (size_t)c->batch * c->sto_nev;
   if (!lt) {
-    if (c->d_sto_cost) (void)hipFree(c->d_sto_cost);
-    c->d_sto_cost = nullptr;
+    c->d_sto_cost.release();
     c->epoch++;
     return RTOC_OK;
   }
-  if (!c->d_sto_cost) {
-    HIP_TRY(hipMalloc((void**)&c->d_sto_cost, sizeof(double) * 2 * ne));
-    c->epoch++;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_sto_cost, lt, sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_sto_cost + ne, qtt_diag, sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
+  bool fresh = false;
+  HIP_TRY(c->d_sto_cost.reserve(2 * ne, &fresh));
+  if (fresh) c->epoch++;
+  HIP_TRY(hipMemcpyAsync(c->d_sto_cost.p, lt, sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_sto_cost.p + ne, qtt_diag, sizeof(double) * ne, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2922,7 +2809,7 @@ int rtoc_sto_set_slack_dual(rtoc_ctx* c, const double* slack, const double* dual
       h[(size_t)b * RTOC_STO_CON_STRIDE + 0 * NP + p] = slack[(size_t)b * np + p];
       h[(size_t)b * RTOC_STO_CON_STRIDE + 1 * NP + p] = dual[(size_t)b * np + p];
     }
-  HIP_TRY(hipMemcpyAsync(c->d_sto_con, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_sto_con.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -2943,24 +2830,24 @@ static int sto_download(rtoc_ctx* c, const double* src, size_t per, double* host
 }
 int rtoc_sto_get_event_times(rtoc_ctx* c, double* host_out, int count) {
   CHECK_READY(c);
-  return sto_download(c, c->d_ts, c->sto_nev, host_out, count);
+  return sto_download(c, c->d_ts.p, c->sto_nev, host_out, count);
 }
 int rtoc_sto_get_time_steps(rtoc_ctx* c, double* host_out, int count) {
   CHECK_READY(c);
-  return sto_download(c, c->d_dt, c->nstages, host_out, count);
+  return sto_download(c, c->d_dt.p, c->nstages, host_out, count);
 }
 int rtoc_sto_get_constraint_data(rtoc_ctx* c, double* host_out, int count) {
   CHECK_READY(c);
-  return sto_download(c, c->d_sto_con, RTOC_STO_CON_STRIDE, host_out, count);
+  return sto_download(c, c->d_sto_con.p, RTOC_STO_CON_STRIDE, host_out, count);
 }
 int rtoc_sto_get_kkt_terms(rtoc_ctx* c, double* host_lt, double* host_qtt, double* host_err_sq, int count) {
   CHECK_READY(c);
   if (!c->sto_on) return RTOC_ERR_NOT_READY;
   const size_t ne = (size_t)c->batch * c->sto_nev;
   int rc = RTOC_OK;
-  if (host_lt) rc = sto_download(c, c->d_sto_out, c->sto_nev, host_lt, count);
-  if (!rc && host_qtt) rc = sto_download(c, c->d_sto_out + ne, c->sto_nev, host_qtt, count);
-  if (!rc && host_err_sq) rc = sto_download(c, c->d_sto_out + 2 * ne, 1, host_err_sq, count);
+  if (host_lt) rc = sto_download(c, c->d_sto_out.p, c->sto_nev, host_lt, count);
+  if (!rc && host_qtt) rc = sto_download(c, c->d_sto_out.p + ne, c->sto_nev, host_qtt, count);
+  if (!rc && host_err_sq) rc = sto_download(c, c->d_sto_out.p + 2 * ne, 1, host_err_sq, count);
   return rc;
 }
 
@@ -2987,12 +2874,12 @@ int rtoc_sto_integrate_solution(rtoc_ctx* c) {
 
 // ---- filter line search (line_search_filter.cpp), batched ---------------------------------------
 static int ensure_filter(rtoc_ctx* c) {
-  if (c->d_filter) return RTOC_OK;
-  HIP_TRY(hipMalloc((void**)&c->d_filter, sizeof(double) * 2 * RTOC_LINE_SEARCH_FILTER_CAPACITY * c->batch));
-  HIP_TRY(hipMalloc((void**)&c->d_nfilter, sizeof(int) * c->batch));
-  HIP_TRY(hipMalloc((void**)&c->d_ls_in, sizeof(double) * 2 * c->batch));
-  HIP_TRY(hipMalloc((void**)&c->d_ls_flags, sizeof(int) * 2 * c->batch));
-  HIP_TRY(hipMemsetAsync(c->d_nfilter, 0, sizeof(int) * c->batch, c->stream));
+  if (c->d_filter.p) return RTOC_OK;
+  HIP_TRY(c->d_filter.reserve((size_t)2 * RTOC_LINE_SEARCH_FILTER_CAPACITY * c->batch));
+  HIP_TRY(c->d_nfilter.reserve(c->batch));
+  HIP_TRY(c->d_ls_in.reserve((size_t)2 * c->batch));
+  HIP_TRY(c->d_ls_flags.reserve((size_t)2 * c->batch));
+  HIP_TRY(hipMemsetAsync(c->d_nfilter.p, 0, sizeof(int) * c->batch, c->stream));
   return RTOC_OK;
 }
 
@@ -3001,7 +2888,7 @@ int rtoc_line_search_clear(rtoc_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = ensure_filter(c);
   if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(c->d_nfilter, 0, sizeof(int) * c->batch, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_nfilter.p, 0, sizeof(int) * c->batch, c->stream));
   return RTOC_OK;
 }
 
@@ -3013,16 +2900,16 @@ int rtoc_line_search_filter(rtoc_ctx* c, const double* cost, const double* viola
   int rc = ensure_filter(c);
   if (rc) return rc;
   if (count == 0) return RTOC_OK;
-  HIP_TRY(hipMemcpyAsync(c->d_ls_in, cost, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_ls_in + c->batch, violation, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(c->d_ls_flags, mask, sizeof(int) * count, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_ls_in.p, cost, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_ls_in.p + c->batch, violation, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+  if (mask) HIP_TRY(hipMemcpyAsync(c->d_ls_flags.p, mask, sizeof(int) * count, hipMemcpyHostToDevice, c->stream));
   FilterArgs a;
-  a.filt = c->d_filter;
-  a.nfilt = c->d_nfilter;
-  a.cost = c->d_ls_in;
-  a.viol = c->d_ls_in + c->batch;
-  a.mask = mask ? c->d_ls_flags : nullptr;
-  a.accepted = c->d_ls_flags + c->batch;
+  a.filt = c->d_filter.p;
+  a.nfilt = c->d_nfilter.p;
+  a.cost = c->d_ls_in.p;
+  a.viol = c->d_ls_in.p + c->batch;
+  a.mask = mask ? c->d_ls_flags.p : nullptr;
+  a.accepted = c->d_ls_flags.p + c->batch;
   a.count = count;
   a.cap = RTOC_LINE_SEARCH_FILTER_CAPACITY;
   a.cost_rate = cost_rate;
@@ -3030,7 +2917,7 @@ int rtoc_line_search_filter(rtoc_ctx* c, const double* cost, const double* viola
   a.seed_empty = 0;
   hipLaunchKernelGGL(line_search_filter_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(accepted, c->d_ls_flags + c->batch, sizeof(int) * count, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(accepted, c->d_ls_flags.p + c->batch, sizeof(int) * count, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -3039,26 +2926,26 @@ int rtoc_line_search_filter(rtoc_ctx* c, const double* cost, const double* viola
 static int ensure_line_search(rtoc_ctx* c) {
   int rc = ensure_filter(c);
   if (rc) return rc;
-  if (!c->d_eval) HIP_TRY(hipMalloc((void**)&c->d_eval, sizeof(double) * 4 * c->batch));
-  if (!c->d_eval_part) HIP_TRY(hipMalloc((void**)&c->d_eval_part, sizeof(double) * 2 * c->batch * c->max_stages));
-  if (!c->d_ls_steps) HIP_TRY(hipMalloc((void**)&c->d_ls_steps, sizeof(double) * 3 * c->batch));
-  if (!c->d_ls_active) HIP_TRY(hipMalloc((void**)&c->d_ls_active, sizeof(int) * (c->batch + 1)));
-  if (!c->d_ls_merit) HIP_TRY(hipMalloc((void**)&c->d_ls_merit, sizeof(double) * 2 * c->batch));
+  HIP_TRY(c->d_eval.reserve((size_t)4 * c->batch));
+  HIP_TRY(c->d_eval_part.reserve((size_t)2 * c->batch * c->max_stages));
+  HIP_TRY(c->d_ls_steps.reserve((size_t)3 * c->batch));
+  HIP_TRY(c->d_ls_active.reserve((size_t)c->batch + 1));
+  HIP_TRY(c->d_ls_merit.reserve((size_t)2 * c->batch));
   return RTOC_OK;
 }
 
 // (cost + cost_barrier | primal_feasibility) of every instance from the records rtoc_contact_eval_kkt has just written
 // (pre-condensation) into out[2][batch]
 static int launch_eval_ocp(rtoc_ctx* c, double* out) {
-  if (!c->d_costval || !c->buf[RTOC_BUF_KKT] || !c->buf[RTOC_BUF_CDD]) return RTOC_ERR_NOT_READY;
+  if (!c->d_costval.p || !c->buf[RTOC_BUF_KKT].p || !c->buf[RTOC_BUF_CDD].p) return RTOC_ERR_NOT_READY;
   EvalOcpArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT];
-  a.cdd = c->buf[RTOC_BUF_CDD];
-  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON] : nullptr;
-  a.costval = c->d_costval;
-  a.rows = c->d_rows;
-  a.grid = c->d_grid;
-  a.partial = c->d_eval_part;
+  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
+  a.costval = c->d_costval.p;
+  a.rows = c->d_rows.p;
+  a.grid = c->d_grid.p;
+  a.partial = c->d_eval_part.p;
   a.nstages = c->nstages, a.batch = c->batch, a.nrows = c->nrows;
   a.cone_contacts = c->cone_contacts, a.cone_dim = c->cone_dim > 0 ? c->cone_dim : 3, a.cone_rows = c->cone_rows;
   a.nc_max = c->dims.nc_max, a.impact_cones = c->impact_cones;
@@ -3066,7 +2953,7 @@ static int launch_eval_ocp(rtoc_ctx* c, double* out) {
   a.barrier = c->barrier;
   a.kl = c->L.kkt, a.cl = c->L.cdd, a.nl = c->L.con;
   hipLaunchKernelGGL(eval_ocp_kernel, dim3(c->nstages, c->batch), dim3(64), 0, c->stream, a);
-  hipLaunchKernelGGL(eval_ocp_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, c->d_eval_part, out, c->nstages, c->batch);
+  hipLaunchKernelGGL(eval_ocp_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, c->d_eval_part.p, out, c->nstages, c->batch);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -3089,23 +2976,23 @@ int rtoc_set_line_search(rtoc_ctx* c, int enable, double step_size_reduction_rat
 // by step x dslack, step = the primal entry of RTOC_BUF_STEP of every instance; RTOC_BUF_SOL / CON / DIR / STEP keep their
 // contents, the KKT / CDD records are overwritten (the next rtoc_contact_eval_kkt rewrites them anyway).
 static int eval_ocp_trial(rtoc_ctx* c, const double* steps, double* out) {
-  const size_t nsol = c->count[RTOC_BUF_SOL], ncon = c->count[RTOC_BUF_CON];
-  const bool has_con = c->buf[RTOC_BUF_CON] != nullptr;
-  if (!c->d_sol_trial) HIP_TRY(hipMalloc((void**)&c->d_sol_trial, sizeof(double) * nsol));
-  if (has_con && !c->d_con_trial) HIP_TRY(hipMalloc((void**)&c->d_con_trial, sizeof(double) * ncon));
-  HIP_TRY(hipMemcpyAsync(c->d_sol_trial, c->buf[RTOC_BUF_SOL], sizeof(double) * nsol, hipMemcpyDeviceToDevice, c->stream));
-  if (has_con) HIP_TRY(hipMemcpyAsync(c->d_con_trial, c->buf[RTOC_BUF_CON], sizeof(double) * ncon, hipMemcpyDeviceToDevice, c->stream));
-  double* const sol = c->buf[RTOC_BUF_SOL];
-  double* const con = c->buf[RTOC_BUF_CON];
-  double* const stp = c->buf[RTOC_BUF_STEP];
-  c->buf[RTOC_BUF_SOL] = c->d_sol_trial;
-  if (has_con) c->buf[RTOC_BUF_CON] = c->d_con_trial;
-  c->buf[RTOC_BUF_STEP] = const_cast<double*>(steps);
+  const size_t nsol = c->want[RTOC_BUF_SOL], ncon = c->want[RTOC_BUF_CON];
+  const bool has_con = c->buf[RTOC_BUF_CON].p != nullptr;
+  HIP_TRY(c->d_sol_trial.reserve(nsol));
+  if (has_con) HIP_TRY(c->d_con_trial.reserve(ncon));
+  HIP_TRY(hipMemcpyAsync(c->d_sol_trial.p, c->buf[RTOC_BUF_SOL].p, sizeof(double) * nsol, hipMemcpyDeviceToDevice, c->stream));
+  if (has_con) HIP_TRY(hipMemcpyAsync(c->d_con_trial.p, c->buf[RTOC_BUF_CON].p, sizeof(double) * ncon, hipMemcpyDeviceToDevice, c->stream));
+  double* const sol = c->buf[RTOC_BUF_SOL].p;
+  double* const con = c->buf[RTOC_BUF_CON].p;
+  double* const stp = c->buf[RTOC_BUF_STEP].p;
+  c->buf[RTOC_BUF_SOL].p = c->d_sol_trial.p;
+  if (has_con) c->buf[RTOC_BUF_CON].p = c->d_con_trial.p;
+  c->buf[RTOC_BUF_STEP].p = const_cast<double*>(steps);
   int rc = rtoc_update(c);                       // slack += step dslack (dual step 0)
   if (!rc) rc = rtoc_integrate_solution(c);      // SplitSolution::integrate with the trial step
   if (!rc) rc = c->ls_unconstr_dt > 0.0 ? rtoc_unconstr_eval_kkt(c, c->ls_unconstr_dt) : rtoc_contact_eval_kkt(c);   // evalOCP's quantities (and, unused here, the derivatives)
   if (!rc) rc = launch_eval_ocp(c, out);
-  c->buf[RTOC_BUF_SOL] = sol, c->buf[RTOC_BUF_CON] = con, c->buf[RTOC_BUF_STEP] = stp;
+  c->buf[RTOC_BUF_SOL].p = sol, c->buf[RTOC_BUF_CON].p = con, c->buf[RTOC_BUF_STEP].p = stp;
   c->vals_fresh = 0;
   c->fxx_state = 0;
   return rc;
@@ -3116,8 +3003,8 @@ int rtoc_contact_eval_ocp(rtoc_ctx* c, int trial, double* host_cost, double* hos
   if (count < 0 || count > c->batch || (count > 0 && (!host_cost || !host_violation))) return RTOC_ERR_BAD_ARG;
   int rc = ensure_line_search(c);
   if (rc) return rc;
-  double* out = c->d_eval + (trial ? 2 * c->batch : 0);
-  rc = trial ? eval_ocp_trial(c, c->buf[RTOC_BUF_STEP], out) : launch_eval_ocp(c, out);
+  double* out = c->d_eval.p + (trial ? 2 * c->batch : 0);
+  rc = trial ? eval_ocp_trial(c, c->buf[RTOC_BUF_STEP].p, out) : launch_eval_ocp(c, out);
   if (rc) return rc;
   if (count > 0) {
     HIP_TRY(hipMemcpyAsync(host_cost, out, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
@@ -3129,10 +3016,10 @@ int rtoc_contact_eval_ocp(rtoc_ctx* c, int trial, double* host_cost, double* hos
 
 static int launch_filter_device(rtoc_ctx* c, const double* eval, const int* mask, int seed_empty) {
   FilterArgs a;
-  a.filt = c->d_filter, a.nfilt = c->d_nfilter;
+  a.filt = c->d_filter.p, a.nfilt = c->d_nfilter.p;
   a.cost = eval, a.viol = eval + c->batch;
   a.mask = mask;
-  a.accepted = c->d_ls_flags + c->batch;
+  a.accepted = c->d_ls_flags.p + c->batch;
   a.count = c->batch, a.cap = RTOC_LINE_SEARCH_FILTER_CAPACITY;
   a.cost_rate = c->ls_cost_rate, a.viol_rate = c->ls_viol_rate;
   a.seed_empty = seed_empty;
@@ -3162,10 +3049,10 @@ int rtoc_line_search_trials(rtoc_ctx* c, int* trials) {
 
 int rtoc_line_search_merit_terms(rtoc_ctx* c, double* host_penalty, double* host_directional_derivative, int count) {
   CHECK_READY(c);
-  if (count < 0 || count > c->batch || !c->d_ls_merit) return RTOC_ERR_BAD_ARG;
-  if (host_penalty) HIP_TRY(hipMemcpyAsync(host_penalty, c->d_ls_merit, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+  if (count < 0 || count > c->batch || !c->d_ls_merit.p) return RTOC_ERR_BAD_ARG;
+  if (host_penalty) HIP_TRY(hipMemcpyAsync(host_penalty, c->d_ls_merit.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
   if (host_directional_derivative)
-    HIP_TRY(hipMemcpyAsync(host_directional_derivative, c->d_ls_merit + c->batch, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(host_directional_derivative, c->d_ls_merit.p + c->batch, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -3180,34 +3067,34 @@ int rtoc_contact_line_search(rtoc_ctx* c, int* host_trials) {
   const bool merit = c->ls_method == 1 && !(c->ls_unconstr_dt > 0.0);
   LsMeritArgs ma;
   if (!merit) {
-    rc = launch_filter_device(c, c->d_eval, nullptr, 1);   // an empty filter is seeded with the current iterate (:58-62)
+    rc = launch_filter_device(c, c->d_eval.p, nullptr, 1);   // an empty filter is seeded with the current iterate (:58-62)
     if (rc) return rc;
   } else {
     // meritBacktrackingLineSearch (:87-109): penalty parameter from the multipliers of the iterate, directional derivative of the
     // merit function from ONE more trial at step eps for every instance
-    if (!c->buf[RTOC_BUF_SOL]) return RTOC_ERR_NOT_READY;
+    if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
     LsPenaltyArgs pa;
-    pa.sol = c->buf[RTOC_BUF_SOL], pa.grid = c->d_grid, pa.penalty = c->d_ls_merit;
+    pa.sol = c->buf[RTOC_BUF_SOL].p, pa.grid = c->d_grid.p, pa.penalty = c->d_ls_merit.p;
     pa.nstages = c->nstages, pa.batch = c->batch, pa.nv = c->dims.nv, pa.np = c->dims.np, pa.sl = c->L.sol, pa.margin = c->ls_margin;
     hipLaunchKernelGGL(ls_penalty_kernel, dim3(c->batch), dim3(64), 0, c->stream, pa);
-    ma.cur = c->d_eval, ma.trial = c->d_eval + 2 * c->batch, ma.penalty = c->d_ls_merit, ma.dd = c->d_ls_merit + c->batch;
-    ma.trial_steps = c->d_ls_steps, ma.alpha = c->d_ls_steps + 2 * c->batch, ma.active = c->d_ls_active, ma.accepted = c->d_ls_flags + c->batch;
+    ma.cur = c->d_eval.p, ma.trial = c->d_eval.p + 2 * c->batch, ma.penalty = c->d_ls_merit.p, ma.dd = c->d_ls_merit.p + c->batch;
+    ma.trial_steps = c->d_ls_steps.p, ma.alpha = c->d_ls_steps.p + 2 * c->batch, ma.active = c->d_ls_active.p, ma.accepted = c->d_ls_flags.p + c->batch;
     ma.batch = c->batch, ma.eps = c->ls_eps, ma.armijo = c->ls_armijo;
     ma.phase = 0;
     hipLaunchKernelGGL(ls_merit_kernel, dim3((c->batch + 255) / 256), dim3(256), 0, c->stream, ma);
-    rc = eval_ocp_trial(c, c->d_ls_steps, c->d_eval + 2 * c->batch);
+    rc = eval_ocp_trial(c, c->d_ls_steps.p, c->d_eval.p + 2 * c->batch);
     if (rc) return rc;
     ma.phase = 1;
     hipLaunchKernelGGL(ls_merit_kernel, dim3((c->batch + 255) / 256), dim3(256), 0, c->stream, ma);
     HIP_TRY(hipGetLastError());
   }
   LsArgs a;
-  a.steps = c->buf[RTOC_BUF_STEP];
-  a.trial_steps = c->d_ls_steps;
-  a.alpha = c->d_ls_steps + 2 * c->batch;
-  a.active = c->d_ls_active;
-  a.accepted = c->d_ls_flags + c->batch;
-  a.nactive = c->d_ls_active + c->batch;
+  a.steps = c->buf[RTOC_BUF_STEP].p;
+  a.trial_steps = c->d_ls_steps.p;
+  a.alpha = c->d_ls_steps.p + 2 * c->batch;
+  a.active = c->d_ls_active.p;
+  a.accepted = c->d_ls_flags.p + c->batch;
+  a.nactive = c->d_ls_active.p + c->batch;
   a.batch = c->batch;
   a.rate = c->ls_rate, a.min_step = c->ls_min_step;
   const dim3 grid((c->batch + 255) / 256), block(256);
@@ -3220,10 +3107,10 @@ int rtoc_contact_line_search(rtoc_ctx* c, int* host_trials) {
   // log(min_step) / log(rate) reductions from a full step; the bound only guards against a loop that never drains
   const int max_trials = (int)ceil(log(c->ls_min_step < 1.0 ? c->ls_min_step : 1.0) / log(c->ls_rate)) + 2;
   while (nactive > 0 && trials < max_trials + (merit ? 1 : 0)) {
-    rc = eval_ocp_trial(c, c->d_ls_steps, c->d_eval + 2 * c->batch);
+    rc = eval_ocp_trial(c, c->d_ls_steps.p, c->d_eval.p + 2 * c->batch);
     if (rc) return rc;
     if (!merit) {
-      rc = launch_filter_device(c, c->d_eval + 2 * c->batch, c->d_ls_active, 0);   // isAccepted + augment of the active instances
+      rc = launch_filter_device(c, c->d_eval.p + 2 * c->batch, c->d_ls_active.p, 0);   // isAccepted + augment of the active instances
       if (rc) return rc;
     } else {
       ma.phase = 2;   // armijoCondition of the active instances
@@ -3255,9 +3142,9 @@ __global__ void mask_converged_kernel(double* steps, const double* kkterr, int* 
 }
 
 static int newton_iteration_body(rtoc_ctx* c, const BwdPlan& p, double kkt_tol, double tau) {
-  HIP_TRY(hipMemsetAsync(c->d_nconv, 0, sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_nconv.p, 0, sizeof(int), c->stream));
   int rc = launch_kkt_error(c);  // on the freshly linearised (pre-condensation) records
-  if (!rc && c->ls_on) rc = launch_eval_ocp(c, c->d_eval);   // dms_.getEval(): cost + barrier, violation of the current iterate
+  if (!rc && c->ls_on) rc = launch_eval_ocp(c, c->d_eval.p);   // dms_.getEval(): cost + barrier, violation of the current iterate
   if (!rc) rc = rtoc_condense(c);
   if (!rc && c->sto_on) STO_LAUNCH(sto_eval_kkt_dev_kernel, c);   // sto_.evalKKT (ocp_solver.cpp:119); KKTError() gains the STO term
   if (!rc) rc = launch_sweep(c, p);
@@ -3265,14 +3152,14 @@ static int newton_iteration_body(rtoc_ctx* c, const BwdPlan& p, double kkt_tol, 
   if (rc) return rc;
   if (c->sto_on) STO_LAUNCH(sto_step_sizes_kernel, c);             // sto_.computeStepSizes, min with the stages' steps (:128-132)
   hipLaunchKernelGGL(mask_converged_kernel, dim3((c->batch + 255) / 256), dim3(256), 0, c->stream,
-                     c->buf[RTOC_BUF_STEP], c->d_kkterr, c->d_nconv, kkt_tol, c->batch);
+                     c->buf[RTOC_BUF_STEP].p, c->d_kkterr.p, c->d_nconv.p, kkt_tol, c->batch);
   HIP_TRY(hipGetLastError());
   if (c->ls_on) {   // line_search_.computeStepSize (:133-139): the accepted primal steps replace the maximum ones
     rc = rtoc_contact_line_search(c, nullptr);
     if (rc) return rc;
   }
   rc = rtoc_update(c);
-  if (!rc && c->buf[RTOC_BUF_SOL]) rc = rtoc_integrate_solution(c);
+  if (!rc && c->buf[RTOC_BUF_SOL].p) rc = rtoc_integrate_solution(c);
   if (!rc && c->sto_on) STO_LAUNCH(sto_integrate_kernel, c);       // sto_.integrateSolution (:143)
   return rc;
 }
@@ -3280,7 +3167,7 @@ static int newton_iteration_body(rtoc_ctx* c, const BwdPlan& p, double kkt_tol, 
 int rtoc_newton_iteration(rtoc_ctx* c, double kkt_tol, double tau) {
   CHECK_READY(c);
   if (!(kkt_tol >= 0.0) || !(tau > 0.0 && tau <= 1.0)) return RTOC_ERR_BAD_ARG;
-  if (!c->d_nconv) HIP_TRY(hipMalloc((void**)&c->d_nconv, sizeof(int)));
+  HIP_TRY(c->d_nconv.reserve(1));
   BwdPlan p;
   int rc = plan_backward(c, &p);   // (the condensation ahead of the sweep leaves the rows of Fxx the check reads as they are)
   if (rc) return rc;
@@ -3294,36 +3181,16 @@ int rtoc_newton_iteration(rtoc_ctx* c, double kkt_tol, double tau) {
 int rtoc_converged_count(rtoc_ctx* c, int* host_count) {
   CHECK_READY(c);
   if (!host_count) return RTOC_ERR_BAD_ARG;
-  if (!c->d_nconv) return RTOC_ERR_NOT_READY;
-  HIP_TRY(hipMemcpyAsync(host_count, c->d_nconv, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (!c->d_nconv.p) return RTOC_ERR_NOT_READY;
+  HIP_TRY(hipMemcpyAsync(host_count, c->d_nconv.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
 
 // ---- stage dump / replay --------------------------------------------------------------------
-static size_t dump_count(const rtoc_ctx* c, int b) {  // doubles of buffer b the kernels index
-  const size_t per = (size_t)c->batch * c->nstages;
-  switch (b) {
-    case RTOC_BUF_KKT: return per * c->L.kkt.stride;
-    case RTOC_BUF_RIC: return per * c->L.ric.stride;
-    case RTOC_BUF_DIR: return per * c->L.dir.stride;
-    case RTOC_BUF_CDD: return per * c->L.cdd.stride;
-    case RTOC_BUF_CON: return per * c->L.con.stride;
-    case RTOC_BUF_DX0: return (size_t)c->batch * c->L.nx;
-    case RTOC_BUF_STEP: return (size_t)c->batch * 2;
-    case RTOC_BUF_SE3: return per * RTOC_SE3_STRIDE;
-    case RTOC_BUF_CONE:
-      if (c->cone_contacts <= 0) return 0;
-      return per * (c->cone_rows == RTOC_WRENCH_ROWS ? rtoc_wrench_cone_stride(c->cone_contacts)
-                                                     : rtoc_cone_stride(c->dims.nv, c->cone_contacts));
-    case RTOC_BUF_SOL: return per * c->L.sol.stride;
-    default: return 0;
-  }
-}
-
 int rtoc_save_stage_dump(rtoc_ctx* c, const char* path, unsigned int mask) {
   CHECK_READY(c);
-  if (!path || !c->h_grid) return RTOC_ERR_BAD_ARG;
+  if (!path || c->h_grid.empty()) return RTOC_ERR_BAD_ARG;
   rtoc_dump_header h;
   memset(&h, 0, sizeof(h));
   memcpy(h.magic, "RTOCDMP1", 8);
@@ -3337,17 +3204,17 @@ int rtoc_save_stage_dump(rtoc_ctx* c, const char* path, unsigned int mask) {
   h.cone_dim = c->cone_dim;
   h.cone_rows = c->cone_contacts > 0 ? c->cone_rows : 0;
   for (int b = 0; b < RTOC_NUM_BUFFERS; ++b)
-    if ((mask >> b & 1u) && c->buf[b]) h.count[b] = dump_count(c, b);
+    if ((mask >> b & 1u) && c->buf[b].p) h.count[b] = buffer_count(c, b, c->nstages);
   FILE* f = fopen(path, "wb");
   if (!f) return RTOC_ERR_IO;
   bool ok = fwrite(&h, sizeof(h), 1, f) == 1 &&
-            fwrite(c->h_grid, sizeof(rtoc_grid), c->nstages, f) == (size_t)c->nstages &&
-            (c->nrows == 0 || fwrite(c->h_rows, sizeof(rtoc_box_row), c->nrows, f) == (size_t)c->nrows);
+            fwrite(c->h_grid.data(), sizeof(rtoc_grid), c->nstages, f) == (size_t)c->nstages &&
+            (c->nrows == 0 || fwrite(c->h_rows.data(), sizeof(rtoc_box_row), c->nrows, f) == (size_t)c->nrows);
   std::vector<double> stage;
   for (int b = 0; ok && b < RTOC_NUM_BUFFERS; ++b) {
     if (!h.count[b]) continue;
     stage.resize(h.count[b]);
-    if (hipMemcpyAsync(stage.data(), c->buf[b], h.count[b] * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
+    if (hipMemcpyAsync(stage.data(), c->buf[b].p, h.count[b] * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
             hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
       fclose(f);
@@ -3386,7 +3253,7 @@ int rtoc_load_stage_dump(const char* path, int device, rtoc_ctx** out) {
   std::vector<double> stage;
   for (int b = 0; !rc && b < RTOC_NUM_BUFFERS; ++b) {
     if (!h.count[b]) continue;
-    if (h.count[b] != dump_count(c, b)) {
+    if (h.count[b] != buffer_count(c, b, c->nstages)) {
       rc = RTOC_ERR_IO;
       break;
     }
@@ -3423,7 +3290,7 @@ int rtoc_gather_directions(rtoc_ctx* c, void* nccl_comm, double* out) {
   }
   const size_t count = (size_t)c->batch * c->nstages * c->L.dir.stride;
   const int nccl_float64 = 8;  // ncclFloat64 / ncclDouble
-  const int rc = fn(c->buf[RTOC_BUF_DIR], out, count, nccl_float64, nccl_comm, c->stream);
+  const int rc = fn(c->buf[RTOC_BUF_DIR].p, out, count, nccl_float64, nccl_comm, c->stream);
   return rc == 0 ? RTOC_OK : RTOC_ERR_RCCL;
 }
 

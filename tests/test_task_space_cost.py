@@ -221,6 +221,37 @@ def test_off_means_unchanged_graphs_and_clones():
     assert not np.array_equal(ctx.download_records(BUF_SOL, "sol"), plain_ctx.download_records(BUF_SOL, "sol"))
 
 
+@pytest.mark.gpu
+def test_clone_takes_more_terms_than_its_source_had():
+    """rtoc_clone copies the term table with the capacity it was allocated with (RTOC_MAX_TASK_COSTS per instance), not the
+    part in use when the clone is taken: a clone of a context with one shared term takes all five terms, and five terms per
+    instance, and evaluates them like a fresh context that was given the same terms directly"""
+    batch = 4
+    m, grids, times, ctx, sol, S = _trot_setup(batch=batch, seed=5)
+    ctx.set_task_costs(_trot_terms(m)[:1])
+    one = _eval(ctx)
+    cl = _clone(ctx)
+    fresh = _trot_setup(batch=batch, seed=5)[3]
+    per = []
+    for b in range(batch):
+        inst = _trot_terms(m)
+        for k, t in enumerate(inst):
+            t.set_weight([1e3 * (b + 1), 2e3 + k, 3e3])
+        per.append(inst)
+    seen = [one]
+    for larger, per_instance in ((_trot_terms(m), False), (per, True)):
+        cl.set_task_costs(larger, per_instance=per_instance)
+        fresh.set_task_costs(larger, per_instance=per_instance)
+        cl_rec, fresh_rec = _eval(cl), _eval(fresh)
+        assert all(np.array_equal(x, y) for x, y in zip(cl_rec, fresh_rec)), per_instance
+        assert all(not np.array_equal(cl_rec[0], r[0]) for r in seen)   # the larger set took effect
+        seen.append(cl_rec)
+    # the source keeps its one term
+    assert all(np.array_equal(x, y) for x, y in zip(one, _eval(ctx)))
+    for c in (cl, fresh, ctx):
+        c.close()
+
+
 def _correct_time_steps(grids, t, T, ts):
     """TimeDiscretization::correctTimeSteps (time_discretization.cpp:186-222), grid times only"""
     N = len(grids) - 1
