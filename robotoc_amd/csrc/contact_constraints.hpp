@@ -19,23 +19,13 @@
 namespace rtoc {
 
 struct CcArgs {
-  const rbd::DevModel* model;
-  const double* sol;
-  double* kkt;
-  double* cdd;
-  double* con;
-  double* cone;
-  const rtoc_grid* grid;
-  const unsigned* active;
-  const double* rotations;  // [nstages][ncontacts][9] or nullptr
+  RecView rv;
+  ModelDims md;
   const double* mu;         // [ncontacts]
-  int nstages, batch, nv, njoints, ncontacts, nlevels, mode;
+  int mode;
   int contact_dim, row0, cone_stride, dgdf_off, impact_cones;
   int exact_jacobian;   // RTOC_OPT_CONE_JACOBIAN: 0 = w_local x f_W as the reference composes it, 1 = w_world x f_W
   double barrier;
-  int sol_stride, kkt_stride, cdd_stride, con_stride;
-  int o_q, o_f, o_lx, o_lf;
-  rtoc_record_layout nl;
 };
 enum { CC_INIT = 0, CC_LINEARIZE = 1 };
 
@@ -49,31 +39,31 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
   using rbd::JP;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.rv.nstages - 1;
   const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;   // the terminal grid point has no rows
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   if (g.dimf == 0 || (g.type == RTOC_GRID_IMPACT && !a.impact_cones)) return;
-  const unsigned act = a.active[st];
-  const int nv = a.nv, nb = a.njoints, ncon = a.ncontacts, nlev = a.nlevels, cd = a.contact_dim;
+  const unsigned act = a.rv.active[st];
+  const int nv = a.rv.nv(), nb = a.md.njoints, ncon = a.md.ncontacts, nlev = a.md.nlevels, cd = a.contact_dim;
   double* const lval = smem;
   double* const ltan = lval + (size_t)nlev * 32;
   double* const sjm = ltan + (size_t)nlev * 6 * 64;
   double* const scm = sjm + nb * JP;
   double* const sq = scm + ncon * CP;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const kr = a.kkt ? a.kkt + rec * a.kkt_stride : nullptr;
-  double* const cr = a.cdd ? a.cdd + rec * a.cdd_stride : nullptr;
-  double* const nr = a.con + rec * a.con_stride;
-  double* const gr = a.cone ? a.cone + rec * a.cone_stride : nullptr;
-  const int* const no = a.nl.off;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const lx = a.rv.kkt ? a.rv.kkt_at(rec) + a.rv.kkt_off(RTOC_KKT_LX) : nullptr;
+  double* const cr = a.rv.cdd ? a.rv.cdd_at(rec) : nullptr;
+  double* const nr = a.rv.con_at(rec);
+  double* const gr = a.rv.cone ? a.rv.cone + rec * a.cone_stride : nullptr;
+  const int* const no = a.rv.L.con.off;
   {
-    const double* const gj = &a.model->joint[0][0];
-    const double* const gc = &a.model->contact[0][0];
+    const double* const gj = &a.rv.model->joint[0][0];
+    const double* const gc = &a.rv.model->contact[0][0];
     for (int e = lane; e < nb * JP; e += 64) sjm[e] = gj[e];
     for (int e = lane; e < ncon * CP; e += 64) scm[e] = gc[e];
-    for (int e = lane; e < a.model->m.nq; e += 64) sq[e] = s[a.o_q + e];
+    for (int e = lane; e < a.rv.model->m.nq; e += 64) sq[e] = s[a.rv.sol_off(RTOC_SOL_Q) + e];
   }
   __syncthreads();
   const int j = lane;
@@ -117,10 +107,10 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
       const bool on = (act >> c) & 1u;
       if (on && (int)scm[c * CP + 14] == i) {
         const M3 Rwf = rbd::mul(oR, rbd::ldm3(&scm[c * CP]));
-        const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.o_f + k * cd));
+        const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
         M3 Rs;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) Rs.m[e] = a.rotations ? a.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
+        for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
         const double m = a.mu[c] * 0.70710678118654752440;
         // rows of cone_local = cone_world R_surface^T: row r = R_surface * (row r of cone_world)
         V3 row[5];
@@ -160,7 +150,7 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
               gr[a.dgdf_off + k * 15 + r + 5 * lane] = e;
               acc += e * dual[r];
             }
-            cr[a.o_lf + k * cd + lane] += acc;
+            cr[a.rv.cdd_off(RTOC_CDD_LF) + k * cd + lane] += acc;
           }
           if (lane_on) {    // column j of dg/dq
             // the reference crosses the LOCAL-frame angular Jacobian column with the WORLD-frame force (robot.hxx:247-253,
@@ -178,7 +168,7 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
       k += on ? 1 : 0;
     }
   }
-  if (lin && lane_on) kr[a.o_lx + j] += lq;
+  if (lin && lane_on) lx[j] += lq;
 }
 
 }  // namespace rtoc
@@ -199,40 +189,40 @@ static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) 
   using rbd::CP;
   const CcArgs& a = v.c;
   const int lane = threadIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.rv.nstages - 1;
   const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   if (g.dimf == 0 || (g.type == RTOC_GRID_IMPACT && !a.impact_cones)) return;
-  const unsigned act = a.active[st];
-  const int nv = a.nv, nb = a.njoints, ncon = a.ncontacts, cd = a.contact_dim;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
-  double* const nr = a.con + rec * a.con_stride;
-  double* const gr = a.cone + rec * a.cone_stride;
+  const unsigned act = a.rv.active[st];
+  const int nv = a.rv.nv(), nb = a.md.njoints, ncon = a.md.ncontacts, cd = a.contact_dim;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const kr = a.rv.kkt_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
+  double* const nr = a.rv.con_at(rec);
+  double* const gr = a.rv.cone + rec * a.cone_stride;
   const double* const vb = v.vals + rec * (size_t)nb * rbd::VAL_SLOTS;
-  const int* const no = a.nl.off;
+  const int* const no = a.rv.L.con.off;
   const int j = lane;
   const bool lane_on = j < nv;
   // this dof's rotation axis in the world frame
   V3 wj = rbd::mk(0, 0, 0);
   if (lane_on) {
-    const double* const blk = vb + (size_t)a.model->dof_body[j] * rbd::VAL_SLOTS;
-    wj = rbd::mul(rbd::ldm3(blk + 12), rbd::ldv3(a.model->dof_axis[j]));
+    const double* const blk = vb + (size_t)a.rv.model->dof_body[j] * rbd::VAL_SLOTS;
+    wj = rbd::mul(rbd::ldm3(blk + 12), rbd::ldv3(a.rv.model->dof_axis[j]));
   }
   double lq = 0.0;
   int k = 0;
   for (int c = 0; c < ncon; ++c) {
     if (!((act >> c) & 1u)) continue;
-    const double* const cm = &a.model->contact[c][0];
+    const double* const cm = &a.rv.model->contact[c][0];
     const double* const blk = vb + (size_t)(int)cm[14] * rbd::VAL_SLOTS;
     const M3 Rwf = rbd::mul(rbd::ldm3(blk + 12), rbd::ldm3(cm));
-    const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.o_f + k * cd));
+    const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
     M3 Rs;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) Rs.m[e] = a.rotations ? a.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
+    for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
     const double m = a.mu[c] * 0.70710678118654752440;
     V3 row[5];
     row[0] = rbd::mul(Rs, rbd::mk(0, 0, -1));
@@ -262,10 +252,10 @@ static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) 
         gr[a.dgdf_off + k * 15 + r + 5 * lane] = e;
         acc += e * dual[r];
       }
-      cr[a.o_lf + k * cd + lane] += acc;
+      cr[a.rv.cdd_off(RTOC_CDD_LF) + k * cd + lane] += acc;
     }
     if (lane_on) {
-      const bool path = (a.model->contact_dofs[c] >> j) & 1ull;
+      const bool path = (a.rv.model->contact_dofs[c] >> j) & 1ull;
       // reference: LOCAL-frame angular Jacobian column x WORLD-frame force (see contact_cone_kernel); exact: w_world x f_W
       const V3 wxf = path ? rbd::cross(a.exact_jacobian ? wj : rbd::mulT(Rwf, wj), fW) : rbd::mk(0, 0, 0);
 #pragma unroll
@@ -277,7 +267,7 @@ static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) 
     }
     ++k;
   }
-  if (lane_on) kr[a.o_lx + j] += lq;
+  if (lane_on) kr[a.rv.kkt_off(RTOC_KKT_LX) + j] += lq;
 }
 
 }  // namespace rtoc
@@ -292,37 +282,30 @@ namespace rtoc {
 //   LINEARIZE  residual = g + slack, cmpl = slack dual - barrier, lf += cone^T dual
 // One wave per (instance, grid point), lane r < 17 = row r of a contact.
 struct WcArgs {
-  const double* sol;
-  double* cdd;
-  double* con;
-  double* cone;
+  RecView rv;
+  ModelDims md;
   const double* table;   // [ncontacts][17 x 6], column-major (ld 17)
-  const rtoc_grid* grid;
-  const unsigned* active;
-  int nstages, batch, ncontacts, mode, row0, cone_stride, impact_cones;
+  int mode, row0, cone_stride, impact_cones;
   double barrier;
-  int sol_stride, cdd_stride, con_stride;
-  int o_f, o_lf;
-  rtoc_record_layout nl;
 };
 
 static __global__ __launch_bounds__(64) void wrench_cone_eval_kernel(WcArgs a) {
   __shared__ double sd[RTOC_WRENCH_ROWS];
   const int lane = threadIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.rv.nstages - 1;
   const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   if (g.dimf == 0 || (g.type == RTOC_GRID_IMPACT && !a.impact_cones)) return;
-  const unsigned act = a.active[st];
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const cr = a.cdd ? a.cdd + rec * a.cdd_stride : nullptr;
-  double* const nr = a.con + rec * a.con_stride;
-  double* const gr = a.cone + rec * a.cone_stride;
-  const int* const no = a.nl.off;
+  const unsigned act = a.rv.active[st];
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const cr = a.rv.cdd ? a.rv.cdd_at(rec) : nullptr;
+  double* const nr = a.rv.con_at(rec);
+  double* const gr = a.rv.cone + rec * a.cone_stride;
+  const int* const no = a.rv.L.con.off;
   int k = 0;
-  for (int c = 0; c < a.ncontacts; ++c) {
+  for (int c = 0; c < a.md.ncontacts; ++c) {
     if (!((act >> c) & 1u)) continue;
     const double* const A = a.table + (size_t)c * RTOC_WRENCH_ROWS * 6;
     const int r0 = a.row0 + RTOC_WRENCH_ROWS * k;
@@ -331,7 +314,7 @@ static __global__ __launch_bounds__(64) void wrench_cone_eval_kernel(WcArgs a) {
     if (lane < RTOC_WRENCH_ROWS) {
       double gval = 0.0;
 #pragma unroll
-      for (int t = 0; t < 6; ++t) gval += A[lane + RTOC_WRENCH_ROWS * t] * s[a.o_f + 6 * k + t];
+      for (int t = 0; t < 6; ++t) gval += A[lane + RTOC_WRENCH_ROWS * t] * s[a.rv.sol_off(RTOC_SOL_F) + 6 * k + t];
       if (a.mode == CC_INIT) {
         double slack = -gval;
         const double sb = sqrt(a.barrier);
@@ -350,7 +333,7 @@ static __global__ __launch_bounds__(64) void wrench_cone_eval_kernel(WcArgs a) {
       if (lane < 6) {
         double acc = 0.0;
         for (int r = 0; r < RTOC_WRENCH_ROWS; ++r) acc += A[r + RTOC_WRENCH_ROWS * lane] * sd[r];
-        cr[a.o_lf + 6 * k + lane] += acc;
+        cr[a.rv.cdd_off(RTOC_CDD_LF) + 6 * k + lane] += acc;
       }
       __syncthreads();
     }

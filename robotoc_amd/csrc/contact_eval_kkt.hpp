@@ -15,16 +15,8 @@
 namespace rtoc {
 
 struct CostArgs {
-  const double* sol;
+  RecView rv;
   const double* cost;
-  double* kkt;
-  double* cdd;
-  const rtoc_grid* grid;
-  int nstages, batch, nv, nu, nf_max, ns_max, floating;
-  int sol_stride, kkt_stride, cdd_stride;
-  int o_q, o_v, o_a, o_u;
-  rtoc_record_layout kl, cl;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
   double* cost_out;       // [batch][nstages] value of the stage / impact / terminal cost (evalOCP: line search), or nullptr
 };
 
@@ -36,28 +28,25 @@ struct CostArgs {
 // same reason, the constant part of linearizeStateEquation: Fqq = I, Fqv = dt I (state_equation.cpp:29-40; the base corner of a
 // floating base is overwritten by state_equation_lin_kernel).
 struct InitArgs {
-  double* kkt;
+  RecView rv;
   const double* cost;      // the table of contact_cost_kernel
-  const rtoc_grid* grid;
-  const double* dt_inst;
-  int nstages, batch, nv, nu, floating, kkt_stride, o_qxx, o_quu, o_fxx;
 };
 static __global__ __launch_bounds__(256) void init_records_kernel(InitArgs a) {
   typedef double dbl2 __attribute__((ext_vector_type(2)));
-  const int nv = a.nv, nu = a.nu, nx = 2 * nv, M = nv + 1, nb = a.floating ? 6 : 0;
+  const int nv = a.rv.nv(), nu = a.rv.nu(), nx = 2 * nv, M = nv + 1, nb = a.rv.floating() ? 6 : 0;
   const double *wq = a.cost + 3 * M, *wv = wq + M, *wu = wv + 2 * M, *wqT = wu + M, *wvT = wqT + M, *wqI = wvT + M, *wvI = wqI + M;
-  const int half = a.kkt_stride / 2, qxx0 = a.o_qxx, qxx1 = a.o_qxx + nx * nx, quu0 = a.o_quu, quu1 = a.o_quu + nu * nu;
-  const int fxx0 = a.o_fxx, fxx1 = a.o_fxx + nx * nx;
-  const long long nrec = (long long)a.batch * a.nstages;
+  const int half = a.rv.L.kkt.stride / 2, qxx0 = a.rv.kkt_off(RTOC_KKT_QXX), qxx1 = a.rv.kkt_off(RTOC_KKT_QXX) + nx * nx, quu0 = a.rv.kkt_off(RTOC_KKT_QUU), quu1 = a.rv.kkt_off(RTOC_KKT_QUU) + nu * nu;
+  const int fxx0 = a.rv.kkt_off(RTOC_KKT_FXX), fxx1 = a.rv.kkt_off(RTOC_KKT_FXX) + nx * nx;
+  const long long nrec = (long long)a.rv.batch * a.rv.nstages;
   for (long long rec = blockIdx.x; rec < nrec; rec += gridDim.x) {
-    const int b = (int)(rec / a.nstages), st = (int)(rec % a.nstages);
-    const bool impact = a.grid[st].type == RTOC_GRID_IMPACT, terminal = st == a.nstages - 1;
-    const double scale = (impact || terminal) ? 1.0 : grid_dt(a.grid, a.dt_inst, b, a.nstages, st);
+    const int b = (int)(rec / a.rv.nstages), st = (int)(rec % a.rv.nstages);
+    const bool impact = a.rv.grid[st].type == RTOC_GRID_IMPACT, terminal = st == a.rv.nstages - 1;
+    const double scale = (impact || terminal) ? 1.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
     const double* const Wq = terminal ? wqT : impact ? wqI : wq;
     const double* const Wv = terminal ? wvT : impact ? wvI : wv;
     const bool sto = !terminal && !impact;
     const double dt = impact ? 0.0 : scale;   // terminal records: no state equation
-    dbl2* const p2 = reinterpret_cast<dbl2*>(a.kkt + rec * a.kkt_stride);
+    dbl2* const p2 = reinterpret_cast<dbl2*>(a.rv.kkt_at(rec));
     for (int t = threadIdx.x; t < half; t += 256) {
       dbl2 v = {0.0, 0.0};
       const int w = 2 * t;   // the pair (w, w + 1) of the record; fields start on multiples of 8 doubles
@@ -95,20 +84,20 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   const int lane = threadIdx.x % COST_LW, grp = threadIdx.x / COST_LW;   // `lane`: within the grid point's COST_LW lanes
   double* const J = Js[grp];
   double* const wd = wds[grp];
-  const long long nitems = (long long)a.batch * a.nstages;
+  const long long nitems = (long long)a.rv.batch * a.rv.nstages;
   long long item = (long long)blockIdx.x * COST_GP + grp;
   item = item < nitems ? item : nitems - 1;
-  const int b = (int)(item / a.nstages), st = (int)(item % a.nstages);
-  const rtoc_grid g = a.grid[st];
-  const bool impact = g.type == RTOC_GRID_IMPACT, terminal = st == a.nstages - 1;
-  const int nv = a.nv, nu = a.nu, nx = 2 * nv, nb = a.floating ? 6 : 0, M = nv + 1, np = nv - nu;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
+  const int b = (int)(item / a.rv.nstages), st = (int)(item % a.rv.nstages);
+  const rtoc_grid g = a.rv.grid[st];
+  const bool impact = g.type == RTOC_GRID_IMPACT, terminal = st == a.rv.nstages - 1;
+  const int nv = a.rv.nv(), nu = a.rv.nu(), nx = 2 * nv, nb = a.rv.floating() ? 6 : 0, M = nv + 1, np = nv - nu;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const kr = a.rv.kkt_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
   const double *qr = a.cost, *vr = qr + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M, *wqT = wu + M,
                *wvT = wqT + M, *wqI = wvT + M, *wvI = wqI + M, *wdvI = wvI + M;
-  const double scale = (impact || terminal) ? 1.0 : grid_dt(a.grid, a.dt_inst, b, a.nstages, st);
+  const double scale = (impact || terminal) ? 1.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
   const double* const Wq = terminal ? wqT : impact ? wqI : wq;
   const double* const Wv = terminal ? wvT : impact ? wvI : wv;
   // ---- setZero of the RTOC_BUF_CDD fields the stages below accumulate into (the KKT record: init_records_kernel) ----
@@ -124,28 +113,28 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   // arithmetic.  The KKT record was zeroed as a whole by init_records_kernel, which also wrote the diagonals dt W of Qqq (joints),
   // Qvv and Quu.
   auto zero_cdd = [&]() {
-    if (a.ns_max > 0) zero(cr + a.cl.off[RTOC_CDD_PHIA], a.ns_max * nv);
+    if (a.rv.L.dims.ns_max > 0) zero(cr + a.rv.cdd_off(RTOC_CDD_PHIA), a.rv.L.dims.ns_max * nv);
     if (terminal) {
-      zero(cr + a.cl.off[RTOC_CDD_QAA], nv);
-      zero(cr + a.cl.off[RTOC_CDD_LA], nv);
-      zero(cr + a.cl.off[RTOC_CDD_HA], nv);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_QAA), nv);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_LA), nv);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_HA), nv);
     }
-    zero(cr + a.cl.off[RTOC_CDD_LUP], 8);
-    if (a.nf_max > 0) {
-      zero(cr + a.cl.off[RTOC_CDD_QFF], a.nf_max * a.nf_max);
-      zero(cr + a.cl.off[RTOC_CDD_QQF], nv * a.nf_max);
-      zero(cr + a.cl.off[RTOC_CDD_LF], a.nf_max);
-      zero(cr + a.cl.off[RTOC_CDD_HF], a.nf_max);
+    zero(cr + a.rv.cdd_off(RTOC_CDD_LUP), 8);
+    if (a.rv.L.dims.nf_max > 0) {
+      zero(cr + a.rv.cdd_off(RTOC_CDD_QFF), a.rv.L.dims.nf_max * a.rv.L.dims.nf_max);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_QQF), nv * a.rv.L.dims.nf_max);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_LF), a.rv.L.dims.nf_max);
+      zero(cr + a.rv.cdd_off(RTOC_CDD_HF), a.rv.L.dims.nf_max);
     }
   };
-  const double *q = s + a.o_q, *v = s + a.o_v, *acc = s + a.o_a, *u = s + a.o_u;
-  double* const Qxx = kr + a.kl.off[RTOC_KKT_QXX];
-  double* const lx = kr + a.kl.off[RTOC_KKT_LX];
+  const double *q = s + a.rv.sol_off(RTOC_SOL_Q), *v = s + a.rv.sol_off(RTOC_SOL_V), *acc = s + a.rv.sol_off(RTOC_SOL_A), *u = s + a.rv.sol_off(RTOC_SOL_U);
+  double* const Qxx = kr + a.rv.kkt_off(RTOC_KKT_QXX);
+  double* const lx = kr + a.rv.kkt_off(RTOC_KKT_LX);
   // ---- joints of q, v, a, u ----
   // The STO sensitivities of the stage cost on intermediate grids (intermediate_stage.cpp:103-108): h = cost / dt and
   // hx, hu, ha = lx, lu, la / dt BEFORE constraints and dynamics add their terms -- i.e. the cost gradient without the dt
   const bool sto = !terminal && !impact;
-  double* const hx = kr + a.kl.off[RTOC_KKT_HX];
+  double* const hx = kr + a.rv.kkt_off(RTOC_KKT_HX);
   double hval = 0.0;   // this lane's share of cost / dt (cost itself on impact / terminal grids) = 1/2 sum of weight * difference^2
   for (int i = lane; i < nv; i += COST_LW) {
     if (i >= nb) {
@@ -160,22 +149,22 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
     hval += 0.5 * Wv[i] * dv * dv;
     if (!terminal) {
       const double w = impact ? wdvI[i] : scale * wa[i];   // a on contact grids, dv on impact grids (both in the A slot)
-      cr[a.cl.off[RTOC_CDD_LA] + i] = w * acc[i];
-      cr[a.cl.off[RTOC_CDD_QAA] + i] = w;
-      cr[a.cl.off[RTOC_CDD_HA] + i] = sto ? wa[i] * acc[i] : 0.0;
+      cr[a.rv.cdd_off(RTOC_CDD_LA) + i] = w * acc[i];
+      cr[a.rv.cdd_off(RTOC_CDD_QAA) + i] = w;
+      cr[a.rv.cdd_off(RTOC_CDD_HA) + i] = sto ? wa[i] * acc[i] : 0.0;
       hval += 0.5 * (impact ? wdvI[i] : wa[i]) * acc[i] * acc[i];
     }
   }
   if (sto)
     for (int i = lane; i < nu; i += COST_LW) {
       const double du = u[i] - ur[i];
-      kr[a.kl.off[RTOC_KKT_LU] + i] = scale * wu[i] * du;
-      kr[a.kl.off[RTOC_KKT_HU] + i] = wu[i] * du;
+      kr[a.rv.kkt_off(RTOC_KKT_LU) + i] = scale * wu[i] * du;
+      kr[a.rv.kkt_off(RTOC_KKT_HU) + i] = wu[i] * du;
       hval += 0.5 * wu[i] * du * du;
     }
   (void)np;
   // ---- the free-flyer base of q: qdiff = log6(M_ref^-1 M), J = Jlog6 ----
-  if (a.floating) {
+  if (a.rv.floating()) {
     M3 Rx;
     V3 px;
     rel(quat_R(qr + 3), rbd::ldv3(qr), quat_R(q + 3), rbd::ldv3(q), Rx, px);
@@ -207,7 +196,7 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   if (sto || a.cost_out) {
 #pragma unroll
     for (int off = COST_LW / 2; off > 0; off >>= 1) hval += __shfl_xor(hval, off, 64);   // within the grid point's lanes
-    if (lane == 0 && sto) kr[a.kl.off[RTOC_KKT_SCAL] + RTOC_KKT_SCAL_H] = hval;
+    if (lane == 0 && sto) kr[a.rv.kkt_off(RTOC_KKT_SCAL) + RTOC_KKT_SCAL_H] = hval;
     // the value of the cost itself (evalStageCost / evalImpactCost / evalTerminalCost): what evalOCP sums for the line search
     if (lane == 0 && a.cost_out) a.cost_out[rec] = scale * hval;
   }

@@ -21,6 +21,7 @@
 // column j is the v-tangent of the frame velocity -- held by the neighbouring lane (point_contact.hxx:78-80).
 #pragma once
 #include "device_utils.hpp"
+#include "record_view.hpp"
 #include "../../include/rtoc_robot.h"
 
 #ifndef RTOC_RBD_WAVES
@@ -215,25 +216,8 @@ typedef const int __attribute__((address_space(4))) lin_const_int;
 __device__ __forceinline__ int sload_int(const int* p) { return *(lin_const_int*)(unsigned long long)p; }
 
 struct LinArgs {
-  const DevModel* model;
-  const double* sol;
-  double* cdd;
-  const rtoc_grid* grid;
-  const unsigned* active;    // [nstages]
-  const double* positions;   // [nstages][ncontacts][3] or nullptr
-  const double* rotations;   // [nstages][ncontacts][9] or nullptr (surface contacts: desired rotation)
-  int nstages, batch;
-  int sol_stride, cdd_stride;
-  int o_q, o_v, o_a, o_u, o_f;                 // RTOC_BUF_SOL field offsets
-  int o_idc, o_didda, o_dcda, o_didcdqv;       // RTOC_BUF_CDD field offsets
-  int ldv, nf_max;                             // leading dimensions of DIDCDQV / DCDA
-  int nlevels, nbranch, dpp, nv, nq, njoints, ncontacts, nu;
-  double gx, gy, gz;                           // gravity
-  // multiplier terms of linearizeContactDynamics / linearizeImpactDynamics (kkt == nullptr: left out)
-  double* kkt;
-  int kkt_stride, o_lx, o_lu;                  // RTOC_BUF_KKT: lx = [lq; lv], lu
-  int o_la, o_lf, o_lup;                       // RTOC_BUF_CDD: la (ldv on impact grids), lf, lu_passive
-  int o_beta, o_mu, o_nup;                     // RTOC_BUF_SOL
+  RecView rv;           // kkt == nullptr: the multiplier terms of linearizeContactDynamics / linearizeImpactDynamics are left out
+  ModelDims md;
   // UnconstrDynamics::linearizeUnconstrDynamics (unconstr_dynamics.cpp:52-64): the multiplier terms carry dt, and the
   // records follow the convention of rtoc_unconstr_condense (la lives in KKT.lu, lu in CDD.la)
   int unconstr;
@@ -337,68 +321,60 @@ inline void plan_passes(DevModel* h, int forced_dpp) {
 // (the value part of RTOC_CDD_IDC).  trav: 0 = the dynamics traversal, 1 = the kinematics traversal at v + dv of impact
 // grids (impact_stage.cpp:61), other grids idle.
 struct ValArgs {
-  const DevModel* model;
-  const double* sol;
-  double* cdd;
+  RecView rv;           // positions / rotations: the desired contact placements (the value rows of C below)
+  ModelDims md;
   double* vals;         // [batch * nstages][njoints][64]
-  const rtoc_grid* grid;
-  const unsigned* active;
-  int nstages, batch, nv, nu, njoints, ncontacts, nlevels, gs, trav, unconstr;
+  int trav, unconstr;
   int nsel, sel[16];    // nsel > 0: only the grid points sel[0..nsel) of every instance (the impact grids of trav 1)
-  int sol_stride, cdd_stride;
-  int o_q, o_v, o_a, o_u, o_f, o_idc;
-  double gx, gy, gz;
-  const double* positions;   // [nstages][ncontacts][3] or nullptr: desired contact positions (the value rows of C below)
-  const double* rotations;   // [nstages][ncontacts][9] or nullptr (surface contacts)
 };
 constexpr int VAL_SLOTS = 64;
 
 static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];   // [G][njoints][64]
-  const int lane = threadIdx.x, GS = a.gs, G = 64 / GS, nb = a.njoints, ncon = a.ncontacts;
+  const int lane = threadIdx.x, GS = a.md.gs, G = 64 / GS, nb = a.md.njoints, ncon = a.md.ncontacts;
   const int grp = lane / GS, i = lane % GS;
-  const int nst1 = a.nsel > 0 ? a.nsel : a.nstages - 1;   // grid points per instance this launch covers
-  const long long item = (long long)blockIdx.x * G + grp, nitems = (long long)a.batch * nst1;
+  const int nst1 = a.nsel > 0 ? a.nsel : a.rv.nstages - 1;   // grid points per instance this launch covers
+  const long long item = (long long)blockIdx.x * G + grp, nitems = (long long)a.rv.batch * nst1;
   const bool gvalid = item < nitems;
   const int b = gvalid ? (int)(item / nst1) : 0;
   const int st = !gvalid ? 0 : (a.nsel > 0 ? a.sel[item % nst1] : (int)(item % nst1));
-  const rtoc_grid g = a.grid[st];
+  const rtoc_grid g = a.rv.grid[st];
   const bool impact = g.type == RTOC_GRID_IMPACT;
   const bool dyn = a.trav == 0;
   const bool on = gvalid && i < nb && (dyn || impact);
   const int ib = i < nb ? i : 0;
   double* const V = smem + (size_t)grp * nb * VAL_SLOTS;
   double* const me = V + (size_t)ib * VAL_SLOTS;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const sr = a.sol + rec * a.sol_stride;
-  const unsigned active = a.active[st];
-  const int nv = a.nv, nu = a.nu;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const sr = a.rv.sol_at(rec);
+  const unsigned active = a.rv.active[st];
+  const int nv = a.rv.nv(), nu = a.rv.nu();
   // ---- this body's constants and joint state ----
-  const double* const jm = &a.model->joint[ib][0];
+  const double* const jm = &a.rv.model->joint[ib][0];
   const int type = (int)jm[28], iq = (int)jm[29], iv = (int)jm[30], depth = (int)jm[31];
-  const int par = a.model->m.parent[ib];
+  const int par = a.rv.model->m.parent[ib];
   const bool ff = type == RTOC_JOINT_FREE_FLYER;
   const V3 ax = ldv3(jm + 12);
   M3 Rj;
   V3 pj = mk(0, 0, 0);
   SV vj, aj;
   if (ff) {
-    const double x = sr[a.o_q + iq + 3], y = sr[a.o_q + iq + 4], z = sr[a.o_q + iq + 5], w = sr[a.o_q + iq + 6];
+    const double x = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 3], y = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 4], z = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 5], w = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 6];
     Rj.m[0] = 1 - 2 * (y * y + z * z), Rj.m[1] = 2 * (x * y - z * w), Rj.m[2] = 2 * (x * z + y * w);
     Rj.m[3] = 2 * (x * y + z * w), Rj.m[4] = 1 - 2 * (x * x + z * z), Rj.m[5] = 2 * (y * z - x * w);
     Rj.m[6] = 2 * (x * z - y * w), Rj.m[7] = 2 * (y * z + x * w), Rj.m[8] = 1 - 2 * (x * x + y * y);
-    pj = ldv3(sr + a.o_q + iq);
-    vj = SV{ldv3(sr + a.o_v + iv), ldv3(sr + a.o_v + iv + 3)};
-    aj = SV{ldv3(sr + a.o_a + iv), ldv3(sr + a.o_a + iv + 3)};
+    pj = ldv3(sr + a.rv.sol_off(RTOC_SOL_Q) + iq);
+    vj = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_V) + iv), ldv3(sr + a.rv.sol_off(RTOC_SOL_V) + iv + 3)};
+    aj = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_A) + iv), ldv3(sr + a.rv.sol_off(RTOC_SOL_A) + iv + 3)};
     if (impact && !dyn) vj = vj + aj;  // kinematics at v + dv
   } else {
-    const double th = sr[a.o_q + iq], c = cos(th), s = sin(th), t = 1.0 - c;
+    const double th = sr[a.rv.sol_off(RTOC_SOL_Q) + iq], c = cos(th), s = sin(th), t = 1.0 - c;
     Rj.m[0] = t * ax.x * ax.x + c, Rj.m[1] = t * ax.x * ax.y - s * ax.z, Rj.m[2] = t * ax.x * ax.z + s * ax.y;
     Rj.m[3] = t * ax.x * ax.y + s * ax.z, Rj.m[4] = t * ax.y * ax.y + c, Rj.m[5] = t * ax.y * ax.z - s * ax.x;
     Rj.m[6] = t * ax.x * ax.z - s * ax.y, Rj.m[7] = t * ax.y * ax.z + s * ax.x, Rj.m[8] = t * ax.z * ax.z + c;
-    const double vq = (impact && !dyn) ? sr[a.o_v + iv] + sr[a.o_a + iv] : sr[a.o_v + iv];
+    const double vq = (impact && !dyn) ? sr[a.rv.sol_off(RTOC_SOL_V) + iv] + sr[a.rv.sol_off(RTOC_SOL_A) + iv] : sr[a.rv.sol_off(RTOC_SOL_V) + iv];
     vj = SV{mk(0, 0, 0), vq * ax};
-    aj = SV{mk(0, 0, 0), sr[a.o_a + iv] * ax};
+    aj = SV{mk(0, 0, 0), sr[a.rv.sol_off(RTOC_SOL_A) + iv] * ax};
   }
   if (impact && dyn) vj = sv0();   // impact model: v = 0
   if (impact && !dyn) aj = sv0();  // velocity-level rows only
@@ -412,12 +388,12 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   auto st_sv6 = [&](double* d, SV x) { st_v3(d, x.l), st_v3(d + 3, x.a); };
   auto ld_sv6 = [&](const double* d) { return SV{ldv3(d), ldv3(d + 3)}; };
   // ---- down the levels: placements, velocities, accelerations, own forces ----
-  for (int d = 0; d < a.nlevels; ++d) {
+  for (int d = 0; d < a.md.nlevels; ++d) {
     if (on && depth == d) {
       M3 oR = R;
       V3 op = p;
       SV vpar = sv0(), apar = sv0();
-      V3 gi = mulT(R, mk(-a.gx, -a.gy, -a.gz));
+      V3 gi = mulT(R, mk(-a.md.gx, -a.md.gy, -a.md.gz));
       if (d > 0) {
         const double* const pa = V + (size_t)par * VAL_SLOTS;
         const M3 oRp = ldm3(pa + 12);
@@ -434,11 +410,11 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
       SV f = inertia_mul(mass, com, I, SV{acc.l + gi, acc.a}) + fcross(v, h);
       int roff = 0;
       for (int c = 0; c < ncon; ++c) {
-        const double* const cm = &a.model->contact[c][0];
+        const double* const cm = &a.rv.model->contact[c][0];
         const bool con_on = (active >> c) & 1u;
         const bool surf = (int)cm[15] == RTOC_CONTACT_SURFACE;
         if (con_on && (int)cm[14] == ib) {
-          const SV fc = SV{ldv3(sr + a.o_f + roff), surf ? ldv3(sr + a.o_f + roff + 3) : mk(0, 0, 0)};
+          const SV fc = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_F) + roff), surf ? ldv3(sr + a.rv.sol_off(RTOC_SOL_F) + roff + 3) : mk(0, 0, 0)};
           f = f - act_f(ldm3(cm), ldv3(cm + 9), fc);
         }
         roff += con_on ? (surf ? 6 : 3) : 0;
@@ -456,7 +432,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   }
   // ---- up the bodies, children before parents (reverse depth-first order): total forces ----
   for (int k = nb - 1; k >= 1; --k) {
-    const int pk = a.model->m.parent[k];
+    const int pk = a.rv.model->m.parent[k];
     if (on && ib == pk) {
       const double* const ch = V + (size_t)k * VAL_SLOTS;
       st_sv6(me + 39, ld_sv6(me + 39) + act_f(ldm3(ch), ldv3(ch + 9), ld_sv6(ch + 39)));
@@ -465,27 +441,27 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   }
   // ---- ID = S^T f - [0; u] (the value rows of RTOC_CDD_IDC; contact_dynamics.cpp:21-24, impact_dynamics.cpp:12-14) ----
   if (on && dyn) {
-    double* const cr = a.cdd + rec * a.cdd_stride;
+    double* const cr = a.rv.cdd_at(rec);
     const SV f = ld_sv6(me + 39);
     if (ff) {
       const double fv[6] = {f.l.x, f.l.y, f.l.z, f.a.x, f.a.y, f.a.z};
 #pragma unroll
-      for (int k = 0; k < 6; ++k) cr[a.o_idc + iv + k] = fv[k] - ((!impact && iv + k >= nv - nu) ? sr[a.o_u + iv + k - (nv - nu)] : 0.0);
+      for (int k = 0; k < 6; ++k) cr[a.rv.cdd_off(RTOC_CDD_IDC) + iv + k] = fv[k] - ((!impact && iv + k >= nv - nu) ? sr[a.rv.sol_off(RTOC_SOL_U) + iv + k - (nv - nu)] : 0.0);
     } else {
-      cr[a.o_idc + iv] = dot(ax, f.a) - ((!impact && iv >= nv - nu) ? sr[a.o_u + iv - (nv - nu)] : 0.0);
+      cr[a.rv.cdd_off(RTOC_CDD_IDC) + iv] = dot(ax, f.a) - ((!impact && iv >= nv - nu) ? sr[a.rv.sol_off(RTOC_SOL_U) + iv - (nv - nu)] : 0.0);
     }
   }
   // ---- C = the Baumgarte residual of the contacts this body carries (point_contact.hxx:14-31, surface_contact.hxx:12-29), on
   //      impact grids the contact velocity at v + dv from the kinematics traversal (point_contact.hxx:84-96): the value rows
   //      nv.. of RTOC_CDD_IDC.  Lane-invariant in the tangent walk, which used to evaluate them in every lane. ----
   if (on && (impact ? !dyn : dyn)) {
-    double* const cr = a.cdd + rec * a.cdd_stride;
+    double* const cr = a.rv.cdd_at(rec);
     const SV v = ld_sv6(me + 24), acc = ld_sv6(me + 30);
     const M3 oR = ldm3(me + 12);
     const V3 op = ldv3(me + 21);
     int roff = 0;
     for (int c = 0; c < ncon; ++c) {
-      const double* const cm = &a.model->contact[c][0];
+      const double* const cm = &a.rv.model->contact[c][0];
       const bool con_on = (active >> c) & 1u;
       const bool surf = (int)cm[15] == RTOC_CONTACT_SURFACE;
       const int nr = surf ? 6 : 3;
@@ -498,7 +474,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
           const SV af = act_inv(Rf, pf, acc);
           const double kp = cm[12], kd = cm[13];
           const V3 pw = op + mul(oR, pf);
-          const V3 pr = a.positions ? ldv3(a.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
+          const V3 pr = a.rv.positions ? ldv3(a.rv.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
           if (!surf) {
             C.l = af.l + cross(vf.a, vf.l) + kd * vf.l + kp * (pw - pr);
           } else {
@@ -506,14 +482,14 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
-              for (int cc = 0; cc < 3; ++cc) Rdt.m[3 * r + cc] = a.rotations ? a.rotations[((size_t)st * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
+              for (int cc = 0; cc < 3; ++cc) Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
             SV lg, dlg;
             log6_fwd(mul(Rdt, mul(oR, Rf)), mul(Rdt, pw - pr), sv0(), lg, dlg);
             C = SV{af.l + kd * vf.l + kp * lg.l, af.a + kd * vf.a + kp * lg.a};
           }
         }
         const double Cv[6] = {C.l.x, C.l.y, C.l.z, C.a.x, C.a.y, C.a.z};
-        for (int t = 0; t < nr; ++t) cr[a.o_idc + nv + roff + t] = Cv[t];
+        for (int t = 0; t < nr; ++t) cr[a.rv.cdd_off(RTOC_CDD_IDC) + nv + roff + t] = Cv[t];
       }
       roff += con_on ? nr : 0;
     }
@@ -525,8 +501,8 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
     const long long it2 = (long long)blockIdx.x * G + g2;
     if (it2 >= nitems) continue;
     const int b2 = (int)(it2 / nst1), st2 = a.nsel > 0 ? a.sel[it2 % nst1] : (int)(it2 % nst1);
-    if (!dyn && a.grid[st2].type != RTOC_GRID_IMPACT) continue;
-    a.vals[((size_t)b2 * a.nstages + st2) * per + (e - g2 * per)] = smem[e];
+    if (!dyn && a.rv.grid[st2].type != RTOC_GRID_IMPACT) continue;
+    a.vals[((size_t)b2 * a.rv.nstages + st2) * per + (e - g2 * per)] = smem[e];
   }
 }
 
@@ -539,17 +515,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.rv.nstages - 1;
   const int b = item / nst1, st = item % nst1;
-  if (b >= a.batch) return;
-  const int nlev = a.nlevels, nv = a.nv, nb = a.njoints, ncon = a.ncontacts;
-  const rtoc_grid g = a.grid[st];
+  if (b >= a.rv.batch) return;
+  const int nlev = a.md.nlevels, nv = a.rv.nv(), nb = a.md.njoints, ncon = a.md.ncontacts;
+  const rtoc_grid g = a.rv.grid[st];
   const bool impact = g.type == RTOC_GRID_IMPACT;
-  const unsigned active = a.active[st];
+  const unsigned active = a.rv.active[st];
   double* const lval = smem;                                      // [nlev][VAL_DOUBLES]
-  const int LW = lin_lane_stride(a.dpp);
+  const int LW = lin_lane_stride(a.md.dpp);
   double* const lfwd = lval + (size_t)nlev * VAL_DOUBLES;         // [nbranch][FWD_SLOTS][LW]: dv, da, dg of the branching bodies
-  double* const ldf = lfwd + (size_t)a.nbranch * FWD_SLOTS * LW;  // [nlev - 1][DF_SLOTS][LW]: df of the open non-leaf levels
+  double* const ldf = lfwd + (size_t)a.md.nbranch * FWD_SLOTS * LW;  // [nlev - 1][DF_SLOTS][LW]: df of the open non-leaf levels
   double* const sq = ldf + (size_t)(nlev > 1 ? nlev - 1 : 0) * DF_SLOTS * LW;   // q, v, a, f, u of the grid point
   double* const sv = sq + (PRE ? 0 : lin_pad8(nv + 1));   // (PRE: the staging vectors of the values are not allocated)
   double* const sa = sv + (PRE ? 0 : lin_pad8(nv));
@@ -560,45 +536,45 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
   double* const slf = smu + lin_pad8(6 * ncon);         // dC/da beta, accumulated over the passes
   constexpr int JPW = PRE ? JP_PRE : JP, JOFF = PRE ? JP_PRE_OFF : 0;
   double* const sjm = slf + lin_pad8(6 * ncon);         // model: [njoints][JPW] (PRE: axis .. depth only), then [ncontacts][CP]
-  double* const scm = sjm + a.njoints * JPW;
-  const bool aug = a.kkt != nullptr;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const sr = a.sol + rec * a.sol_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
-  const int nu = a.nu;
+  double* const scm = sjm + a.md.njoints * JPW;
+  const bool aug = a.rv.kkt != nullptr;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const sr = a.rv.sol_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
+  const int nu = a.rv.nu();
   {
-    const double* const gj = &a.model->joint[0][0];
-    const double* const gc = &a.model->contact[0][0];
+    const double* const gj = &a.rv.model->joint[0][0];
+    const double* const gc = &a.rv.model->contact[0][0];
     for (int e = lane; e < nb * JPW; e += 64) sjm[e] = gj[(e / JPW) * JP + JOFF + e % JPW];
     for (int e = lane; e < ncon * CP; e += 64) scm[e] = gc[e];
   }
   if constexpr (!PRE) {
-    for (int e = lane; e < a.nq; e += 64) sq[e] = sr[a.o_q + e];
+    for (int e = lane; e < a.md.nq; e += 64) sq[e] = sr[a.rv.sol_off(RTOC_SOL_Q) + e];
     for (int e = lane; e < nv; e += 64) {
-      sv[e] = sr[a.o_v + e];
-      sa[e] = sr[a.o_a + e];
+      sv[e] = sr[a.rv.sol_off(RTOC_SOL_V) + e];
+      sa[e] = sr[a.rv.sol_off(RTOC_SOL_A) + e];
     }
-    for (int e = lane; e < g.dimf; e += 64) sf[e] = sr[a.o_f + e];
-    for (int e = lane; e < nu; e += 64) su[e] = sr[a.o_u + e];
+    for (int e = lane; e < g.dimf; e += 64) sf[e] = sr[a.rv.sol_off(RTOC_SOL_F) + e];
+    for (int e = lane; e < nu; e += 64) su[e] = sr[a.rv.sol_off(RTOC_SOL_U) + e];
   }
   if (aug) {
-    for (int e = lane; e < nv; e += 64) sbeta[e] = sr[a.o_beta + e];
-    for (int e = lane; e < g.dimf; e += 64) smu[e] = sr[a.o_mu + e];
+    for (int e = lane; e < nv; e += 64) sbeta[e] = sr[a.rv.sol_off(RTOC_SOL_BETA) + e];
+    for (int e = lane; e < g.dimf; e += 64) smu[e] = sr[a.rv.sol_off(RTOC_SOL_MU) + e];
     for (int e = lane; e < 6 * ncon; e += 64) slf[e] = 0.0;
   }
   __syncthreads();
-  const V3 grav = mk(a.gx, a.gy, a.gz);
+  const V3 grav = mk(a.md.gx, a.md.gy, a.md.gz);
   // impact grids: a dynamics traversal (zero gravity, zero velocity, acceleration = dv; robot.hxx:590-624) and a
   // kinematics traversal at v + dv for the contact-velocity rows (impact_stage.cpp:61); other grids: one traversal
   const int ntrav = impact ? 2 : 1;
   for (int trav = 0; trav < ntrav; ++trav) {
     const bool dyn = trav == 0;                 // writes ID and its derivatives
     const bool rows = !impact || trav == 1;     // writes C and its derivatives
-    for (int j0 = 0, ps = 0; j0 < nv; j0 += a.dpp, ++ps) {
+    for (int j0 = 0, ps = 0; j0 < nv; j0 += a.md.dpp, ++ps) {
       const int j = j0 + lane / 3, kind = lane % 3;  // 0: q, 1: v, 2: a
-      const bool lane_on = lane < 3 * a.dpp && j < nv;
+      const bool lane_on = lane < 3 * a.md.dpp && j < nv;
       // (without the values pre-pass every pass accumulates the forces of all bodies: no skipping)
-      const unsigned long long visit_mask = PRE ? a.model->pass_bodies[ps] : ~0ull;
+      const unsigned long long visit_mask = PRE ? a.rv.model->pass_bodies[ps] : ~0ull;
       int top = -1;
       double wsum = 0.0;  // this lane's column of [dID; dC] against [beta; mu]
       // body of the level that is being closed / visited is kept in LDS as an int in the value block
@@ -638,18 +614,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         const bool own = lane_on && j >= iv && j < iv + (cff ? 6 : 1);
         if (dyn) {
           // tau = S^T f: value (lane 0) and this lane's column
-          double* const dcol = kind == 2 ? cr + a.o_didda + (size_t)j * nv : cr + a.o_didcdqv + (size_t)(kind == 1 ? nv + j : j) * a.ldv;
+          double* const dcol = kind == 2 ? cr + a.rv.cdd_off(RTOC_CDD_DIDDA) + (size_t)j * nv : cr + a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max;
           if (cff) {
             const double fv[6] = {f.l.x, f.l.y, f.l.z, f.a.x, f.a.y, f.a.z}, dv6[6] = {df.l.x, df.l.y, df.l.z, df.a.x, df.a.y, df.a.z};
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
-              if (!PRE && lane == 0 && j0 == 0) cr[a.o_idc + iv + k] = fv[k] - ((!impact && iv + k >= nv - nu) ? su[iv + k - (nv - nu)] : 0.0);
+              if (!PRE && lane == 0 && j0 == 0) cr[a.rv.cdd_off(RTOC_CDD_IDC) + iv + k] = fv[k] - ((!impact && iv + k >= nv - nu) ? su[iv + k - (nv - nu)] : 0.0);
               if (lane_on) dcol[iv + k] = dv6[k];
               if (aug) wsum += dv6[k] * sbeta[iv + k];
             }
           } else {
             const V3 ax = ldv3(&JM(i, 12));
-            if (!PRE && lane == 0 && j0 == 0) cr[a.o_idc + iv] = dot(ax, f.a) - ((!impact && iv >= nv - nu) ? su[iv - (nv - nu)] : 0.0);
+            if (!PRE && lane == 0 && j0 == 0) cr[a.rv.cdd_off(RTOC_CDD_IDC) + iv] = dot(ax, f.a) - ((!impact && iv >= nv - nu) ? su[iv - (nv - nu)] : 0.0);
             if (lane_on) dcol[iv] = dot(ax, df.a);
             if (aug) wsum += dot(ax, df.a) * sbeta[iv];
           }
@@ -670,7 +646,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
           if ((visit_mask >> i) & 1ull) continue;
           const int iv = (int)JM(i, 30);
           if (dyn && lane_on) {
-            double* const dcol = kind == 2 ? cr + a.o_didda + (size_t)j * nv : cr + a.o_didcdqv + (size_t)(kind == 1 ? nv + j : j) * a.ldv;
+            double* const dcol = kind == 2 ? cr + a.rv.cdd_off(RTOC_CDD_DIDDA) + (size_t)j * nv : cr + a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max;
             const int ndof = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER ? 6 : 1;
             for (int k = 0; k < ndof; ++k) dcol[iv + k] = 0.0;
           }
@@ -681,8 +657,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
               const int nr = (SURF && (int)scm[c * CP + 15] == RTOC_CONTACT_SURFACE) ? 6 : 3;
               if (on && (int)scm[c * CP + 14] == i && lane_on)
                 for (int t = 0; t < nr; ++t) {
-                  if (kind == 2 || (impact && kind == 1)) cr[a.o_dcda + (size_t)j * a.nf_max + roff + t] = 0.0;
-                  if (kind != 2) cr[a.o_didcdqv + (size_t)(kind == 1 ? nv + j : j) * a.ldv + nv + roff + t] = 0.0;
+                  if (kind == 2 || (impact && kind == 1)) cr[a.rv.cdd_off(RTOC_CDD_DCDA) + (size_t)j * a.rv.L.dims.nf_max + roff + t] = 0.0;
+                  if (kind != 2) cr[a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max + nv + roff + t] = 0.0;
                 }
               roff += on ? nr : 0;
             }
@@ -690,8 +666,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         }
       const double* const vblk = PRE ? (dyn ? a.vals : a.vals2) + rec * (size_t)nb * VAL_SLOTS : nullptr;
       double pv = PRE ? vblk[lane] : 0.0;   // body 0 is in every pass
-      const int* const vlist = a.model->pass_visit[ps];
-      const int nvisit = PRE ? sload_int(a.model->pass_nvisit + ps) : nb;
+      const int* const vlist = a.rv.model->pass_visit[ps];
+      const int nvisit = PRE ? sload_int(a.rv.model->pass_nvisit + ps) : nb;
       for (int t = 0; t < nvisit; ++t) {
         const int i = PRE ? sload_int(vlist + t) : t;   // the bodies a direction of this pass moves or loads, depth first
         const int d = (int)JM(i, 31);
@@ -701,7 +677,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
           --top;
         }
         // ---- visit body i at level d ----
-        const int wk = sload_int(a.model->walk + i);
+        const int wk = sload_int(a.rv.model->walk + i);
         const bool chain = wk & 1, leaf = wk & 2;
         const int sslot = ((wk >> 4) & 15) - 1, pslot = ((wk >> 8) & 15) - 1;
         const int iq = (int)JM(i, 29), iv = (int)JM(i, 30);
@@ -842,7 +818,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
                 const double kp = scm[c * CP + 12], kd = scm[c * CP + 13];
                 const M3 oRf = mul(oR, Rf);
                 const V3 pw = op + mul(oR, pf);
-                const V3 pr = a.positions ? ldv3(a.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
+                const V3 pr = a.rv.positions ? ldv3(a.rv.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
                 // the frame Jacobian column of dof j is the v-tangent of vf, one lane up (kind 0 lanes only use it)
                 const SV jc = SV{mk(__shfl_down(dvf.l.x, 1, 64), __shfl_down(dvf.l.y, 1, 64), __shfl_down(dvf.l.z, 1, 64)),
                                  mk(__shfl_down(dvf.a.x, 1, 64), __shfl_down(dvf.a.y, 1, 64), __shfl_down(dvf.a.z, 1, 64))};
@@ -855,8 +831,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
                 } else {
                   // spatial acceleration + kd v + kp Log6(X_desired^-1 X_frame)   (surface_contact.hxx:12-29, :31-68)
                   M3 Rd;
-                  if (a.rotations) {
-                    Rd = ldm3(a.rotations + ((size_t)st * ncon + c) * 9);
+                  if (a.rv.rotations) {
+                    Rd = ldm3(a.rv.rotations + ((size_t)st * ncon + c) * 9);
                   } else {
 #pragma unroll
                     for (int e = 0; e < 9; ++e) Rd.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
@@ -892,11 +868,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
 #pragma unroll
               for (int t = 0; t < 6; ++t) {
                 if (t < nr) {
-                  if (!PRE && lane == 0 && j0 == 0) cr[a.o_idc + r0 + t] = Cv[t];   // PRE: rbd_values_kernel wrote the values
+                  if (!PRE && lane == 0 && j0 == 0) cr[a.rv.cdd_off(RTOC_CDD_IDC) + r0 + t] = Cv[t];   // PRE: rbd_values_kernel wrote the values
                   if (lane_on) {
                     // impact: dC/dv = dC/d(dv) goes where the condensation reads it (the v block of DIDCDQV) and into DCDA
-                    if (kind == 2 || (impact && kind == 1)) cr[a.o_dcda + (size_t)j * a.nf_max + (r0 - nv) + t] = dCv[t];
-                    if (kind != 2) cr[a.o_didcdqv + (size_t)(kind == 1 ? nv + j : j) * a.ldv + r0 + t] = dCv[t];
+                    if (kind == 2 || (impact && kind == 1)) cr[a.rv.cdd_off(RTOC_CDD_DCDA) + (size_t)j * a.rv.L.dims.nf_max + (r0 - nv) + t] = dCv[t];
+                    if (kind != 2) cr[a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max + r0 + t] = dCv[t];
                   }
                 }
               }
@@ -934,20 +910,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
       }
       if (aug && lane_on) {
         // lq / lv / la (ldv) += (this lane's column)^T [beta; mu]  (contact_dynamics.cpp:35-37,49-51; impact_dynamics.cpp:19-25)
-        double* const kr = a.kkt + rec * a.kkt_stride;
-        double* const dst = kind == 0 ? kr + a.o_lx + j : kind == 1 ? kr + a.o_lx + nv + j : a.unconstr ? kr + a.o_lu + j : cr + a.o_la + j;
+        double* const kr = a.rv.kkt_at(rec);
+        double* const dst = kind == 0 ? kr + a.rv.kkt_off(RTOC_KKT_LX) + j : kind == 1 ? kr + a.rv.kkt_off(RTOC_KKT_LX) + nv + j : a.unconstr ? kr + a.rv.kkt_off(RTOC_KKT_LU) + j : cr + a.rv.cdd_off(RTOC_CDD_LA) + j;
         if (!(impact && dyn && kind == 1)) *dst += a.scale * wsum;
       }
     }
   }
   if (aug) {
     __syncthreads();
-    double* const kr = a.kkt + rec * a.kkt_stride;
-    if (lane < g.dimf) cr[a.o_lf + lane] -= slf[lane];
+    double* const kr = a.rv.kkt_at(rec);
+    if (lane < g.dimf) cr[a.rv.cdd_off(RTOC_CDD_LF) + lane] -= slf[lane];
     if (a.unconstr) {
-      if (lane < nv) cr[a.o_la + lane] -= a.scale * sbeta[lane];                         // lu -= dt beta (:63)
-    } else if (!impact && lane < nu) kr[a.o_lu + lane] -= sbeta[nv - nu + lane];           // lu -= beta (actuated part)
-    if (nu < nv && lane < nv - nu) cr[a.o_lup + lane] = impact ? 0.0 : sr[a.o_nup + lane] - sbeta[lane];  // lu_passive
+      if (lane < nv) cr[a.rv.cdd_off(RTOC_CDD_LA) + lane] -= a.scale * sbeta[lane];                         // lu -= dt beta (:63)
+    } else if (!impact && lane < nu) kr[a.rv.kkt_off(RTOC_KKT_LU) + lane] -= sbeta[nv - nu + lane];           // lu -= beta (actuated part)
+    if (nu < nv && lane < nv - nu) cr[a.rv.cdd_off(RTOC_CDD_LUP) + lane] = impact ? 0.0 : sr[a.rv.sol_off(RTOC_SOL_NUP) + lane] - sbeta[lane];  // lu_passive
   }
 }
 
@@ -962,32 +938,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
 // cost: [q_ref | v_ref | u_ref | wq | wv | wa | wu | wq_terminal | wv_terminal | impact weights x 3], nv + 1 doubles each
 // (the table of contact_eval_kkt.hpp).
 struct UkArgs {
-  const double* sol;
-  double* kkt;
-  double* cdd;
+  RecView rv;         // dx0: [batch][2 nv] computeInitialStateDirection: x0 - s[0].x
   const double* cost;
   const double* x0;   // [batch][2 nv] initial state of the horizon (q, v of updateSolution(t, q, v)); may be nullptr
-  double* dx0;        // [batch][2 nv] computeInitialStateDirection: x0 - s[0].x
-  int nstages, batch, nv;
   double dt;
-  int sol_stride, kkt_stride, cdd_stride;
-  int o_q, o_v, o_a, o_u, o_lmd, o_gmm;
-  int o_qxx, o_qxu, o_quu, o_fx, o_lx, o_lu;
-  int o_qaa, o_la, o_mj;
   double* cost_out;   // [batch][nstages] value of the stage / terminal cost (the line search's evalOCP reads it), or nullptr
 };
 
 static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) {
   const int lane = threadIdx.x;
-  const int b = blockIdx.x / a.nstages, st = blockIdx.x % a.nstages;
-  if (b >= a.batch) return;
-  const int nv = a.nv, nx = 2 * nv;
-  const bool terminal = st == a.nstages - 1;
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  const double* const sn = s + a.sol_stride;  // next grid point (not read on the terminal one)
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
+  const int b = blockIdx.x / a.rv.nstages, st = blockIdx.x % a.rv.nstages;
+  if (b >= a.rv.batch) return;
+  const int nv = a.rv.nv(), nx = 2 * nv;
+  const bool terminal = st == a.rv.nstages - 1;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  const double* const sn = s + a.rv.L.sol.stride;  // next grid point (not read on the terminal one)
+  double* const kr = a.rv.kkt_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
   const int M = nv + 1;
   const double *qr = a.cost, *vr = qr + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M,
                *wqf = wu + M, *wvf = wqf + M;
@@ -997,40 +965,40 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
     const int r = e % nx, c = e / nx;
     double v = 0.0;
     if (r == c) v = terminal ? (r < nv ? wqf[r] : wvf[r - nv]) : dt * (r < nv ? wq[r] : wv[r - nv]);
-    kr[a.o_qxx + e] = v;
+    kr[a.rv.kkt_off(RTOC_KKT_QXX) + e] = v;
   }
-  for (int e = lane; e < nx * nv; e += 64) kr[a.o_qxu + e] = 0.0;
-  for (int e = lane; e < nv * nv; e += 64) kr[a.o_quu + e] = (!terminal && e % nv == e / nv) ? dt * wa[e % nv] : 0.0;
-  for (int e = lane; e < nv * nv; e += 64) cr[a.o_mj + e] = 0.0;  // off-diagonal part of Quu: a diagonal cost
+  for (int e = lane; e < nx * nv; e += 64) kr[a.rv.kkt_off(RTOC_KKT_QXU) + e] = 0.0;
+  for (int e = lane; e < nv * nv; e += 64) kr[a.rv.kkt_off(RTOC_KKT_QUU) + e] = (!terminal && e % nv == e / nv) ? dt * wa[e % nv] : 0.0;
+  for (int e = lane; e < nv * nv; e += 64) cr[a.rv.cdd_off(RTOC_CDD_MJTJINV) + e] = 0.0;  // off-diagonal part of Quu: a diagonal cost
   for (int i = lane; i < nv; i += 64) {
-    const double q = s[a.o_q + i], v = s[a.o_v + i], lmd = s[a.o_lmd + i], gmm = s[a.o_gmm + i];
+    const double q = s[a.rv.sol_off(RTOC_SOL_Q) + i], v = s[a.rv.sol_off(RTOC_SOL_V) + i], lmd = s[a.rv.sol_off(RTOC_SOL_LMD) + i], gmm = s[a.rv.sol_off(RTOC_SOL_GMM) + i];
     if (terminal) {
-      kr[a.o_lx + i] = wqf[i] * (q - qr[i]) - lmd;        // evalTerminalCostDerivatives + ...ForwardEulerTerminal
-      kr[a.o_lx + nv + i] = wvf[i] * (v - vr[i]) - gmm;
-      kr[a.o_fx + i] = 0.0, kr[a.o_fx + nv + i] = 0.0;
-      kr[a.o_lu + i] = 0.0;
-      cr[a.o_qaa + i] = 0.0, cr[a.o_la + i] = 0.0;
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = wqf[i] * (q - qr[i]) - lmd;        // evalTerminalCostDerivatives + ...ForwardEulerTerminal
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] = wvf[i] * (v - vr[i]) - gmm;
+      kr[a.rv.kkt_off(RTOC_KKT_FX) + i] = 0.0, kr[a.rv.kkt_off(RTOC_KKT_FX) + nv + i] = 0.0;
+      kr[a.rv.kkt_off(RTOC_KKT_LU) + i] = 0.0;
+      cr[a.rv.cdd_off(RTOC_CDD_QAA) + i] = 0.0, cr[a.rv.cdd_off(RTOC_CDD_LA) + i] = 0.0;
     } else {
-      const double acc = s[a.o_a + i], u = s[a.o_u + i];
-      const double qn = sn[a.o_q + i], vn = sn[a.o_v + i], lmdn = sn[a.o_lmd + i], gmmn = sn[a.o_gmm + i];
-      kr[a.o_fx + i] = q + dt * v - qn;                                            // Fq (:60)
-      kr[a.o_fx + nv + i] = v + dt * acc - vn;                                     // Fv (:61)
-      kr[a.o_lx + i] = dt * wq[i] * (q - qr[i]) + (lmdn - lmd);                    // lq
-      kr[a.o_lx + nv + i] = dt * wv[i] * (v - vr[i]) + (dt * lmdn + gmmn - gmm);   // lv
-      kr[a.o_lu + i] = dt * wa[i] * acc + dt * gmmn;                               // la (in the lu slot)
-      cr[a.o_la + i] = dt * wu[i] * (u - ur[i]);                                   // lu (in CDD.la)
-      cr[a.o_qaa + i] = dt * wu[i];                                                // diag(Quu)
+      const double acc = s[a.rv.sol_off(RTOC_SOL_A) + i], u = s[a.rv.sol_off(RTOC_SOL_U) + i];
+      const double qn = sn[a.rv.sol_off(RTOC_SOL_Q) + i], vn = sn[a.rv.sol_off(RTOC_SOL_V) + i], lmdn = sn[a.rv.sol_off(RTOC_SOL_LMD) + i], gmmn = sn[a.rv.sol_off(RTOC_SOL_GMM) + i];
+      kr[a.rv.kkt_off(RTOC_KKT_FX) + i] = q + dt * v - qn;                                            // Fq (:60)
+      kr[a.rv.kkt_off(RTOC_KKT_FX) + nv + i] = v + dt * acc - vn;                                     // Fv (:61)
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = dt * wq[i] * (q - qr[i]) + (lmdn - lmd);                    // lq
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] = dt * wv[i] * (v - vr[i]) + (dt * lmdn + gmmn - gmm);   // lv
+      kr[a.rv.kkt_off(RTOC_KKT_LU) + i] = dt * wa[i] * acc + dt * gmmn;                               // la (in the lu slot)
+      cr[a.rv.cdd_off(RTOC_CDD_LA) + i] = dt * wu[i] * (u - ur[i]);                                   // lu (in CDD.la)
+      cr[a.rv.cdd_off(RTOC_CDD_QAA) + i] = dt * wu[i];                                                // diag(Quu)
     }
   }
   if (a.cost_out) {
     // ConfigurationSpaceCost::evalStageCost / evalTerminalCost (configuration_space_cost.cpp:251-271, :323-338): the VALUE
     double l = 0.0;
     for (int i = lane; i < nv; i += 64) {
-      const double dq = s[a.o_q + i] - qr[i], dv = s[a.o_v + i] - vr[i];
+      const double dq = s[a.rv.sol_off(RTOC_SOL_Q) + i] - qr[i], dv = s[a.rv.sol_off(RTOC_SOL_V) + i] - vr[i];
       if (terminal) {
         l += wqf[i] * dq * dq + wvf[i] * dv * dv;
       } else {
-        const double acc = s[a.o_a + i], du = s[a.o_u + i] - ur[i];
+        const double acc = s[a.rv.sol_off(RTOC_SOL_A) + i], du = s[a.rv.sol_off(RTOC_SOL_U) + i] - ur[i];
         l += wq[i] * dq * dq + wv[i] * dv * dv + wa[i] * acc * acc + wu[i] * du * du;
       }
     }
@@ -1038,10 +1006,10 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
     for (int off = 32; off > 0; off >>= 1) l += __shfl_xor(l, off, 64);
     if (lane == 0) a.cost_out[rec] = (terminal ? 0.5 : 0.5 * dt) * l;
   }
-  if (st == 0 && a.x0 && a.dx0) {
+  if (st == 0 && a.x0 && a.rv.dx0) {
     for (int i = lane; i < nv; i += 64) {
-      a.dx0[(size_t)b * nx + i] = a.x0[(size_t)b * nx + i] - s[a.o_q + i];
-      a.dx0[(size_t)b * nx + nv + i] = a.x0[(size_t)b * nx + nv + i] - s[a.o_v + i];
+      a.rv.dx0[(size_t)b * nx + i] = a.x0[(size_t)b * nx + i] - s[a.rv.sol_off(RTOC_SOL_Q) + i];
+      a.rv.dx0[(size_t)b * nx + nv + i] = a.x0[(size_t)b * nx + nv + i] - s[a.rv.sol_off(RTOC_SOL_V) + i];
     }
   }
 }

@@ -16,6 +16,7 @@
 #include "../../include/rtoc_robot.h"
 #include "device_buffer.hpp"
 #include "kernel_set.hpp"
+#include "record_view.hpp"
 #include "rigid_body.hpp"
 #include "unconstr_constraints.hpp"
 #include "state_equation_lin.hpp"
@@ -778,6 +779,53 @@ static int ensure_buffer(rtoc_ctx* c, int b) {
   HIP_TRY(hipMemsetAsync(c->buf[b].p, 0, c->want[b] * sizeof(double), c->stream));
   c->epoch++;
   return RTOC_OK;
+}
+
+// The context as the evalKKT-side kernels see it (record_view.hpp).  Taken at every launch and never kept: rtoc_bind and the
+// trial iterate of the line search (eval_ocp_trial) change the pointers between launches.
+static RecView view(const rtoc_ctx* c) {
+  RecView v;
+  v.sol = c->buf[RTOC_BUF_SOL].p, v.kkt = c->buf[RTOC_BUF_KKT].p, v.cdd = c->buf[RTOC_BUF_CDD].p, v.con = c->buf[RTOC_BUF_CON].p;
+  v.dir = c->buf[RTOC_BUF_DIR].p, v.cone = c->buf[RTOC_BUF_CONE].p, v.se3 = c->buf[RTOC_BUF_SE3].p, v.dx0 = c->buf[RTOC_BUF_DX0].p;
+  v.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
+  v.grid = c->d_grid.p, v.active = c->d_active.p;
+  v.positions = c->has_cpos ? c->d_cpos.p : nullptr, v.rotations = c->has_crot ? c->d_crot.p : nullptr;
+  v.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
+  v.model = c->d_model.p;
+  v.nstages = c->nstages, v.batch = c->batch;
+  v.L = c->L;
+  return v;
+}
+// (c->h_model is set)
+static ModelDims model_dims(const rtoc_ctx* c) {
+  const rtoc_robot_model& m = c->h_model->m;
+  ModelDims d;
+  d.nq = m.nq, d.njoints = m.njoints, d.ncontacts = m.ncontacts;
+  d.nlevels = c->h_model->nlevels, d.nbranch = c->h_model->nbranch, d.dpp = c->h_model->dpp;
+  d.gs = 1;
+  while (d.gs < m.njoints) d.gs *= 2;
+  d.floating = m.type[0] == RTOC_JOINT_FREE_FLYER;
+  d.gx = m.gravity[0], d.gy = m.gravity[1], d.gz = m.gravity[2];
+  return d;
+}
+static bool grid_is_impact(const rtoc_grid& g) { return g.type == RTOC_GRID_IMPACT; }
+static bool grid_has_switching(const rtoc_grid& g) { return g.switching_constraint != 0; }
+// whether one of the first n grid points has the property
+static bool any_grid_point(const rtoc_ctx* c, int n, bool (*has)(const rtoc_grid&)) {
+  for (int i = 0; i < n; ++i)
+    if (has(c->h_grid[i])) return true;
+  return false;
+}
+// The non-terminal grid points with the property, for a kernel that is launched over them alone: their number, their indices in
+// sel[16] -- or 0 if there are none or more than 16 (the launch then covers every grid point)
+static int select_grid_points(const rtoc_ctx* c, bool (*has)(const rtoc_grid&), int* sel) {
+  int k = 0;
+  for (int i = 0; i + 1 < c->nstages; ++i)
+    if (has(c->h_grid[i])) {
+      if (k < 16) sel[k] = i;
+      ++k;
+    }
+  return k <= 16 ? k : 0;
 }
 
 // the buffers that more than one entry point allocates on first use
@@ -1904,8 +1952,7 @@ int rtoc_set_contact_schedule(rtoc_ctx* c, const unsigned* active, const double*
 static int ensure_rbd_values(rtoc_ctx* c) {
   if (!c->h_model) return RTOC_ERR_NOT_READY;
   const rtoc_robot_model& m = c->h_model->m;
-  bool any_impact = false;
-  for (int i = 0; i + 1 < c->nstages; ++i) any_impact = any_impact || c->h_grid[i].type == RTOC_GRID_IMPACT;
+  const bool any_impact = any_grid_point(c, c->nstages - 1, grid_is_impact);
   const size_t need = (size_t)c->batch * c->max_stages * m.njoints * rbd::VAL_SLOTS;
   if (c->d_vals.n < need) c->d_vals2.release();   // both grow together: the second one only on grids with an impact
   HIP_TRY(c->d_vals.grow(need));
@@ -1918,40 +1965,21 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   if (c->nstages < 2) return RTOC_OK;
-  const rtoc_robot_model& m = c->h_model->m;
-  bool any_impact = false;
-  for (int i = 0; i + 1 < c->nstages; ++i) any_impact = any_impact || c->h_grid[i].type == RTOC_GRID_IMPACT;
+  const bool any_impact = any_grid_point(c, c->nstages - 1, grid_is_impact);
   rc = ensure_rbd_values(c);
   if (rc) return rc;
   rbd::ValArgs v;
-  v.model = c->d_model.p, v.sol = c->buf[RTOC_BUF_SOL].p, v.cdd = c->buf[RTOC_BUF_CDD].p, v.grid = c->d_grid.p, v.active = c->d_active.p;
-  v.nstages = c->nstages, v.batch = c->batch, v.nv = m.nv, v.njoints = m.njoints, v.ncontacts = m.ncontacts;
-  v.nu = m.type[0] == RTOC_JOINT_FREE_FLYER ? m.nv - 6 : m.nv;
-  v.nlevels = c->h_model->nlevels, v.unconstr = unconstr ? 1 : 0;
-  v.gs = 1;
-  while (v.gs < m.njoints) v.gs *= 2;
-  v.sol_stride = c->L.sol.stride, v.cdd_stride = c->L.cdd.stride;
-  v.o_q = c->L.sol.off[RTOC_SOL_Q], v.o_v = c->L.sol.off[RTOC_SOL_V], v.o_a = c->L.sol.off[RTOC_SOL_A];
-  v.o_u = c->L.sol.off[RTOC_SOL_U], v.o_f = c->L.sol.off[RTOC_SOL_F], v.o_idc = c->L.cdd.off[RTOC_CDD_IDC];
-  v.gx = m.gravity[0], v.gy = m.gravity[1], v.gz = m.gravity[2];
-  v.positions = c->has_cpos ? c->d_cpos.p : nullptr, v.rotations = c->has_crot ? c->d_crot.p : nullptr;
-  const int G = 64 / v.gs;
+  v.rv = view(c), v.md = model_dims(c);
+  v.unconstr = unconstr ? 1 : 0;
+  const int G = 64 / v.md.gs;
   const long long items = (long long)c->batch * (c->nstages - 1);
-  const size_t vlds = sizeof(double) * G * m.njoints * rbd::VAL_SLOTS;
+  const size_t vlds = sizeof(double) * G * v.md.njoints * rbd::VAL_SLOTS;
   for (int trav = 0; trav < (any_impact ? 2 : 1); ++trav) {
     v.trav = trav;
     v.vals = trav == 0 ? c->d_vals.p : c->d_vals2.p;
-    v.nsel = 0;
-    long long n = items;
-    if (trav == 1) {   // the kinematics traversal exists on impact grids only: launch just those (if they fit the list)
-      int k = 0;
-      for (int i = 0; i + 1 < c->nstages && k <= 16; ++i)
-        if (c->h_grid[i].type == RTOC_GRID_IMPACT) {
-          if (k < 16) v.sel[k] = i;
-          ++k;
-        }
-      if (k <= 16) v.nsel = k, n = (long long)c->batch * k;
-    }
+    // the kinematics traversal exists on impact grids only: launch just those (if they fit the list)
+    v.nsel = trav == 1 ? select_grid_points(c, grid_is_impact, v.sel) : 0;
+    const long long n = v.nsel > 0 ? (long long)c->batch * v.nsel : items;
     hipLaunchKernelGGL(rbd::rbd_values_kernel, dim3((unsigned)((n + G - 1) / G)), dim3(64), vlds, c->stream, v);
   }
   HIP_TRY(hipGetLastError());
@@ -1965,45 +1993,8 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   rbd::LinArgs a;
-  a.model = c->d_model.p;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.grid = c->d_grid.p;
-  a.active = c->d_active.p;
-  a.positions = c->has_cpos ? c->d_cpos.p : nullptr;
-  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.sol_stride = c->L.sol.stride;
-  a.cdd_stride = c->L.cdd.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q];
-  a.o_v = c->L.sol.off[RTOC_SOL_V];
-  a.o_a = c->L.sol.off[RTOC_SOL_A];
-  a.o_u = c->L.sol.off[RTOC_SOL_U];
-  a.o_f = c->L.sol.off[RTOC_SOL_F];
-  a.o_idc = c->L.cdd.off[RTOC_CDD_IDC];
-  a.o_didda = c->L.cdd.off[RTOC_CDD_DIDDA];
-  a.o_dcda = c->L.cdd.off[RTOC_CDD_DCDA];
-  a.o_didcdqv = c->L.cdd.off[RTOC_CDD_DIDCDQV];
-  a.ldv = c->dims.nv + c->dims.nf_max;
-  a.nf_max = c->dims.nf_max;
-  {
-    const rtoc_robot_model& m = c->h_model->m;
-    a.nlevels = c->h_model->nlevels, a.nbranch = c->h_model->nbranch, a.dpp = c->h_model->dpp;
-    a.nv = m.nv, a.nq = m.nq, a.njoints = m.njoints, a.ncontacts = m.ncontacts;
-    a.nu = m.type[0] == RTOC_JOINT_FREE_FLYER ? m.nv - 6 : m.nv;
-    a.gx = m.gravity[0], a.gy = m.gravity[1], a.gz = m.gravity[2];
-  }
-  a.kkt = augment_residual ? c->buf[RTOC_BUF_KKT].p : nullptr;
-  a.kkt_stride = c->L.kkt.stride;
-  a.o_lx = c->L.kkt.off[RTOC_KKT_LX];
-  a.o_lu = c->L.kkt.off[RTOC_KKT_LU];
-  a.o_la = c->L.cdd.off[RTOC_CDD_LA];
-  a.o_lf = c->L.cdd.off[RTOC_CDD_LF];
-  a.o_lup = c->L.cdd.off[RTOC_CDD_LUP];
-  a.o_beta = c->L.sol.off[RTOC_SOL_BETA];
-  a.o_mu = c->L.sol.off[RTOC_SOL_MU];
-  a.o_nup = c->L.sol.off[RTOC_SOL_NUP];
+  a.rv = view(c), a.md = model_dims(c);
+  if (!augment_residual) a.rv.kkt = nullptr;
   a.unconstr = unconstr ? 1 : 0;
   a.scale = scale;
   if (c->nstages < 2) return RTOC_OK;
@@ -2085,22 +2076,9 @@ static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   if (!rc && c->dims.np == 6) rc = ensure_buffer(c, RTOC_BUF_SE3);
   if (rc) return rc;
   SeLinArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.rv = view(c);
   a.x0 = c->d_x0.p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.se3 = c->dims.np == 6 ? c->buf[RTOC_BUF_SE3].p : nullptr;
-  a.dx0 = c->d_x0.p ? c->buf[RTOC_BUF_DX0].p : nullptr;
-  a.grid = c->d_grid.p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.floating = c->dims.np == 6;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A];
-  a.o_lmd = c->L.sol.off[RTOC_SOL_LMD], a.o_gmm = c->L.sol.off[RTOC_SOL_GMM];
-  a.o_fxx = c->L.kkt.off[RTOC_KKT_FXX], a.o_fx = c->L.kkt.off[RTOC_KKT_FX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX];
-  a.o_hx = c->L.kkt.off[RTOC_KKT_HX], a.o_ffx = c->L.kkt.off[RTOC_KKT_FFX], a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
-  a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_ha = c->L.cdd.off[RTOC_CDD_HA];
   a.zeroed = zeroed ? 1 : 0;
-  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   hipLaunchKernelGGL(state_equation_lin_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fxx_state = zeroed ? 1 : 0;
@@ -2121,28 +2099,14 @@ int rtoc_set_constraint_bounds(rtoc_ctx* c, const double* bounds, int nrows, dou
 
 static int launch_ubox(rtoc_ctx* c, int mode, bool contact = false) {
   UboxArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.con = c->buf[RTOC_BUF_CON].p;
-  a.dir = c->buf[RTOC_BUF_DIR].p;
+  a.rv = view(c);
   a.rows = c->d_rows.p;
   a.entry = c->d_entry.p;
   a.bounds = c->d_bounds.p;
-  a.grid = c->d_grid.p;
-  a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nrows = c->nrows, a.nv = c->dims.nv, a.nu = c->dims.nu, a.mode = mode;
+  a.nrows = c->nrows, a.mode = mode;
   a.barrier = c->barrier, a.tau = c->ftb_rule;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
-  a.con_stride = c->L.con.stride, a.dir_stride = c->L.dir.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_u = c->L.sol.off[RTOC_SOL_U], a.o_a = c->L.sol.off[RTOC_SOL_A];
-  a.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX];
-  a.o_qaa = c->L.cdd.off[RTOC_CDD_QAA], a.o_la = c->L.cdd.off[RTOC_CDD_LA];
-  a.o_dx = c->L.dir.off[RTOC_DIR_DX], a.o_du = c->L.dir.off[RTOC_DIR_DU];
-  a.nl = c->L.con;
   a.contact = contact ? 1 : 0;
   a.q_shift = (contact && c->dims.np == 6) ? 1 : 0;
-  a.o_lu = c->L.kkt.off[RTOC_KKT_LU];
   hipLaunchKernelGGL(unconstr_box_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -2173,22 +2137,10 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   HIP_TRY(reserve_active(c, &fresh));
   if (fresh) HIP_TRY(hipMemsetAsync(c->d_active.p, 0, sizeof(unsigned) * c->max_stages, c->stream));  // no contacts: an all-zero schedule
   rbd::UkArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
+  a.rv = view(c);
   a.cost = c->d_cost.p;
   a.x0 = c->d_x0.p;
-  a.dx0 = c->buf[RTOC_BUF_DX0].p;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.nv = c->dims.nv;
   a.dt = dt;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A], a.o_u = c->L.sol.off[RTOC_SOL_U];
-  a.o_lmd = c->L.sol.off[RTOC_SOL_LMD], a.o_gmm = c->L.sol.off[RTOC_SOL_GMM];
-  a.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], a.o_qxu = c->L.kkt.off[RTOC_KKT_QXU], a.o_quu = c->L.kkt.off[RTOC_KKT_QUU];
-  a.o_fx = c->L.kkt.off[RTOC_KKT_FX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_lu = c->L.kkt.off[RTOC_KKT_LU];
-  a.o_qaa = c->L.cdd.off[RTOC_CDD_QAA], a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_mj = c->L.cdd.off[RTOC_CDD_MJTJINV];
   c->ls_unconstr_dt = dt;
   if (c->ls_on) HIP_TRY(reserve_costval(c));
   a.cost_out = c->ls_on ? c->d_costval.p : nullptr;   // the line search's evalOCP (unconstr_line_search.cpp:56-83)
@@ -2292,20 +2244,12 @@ static int launch_wrench_cones(rtoc_ctx* c, int mode) {
   for (int k = 0; k < m.ncontacts; ++k)
     if (m.contact_type[k] != RTOC_CONTACT_SURFACE) return RTOC_ERR_BAD_ARG;
   WcArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.con = c->buf[RTOC_BUF_CON].p;
-  a.cone = c->buf[RTOC_BUF_CONE].p;
+  a.rv = view(c), a.md = model_dims(c);
   a.table = c->d_wcone.p;
-  a.grid = c->d_grid.p;
-  a.active = c->d_active.p;
-  a.nstages = c->nstages, a.batch = c->batch, a.ncontacts = m.ncontacts, a.mode = mode;
+  a.mode = mode;
   a.row0 = c->dims.nc_max - RTOC_WRENCH_ROWS * c->cone_contacts, a.cone_stride = rtoc_wrench_cone_stride(c->cone_contacts);
   a.impact_cones = c->impact_cones;
   a.barrier = c->barrier;
-  a.sol_stride = c->L.sol.stride, a.cdd_stride = c->L.cdd.stride, a.con_stride = c->L.con.stride;
-  a.o_f = c->L.sol.off[RTOC_SOL_F], a.o_lf = c->L.cdd.off[RTOC_CDD_LF];
-  a.nl = c->L.con;
   hipLaunchKernelGGL(wrench_cone_eval_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -2318,26 +2262,14 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
   for (int k = 0; k < m.ncontacts; ++k)
     if ((m.contact_type[k] == RTOC_CONTACT_SURFACE ? 6 : 3) != c->cone_dim) return RTOC_ERR_BAD_ARG;
   CcArgs a;
-  a.model = c->d_model.p;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.con = c->buf[RTOC_BUF_CON].p;
-  a.cone = c->buf[RTOC_BUF_CONE].p;
-  a.grid = c->d_grid.p;
-  a.active = c->d_active.p;
-  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
+  a.rv = view(c), a.md = model_dims(c);
   a.mu = c->d_mu.p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nv = m.nv, a.njoints = m.njoints, a.ncontacts = m.ncontacts;
-  a.nlevels = c->h_model->nlevels, a.mode = mode;
+  a.mode = mode;
   a.contact_dim = c->cone_dim, a.row0 = c->dims.nc_max - RTOC_FRICTION_ROWS * c->cone_contacts;
   a.cone_stride = rtoc_cone_stride(c->dims.nv, c->cone_contacts), a.dgdf_off = rtoc_cone_dgdf_off(c->dims.nv, c->cone_contacts);
   a.impact_cones = c->impact_cones;
   a.exact_jacobian = c->exact_cone_jacobian;
   a.barrier = c->barrier;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride, a.con_stride = c->L.con.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_f = c->L.sol.off[RTOC_SOL_F], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_lf = c->L.cdd.off[RTOC_CDD_LF];
-  a.nl = c->L.con;
   if (mode == CC_LINEARIZE && c->vals_fresh && c->d_vals.p) {   // kinematics already there: no tree walk (contact_cone_vals_kernel)
     CvArgs v;
     v.c = a;
@@ -2346,7 +2278,7 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
     HIP_TRY(hipGetLastError());
     return RTOC_OK;
   }
-  const size_t lds = cc_lds_bytes(a.nlevels, a.njoints, a.ncontacts);
+  const size_t lds = cc_lds_bytes(a.md.nlevels, a.md.njoints, a.md.ncontacts);
   HIP_TRY(hipFuncSetAttribute((const void*)contact_cone_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(contact_cone_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
   HIP_TRY(hipGetLastError());
@@ -2372,37 +2304,14 @@ int rtoc_contact_init_constraints(rtoc_ctx* c) {
 
 // linearizeSwitchingConstraint (src/dynamics/switching_constraint.cpp:26-70) on the grids that carry one
 static int launch_switching_constraint(rtoc_ctx* c) {
-  const rtoc_robot_model& m = c->h_model->m;
   SwLinArgs a;
-  a.model = c->d_model.p;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.grid = c->d_grid.p;
-  a.active = c->d_active.p;
-  a.positions = c->has_cpos ? c->d_cpos.p : nullptr;
-  a.rotations = c->has_crot ? c->d_crot.p : nullptr;
-  a.nstages = c->nstages, a.batch = c->batch, a.nv = m.nv, a.nq = m.nq, a.njoints = m.njoints, a.ncontacts = m.ncontacts;
-  a.nlevels = c->h_model->nlevels, a.floating = m.type[0] == RTOC_JOINT_FREE_FLYER, a.ns_max = c->dims.ns_max;
+  a.rv = view(c), a.md = model_dims(c);
   a.exact_transport = c->exact_transport;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A], a.o_xi = c->L.sol.off[RTOC_SOL_XI];
-  a.o_phix = c->L.kkt.off[RTOC_KKT_PHIX], a.o_phit = c->L.kkt.off[RTOC_KKT_PHIT], a.o_pres = c->L.kkt.off[RTOC_KKT_PRES];
-  a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_hx = c->L.kkt.off[RTOC_KKT_HX], a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
-  a.o_phia = c->L.cdd.off[RTOC_CDD_PHIA], a.o_la = c->L.cdd.off[RTOC_CDD_LA], a.o_ha = c->L.cdd.off[RTOC_CDD_HA];
-  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   for (int i = 0; i < c->nstages; ++i)
     if (c->h_grid[i].switching_constraint && c->h_grid[i].dims > c->dims.ns_max) return RTOC_ERR_BAD_ARG;
-  a.nsel = 0;
-  int nsw = 0;
-  for (int i = 0; i + 1 < c->nstages; ++i)
-    if (c->h_grid[i].switching_constraint) {
-      if (nsw < 16) a.sel[nsw] = i;
-      ++nsw;
-    }
-  if (nsw <= 16) a.nsel = nsw;
+  a.nsel = select_grid_points(c, grid_has_switching, a.sel);
   const int per = a.nsel > 0 ? a.nsel : c->nstages - 1;
-  const size_t lds = sw_lds_bytes(a.nlevels, a.njoints, a.ncontacts);
+  const size_t lds = sw_lds_bytes(a.md.nlevels, a.md.njoints, a.md.ncontacts);
   HIP_TRY(hipFuncSetAttribute((const void*)switching_constraint_lin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(switching_constraint_lin_kernel, dim3(c->batch * per), dim3(64), lds, c->stream, a);
   HIP_TRY(hipGetLastError());
@@ -2482,21 +2391,14 @@ static int launch_task_costs(rtoc_ctx* c) {
   if (!c->sto_on && (int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
   if (c->sto_on && !c->d_gt_inst.p) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
   TaskCostArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
+  a.rv = view(c);
   a.cost_out = c->d_costval.p;
-  a.grid = c->d_grid.p;
-  a.model = c->d_model.p;
   a.terms = c->d_tasks.p;
   a.t_fixed = c->sto_on ? nullptr : c->d_gt.p;
   a.t_inst = c->sto_on ? c->d_gt_inst.p : nullptr;
-  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
-  a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.o_q = c->L.sol.off[RTOC_SOL_Q];
-  a.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], a.o_lx = c->L.kkt.off[RTOC_KKT_LX], a.o_hx = c->L.kkt.off[RTOC_KKT_HX];
-  a.o_scal = c->L.kkt.off[RTOC_KKT_SCAL];
+  a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
   // the 16-byte row pairs of Qqq need an even record stride and column length and an even field offset
-  if ((a.kkt_stride | a.o_qxx) & 1) return RTOC_ERR_BAD_ARG;
+  if ((c->L.kkt.stride | c->L.kkt.off[RTOC_KKT_QXX]) & 1) return RTOC_ERR_BAD_ARG;
   const long long items = (long long)c->batch * c->nstages;
   const size_t lds1 = sizeof(double) * task_cost_lds_doubles(c->h_model->m.njoints, c->ntasks, c->dims.nv);
   if (c->dims.nv <= 32) {
@@ -2511,8 +2413,7 @@ static int launch_task_costs(rtoc_ctx* c) {
 int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   CHECK_READY(c);
   if (!c->h_model || !c->d_active.p || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
-  bool switching = false;
-  for (int i = 0; i < c->nstages; ++i) switching = switching || c->h_grid[i].switching_constraint;
+  const bool switching = any_grid_point(c, c->nstages, grid_has_switching);
   int rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
@@ -2526,17 +2427,8 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   if (c->sto_on) STO_LAUNCH(sto_time_steps_kernel, c);
   HIP_TRY(reserve_costval(c));
   CostArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
+  a.rv = view(c);
   a.cost = c->d_cost.p;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.grid = c->d_grid.p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nv = c->dims.nv, a.nu = c->dims.nu;
-  a.nf_max = c->dims.nf_max, a.ns_max = c->dims.ns_max, a.floating = c->dims.np == 6;
-  a.sol_stride = c->L.sol.stride, a.kkt_stride = c->L.kkt.stride, a.cdd_stride = c->L.cdd.stride;
-  a.o_q = c->L.sol.off[RTOC_SOL_Q], a.o_v = c->L.sol.off[RTOC_SOL_V], a.o_a = c->L.sol.off[RTOC_SOL_A], a.o_u = c->L.sol.off[RTOC_SOL_U];
-  a.kl = c->L.kkt, a.cl = c->L.cdd;
-  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   a.cost_out = c->d_costval.p;
   {
     // setZero of the KKT records (+ the constant diagonals of the cost) as one stream on the context's second stream (rtoc_riccati_sweep's), BESIDE
@@ -2544,9 +2436,7 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
     // here zeroes): the one is bound by HBM writes, the other by latency -- 1.1 ms each per 4096 x 47 grid points, one after the
     // other on one stream.  The cost kernel and everything behind it wait for both.
     InitArgs ia;
-    ia.kkt = c->buf[RTOC_BUF_KKT].p, ia.cost = c->d_cost.p, ia.grid = c->d_grid.p, ia.dt_inst = a.dt_inst;
-    ia.nstages = c->nstages, ia.batch = c->batch, ia.nv = c->dims.nv, ia.nu = c->dims.nu, ia.floating = a.floating;
-    ia.kkt_stride = c->L.kkt.stride, ia.o_qxx = c->L.kkt.off[RTOC_KKT_QXX], ia.o_quu = c->L.kkt.off[RTOC_KKT_QUU], ia.o_fxx = c->L.kkt.off[RTOC_KKT_FXX];
+    ia.rv = a.rv, ia.cost = c->d_cost.p;
     const long long nrec = (long long)c->batch * c->nstages;
     // four workgroups per CU: half of the wave slots, so that the pre-pass's waves are resident beside them
     // (CUs from the device: four workgroups each)
@@ -2556,7 +2446,7 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
     // init_records_kernel moves 16-byte pairs that must not straddle a field: record stride, the three fields it writes constants
     // into and the state dimension are even (rtoc_compute_layout pads fields to 64 B; checked here so that a layout change cannot
     // silently misplace the cost diagonals)
-    if ((ia.kkt_stride | ia.o_qxx | ia.o_quu | ia.o_fxx) & 1) return RTOC_ERR_BAD_ARG;
+    if ((c->L.kkt.stride | c->L.kkt.off[RTOC_KKT_QXX] | c->L.kkt.off[RTOC_KKT_QUU] | c->L.kkt.off[RTOC_KKT_FXX]) & 1) return RTOC_ERR_BAD_ARG;
     // the (re)allocation of the pre-pass's scratch synchronises the device: ahead of the fork, never under it
     if (!c->linearize_fused) {
       rc = ensure_rbd_values(c);

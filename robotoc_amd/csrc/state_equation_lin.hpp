@@ -19,20 +19,9 @@
 namespace rtoc {
 
 struct SeLinArgs {
-  const double* sol;
+  RecView rv;            // se3: written on a floating base only; dx0: computeInitialStateDirection (state_equation.cpp:99-109), with x0 only
   const double* x0;      // [batch][nq + nv]: q_prev of grid point 0 (the initial state), may be nullptr -> q_prev = q
-  double* kkt;
-  double* cdd;
-  double* se3;           // may be nullptr on a fixed base
-  double* dx0;           // may be nullptr: computeInitialStateDirection (state_equation.cpp:99-109) into RTOC_BUF_DX0
-  const rtoc_grid* grid;
-  int nstages, batch, nv, floating;
   int zeroed;            // the KKT record was initialised just before (init_records_kernel: zeros, Fqq = I, Fqv = dt I): only the base corner is written
-  int sol_stride, kkt_stride, cdd_stride;
-  int o_q, o_v, o_a, o_lmd, o_gmm;
-  int o_fxx, o_fx, o_lx, o_hx, o_ffx, o_scal;
-  int o_la, o_ha;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
 };
 
 namespace selin {
@@ -129,24 +118,24 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
   using namespace selin;
   __shared__ double J[3][36];  // Fqq, Fqq_prev, d/dq0 of (q (-) q_next): 6 x 6, column-major
   const int lane = threadIdx.x;
-  const int b = blockIdx.x / a.nstages, st = blockIdx.x % a.nstages;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  const int b = blockIdx.x / a.rv.nstages, st = blockIdx.x % a.rv.nstages;
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   const bool impact = g.type == RTOC_GRID_IMPACT;
-  if (st == a.nstages - 1) {
+  if (st == a.rv.nstages - 1) {
     // linearizeTerminalStateEquation (src/dynamics/terminal_state_equation.cpp:8-28): lq -= lmd (base: += Fqq_prev^T lmd),
     // lv -= gmm; Fqq_prev_inv for correctCostateDirection / correctLinearizeTerminalStateEquation
-    const int nv = a.nv, nb = a.floating ? 6 : 0;
-    const size_t rec = (size_t)b * a.nstages + st;
-    const double* const s = a.sol + rec * a.sol_stride;
-    double* const kr = a.kkt + rec * a.kkt_stride;
+    const int nv = a.rv.nv(), nb = a.rv.floating() ? 6 : 0;
+    const size_t rec = (size_t)b * a.rv.nstages + st;
+    const double* const s = a.rv.sol_at(rec);
+    double* const kr = a.rv.kkt_at(rec);
     for (int i = lane; i < nv; i += 64) {
-      if (i >= nb) kr[a.o_lx + i] -= s[a.o_lmd + i];
-      kr[a.o_lx + nv + i] -= s[a.o_gmm + i];
+      if (i >= nb) kr[a.rv.kkt_off(RTOC_KKT_LX) + i] -= s[a.rv.sol_off(RTOC_SOL_LMD) + i];
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] -= s[a.rv.sol_off(RTOC_SOL_GMM) + i];
     }
-    if (a.floating) {
-      const double* q = s + a.o_q;
-      const double* qp = s - a.sol_stride + a.o_q;
+    if (a.rv.floating()) {
+      const double* q = s + a.rv.sol_off(RTOC_SOL_Q);
+      const double* qp = s - a.rv.L.sol.stride + a.rv.sol_off(RTOC_SOL_Q);
       M3 R0;
       V3 p0;
       rel(quat_R(q + 3), rbd::ldv3(q), quat_R(qp + 3), rbd::ldv3(qp), R0, p0);
@@ -161,11 +150,11 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
       if (lane < 6) {
         double t = 0.0;
 #pragma unroll
-        for (int r = 0; r < 6; ++r) t += J[1][r + 6 * lane] * s[a.o_lmd + r];
-        kr[a.o_lx + lane] += t;
+        for (int r = 0; r < 6; ++r) t += J[1][r + 6 * lane] * s[a.rv.sol_off(RTOC_SOL_LMD) + r];
+        kr[a.rv.kkt_off(RTOC_KKT_LX) + lane] += t;
       }
-      if (lane == 0 && a.se3) {
-        double* const se = a.se3 + rec * RTOC_SE3_STRIDE;
+      if (lane == 0 && a.rv.se3) {
+        double* const se = a.rv.se3 + rec * RTOC_SE3_STRIDE;
         double A[36];
         inv6_block_ut(J[1], A);
 #pragma unroll
@@ -174,16 +163,16 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     }
     return;
   }
-  const double dt = impact ? 0.0 : grid_dt(a.grid, a.dt_inst, b, a.nstages, st);
-  const int nv = a.nv, nx = 2 * nv, nb = a.floating ? 6 : 0, nq = nv + (a.floating ? 1 : 0);
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  const double* const sn = s + a.sol_stride;
-  const double* const qp = st > 0 ? s - a.sol_stride + a.o_q : (a.x0 ? a.x0 + (size_t)b * (nq + nv) : s + a.o_q);
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
-  const double *q = s + a.o_q, *v = s + a.o_v, *acc = s + a.o_a, *lmd = s + a.o_lmd, *gmm = s + a.o_gmm;
-  const double *qn = sn + a.o_q, *vn = sn + a.o_v, *lmdn = sn + a.o_lmd, *gmmn = sn + a.o_gmm;
+  const double dt = impact ? 0.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
+  const int nv = a.rv.nv(), nx = 2 * nv, nb = a.rv.floating() ? 6 : 0, nq = nv + (a.rv.floating() ? 1 : 0);
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  const double* const sn = s + a.rv.L.sol.stride;
+  const double* const qp = st > 0 ? s - a.rv.L.sol.stride + a.rv.sol_off(RTOC_SOL_Q) : (a.x0 ? a.x0 + (size_t)b * (nq + nv) : s + a.rv.sol_off(RTOC_SOL_Q));
+  double* const kr = a.rv.kkt_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
+  const double *q = s + a.rv.sol_off(RTOC_SOL_Q), *v = s + a.rv.sol_off(RTOC_SOL_V), *acc = s + a.rv.sol_off(RTOC_SOL_A), *lmd = s + a.rv.sol_off(RTOC_SOL_LMD), *gmm = s + a.rv.sol_off(RTOC_SOL_GMM);
+  const double *qn = sn + a.rv.sol_off(RTOC_SOL_Q), *vn = sn + a.rv.sol_off(RTOC_SOL_V), *lmdn = sn + a.rv.sol_off(RTOC_SOL_LMD), *gmmn = sn + a.rv.sol_off(RTOC_SOL_GMM);
   // ---- Fxx top half: Fqq = I (joints), Fqv = dt I; the bottom half belongs to the dynamics condensation ----
   if (a.zeroed) {
     // rtoc_contact_eval_kkt: init_records_kernel has just written the record, zeros and the diagonals Fqq = I, Fqv = dt I with
@@ -191,7 +180,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
   } else {
     int r = lane % nx, c = lane / nx;
     for (int e = lane; e < nx * nx; e += 64) {
-      if (r < nv) kr[a.o_fxx + e] = (c == r) ? 1.0 : (c == nv + r ? dt : 0.0);
+      if (r < nv) kr[a.rv.kkt_off(RTOC_KKT_FXX) + e] = (c == r) ? 1.0 : (c == nv + r ? dt : 0.0);
       r += 64;
       while (r >= nx) r -= nx, ++c;
     }
@@ -199,17 +188,17 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
   // ---- joints and velocities ----
   for (int i = lane; i < nv; i += 64) {
     if (i >= nb) {
-      kr[a.o_fx + i] = q[(nb ? 1 : 0) + i] + dt * v[i] - qn[(nb ? 1 : 0) + i];   // Fq (:17-18), joints; q carries 7 base entries
-      kr[a.o_lx + i] += lmdn[i] - lmd[i];                                         // (:47-48 / :52)
+      kr[a.rv.kkt_off(RTOC_KKT_FX) + i] = q[(nb ? 1 : 0) + i] + dt * v[i] - qn[(nb ? 1 : 0) + i];   // Fq (:17-18), joints; q carries 7 base entries
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] += lmdn[i] - lmd[i];                                         // (:47-48 / :52)
     }
-    kr[a.o_fx + nv + i] = v[i] + (impact ? acc[i] : dt * acc[i]) - vn[i];         // Fv (:19; impact :15)
-    kr[a.o_lx + nv + i] += dt * lmdn[i] + gmmn[i] - gmm[i];                       // lv (:55; impact :53)
-    cr[a.o_la + i] += impact ? gmmn[i] : dt * gmmn[i];                            // la (:56) / ldv (impact :54)
+    kr[a.rv.kkt_off(RTOC_KKT_FX) + nv + i] = v[i] + (impact ? acc[i] : dt * acc[i]) - vn[i];         // Fv (:19; impact :15)
+    kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] += dt * lmdn[i] + gmmn[i] - gmm[i];                       // lv (:55; impact :53)
+    cr[a.rv.cdd_off(RTOC_CDD_LA) + i] += impact ? gmmn[i] : dt * gmmn[i];                            // la (:56) / ldv (impact :54)
     if (!impact) {                                                                 // STO sensitivities (:58-63)
-      kr[a.o_hx + nv + i] += lmdn[i];
-      cr[a.o_ha + i] += gmmn[i];
-      kr[a.o_ffx + i] = v[i];
-      kr[a.o_ffx + nv + i] = acc[i];
+      kr[a.rv.kkt_off(RTOC_KKT_HX) + nv + i] += lmdn[i];
+      cr[a.rv.cdd_off(RTOC_CDD_HA) + i] += gmmn[i];
+      kr[a.rv.kkt_off(RTOC_KKT_FFX) + i] = v[i];
+      kr[a.rv.kkt_off(RTOC_KKT_FFX) + nv + i] = acc[i];
     }
   }
   if (!impact) {
@@ -217,11 +206,11 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     for (int i = lane; i < nv; i += 64) h += lmdn[i] * v[i] + gmmn[i] * acc[i];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
-    if (lane == 0) kr[a.o_scal + RTOC_KKT_SCAL_H] += h;
+    if (lane == 0) kr[a.rv.kkt_off(RTOC_KKT_SCAL) + RTOC_KKT_SCAL_H] += h;
   }
-  if (st == 0 && a.dx0 && !a.floating && a.x0)
-    for (int i = lane; i < nx; i += 64) a.dx0[(size_t)b * nx + i] = a.x0[(size_t)b * nx + i] - (i < nv ? q[i] : v[i - nv]);
-  if (!a.floating) return;
+  if (st == 0 && a.rv.dx0 && !a.rv.floating() && a.x0)
+    for (int i = lane; i < nx; i += 64) a.rv.dx0[(size_t)b * nx + i] = a.x0[(size_t)b * nx + i] - (i < nv ? q[i] : v[i - nv]);
+  if (!a.rv.floating()) return;
   // ---- the free-flyer base: differences on SE(3) ----
   const M3 R = quat_R(q + 3), Rn = quat_R(qn + 3), Rp = quat_R(qp + 3);
   const V3 p = rbd::ldv3(q), pn = rbd::ldv3(qn), pp = rbd::ldv3(qp);
@@ -244,7 +233,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       J[m][r + 6 * c] = col[r];
-      if (m == 0) kr[a.o_fxx + r + (size_t)c * nx] = col[r];  // Fqq top-left corner
+      if (m == 0) kr[a.rv.kkt_off(RTOC_KKT_FXX) + r + (size_t)c * nx] = col[r];  // Fqq top-left corner
     }
     if (c == 0 && m < 2) {
       const double l6[6] = {val.l.x, val.l.y, val.l.z, val.a.x, val.a.y, val.a.z};
@@ -252,7 +241,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
       for (int r = 0; r < 6; ++r) sLog[m][r] = l6[r];
       if (m == 0) {   // Fq (base) = log6(X1) + dt v
 #pragma unroll
-        for (int r = 0; r < 6; ++r) kr[a.o_fx + r] = l6[r] + dt * v[r];
+        for (int r = 0; r < 6; ++r) kr[a.rv.kkt_off(RTOC_KKT_FX) + r] = l6[r] + dt * v[r];
       }
     }
   }
@@ -262,20 +251,20 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     double t = 0.0;
 #pragma unroll
     for (int r = 0; r < 6; ++r) t += J[0][r + 6 * lane] * lmdn[r] + J[1][r + 6 * lane] * lmd[r];
-    kr[a.o_lx + lane] += t;
+    kr[a.rv.kkt_off(RTOC_KKT_LX) + lane] += t;
   }
-  if (a.se3 && lane >= 32 && lane < 34) {
+  if (a.rv.se3 && lane >= 32 && lane < 34) {
     // two lanes, one block-triangular inverse each: Fqq_inv (from the d/dq0 Jacobian), Fqq_prev_inv
     const int which = lane - 32;
-    double* const se = a.se3 + rec * RTOC_SE3_STRIDE;
+    double* const se = a.rv.se3 + rec * RTOC_SE3_STRIDE;
     double A[36];
     inv6_block_ut(J[which == 0 ? 2 : 1], A);
 #pragma unroll
     for (int e = 0; e < 36; ++e) se[36 * which + e] = A[e];
-    if (which == 1 && st == 0 && a.dx0 && a.x0) {
+    if (which == 1 && st == 0 && a.rv.dx0 && a.x0) {
       // computeInitialStateDirection (:99-109): dq0 = q0 (-) s0.q = log6(M^-1 M0) = log6(X0) for the base, with the
       // -Fqq_prev_inv correction rtoc_compute_initial_state_direction would apply; joints and velocities plain
-      double* const o = a.dx0 + (size_t)b * nx;
+      double* const o = a.rv.dx0 + (size_t)b * nx;
 #pragma unroll
       for (int r = 0; r < 6; ++r) {
         double t = 0.0;

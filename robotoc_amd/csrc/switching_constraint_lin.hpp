@@ -19,22 +19,10 @@
 namespace rtoc {
 
 struct SwLinArgs {
-  const rbd::DevModel* model;
-  const double* sol;
-  double* kkt;
-  double* cdd;
-  const rtoc_grid* grid;
-  const unsigned* active;
-  const double* positions;  // [nstages][ncontacts][3] or nullptr
-  const double* rotations;  // [nstages][ncontacts][9] or nullptr (surface contacts)
-  int nstages, batch, nv, nq, njoints, ncontacts, nlevels, floating, ns_max;
+  RecView rv;
+  ModelDims md;
   int exact_transport;  // RTOC_OPT_SWITCHING_TRANSPORT
   int nsel, sel[16];    // the grid points with a switching constraint (nsel == 0: all grid points are launched)
-  int sol_stride, kkt_stride, cdd_stride;
-  int o_q, o_v, o_a, o_xi;
-  int o_phix, o_phit, o_pres, o_lx, o_hx, o_scal;
-  int o_phia, o_la, o_ha;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
 };
 
 __host__ __device__ constexpr size_t sw_lds_bytes(int nlevels, int njoints, int ncontacts) {
@@ -49,14 +37,14 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   // launched over the grid points that carry a switching constraint only (sel), or over all of them (nsel == 0)
-  const int nst1 = a.nsel > 0 ? a.nsel : a.nstages - 1;
+  const int nst1 = a.nsel > 0 ? a.nsel : a.rv.nstages - 1;
   const int b = blockIdx.x / nst1, st = a.nsel > 0 ? a.sel[blockIdx.x % nst1] : blockIdx.x % nst1;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
-  if (!g.switching_constraint || st + 2 >= a.nstages) return;
-  const int nv = a.nv, nx = 2 * nv, nb = a.njoints, ncon = a.ncontacts, nlev = a.nlevels, ns = g.dims, LDSW = a.ns_max;
-  const double dt1 = grid_dt(a.grid, a.dt_inst, b, a.nstages, st), dt2 = grid_dt(a.grid, a.dt_inst, b, a.nstages, st + 1);
-  const unsigned impact = a.active[st + 2];  // ImpactStatus of the impact two grid points ahead
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
+  if (!g.switching_constraint || st + 2 >= a.rv.nstages) return;
+  const int nv = a.rv.nv(), nx = 2 * nv, nb = a.md.njoints, ncon = a.md.ncontacts, nlev = a.md.nlevels, ns = g.dims, LDSW = a.rv.L.dims.ns_max;
+  const double dt1 = grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st), dt2 = grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st + 1);
+  const unsigned impact = a.rv.active[st + 2];  // ImpactStatus of the impact two grid points ahead
   double* const lval = smem;                               // [nlev][32]: R 9, p 3, oR 9, op 3, body index
   double* const ltan = lval + (size_t)nlev * 32;           // [nlev][6][64]
   double* const sjm = ltan + (size_t)nlev * 6 * 64;
@@ -67,29 +55,29 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   double* const spq = sxi + RTOC_MAX_JOINTS + 8;           // Pq base block [rows][8], then P residual etc.
   double* const sT = spq + 6 * RTOC_MAX_CONTACTS * 8;      // Tq (36) | Jr (36), column-major
   double* const sPq = sT + 72;                             // Pq [3 ncontacts][nv] row-major
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const cr = a.cdd + rec * a.cdd_stride;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const kr = a.rv.kkt_at(rec);
+  double* const cr = a.rv.cdd_at(rec);
   {
-    const double* const gj = &a.model->joint[0][0];
-    const double* const gc = &a.model->contact[0][0];
+    const double* const gj = &a.rv.model->joint[0][0];
+    const double* const gc = &a.rv.model->contact[0][0];
     for (int e = lane; e < nb * JP; e += 64) sjm[e] = gj[e];
     for (int e = lane; e < ncon * CP; e += 64) scm[e] = gc[e];
   }
-  for (int i = lane; i < nv; i += 64) sdq[i] = (dt1 + dt2) * s[a.o_v + i] + dt1 * dt2 * s[a.o_a + i];   // (:19)
-  for (int i = lane; i < ns; i += 64) sxi[i] = s[a.o_xi + i];
+  for (int i = lane; i < nv; i += 64) sdq[i] = (dt1 + dt2) * s[a.rv.sol_off(RTOC_SOL_V) + i] + dt1 * dt2 * s[a.rv.sol_off(RTOC_SOL_A) + i];   // (:19)
+  for (int i = lane; i < ns; i += 64) sxi[i] = s[a.rv.sol_off(RTOC_SOL_XI) + i];
   __syncthreads();
   // ---- q+ = q (+) dq (:20): joints additively, the base by the SE(3) exponential; X = exp6(dq_b) for the transports ----
-  const int nbase = a.floating ? 6 : 0;
-  for (int i = lane; i < nv - nbase; i += 64) sqp[(nbase ? 7 : 0) + i] = s[a.o_q + (nbase ? 7 : 0) + i] + sdq[nbase + i];
+  const int nbase = a.md.floating ? 6 : 0;
+  for (int i = lane; i < nv - nbase; i += 64) sqp[(nbase ? 7 : 0) + i] = s[a.rv.sol_off(RTOC_SOL_Q) + (nbase ? 7 : 0) + i] + sdq[nbase + i];
   M3 E;     // rotation of exp6(dq_b)
   V3 pe = rbd::mk(0, 0, 0);
 #pragma unroll
   for (int e = 0; e < 9; ++e) E.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
   M3 Rb;    // base rotation at q+
   V3 pb = rbd::mk(0, 0, 0);
-  if (a.floating) {
+  if (a.md.floating) {
     const V3 vl = rbd::mk(sdq[0], sdq[1], sdq[2]), w = rbd::mk(sdq[3], sdq[4], sdq[5]);
     const double th = sqrt(rbd::dot(w, w));
     double A, B;
@@ -112,9 +100,9 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
         for (int k = 0; k < 3; ++k) w2 += wx[3 * r + k] * wx[3 * k + c];
         E.m[3 * r + c] = (r == c ? 1.0 : 0.0) + sa * wx[3 * r + c] + A * w2;
       }
-    const M3 R0 = quat_R(s + a.o_q + 3);
+    const M3 R0 = quat_R(s + a.rv.sol_off(RTOC_SOL_Q) + 3);
     Rb = rbd::mul(R0, E);
-    pb = rbd::ldv3(s + a.o_q) + rbd::mul(R0, pe);
+    pb = rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_Q)) + rbd::mul(R0, pe);
   }
   __syncthreads();
   // ---- depth-first walk at q+: values per level, this lane's Jacobian column (body-frame twist per unit rate of dof j) ----
@@ -166,7 +154,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
         const V3 pf = rbd::ldv3(&scm[c * CP + 9]);
         const M3 oRf = rbd::mul(oR, Rf);
         const V3 pw = op + rbd::mul(oR, pf);
-        const V3 pr = a.positions ? rbd::ldv3(a.positions + ((size_t)(st + 2) * ncon + c) * 3) : rbd::mk(0, 0, 0);
+        const V3 pr = a.rv.positions ? rbd::ldv3(a.rv.positions + ((size_t)(st + 2) * ncon + c) * 3) : rbd::mk(0, 0, 0);
         const SV jf = rbd::act_inv(Rf, pf, Jc);   // this lane's column of the LOCAL frame Jacobian
         double* const Pres = spq + 6 * RTOC_MAX_CONTACTS * 4;
         if (!surf) {
@@ -180,7 +168,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
           for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc)
-              Rdt.m[3 * r + cc] = a.rotations ? a.rotations[((size_t)(st + 2) * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
+              Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[((size_t)(st + 2) * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
           SV lg, dlg;
           rbd::log6_fwd(rbd::mul(Rdt, oRf), rbd::mul(Rdt, pw - pr), jf, lg, dlg);
           const double pv[6] = {lg.l.x, lg.l.y, lg.l.z, lg.a.x, lg.a.y, lg.a.z}, dv6[6] = {dlg.l.x, dlg.l.y, dlg.l.z, dlg.a.x, dlg.a.y, dlg.a.z};
@@ -195,7 +183,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
     }
   }
   // ---- transports of the base block: Tq = Ad_{exp(dq_b)}^-1, Jr = Jlog6(exp6(dq_b))^-1 ----
-  if (a.floating && lane < 6) {
+  if (a.md.floating && lane < 6) {
     const SV t = rbd::act_inv(E, pe, unit_twist(lane));
     const double tc[6] = {t.l.x, t.l.y, t.l.z, t.a.x, t.a.y, t.a.z};
     SV val, der;
@@ -205,7 +193,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
     for (int r = 0; r < 6; ++r) sT[r + 6 * lane] = tc[r], sT[36 + r + 6 * lane] = jc[r];
   }
   __syncthreads();
-  if (a.floating && lane == 0) {   // Jlog6 is block upper-triangular in the (linear, angular) ordering: 3 x 3 cofactor inverses
+  if (a.md.floating && lane == 0) {   // Jlog6 is block upper-triangular in the (linear, angular) ordering: 3 x 3 cofactor inverses
     double A[36];
     inv6_block_ut(sT + 36, A);
 #pragma unroll
@@ -218,7 +206,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
     double lq = 0.0, lvv = 0.0, laa = 0.0, pqxi = 0.0;
     for (int r = 0; r < ns; ++r) {
       double pq = sPq[r * nv + j], pqq = pq, pqv = pq;
-      if (a.floating && j < 6) {
+      if (a.md.floating && j < 6) {
         pqq = 0.0, pqv = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -228,32 +216,32 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
           pqq += sPq[r * nv + k] * sT[e], pqv += sPq[r * nv + k] * sT[36 + e];
         }
       }
-      kr[a.o_phix + r + (size_t)j * LDSW] = pqq;                           // Phiq
-      kr[a.o_phix + r + (size_t)(nv + j) * LDSW] = (dt1 + dt2) * pqv;      // Phiv (:45-46)
-      cr[a.o_phia + r + (size_t)j * LDSW] = dt1 * dt2 * pqv;               // Phia
+      kr[a.rv.kkt_off(RTOC_KKT_PHIX) + r + (size_t)j * LDSW] = pqq;                           // Phiq
+      kr[a.rv.kkt_off(RTOC_KKT_PHIX) + r + (size_t)(nv + j) * LDSW] = (dt1 + dt2) * pqv;      // Phiv (:45-46)
+      cr[a.rv.cdd_off(RTOC_CDD_PHIA) + r + (size_t)j * LDSW] = dt1 * dt2 * pqv;               // Phia
       lq += pqq * sxi[r], lvv += (dt1 + dt2) * pqv * sxi[r], laa += dt1 * dt2 * pqv * sxi[r], pqxi += pq * sxi[r];
     }
-    kr[a.o_lx + j] += lq;                 // lx += Phix^T xi (:52)
-    kr[a.o_lx + nv + j] += lvv;
-    cr[a.o_la + j] += laa;                // la += Phia^T xi (:53)
-    kr[a.o_hx + nv + j] += 2.0 * pqxi;    // hv += 2 Pq^T xi (:61)
-    cr[a.o_ha + j] += 2.0 * dt1 * pqxi;   // ha += 2 dt1 Pq^T xi (:62)
+    kr[a.rv.kkt_off(RTOC_KKT_LX) + j] += lq;                 // lx += Phix^T xi (:52)
+    kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + j] += lvv;
+    cr[a.rv.cdd_off(RTOC_CDD_LA) + j] += laa;                // la += Phia^T xi (:53)
+    kr[a.rv.kkt_off(RTOC_KKT_HX) + nv + j] += 2.0 * pqxi;    // hv += 2 Pq^T xi (:61)
+    cr[a.rv.cdd_off(RTOC_CDD_HA) + j] += 2.0 * dt1 * pqxi;   // ha += 2 dt1 Pq^T xi (:62)
   }
   // Phit = Pq (2 (v + dt1 a)) (:56-57); h += xi . Phit (:58); Qtt += 2 (Pq^T xi) . a (:60)
   double hacc = 0.0, qacc = 0.0;
   for (int r = lane; r < ns; r += 64) {
     double t = 0.0, ta = 0.0;
-    for (int k = 0; k < nv; ++k) t += sPq[r * nv + k] * 2.0 * (s[a.o_v + k] + dt1 * s[a.o_a + k]), ta += sPq[r * nv + k] * s[a.o_a + k];
-    kr[a.o_phit + r] = t;
-    kr[a.o_pres + r] = P[r];
+    for (int k = 0; k < nv; ++k) t += sPq[r * nv + k] * 2.0 * (s[a.rv.sol_off(RTOC_SOL_V) + k] + dt1 * s[a.rv.sol_off(RTOC_SOL_A) + k]), ta += sPq[r * nv + k] * s[a.rv.sol_off(RTOC_SOL_A) + k];
+    kr[a.rv.kkt_off(RTOC_KKT_PHIT) + r] = t;
+    kr[a.rv.kkt_off(RTOC_KKT_PRES) + r] = P[r];
     hacc += sxi[r] * t;
     qacc += 2.0 * sxi[r] * ta;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) hacc += __shfl_xor(hacc, off, 64), qacc += __shfl_xor(qacc, off, 64);
   if (lane == 0) {
-    kr[a.o_scal + RTOC_KKT_SCAL_H] += hacc;
-    kr[a.o_scal + RTOC_KKT_SCAL_QTT] += qacc;
+    kr[a.rv.kkt_off(RTOC_KKT_SCAL) + RTOC_KKT_SCAL_H] += hacc;
+    kr[a.rv.kkt_off(RTOC_KKT_SCAL) + RTOC_KKT_SCAL_QTT] += qacc;
   }
 }
 

@@ -22,17 +22,12 @@
 namespace rtoc {
 
 struct TaskCostArgs {
-  const double* sol;
-  double* kkt;
+  RecView rv;
   double* cost_out;              // [batch][nstages] (evalOCP's stage costs), added to
-  const rtoc_grid* grid;
-  const rbd::DevModel* model;
   const rtoc_task_cost* terms;   // [nterms] or [batch][nterms]
   const double* t_fixed;         // [nstages] (fixed grids) or nullptr
   const double* t_inst;          // [batch][nstages] (switching-time optimisation) or nullptr
-  const double* dt_inst;         // per-instance time steps or nullptr (grid_dt)
-  int nstages, batch, nv, nterms, per_instance;
-  int sol_stride, kkt_stride, o_q, o_qxx, o_lx, o_hx, o_scal;
+  int nterms, per_instance;
 };
 
 namespace tsc {
@@ -93,25 +88,25 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   constexpr int LW = 64 / GP;
   extern __shared__ double tc_lds[];
   const int lane = threadIdx.x % LW, grp = threadIdx.x / LW;
-  const rbd::DevModel& md = *a.model;
-  const int nj = md.m.njoints, nv = a.nv, nx = 2 * nv, nt = a.nterms;
+  const rbd::DevModel& md = *a.rv.model;
+  const int nj = md.m.njoints, nv = a.rv.nv(), nx = 2 * nv, nt = a.nterms;
   double* const W = tc_lds + (size_t)grp * task_cost_lds_doubles(nj, nt, nv);
   double* const Rw = W;             // [nj][9]
   double* const pw = W + 9 * nj;    // [nj][3]
   double* const mc = W + 12 * nj;   // [nj][3]: mass x world centre of mass
   double* const Jl = W + 15 * nj;   // [nt][3][nv]
-  const long long nitems = (long long)a.batch * a.nstages;
+  const long long nitems = (long long)a.rv.batch * a.rv.nstages;
   long long item = (long long)blockIdx.x * GP + grp;
   const bool real = item < nitems;   // a trailing group without a grid point computes the last one and writes nothing
   item = real ? item : nitems - 1;
-  const int b = (int)(item / a.nstages), st = (int)(item % a.nstages);
-  const rtoc_grid g = a.grid[st];
-  const bool impact = g.type == RTOC_GRID_IMPACT, terminal = st == a.nstages - 1, sto = !terminal && !impact;
-  const double s = (impact || terminal) ? 1.0 : grid_dt(a.grid, a.dt_inst, b, a.nstages, st);
-  const double t = a.t_inst ? a.t_inst[(size_t)b * a.nstages + st] : (a.t_fixed ? a.t_fixed[st] : 0.0);
+  const int b = (int)(item / a.rv.nstages), st = (int)(item % a.rv.nstages);
+  const rtoc_grid g = a.rv.grid[st];
+  const bool impact = g.type == RTOC_GRID_IMPACT, terminal = st == a.rv.nstages - 1, sto = !terminal && !impact;
+  const double s = (impact || terminal) ? 1.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
+  const double t = a.t_inst ? a.t_inst[(size_t)b * a.rv.nstages + st] : (a.t_fixed ? a.t_fixed[st] : 0.0);
   const rtoc_task_cost* const terms = a.terms + (a.per_instance ? (size_t)b * nt : 0);
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const q = a.sol + rec * a.sol_stride + a.o_q;
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const q = a.rv.sol_at(rec) + a.rv.sol_off(RTOC_SOL_Q);
   // ---- which terms are on at this grid point (uniform over the group) ----
   unsigned on = 0;
   for (int k = 0; k < nt; ++k) {
@@ -238,16 +233,16 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   }
   __syncthreads();
   if (!real || on == 0) return;   // nothing active: the record is left as contact_cost_kernel wrote it
-  double* const kr = a.kkt + rec * a.kkt_stride;
-  double* const Qxx = kr + a.o_qxx;
+  double* const kr = a.rv.kkt_at(rec);
+  double* const Qxx = kr + a.rv.kkt_off(RTOC_KKT_QXX);
   for (int h = 0; h < 2; ++h) {
     const int j = lane + h * LW;
     if (j >= nv) break;
-    kr[a.o_lx + j] += s * lq[h];
-    if (sto) kr[a.o_hx + j] += lq[h];
+    kr[a.rv.kkt_off(RTOC_KKT_LX) + j] += s * lq[h];
+    if (sto) kr[a.rv.kkt_off(RTOC_KKT_HX) + j] += lq[h];
   }
   if (lane == 0) {
-    if (sto) kr[a.o_scal + RTOC_KKT_SCAL_H] += cost;
+    if (sto) kr[a.rv.kkt_off(RTOC_KKT_SCAL) + RTOC_KKT_SCAL_H] += cost;
     if (a.cost_out) a.cost_out[rec] += s * cost;
   }
   // ---- Qqq += s sum_k J_k^T W_k J_k: row pairs (r, r + 1) of column c to neighbouring lanes ----

@@ -18,57 +18,45 @@
 // contact path's own kernels (condense.hpp).
 #pragma once
 #include "device_utils.hpp"
-#include "../../include/rtoc.h"
+#include "record_view.hpp"
 
 namespace rtoc {
 
 struct UboxArgs {
-  const double* sol;
-  double* kkt;
-  double* cdd;
-  double* con;
-  const double* dir;
+  RecView rv;                   // CDD.Qaa / CDD.la: diag Quu, lu on the unconstrained path
   const rtoc_box_row* rows;
   const int* entry;           // CSR of the rows per primal entry (q_0.., v_0.., u_0..): [ne + 1] offsets, then row ids
   const double* bounds;
-  const rtoc_grid* grid;
-  unsigned long long* steps;  // [batch][2] bit patterns
-  int nstages, batch, nrows, nv, nu, mode;
+  int nrows, mode;
   double barrier, tau;
-  int sol_stride, kkt_stride, cdd_stride, con_stride, dir_stride;
-  int o_q, o_v, o_u, o_a;       // RTOC_BUF_SOL
-  int o_qxx, o_lx;              // RTOC_BUF_KKT
-  int o_qaa, o_la;              // RTOC_BUF_CDD (diag Quu, lu)
-  int o_dx, o_du;               // RTOC_BUF_DIR
   int contact;                  // contact path (rtoc_contact_eval_kkt): the u rows act on KKT.lu; INIT / LINEARIZE only
-  int q_shift, o_lu;            // nq - nv (the joint entries of q sit one further with a free-flyer's quaternion)
-  rtoc_record_layout nl;
+  int q_shift;                  // nq - nv (the joint entries of q sit one further with a free-flyer's quaternion)
 };
 enum { UBOX_INIT = 0, UBOX_LINEARIZE = 1, UBOX_CONDENSE = 2, UBOX_EXPAND = 3 };
 
 static __global__ __launch_bounds__(64) void unconstr_box_kernel(UboxArgs a) {
   const int lane = threadIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.rv.nstages - 1;
   const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;  // the terminal grid point has no rows
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
-  const size_t rec = (size_t)b * a.nstages + st;
-  const double* const s = a.sol + rec * a.sol_stride;
-  double* const kr = a.kkt ? a.kkt + rec * a.kkt_stride : nullptr;
-  double* const cr = a.cdd ? a.cdd + rec * a.cdd_stride : nullptr;
-  double* const nr = a.con + rec * a.con_stride;
-  const double* const dr = a.dir ? a.dir + rec * a.dir_stride : nullptr;
-  const int* const no = a.nl.off;
-  const int nv = a.nv, nx = 2 * nv;
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
+  const size_t rec = (size_t)b * a.rv.nstages + st;
+  const double* const s = a.rv.sol_at(rec);
+  double* const kr = a.rv.kkt ? a.rv.kkt_at(rec) : nullptr;
+  double* const cr = a.rv.cdd ? a.rv.cdd_at(rec) : nullptr;
+  double* const nr = a.rv.con_at(rec);
+  const double* const dr = a.rv.dir ? a.rv.dir_at(rec) : nullptr;
+  const int* const no = a.rv.L.con.off;
+  const int nv = a.rv.nv(), nx = 2 * nv;
   double fp = 1.0, fd = 1.0;
   auto value_of = [&](const rtoc_box_row& w) {
-    return w.var == RTOC_VAR_Q ? s[a.o_q + w.index + a.q_shift]
-                               : w.var == RTOC_VAR_V ? s[a.o_v + w.index] : w.var == RTOC_VAR_A ? s[a.o_a + w.index] : s[a.o_u + w.index];
+    return w.var == RTOC_VAR_Q ? s[a.rv.sol_off(RTOC_SOL_Q) + w.index + a.q_shift]
+                               : w.var == RTOC_VAR_V ? s[a.rv.sol_off(RTOC_SOL_V) + w.index] : w.var == RTOC_VAR_A ? s[a.rv.sol_off(RTOC_SOL_A) + w.index] : s[a.rv.sol_off(RTOC_SOL_U) + w.index];
   };
   if (a.mode == UBOX_LINEARIZE || a.mode == UBOX_CONDENSE) {
     // one lane per primal entry, its rows in row order: a lower and an upper limit meet on the same entry, and every
     // entry is accumulated by a single lane (deterministic, no atomics) -- like the box rows of condense_kernel
-    const int ne = 3 * nv + a.nu;  // q, v, u, a (rtoc_set_constraint_rows)
+    const int ne = 3 * nv + a.rv.nu();  // q, v, u, a (rtoc_set_constraint_rows)
     const int* const rowid = a.entry + (ne + 1);
     for (int t = lane; t < ne; t += 64) {
       double grad = 0.0, hess = 0.0;
@@ -89,19 +77,19 @@ static __global__ __launch_bounds__(64) void unconstr_box_kernel(UboxArgs a) {
         }
       }
       if (a.contact) {   // LINEARIZE only: the condensation of these rows is condense_kernel's
-        if (t < 2 * nv) kr[a.o_lx + t] += grad;
+        if (t < 2 * nv) kr[a.rv.kkt_off(RTOC_KKT_LX) + t] += grad;
         else if (a.entry[t + 1] > a.entry[t]) {
-          if (t < 2 * nv + a.nu) kr[a.o_lu + (t - 2 * nv)] += grad;
-          else cr[a.o_la + (t - 2 * nv - a.nu)] += grad;   // JointAcceleration*Limit::evalDerivatives: la -/+= dual
+          if (t < 2 * nv + a.rv.nu()) kr[a.rv.kkt_off(RTOC_KKT_LU) + (t - 2 * nv)] += grad;
+          else cr[a.rv.cdd_off(RTOC_CDD_LA) + (t - 2 * nv - a.rv.nu())] += grad;   // JointAcceleration*Limit::evalDerivatives: la -/+= dual
         }
-      } else if (t >= 2 * nv + a.nu) {
+      } else if (t >= 2 * nv + a.rv.nu()) {
         // (acceleration rows exist on the contact path only: rtoc_set_constraint_rows refuses them without contacts)
       } else if (t < 2 * nv) {
-        kr[a.o_lx + t] += grad;
-        kr[a.o_qxx + t + (size_t)t * nx] += hess;
+        kr[a.rv.kkt_off(RTOC_KKT_LX) + t] += grad;
+        kr[a.rv.kkt_off(RTOC_KKT_QXX) + t + (size_t)t * nx] += hess;
       } else {
-        cr[a.o_la + (t - 2 * nv)] += grad;
-        cr[a.o_qaa + (t - 2 * nv)] += hess;
+        cr[a.rv.cdd_off(RTOC_CDD_LA) + (t - 2 * nv)] += grad;
+        cr[a.rv.cdd_off(RTOC_CDD_QAA) + (t - 2 * nv)] += hess;
       }
     }
     return;
@@ -119,7 +107,7 @@ static __global__ __launch_bounds__(64) void unconstr_box_kernel(UboxArgs a) {
     }
     // UBOX_EXPAND
     const double slack = nr[no[RTOC_CON_SLACK] + r], dual = nr[no[RTOC_CON_DUAL] + r];
-    const double dz = w.var == RTOC_VAR_Q ? dr[a.o_dx + w.index] : w.var == RTOC_VAR_V ? dr[a.o_dx + nv + w.index] : dr[a.o_du + w.index];  // (no RTOC_VAR_A here)
+    const double dz = w.var == RTOC_VAR_Q ? dr[a.rv.dir_off(RTOC_DIR_DX) + w.index] : w.var == RTOC_VAR_V ? dr[a.rv.dir_off(RTOC_DIR_DX) + nv + w.index] : dr[a.rv.dir_off(RTOC_DIR_DU) + w.index];  // (no RTOC_VAR_A here)
     const double residual = nr[no[RTOC_CON_RESIDUAL] + r], cmpl = nr[no[RTOC_CON_CMPL] + r];
     const double dslack = -w.sign * dz - residual;
     const double ddual = -(dual * dslack + cmpl) / slack;
@@ -136,8 +124,8 @@ static __global__ __launch_bounds__(64) void unconstr_box_kernel(UboxArgs a) {
       fd = fmin(fd, __shfl_xor(fd, off, 64));
     }
     if (lane == 0) {
-      atomicMin(&a.steps[2 * b + 0], (unsigned long long)__double_as_longlong(fp));
-      atomicMin(&a.steps[2 * b + 1], (unsigned long long)__double_as_longlong(fd));
+      atomicMin(&a.rv.steps[2 * b + 0], (unsigned long long)__double_as_longlong(fp));
+      atomicMin(&a.rv.steps[2 * b + 1], (unsigned long long)__double_as_longlong(fd));
     }
   }
 }

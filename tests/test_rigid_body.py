@@ -422,6 +422,37 @@ def test_gpu_linearisation_matches_the_restatement_and_its_complex_step_derivati
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("fused", [False, True])
+def test_gpu_linearisation_without_the_multiplier_terms_leaves_the_kkt_records_alone(fused):
+    """rtoc_linearize_contact_dynamics(augment_residual = 0) writes RTOC_BUF_CDD only: the KKT buffer is withheld from the kernel,
+    whatever it holds stays bit for bit."""
+    m = model("anymal")
+    dims, grids, _ = pr.config_anymal_trot()
+    batch = 2
+    ctx = capi.Context(dims, len(grids), batch, 0)
+    try:
+        ctx.set_grid(grids)
+        ctx.set_robot_model(m)
+        ctx.set_linearize_fused(fused)
+        rng = np.random.default_rng(41)
+        ctx.set_contact_schedule(_masks(grids), rng.uniform(-0.5, 0.5, (len(grids), 4, 3)))
+        sol, o = np.zeros(ctx.shape("sol")), ctx.L.sol.off
+        for b in range(batch):
+            for i in range(len(grids)):
+                q, v, a = rm.random_configuration(m, rng, 0.8)
+                sol[b, i, o[0]:o[0] + m.nq], sol[b, i, o[1]:o[1] + m.nv], sol[b, i, o[2]:o[2] + m.nv] = q, v, a
+                sol[b, i, o[4]:o[4] + 12] = rng.uniform(-20, 20, 12)
+        kkt0 = rng.uniform(-1, 1, ctx.shape("kkt"))
+        ctx.upload(BUF_SOL, sol)
+        ctx.upload(BUF_KKT, kkt0)
+        ctx.linearize_contact_dynamics(augment_residual=False)
+        ctx.sync()
+        assert np.array_equal(ctx.download(BUF_KKT, ctx.shape("kkt")), kkt0)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dpp", [9, 6, 5])
 def test_gpu_linearisation_does_not_depend_on_the_passes(dpp):
     """ANYmal trot (ordinary, impact and flight grids): the linearisation and its multiplier terms with 2, 3 and 4 passes

@@ -146,3 +146,64 @@ def test_state_equation_linearisation_fixed_base():
             assert np.allclose(K.f(kkt[b, i], "lx"), lx, atol=1e-14)
         assert np.allclose(dx0[b], x0[b] - np.concatenate([S.f(sol[b, 0], "q")[:nv], S.f(sol[b, 0], "v")]), atol=1e-15)
     ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg", ["anymal_trot", "iiwa14"])
+def test_state_equation_without_an_initial_state_leaves_dx0_alone(cfg):
+    """A context that never had rtoc_set_initial_state: q_prev of grid point 0 is q itself (X0 = identity: Fqq_prev = -I on the
+    base, so lq[:6] gets Fqq^T lmd_next - lmd), and RTOC_BUF_DX0 is not written -- whatever it holds stays bit for bit."""
+    dims, grids, _ = getattr(pr, "config_" + cfg)()
+    batch, n, nv = 2, len(grids), dims.nv
+    ctx = capi.Context(dims, n, batch, 0)
+    try:
+        L = ctx.L
+        ctx.set_grid(grids)
+        rng = np.random.default_rng(14)
+        S, K = Records(L, "sol"), Records(L, "kkt")
+        sol = rng.uniform(-1, 1, ctx.shape("sol"))
+        if dims.np == 6:
+            sol[..., L.sol.off[0]:L.sol.off[0] + 7] = rng.uniform(-1, 1, (batch, 1, 7)) + 0.3 * rng.uniform(-1, 1, (batch, n, 7))
+            _unit_quats(sol, L.sol.off[0])
+        kkt0, dx00 = rng.uniform(-1, 1, ctx.shape("kkt")), rng.uniform(-1, 1, (batch, 2 * nv))
+        ctx.upload(BUF_SOL, sol)
+        ctx.upload(BUF_KKT, kkt0)
+        ctx.upload(BUF_CDD, rng.uniform(-1, 1, ctx.shape("cdd")))
+        ctx.upload(BUF_DX0, dx00)
+        ctx.linearize_state_equation()
+        ctx.sync()
+        assert np.array_equal(ctx.download(BUF_DX0, (batch, 2 * nv)), dx00)
+        kkt = ctx.download_records(BUF_KKT, "kkt")
+        if dims.np == 6:
+            se3 = ctx.download(BUF_SE3, (batch, n, 72))
+            for b in range(batch):
+                # q_prev = q: Fqq_prev = -Jlog6(I) Ad_I = -I, and so is its inverse
+                assert np.allclose(se3[b, 0, 36:].reshape(6, 6), -np.eye(6), atol=1e-14)
+                lmd, lmdn = S.f(sol[b, 0], "lmd"), S.f(sol[b, 1], "lmd")
+                Fqq = K.f(kkt[b, 0], "Fxx")[:6, :6]
+                want = K.f(kkt0[b, 0], "lx")[:6] + Fqq.T @ lmdn[:6] - lmd[:6]
+                assert np.allclose(K.f(kkt[b, 0], "lx")[:6], want, atol=1e-13)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_state_equation_on_a_fixed_base_does_not_touch_se3():
+    """RTOC_BUF_SE3 belongs to the free-flyer base: a fixed-base context linearises without it (the tests above never allocate
+    it), and one that has the buffer finds it unchanged bit for bit."""
+    dims, grids, _ = pr.config_iiwa14()
+    batch, n, nv = 2, len(grids), dims.nv
+    ctx = capi.Context(dims, n, batch, 0)
+    try:
+        ctx.set_grid(grids)
+        rng = np.random.default_rng(15)
+        se30 = rng.uniform(-1, 1, (batch, n, 72))
+        ctx.upload(BUF_SOL, rng.uniform(-1, 1, ctx.shape("sol")))
+        ctx.upload(BUF_KKT, rng.uniform(-1, 1, ctx.shape("kkt")))
+        ctx.upload(BUF_SE3, se30)
+        ctx.set_initial_state(rng.uniform(-1, 1, (batch, 2 * nv)))
+        ctx.linearize_state_equation()
+        ctx.sync()
+        assert np.array_equal(ctx.download(BUF_SE3, (batch, n, 72)), se30)
+    finally:
+        ctx.close()
