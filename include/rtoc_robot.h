@@ -112,31 +112,58 @@ int rtoc_contact_eval_kkt(rtoc_ctx* ctx);
  * intermediate / lift grids with `weight`, 1 on impact grids with `weight_impact` and on the terminal grid with
  * `weight_terminal`; on intermediate / lift grids also hx += J^T W diff and h += 1/2 sum W diff^2 (the STO sensitivities).
  * A term whose weight of the grid's kind is zero is off there, as in the reference (enable_cost_).
- * A frame term needs only the frame's origin in its parent joint's frame: the world-aligned linear Jacobian does not depend
- * on the frame's rotation. */
+ * A 3D frame term needs only the frame's origin in its parent joint's frame: the world-aligned linear Jacobian does not depend
+ * on the frame's rotation.
+ * TaskSpace6DCost (src/cost/task_space_6d_cost.cpp, include/robotoc/cost/task_space_6d_cost.hpp:184-214: the world placement of
+ * a frame): X = X_ref^-1 oMf, d = log6(X) in Pinocchio's Motion order [linear(3); angular(3)], JJ = Jlog6(X) J_frame with J_frame
+ * the LOCAL frame Jacobian; lq += s JJ^T W d, Qqq += s JJ^T W JJ, the value s/2 sum W d^2, s and W by the rules above.  Parity
+ * with Pinocchio's log6 / Jlog6 / getFrameJacobian is UNPINNED (Pinocchio is absent): the term is validated against a numpy
+ * restatement that is itself pinned by finite differences (tests/task_cost_6d_restatement.py).
+ * WEIGHT ORDER: the reference stores weight_.head<3>() = weight_rotation, tail<3>() = weight_position
+ * (task_space_6d_cost.cpp:124-125) and multiplies Log6Map(...) componentwise, whose first three components are the LINEAR part: the
+ * argument called "rotation" weights the linear components.  This struct carries the six weights in the order they multiply d
+ * (weight*: components 0..2, weight_angular*: components 3..5); the host classes fill them exactly as the reference's setters do.
+ * A per-grid-point reference table (RTOC_REF_TABLE, rtoc_set_task_ref_table) serves references that are the user's objects
+ * (TaskSpace6DRefBase / TaskSpace3DRefBase / CoMRefBase have no concrete class in the reference library): the host calls the
+ * object's updateRef / isActive once per grid point and hands the results over. */
 #define RTOC_TASK_FRAME_3D 0       /* TaskSpace3DCost                                                   */
 #define RTOC_TASK_COM 1            /* CoMCost                                                           */
+#define RTOC_TASK_FRAME_6D 2       /* TaskSpace6DCost                                                   */
 #define RTOC_REF_CONST 0           /* set_const_ref: x0 is the reference, always active                 */
 #define RTOC_REF_PERIODIC_FOOT 1   /* PeriodicSwingFootRef(x3d0 = x0, step_length = rate, step_height, t0,
                                     *   period_swing = period_active, period_stance = period_inactive, is_first_step_half) */
 #define RTOC_REF_PERIODIC_COM 2    /* PeriodicCoMRef(com_ref0 = x0, vcom_ref = rate, t0, period_active, period_inactive,
                                     *   is_first_move_half)                                              */
+#define RTOC_REF_TABLE 3           /* rtoc_set_task_ref_table: placement and active flag per grid point  */
 #define RTOC_MAX_TASK_COSTS 8
 typedef struct rtoc_task_cost {
   int kind, ref_kind;
-  int frame_parent;            /* RTOC_TASK_FRAME_3D: joint the frame is attached to                   */
+  int frame_parent;            /* RTOC_TASK_FRAME_3D / _6D: joint the frame is attached to             */
   int first_half;              /* is_first_step_half / is_first_move_half                              */
   double frame_p[3];           /* frame origin in that joint's frame                                   */
   double weight[3], weight_terminal[3], weight_impact[3];
   double x0[3];                /* const ref / x3d0 / com_ref0                                          */
   double rate[3];              /* step_length (foot) / vcom_ref (CoM)                                  */
   double step_height, t0, period_active, period_inactive;   /* swing | stance, active | inactive       */
+  /* RTOC_TASK_FRAME_6D (appended: everything above is the layout the 3D terms have always had) */
+  double frame_R[9];           /* frame axes in that joint's frame (row-major)                         */
+  double ref_R[9];             /* const ref: rotation (x0 is its position)                             */
+  double weight_angular[3], weight_angular_terminal[3], weight_angular_impact[3];   /* components 3..5 of d: what the
+                                * reference's setters call weight_position (WEIGHT ORDER above); weight* multiply 0..2 */
 } rtoc_task_cost;
+/* one grid point of a reference table: what the user's updateRef / isActive returned there.  A 3D / CoM term reads only p. */
+typedef struct rtoc_task_ref_entry {
+  double R[9], p[3];           /* reference placement (R row-major)                                    */
+  int active, pad;             /* isActive(grid_info)                                                  */
+} rtoc_task_ref_entry;
 /* terms[nterms] shared by the batch (per_instance = 0) or terms[batch][nterms] (per_instance = 1: every instance its own
  * references).  RTOC_ERR_BAD_ARG: nterms outside [0, RTOC_MAX_TASK_COSTS], a negative weight, a frame parent outside the
  * model's joints, a non-positive period of a periodic reference, an unknown kind / ref_kind; needs rtoc_set_robot_model.
+ * A RTOC_TASK_FRAME_6D term: all 18 weights non-negative, frame_R / ref_R finite.
  * nterms = 0 (terms may be NULL) removes the terms: rtoc_contact_eval_kkt then launches exactly what it launched before.
- * The terms belong to the contact path: with terms set, rtoc_unconstr_eval_kkt (and what calls it) returns RTOC_ERR_BAD_ARG.
+ * rtoc_unconstr_eval_kkt (and what calls it) evaluates the terms as well: s = its dt on every grid point but the last, 1 and
+ * weight_terminal on the last, no impact kind, hx / h untouched (unconstr_intermediate_stage.cpp has no Hamiltonian terms),
+ * the cost value only when the line search asks for it; times from rtoc_set_grid_times under the same readiness rule.
  * The kernel takes the subtree of a joint as the joints after it in the table down to the next one no deeper, which holds
  * because rtoc_set_robot_model only accepts depth-first ordered tables. */
 int rtoc_set_task_costs(rtoc_ctx* ctx, const rtoc_task_cost* terms, int nterms, int per_instance);
@@ -147,6 +174,12 @@ int rtoc_set_task_costs(rtoc_ctx* ctx, const rtoc_task_cost* terms, int nterms, 
 /* rtoc_set_grid forgets the times of a fixed grid: set them again after it, or rtoc_contact_eval_kkt returns
  * RTOC_ERR_NOT_READY while terms are set. */
 int rtoc_set_grid_times(rtoc_ctx* ctx, const double* t, int nstages);
+/* The reference table of term `term` (its ref_kind must be RTOC_REF_TABLE): entries[nstages] shared by the batch
+ * (per_instance = 0) or entries[batch][nstages], indexed by GRID POINT, not by time; nstages must be the current grid's.
+ * RTOC_ERR_BAD_ARG: term outside [0, RTOC_MAX_TASK_COSTS), a wrong nstages, a non-finite entry.  rtoc_set_grid forgets every
+ * table, as it forgets the grid times; rtoc_set_task_costs keeps them (a table belongs to the term INDEX).  Evaluating a
+ * RTOC_REF_TABLE term without a table returns RTOC_ERR_NOT_READY.  rtoc_clone copies the tables. */
+int rtoc_set_task_ref_table(rtoc_ctx* ctx, int term, const rtoc_task_ref_entry* entries, int nstages, int per_instance);
 int rtoc_get_grid_times(rtoc_ctx* ctx, double* host_out, int count);
 
 /* ---- inequality rows of the contact path evaluated on the device (the Constraints object of examples/anymal/trot.cpp:
@@ -266,7 +299,9 @@ int rtoc_linearize_state_equation(rtoc_ctx* ctx);
  * RNEA, its derivatives, the dt-scaled multiplier terms), and computeInitialStateDirection (x0 - s[0].x into
  * RTOC_BUF_DX0) -- from RTOC_BUF_SOL into RTOC_BUF_KKT / RTOC_BUF_CDD in the record convention of rtoc_unconstr_condense.
  * With joint-limit rows and bounds set (below): constraints_->linearizeConstraints as well (residual, cmpl into
- * RTOC_BUF_CON, the duals into the gradients). */
+ * RTOC_BUF_CON, the duals into the gradients).  With task-space terms set (rtoc_set_task_costs): those components of the cost
+ * function as well, right behind the configuration cost (s = dt, the last grid point terminal; needs rtoc_set_grid_times and
+ * the table of every RTOC_REF_TABLE term, else RTOC_ERR_NOT_READY before anything is launched). */
 int rtoc_unconstr_eval_kkt(rtoc_ctx* ctx, double dt);
 /* The joint-limit rows of this path live on the device for their whole life.  After rtoc_set_constraint_rows: the bound
  * of every row, g(z) = sign * z - bound <= 0 (lower limit zmin: sign -1, bound -zmin; upper limit zmax: sign +1, bound

@@ -175,6 +175,7 @@ def lib():
         L.rtoc_error_string.restype = C.c_char_p
         L.rtoc_set_task_costs.argtypes = [vp, vp, C.c_int, C.c_int]
         L.rtoc_set_grid_times.argtypes = [vp, dp, C.c_int]
+        L.rtoc_set_task_ref_table.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
         L.rtoc_get_grid_times.argtypes = [vp, dp, C.c_int]
         _LIB = L
     return _LIB
@@ -535,7 +536,7 @@ class Context:
         _chk(lib().rtoc_contact_eval_kkt(self._h))
 
     def set_task_costs(self, terms, per_instance=False):
-        """rtoc_set_task_costs: `terms` = a list of robotoc_amd.costs.TaskSpace3DCost / CoMCost (or TaskCost structs) shared by
+        """rtoc_set_task_costs: `terms` = a list of robotoc_amd.costs.TaskSpace3DCost / CoMCost / TaskSpace6DCost (or TaskCost structs) shared by
         the batch, with per_instance a list of `batch` such lists; None or [] removes the terms"""
         from .costs import TaskCost
         if not terms:
@@ -547,6 +548,30 @@ class Context:
             raise ValueError("every instance needs the same number of terms")
         arr = (TaskCost * len(rows))(*[t if isinstance(t, TaskCost) else t.to_struct() for t in rows])
         _chk(lib().rtoc_set_task_costs(self._h, C.cast(arr, C.c_void_p), n, 1 if per_instance else 0))
+
+    def set_task_ref_table(self, term, entries, per_instance=False):
+        """rtoc_set_task_ref_table: the reference table of term `term` (ref_kind RTOC_REF_TABLE) -- `entries` = a
+        costs.TaskRefEntry array with one entry per grid point (what a cost's `ref_table(grid_infos)` returns), with
+        per_instance a list of `batch` such arrays"""
+        from .costs import TaskRefEntry
+        if per_instance:
+            if len(entries) != self.batch:
+                raise ValueError("a per-instance table needs one array per instance")
+            n = len(entries[0])
+            if any(len(e) != n for e in entries):
+                raise ValueError("every instance needs a table of the same length")
+            arr = (TaskRefEntry * (n * self.batch))(*[x for e in entries for x in e])
+        else:
+            n, arr = len(entries), (TaskRefEntry * len(entries))(*entries)
+        _chk(lib().rtoc_set_task_ref_table(self._h, int(term), C.cast(arr, C.c_void_p), n, 1 if per_instance else 0))
+
+    def set_task_ref_tables(self, terms, infos):
+        """fills and uploads the table of every term of `terms` (the list given to set_task_costs, shared by the batch) whose
+        reference is the user's object, asking it at the grid points `infos` (costs.grid_infos)"""
+        for k, t in enumerate(terms):
+            tab = t.ref_table(infos) if hasattr(t, "ref_table") else None
+            if tab is not None:
+                self.set_task_ref_table(k, tab)
 
     def set_grid_times(self, t):
         """rtoc_set_grid_times: GridInfo::t of every grid point of a fixed grid"""

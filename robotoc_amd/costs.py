@@ -1,13 +1,19 @@
-"""TaskSpace3DCost and CoMCost with their periodic references, as a robotoc OCP declares them (reference
-src/cost/task_space_3d_cost.cpp, com_cost.cpp, periodic_swing_foot_ref.cpp, periodic_com_ref.cpp): constructor argument
-order, setters and argument checks of the reference.  The costs themselves are evaluated on the device by
-rtoc_contact_eval_kkt (csrc/task_space_cost.hpp); these classes describe them (`to_struct`: one `rtoc_task_cost`) and
-restate isActive / updateRef on the host for set-up and checks.
+"""TaskSpace3DCost, CoMCost and TaskSpace6DCost with their references, as a robotoc OCP declares them (reference
+src/cost/task_space_3d_cost.cpp, com_cost.cpp, task_space_6d_cost.cpp, periodic_swing_foot_ref.cpp, periodic_com_ref.cpp):
+constructor argument order, setters and argument checks of the reference.  The costs themselves are evaluated on the device by
+rtoc_contact_eval_kkt / rtoc_unconstr_eval_kkt (csrc/task_space_cost.hpp); these classes describe them (`to_struct`: one
+`rtoc_task_cost`) and restate isActive / updateRef on the host for set-up and checks.
+
+A reference that is the user's own object (the reference library ships no concrete TaskSpace6DRefBase) reaches the device as
+a table with one entry per grid point: `ref_table(grid_infos)` calls the object's `update_ref` / `is_active` once per grid
+point, `capi.Context.set_task_ref_table` uploads the result.
 
 `robot` is a robotoc_amd.robot_model.RobotModel or the name of a bundled table ("anymal", "icub", ...).  A frame is a contact
 frame name of the table (models/*.json contacts[].frame), a joint name with an offset in that joint's frame
-(`("l_wrist_yaw", [0, 0, 0.1])`), or a (parent joint index, offset) pair.
+(`("l_wrist_yaw", [0, 0, 0.1])`), or a (parent joint index, offset) pair; a 6D term's frame may carry a rotation as well:
+(joint name or index, offset[, rotation 3x3]), or the name of a frame in FRAMES.
 """
+import collections
 import ctypes as C
 import json
 import os
@@ -16,8 +22,8 @@ import numpy as np
 
 from . import robot_model as rm
 
-TASK_FRAME_3D, TASK_COM = 0, 1                          # RTOC_TASK_*
-REF_CONST, REF_PERIODIC_FOOT, REF_PERIODIC_COM = 0, 1, 2  # RTOC_REF_*
+TASK_FRAME_3D, TASK_COM, TASK_FRAME_6D = 0, 1, 2                        # RTOC_TASK_*
+REF_CONST, REF_PERIODIC_FOOT, REF_PERIODIC_COM, REF_TABLE = 0, 1, 2, 3   # RTOC_REF_*
 MAX_TASK_COSTS = 8
 
 
@@ -26,7 +32,37 @@ class TaskCost(C.Structure):
     _fields_ = [("kind", C.c_int), ("ref_kind", C.c_int), ("frame_parent", C.c_int), ("first_half", C.c_int),
                 ("frame_p", C.c_double * 3), ("weight", C.c_double * 3), ("weight_terminal", C.c_double * 3),
                 ("weight_impact", C.c_double * 3), ("x0", C.c_double * 3), ("rate", C.c_double * 3),
-                ("step_height", C.c_double), ("t0", C.c_double), ("period_active", C.c_double), ("period_inactive", C.c_double)]
+                ("step_height", C.c_double), ("t0", C.c_double), ("period_active", C.c_double), ("period_inactive", C.c_double),
+                ("frame_R", C.c_double * 9), ("ref_R", C.c_double * 9), ("weight_angular", C.c_double * 3),
+                ("weight_angular_terminal", C.c_double * 3), ("weight_angular_impact", C.c_double * 3)]
+
+
+class TaskRefEntry(C.Structure):
+    """include/rtoc_robot.h rtoc_task_ref_entry: one grid point of a reference table"""
+    _fields_ = [("R", C.c_double * 9), ("p", C.c_double * 3), ("active", C.c_int), ("pad", C.c_int)]
+
+
+# what a user's reference object is asked with (robotoc::GridInfo: the fields a reference can depend on)
+GridInfo = collections.namedtuple("GridInfo", "t dt stage")
+
+
+def grid_infos(times, dts=None):
+    """GridInfo of every grid point from the grid times (and time steps, where known)"""
+    return [GridInfo(float(t), float(dts[i]) if dts is not None else 0.0, i) for i, t in enumerate(times)]
+
+
+def rpy_rotation(roll, pitch, yaw):
+    """Rz(yaw) Ry(pitch) Rx(roll): a URDF origin's rpy"""
+    cr, sr, cp, sp, cy, sy = np.cos(roll), np.sin(roll), np.cos(pitch), np.sin(pitch), np.cos(yaw), np.sin(yaw)
+    Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+    Ry = np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
+    Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+# frames behind fixed joints that the bundled tables welded into their parent: name -> (joint, xyz, rpy) as the URDF prints them.
+# iiwa14's end-effector frame: the printed rpy is pi to twelve digits, so the rotation is near but not exactly the identity.
+FRAMES = {"iiwa14": {"iiwa_link_ee_kuka": ("iiwa_joint_7", (0.0, 0.0, 0.045), (3.14159265359, 3.14159265359, 3.14159265359))}}
 
 
 def resolve_frame(model_name, frame):
@@ -42,6 +78,29 @@ def resolve_frame(model_name, frame):
     if name not in names:
         raise ValueError("no joint named %r in %s" % (name, model_name))
     return names.index(name), np.asarray(offset, dtype=float).reshape(3)
+
+
+def resolve_frame_6d(robot, frame):
+    """(parent joint index, origin, rotation) of a 6D term's frame: a name in FRAMES, a contact frame name, or
+    (joint name or index, offset[, rotation])"""
+    if isinstance(frame, str):
+        if isinstance(robot, str) and frame in FRAMES.get(robot, {}):
+            joint, xyz, rpy = FRAMES[robot][frame]
+            return resolve_frame(robot, (joint, xyz))[0], np.asarray(xyz, dtype=float), rpy_rotation(*rpy)
+        if not isinstance(robot, str):
+            raise ValueError("[TaskSpace6DCost] a frame given by name needs the name of a bundled model table")
+        d = json.load(open(os.path.join(rm.MODEL_DIR, robot + ".json")))
+        for c in d["contacts"]:
+            if c.get("frame") == frame:
+                return int(c["parent"]), np.asarray(c["p"], dtype=float), np.asarray(c.get("R", np.eye(3)), dtype=float).reshape(3, 3)
+        raise ValueError("no frame named %r in %s" % (frame, robot))
+    joint, offset = frame[0], frame[1]
+    R = np.asarray(frame[2], dtype=float).reshape(3, 3) if len(frame) > 2 else np.eye(3)
+    if isinstance(joint, (int, np.integer)):
+        return int(joint), np.asarray(offset, dtype=float).reshape(3), R
+    if not isinstance(robot, str):
+        raise ValueError("[TaskSpace6DCost] a frame given by name needs the name of a bundled model table")
+    return resolve_frame(robot, (joint, offset))[0], np.asarray(offset, dtype=float).reshape(3), R
 
 
 class PeriodicSwingFootRef:
@@ -135,7 +194,7 @@ class _Cost3D:
         self.const_ref, self.ref = np.zeros(3), None
         if ref is None:
             pass
-        elif isinstance(ref, (PeriodicSwingFootRef, PeriodicCoMRef)):
+        elif hasattr(ref, "update_ref"):   # a periodic reference or the user's own object
             self.set_ref(ref)
         else:
             self.set_const_ref(ref)
@@ -156,10 +215,27 @@ class _Cost3D:
         self.weight_impact = self._check(weight_impact, "weight_impact")
 
     def set_ref(self, ref):
+        """a PeriodicSwingFootRef / PeriodicCoMRef (evaluated on the device from the grid time), or the user's own object with
+        update_ref(grid_info) -> position and is_active(grid_info) (TaskSpace3DRefBase / CoMRefBase): a table reference"""
         self.ref = ref
 
     def set_const_ref(self, const_ref):
         self.const_ref, self.ref = np.asarray(const_ref, dtype=float).reshape(3).copy(), None
+
+    def uses_table(self):
+        return self.ref is not None and not hasattr(self.ref, "_fill")
+
+    def ref_table(self, infos):
+        """the rtoc_task_ref_entry array of a table reference: the user's object asked once per grid point; None otherwise"""
+        if not self.uses_table():
+            return None
+        arr = (TaskRefEntry * len(infos))()
+        for e, g in zip(arr, infos):
+            e.R[:] = np.eye(3).ravel()
+            e.active = int(bool(self.ref.is_active(g)))
+            if e.active:   # updateRef is only called where the reference is active, as in the reference's evalDiff
+                e.p[:] = np.asarray(self.ref.update_ref(g), dtype=float).reshape(3)
+        return arr
 
     def is_cost_active(self, t):
         return True if self.ref is None else self.ref.is_active(t)
@@ -173,6 +249,8 @@ class _Cost3D:
         s.weight[:], s.weight_terminal[:], s.weight_impact[:] = self.weight, self.weight_terminal, self.weight_impact
         if self.ref is None:
             s.ref_kind, s.x0[:] = REF_CONST, self.const_ref
+        elif self.uses_table():
+            s.ref_kind = REF_TABLE
         else:
             self.ref._fill(s)
         return s
@@ -208,4 +286,92 @@ class CoMCost(_Cost3D):
     def to_struct(self):
         s = super().to_struct()
         s.kind = TASK_COM
+        return s
+
+
+class TaskSpace6DRefBase:
+    """include/robotoc/cost/task_space_6d_ref_base.hpp: the protocol of a user's reference placement.  Subclass it, or hand
+    TaskSpace6DCost any object with these two methods."""
+
+    def update_ref(self, grid_info):
+        """(rotation 3x3, position 3) of the reference placement at this grid point"""
+        raise NotImplementedError
+
+    def is_active(self, grid_info):
+        raise NotImplementedError
+
+
+class TaskSpace6DCost:
+    """src/cost/task_space_6d_cost.cpp: TaskSpace6DCost(robot, frame[, ref | (position, rotation)]); a constant reference is the
+    pair (const_position_ref, const_rotation_ref) in the reference's argument order"""
+
+    def __init__(self, robot, frame, ref=None):
+        self.frame_parent, self.frame_p, self.frame_R = resolve_frame_6d(robot, frame)
+        self.weight, self.weight_terminal, self.weight_impact = np.zeros(6), np.zeros(6), np.zeros(6)
+        self.const_position_ref, self.const_rotation_ref, self.ref = np.zeros(3), np.eye(3), None
+        if ref is None:
+            pass
+        elif hasattr(ref, "update_ref"):
+            self.set_ref(ref)
+        else:
+            self.set_const_ref(*ref)
+
+    @staticmethod
+    def _check(wp, wr, suffix):
+        wp, wr = np.asarray(wp, dtype=float).reshape(3), np.asarray(wr, dtype=float).reshape(3)
+        if wp.min() < 0.0:
+            raise ValueError("[TaskSpace6DCost] invalid argument: elements of 'weight_position%s' must be non-negative!" % suffix)
+        if wr.min() < 0.0:
+            raise ValueError("[TaskSpace6DCost] invalid argument: elements of 'weight_rotation%s' must be non-negative!" % suffix)
+        # task_space_6d_cost.cpp:124-125, as written: weight_.head<3>() = weight_rotation, weight_.tail<3>() = weight_position,
+        # and weight_ multiplies Log6Map(...) = [linear; angular] componentwise -- `weight_rotation` weights the linear components
+        return np.concatenate([wr, wp])
+
+    def set_weight(self, weight_position, weight_rotation):
+        self.weight = self._check(weight_position, weight_rotation, "")
+
+    def set_weight_terminal(self, weight_position_terminal, weight_rotation_terminal):
+        self.weight_terminal = self._check(weight_position_terminal, weight_rotation_terminal, "_terminal")
+
+    def set_weight_impact(self, weight_position_impact, weight_rotation_impact):
+        self.weight_impact = self._check(weight_position_impact, weight_rotation_impact, "_impact")
+
+    def set_ref(self, ref):
+        self.ref = ref
+
+    def set_const_ref(self, const_position_ref, const_rotation_ref):
+        self.const_position_ref = np.asarray(const_position_ref, dtype=float).reshape(3).copy()
+        self.const_rotation_ref = np.asarray(const_rotation_ref, dtype=float).reshape(3, 3).copy()
+        self.ref = None
+
+    def uses_table(self):
+        return self.ref is not None
+
+    def ref_table(self, infos):
+        """the rtoc_task_ref_entry array of a user's reference object, asked once per grid point; None for a constant reference"""
+        if self.ref is None:
+            return None
+        arr = (TaskRefEntry * len(infos))()
+        for e, g in zip(arr, infos):
+            e.R[:] = np.eye(3).ravel()
+            e.active = int(bool(self.ref.is_active(g)))
+            if e.active:   # updateRef is only called where the reference is active (task_space_6d_cost.hpp:200-209)
+                R, p = self.ref.update_ref(g)
+                e.R[:], e.p[:] = np.asarray(R, dtype=float).reshape(9), np.asarray(p, dtype=float).reshape(3)
+        return arr
+
+    def to_struct(self):
+        s = TaskCost()
+        s.kind, s.frame_parent = TASK_FRAME_6D, self.frame_parent
+        s.frame_p[:], s.frame_R[:] = self.frame_p, self.frame_R.ravel()
+        # the six weights in the order they multiply d = [linear; angular] (include/rtoc_robot.h: WEIGHT ORDER): the first triple
+        # is what the caller passed as weight_rotation, the second what they passed as weight_position -- the reference as written
+        s.weight[:], s.weight_angular[:] = self.weight[:3], self.weight[3:]
+        s.weight_terminal[:], s.weight_angular_terminal[:] = self.weight_terminal[:3], self.weight_terminal[3:]
+        s.weight_impact[:], s.weight_angular_impact[:] = self.weight_impact[:3], self.weight_impact[3:]
+        s.ref_R[:] = np.eye(3).ravel()
+        if self.ref is None:
+            s.ref_kind, s.x0[:], s.ref_R[:] = REF_CONST, self.const_position_ref, self.const_rotation_ref.ravel()
+        else:
+            s.ref_kind = REF_TABLE
         return s

@@ -279,9 +279,16 @@ struct rtoc_ctx : CtxStreams, CtxOptions {
   // task-space cost components (rtoc_set_task_costs; task_space_cost.hpp)
   DevBuf<rtoc_task_cost> d_tasks;  // capacity [batch][RTOC_MAX_TASK_COSTS]; in use [ntasks] or [batch][ntasks]
   int ntasks = 0, tasks_per_instance = 0;
+  unsigned h_task_table = 0;       // bit k: term k (of some instance) has ref_kind RTOC_REF_TABLE
   DevBuf<double> d_gt;             // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
   std::vector<double> h_gt;        // host copy of the same, its size = the grid it belongs to (empty: none)
   DevBuf<double> d_gt_inst;        // [batch][max_stages] per-instance grid times written by sto_time_steps_kernel, or unallocated
+  // reference tables of RTOC_REF_TABLE terms (rtoc_set_task_ref_table), by term index: capacity [max_stages] or [batch][max_stages],
+  // in use [nstages] or [batch][nstages]; reftab_n[k] = the nstages table k was set for (0: none), bit k of reftab_inst: per instance
+  DevBuf<rtoc_task_ref_entry> d_reftab[RTOC_MAX_TASK_COSTS];
+  int reftab_n[RTOC_MAX_TASK_COSTS] = {};
+  unsigned reftab_inst = 0;
+  int task_rows = 0, task_ext = 0; // LDS rows of the term lists (the largest instance), 1: a 6D term or a table reference among them
   DevBuf<double> d_ls_merit;   // [batch] penalty parameter + [batch] directional derivative
   double ls_unconstr_dt = 0.0; // > 0: the last evalKKT was rtoc_unconstr_eval_kkt(dt) -- trial iterates of the line search are evaluated by it
   DevBuf<double> d_eval;       // [2][2][batch]: (cost + barrier | violation) of the current iterate, of the trial iterate
@@ -565,6 +572,11 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
   }
   dup(n->d_gt, c->d_gt);
   if (!rc) n->h_gt = c->h_gt;
+  n->task_rows = c->task_rows, n->task_ext = c->task_ext, n->reftab_inst = c->reftab_inst, n->h_task_table = c->h_task_table;
+  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) {
+    n->reftab_n[k] = c->reftab_n[k];
+    dup(n->d_reftab[k], c->d_reftab[k]);
+  }
   for (int b = 0; b < RTOC_NUM_BUFFERS; ++b) {
     if (!c->buf[b].p) continue;
     n->want[b] = c->want[b];
@@ -624,6 +636,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
     if (nev != c->sto_nev) c->sto_on = 0;   // rtoc_sto_set_problem again
   }
   c->h_gt.clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
+  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) c->reftab_n[k] = 0;   // and so do the reference tables: rtoc_set_task_ref_table again
   return RTOC_OK;
 }
 
@@ -2123,13 +2136,16 @@ int rtoc_unconstr_init_constraints(rtoc_ctx* c) {
   return launch_ubox(c, UBOX_INIT);
 }
 
+static int task_costs_ready(rtoc_ctx* c, bool unconstr);
+static int launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out);
+
 int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   CHECK_READY(c);
   if (!(dt > 0.0) || c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
-  if (c->ntasks > 0) return RTOC_ERR_BAD_ARG;   // task-space costs are evaluated on the contact path only
   if (!c->h_model || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
-  int rc = ensure_buffer(c, RTOC_BUF_KKT);
+  int rc = c->ntasks > 0 ? task_costs_ready(c, true) : RTOC_OK;   // ahead of the first launch: a refusal leaves the records alone
+  if (!rc) rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_DX0);
   if (rc) return rc;
@@ -2147,6 +2163,11 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   hipLaunchKernelGGL(rbd::unconstr_eval_kkt_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fxx_state = 0;
+  // the task-space terms of the cost function (TaskSpace6DCost / TaskSpace3DCost / CoMCost), added to what the configuration cost stored
+  if (c->ntasks > 0) {
+    rc = launch_task_costs(c, dt, a.cost_out);
+    if (rc) return rc;
+  }
   rc = launch_linearize(c, 1, true, dt);
   if (!rc && ubox_on(c)) rc = launch_ubox(c, UBOX_LINEARIZE);  // constraints_->linearizeConstraints (unconstr_intermediate_stage.cpp:68-69)
   return rc;
@@ -2318,14 +2339,23 @@ static int launch_switching_constraint(rtoc_ctx* c) {
   return RTOC_OK;
 }
 
-// ---- TaskSpace3DCost / CoMCost (task_space_cost.hpp) ----
+// ---- TaskSpace3DCost / CoMCost / TaskSpace6DCost (task_space_cost.hpp) ----
 static bool task_cost_valid(const rtoc_task_cost& t, int njoints) {
-  if (t.kind != RTOC_TASK_FRAME_3D && t.kind != RTOC_TASK_COM) return false;
-  if (t.ref_kind != RTOC_REF_CONST && t.ref_kind != RTOC_REF_PERIODIC_FOOT && t.ref_kind != RTOC_REF_PERIODIC_COM) return false;
-  if (t.kind == RTOC_TASK_FRAME_3D && (t.frame_parent < 0 || t.frame_parent >= njoints)) return false;
+  if (t.kind != RTOC_TASK_FRAME_3D && t.kind != RTOC_TASK_COM && t.kind != RTOC_TASK_FRAME_6D) return false;
+  if (t.ref_kind != RTOC_REF_CONST && t.ref_kind != RTOC_REF_PERIODIC_FOOT && t.ref_kind != RTOC_REF_PERIODIC_COM && t.ref_kind != RTOC_REF_TABLE)
+    return false;
+  if (t.kind != RTOC_TASK_COM && (t.frame_parent < 0 || t.frame_parent >= njoints)) return false;
   for (int k = 0; k < 3; ++k)   // set_weight / set_weight_terminal / set_weight_impact: elements must be non-negative
     if (!(t.weight[k] >= 0.0) || !(t.weight_terminal[k] >= 0.0) || !(t.weight_impact[k] >= 0.0)) return false;
-  if (t.ref_kind != RTOC_REF_CONST && (!(t.period_active > 0.0) || !(t.period_inactive >= 0.0))) return false;
+  const bool periodic = t.ref_kind == RTOC_REF_PERIODIC_FOOT || t.ref_kind == RTOC_REF_PERIODIC_COM;
+  if (periodic && (!(t.period_active > 0.0) || !(t.period_inactive >= 0.0))) return false;
+  if (t.kind == RTOC_TASK_FRAME_6D) {
+    if (periodic) return false;   // the periodic references are positions
+    for (int k = 0; k < 3; ++k)   // the six weights in the order they multiply d (rtoc_robot.h: WEIGHT ORDER)
+      if (!(t.weight_angular[k] >= 0.0) || !(t.weight_angular_terminal[k] >= 0.0) || !(t.weight_angular_impact[k] >= 0.0)) return false;
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(t.frame_R[k]) || !std::isfinite(t.ref_R[k])) return false;
+  }
   return true;
 }
 
@@ -2346,7 +2376,44 @@ int rtoc_set_task_costs(rtoc_ctx* c, const rtoc_task_cost* terms, int nterms, in
   HIP_TRY(hipMemcpyAsync(c->d_tasks.p, terms, sizeof(rtoc_task_cost) * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->ntasks = nterms, c->tasks_per_instance = per_instance ? 1 : 0;
+  // which instantiation serves these terms, and the Jacobian rows its LDS holds (the largest term list of the batch)
+  c->task_rows = 0, c->task_ext = 0;
+  for (size_t i = 0; i < n; i += nterms) {
+    int rows = 0;
+    for (int k = 0; k < nterms; ++k) {
+      rows += task_cost_rows(terms[i + k].kind);
+      if (terms[i + k].kind == RTOC_TASK_FRAME_6D || terms[i + k].ref_kind == RTOC_REF_TABLE) c->task_ext = 1;
+    }
+    if (rows > c->task_rows) c->task_rows = rows;
+  }
+  c->h_task_table = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (terms[i].ref_kind == RTOC_REF_TABLE) c->h_task_table |= 1u << (i % nterms);
   c->epoch++;   // launch parameters baked into captured graphs
+  return RTOC_OK;
+}
+
+int rtoc_set_task_ref_table(rtoc_ctx* c, int term, const rtoc_task_ref_entry* entries, int nstages, int per_instance) {
+  if (!c || !entries || term < 0 || term >= RTOC_MAX_TASK_COSTS) return RTOC_ERR_BAD_ARG;
+  if (c->nstages < 2) return RTOC_ERR_NOT_READY;   // rtoc_set_grid
+  if (nstages != c->nstages) return RTOC_ERR_BAD_ARG;
+  const size_t n = (size_t)nstages * (per_instance ? c->batch : 1);
+  for (size_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(entries[i].R[k])) return RTOC_ERR_BAD_ARG;
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(entries[i].p[k])) return RTOC_ERR_BAD_ARG;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  bool fresh = false;
+  HIP_TRY(c->d_reftab[term].reserve((size_t)c->max_stages * (per_instance ? c->batch : 1), &fresh));
+  HIP_TRY(hipMemcpyAsync(c->d_reftab[term].p, entries, sizeof(rtoc_task_ref_entry) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const unsigned bit = 1u << term, inst = per_instance ? bit : 0u;
+  // captured graphs bake the pointer and the per-instance flag in
+  if (fresh || c->reftab_n[term] != nstages || (c->reftab_inst & bit) != inst) c->epoch++;
+  c->reftab_n[term] = nstages;
+  c->reftab_inst = (c->reftab_inst & ~bit) | inst;
   return RTOC_OK;
 }
 
@@ -2386,25 +2453,48 @@ int rtoc_get_grid_times(rtoc_ctx* c, double* host_out, int count) {
   return RTOC_OK;
 }
 
-static int launch_task_costs(rtoc_ctx* c) {
+// what the task kernel reads besides the records: the grid times (the contact path's switching-time problems write their own
+// on the device; the unconstrained path has none) and the table of every RTOC_REF_TABLE term, set for the current grid
+static int task_costs_ready(rtoc_ctx* c, bool unconstr) {
   if (!c->h_model || !c->d_model.p || !c->d_tasks.p) return RTOC_ERR_NOT_READY;
-  if (!c->sto_on && (int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
-  if (c->sto_on && !c->d_gt_inst.p) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
+  const bool sto = c->sto_on && !unconstr;
+  if (!sto && (int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
+  if (sto && !c->d_gt_inst.p) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
+  for (int k = 0; k < c->ntasks; ++k)
+    if (((c->h_task_table >> k) & 1u) && (c->reftab_n[k] != c->nstages || !c->d_reftab[k].p)) return RTOC_ERR_NOT_READY;   // rtoc_set_task_ref_table
+  return RTOC_OK;
+}
+
+// unconstr_dt > 0: from rtoc_unconstr_eval_kkt(dt) -- always the extended instantiation, which knows that path's scaling
+static int launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out) {
+  const bool unconstr = unconstr_dt > 0.0;
+  int rc = task_costs_ready(c, unconstr);
+  if (rc) return rc;
+  const bool sto = c->sto_on && !unconstr;
   TaskCostArgs a;
   a.rv = view(c);
-  a.cost_out = c->d_costval.p;
+  a.cost_out = cost_out;
   a.terms = c->d_tasks.p;
-  a.t_fixed = c->sto_on ? nullptr : c->d_gt.p;
-  a.t_inst = c->sto_on ? c->d_gt_inst.p : nullptr;
+  a.t_fixed = sto ? nullptr : c->d_gt.p;
+  a.t_inst = sto ? c->d_gt_inst.p : nullptr;
   a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
+  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) a.tab[k] = (k < c->ntasks && ((c->h_task_table >> k) & 1u)) ? c->d_reftab[k].p : nullptr;
+  a.tab_inst = c->reftab_inst;
+  a.nrows = c->task_rows;
+  a.unconstr_dt = unconstr ? unconstr_dt : 0.0;
   // the 16-byte row pairs of Qqq need an even record stride and column length and an even field offset
   if ((c->L.kkt.stride | c->L.kkt.off[RTOC_KKT_QXX]) & 1) return RTOC_ERR_BAD_ARG;
   const long long items = (long long)c->batch * c->nstages;
-  const size_t lds1 = sizeof(double) * task_cost_lds_doubles(c->h_model->m.njoints, c->ntasks, c->dims.nv);
+  const bool ext = c->task_ext || unconstr;
+  const size_t lds1 = sizeof(double) * task_cost_lds_doubles(c->h_model->m.njoints, ext ? c->task_rows : 3 * c->ntasks, c->dims.nv);
+  if (2 * lds1 > 64 * 1024) return RTOC_ERR_UNSUPPORTED_DIMS;   // (48 joints, eight 6D terms, 64 dofs: 30 KB per grid point)
+  const dim3 grid2((unsigned)((items + 1) / 2)), grid1((unsigned)items);
   if (c->dims.nv <= 32) {
-    hipLaunchKernelGGL(task_space_cost_kernel<2>, dim3((unsigned)((items + 1) / 2)), dim3(64), 2 * lds1, c->stream, a);
+    if (ext) hipLaunchKernelGGL((task_space_cost_kernel<2, true>), grid2, dim3(64), 2 * lds1, c->stream, a);
+    else hipLaunchKernelGGL((task_space_cost_kernel<2, false>), grid2, dim3(64), 2 * lds1, c->stream, a);
   } else {
-    hipLaunchKernelGGL(task_space_cost_kernel<1>, dim3((unsigned)items), dim3(64), lds1, c->stream, a);
+    if (ext) hipLaunchKernelGGL((task_space_cost_kernel<1, true>), grid1, dim3(64), lds1, c->stream, a);
+    else hipLaunchKernelGGL((task_space_cost_kernel<1, false>), grid1, dim3(64), lds1, c->stream, a);
   }
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -2471,7 +2561,7 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   HIP_TRY(hipGetLastError());
   // TaskSpace3DCost / CoMCost: added to what the configuration cost stored, ahead of the constraints and the dynamics
   if (c->ntasks > 0) {
-    rc = launch_task_costs(c);
+    rc = launch_task_costs(c, 0.0, c->d_costval.p);
     if (rc) {
       c->vals_fresh = 0;
       return rc;

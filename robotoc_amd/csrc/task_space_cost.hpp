@@ -16,6 +16,16 @@
 // Layout: GP grid points per wave (two for nv <= 32), 64 / GP lanes each; the Jacobians of the active terms go to LDS and
 // the Qqq read-modify-write gives neighbouring lanes the row pairs of a column (16-byte accesses, an odd nv ends on one double).
 // Grid points where no term is active are not written.  No atomics: every record is owned by one lane group.
+//
+// TaskSpace6DCost (reference src/cost/task_space_6d_cost.cpp, include/robotoc/cost/task_space_6d_cost.hpp:184-214):
+//   X = X_ref^-1 oMf   d = log6(X)  [linear; angular]   JJ = Jlog6(X) J_frame (LOCAL frame Jacobian)
+//   lq += s JJ^T W d   Qqq += s JJ^T W JJ   cost += s/2 sum W d^2
+// lane j holds column j of J_frame, the frame's spatial velocity for a unit rate of dof j in the frame's own axes: a rotation
+// about w through p_b gives (R_f^T (w x (x - p_b)), R_f^T w), base linear dof k gives (R_f^T R_0 e_k, 0), zero outside the subtree;
+// JJ(:, j) is the `der` of rbd::log6_fwd along that column, d its `val`.  Six rows of LDS per 6D term.
+// The extended instantiation (EXT) carries what a context with only 3D / CoM terms and formula references never needs: the 6D
+// arithmetic, references read from a per-grid-point table (RTOC_REF_TABLE), and the unconstrained path's scaling (dt from the
+// call, no impact kind, hx / h untouched).  The host picks it; EXT = false is the kernel as it was.
 #pragma once
 #include "rigid_body.hpp"
 
@@ -28,6 +38,11 @@ struct TaskCostArgs {
   const double* t_fixed;         // [nstages] (fixed grids) or nullptr
   const double* t_inst;          // [batch][nstages] (switching-time optimisation) or nullptr
   int nterms, per_instance;
+  // EXT only
+  const rtoc_task_ref_entry* tab[RTOC_MAX_TASK_COSTS];   // per term: [nstages] / [batch][nstages] entries of its table, or nullptr
+  unsigned tab_inst;             // bit k: table k is per instance
+  int nrows;                     // Jacobian rows in LDS per lane group: the largest sum over a term list (3 per 3D / CoM, 6 per 6D term)
+  double unconstr_dt;            // > 0: rtoc_unconstr_eval_kkt's dt; 0: the contact path
 };
 
 namespace tsc {
@@ -78,31 +93,38 @@ __device__ inline void periodic_ref(const rtoc_task_cost& T, double t, double x[
   }
 }
 
+// the table entry of term k at grid point (b, st); the host launches only when every RTOC_REF_TABLE term has its table
+__device__ inline const rtoc_task_ref_entry& table_entry(const TaskCostArgs& a, int k, int b, int st) {
+  return a.tab[k][(((a.tab_inst >> k) & 1u) ? (size_t)b * a.rv.nstages : 0) + st];
+}
+
 }  // namespace tsc
 
-// LDS per lane group: per joint R (9), p (3), m c (3) in world coordinates; per term J (3 x nv, row-major) of the active terms
-__host__ __device__ inline size_t task_cost_lds_doubles(int njoints, int nterms, int nv) { return (size_t)njoints * 15 + (size_t)nterms * 3 * nv; }
+// LDS per lane group: per joint R (9), p (3), m c (3) in world coordinates; per term J (3 or 6 rows x nv, row-major) of the active terms
+__host__ __device__ inline size_t task_cost_lds_doubles(int njoints, int nrows, int nv) { return (size_t)njoints * 15 + (size_t)nrows * nv; }
+__host__ __device__ inline int task_cost_rows(int kind) { return kind == RTOC_TASK_FRAME_6D ? 6 : 3; }
 
-template <int GP>
+template <int GP, bool EXT>
 static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs a) {
   constexpr int LW = 64 / GP;
   extern __shared__ double tc_lds[];
   const int lane = threadIdx.x % LW, grp = threadIdx.x / LW;
   const rbd::DevModel& md = *a.rv.model;
   const int nj = md.m.njoints, nv = a.rv.nv(), nx = 2 * nv, nt = a.nterms;
-  double* const W = tc_lds + (size_t)grp * task_cost_lds_doubles(nj, nt, nv);
+  double* const W = tc_lds + (size_t)grp * task_cost_lds_doubles(nj, EXT ? a.nrows : 3 * nt, nv);
   double* const Rw = W;             // [nj][9]
   double* const pw = W + 9 * nj;    // [nj][3]
   double* const mc = W + 12 * nj;   // [nj][3]: mass x world centre of mass
-  double* const Jl = W + 15 * nj;   // [nt][3][nv]
+  double* const Jl = W + 15 * nj;   // [nt][3][nv]; EXT: [rows of term 0 .. nt - 1][nv]
   const long long nitems = (long long)a.rv.batch * a.rv.nstages;
   long long item = (long long)blockIdx.x * GP + grp;
   const bool real = item < nitems;   // a trailing group without a grid point computes the last one and writes nothing
   item = real ? item : nitems - 1;
   const int b = (int)(item / a.rv.nstages), st = (int)(item % a.rv.nstages);
   const rtoc_grid g = a.rv.grid[st];
-  const bool impact = g.type == RTOC_GRID_IMPACT, terminal = st == a.rv.nstages - 1, sto = !terminal && !impact;
-  const double s = (impact || terminal) ? 1.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
+  const bool unc = EXT && a.unconstr_dt > 0.0;
+  const bool impact = !unc && g.type == RTOC_GRID_IMPACT, terminal = st == a.rv.nstages - 1, sto = !terminal && !impact && !unc;
+  const double s = (impact || terminal) ? 1.0 : (unc ? a.unconstr_dt : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st));
   const double t = a.t_inst ? a.t_inst[(size_t)b * a.rv.nstages + st] : (a.t_fixed ? a.t_fixed[st] : 0.0);
   const rtoc_task_cost* const terms = a.terms + (a.per_instance ? (size_t)b * nt : 0);
   const size_t rec = (size_t)b * a.rv.nstages + st;
@@ -112,9 +134,19 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   for (int k = 0; k < nt; ++k) {
     const rtoc_task_cost& T = terms[k];
     const double* w = terminal ? T.weight_terminal : impact ? T.weight_impact : T.weight;
-    const bool enabled = w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0;
+    bool enabled = w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0;
     const double period = T.period_active + T.period_inactive;   // period_ = period_swing + period_stance
-    const bool active = T.ref_kind == RTOC_REF_CONST || tsc::periodic_active(t, T.t0, T.period_active, period);
+    bool active;
+    if constexpr (EXT) {
+      if (T.kind == RTOC_TASK_FRAME_6D) {   // enable_cost_ = !weight_.isZero() over all six
+        const double* wa = terminal ? T.weight_angular_terminal : impact ? T.weight_angular_impact : T.weight_angular;
+        enabled = enabled || wa[0] != 0.0 || wa[1] != 0.0 || wa[2] != 0.0;
+      }
+      if (T.ref_kind == RTOC_REF_TABLE) active = tsc::table_entry(a, k, b, st).active != 0;
+      else active = T.ref_kind == RTOC_REF_CONST || tsc::periodic_active(t, T.t0, T.period_active, period);
+    } else {
+      active = T.ref_kind == RTOC_REF_CONST || tsc::periodic_active(t, T.t0, T.period_active, period);
+    }
     if (enabled && active) on |= 1u << k;
   }
   // ---- local placements (lane per joint), then the tree level by level ----
@@ -171,11 +203,67 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
     for (int r = 0; r < 3; ++r) S[r] += mc[3 * k + r];
   }
   double lq[2] = {0.0, 0.0}, cost = 0.0;   // lane j's J^T W diff (lq[0]: dof lane, lq[1]: dof lane + LW), 1/2 sum W diff^2
-  for (int k = 0; k < nt; ++k) {
+  int row0 = 0;                            // EXT: first LDS row of term k
+  for (int k = 0; k < nt; row0 += EXT ? task_cost_rows(terms[k].kind) : 3, ++k) {
     if (!((on >> k) & 1u)) continue;
     const rtoc_task_cost& T = terms[k];
     const double* w = terminal ? T.weight_terminal : impact ? T.weight_impact : T.weight;
     const bool com = T.kind == RTOC_TASK_COM;
+    if constexpr (EXT) {
+      if (T.kind == RTOC_TASK_FRAME_6D) {
+        const double* wa = terminal ? T.weight_angular_terminal : impact ? T.weight_angular_impact : T.weight_angular;
+        const int f = T.frame_parent;
+        const rbd::M3 Rp = rbd::ldm3(Rw + 9 * f), Rf = rbd::mul(Rp, rbd::ldm3(T.frame_R));   // oMf = parent joint placement (frame_R, frame_p)
+        const rbd::V3 xf = rbd::mul(Rp, rbd::ldv3(T.frame_p)) + rbd::ldv3(pw + 3 * f);
+        const bool tab = T.ref_kind == RTOC_REF_TABLE;
+        const rbd::M3 Rr = rbd::ldm3(tab ? tsc::table_entry(a, k, b, st).R : T.ref_R);
+        const rbd::V3 pr = rbd::ldv3(tab ? tsc::table_entry(a, k, b, st).p : T.x0);
+        // X = X_ref^-1 oMf
+        rbd::M3 XR;
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) XR.m[3 * r + c] = Rr.m[r] * Rf.m[c] + Rr.m[3 + r] * Rf.m[3 + c] + Rr.m[6 + r] * Rf.m[6 + c];
+        const rbd::V3 Xp = rbd::mulT(Rr, xf - pr);
+        // one inlined log6_fwd: the loop is kept rolled, and its first trip (every lane takes it, with a zero column where the
+        // lane has no dof) also yields d
+        rbd::SV wd = rbd::sv0();
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+          const int j = lane + h * LW;
+          if (h > 0 && j >= nv) break;
+          rbd::SV col = rbd::sv0();
+          if (j < nv) {
+            const int bj = md.dof_body[j];
+            const double* Jb = md.joint[bj];
+            const bool lin = (int)Jb[28] == RTOC_JOINT_FREE_FLYER && j - (int)Jb[30] < 3;
+            int end = bj + 1;
+            while (end < nj && md.depth[end] > md.depth[bj]) ++end;
+            if (f >= bj && f < end) {
+              if (lin) {
+                const int e = j - (int)Jb[30];
+                col.l = rbd::mulT(Rf, rbd::mk(Rw[9 * bj + e], Rw[9 * bj + 3 + e], Rw[9 * bj + 6 + e]));
+              } else {
+                const rbd::V3 wv = rbd::mul(rbd::ldm3(Rw + 9 * bj), rbd::ldv3(md.dof_axis[j]));
+                col = rbd::SV{rbd::mulT(Rf, rbd::cross(wv, xf - rbd::ldv3(pw + 3 * bj))), rbd::mulT(Rf, wv)};
+              }
+            }
+          }
+          rbd::SV d, der;
+          rbd::log6_fwd(XR, Xp, col, d, der);
+          if (h == 0) {
+            wd = rbd::SV{rbd::mk(w[0] * d.l.x, w[1] * d.l.y, w[2] * d.l.z), rbd::mk(wa[0] * d.a.x, wa[1] * d.a.y, wa[2] * d.a.z)};
+            cost += 0.5 * (rbd::dot(wd.l, d.l) + rbd::dot(wd.a, d.a));
+          }
+          if (j >= nv) break;
+          const double jj[6] = {der.l.x, der.l.y, der.l.z, der.a.x, der.a.y, der.a.z};
+          for (int r = 0; r < 6; ++r) Jl[(row0 + r) * nv + j] = jj[r];
+          const double g = rbd::dot(der.l, wd.l) + rbd::dot(der.a, wd.a);
+          if (h == 0) lq[0] += g;   // (no indexing of lq by the rolled loop's counter: it lives in registers)
+          else lq[1] += g;
+        }
+        continue;
+      }
+    }
+    const int jrow = EXT ? row0 : 3 * k;
     double x[3], xr[3];
     if (com) {
       for (int r = 0; r < 3; ++r) x[r] = S[r] / mtot;
@@ -186,6 +274,8 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
     }
     if (T.ref_kind == RTOC_REF_CONST) {
       for (int r = 0; r < 3; ++r) xr[r] = T.x0[r];
+    } else if (EXT && T.ref_kind == RTOC_REF_TABLE) {
+      for (int r = 0; r < 3; ++r) xr[r] = tsc::table_entry(a, k, b, st).p[r];
     } else {
       tsc::periodic_ref(T, t, xr);
     }
@@ -227,7 +317,7 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
         col[0] = wv[1] * d[2] - wv[2] * d[1], col[1] = wv[2] * d[0] - wv[0] * d[2], col[2] = wv[0] * d[1] - wv[1] * d[0];
       }
       if (!com && lin && !(T.frame_parent >= bj && T.frame_parent < end)) col[0] = col[1] = col[2] = 0.0;
-      for (int r = 0; r < 3; ++r) Jl[(3 * k + r) * nv + j] = col[r];
+      for (int r = 0; r < 3; ++r) Jl[(jrow + r) * nv + j] = col[r];
       lq[h] += col[0] * wd[0] + col[1] * wd[1] + col[2] * wd[2];
     }
   }
@@ -251,14 +341,26 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
     const int c = e / npair, r = 2 * (e - c * npair);
     const bool two = r + 1 < nv;
     double v0 = 0.0, v1 = 0.0;
-    for (int k = 0; k < nt; ++k) {
+    int krow = 0;
+    for (int k = 0; k < nt; krow += EXT ? task_cost_rows(terms[k].kind) : 3, ++k) {
       if (!((on >> k) & 1u)) continue;
       const double* w = terminal ? terms[k].weight_terminal : impact ? terms[k].weight_impact : terms[k].weight;
       for (int d = 0; d < 3; ++d) {
-        const double* Jr = Jl + (3 * k + d) * nv;
+        const double* Jr = Jl + ((EXT ? krow : 3 * k) + d) * nv;
         const double wc = w[d] * Jr[c];
         v0 += Jr[r] * wc;
         if (two) v1 += Jr[r + 1] * wc;
+      }
+      if constexpr (EXT) {
+        if (terms[k].kind == RTOC_TASK_FRAME_6D) {
+          const double* wa = terminal ? terms[k].weight_angular_terminal : impact ? terms[k].weight_angular_impact : terms[k].weight_angular;
+          for (int d = 0; d < 3; ++d) {
+            const double* Jr = Jl + (krow + 3 + d) * nv;
+            const double wc = wa[d] * Jr[c];
+            v0 += Jr[r] * wc;
+            if (two) v1 += Jr[r + 1] * wc;
+          }
+        }
       }
     }
     double* const p = Qxx + r + (size_t)c * nx;

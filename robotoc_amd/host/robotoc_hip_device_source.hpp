@@ -25,8 +25,9 @@ class ConfigurationCostSource : public StageDataSource {
     if (active.size() != grid.size() || contact_positions.size() != grid.size() * static_cast<size_t>(model.ncontacts) * 3)
       throw std::invalid_argument("[ConfigurationCostSource] one contact mask and ncontacts positions per grid point");
   }
-  // The same with TaskSpace3DCost / CoMCost components beside the ConfigurationSpaceCost (the cost function's other
-  // components, evaluated on the device by rtoc_contact_eval_kkt); their periodic references read GridInfo::t of `grid`.
+  // The same with TaskSpace3DCost / CoMCost / TaskSpace6DCost components beside the ConfigurationSpaceCost (the cost function's
+  // other components, evaluated on the device by rtoc_contact_eval_kkt); their periodic references read GridInfo::t of `grid`, a
+  // user's TaskSpace6DRefBase is asked once per grid point of `grid` (a table on the device).
   ConfigurationCostSource(const rtoc_robot_model& model, const rtoc_configuration_cost& cost,
                           const std::vector<std::shared_ptr<TaskCostComponent>>& task_costs, const std::vector<GridInfo>& grid,
                           const std::vector<unsigned>& active, const std::vector<double>& contact_positions, const Solution& s0)
@@ -53,6 +54,7 @@ class ConfigurationCostSource : public StageDataSource {
       if (!c) throw std::invalid_argument("[ConfigurationCostSource] null task-space cost");
       tasks_.push_back(c->term());
     }
+    task_costs_ = task_costs;
   }
   ContactSequence* contactSequence() override { return cs_.get(); }
   const STOConstraints* stoConstraints() const override { return sto_.get(); }
@@ -143,6 +145,14 @@ class ConfigurationCostSource : public StageDataSource {
       std::vector<double> t(td_.size());
       for (int i = 0; i < td_.size(); ++i) t[i] = td_[i].t;
       chk(rtoc_set_grid_times(ctx, t.data(), td_.size()), "rtoc_set_grid_times");
+      // references that are the user's objects: updateRef / isActive at every grid point of the grid in force
+      for (size_t k = 0; k < task_costs_.size(); ++k) {
+        if (!task_costs_[k]->usesTable()) continue;
+        std::vector<GridInfo> grid(td_.size());
+        for (int i = 0; i < td_.size(); ++i) grid[i] = td_[i];
+        const std::vector<rtoc_task_ref_entry> tab = task_costs_[k]->refTable(grid);
+        chk(rtoc_set_task_ref_table(ctx, static_cast<int>(k), tab.data(), static_cast<int>(tab.size()), 0), "rtoc_set_task_ref_table");
+      }
     }
     chk(rtoc_contact_eval_kkt(ctx), "rtoc_contact_eval_kkt");
   }
@@ -171,6 +181,7 @@ class ConfigurationCostSource : public StageDataSource {
   std::vector<double> crot_;   // [grid point][contact][9] or empty (surface contacts: ContactSequence rotations)
   Solution s0_;
   std::vector<rtoc_task_cost> tasks_;
+  std::vector<std::shared_ptr<TaskCostComponent>> task_costs_;
   std::vector<rtoc_box_row> rows_;
   std::vector<double> bounds_, mu_;
   bool impact_cone_ = false;

@@ -1,7 +1,12 @@
-// robotoc_hip_task_costs.hpp -- TaskSpace3DCost, CoMCost, PeriodicSwingFootRef and PeriodicCoMRef with the reference's
-// constructors and setters (src/cost/task_space_3d_cost.cpp, com_cost.cpp, periodic_swing_foot_ref.cpp, periodic_com_ref.cpp).
-// They describe the terms; rtoc_contact_eval_kkt evaluates them on the device (include/rtoc_robot.h: rtoc_task_cost).  Hand
-// them to the ConfigurationCostSource overload of robotoc_hip_device_source.hpp.  Header-only, C++11.
+// robotoc_hip_task_costs.hpp -- TaskSpace3DCost, CoMCost, TaskSpace6DCost, PeriodicSwingFootRef, PeriodicCoMRef and
+// TaskSpace6DRefBase with the reference's constructors and setters (src/cost/task_space_3d_cost.cpp, com_cost.cpp,
+// task_space_6d_cost.cpp, periodic_swing_foot_ref.cpp, periodic_com_ref.cpp, include/robotoc/cost/task_space_6d_ref_base.hpp).
+// They describe the terms; rtoc_contact_eval_kkt / rtoc_unconstr_eval_kkt evaluate them on the device (include/rtoc_robot.h:
+// rtoc_task_cost).  Hand them to the ConfigurationCostSource overload of robotoc_hip_device_source.hpp or to UnconstrOCP::task_costs
+// (robotoc_hip_unconstr_solver.hpp).  Header-only, C++11.
+//
+// A TaskSpace6DRefBase is the user's own class (the reference ships no concrete one): the shells call its updateRef / isActive
+// once per grid point when they discretise and hand the device a table (rtoc_set_task_ref_table).
 //
 // A frame is a contact frame of the model table (its index k: contact_parent[k], contact_p[k]) or a parent joint with an offset
 // in that joint's frame: the world position of a frame depends on its origin only.  isActive / updateRef restate the reference's
@@ -14,11 +19,33 @@
 #include <stdexcept>
 #include <string>
 
+#include <vector>
+
 #include "../../include/rtoc_robot.h"
+#include "robotoc_hip.hpp"
 
 namespace robotoc {
 
 typedef std::array<double, 3> Vector3d;
+typedef std::array<double, 9> Matrix3d;   // row-major
+
+// pinocchio::SE3 as the cost classes use it: SE3(rotation, translation)
+struct SE3 {
+  Matrix3d R;
+  Vector3d p;
+  SE3() : R(Matrix3d{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}}), p(Vector3d{{0.0, 0.0, 0.0}}) {}
+  SE3(const Matrix3d& rotation, const Vector3d& translation) : R(rotation), p(translation) {}
+  const Matrix3d& rotation() const { return R; }
+  const Vector3d& translation() const { return p; }
+};
+
+// include/robotoc/cost/task_space_6d_ref_base.hpp
+class TaskSpace6DRefBase {
+ public:
+  virtual ~TaskSpace6DRefBase() {}
+  virtual void updateRef(const GridInfo& grid_info, SE3& ref_6d) const = 0;
+  virtual bool isActive(const GridInfo& grid_info) const = 0;
+};
 
 class TaskSpace3DRefBase {
  public:
@@ -141,6 +168,9 @@ class TaskCostComponent {
     }
     return s;
   }
+  // a reference that is the user's object: one rtoc_task_ref_entry per grid point (rtoc_set_task_ref_table)
+  virtual bool usesTable() const { return false; }
+  virtual std::vector<rtoc_task_ref_entry> refTable(const std::vector<GridInfo>&) const { return std::vector<rtoc_task_ref_entry>(); }
 
  protected:
   explicit TaskCostComponent(const char* name) : name_(name) {}
@@ -194,6 +224,84 @@ class CoMCost : public TaskCostComponent {
     s.kind = RTOC_TASK_COM;
     return s;
   }
+};
+
+// src/cost/task_space_6d_cost.cpp.  The model table keeps no frames beyond the contacts, so a frame is its parent joint and its
+// placement in that joint's frame (model.frames[frame_id].parent / .placement).
+class TaskSpace6DCost : public TaskCostComponent {
+ public:
+  TaskSpace6DCost(const rtoc_robot_model& robot, const int parent_joint, const SE3& frame_placement)
+      : TaskCostComponent("TaskSpace6DCost"), parent_(parent_joint), frame_(frame_placement) {
+    if (parent_joint < 0 || parent_joint >= robot.njoints) throw std::out_of_range("[TaskSpace6DCost] no such joint");
+    for (int k = 0; k < 6; ++k) weight6_[k] = weight6_terminal_[k] = weight6_impact_[k] = 0.0;
+  }
+  TaskSpace6DCost(const rtoc_robot_model& robot, const int parent_joint, const SE3& frame_placement, const std::shared_ptr<TaskSpace6DRefBase>& ref)
+      : TaskSpace6DCost(robot, parent_joint, frame_placement) { set_ref(ref); }
+  TaskSpace6DCost(const rtoc_robot_model& robot, const int parent_joint, const SE3& frame_placement, const SE3& const_ref)
+      : TaskSpace6DCost(robot, parent_joint, frame_placement) { set_const_ref(const_ref); }
+  TaskSpace6DCost(const rtoc_robot_model& robot, const int parent_joint, const SE3& frame_placement, const Vector3d& const_position_ref,
+                  const Matrix3d& const_rotation_ref)
+      : TaskSpace6DCost(robot, parent_joint, frame_placement) { set_const_ref(const_position_ref, const_rotation_ref); }
+
+  void set_ref(const std::shared_ptr<TaskSpace6DRefBase>& ref) { ref6_ = ref; }
+  void set_const_ref(const SE3& const_ref) { const_ref6_ = const_ref, ref6_.reset(); }
+  void set_const_ref(const Vector3d& const_position_ref, const Matrix3d& const_rotation_ref) { set_const_ref(SE3(const_rotation_ref, const_position_ref)); }
+  void set_weight(const Vector3d& weight_position, const Vector3d& weight_rotation) {
+    fill(weight6_, weight_position, weight_rotation, "weight_position", "weight_rotation");
+  }
+  void set_weight_terminal(const Vector3d& weight_position_terminal, const Vector3d& weight_rotation_terminal) {
+    fill(weight6_terminal_, weight_position_terminal, weight_rotation_terminal, "weight_position_terminal", "weight_rotation_terminal");
+  }
+  void set_weight_impact(const Vector3d& weight_position_impact, const Vector3d& weight_rotation_impact) {
+    fill(weight6_impact_, weight_position_impact, weight_rotation_impact, "weight_position_impact", "weight_rotation_impact");
+  }
+  bool isCostActive(const GridInfo& grid_info) const { return ref6_ ? ref6_->isActive(grid_info) : true; }
+
+  rtoc_task_cost term() const override {
+    rtoc_task_cost s = rtoc_task_cost();
+    s.kind = RTOC_TASK_FRAME_6D, s.frame_parent = parent_;
+    for (int k = 0; k < 3; ++k) s.frame_p[k] = frame_.p[k];
+    for (int k = 0; k < 9; ++k) s.frame_R[k] = frame_.R[k], s.ref_R[k] = k % 4 == 0 ? 1.0 : 0.0;
+    // the six weights in the order they multiply d = [linear; angular] (include/rtoc_robot.h: WEIGHT ORDER): the first triple is
+    // what the caller passed as weight_rotation, the second what they passed as weight_position -- the reference as written
+    for (int k = 0; k < 3; ++k) {
+      s.weight[k] = weight6_[k], s.weight_angular[k] = weight6_[3 + k];
+      s.weight_terminal[k] = weight6_terminal_[k], s.weight_angular_terminal[k] = weight6_terminal_[3 + k];
+      s.weight_impact[k] = weight6_impact_[k], s.weight_angular_impact[k] = weight6_impact_[3 + k];
+    }
+    if (ref6_) {
+      s.ref_kind = RTOC_REF_TABLE;
+    } else {
+      s.ref_kind = RTOC_REF_CONST;
+      for (int k = 0; k < 3; ++k) s.x0[k] = const_ref6_.p[k];
+      for (int k = 0; k < 9; ++k) s.ref_R[k] = const_ref6_.R[k];
+    }
+    return s;
+  }
+  bool usesTable() const override { return static_cast<bool>(ref6_); }
+  std::vector<rtoc_task_ref_entry> refTable(const std::vector<GridInfo>& grid) const override {
+    std::vector<rtoc_task_ref_entry> out(ref6_ ? grid.size() : 0);
+    for (size_t i = 0; i < out.size(); ++i) {
+      SE3 ref;   // updateRef is only called where the reference is active (task_space_6d_cost.hpp:200-209)
+      out[i].active = ref6_->isActive(grid[i]) ? 1 : 0, out[i].pad = 0;
+      if (out[i].active) ref6_->updateRef(grid[i], ref);
+      for (int k = 0; k < 9; ++k) out[i].R[k] = ref.R[k];
+      for (int k = 0; k < 3; ++k) out[i].p[k] = ref.p[k];
+    }
+    return out;
+  }
+
+ private:
+  // task_space_6d_cost.cpp:114-127, as written: weight_.head<3>() = weight_rotation, weight_.tail<3>() = weight_position, and
+  // weight_ multiplies Log6Map(...) = [linear; angular] componentwise -- `weight_rotation` weights the linear components
+  void fill(double* w6, const Vector3d& wp, const Vector3d& wr, const char* np, const char* nr) const {
+    check(wp, np), check(wr, nr);
+    for (int k = 0; k < 3; ++k) w6[k] = wr[k], w6[3 + k] = wp[k];
+  }
+  int parent_ = 0;
+  SE3 frame_, const_ref6_;
+  double weight6_[6], weight6_terminal_[6], weight6_impact_[6];
+  std::shared_ptr<TaskSpace6DRefBase> ref6_;
 };
 
 }  // namespace robotoc

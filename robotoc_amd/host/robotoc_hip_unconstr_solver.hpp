@@ -6,9 +6,9 @@
 // updateSolution (:96-118) is left on the host here: for a fixed-base robot without contacts the cost
 // (ConfigurationSpaceCost), the state equation, the rigid-body linearisation, the condensation, the Riccati recursion,
 // the expansion and the solution update all run in rtoc_unconstr_update_solution (include/rtoc_robot.h).
-// The six joint-limit components of the reference's examples run on the device too (unconstr_constraints.hpp).  What the
-// reference's OCP can carry beyond that -- other cost components, the line search -- is not part of this path
-// (std::logic_error if the line search is requested).
+// The six joint-limit components of the reference's examples run on the device too (unconstr_constraints.hpp), and so do
+// the task-space components of the cost function (UnconstrOCP::task_costs: TaskSpace6DCost / TaskSpace3DCost / CoMCost,
+// examples/iiwa14/task_space_ocp.cpp) and the filter line search.
 #ifndef ROBOTOC_HIP_UNCONSTR_SOLVER_HPP_
 #define ROBOTOC_HIP_UNCONSTR_SOLVER_HPP_
 
@@ -18,6 +18,7 @@
 
 #include "../../include/rtoc_robot.h"
 #include "robotoc_hip_solver.hpp"
+#include "robotoc_hip_task_costs.hpp"
 
 namespace robotoc {
 
@@ -33,6 +34,9 @@ struct UnconstrOCP {
   std::vector<rtoc_box_row> constraint_rows;
   std::vector<double> constraint_bounds;
   double barrier_param = 1.0e-03;  // ConstraintsBase default
+  // the cost function's components beside the ConfigurationSpaceCost (at most RTOC_MAX_TASK_COSTS); a TaskSpace6DRefBase is
+  // asked at t + i dt of every grid point when the solver discretises
+  std::vector<std::shared_ptr<TaskCostComponent>> task_costs;
 };
 
 class UnconstrOCPSolver {
@@ -51,6 +55,15 @@ class UnconstrOCPSolver {
     check(rtoc_get_layout(c, &L_), "rtoc_get_layout");
     check(rtoc_set_robot_model(c, &ocp.robot), "rtoc_set_robot_model");
     check(rtoc_set_configuration_cost(c, &ocp.cost), "rtoc_set_configuration_cost");
+    if (ocp.task_costs.size() > static_cast<size_t>(RTOC_MAX_TASK_COSTS)) throw std::invalid_argument("[UnconstrOCPSolver] at most RTOC_MAX_TASK_COSTS task-space costs");
+    if (!ocp.task_costs.empty()) {
+      std::vector<rtoc_task_cost> terms;
+      for (const auto& t : ocp.task_costs) {
+        if (!t) throw std::invalid_argument("[UnconstrOCPSolver] null task-space cost");
+        terms.push_back(t->term());
+      }
+      check(rtoc_set_task_costs(c, terms.data(), static_cast<int>(terms.size()), 0), "rtoc_set_task_costs");
+    }
     if (!ocp.constraint_rows.empty())
       check(rtoc_set_constraint_rows(c, ocp.constraint_rows.data(), static_cast<int>(ocp.constraint_rows.size())), "rtoc_set_constraint_rows");
     s_.assign(ocp.N + 1, SplitSolution(dims_));
@@ -92,8 +105,8 @@ class UnconstrOCPSolver {
       check(rtoc_set_constraint_bounds(ctx_.get(), ocp_.constraint_bounds.data(), static_cast<int>(ocp_.constraint_bounds.size()),
                                        ocp_.barrier_param, solver_options.fraction_to_boundary_rule), "rtoc_set_constraint_bounds");
   }
-  // discretize (:85-88): N uniform intervals, no events
-  void discretize(const double) {
+  // discretize (:85-88): N uniform intervals, no events; GridInfo::t = t + i dt for the references of the task-space costs
+  void discretize(const double t) {
     std::vector<rtoc_grid> g(ocp_.N + 1);
     for (int i = 0; i <= ocp_.N; ++i) {
       g[i] = rtoc_grid{};
@@ -103,6 +116,21 @@ class UnconstrOCPSolver {
       g[i].dt = i == ocp_.N ? 0.0 : dt_;
     }
     check(rtoc_set_grid(ctx_.get(), g.data(), ocp_.N + 1), "rtoc_set_grid");
+    if (ocp_.task_costs.empty()) return;
+    std::vector<double> times(ocp_.N + 1);
+    std::vector<GridInfo> grid(ocp_.N + 1);
+    for (int i = 0; i <= ocp_.N; ++i) {
+      times[i] = t + i * dt_;
+      grid[i].type = i == ocp_.N ? GridType::Terminal : GridType::Intermediate;
+      grid[i].t0 = t, grid[i].t = times[i], grid[i].dt = g[i].dt, grid[i].stage = i, grid[i].stage_in_phase = i;
+      grid[i].num_grids_in_phase = ocp_.N;
+    }
+    check(rtoc_set_grid_times(ctx_.get(), times.data(), ocp_.N + 1), "rtoc_set_grid_times");
+    for (size_t k = 0; k < ocp_.task_costs.size(); ++k) {
+      if (!ocp_.task_costs[k]->usesTable()) continue;
+      const std::vector<rtoc_task_ref_entry> tab = ocp_.task_costs[k]->refTable(grid);
+      check(rtoc_set_task_ref_table(ctx_.get(), static_cast<int>(k), tab.data(), static_cast<int>(tab.size()), 0), "rtoc_set_task_ref_table");
+    }
   }
   // initConstraints (:91-93): setSlackAndDual of the joint-limit rows at the current iterate
   void initConstraints() {

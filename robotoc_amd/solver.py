@@ -13,6 +13,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import capi
+from .costs import grid_infos
 from .grid import ContactSequence, Event, contact_masks, discretize, discretize_structure_preserving, max_time_step
 from .types import BUF_SOL, GRID_IMPACT, GRID_LIFT, GRID_TERMINAL, Dims, Records, joint_limit_rows
 
@@ -147,7 +148,7 @@ class OCPSolver:
                  batch=1, device=0, impact_cones=False, task_costs=None):
         """cost: keyword arguments of capi.Context.set_configuration_cost; joint_limits: (q_min, q_max, v_max, u_max) over the
         actuated joints or None; friction_coefficients: per contact or None; task_costs: robotoc_amd.costs.TaskSpace3DCost /
-        CoMCost components added to the configuration cost (a list shared by the batch) or None."""
+        CoMCost / TaskSpace6DCost components added to the configuration cost (a list shared by the batch) or None."""
         self.model, self.plan, self.T, self.N = model, plan, float(T), int(N)
         self.options = options or SolverOptions()
         self.sto = sto_constraints
@@ -216,6 +217,8 @@ class OCPSolver:
         c.set_grid(grids)
         if self.task_costs:
             c.set_grid_times(times)   # the periodic references' GridInfo::t (with STO the device keeps its own per instance)
+            # references that are the user's objects: asked once per grid point (rtoc_set_grid has just forgotten the tables)
+            c.set_task_ref_tables(self.task_costs, grid_infos(times, [g.dt for g in grids]))
         self.masks = contact_masks(grids, self.plan.phase_masks, self.plan.impact_masks())
         pos, phase = np.zeros((len(grids), self.nc, 3)), 0
         for i, g in enumerate(grids):
