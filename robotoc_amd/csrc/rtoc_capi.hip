@@ -117,6 +117,13 @@ static const KernelSet* find_set(const rtoc_dims* d) {
     if (k.nv == d->nv && k.nu == d->nu && k.ns == d->ns_max) return &k;
   return load_plugin(d);
 }
+// every launch of a kernel of the set: block size and LDS are the descriptor's (extra_lds: what only the launch knows)
+template <class A>
+static void launch(const Kern<A>& k, dim3 grid, hipStream_t stream, const A& a, int extra_lds = 0) {
+  hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), (size_t)(k.lds + extra_lds), stream, a);
+}
+// role-split kernel where it exists
+static int default_bwd_variant(const KernelSet* ks) { return (ks->nvariants >= 3) ? ks->nvariants - 1 : 0; }
 
 static bool model_has_surface_contacts(const rtoc_robot_model& m) {
   for (int k = 0; k < m.ncontacts; ++k)
@@ -153,7 +160,7 @@ static hipError_t set_linearize_lds(const rtoc_robot_model& m, int nlevels, int 
 enum BwdPath { BWD_SCAN, BWD_RV, BWD_RW, BWD_TILE };
 struct BwdPlan {
   BwdPath path = BWD_SCAN;  // horizon scan, register-resident, register-wide (iCub-size shapes), tile-split / role-split
-  bwd_fn kern = nullptr;    // the kernel of the path (scan: its policy kernel; register-wide: the one between the one-stage launches)
+  const Kern<BwdArgs>* kern = nullptr;  // the kernel of the path (scan: its policy kernel; register-wide: the one between the one-stage launches)
   int check_fxx = 0;        // BwdArgs::check_fxx of the register-resident kernel: verify the structured rows as it goes
 };
 // Streams and events of a context.  A base of rtoc_ctx, so that it is destroyed after every member: device memory is freed
@@ -432,7 +439,7 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   c->max_stages = max_stages;
   c->batch = batch;
   c->device = device;
-  c->bwd_variant = (ks->nvariants >= 3) ? ks->nvariants - 1 : 0;  // role-split kernel where it exists
+  c->bwd_variant = default_bwd_variant(ks);
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
@@ -463,20 +470,13 @@ static int create_members(rtoc_ctx* c, const rtoc_dims* dims, const KernelSet* k
   HIP_TRY(c->d_stage_list.reserve(max_stages));
   HIP_TRY(c->d_status.reserve(batch));
   HIP_TRY(hipMemsetAsync(c->d_status.p, 0, sizeof(uint32_t) * batch, c->stream));
-  // dynamic LDS beyond the default limit: every kernel a launch may name (nullptr: not in this shape's kernel set)
-  const struct { const void* f; int bytes; } lds[] = {
-      {(const void*)ks->bwd_sa, ks->bwd_lds[3]},        {(const void*)ks->bwd_rv, ks->bwd_rv_lds},
-      {(const void*)ks->bwd_rv_sa, ks->bwd_rv_lds},     {(const void*)ks->bwd_rv_sto, ks->bwd_rv_lds},
-      {(const void*)ks->bwd_rw, ks->bwd_rw_lds},        {(const void*)ks->cond, ks->cond_lds},
-      {(const void*)ks->cond_split, ks->cond_split_lds}, {(const void*)ks->mjt, ks->mjt_lds},
-      {(const void*)ks->expd, ks->expd_lds},            {(const void*)ks->scan_elt, ks->scan_elt_lds},
-      {(const void*)ks->scan_comb, ks->scan_comb_lds},  {(const void*)ks->fscan_elt, ks->fscan_lds},
-      {(const void*)ks->fscan_comb, ks->fscan_lds},     {(const void*)ks->sto_prep, ks->sto_prep_lds},
-      {(const void*)ks->sto_vec, ks->sto_vec_lds}};
-  for (int v = 0; v < ks->nvariants; ++v)
-    HIP_TRY(hipFuncSetAttribute((const void*)ks->bwd[v], hipFuncAttributeMaxDynamicSharedMemorySize, ks->bwd_lds[v]));
-  for (const auto& k : lds)
-    if (k.f) HIP_TRY(hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
+  // dynamic LDS beyond the default limit: every kernel of the set whose descriptor asks for any (the forward kernel's grid table,
+  // four bytes per grid point on top of none, stays under the default)
+  hipError_t lds_err = hipSuccess;
+  for_each_kernel(*ks, [&](const auto& k) {
+    if (k && k.lds > 0 && lds_err == hipSuccess) lds_err = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
+  });
+  HIP_TRY(lds_err);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -680,7 +680,7 @@ int rtoc_get_option(rtoc_ctx* c, int option, int64_t* value) {
     case RTOC_OPT_LINEARIZE_DOFS_PER_PASS: *value = c->h_model ? c->h_model->dpp : 0; return RTOC_OK;
     case RTOC_OPT_BACKWARD_REGISTER: *value = c->bwd_register; return RTOC_OK;
     case RTOC_OPT_CONDENSE_REGISTER: *value = c->cond_register; return RTOC_OK;
-    case RTOC_OPT_BACKWARD_WAVES: *value = c->ks->bwd_waves[c->bwd_variant]; return RTOC_OK;
+    case RTOC_OPT_BACKWARD_WAVES: *value = c->ks->bwd[c->bwd_variant].threads / 64; return RTOC_OK;
     case RTOC_OPT_SWITCHING_TRANSPORT: *value = c->exact_transport; return RTOC_OK;
     case RTOC_OPT_UNCONSTR_DENSE: *value = c->unconstr_dense; return RTOC_OK;
     case RTOC_OPT_LINEARIZE_FUSED: *value = c->linearize_fused; return RTOC_OK;
@@ -736,11 +736,11 @@ int rtoc_set_option(rtoc_ctx* c, int option, int64_t value) {
     }
     case RTOC_OPT_BACKWARD_WAVES: {
       if (value == 0) {
-        c->bwd_variant = (c->ks->nvariants >= 3) ? c->ks->nvariants - 1 : 0;
+        c->bwd_variant = default_bwd_variant(c->ks);
         return RTOC_OK;
       }
       for (int v = 0; v < c->ks->nvariants; ++v)
-        if (c->ks->bwd_waves[v] == (int)value) {
+        if (c->ks->bwd[v].threads / 64 == (int)value) {
           c->bwd_variant = v;
           return RTOC_OK;
         }
@@ -1001,13 +1001,13 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   s.batch = end;
   s.first = first;
   s.dist = 0;
-  hipLaunchKernelGGL(ks->scan_elt, dim3(n, nb), dim3(SCAN_ELT_NT), ks->scan_elt_lds, stream, s);
+  launch(ks->scan_elt, dim3(n, nb), stream, s);
   int cur = 0;
   for (int d = 1; d < n; d *= 2) {
     s.src = c->d_scan[cur].p;
     s.dst = c->d_scan[cur ^ 1].p;
     s.dist = d;
-    hipLaunchKernelGGL(ks->scan_comb, dim3(n - d, nb, 2), dim3(ks->scan_comb_threads), ks->scan_comb_lds, stream, s);
+    launch(ks->scan_comb, dim3(n - d, nb, 2), stream, s);
     cur ^= 1;
   }
   BwdArgs a = bwd_args(c, first, end);
@@ -1015,22 +1015,21 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   a.scan_ps = c->d_scan[2].p;
   a.scan_ps_stride = ks->scan_ps_stride;
   a.scan_ps_soff = ks->scan_ps_soff;
-  const int v = ks->scan_policy_variant;
   const bool sto = grid_has_sto(c);
   StoScanArgs t;
   // Grids with switching-time optimisation: the bundles of the vector pass (everything of the vector recursion that does not depend
   // on the chain) are prepared by n - 1 more workgroups per instance of the SAME launch -- unless the policy workgroups write the
   // mutated Quu, lu back into the KKT records (RTOC_OPT_WRITEBACK_KKT), which the preparation reads: then it runs first, by itself.
-  const bool ride = sto && !c->writeback && ks->sto_prep_lds <= ks->bwd_lds[v];
+  const bool ride = sto && !c->writeback && ks->sto_prep.lds <= p.kern->lds;
   if (sto) {
     t.kkt = c->buf[RTOC_BUF_KKT].p, t.ric = c->buf[RTOC_BUF_RIC].p, t.grid = c->d_grid.p, t.status = c->d_status.p;
     t.ps = c->d_scan[2].p, t.scr = c->d_scan_sto.p;
     t.nstages = n, t.batch = end, t.first = first, t.max_dts0 = c->max_dts0, t.prof = c->d_prof.p;
-    if (!ride) hipLaunchKernelGGL(ks->sto_prep, dim3(n - 1, nb), dim3(SCAN_STO_PREP_NT), ks->sto_prep_lds, stream, t);
+    if (!ride) launch(ks->sto_prep, dim3(n - 1, nb), stream, t);
   }
   a.sto_scr = ride ? c->d_scan_sto.p : nullptr;
-  hipLaunchKernelGGL(p.kern, dim3(nb, ride ? 2 * n - 1 : n), dim3(64 * ks->bwd_waves[v]), ks->bwd_lds[v], stream, a);
-  if (sto) hipLaunchKernelGGL(ks->sto_vec, dim3(nb), dim3(ks->sto_vec_threads), ks->sto_vec_lds, stream, t);   // s, k, m, the STO quantities
+  launch(*p.kern, dim3(nb, ride ? 2 * n - 1 : n), stream, a);
+  if (sto) launch(ks->sto_vec, dim3(nb), stream, t);   // s, k, m, the STO quantities
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1068,7 +1067,7 @@ static int plan_backward(rtoc_ctx* c, BwdPlan* out) {
   const KernelSet* ks = c->ks;
   // the register kernels: the default variant only (an explicit RTOC_OPT_BACKWARD_WAVES keeps its kernel)
   const bool reg = c->bwd_register && !c->h_grid.empty() && c->nstages >= 2 && c->nstages <= RV_MAX_STAGES && !c->writeback &&
-                   c->bwd_variant == ((ks->nvariants >= 3) ? ks->nvariants - 1 : 0);
+                   c->bwd_variant == default_bwd_variant(ks);
   const bool sto = reg && grid_has_sto(c);
   const bool rw = reg && ks->bwd_rw && !sto && (c->bwd_register >= 2 || c->batch > c->num_cus);
   // the caller may have rewritten the records since the runtime last saw them (a bound buffer, or its pointer handed out)
@@ -1082,18 +1081,18 @@ static int plan_backward(rtoc_ctx* c, BwdPlan* out) {
   };
   BwdPlan p = {BWD_TILE, nullptr, 0};
   if (scan_applies(c)) {
-    p = {BWD_SCAN, ks->bwd[ks->scan_policy_variant], 0};
+    p = {BWD_SCAN, &ks->bwd[ks->scan_policy_variant], 0};
   } else if (reg && ks->bwd_rv && (!sto || (ks->bwd_rv_sto && structured()))) {
     p.path = BWD_RV;
-    p.kern = sto ? ks->bwd_rv_sto : (ks->bwd_rv_sa && structured()) ? ks->bwd_rv_sa : ks->bwd_rv;
+    p.kern = sto ? &ks->bwd_rv_sto : (ks->bwd_rv_sa && structured()) ? &ks->bwd_rv_sa : &ks->bwd_rv;
     // a rewritable buffer may have changed since the check that chose the structured form: the kernel verifies as it goes
-    p.check_fxx = (p.kern != ks->bwd_rv && rewritable) ? 1 : 0;
+    p.check_fxx = (p.kern != &ks->bwd_rv && rewritable) ? 1 : 0;
   } else {
     // the register-wide kernel never loads the structured rows of Fxx, so it cannot verify them: check them for every call
     if (rw && rewritable) c->fxx_state = 0;
     const bool s = structured();
     p.path = (rw && s) ? BWD_RW : BWD_TILE;
-    p.kern = (rw && s) ? ks->bwd_rw : s ? ks->bwd_sa : ks->bwd[c->bwd_variant];
+    p.kern = (rw && s) ? &ks->bwd_rw : s ? &ks->bwd_sa : &ks->bwd[c->bwd_variant];
   }
   if (rc) return rc;
   // the plan is part of a captured graph: a new epoch when it changes, not whenever the records are checked again
@@ -1112,7 +1111,7 @@ static int launch_backward_rv(rtoc_ctx* c, const BwdPlan& p, int first, int end,
 #ifdef RTOC_RV_DEBUG_MASK
   if (const char* e = getenv("RTOC_RV_DEBUG")) a.scan_ps_soff = atoi(e);
 #endif
-  if (N >= 1) hipLaunchKernelGGL(p.kern, dim3(end - first), dim3(64), c->ks->bwd_rv_lds, stream, a);
+  if (N >= 1) launch(*p.kern, dim3(end - first), stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1121,7 +1120,6 @@ static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end,
   const KernelSet* ks = c->ks;
   const int N = c->nstages - 1, nb = end - first;
   BwdArgs a = bwd_args(c, first, end);
-  const int v1 = ks->scan_policy_variant;
   auto constrained = [&](int st) { return c->h_grid[st].type != RTOC_GRID_IMPACT && c->h_grid[st].dims > 0; };
   auto one_stage = [&](int st) {   // tile-split kernel, grid point st only (st == N: the terminal record)
     BwdArgs o = a;
@@ -1129,7 +1127,7 @@ static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end,
     o.scan_ps_stride = c->L.ric.stride;
     o.scan_ps_soff = c->L.ric.off[RTOC_RIC_S] - c->L.ric.off[RTOC_RIC_P];
     o.seg_hi = o.seg_lo = st;
-    hipLaunchKernelGGL(ks->bwd[v1], dim3(nb, 1), dim3(64 * ks->bwd_waves[v1]), ks->bwd_lds[v1], stream, o);
+    launch(ks->bwd[ks->scan_policy_variant], dim3(nb, 1), stream, o);
   };
   if (N == 0 || constrained(N - 1)) one_stage(N);   // nobody else writes the terminal record then
   int hi = N - 1;
@@ -1143,7 +1141,7 @@ static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end,
     while (lo > 0 && !constrained(lo - 1)) --lo;
     a.seg_hi = hi;
     a.seg_lo = lo;
-    hipLaunchKernelGGL(p.kern, dim3(nb), dim3(ks->bwd_rw_threads), ks->bwd_rw_lds, stream, a);
+    launch(*p.kern, dim3(nb), stream, a);
     hi = lo - 1;
   }
   HIP_TRY(hipGetLastError());
@@ -1151,9 +1149,7 @@ static int launch_backward_rw(rtoc_ctx* c, const BwdPlan& p, int first, int end,
 }
 
 static int launch_backward_tile(rtoc_ctx* c, const BwdPlan& p, int first, int end, hipStream_t stream) {
-  const int v = c->bwd_variant, ni = c->ks->bwd_inst[v];
-  const BwdArgs a = bwd_args(c, first, end);
-  hipLaunchKernelGGL(p.kern, dim3((end - first + ni - 1) / ni), dim3(64 * c->ks->bwd_waves[v]), c->ks->bwd_lds[v], stream, a);
+  launch(*p.kern, dim3((end - first + p.kern->inst - 1) / p.kern->inst), stream, bwd_args(c, first, end));
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1187,16 +1183,16 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
   s.batch = end;
   s.first = first;
   s.dist = 0;
-  hipLaunchKernelGGL(ks->fscan_elt, dim3(N, nb), dim3(SCAN_FWD_NT), ks->fscan_lds, stream, s);
+  launch(ks->fscan_elt, dim3(N, nb), stream, s);
   int cur = 0;
   for (int d = 1; d < N; d *= 2) {
     s.src = c->d_scan[cur].p;
     s.dst = c->d_scan[cur ^ 1].p;
     s.dist = d;
-    hipLaunchKernelGGL(ks->fscan_comb, dim3(N - d, nb), dim3(SCAN_FWD_NT), ks->fscan_lds, stream, s);
+    launch(ks->fscan_comb, dim3(N - d, nb), stream, s);
     cur ^= 1;
   }
-  hipLaunchKernelGGL(ks->fscan_fin, dim3(n, nb), dim3(64), 0, stream, s);
+  launch(ks->fscan_fin, dim3(n, nb), stream, s);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1214,7 +1210,7 @@ static int launch_forward_range(rtoc_ctx* c, int first, int end, hipStream_t str
   a.first = first;
   // (a structured-Fxx form of this kernel -- top half of Fxx not read, 15 % fewer bytes -- was measured at 1.27 vs
   // 1.28 ms: the kernel is bound by its load queue, not by the bytes it requests; not kept)
-  hipLaunchKernelGGL(c->ks->fwd, dim3(end - first), dim3(c->ks->fwd_threads), (size_t)((a.nstages + 3) & ~3) * sizeof(int), stream, a);  // grid table in LDS
+  launch(c->ks->fwd, dim3(end - first), stream, a, ((a.nstages + 3) & ~3) * (int)sizeof(int));  // grid table in LDS
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1307,23 +1303,23 @@ static int launch_condense(rtoc_ctx* c) {
     a.nlist = c->n_stage_contact;
 #ifdef RTOC_CRV_DEBUG_LDS_PAD   // occupancy experiments (debug builds only): extra dynamic LDS per work item, clamped to what a launch accepts
     static const int lds_pad_env = getenv("RTOC_CRV_LDS_PAD") ? atoi(getenv("RTOC_CRV_LDS_PAD")) : 0;
-    const int lds_room = 64 * 1024 - c->ks->cond_rv_lds;
+    const int lds_room = 64 * 1024 - c->ks->cond_rv.lds;
     const int lds_pad = lds_pad_env < 0 ? 0 : (lds_pad_env > lds_room ? lds_room : lds_pad_env);
 #else
     constexpr int lds_pad = 0;
 #endif
     if (a.nlist > 0) {
-      hipLaunchKernelGGL(a.cone_rows ? c->ks->cond_rv : c->ks->cond_rv_nc, dim3(c->batch * a.nlist), dim3(64), c->ks->cond_rv_lds + lds_pad, c->stream, a);
+      launch(a.cone_rows ? c->ks->cond_rv : c->ks->cond_rv_nc, dim3(c->batch * a.nlist), c->stream, a, lds_pad);
       HIP_TRY(hipGetLastError());
     }
     a.stage_list = c->d_stage_list.p + c->n_stage_contact;
     a.nlist = c->n_stage_impact;
-    if (a.nlist > 0) hipLaunchKernelGGL(c->ks->cond, dim3(c->batch * a.nlist), dim3(c->ks->cond_threads), c->ks->cond_lds, c->stream, a);
+    if (a.nlist > 0) launch(c->ks->cond, dim3(c->batch * a.nlist), c->stream, a);
   } else if (c->condense_split) {
-    hipLaunchKernelGGL(c->ks->mjt, dim3(nblocks), dim3(64), c->ks->mjt_lds, c->stream, a);
-    hipLaunchKernelGGL(c->ks->cond_split, dim3(nblocks), dim3(c->ks->cond_threads), c->ks->cond_split_lds, c->stream, a);
+    launch(c->ks->mjt, dim3(nblocks), c->stream, a);
+    launch(c->ks->cond_split, dim3(nblocks), c->stream, a);
   } else {
-    hipLaunchKernelGGL(c->ks->cond, dim3(nblocks), dim3(c->ks->cond_threads), c->ks->cond_lds, c->stream, a);
+    launch(c->ks->cond, dim3(nblocks), c->stream, a);
   }
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -1351,7 +1347,7 @@ static int launch_expand(rtoc_ctx* c, double tau) {
   hipLaunchKernelGGL(fill_steps_kernel, dim3((2 * c->batch + 255) / 256), dim3(256), 0, c->stream,
                      c->buf[RTOC_BUF_STEP].p, 2 * c->batch);
   const int nblocks = c->batch * (c->nstages - 1);
-  hipLaunchKernelGGL(c->ks->expd, dim3(nblocks), dim3(c->ks->expd_threads), c->ks->expd_lds, c->stream, a);
+  launch(c->ks->expd, dim3(nblocks), c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1386,9 +1382,9 @@ static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 
   a.dl = c->L.dir;
   const dim3 grid(c->batch * (c->nstages - 1));
   if (phase == 0)
-    hipLaunchKernelGGL(wrench ? c->ks->wcond : c->ks->ccond, grid, dim3(64), 0, c->stream, a);
+    launch(wrench ? c->ks->wcond : c->ks->ccond, grid, c->stream, a);
   else if (phase == 1)
-    hipLaunchKernelGGL(wrench ? c->ks->wexp : c->ks->cexp, grid, dim3(64), 0, c->stream, a);
+    launch(wrench ? c->ks->wexp : c->ks->cexp, grid, c->stream, a);
   else
     hipLaunchKernelGGL(cone_update_kernel, grid, dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
@@ -1533,7 +1529,7 @@ static int launch_fill(rtoc_ctx* c, double dt) {
   a.batch = c->batch;
   a.dt = dt;
   a.kl = c->L.kkt;
-  hipLaunchKernelGGL(c->ks->fill, dim3(c->batch * c->nstages), dim3(128), 0, c->stream, a);
+  launch(c->ks->fill, dim3(c->batch * c->nstages), c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1541,7 +1537,7 @@ static int launch_fill(rtoc_ctx* c, double dt) {
 // UnconstrRiccatiRecursion in its structured form (unconstr_riccati.hpp): whenever the shape has the kernels and the
 // horizon scan is not asked for (the scan works on the general elements, i.e. on materialised A, B)
 static bool unconstr_structured(const rtoc_ctx* c) {
-  return c->ks->ubwd != nullptr && c->dims.nf_max == 0 && !scan_applies(c) && !c->unconstr_dense;
+  return c->ks->ubwd && c->dims.nf_max == 0 && !scan_applies(c) && !c->unconstr_dense;
 }
 static int launch_unconstr_riccati(rtoc_ctx* c, double dt, bool forward) {
   int rc = ensure_buffer(c, RTOC_BUF_RIC);
@@ -1558,7 +1554,7 @@ static int launch_unconstr_riccati(rtoc_ctx* c, double dt, bool forward) {
   a.nstages = c->nstages, a.batch = c->batch, a.writeback = c->writeback;
   a.dt = dt;
   a.kl = c->L.kkt, a.rl = c->L.ric, a.dl = c->L.dir;
-  hipLaunchKernelGGL(forward ? c->ks->ufwd : c->ks->ubwd, dim3(c->batch), dim3(64), 0, c->stream, a);
+  launch(forward ? c->ks->ufwd : c->ks->ubwd, dim3(c->batch), c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
@@ -1587,8 +1583,7 @@ static int launch_unconstr_dynamics(rtoc_ctx* c, bool expand, double dt) {
   a.kl = c->L.kkt;
   a.cl = c->L.cdd;
   a.dl = c->L.dir;
-  hipLaunchKernelGGL(expand ? c->ks->uexp : c->ks->ucond, dim3(c->batch * (c->nstages - 1)), dim3(64), 0,
-                     c->stream, a);
+  launch(expand ? c->ks->uexp : c->ks->ucond, dim3(c->batch * (c->nstages - 1)), c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
