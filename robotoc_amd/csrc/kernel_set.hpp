@@ -116,8 +116,8 @@ inline KernelSet make_set() {
   k.bwd[0] = {riccati_backward_kernel<NV, NU, NS, NW0>, 64 * NW0, BwdCfg<NV, NU, NS, NW0>::LDS_BYTES, 1};
   k.bwd[1] = {riccati_backward_kernel<NV, NU, NS, NW1>, 64 * NW1, BwdCfg<NV, NU, NS, NW1>::LDS_BYTES, 1};
   // role-split kernel: matrix wave + vector wave per instance; needs the state in 4 tiles, the control Hessian and the
-  // three free-rider columns of the G product in one 16-column tile
-  if constexpr (2 * NV + 1 <= 64 && NU + 3 <= 16) {
+  // three free-rider columns of the G product in one 16-column tile, and two spare columns in the state's last tile
+  if constexpr (2 * NV + 1 <= 64 && NU + 3 <= 16 && rs_rider_columns_fit<NV>) {
     k.bwd[2] = {riccati_backward_rs_kernel<NV, NU, NS>, 128, BwdCfg<NV, NU, NS, 2>::LDS_BYTES, 1};
     k.nvariants = 3;
     // four instances per workgroup, both waves of an instance on one SIMD

@@ -77,6 +77,11 @@ __device__ __forceinline__ void rs_sync(volatile int* cnt, int& epoch, int lane)
 }
 #define RTOC_BLOCK_SYNC() rs_sync<NI>(sFlag + 1, epoch, lane)
 
+// The matrix wave multiplies Fx and (on STO stages) fx as columns NX and NX + 1 of the LAST 16-column tile of A: a state that
+// fills its last tile (nv a multiple of 8) has no room for them, and such a shape gets no role-split kernel (make_set).
+template <int NV>
+inline constexpr bool rs_rider_columns_fit = ((2 * NV + 15) / 16) * 16 >= 2 * NV + 2;
+
 // SA ("structured A"): the caller guarantees (rtoc_check_fxx_structure) that the top half of every Fxx has the shape
 // linearizeStateEquation / correctLinearizeStateEquation leave (src/dynamics/state_equation.cpp:52-55,80-82):
 //   rows [NP, NV):  a e_i^T | c e_i^T      (Fqq = a I, Fqv = c I: a = 1, c = dt; c = 0 on impact grids)
@@ -418,7 +423,7 @@ __device__ __forceinline__ void riccati_backward_rs_body(const BwdArgs& a, const
       }
       // last column tile: columns j < NX are A, column NX is Fx (not in STO stages, which keep the
       // VALU path for their extra vectors) -- P+ Fx and PB^T Fx come out of the same MFMAs
-      static_assert(TNX * 16 >= NX + 2, "no spare columns for Fx / fx in the last tile");
+      static_assert(rs_rider_columns_fit<NV>, "no spare columns for Fx / fx in the last tile");
       constexpr int JL = (CNT - 1) * 16;
       // column NX: Fx (-> P+ Fx, PB^T Fx); column NX+1 on STO stages: fx (-> P+ fx, PB^T fx)
       const int colsel = (JL + li == NX) ? 1 : ((JL + li == NX + 1 && sto) ? 2 : 0);

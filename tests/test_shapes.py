@@ -115,6 +115,19 @@ def test_plugin_shapes_build_and_are_picked_up():
         assert lib.rtoc_dims_supported(C.byref(Dims(nv, nu, nv - nu, ns, ns, 0))) == 1, (nv, nu, ns)
 
 
+ARM_SHAPES = [(8, 8, 0), (9, 9, 0), (12, 12, 0), (16, 16, 0)]  # fixed-base arms beyond iiwa14 (tests/test_unconstr_arm_sizes.py)
+
+
+def test_arm_shapes_build_and_are_picked_up():
+    """nv = 8 and 16 fill the last 16-column tile of their state: no role-split backward kernel (kernel_set.hpp: make_set), and they
+    build; 9 and 12 take the LDS form of the structured recursion."""
+    from robotoc_amd import capi
+    lib = capi.lib()
+    for nv, nu, ns in ARM_SHAPES:
+        capi.build_plugin(nv, nu, ns)
+        assert lib.rtoc_dims_supported(C.byref(Dims(nv, nu, 0, 0, 0, 0))) == 1, (nv, nu, ns)
+
+
 def test_library_builds_a_missing_shape_itself_when_asked(tmp_path):
     """RTOC_SHAPE_JIT=1: rtoc_dims_supported / rtoc_create run `make plugin` for a shape nobody built (needs hipcc and the
     source directory the library was built from; a fresh process, because the switch is read from the environment)."""
@@ -122,11 +135,11 @@ def test_library_builds_a_missing_shape_itself_when_asked(tmp_path):
     import subprocess
     import sys
     from robotoc_amd import capi
-    so = os.path.join(os.path.dirname(capi.lib_path()), "librtoc_shape_9_9_0.so")
+    so = os.path.join(os.path.dirname(capi.lib_path()), "librtoc_shape_10_10_0.so")
     if os.path.exists(so):
         os.remove(so)
     code = ("import ctypes as C, sys; sys.path.insert(0, %r); from robotoc_amd import capi; from robotoc_amd.types import Dims; "
-            "print(capi.lib().rtoc_dims_supported(C.byref(Dims(9, 9, 0, 0, 0, 0))))" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+            "print(capi.lib().rtoc_dims_supported(C.byref(Dims(10, 10, 0, 0, 0, 0))))" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     off = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env={**os.environ, "RTOC_SHAPE_JIT": "0"}, timeout=300)
     assert off.stdout.strip().endswith("0"), (off.stdout, off.stderr)
     on = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env={**os.environ, "RTOC_SHAPE_JIT": "1"}, timeout=300)
