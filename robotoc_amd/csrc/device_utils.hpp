@@ -20,6 +20,13 @@ __device__ __forceinline__ d4 mfma16(double a, double b, d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// v_mfma_f64_4x4x4_4b_f64: FOUR independent 4x4x4 products per instruction, one double of A, B and the accumulator per lane.
+// With lane = li + 16 q and li = 4 blk + e (tools/probes/mfma4_layout_probe.hip): a = A_blk[i = e][k = q], b = B_blk[k = q][j = e],
+// result D_blk[i = q][j = e].  18 issue cycles against 64 for mfma16 (tools/probes/mfma_small_probe.hip).
+__device__ __forceinline__ double mfma4(double a, double b, double c) {
+  return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+}
+
 // Row (within the 16x16 tile) of result register r for a lane with q = lane>>4.
 __device__ __forceinline__ constexpr int drow(int q, int r) { return q + 4 * r; }
 

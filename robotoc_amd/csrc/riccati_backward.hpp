@@ -315,7 +315,8 @@ __device__ __forceinline__ void llt_inv_load(LltInvState<NMAX>& s, const double*
   }
   s.bad = false;
 }
-template <int NMAX, int J0, int J1>
+// KEEP_L = false: a caller that reads only Y afterwards; neither 1/diag(L) nor L is stored (linv, Ldst are not touched).
+template <int NMAX, int J0, int J1, bool KEEP_L = true>
 __device__ __forceinline__ void llt_inv_steps(LltInvState<NMAX>& s, double* __restrict__ linv, int n, int lane) {
 #pragma unroll
   for (int j = J0; j < J1; ++j) {
@@ -325,7 +326,7 @@ __device__ __forceinline__ void llt_inv_steps(LltInvState<NMAX>& s, double* __re
       const double inv = rsqrt_d(d);
       const double xj = s.g[j] * inv;  // L[lane][j] | Y[j][lane-YOFF]
       s.g[j] = xj;
-      if (lane == j) linv[j] = inv;
+      if (KEEP_L && lane == j) linv[j] = inv;
 #pragma unroll
       for (int k = j + 1; k < NMAX; ++k) {
         if (k < n) {
@@ -336,11 +337,11 @@ __device__ __forceinline__ void llt_inv_steps(LltInvState<NMAX>& s, double* __re
     }
   }
 }
-template <int NMAX, int LD, int YOFF>
+template <int NMAX, int LD, int YOFF, bool KEEP_L = true>
 __device__ __forceinline__ bool llt_inv_store(const LltInvState<NMAX>& s, double* __restrict__ Ldst, double* __restrict__ Ydst, int n,
                                               int lane) {
   const bool ylane = lane >= YOFF;
-  if (lane < n) {
+  if (KEEP_L && lane < n) {
 #pragma unroll
     for (int k = 0; k < NMAX; ++k)
       if (k < n) Ldst[lane + k * LD] = (k <= lane) ? s.g[k] : 0.0;
@@ -351,14 +352,14 @@ __device__ __forceinline__ bool llt_inv_store(const LltInvState<NMAX>& s, double
   }
   return s.bad;
 }
-template <int NMAX, int LD, int YOFF = 16>
+template <int NMAX, int LD, int YOFF = 16, bool KEEP_L = true>
 __device__ __forceinline__ bool wave_llt_inv(const double* __restrict__ A, double* __restrict__ Ldst,
                                              double* __restrict__ linv, double* __restrict__ Ydst,
                                              int n, int lane) {
   LltInvState<NMAX> s;
   llt_inv_load<NMAX, LD, YOFF>(s, A, n, lane);
-  llt_inv_steps<NMAX, 0, NMAX>(s, linv, n, lane);
-  return llt_inv_store<NMAX, LD, YOFF>(s, Ldst, Ydst, n, lane);
+  llt_inv_steps<NMAX, 0, NMAX, KEEP_L>(s, linv, n, lane);
+  return llt_inv_store<NMAX, LD, YOFF, KEEP_L>(s, Ldst, Ydst, n, lane);
 }
 
 // x <- (L L^T)^-1 x for one right-hand side held in registers (x[NMAX]); L in LDS.

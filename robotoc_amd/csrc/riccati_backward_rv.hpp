@@ -23,6 +23,10 @@
 //   * The stage record comes in by LDS-DMA (global_load_lds_dwordx4: no prefetch registers, no VALU unpack): A into a padded
 //     (conflict-free) layout by per-lane source addresses, Bv | Quu | Fx lx lu as one strip; Qxx and Qxu^T by per-lane loads
 //     straight into accumulators.  The DMA of stage st - 1 is issued when the F product of stage st has read A for the last time.
+//   * NX = 32 + 4 (RvCfg::STRIP4): the 4 leftover state columns and the rider of W = [P+; PB^T] [A | Fx], and the 4 x 5 corner of
+//     F = Qxx + A^T W, run on v_mfma_f64_4x4x4_4b (18 issue cycles for four 4x4x4 blocks against 64 for a 16-wide tile that is 5/16 full):
+//     a register of P+ is, unmoved, the A operand of the four row blocks of its tile, a register of W in C layout the B operand of
+//     four column blocks; the other operand is a broadcast LDS read.
 //   * new P = sym(F): upper tiles computed, diagonal tiles mirrored, lower tiles transposed through a 16 x 17 LDS scratch;
 //     P goes to HBM from the registers during the NEXT stage (coalesced through the symmetric index pair).
 //
@@ -47,6 +51,9 @@ struct RvCfg {
   static constexpr int SCOL = NX - 16 * (T - 1);      // lane of column NX in the last column tile = lane shift of the controls
   static constexpr int G0 = NV / 4;                   // first k group that meets the rows [NV, NX)
   static constexpr int GS = 4 * (T - 1) + SCOL / 4;   // k group of row NX (the first PB^T row) of the stacked operand
+  // the last column tile of W = [P+; PB^T] [A | Fx] on 4x4x4 MFMAs (the stage loop, "D4 layout"): its SCOL = 4 state columns are
+  // one 4-column block, the rider a second one; and the SCOL x (SCOL + 1) corner of F = Qxx + A^T W as one row strip
+  static constexpr bool STRIP4 = (SCOL == 4);
   static constexpr bool OK = (NX + NU == 16 * T) && (NX % 4 == 0) && (NU % 4 == 0) && (SCOL % 4 == 0) && (SCOL >= 1) &&
                              ((NV * NU) % 2 == 0) && (LDP % 2 == 0);
   // ---- LDS carve (doubles) ----
@@ -116,6 +123,22 @@ __device__ __forceinline__ double dpp_from_left(double v) {    // lane li reads 
   return __hiloint2double(hi, lo);
 }
 
+// D4 -> C layout of the last column tile (RvCfg::STRIP4), register R of a tile: within its 16-lane row, lane li takes lane li + 4 R of
+// `d0` on lanes 0..3 (the state block), lane li + 4 R - 4 of `d1` on lanes 4..7 (the rider block), zero on lanes 8..15.  Two DPP
+// moves per half: the bank mask picks the four lanes written, the others keep `old`.
+constexpr int rv_dpp_ctrl(int from) { return from > 0 ? 0x100 + from : (from < 0 ? 0x110 - from : 0xE4); }   // row_shl / row_shr / quad_perm:[0,1,2,3]
+template <int R>
+__device__ __forceinline__ double d4_to_c(double d0, double d1) {
+  int h[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int a0 = e ? __double2hiint(d0) : __double2loint(d0), a1 = e ? __double2hiint(d1) : __double2loint(d1);
+    const int x = __builtin_amdgcn_update_dpp(0, a0, rv_dpp_ctrl(4 * R), 0xF, 0x1, true);
+    h[e] = __builtin_amdgcn_update_dpp(x, a1, rv_dpp_ctrl(4 * R - 4), 0xF, 0x2, true);
+  }
+  return __hiloint2double(h[1], h[0]);
+}
+
 // the n-th upper tile (c, t) of a T x T tiling in the order the transposes take them: off-diagonal tiles first, then the diagonal
 __host__ __device__ constexpr int rv_tile_row(int T, int n) {
   int k = 0;
@@ -173,6 +196,7 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
   static_assert(!SA || (NV % 16 == 2 && C::T == 3 && NP_ > 0 && NP_ <= 8 && NP_ % 2 == 0),
                 "structured form: the lane shift of the c-part is NV mod 16 = 2, corner columns in tiles 0 and 1");
   constexpr int NX = C::NX, T = C::T, LDP = C::LDP, KG = C::KG, KSU = C::KSU, SCOL = C::SCOL, G0 = C::G0, GS = C::GS;
+  constexpr bool STRIP4 = C::STRIP4 && !STO && RTOC_RV_MERGE_PBT;   // (the STO form keeps the 16-wide tile: two more rider columns)
   constexpr int RS = SCOL / 4;   // first register group of the last row tile that holds PB^T rows
   constexpr rtoc_layout SL = StaticLayout<NV, NU, NS>::make();
   constexpr rtoc_record_layout KL = SL.kkt, RL = SL.ric;
@@ -496,8 +520,9 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
     RV_PROF(4);
     if (!impact) {
       rv_lds_sync();
-      // LLT(G) (riccati_factorizer.cpp:49) and Y = L^-1 in the same instruction stream; L itself is not used again
-      if (wave_llt_inv<NU, NU>(sG, scr, smem + OFF_LINV, sY, NU, lane)) stat |= RTOC_STAT_QUU_NOT_SPD;
+      // LLT(G) (riccati_factorizer.cpp:49) and Y = L^-1 in the same instruction stream; L and 1/diag(L) are not used again and
+      // not stored (KEEP_L = false)
+      if (wave_llt_inv<NU, NU, 16, false>(sG, scr, smem + OFF_LINV, sY, NU, lane)) stat |= RTOC_STAT_QUU_NOT_SPD;
       rv_lds_sync();
     }
 
@@ -522,10 +547,56 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
       auto group_dense = [](int g) { return 4 * g < NP_ || 4 * g + 3 >= NV; };
       auto row_dense = [&](int g) { return 4 * g + q < NP_ || 4 * g + q >= NV; };
       const bool sa_tile = SA && t < T - 1;   // (the last column tile carries the riders and stays dense)
+      if constexpr (STRIP4) {
+        if (t == T - 1) {
+          // ---- the last column tile on 4x4x4 MFMAs.  D4 layout: ws4[tm][nb], lane (q = i, li = 4 blk + j) <-> row 16 tm + 4 blk + i, column
+          //      16 (T - 1) + 4 nb + j; nb = 0: the SCOL state columns, nb = 1: the rider Fx (j = 0).  A register of the stacked operand is,
+          //      unmoved, the A operand of the four row blocks of its row tile (P+ symmetric: lane (q = k, li = 4 blk + i) holds row
+          //      16 tm + 4 blk + i at k = 4g + q); the B operand depends on (li & 3, q) only -- a broadcast read, one per k group and
+          //      block, shared by the row tiles.  Structured form: a k group of corner rows and of structured rows k whose c-entry
+          //      (column NV + k) lies left of this tile has no entry in the state block and is skipped there (check_fxx covers those
+          //      rows).  45 (dense: 54) instructions of 18 cycles for 27 of 64 ----
+          static_assert(!SA || NV + NP_ <= 16 * (T - 1), "the corner columns lie left of the last column tile");
+          auto state_block_empty = [](int g) { return SA && 4 * g + 3 < NV && 4 * g + 3 + NV < 16 * (T - 1); };
+          const int j4 = li & 3;
+          const double* pbs = sA + q + (16 * (T - 1) + j4) * LDP;
+          const double* pbr = smem + ST_FX + q;
+          const double mr = (j4 == 0) ? 1.0 : 0.0;
+          double ws4[T][2];
+#pragma unroll
+          for (int tm = 0; tm < T; ++tm) ws4[tm][0] = 0.0, ws4[tm][1] = 0.0;
+          double bs4[2] = {0.0, 0.0}, br4[2];
+          if (!state_block_empty(0)) bs4[0] = pbs[0];
+          br4[0] = pbr[0];
+#pragma unroll
+          for (int g = 0; g < KG; ++g) {
+            if (g + 1 < KG) {
+              if (!state_block_empty(g + 1)) bs4[(g + 1) & 1] = pbs[4 * (g + 1)];
+              br4[(g + 1) & 1] = pbr[4 * (g + 1)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const double b0 = bs4[g & 1], b1 = mr * br4[g & 1];
+#pragma unroll
+            for (int tm = 0; tm < T; ++tm) {
+              if (!state_block_empty(g)) ws4[tm][0] = mfma4(pp[g / 4][tm][g % 4], b0, ws4[tm][0]);
+              ws4[tm][1] = mfma4(pp[g / 4][tm][g % 4], b1, ws4[tm][1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          // the seam: D4 -> C layout (the H^T rows hold their start values Qxu^T, set above; every other register is zero)
+#pragma unroll
+          for (int tm = 0; tm < T; ++tm) {
+            const d4 cv = {d4_to_c<0>(ws4[tm][0], ws4[tm][1]), d4_to_c<1>(ws4[tm][0], ws4[tm][1]), d4_to_c<2>(ws4[tm][0], ws4[tm][1]),
+                           d4_to_c<3>(ws4[tm][0], ws4[tm][1])};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) w[tm][r] = (tm == T - 1 && r >= RS) ? w[tm][r] + cv[r] : cv[r];
+          }
+        }
+      }
       double braw[2];
       braw[0] = pb_[0];
 #pragma unroll
-      for (int g = 0; g < KG; ++g) {
+      for (int g = 0; g < (STRIP4 && t == T - 1 ? 0 : KG); ++g) {
         if (g + 1 < KG) braw[(g + 1) & 1] = pb_[4 * (g + 1)];
         __builtin_amdgcn_sched_barrier(0);
         const double bv = okb ? braw[g & 1] : 0.0;
@@ -630,11 +701,15 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
       }
 #pragma unroll
       for (int ks = 0; ks < KSU; ++ks) hT[t][ks] = w[T - 1][RS + ks];
-      // F[c][t] += A^T[c] W[:, t]: A fragment A[k = 4g + q][m = 16c + li] (the same LDS words as above), B fragment W in its C layout
+      // F[c][t] += A^T[c] W[:, t]: A fragment A[k = 4g + q][m = 16c + li] (the same LDS words as above), B fragment W in its C layout.
+      // STRIP4, the corner tile (T - 1, T - 1): its SCOL = 4 rows as ONE 4x4x4 instruction per k group -- a W register in C layout is,
+      // unmoved, the B operand of four blocks (lane (q = k, li = 4 blk + j): W[4g + k][16 t + 4 blk + j]), the A operand
+      // A[4g + q][16 (T - 1) + (li & 3)] is a broadcast read, and the result (lane (q, li): row 16 (T - 1) + q, column 16 t + li) IS register 0
+      // of the tile in C layout; the rider column comes with it
       double araw[2][T];
       auto load_a = [&](int g, double (&d)[T]) {
 #pragma unroll
-        for (int c = 0; c <= t; ++c) d[c] = sA[q + 4 * g + (16 * c + li) * LDP];
+        for (int c = 0; c <= t; ++c) d[c] = sA[q + 4 * g + (16 * c + ((STRIP4 && c == T - 1) ? (li & 3) : li)) * LDP];
       };
       if constexpr (!SA) {
       load_a(0, araw[0]);
@@ -645,6 +720,10 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
         const double bw = w[g / 4][g % 4];
 #pragma unroll
         for (int c = 0; c <= t; ++c) {
+          if (STRIP4 && c == T - 1) {
+            f[c][t][0] = mfma4(araw[g & 1][c], bw, f[c][t][0]);
+            continue;
+          }
           const double av = (c < T - 1 || li < SCOL) ? araw[g & 1][c] : 0.0;
           f[c][t] = mfma16(av, bw, f[c][t]);
         }
@@ -669,9 +748,10 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
 #pragma unroll
           for (int c = 0; c <= t; ++c) {
             if (corner_only && c == T - 1) continue;
-            double av = (c < T - 1 || li < SCOL) ? araw[par][c] : 0.0;
+            double av = (c < T - 1 || li < SCOL || STRIP4) ? araw[par][c] : 0.0;
             av = row_dense(g) ? av : 0.0;
-            f[c][t] = mfma16(av, bw, f[c][t]);
+            if (STRIP4 && c == T - 1) f[c][t][0] = mfma4(av, bw, f[c][t][0]);
+            else f[c][t] = mfma16(av, bw, f[c][t]);
           }
           __builtin_amdgcn_sched_barrier(0);
           par ^= 1;
@@ -822,7 +902,7 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
 #pragma unroll
             for (int c = 0; c < T; ++c) t1[c] = mfma16(zd[ks], zt[c][ks], t1[c]);   // Zd^T Zh - [Phix | -Pres]
           rv_lds_sync();
-          if (wave_llt_inv<NS, NS>(sS, sLs, sLsInv, sWs, ns, lane)) stat |= RTOC_STAT_S_NOT_SPD;
+          if (wave_llt_inv<NS, NS, 16, false>(sS, sLs, sLsInv, sWs, ns, lane)) stat |= RTOC_STAT_S_NOT_SPD;   // (only Ws is read)
           rv_lds_sync();
           d4 eh[T], mm[T];
 #pragma unroll

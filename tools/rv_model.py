@@ -32,6 +32,72 @@ def mfma16(a, b, c):
     return out
 
 
+def mfma4(a, b, c):
+    """v_mfma_f64_4x4x4_4b_f64: FOUR independent products D_blk = A_blk B_blk + C_blk, one double of each per lane.  Probed layout
+    (tools/probes/mfma4_layout_probe.hip): A lane = 16 k + 4 blk + i, B lane = 16 k + 4 blk + j, D lane = 16 i + 4 blk + j, i.e. with
+    lane = li + 16 q: a = A_blk[i = li & 3][k = q], b = B_blk[k = q][j = li & 3], c, d = D_blk[i = q][j = li & 3], blk = li >> 2."""
+    BLK, E = LI >> 2, LI & 3
+    A = np.zeros((4, 4, 4))
+    B = np.zeros((4, 4, 4))
+    A[BLK, E, Q] = a
+    B[BLK, Q, E] = b
+    D = np.einsum("bik,bkj->bij", A, B)
+    return c + D[BLK, Q, E]
+
+
+def dpp_banked(old, v, frm, bank_mask):
+    """v_mov_b32_dpp with a bank mask: lanes of the 16-lane row whose bank (li >> 2) is in `bank_mask` take lane li + frm of the row
+    (row_shl:frm, row_shr:-frm or the identity quad_perm; bound_ctrl: 0 beyond the row), the others keep `old`."""
+    out = np.array(old, dtype=float, copy=True)
+    for lane in range(64):
+        if (bank_mask >> ((lane & 15) >> 2)) & 1:
+            src = (lane & 15) + frm
+            out[lane] = v[(lane & ~15) + src] if 0 <= src < 16 else 0.0
+    return out
+
+
+def d4_to_c(r, d0, d1):
+    """Register r of a tile of the last column tile in C layout from the two D4 registers of its row tile: lanes 0..3 take lane
+    li + 4r of the state block, lanes 4..7 lane li + 4r - 4 of the rider block, lanes 8..15 are zero (d4_to_c in the kernel)."""
+    return dpp_banked(dpp_banked(np.zeros(64), d0, 4 * r, 0x1), d1, 4 * r - 4, 0x2)
+
+
+def strip_identities(rng):
+    """The three identities the 4x4x4 strip rests on (NX = 36: the strip is columns / rows 32..35), each against plain numpy.
+    Returns the largest absolute deviation."""
+    NX, T = 36, 3
+    P = rng.standard_normal((NX, NX))
+    P = P + P.T
+    A = rng.standard_normal((NX, NX))
+    pp = to_tiles(P, NX)
+    KG = NX // 4
+    worst = 0.0
+    # 1. a register of symmetric P in C layout is, unmoved, the A operand of the four row blocks of its row tile; the B operand
+    #    depends on (li & 3, q) only.  D4 layout: lane (q = i, li = 4 blk + j) <-> row 16 tm + 4 blk + i, column 32 + j
+    W = P @ A
+    for tm in range(T):
+        d = np.zeros(64)
+        for g in range(KG):
+            d = mfma4(pp[g // 4][tm][:, g % 4], A[4 * g + Q, 32 + (LI & 3)], d)
+        row = 16 * tm + 4 * (LI >> 2) + Q
+        want = np.where(row < NX, W[np.clip(row, 0, NX - 1), 32 + (LI & 3)], 0.0)
+        worst = max(worst, np.abs(d - want).max())
+    # 2. a register of W in C layout (column tile t, k group g) is, unmoved, the B operand of four blocks: the row strip
+    #    F[32..35][16t..16t + 15] = A[:, 32..35]^T W[:, t] with a broadcast A operand A[4g + q][32 + (li & 3)]
+    # 3. ... and its D layout is register 0 of tile (2, t) in C layout (row 32 + q, column 16 t + li)
+    F = A.T @ W
+    wt, ft = to_tiles(W, NX), to_tiles(F, NX)
+    for t in range(T):
+        d = np.zeros(64)
+        for g in range(KG):
+            d = mfma4(A[4 * g + Q, 32 + (LI & 3)], wt[g // 4][t][:, g % 4], d)
+        col = 16 * t + LI
+        want = np.where(col < NX, F[32 + Q, np.clip(col, 0, NX - 1)], 0.0)
+        worst = max(worst, np.abs(d - want).max())                       # identity 2
+        worst = max(worst, np.abs(d - ft[2][t][:, 0]).max())             # identity 3
+    return worst / np.abs(F).max()
+
+
 def row_shift(v, n):
     """DPP row_shr:n (n > 0: lane li takes the value of lane li - n of its 16-lane row; lanes li < n get 0) / row_shl:-n."""
     out = np.zeros_like(v)
@@ -42,7 +108,7 @@ def row_shift(v, n):
     return out
 
 
-def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=False):
+def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=False, strip4=None):
     """pp[kt][mt]: (64,4) tiles of P+ in C layout, zero outside NX x NX; sv[c]: (64,4), s+[16c + 4r + q] on lanes li == SCOL.
     sc = (Phix [ns x NX], Phiu [ns x NU], Pres [ns]) on a grid point with a switching constraint (riccati_factorizer.cpp:58-89).
     Returns (pp_new, sv_new, K, k) and, with sc, (.., M, m)."""
@@ -56,6 +122,8 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
     G0, G1 = NV // 4, (NX + 3) // 4          # aligned k groups that meet the rows [NV, NX)
     KG = (NX + 3) // 4
     z4 = lambda: np.zeros((64, 4))
+    if strip4 is None:
+        strip4 = SCOL == 4                   # RvCfg::STRIP4: the last column tile of W on 4x4x4 MFMAs
     # ---- PB = P+[:, v] Bv with the control columns shifted by SH lanes ----
     acc = [z4() for _ in range(T)]
     gacc = z4()
@@ -93,7 +161,10 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
                 ok = (u >= 0) & (x < NX)
                 pa[TM - 1][c][:, r] = np.where(ok, Qxu[np.clip(x, 0, NX - 1), np.clip(u, 0, NU - 1)], 0.0)
     NP = NV - NU
-    nmf = 0
+    nmf = nmf4 = 0
+    # D4 layout of the last column tile: d4[tm][nb], lane (q = i, li = 4 blk + j) <-> row 16 tm + 4 blk + i, column 16 (T - 1) + 4 nb + j;
+    # nb = 0: the SCOL = 4 state columns, nb = 1: the rider Fx (j = 0)
+    d4 = [[np.zeros(64), np.zeros(64)] for _ in range(TM)]
     in_R = lambda k: (k < NP) | (k >= NV)          # rows of A that are dense (corner rows, velocity rows)
     for g in range(KG):
         k = 4 * g + Q
@@ -111,6 +182,19 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
             if tm == TM - 1:   # lanes li >= SH: PB^T[u = li - SH][4g + q] = acc at the same lane
                 a = np.where(LI >= SH, acc[g // 4][:, g % 4], a)
             for c in range(T):
+                if strip4 and c == T - 1:
+                    # the operand register unmoved; B is a broadcast read: A[4g + q][32 + (li & 3)] and Fx[4g + q] on the lanes j = 0
+                    b0 = np.where(kok, A[np.clip(k, 0, NX - 1), 16 * (T - 1) + (LI & 3)], 0.0)
+                    b1 = np.where(kok & ((LI & 3) == 0), Fx[np.clip(k, 0, NX - 1)], 0.0)
+                    # structured form: a k group of corner rows and of structured rows whose c-entry (column NV + k) lies left of
+                    # this tile has no entry in the state block
+                    if not (sa and 4 * g + 3 < NV and 4 * g + 3 + NV < 16 * (T - 1)):
+                        assert (not sa) or NV + NP <= 16 * (T - 1)
+                        d4[tm][0] = mfma4(a, b0, d4[tm][0])
+                        nmf4 += 1
+                    d4[tm][1] = mfma4(a, b1, d4[tm][1])
+                    nmf4 += 1
+                    continue
                 if sa and c < T - 1 and tm < TM - 1:
                     # structured column tiles, P+ row tiles: only the k groups that meet dense rows; corner rows (g with rows < NP) only
                     # reach the column tiles that hold corner columns -- all of them here (columns [0, NP) in tile 0, [NV, NV + NP) in tile 1)
@@ -120,6 +204,11 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
                 else:
                     pa[tm][c] = mfma16(a, bs[c], pa[tm][c])
                 nmf += 1
+    if strip4:
+        # the seam: D4 -> C layout, added to the start values (Qxu^T in the H^T rows)
+        for tm in range(TM):
+            for r in range(4):
+                pa[tm][T - 1][:, r] += d4_to_c(r, d4[tm][0], d4[tm][1])
     if sa:
         # structured rows k in [NP, NV) of A: W[:, k] += a S[:, k], W[:, NV + k] += c S[:, k] for the P+ row tiles of the structured
         # column tiles (the PB^T rows and the last column tile went through the dense products above)
@@ -181,6 +270,15 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
                 if (4 * g + 3 < NP) and c == T - 1:
                     continue
             for t in range(c, T):
+                if strip4 and c == T - 1:
+                    # the corner tile as a row strip: W in C layout is, unmoved, the B operand of four blocks; the A operand
+                    # A[4g + q][16 (T - 1) + (li & 3)] is a broadcast read; the result is register 0 of the tile in C layout (rider included)
+                    ab = np.where(kok, A[np.clip(k, 0, NX - 1), 16 * (T - 1) + (LI & 3)], 0.0)
+                    if sa:
+                        ab = np.where(in_R(k), ab, 0.0)
+                    f[c][t][:, 0] = mfma4(ab, pa[g // 4][t][:, g % 4], f[c][t][:, 0])
+                    nmf4 += 1
+                    continue
                 f[c][t] = mfma16(a, pa[g // 4][t][:, g % 4], f[c][t])
                 nmf += 1
     if sa:
@@ -201,6 +299,7 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
                         got = send[LANES ^ 32]
                         f[c][t][:, r] += np.where((i >= NV + NP) & (i < NX), cc * got, 0.0)
     stage.mfma_wf = nmf
+    stage.mfma4_wf = nmf4
     K = np.zeros((NU, NX))
     kv = np.zeros(NU)
     if not impact:
@@ -369,7 +468,9 @@ def from_tiles(pp, NX):
     return P
 
 
-def main():
+def run(stages=(45, 35, 33, 20, 15), sa=True, strip4=None, verbose=True):
+    """The stages `stages` of one ANYmal trot instance (47 grid points: 45, 20 regular, 35 an impact, 33 and 15 switching constraints
+    with 6 rows) through stage() from the oracle's value function of the grid point behind; returns {stage: {field: relative error}}."""
     from oracle import oracle as orc
     from robotoc_amd import problems as pr
     from robotoc_amd.types import GRID_IMPACT, Records
@@ -381,9 +482,8 @@ def main():
     ric = Rr.zeros(1, len(grids))[0]
     kk = kkt.copy()
     orc.riccati_backward(L, grids, kk, ric)
-    worst = 0.0
-    SA = "--dense" not in sys.argv
-    for st in (45, 35, 33, 20, 15):
+    SA, STRIP4, all_errs = sa, strip4, {}
+    for st in stages:
         g = grids[st]
         rec, nxt, out = kkt[st], ric[st + 1], ric[st]
         P1 = Rr.f(nxt, "P").copy()
@@ -400,7 +500,7 @@ def main():
         if g.type != GRID_IMPACT and g.dims > 0:
             sc = (f("Phix")[:g.dims], f("Phiu")[:g.dims], f("Pres")[:g.dims])
         out_ = stage(NV, NU, to_tiles(P1, NX), sv, f("Fxx"), f("Fvu"), f("Qxx"), f("Qxu"), f("Quu"), f("Fx"), f("lx"), f("lu"),
-                     g.type == GRID_IMPACT, sc, sa=SA)
+                     g.type == GRID_IMPACT, sc, sa=SA, strip4=STRIP4)
         pn, svn, K, k = out_[:4]
         P = from_tiles(pn, NX)
         s = np.zeros(NX)
@@ -419,9 +519,20 @@ def main():
         if sc is not None:
             errs["M"] = np.abs(out_[4] - Rr.f(out, "M")[:g.dims]).max() / np.abs(Rr.f(out, "M")[:g.dims]).max()
             errs["m"] = np.abs(out_[5] - Rr.f(out, "m")[:g.dims]).max() / max(np.abs(Rr.f(out, "m")[:g.dims]).max(), 1e-300)
-        print("W + F products: %d MFMAs;" % stage.mfma_wf, end=" ")
-        print("stage", st, "type", g.type, "dims", g.dims, {n: float("%.2e" % v) for n, v in errs.items()})
-        worst = max(worst, max(v for n, v in errs.items()))
+        if verbose:
+            print("W + F products: %d MFMAs (16x16x4) + %d (4x4x4);" % (stage.mfma_wf, stage.mfma4_wf), end=" ")
+            print("stage", st, "type", g.type, "dims", g.dims, {n: float("%.2e" % v) for n, v in errs.items()})
+        all_errs[st] = errs
+    return all_errs
+
+
+def main():
+    e_id = strip_identities(np.random.default_rng(0))
+    print("4x4x4 strip identities: worst deviation %.2e" % e_id)
+    assert e_id < 1e-13, e_id
+    # (--no-strip4: the last column tile on the 16-wide instruction, as the STO instantiation keeps it)
+    errs = run(sa="--dense" not in sys.argv, strip4=False if "--no-strip4" in sys.argv else None)
+    worst = max(v for e in errs.values() for v in e.values())
     assert worst < 1e-10, worst
     print("rv lane model: ok")
 
