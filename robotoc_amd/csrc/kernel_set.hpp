@@ -1,10 +1,10 @@
 // kernel_set.hpp -- the kernels of ONE robot shape <NV, NU, NS> (NF = NS: the reference sizes the switching-
 // constraint blocks with max_dimf too, split_kkt_matrix.cpp:7-34) gathered behind descriptors, so that the host
-// runtime (rtoc_capi.hip) dispatches by dimensions at run time.  Every shape is compiled in its own translation unit
+// runtime (rt_shapes.hip) dispatches by dimensions at run time.  Every shape is compiled in its own translation unit
 // (shape_inst.hip, once per entry of the SHAPES list in the Makefile): adding a robot = one entry + make.
 // A descriptor (Kern) is the kernel's entry point WITH its launch geometry: block size, dynamic LDS, instances per
 // workgroup.  make_set writes the three next to the kernel they belong to (the block size is the kernel's
-// __launch_bounds__), and the host launches through the descriptor alone (rtoc_capi.hip: launch).  Adding a kernel =
+// __launch_bounds__), and the host launches through the descriptor alone (rt_context.hpp: launch).  Adding a kernel =
 // a Kern member of KernelSet, a line in for_each_kernel (the static_assert below refuses the one without the other)
 // and a statement in make_set.
 #pragma once

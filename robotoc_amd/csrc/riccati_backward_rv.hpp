@@ -30,7 +30,7 @@
 //   * new P = sym(F): upper tiles computed, diagonal tiles mirrored, lower tiles transposed through a 16 x 17 LDS scratch;
 //     P goes to HBM from the registers during the NEXT stage (coalesced through the symmetric index pair).
 //
-// Scope (plan_backward, rtoc_capi.hip): shapes whose stacked operand fills its tiles (RvCfg::OK: nv = 18, nu = 12), horizons of at most
+// Scope (plan_backward, rt_sweep.hip): shapes whose stacked operand fills its tiles (RvCfg::OK: nv = 18, nu = 12), horizons of at most
 // RV_MAX_STAGES grid points, RTOC_OPT_WRITEBACK_KKT = 0, the default RTOC_OPT_BACKWARD_WAVES.  ONE launch walks the whole horizon
 // (seg_hi = N - 1, seg_lo = 0): regular, lift, impact and switching-constraint grid points (factorised Schur form, below) are all
 // the kernel's own; grids with switching-time optimisation run the STO instantiation (structured Fxx only; the phase transition

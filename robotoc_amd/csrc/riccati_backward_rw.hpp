@@ -24,7 +24,7 @@
 //   * Record traffic: the dense k groups of A and the strip Fx | lx | lu by LDS-DMA; Bv, Quu, Qxu^T, Qxx by per-lane loads
 //     straight into operand / accumulator registers.
 //
-// Scope (plan_backward, rtoc_capi.hip): grids without switching-time optimisation; switching-constraint grid points are single
+// Scope (plan_backward, rt_sweep.hip): grids without switching-time optimisation; switching-constraint grid points are single
 // launches of the tile-split kernel (its one-stage mode), P+ / s+ handed over through the Riccati records -- the host cuts the
 // horizon into segments [seg_hi .. seg_lo]; structured Fxx; RTOC_OPT_WRITEBACK_KKT = 0.  tests/rw_lane_model.py states the lane
 // algebra in numpy against the oracle (tests/test_rw_lane_model.py).

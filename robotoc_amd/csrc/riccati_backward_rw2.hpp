@@ -21,7 +21,7 @@
 // 1's column tiles of H^T; per wave: G / Y / scratch / vectors (wave 0), Qxu / wave 0's column tiles of H^T (wave 1) -- the landing
 // zone of the wave's Qxx panels.  79 KB per instance.
 //
-// Same scope as riccati_backward_rw.hpp (plan_backward, rtoc_capi.hip): structured Fxx, no switching-time optimisation, switching-
+// Same scope as riccati_backward_rw.hpp (plan_backward, rt_sweep.hip): structured Fxx, no switching-time optimisation, switching-
 // constraint grid points as one-stage launches of the tile-split kernel, batches larger than the device's CU count.
 #pragma once
 #include "riccati_backward_rw.hpp"

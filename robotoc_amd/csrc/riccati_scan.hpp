@@ -1,6 +1,6 @@
 // riccati_scan.hpp -- HIP kernels of the horizon scan (see riccati_scan_core.hpp for the algorithm).
 //
-// Launch sequence of one backward recursion with RTOC_OPT_BACKWARD_SCAN (rtoc_capi.hip: launch_backward_scan):
+// Launch sequence of one backward recursion with RTOC_OPT_BACKWARD_SCAN (rt_sweep.hip: launch_backward_scan):
 //   scan_element_kernel    grid (nstages, batch)      every grid point -> its interval element
 //   scan_combine_kernel    grid (nstages - d, batch, 2) for d = 1, 2, 4, ... : element(i) <- element(i) o element(i+d);
 //                                                     elements that reach the terminal grid point become value

@@ -1,7 +1,7 @@
 // shape_inst.hip -- one translation unit per robot shape: compiled once per entry of the Makefile's SHAPES list with
 //   -DRTOC_SHAPE_NV=.. -DRTOC_SHAPE_NU=.. -DRTOC_SHAPE_NS=.. -DRTOC_SHAPE_NW0=.. -DRTOC_SHAPE_NW1=..
 // (NW0 / NW1: wavefronts per instance of the two tile-split backward variants).  Instantiates every kernel of the
-// shape and hands their entry points to the host runtime (rtoc_capi.hip: kernel_table).
+// shape and hands their entry points to the host runtime (rt_shapes.hip: kernel_table).
 #include <hip/hip_runtime.h>
 
 #include "kernel_set.hpp"
@@ -18,7 +18,7 @@ KernelSet RTOC_SHAPE_FN() {
 
 #ifdef RTOC_SHAPE_PLUGIN
 // Built on its own (make plugin SHAPE=nv:nu:ns:nw0:nw1 -> ../librtoc_shape_<nv>_<nu>_<ns>.so): the host runtime loads the
-// kernel set of a shape that is not in its compiled-in table through this one entry point (rtoc_capi.hip: load_plugin).
+// kernel set of a shape that is not in its compiled-in table through this one entry point (rt_shapes.hip: load_plugin).
 extern "C" int rtoc_shape_plugin(rtoc::KernelSet* out, size_t size_of_kernel_set, size_t abi_stamp) {
   // built from another revision of the kernel headers (table or argument blocks differ): refuse
   if (!out || size_of_kernel_set != sizeof(rtoc::KernelSet) || abi_stamp != rtoc::kernel_abi_stamp()) return -1;

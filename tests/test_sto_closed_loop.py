@@ -6,10 +6,13 @@ computeStepSizes / integrateSolution, mesh refinement with solution interpolatio
 The single iteration is pinned to the reference's sources by tests/test_golden_ref.py (STO fixture); here: convergence of the
 whole solve, the event times it finds, and the converged trajectory re-evaluated by the CPU restatement with the time steps
 that belong to the optimised event times (rigid-body side parity-unpinned, Pinocchio absent)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
-from robotoc_amd.types import GRID_IMPACT, Records
+from robotoc_amd import capi
+from robotoc_amd.types import BUF_CON, BUF_CONE, BUF_SOL, GRID_IMPACT, Records
 
 
 def _residuals(oracle, solver, b, sol):
@@ -135,4 +138,45 @@ def test_icub_jump_example_converges_on_the_device():
         q = S.f(solver.get_solution()[0], "q")
         assert abs(q[len(solver.grids) - 1, 0] - 1.0) < 0.15
     finally:
+        solver.close()
+
+
+@pytest.mark.gpu
+def test_clone_of_a_configured_context_takes_the_same_next_iteration():
+    """rtoc_clone with every subsystem configured at once -- robot model, cost, joint-limit rows, friction cones, switching-time
+    optimisation, filter line search -- after two iterations have moved slacks, duals, event times and filters: one more
+    rtoc_contact_update_solution on the source and on the clone leaves both with the same bits."""
+    from robotoc_amd import problems_jump as pj
+    solver, x0, info = pj.anymal_jump_sto_solver(batch=2)
+    cl = None
+    try:
+        c = solver.ctx
+        c.set_line_search(True)
+        c.set_initial_state(x0)
+        solver.init_constraints()
+        c.line_search_clear()
+        c.sto_set_regularization(0.1)
+        ts0 = c.sto_event_times()
+        for _ in range(2):
+            solver.update_solution(0.0)
+        assert np.abs(c.sto_event_times() - ts0).min() > 0.0   # the event times have moved
+        h = C.c_void_p()
+        assert capi.lib().rtoc_clone(c._h, C.byref(h)) == 0
+        cl = object.__new__(capi.Context)
+        cl.__dict__.update(c.__dict__)
+        cl._h = h.value
+
+        def state(ctx):
+            err = ctx.contact_update_solution(solver.tau)
+            return dict(kkt_error=err, sol=ctx.download_records(BUF_SOL, "sol"), con=ctx.download(BUF_CON, (ctx.buffer_count(BUF_CON),)),
+                        cone=ctx.download(BUF_CONE, (ctx.buffer_count(BUF_CONE),)), event_times=ctx.sto_event_times(),
+                        sto_rows=ctx.sto_constraint_data(), status=ctx.status())
+        src, dup = state(c), state(cl)
+        assert np.isfinite(src["kkt_error"]).all() and (src["status"] == 0).all()
+        assert src["con"].size > 0 and src["cone"].size > 0
+        for name in src:
+            assert np.array_equal(src[name], dup[name]), name
+    finally:
+        if cl is not None:
+            cl.close()
         solver.close()

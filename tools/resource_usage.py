@@ -1,5 +1,5 @@
 """Kernel resource table (VGPRs / AGPRs / scratch / spills / occupancy) from the compiler:
-  hipcc ... -Rpass-analysis=kernel-resource-usage -c rtoc_capi.hip 2> usage.txt; python tools/resource_usage.py usage.txt"""
+  hipcc ... -Rpass-analysis=kernel-resource-usage -c rt_eval_kkt.hip 2> usage.txt  (any unit of robotoc_amd/csrc); python tools/resource_usage.py usage.txt"""
 import re, subprocess, sys
 txt = open(sys.argv[1]).read()
 blocks = re.split(r'remark: Function Name: ', txt)[1:]
