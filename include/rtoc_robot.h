@@ -181,6 +181,25 @@ int rtoc_set_grid_times(rtoc_ctx* ctx, const double* t, int nstages);
  * RTOC_REF_TABLE term without a table returns RTOC_ERR_NOT_READY.  rtoc_clone copies the tables. */
 int rtoc_set_task_ref_table(rtoc_ctx* ctx, int term, const rtoc_task_ref_entry* entries, int nstages, int per_instance);
 int rtoc_get_grid_times(rtoc_ctx* ctx, double* host_out, int count);
+/* LocalContactForceCost (src/cost/local_contact_force_cost.cpp) evaluated by rtoc_contact_eval_kkt behind the terms above and
+ * ahead of the constraints and the dynamics.  Per contact i active at the grid point, d = f_i[0:3] - f_ref[i], o_i its offset
+ * in the stack of the active contacts (3 rows per point contact, 6 per surface contact, only the first 3 of which are touched):
+ * intermediate / lift grids (:81-144): lf[o_i:o_i+3] += dt f_weight[i] d, diag(Qff)[o_i:o_i+3] += dt f_weight[i], the cost value
+ * += dt/2 sum f_weight[i] d^2, and the STO sensitivities hf[o_i:o_i+3] = f_weight[i] d, h += 1/2 sum f_weight[i] d^2
+ * (intermediate_stage.cpp:104-108), dt the instance's own time step with switching-time optimisation; impact grids (:169-230):
+ * the same with fi_ref / fi_weight over the impacting contacts, scale 1, hf and h untouched; the terminal grid (:147-166):
+ * nothing.  Written: RTOC_CDD_LF, the diagonal of RTOC_CDD_QFF, RTOC_CDD_HF, RTOC_KKT_SCAL[RTOC_KKT_SCAL_H] and the cost value
+ * rtoc_contact_eval_ocp sums.
+ * cost[1] shared by the batch (per_instance = 0) or cost[batch] (per_instance = 1); cost = NULL removes the term:
+ * rtoc_contact_eval_kkt then launches exactly what it launched before.  Contacts at and beyond the model's ncontacts are
+ * ignored.  RTOC_ERR_NOT_READY without rtoc_set_robot_model; RTOC_ERR_BAD_ARG: a negative or non-finite weight, a non-finite
+ * reference, a context with dims.nf_max == 0 -- a refused call leaves the term that was set in force.  rtoc_clone copies the
+ * term; rtoc_unconstr_eval_kkt has no contacts and ignores it. */
+typedef struct rtoc_contact_force_cost {
+  double f_ref[RTOC_MAX_CONTACTS][3], f_weight[RTOC_MAX_CONTACTS][3];     /* set_f_ref / set_f_weight   */
+  double fi_ref[RTOC_MAX_CONTACTS][3], fi_weight[RTOC_MAX_CONTACTS][3];   /* set_fi_ref / set_fi_weight */
+} rtoc_contact_force_cost;
+int rtoc_set_contact_force_cost(rtoc_ctx* ctx, const rtoc_contact_force_cost* cost, int per_instance);
 
 /* ---- inequality rows of the contact path evaluated on the device (the Constraints object of examples/anymal/trot.cpp:
  * six joint-limit components + FrictionCone) ----

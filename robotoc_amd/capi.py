@@ -36,7 +36,7 @@ EXPORTS = [
     "rtoc_sto_get_event_times", "rtoc_sto_get_time_steps", "rtoc_sto_get_constraint_data", "rtoc_sto_get_kkt_terms",
     "rtoc_sto_set_slack_dual", "rtoc_contact_eval_ocp", "rtoc_set_line_search", "rtoc_contact_line_search",
     "rtoc_bandwidth_probe", "rtoc_get_option",
-    "rtoc_set_task_costs", "rtoc_set_grid_times", "rtoc_get_grid_times",
+    "rtoc_set_task_costs", "rtoc_set_grid_times", "rtoc_get_grid_times", "rtoc_set_contact_force_cost",
 ]
 
 
@@ -177,6 +177,7 @@ def lib():
         L.rtoc_set_grid_times.argtypes = [vp, dp, C.c_int]
         L.rtoc_set_task_ref_table.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
         L.rtoc_get_grid_times.argtypes = [vp, dp, C.c_int]
+        L.rtoc_set_contact_force_cost.argtypes = [vp, vp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -572,6 +573,19 @@ class Context:
             tab = t.ref_table(infos) if hasattr(t, "ref_table") else None
             if tab is not None:
                 self.set_task_ref_table(k, tab)
+
+    def set_contact_force_cost(self, cost, per_instance=False):
+        """rtoc_set_contact_force_cost: `cost` = a robotoc_amd.costs.LocalContactForceCost (or ContactForceCost struct) shared by the
+        batch, with per_instance a list of `batch` of them; None removes the term"""
+        from .costs import ContactForceCost
+        if cost is None:
+            _chk(lib().rtoc_set_contact_force_cost(self._h, None, 0))
+            return
+        rows = list(cost) if per_instance else [cost]
+        if per_instance and len(rows) != self.batch:
+            raise ValueError("a per-instance force cost needs one term per instance")
+        arr = (ContactForceCost * len(rows))(*[t if isinstance(t, ContactForceCost) else t.to_struct() for t in rows])
+        _chk(lib().rtoc_set_contact_force_cost(self._h, C.cast(arr, C.c_void_p), 1 if per_instance else 0))
 
     def set_grid_times(self, t):
         """rtoc_set_grid_times: GridInfo::t of every grid point of a fixed grid"""

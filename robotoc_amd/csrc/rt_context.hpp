@@ -202,6 +202,9 @@ struct TaskState {
   int reftab_n[RTOC_MAX_TASK_COSTS] = {};
   unsigned reftab_inst = 0;
   int task_rows = 0, task_ext = 0; // LDS rows of the term lists (the largest instance), 1: a 6D term or a table reference among them
+  // LocalContactForceCost (rtoc_set_contact_force_cost; contact_force_cost.hpp): capacity [batch]; in use [1] or [batch]
+  DevBuf<rtoc_contact_force_cost> d_fcost;
+  int fcost_on = 0, fcost_per_instance = 0;
   void clone_from(const TaskState& src, CopyChain& dup) {
     if (src.ntasks > 0) {
       ntasks = src.ntasks, tasks_per_instance = src.tasks_per_instance;
@@ -213,6 +216,10 @@ struct TaskState {
     for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) {
       reftab_n[k] = src.reftab_n[k];
       dup(d_reftab[k], src.d_reftab[k]);
+    }
+    if (src.fcost_on) {
+      fcost_on = 1, fcost_per_instance = src.fcost_per_instance;
+      dup(d_fcost, src.d_fcost);
     }
   }
 };
@@ -381,6 +388,7 @@ int launch_kkt_error(rtoc_ctx* c);
 int ensure_grid_times_inst(rtoc_ctx* c);
 int task_costs_ready(rtoc_ctx* c, bool unconstr);
 int launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out);
+int launch_force_cost(rtoc_ctx* c, double* cost_out);
 // rt_sto.hip
 // one kernel of sto.hpp over the instances of the context
 enum StoKernel { STO_TIME_STEPS, STO_INIT, STO_EVAL_KKT, STO_STEP_SIZES, STO_INTEGRATE };

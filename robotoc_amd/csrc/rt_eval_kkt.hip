@@ -647,6 +647,14 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
       return rc;
     }
   }
+  // LocalContactForceCost: into the lf, Qff and hf the cost kernel has just zeroed, ahead of the cones' cone^T dual
+  if (c->fcost_on) {
+    rc = launch_force_cost(c, c->d_costval.p);
+    if (rc) {
+      c->vals_fresh = 0;
+      return rc;
+    }
+  }
   // constraints_->linearizeConstraints (intermediate_stage.cpp:109-110, impact_stage.cpp:95-96) of the rows evaluated here
   if (c->nrows > 0 && c->d_bounds.p && c->buf[RTOC_BUF_CON].p) rc = launch_ubox(c, UBOX_LINEARIZE, true);
   if (!rc && device_cones_on(c) && c->buf[RTOC_BUF_CON].p) rc = launch_contact_cones(c, CC_LINEARIZE);

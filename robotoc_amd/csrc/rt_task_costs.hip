@@ -1,6 +1,8 @@
-// rt_task_costs.hip -- the task-space cost terms of evalKKT: terms, grid times, reference tables, the launch.
+// rt_task_costs.hip -- the task-space cost terms of evalKKT: terms, grid times, reference tables, the launch; the contact-force
+// cost term of the contact path.
 #include "rt_context.hpp"
 #include "task_space_cost.hpp"
+#include "contact_force_cost.hpp"
 
 using namespace rtoc;
 
@@ -162,6 +164,53 @@ int rtoc::launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out) {
     if (ext) hipLaunchKernelGGL((task_space_cost_kernel<1, true>), grid1, dim3(64), lds1, c->stream, a);
     else hipLaunchKernelGGL((task_space_cost_kernel<1, false>), grid1, dim3(64), lds1, c->stream, a);
   }
+  HIP_TRY(hipGetLastError());
+  return RTOC_OK;
+}
+
+// ---- LocalContactForceCost (contact_force_cost.hpp) ----
+int rtoc_set_contact_force_cost(rtoc_ctx* c, const rtoc_contact_force_cost* cost, int per_instance) {
+  if (!c) return RTOC_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!cost) {
+    if (c->fcost_on) c->epoch++;   // the kernel leaves the captured launch sequence
+    c->fcost_on = 0;
+    return RTOC_OK;
+  }
+  if (!c->h_model) return RTOC_ERR_NOT_READY;
+  if (c->dims.nf_max == 0) return RTOC_ERR_BAD_ARG;
+  const int n = per_instance ? c->batch : 1, nc = c->h_model->m.ncontacts;
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < nc; ++k)
+      for (int j = 0; j < 3; ++j) {
+        const double w = cost[i].f_weight[k][j], wi = cost[i].fi_weight[k][j];
+        if (!(w >= 0.0) || !std::isfinite(w) || !(wi >= 0.0) || !std::isfinite(wi)) return RTOC_ERR_BAD_ARG;
+        if (!std::isfinite(cost[i].f_ref[k][j]) || !std::isfinite(cost[i].fi_ref[k][j])) return RTOC_ERR_BAD_ARG;
+      }
+  bool fresh = false;
+  HIP_TRY(c->d_fcost.reserve((size_t)c->batch, &fresh));   // full capacity: a later call may switch to per-instance terms
+  HIP_TRY(hipMemcpyAsync(c->d_fcost.p, cost, sizeof(rtoc_contact_force_cost) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // captured graphs bake the launch, the pointer and the per-instance flag in
+  if (fresh || !c->fcost_on || c->fcost_per_instance != (per_instance ? 1 : 0)) c->epoch++;
+  c->fcost_on = 1, c->fcost_per_instance = per_instance ? 1 : 0;
+  return RTOC_OK;
+}
+
+int rtoc::launch_force_cost(rtoc_ctx* c, double* cost_out) {
+  if (!c->h_model || !c->d_fcost.p || !c->d_active.p) return RTOC_ERR_NOT_READY;
+  const rtoc_robot_model& m = c->h_model->m;
+  ForceCostArgs a;
+  a.rv = view(c);
+  a.cost = c->d_fcost.p;
+  a.cost_out = cost_out;
+  a.per_instance = c->fcost_per_instance;
+  a.ncontacts = m.ncontacts;
+  a.surface = 0;
+  for (int k = 0; k < m.ncontacts; ++k)
+    if (m.contact_type[k] == RTOC_CONTACT_SURFACE) a.surface |= 1u << k;
+  const long long items = (long long)c->batch * c->nstages;
+  hipLaunchKernelGGL(contact_force_cost_kernel, dim3((unsigned)((items + FCOST_GP - 1) / FCOST_GP)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }

@@ -10,7 +10,7 @@ structure the reference produces.
 """
 import math
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 from .types import GRID_IMPACT, GRID_INTERMEDIATE, GRID_LIFT, GRID_TERMINAL, Grid
 
@@ -28,6 +28,10 @@ class ContactSequence:
     """phase_dimf[p] = ContactStatus::dimf() of phase p; events[p] ends phase p."""
     phase_dimf: List[int]
     events: List[Event] = field(default_factory=list)
+    # ContactStatus of every phase where the caller has it: the active-contact bit mask (what contact_masks spreads over the grid)
+    # and the contact positions [ncontacts][3] -- what the DiscreteTime* references of robotoc_amd.costs are set from
+    phase_masks: Optional[List[int]] = None
+    phase_positions: Optional[list] = None
 
     def impacts(self):
         return [e for e in self.events if e.kind == "impact"]
@@ -35,11 +39,24 @@ class ContactSequence:
     def lifts(self):
         return [e for e in self.events if e.kind == "lift"]
 
+    def num_contact_phases(self):
+        """ContactSequence::numContactPhases"""
+        return len(self.phase_dimf)
 
-def discretize(N, T, t, cs: ContactSequence, phase_based=False, times=False):
+    def is_contact_active(self, phase, contact):
+        """contactStatus(phase).isContactActive(contact)"""
+        return bool((int(self.phase_masks[phase]) >> contact) & 1)
+
+    def contact_position(self, phase, contact):
+        """contactStatus(phase).contactPosition(contact)"""
+        return self.phase_positions[phase][contact]
+
+
+def discretize(N, T, t, cs: ContactSequence, phase_based=False, times=False, infos=False):
     """TimeDiscretization::discretize (time_discretization.cpp:43-181) followed, if
     ``phase_based``, by correctTimeSteps (:184-262).  Returns num_grids+1 Grid structs, with ``times``
-    also GridInfo::t of every grid point (what the periodic references of robotoc_amd.costs read)."""
+    also GridInfo::t of every grid point (what the periodic references of robotoc_amd.costs read), with ``infos`` also (last)
+    GridInfo's (type, phase, stage_in_phase, num_grids_in_phase) of every grid point (what the DiscreteTime* references read)."""
     impacts, lifts = cs.impacts(), cs.lifts()
     nmax = N + len(lifts) + 2 * len(impacts) + 2
     g = [dict(type=GRID_INTERMEDIATE, t=0.0, dt=0.0, phase=0, impact_index=-1, lift_index=-1,
@@ -181,8 +198,13 @@ def discretize(N, T, t, cs: ContactSequence, phase_based=False, times=False):
         ts = -1 if gi["type"] == GRID_IMPACT else i
         out.append(Grid(gi["type"], int(gi["sto"]), int(gi["sto_next"]), int(gi["sc"]), dimf, dims,
                         gi["ngp"], ts, gi["dt"]))
+    extra = []
     if times:
-        return out, [g[i]["t"] for i in range(num + 1)]
+        extra.append([g[i]["t"] for i in range(num + 1)])
+    if infos:
+        extra.append([(g[i]["type"], g[i]["phase"], g[i]["sip"], g[i]["ngp"]) for i in range(num + 1)])
+    if extra:
+        return (out, *extra)
     return out
 
 
@@ -211,7 +233,7 @@ def anymal_trot_sequence(t0=0.11, swing=0.2, double_support=0.1, cycles=1):
         ev.append(Event("impact", t, impact_dimf=6))
         phase_dimf.append(12)
         t += double_support
-    return ContactSequence(phase_dimf, ev)
+    return ContactSequence(phase_dimf, ev, phase_masks=[0b1111] + [0b1001, 0b1111, 0b0110, 0b1111] * cycles)
 
 
 def contact_masks(grids, phase_masks, impact_masks):

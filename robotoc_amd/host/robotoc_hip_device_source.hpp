@@ -56,6 +56,8 @@ class ConfigurationCostSource : public StageDataSource {
     }
     task_costs_ = task_costs;
   }
+  // a LocalContactForceCost component of the cost (before the solver is constructed); null: none
+  void setContactForceCost(const std::shared_ptr<LocalContactForceCost>& force_cost) { force_cost_ = force_cost; }
   ContactSequence* contactSequence() override { return cs_.get(); }
   const STOConstraints* stoConstraints() const override { return sto_.get(); }
   double horizonLength() const override { return T_; }
@@ -116,6 +118,10 @@ class ConfigurationCostSource : public StageDataSource {
     chk(rtoc_set_robot_model(ctx, &model_), "rtoc_set_robot_model");
     chk(rtoc_set_configuration_cost(ctx, &cost_), "rtoc_set_configuration_cost");
     if (!tasks_.empty()) chk(rtoc_set_task_costs(ctx, tasks_.data(), static_cast<int>(tasks_.size()), 0), "rtoc_set_task_costs");
+    if (force_cost_) {
+      const rtoc_contact_force_cost fc = force_cost_->term();
+      chk(rtoc_set_contact_force_cost(ctx, &fc, 0), "rtoc_set_contact_force_cost");
+    }
     if (!rows_.empty()) {
       chk(rtoc_set_constraint_rows(ctx, rows_.data(), static_cast<int>(rows_.size())), "rtoc_set_constraint_rows");
       chk(rtoc_set_constraint_bounds(ctx, bounds_.data(), static_cast<int>(bounds_.size()), barrier_, ftb_), "rtoc_set_constraint_bounds");
@@ -145,7 +151,9 @@ class ConfigurationCostSource : public StageDataSource {
       std::vector<double> t(td_.size());
       for (int i = 0; i < td_.size(); ++i) t[i] = td_[i].t;
       chk(rtoc_set_grid_times(ctx, t.data(), td_.size()), "rtoc_set_grid_times");
-      // references that are the user's objects: updateRef / isActive at every grid point of the grid in force
+      // references that are the user's objects, and the DiscreteTime references: updateRef / isActive at every grid point of the
+      // grid in force -- after every (re-)discretisation, mesh refinement included; stage_in_phase / num_grids_in_phase are
+      // structural, so the tables stay valid while the switching times move
       for (size_t k = 0; k < task_costs_.size(); ++k) {
         if (!task_costs_[k]->usesTable()) continue;
         std::vector<GridInfo> grid(td_.size());
@@ -182,6 +190,7 @@ class ConfigurationCostSource : public StageDataSource {
   Solution s0_;
   std::vector<rtoc_task_cost> tasks_;
   std::vector<std::shared_ptr<TaskCostComponent>> task_costs_;
+  std::shared_ptr<LocalContactForceCost> force_cost_;
   std::vector<rtoc_box_row> rows_;
   std::vector<double> bounds_, mu_;
   bool impact_cone_ = false;

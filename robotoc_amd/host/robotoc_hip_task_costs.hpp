@@ -1,12 +1,18 @@
-// robotoc_hip_task_costs.hpp -- TaskSpace3DCost, CoMCost, TaskSpace6DCost, PeriodicSwingFootRef, PeriodicCoMRef and
-// TaskSpace6DRefBase with the reference's constructors and setters (src/cost/task_space_3d_cost.cpp, com_cost.cpp,
-// task_space_6d_cost.cpp, periodic_swing_foot_ref.cpp, periodic_com_ref.cpp, include/robotoc/cost/task_space_6d_ref_base.hpp).
+// robotoc_hip_task_costs.hpp -- TaskSpace3DCost, CoMCost, TaskSpace6DCost, PeriodicSwingFootRef, PeriodicCoMRef,
+// DiscreteTimeSwingFootRef, DiscreteTimeCoMRef, TaskSpace6DRefBase and LocalContactForceCost with the reference's constructors
+// and setters (src/cost/task_space_3d_cost.cpp, com_cost.cpp, task_space_6d_cost.cpp, periodic_swing_foot_ref.cpp,
+// periodic_com_ref.cpp, discrete_time_swing_foot_ref.cpp, discrete_time_com_ref.cpp, local_contact_force_cost.cpp,
+// include/robotoc/cost/task_space_6d_ref_base.hpp).
 // They describe the terms; rtoc_contact_eval_kkt / rtoc_unconstr_eval_kkt evaluate them on the device (include/rtoc_robot.h:
 // rtoc_task_cost).  Hand them to the ConfigurationCostSource overload of robotoc_hip_device_source.hpp or to UnconstrOCP::task_costs
 // (robotoc_hip_unconstr_solver.hpp).  Header-only, C++11.
 //
 // A TaskSpace6DRefBase is the user's own class (the reference ships no concrete one): the shells call its updateRef / isActive
-// once per grid point when they discretise and hand the device a table (rtoc_set_task_ref_table).
+// once per grid point when they discretise and hand the device a table (rtoc_set_task_ref_table).  The DiscreteTime references
+// reach the device the same way: they are functions of a grid point's place in its contact phase, not of its time.  The table
+// fill asks a reference only where the term's weight for that kind of grid point is non-zero and isActive holds (com_cost.cpp:95,
+// 137, 178), and refuses a reference that is not finite: on impact and terminal grid points num_grids_in_phase is 0 and the
+// DiscreteTime references' rate is 0 / 0.
 //
 // A frame is a contact frame of the model table (its index k: contact_parent[k], contact_p[k]) or a parent joint with an offset
 // in that joint's frame: the world position of a frame depends on its origin only.  isActive / updateRef restate the reference's
@@ -15,6 +21,7 @@
 #define ROBOTOC_HIP_TASK_COSTS_HPP_
 
 #include <array>
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -23,6 +30,7 @@
 
 #include "../../include/rtoc_robot.h"
 #include "robotoc_hip.hpp"
+#include "robotoc_hip_planner.hpp"
 
 namespace robotoc {
 
@@ -53,8 +61,31 @@ class TaskSpace3DRefBase {
   virtual bool isActive(const double t) const = 0;
   virtual Vector3d updateRef(const double t) const = 0;
   virtual void fill(rtoc_task_cost& s) const = 0;
+  // The reference's own signatures (task_space_3d_ref_base.hpp, com_ref_base.hpp): what the table fill calls.  A reference
+  // of the grid time alone keeps overriding the forms above.
+  virtual bool isActive(const GridInfo& grid_info) const { return isActive(grid_info.t); }
+  virtual Vector3d updateRef(const GridInfo& grid_info) const { return updateRef(grid_info.t); }
+  // true: served to the device as a table with one entry per grid point (fill then sets RTOC_REF_TABLE)
+  virtual bool usesTable() const { return false; }
 };
 typedef TaskSpace3DRefBase CoMRefBase;
+
+namespace detail {
+inline bool allZero(const double* w, const int n) {
+  for (int k = 0; k < n; ++k)
+    if (w[k] != 0.0) return false;
+  return true;
+}
+inline void checkFiniteRef(const char* name, const GridInfo& g, const double* x, const int n) {
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(x[k]))
+      throw std::invalid_argument(std::string("[") + name + "] the reference at grid point " + std::to_string(g.stage) + " (phase " +
+                                  std::to_string(g.phase) + ", stage " + std::to_string(g.stage_in_phase) + " of " +
+                                  std::to_string(g.num_grids_in_phase) + " in it) is not finite");
+}
+// stage_in_phase / num_grids_in_phase as the reference divides them (0 / 0 on impact and terminal grid points)
+inline double phaseRate(const GridInfo& g) { return static_cast<double>(g.stage_in_phase) / static_cast<double>(g.num_grids_in_phase); }
+}  // namespace detail
 
 class PeriodicSwingFootRef : public TaskSpace3DRefBase {
  public:
@@ -146,6 +177,134 @@ class PeriodicCoMRef : public CoMRefBase {
   bool is_first_move_half_;
 };
 
+// src/cost/discrete_time_swing_foot_ref.cpp
+class DiscreteTimeSwingFootRef : public TaskSpace3DRefBase {
+ public:
+  DiscreteTimeSwingFootRef(const int contact_index, const double swing_height)
+      : contact_index_(contact_index), num_contact_phases_(1), step_height_(swing_height), first_rate_(0.0), last_rate_(0.0) {}
+  void setSwingFootRef(const ContactSequence& contact_sequence) {
+    contact_position_.clear(), is_contact_active_.clear();
+    num_contact_phases_ = contact_sequence.numContactPhases();
+    for (int phase = 0; phase < num_contact_phases_; ++phase) {
+      const std::vector<double>& p = contact_sequence.phasePositions(phase);
+      contact_position_.push_back(Vector3d{{p.at(3 * contact_index_), p.at(3 * contact_index_ + 1), p.at(3 * contact_index_ + 2)}});
+      is_contact_active_.push_back(((contact_sequence.phaseMask(phase) >> contact_index_) & 1u) != 0);
+    }
+    contact_position_.push_back(contact_position_.back());
+    first_rate_ = 1.0, last_rate_ = 1.0;
+  }
+  void setSwingFootRef(const ContactSequence& contact_sequence, const Vector3d& first_contact_position, const Vector3d& last_contact_position,
+                       const double first_rate, const double last_rate) {
+    setSwingFootRef(contact_sequence);
+    contact_position_[0] = first_contact_position;
+    contact_position_[num_contact_phases_] = last_contact_position;
+    first_rate_ = first_rate, last_rate_ = last_rate;
+  }
+  void setSwingFootRef(const std::shared_ptr<ContactSequence>& contact_sequence) { setSwingFootRef(*contact_sequence); }
+  void setSwingFootRef(const std::shared_ptr<ContactSequence>& contact_sequence, const Vector3d& first_contact_position,
+                       const Vector3d& last_contact_position, const double first_rate, const double last_rate) {
+    setSwingFootRef(*contact_sequence, first_contact_position, last_contact_position, first_rate, last_rate);
+  }
+  Vector3d updateRef(const GridInfo& grid_info) const override {
+    Vector3d x = Vector3d{{0.0, 0.0, 0.0}};
+    if (is_contact_active_.at(grid_info.phase)) return x;   // the reference leaves its argument alone where the foot stands
+    double rate = detail::phaseRate(grid_info);
+    if (grid_info.phase == 0) rate = first_rate_ * (1.0 - rate) + rate;
+    else if (grid_info.phase == num_contact_phases_ - 1) rate = last_rate_ * (1.0 - rate) + rate;
+    const Vector3d& a = contact_position_[grid_info.phase == 0 ? 0 : grid_info.phase - 1];
+    const Vector3d& b = contact_position_[grid_info.phase == 0 ? 1 : grid_info.phase + 1];
+    for (int k = 0; k < 3; ++k) x[k] = (1.0 - rate) * a[k] + rate * b[k];
+    if (rate < 0.5) x[2] += 2.0 * rate * step_height_;
+    else x[2] += 2.0 * (1.0 - rate) * step_height_;
+    return x;
+  }
+  bool isActive(const GridInfo& grid_info) const override { return !is_contact_active_.at(grid_info.phase); }
+  // not a function of the time
+  bool isActive(const double) const override { throw std::logic_error("[DiscreteTimeSwingFootRef] isActive needs the GridInfo"); }
+  Vector3d updateRef(const double) const override { throw std::logic_error("[DiscreteTimeSwingFootRef] updateRef needs the GridInfo"); }
+  bool usesTable() const override { return true; }
+  void fill(rtoc_task_cost& s) const override { s.ref_kind = RTOC_REF_TABLE; }
+
+ private:
+  int contact_index_, num_contact_phases_;
+  double step_height_, first_rate_, last_rate_;
+  std::vector<Vector3d> contact_position_;
+  std::vector<bool> is_contact_active_;
+};
+
+// src/cost/discrete_time_com_ref.cpp
+class DiscreteTimeCoMRef : public CoMRefBase {
+ public:
+  explicit DiscreteTimeCoMRef(const std::vector<Vector3d>& com_to_contact_position)
+      : com_to_contact_position_(com_to_contact_position), num_contact_phases_(1), first_rate_(0.0), last_rate_(0.0) {}
+  void setCoMRef(const ContactSequence& contact_sequence) {
+    com_position_.clear(), has_inactive_contacts_.clear();
+    num_contact_phases_ = contact_sequence.numContactPhases();
+    const int nc = contact_sequence.numContacts();
+    if (com_to_contact_position_.size() != static_cast<size_t>(nc)) throw std::invalid_argument("[DiscreteTimeCoMRef] one com_to_contact_position per contact");
+    bool has_active_contacts_prev = true;
+    for (int phase = 0; phase < num_contact_phases_; ++phase) {
+      const std::vector<double>& p = contact_sequence.phasePositions(phase);
+      const unsigned mask = contact_sequence.phaseMask(phase);
+      int num_active_contacts = 0;
+      Vector3d com_avg = Vector3d{{0.0, 0.0, 0.0}};
+      for (int i = 0; i < nc; ++i) {
+        if ((mask >> i) & 1u) {
+          for (int k = 0; k < 3; ++k) com_avg[k] += p.at(3 * i + k);
+          for (int k = 0; k < 3; ++k) com_avg[k] -= com_to_contact_position_[i][k];
+          ++num_active_contacts;
+        }
+      }
+      if (num_active_contacts > 0)
+        for (int k = 0; k < 3; ++k) com_avg[k] *= (1.0 / static_cast<double>(num_active_contacts));
+      com_position_.push_back(com_avg);
+      has_inactive_contacts_.push_back(num_active_contacts < nc);
+      if (!has_active_contacts_prev && phase > 1) com_position_[phase - 1] = mean(com_position_[phase - 2], com_position_[phase]);
+      has_active_contacts_prev = num_active_contacts > 0;
+    }
+    com_position_.push_back(com_position_.back());
+  }
+  void setCoMRef(const ContactSequence& contact_sequence, const Vector3d& first_com_ref, const Vector3d& last_com_ref, const double first_rate,
+                 const double last_rate) {
+    setCoMRef(contact_sequence);
+    const int n = num_contact_phases_;
+    com_position_[0] = first_com_ref;
+    com_position_[n] = last_com_ref;
+    if (n > 1) {
+      if (contact_sequence.phaseMask(1) == 0u) com_position_[1] = mean(com_position_[0], com_position_[2]);
+      if (contact_sequence.phaseMask(n - 1) == 0u) com_position_[n - 1] = mean(com_position_[n - 2], com_position_[n]);
+    }
+    first_rate_ = first_rate, last_rate_ = last_rate;
+  }
+  void setCoMRef(const std::shared_ptr<ContactSequence>& contact_sequence) { setCoMRef(*contact_sequence); }
+  void setCoMRef(const std::shared_ptr<ContactSequence>& contact_sequence, const Vector3d& first_com_ref, const Vector3d& last_com_ref,
+                 const double first_rate, const double last_rate) {
+    setCoMRef(*contact_sequence, first_com_ref, last_com_ref, first_rate, last_rate);
+  }
+  Vector3d updateRef(const GridInfo& grid_info) const override {
+    const int ph = grid_info.phase;
+    if (!has_inactive_contacts_.at(ph)) return com_position_[ph];
+    double rate = detail::phaseRate(grid_info);
+    if (ph == 0) rate = first_rate_ * (1.0 - rate) + rate;
+    else if (ph == num_contact_phases_ - 1) rate = last_rate_ * (1.0 - rate) + rate;
+    Vector3d x;
+    for (int k = 0; k < 3; ++k) x[k] = (1.0 - rate) * com_position_[ph][k] + rate * com_position_[ph + 1][k];
+    return x;
+  }
+  bool isActive(const GridInfo&) const override { return true; }
+  bool isActive(const double) const override { return true; }
+  Vector3d updateRef(const double) const override { throw std::logic_error("[DiscreteTimeCoMRef] updateRef needs the GridInfo"); }
+  bool usesTable() const override { return true; }
+  void fill(rtoc_task_cost& s) const override { s.ref_kind = RTOC_REF_TABLE; }
+
+ private:
+  static Vector3d mean(const Vector3d& a, const Vector3d& b) { return Vector3d{{0.5 * (a[0] + b[0]), 0.5 * (a[1] + b[1]), 0.5 * (a[2] + b[2])}}; }
+  std::vector<Vector3d> com_position_, com_to_contact_position_;
+  std::vector<bool> has_inactive_contacts_;
+  int num_contact_phases_;
+  double first_rate_, last_rate_;
+};
+
 // the weights, references and checks the two components share (CostFunctionComponentBase's part of them)
 class TaskCostComponent {
  public:
@@ -156,6 +315,7 @@ class TaskCostComponent {
   void set_weight_terminal(const Vector3d& weight_terminal) { check(weight_terminal, "weight_terminal"), weight_terminal_ = weight_terminal; }
   void set_weight_impact(const Vector3d& weight_impact) { check(weight_impact, "weight_impact"), weight_impact_ = weight_impact; }
   bool isCostActive(const double t) const { return ref_ ? ref_->isActive(t) : true; }
+  bool isCostActive(const GridInfo& grid_info) const { return ref_ ? ref_->isActive(grid_info) : true; }
   // the device description of the term
   virtual rtoc_task_cost term() const {
     rtoc_task_cost s = rtoc_task_cost();
@@ -169,8 +329,23 @@ class TaskCostComponent {
     return s;
   }
   // a reference that is the user's object: one rtoc_task_ref_entry per grid point (rtoc_set_task_ref_table)
-  virtual bool usesTable() const { return false; }
-  virtual std::vector<rtoc_task_ref_entry> refTable(const std::vector<GridInfo>&) const { return std::vector<rtoc_task_ref_entry>(); }
+  virtual bool usesTable() const { return ref_ && ref_->usesTable(); }
+  virtual std::vector<rtoc_task_ref_entry> refTable(const std::vector<GridInfo>& grid) const {
+    std::vector<rtoc_task_ref_entry> out(usesTable() ? grid.size() : 0);
+    for (size_t i = 0; i < out.size(); ++i) {
+      out[i] = rtoc_task_ref_entry();
+      out[i].R[0] = out[i].R[4] = out[i].R[8] = 1.0;
+      const GridInfo& g = grid[i];
+      const Vector3d& w = g.type == GridType::Terminal ? weight_terminal_ : (g.type == GridType::Impact ? weight_impact_ : weight_);
+      if (detail::allZero(w.data(), 3)) continue;   // enable_cost_ / _terminal_ / _impact_: the reference is not asked
+      out[i].active = ref_->isActive(g) ? 1 : 0;
+      if (!out[i].active) continue;                 // updateRef is only called where the reference is active
+      const Vector3d x = ref_->updateRef(g);
+      detail::checkFiniteRef(name_, g, x.data(), 3);
+      for (int k = 0; k < 3; ++k) out[i].p[k] = x[k];
+    }
+    return out;
+  }
 
  protected:
   explicit TaskCostComponent(const char* name) : name_(name) {}
@@ -283,8 +458,13 @@ class TaskSpace6DCost : public TaskCostComponent {
     std::vector<rtoc_task_ref_entry> out(ref6_ ? grid.size() : 0);
     for (size_t i = 0; i < out.size(); ++i) {
       SE3 ref;   // updateRef is only called where the reference is active (task_space_6d_cost.hpp:200-209)
-      out[i].active = ref6_->isActive(grid[i]) ? 1 : 0, out[i].pad = 0;
-      if (out[i].active) ref6_->updateRef(grid[i], ref);
+      const GridInfo& g = grid[i];
+      const double* const w = g.type == GridType::Terminal ? weight6_terminal_ : (g.type == GridType::Impact ? weight6_impact_ : weight6_);
+      out[i].active = (!detail::allZero(w, 6) && ref6_->isActive(g)) ? 1 : 0, out[i].pad = 0;
+      if (out[i].active) {
+        ref6_->updateRef(g, ref);
+        detail::checkFiniteRef(name_, g, ref.R.data(), 9), detail::checkFiniteRef(name_, g, ref.p.data(), 3);
+      }
       for (int k = 0; k < 9; ++k) out[i].R[k] = ref.R[k];
       for (int k = 0; k < 3; ++k) out[i].p[k] = ref.p[k];
     }
@@ -302,6 +482,43 @@ class TaskSpace6DCost : public TaskCostComponent {
   SE3 frame_, const_ref6_;
   double weight6_[6], weight6_terminal_[6], weight6_impact_[6];
   std::shared_ptr<TaskSpace6DRefBase> ref6_;
+};
+
+// src/cost/local_contact_force_cost.cpp: weights on the first three components of every active contact's force (wrench) in the
+// contact's local frame; f_* on intermediate / lift grid points, fi_* on impact grid points.  Evaluated on the device by
+// rtoc_contact_eval_kkt (rtoc_set_contact_force_cost); hand it to ConfigurationCostSource::setContactForceCost.
+class LocalContactForceCost {
+ public:
+  explicit LocalContactForceCost(const rtoc_robot_model& robot)
+      : max_num_contacts_(robot.ncontacts), f_ref_(robot.ncontacts, zero()), f_weight_(robot.ncontacts, zero()),
+        fi_ref_(robot.ncontacts, zero()), fi_weight_(robot.ncontacts, zero()) {}
+  void set_f_ref(const std::vector<Vector3d>& f_ref) { check(f_ref, "f_ref", false), f_ref_ = f_ref; }
+  void set_f_weight(const std::vector<Vector3d>& f_weight) { check(f_weight, "f_weight", true), f_weight_ = f_weight; }
+  void set_fi_ref(const std::vector<Vector3d>& fi_ref) { check(fi_ref, "fi_ref", false), fi_ref_ = fi_ref; }
+  void set_fi_weight(const std::vector<Vector3d>& fi_weight) { check(fi_weight, "fi_weight", true), fi_weight_ = fi_weight; }
+  // the device description of the term
+  rtoc_contact_force_cost term() const {
+    rtoc_contact_force_cost s = rtoc_contact_force_cost();
+    for (int i = 0; i < max_num_contacts_; ++i)
+      for (int k = 0; k < 3; ++k)
+        s.f_ref[i][k] = f_ref_[i][k], s.f_weight[i][k] = f_weight_[i][k], s.fi_ref[i][k] = fi_ref_[i][k], s.fi_weight[i][k] = fi_weight_[i][k];
+    return s;
+  }
+
+ private:
+  static Vector3d zero() { return Vector3d{{0.0, 0.0, 0.0}}; }
+  void check(const std::vector<Vector3d>& v, const char* what, const bool weight) const {
+    if (v.size() != static_cast<size_t>(max_num_contacts_))
+      throw std::invalid_argument(std::string("[LocalContactForceCost] invalid argument: ") + what + ".size() must be " + std::to_string(max_num_contacts_) + "!");
+    for (const Vector3d& x : v) {
+      if (!std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2]))   // rtoc_set_contact_force_cost would refuse it
+        throw std::invalid_argument(std::string("[LocalContactForceCost] invalid argument: elements of '") + what + "' must be finite!");
+      if (weight && (x[0] < 0.0 || x[1] < 0.0 || x[2] < 0.0))
+        throw std::invalid_argument(std::string("[LocalContactForceCost] invalid argument: elements of '") + what + "' must be non-negative!");
+    }
+  }
+  int max_num_contacts_;
+  std::vector<Vector3d> f_ref_, f_weight_, fi_ref_, fi_weight_;
 };
 
 }  // namespace robotoc

@@ -53,6 +53,16 @@ class ContactPlan:
     events: List[Event] = field(default_factory=list)
     phase_rotations: Optional[List[np.ndarray]] = None   # surface contacts: per phase [ncontacts, 3, 3] (ContactStatus::setContactPlacements)
 
+    # what the DiscreteTime* references of robotoc_amd.costs ask a contact sequence
+    def num_contact_phases(self):
+        return len(self.phase_masks)
+
+    def is_contact_active(self, phase, contact):
+        return bool((int(self.phase_masks[phase]) >> contact) & 1)
+
+    def contact_position(self, phase, contact):
+        return self.phase_positions[phase][contact]
+
     def impact_masks(self):
         out, p = [], 0
         for e in self.events:
@@ -145,10 +155,11 @@ def interpolate_configuration(q1, q2, alpha, floating):
 class OCPSolver:
     def __init__(self, model, plan: ContactPlan, T, N, cost, joint_limits=None, friction_coefficients=None, barrier_param=1.0e-3,
                  fraction_to_boundary_rule=0.995, sto_constraints: Optional[STOConstraints] = None, options: Optional[SolverOptions] = None,
-                 batch=1, device=0, impact_cones=False, task_costs=None):
+                 batch=1, device=0, impact_cones=False, task_costs=None, force_cost=None):
         """cost: keyword arguments of capi.Context.set_configuration_cost; joint_limits: (q_min, q_max, v_max, u_max) over the
         actuated joints or None; friction_coefficients: per contact or None; task_costs: robotoc_amd.costs.TaskSpace3DCost /
-        CoMCost / TaskSpace6DCost components added to the configuration cost (a list shared by the batch) or None."""
+        CoMCost / TaskSpace6DCost components added to the configuration cost (a list shared by the batch) or None; force_cost: a
+        robotoc_amd.costs.LocalContactForceCost (shared by the batch) or None."""
         self.model, self.plan, self.T, self.N = model, plan, float(T), int(N)
         self.options = options or SolverOptions()
         self.sto = sto_constraints
@@ -169,6 +180,9 @@ class OCPSolver:
         self.task_costs = list(task_costs) if task_costs else None
         if self.task_costs:
             c.set_task_costs(self.task_costs)
+        self.force_cost = force_cost
+        if force_cost is not None:
+            c.set_contact_force_cost(force_cost)
         c.set_max_dts0(self.options.max_dts_riccati)
         c.set_backward_scan({"auto": "auto", "on": True, "off": False}[self.options.horizon_scan])
         self.tau = fraction_to_boundary_rule
@@ -205,7 +219,7 @@ class OCPSolver:
         self.t0 = float(t)
         cs = self._sequence(self.event_times.mean(axis=0))
         if self.task_costs:
-            grids, times = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None, times=True)
+            grids, times, structure = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None, times=True, infos=True)
         else:
             grids = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None)
         nev = sum(1 for g in grids if g.type in (GRID_IMPACT, GRID_LIFT))
@@ -217,8 +231,9 @@ class OCPSolver:
         c.set_grid(grids)
         if self.task_costs:
             c.set_grid_times(times)   # the periodic references' GridInfo::t (with STO the device keeps its own per instance)
-            # references that are the user's objects: asked once per grid point (rtoc_set_grid has just forgotten the tables)
-            c.set_task_ref_tables(self.task_costs, grid_infos(times, [g.dt for g in grids]))
+            # references that are the user's objects: asked once per grid point (rtoc_set_grid has just forgotten the tables); the
+            # DiscreteTime* references read the grid point's place in its phase, which the switching times do not move
+            c.set_task_ref_tables(self.task_costs, grid_infos(times, [g.dt for g in grids], structure))
         self.masks = contact_masks(grids, self.plan.phase_masks, self.plan.impact_masks())
         pos, phase = np.zeros((len(grids), self.nc, 3)), 0
         for i, g in enumerate(grids):
