@@ -20,7 +20,8 @@
 // expansion (MJtJinv, MJtJinv_dIDCdqv; Qafqv / Qafu_full on request) are produced in the contact-dynamics record.
 #pragma once
 #include "device_utils.hpp"
-#include "riccati_backward.hpp"  // wave_llt, llt_solve_reg
+#include "kernel_args.hpp"  // CondArgs, ExpArgs
+#include "wave_llt.hpp"     // wave_llt, llt_solve_reg
 #include "lds_gemm.hpp"
 #include "../../include/rtoc.h"
 
@@ -48,50 +49,6 @@ __device__ __forceinline__ void wave_lds_sync_() {
 #else
 #define RTOC_CPROF(k) do { } while (0)
 #endif
-
-struct CondArgs {
-  double* kkt;
-  double* cdd;
-  const rtoc_grid* grid;
-  uint32_t* status;
-  int nstages, batch;
-  double damping;  // RobotModelInfo::contact_inv_damping (robot_model_info.hpp:95)
-  long long* prof;  // optional cycle stamps of work item 0 (tuning aid)
-  double* con;               // constraint records or nullptr
-  const rtoc_box_row* rows;  // [nrows] joint-limit rows (device)
-  const int* entry;          // CSR of the rows per primal entry: [2nv+nu+1] offsets, then row ids
-  const int4* pair;          // per primal entry: {row0, row1, sign0 | level0 << 8, sign1 | level1 << 8}, row = -1: none
-  int nrows;
-  rtoc_record_layout nl;
-  rtoc_record_layout kl, cl;
-  // friction / wrench cone rows condensed by mjtjinv_kernel (split condensation): 0 = none (or done by their
-  // own kernel), RTOC_FRICTION_ROWS, RTOC_WRENCH_ROWS
-  int cone_rows;
-  const double* cone;
-  double* cone_con;  // constraint records (the box rows' `con` may be null when only cones are set)
-  int cone_contacts, cone_dim, cone_row0, cone_stride, cone_dgdf_off, cone_impact;
-  int keep_qaf;  // RTOC_OPT_CONDENSE_KEEP_QAF: also store Qafqv / Qafu_full in the ContactDynamicsData record
-  const double* dt_inst;  // [batch][nstages] per-instance time steps (switching-time optimisation) or nullptr (device_utils.hpp: grid_dt)
-  // work items = batch x these grid points (nullptr: all of 0 .. nstages - 2): the impact grid points behind condense_rv_kernel
-  const int* stage_list;
-  int nlist;
-};
-
-struct ExpArgs {
-  double* cdd;
-  double* dir;
-  double* con;               // constraint records or nullptr
-  const rtoc_box_row* rows;
-  int nrows;
-  rtoc_record_layout nl;
-  unsigned long long* steps; // [batch][2] max primal / dual step (bit patterns of positive doubles)
-  const rtoc_grid* grid;
-  int nstages, batch;
-  rtoc_record_layout cl, dl;
-  double tau;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
-  long long* prof;        // optional cycle stamps (slots 32..39) of the work item in the middle of the launch (tuning aid)
-};
 
 template <int NV, int NU, int NF, int NS, bool SPLIT = false>
 struct CondCfg {
@@ -1355,39 +1312,6 @@ __global__ __launch_bounds__(64) void expand_kernel(ExpArgs a) {
     if (row && hh == 0) dr[DL.off[RTOC_DIR_DBETAMU] + i0] = acc;
   }
   RTOC_CPROF(39);
-}
-
-// updateSlack / updateDual (constraints_impl.hxx:167-182) with the per-instance step sizes
-struct UpdArgs {
-  double* con;
-  const rtoc_box_row* rows;
-  const rtoc_grid* grid;
-  const double* steps;
-  int nrows, nstages, batch;
-  rtoc_record_layout nl;
-};
-
-static __global__ __launch_bounds__(64) void pdipm_update_kernel(UpdArgs a) {
-  const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;
-  const int b = item / nst1, st = item % nst1;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
-  if (g.type == RTOC_GRID_IMPACT) return;
-  double* nr = a.con + ((size_t)b * a.nstages + st) * a.nl.stride;
-  const int* no = a.nl.off;
-  const double ps = a.steps[2 * b], ds = a.steps[2 * b + 1];
-  for (int r = threadIdx.x; r < a.nrows; r += 64) {
-    if (g.time_stage >= a.rows[r].level) {
-      nr[no[RTOC_CON_SLACK] + r] += ps * nr[no[RTOC_CON_DSLACK] + r];
-      nr[no[RTOC_CON_DUAL] + r] += ds * nr[no[RTOC_CON_DDUAL] + r];
-    }
-  }
-}
-
-static __global__ void fill_steps_kernel(double* steps, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) steps[i] = 1.0;
 }
 
 }  // namespace rtoc

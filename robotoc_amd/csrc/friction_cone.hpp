@@ -14,26 +14,11 @@
 // A few kflop per grid point, read-modify-write of a 18x18 block: one wave per grid point.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // ConeArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
 
-struct ConeArgs {
-  double* kkt;
-  double* cdd;
-  double* con;
-  const double* cone;
-  const double* dir;
-  const rtoc_grid* grid;
-  unsigned long long* steps;  // [batch][2] bit patterns (expand) / doubles (update)
-  int nstages, batch;
-  int max_contacts, contact_dim, row0, rows_per_contact;
-  int cone_stride, dgdf_off;
-  int impact_cones;  // RTOC_OPT_IMPACT_CONES: 0 = no rows on impact grids (a Constraints object without ImpactFrictionCone)
-  double tau;
-  rtoc_record_layout kl, cl, nl, dl;
-  long long* prof;
-};
 #ifdef RTOC_ENABLE_PROF
 #define RTOC_KPROF(k) do { if (a.prof && blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) a.prof[(k)] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
@@ -283,22 +268,6 @@ __global__ __launch_bounds__(64) void cone_expand_kernel(ConeArgs a) {
     atomicMin(&a.steps[2 * b + 0], (unsigned long long)__double_as_longlong(fp));
     atomicMin(&a.steps[2 * b + 1], (unsigned long long)__double_as_longlong(fd));
   }
-}
-
-// updateSlack / updateDual of the cone rows (constraints_impl.hxx:167-182)
-static __global__ __launch_bounds__(64) void cone_update_kernel(ConeArgs a) {
-  const int lane = threadIdx.x;
-  const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;
-  const int b = item / nst1, st = item % nst1;
-  if (b >= a.batch) return;
-  const int nact = cone_nact(a.grid[st], a.contact_dim, a.impact_cones);
-  if (lane >= a.rows_per_contact * nact) return;  // <= 5*4 friction rows, <= 17*2 wrench rows
-  double* nr = a.con + ((size_t)b * a.nstages + st) * a.nl.stride;
-  const double* steps = reinterpret_cast<const double*>(a.steps);
-  const int r = a.row0 + lane;
-  nr[a.nl.off[RTOC_CON_SLACK] + r] += steps[2 * b] * nr[a.nl.off[RTOC_CON_DSLACK] + r];
-  nr[a.nl.off[RTOC_CON_DUAL] + r] += steps[2 * b + 1] * nr[a.nl.off[RTOC_CON_DDUAL] + r];
 }
 
 // ---------------------------------------------------------------------------------------------

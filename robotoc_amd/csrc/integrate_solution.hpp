@@ -9,19 +9,10 @@
 // re-normalisation (restated from the Lie-group formulas; Pinocchio absent).  Pure streaming: HBM-bound.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // IntArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-struct IntArgs {
-  double* sol;
-  const double* dir;
-  const double* steps;  // [batch][2]: primal, dual
-  const rtoc_grid* grid;
-  int nstages, batch;
-  int nv, nu, np, nf_max, ns_max;
-  rtoc_record_layout sl, dl;
-};
 
 static __global__ __launch_bounds__(64) void integrate_solution_kernel(IntArgs a) {
   const int lane = threadIdx.x;

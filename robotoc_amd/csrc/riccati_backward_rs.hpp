@@ -1163,35 +1163,4 @@ __global__ __launch_bounds__(512) void riccati_backward_rs4_kernel(BwdArgs a) {
 }
 #undef RTOC_BLOCK_SYNC
 
-// Does every Fxx of the batch have the structure the SA kernels assume (see riccati_backward_rs_body)?  One wave per
-// (instance, grid point); any violation sets *flag.  Reads the top NV rows of Fxx only (~1 GB per 4096 x 47 ANYmal
-// records: 0.2 ms), run once per upload of the KKT records, not per sweep.
-struct FxxCheckArgs {
-  const double* kkt;
-  const rtoc_grid* grid;
-  int* flag;
-  int nstages, batch, nv, np, fxx_off, stride;
-};
-static __global__ __launch_bounds__(64) void fxx_structure_kernel(FxxCheckArgs a) {
-  const int item = blockIdx.x, nst1 = a.nstages - 1;
-  const int b = item / nst1, st = item % nst1;
-  if (b >= a.batch) return;
-  const int nv = a.nv, nx = 2 * nv, np = a.np;
-  const double* A = a.kkt + ((size_t)b * a.nstages + st) * a.stride + a.fxx_off;  // column-major nx x nx
-  const double ca = A[np + (size_t)np * nx], cc = A[np + (size_t)(nv + np) * nx];
-  bool bad = false;
-  for (int e = threadIdx.x; e < nv * nx; e += 64) {
-    const int i = e % nv, j = e / nv;  // rows [0, nv) of column j
-    const double v = A[i + (size_t)j * nx];
-    if (i < np) {
-      const bool corner = j < np || (j >= nv && j < nv + np);
-      if (!corner && v != 0.0) bad = true;
-    } else {
-      const double want = (j == i) ? ca : ((j == nv + i) ? cc : 0.0);
-      if (v != want) bad = true;
-    }
-  }
-  if (__any(bad) && threadIdx.x == 0) atomicOr(a.flag, 1);
-}
-
 }  // namespace rtoc

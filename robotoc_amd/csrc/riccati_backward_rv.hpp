@@ -78,7 +78,6 @@ struct LdsAddr {
   __device__ __forceinline__ explicit LdsAddr(const void* smem) : a((unsigned)(uintptr_t)(lds_ptr_t)smem), g((const char*)smem) {}
   __device__ __forceinline__ lds_ptr_t operator()(const void* p) const { return (lds_ptr_t)(uintptr_t)(a + (unsigned)((const char*)p - g)); }
 };
-constexpr int RV_MAX_STAGES = 64;   // grid points of a horizon the kernel keeps a kind table for (in the slack of its LDS carve)
 
 // Streaming policy of the record traffic (every byte is touched once per sweep): RTOC_RV_NT = 1 marks the loads / DMA / stores
 // non-temporal.  Measured both ways.

@@ -14,20 +14,10 @@
 // thread t < NX owns row t of Fxx and P, threads NX..NX+NU-1 a row of K.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // FwdArgs, FillArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-struct FwdArgs {
-  const double* kkt;
-  const double* ric;
-  double* dir;
-  const double* dx0;  // [batch][nx] or nullptr (then dir[...][0].dx is used as given)
-  const rtoc_grid* grid;
-  int nstages;
-  int batch;  // instances [first, batch) are processed by this launch
-  int first;
-};
 
 #ifndef FWD_PREFETCH
 #define FWD_PREFETCH 12  // Fxx loads of grid point st + 1 requested ahead of the tail of st (all of them for ANYmal)
@@ -566,13 +556,6 @@ __global__ __launch_bounds__(64 * NWF) void riccati_forward_mw_kernel(FwdArgs a)
 // Unconstrained (fixed-base, no contact) OCPs reuse the general kernels: the structured
 // A = [[I, dt I],[0, I]], Bv = dt I of unconstr_backward_riccati_recursion_factorizer.cpp:27-50
 // are materialised once into the Fxx / Fvu slots of every record.
-struct FillArgs {
-  double* kkt;
-  int nstages, batch;
-  double dt;
-  rtoc_record_layout kl;
-};
-
 template <int NV>
 __global__ void unconstr_fill_kernel(FillArgs a) {
   constexpr int NX = 2 * NV;

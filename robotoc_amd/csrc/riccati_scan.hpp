@@ -11,23 +11,11 @@
 // handful of instances this path is meant for.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // ScanArgs, StoScanArgs, FwdScanArgs
 #include "riccati_scan_core.hpp"
 #include "riccati_scan_sto.hpp"
 
 namespace rtoc {
-
-struct ScanArgs {
-  const double* kkt;      // [batch][nstages][kkt stride]
-  const rtoc_grid* grid;  // [nstages] (device)
-  uint32_t* status;       // [batch]
-  const double* src;      // elements before this level [batch][nstages][EltLayout::STRIDE]
-  double* dst;            // elements after this level
-  double* ps;             // value records [batch][nstages][EltLayout::PS_STRIDE]
-  int nstages;
-  int batch;  // instances [first, batch) are processed by this launch
-  int first;
-  int dist;   // distance d of this combination level
-};
 
 constexpr int SCAN_ELT_NT = 256;  // element kernel
 // combination kernel, two workgroups per combination (grid z): the waves share the MFMA tiles; up to 8 lanes per
@@ -80,17 +68,6 @@ __global__ __launch_bounds__(scan_comb_nt(NV), scan_comb_min_waves(NV)) void sca
 }
 
 // ---- grids with switching-time optimisation: stage-parallel preparation + serial vector pass (riccati_scan_sto.hpp) ----
-struct StoScanArgs {
-  const double* kkt;
-  double* ric;
-  const rtoc_grid* grid;
-  uint32_t* status;
-  const double* ps;   // the scan's value records [batch][nstages][PS_STRIDE]
-  double* scr;        // [batch][nstages][StoScratch::STRIDE]
-  int nstages, batch, first;
-  double max_dts0;
-  long long* prof;    // phase stamps of instance 0 (RTOC_ENABLE_PROF builds), else nullptr
-};
 constexpr int SCAN_STO_PREP_NT = 128;
 
 template <int NV, int NU, int NS>
@@ -109,7 +86,6 @@ __global__ __launch_bounds__(SCAN_STO_PREP_NT) void scan_sto_prep_kernel(StoScan
 
 // five wavefronts per instance: a row of the step's products is shared by up to four neighbouring lanes of the first four, the fifth
 // stores the previous grid point's results meanwhile (the bundle of a grid point is prefetched into registers: 14 doubles per lane for ANYmal)
-constexpr int SCAN_STO_MAX_STAGES = 512;   // = scan::StoVecCfg::MAX_STAGES (grids beyond take the serial kernel)
 constexpr int scan_sto_vec_nt(int) { return 320; }
 template <int NV, int NU, int NS, int SCAN_STO_VEC_NT = scan_sto_vec_nt(NV)>
 __global__ __launch_bounds__(SCAN_STO_VEC_NT) void scan_sto_vector_kernel(StoScanArgs a) {
@@ -125,19 +101,6 @@ __global__ __launch_bounds__(SCAN_STO_VEC_NT) void scan_sto_vector_kernel(StoSca
 }
 
 // ---- forward recursion as a prefix scan of the closed-loop maps (riccati_scan_core.hpp) ------------------
-struct FwdScanArgs {
-  const double* kkt;
-  const double* ric;
-  double* dir;
-  const double* dx0;  // [batch][nx] or nullptr (then dir[...][0].dx is used as given)
-  const rtoc_grid* grid;
-  const double* src;  // maps before this level [batch][nstages][EltLayout::STRIDE]
-  double* dst;
-  int nstages;
-  int batch;
-  int first;
-  int dist;
-};
 constexpr int SCAN_FWD_NT = 256;
 
 template <int NV, int NU, int NS>

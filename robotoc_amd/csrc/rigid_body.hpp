@@ -19,9 +19,14 @@
 // lane-strided (conflict-free).  Only the current root-to-body path is live: LDS = levels x (21 x 64 + ~60) doubles.
 // The contact rows ride on the visit of the body that carries the frame; d(position)/dq = R_of * (frame Jacobian), whose
 // column j is the v-tangent of the frame velocity -- held by the neighbouring lane (point_contact.hxx:78-80).
+//
+// The kernels and their argument blocks: rt_eval_kkt.hip launches them and is the one unit that includes this header.  The
+// model they read and the plan of the walk are rigid_body_model.hpp (host), the spatial arithmetic is rigid_body_math.hpp.
 #pragma once
 #include "device_utils.hpp"
 #include "record_view.hpp"
+#include "rigid_body_math.hpp"
+#include "rigid_body_model.hpp"
 #include "../../include/rtoc_robot.h"
 
 #ifndef RTOC_RBD_WAVES
@@ -30,190 +35,6 @@
 
 namespace rtoc {
 namespace rbd {
-
-// per-joint / per-contact constants as the kernel reads them, packed by rtoc_set_robot_model: one coalesced copy into
-// LDS per grid point instead of ~30 dependent L2 round trips per visited body
-constexpr int JP = 32;  // doubles per joint: R 9, p 3, axis 3, mass 1, com 3, I 9 (28), type, idx_q, idx_v, depth
-constexpr int CP = 16;  // doubles per contact: R 9, p 3, kp, kd, parent, type
-struct DevModel {
-  rtoc_robot_model m;
-  int depth[RTOC_MAX_JOINTS];
-  int nlevels;
-  // storage plan of the tangent walk, per body: bit 0 = its parent is the body visited just before it (the parent's forward
-  // tangents are still in registers), bit 1 = leaf (its force tangent is closed from registers), bits 4-7 = 1 + the LDS slot
-  // its own forward tangents are kept in (bodies with two or more children; 0 = none), bits 8-11 = 1 + its parent's slot.
-  // Slots are numbered by the count of branching ancestors: two bodies with the same count are never open at once.
-  int walk[RTOC_MAX_JOINTS];
-  int nbranch;
-  // passes of the tangent walk: pass p carries the dofs [p dpp, (p + 1) dpp), three lanes each; pass_bodies[p] = the bodies
-  // a direction of the pass can move or load (bit i: some dof of the pass sits on the path root -> i or in the subtree of i);
-  // the other bodies are skipped by the whole wave (their columns are zero)
-  int dpp, npass;
-  unsigned long long pass_bodies[RTOC_MAX_JOINTS + 8];
-  int pass_nvisit[RTOC_MAX_JOINTS + 8];                          // the same as lists, in depth-first order
-  int pass_visit[RTOC_MAX_JOINTS + 8][RTOC_MAX_JOINTS];       // (ints: read through the scalar cache)
-  double joint[RTOC_MAX_JOINTS][JP];
-  double contact[RTOC_MAX_CONTACTS][CP];
-  // per dof: the body it moves and its angular axis in that body's frame (zero for the linear dofs of a free-flyer);
-  // per contact: the dofs on the path from the root to the contact's body (bit j): everything the world-aligned angular
-  // Jacobian column of a contact frame needs besides the bodies' world rotations (contact_cone_vals_kernel)
-  int dof_body[RTOC_MAX_JOINTS + 8];
-  double dof_axis[RTOC_MAX_JOINTS + 8][3];
-  unsigned long long contact_dofs[RTOC_MAX_CONTACTS];
-};
-// nbranch of a model (the number of LDS slots the walk needs for forward tangents): 1 + the largest count of branching
-// ancestors of a branching body, 0 for a chain
-inline int walk_plan(const rtoc_robot_model& m, int* walk) {
-  int nchild[RTOC_MAX_JOINTS] = {}, slot[RTOC_MAX_JOINTS], nbranch = 0;
-  for (int i = 1; i < m.njoints; ++i)
-    if (m.parent[i] >= 0 && m.parent[i] < i) nchild[m.parent[i]]++;
-  for (int i = 0; i < m.njoints; ++i) {
-    const int par = (i > 0 && m.parent[i] >= 0 && m.parent[i] < i) ? m.parent[i] : -1;
-    // slot[i]: the slot a branching body i would use = the number of branching bodies above it
-    slot[i] = par < 0 ? 0 : slot[par] + (nchild[par] >= 2 ? 1 : 0);
-    const int own = nchild[i] >= 2 ? slot[i] + 1 : 0;
-    const int pslot = (par >= 0 && nchild[par] >= 2) ? slot[par] + 1 : 0;
-    if (own > nbranch) nbranch = own;
-    if (walk) walk[i] = ((par >= 0 && par == i - 1) ? 1 : 0) | (nchild[i] == 0 ? 2 : 0) | (own << 4) | (pslot << 8);
-  }
-  return nbranch;
-}
-inline void plan_passes(DevModel* h, int forced_dpp = 0);
-inline void pack_model(DevModel* h) {
-  const rtoc_robot_model& m = h->m;
-  for (int i = 0; i < RTOC_MAX_JOINTS; ++i) h->walk[i] = 0;
-  h->nbranch = walk_plan(m, h->walk);
-  plan_passes(h);
-  for (int i = 0; i < m.njoints; ++i) {
-    double* o = h->joint[i];
-    for (int k = 0; k < 9; ++k) o[k] = m.placement_R[i][k], o[19 + k] = m.inertia[i][k];
-    for (int k = 0; k < 3; ++k) o[9 + k] = m.placement_p[i][k], o[12 + k] = m.axis[i][k], o[16 + k] = m.com[i][k];
-    o[15] = m.mass[i];
-    o[28] = m.type[i], o[29] = m.idx_q[i], o[30] = m.idx_v[i], o[31] = h->depth[i];
-  }
-  for (int j = 0; j < RTOC_MAX_JOINTS + 8; ++j) h->dof_body[j] = 0, h->dof_axis[j][0] = h->dof_axis[j][1] = h->dof_axis[j][2] = 0.0;
-  for (int i = 0; i < m.njoints; ++i) {
-    const int ndof = m.type[i] == RTOC_JOINT_FREE_FLYER ? 6 : 1;
-    for (int k = 0; k < ndof; ++k) {
-      const int j = m.idx_v[i] + k;
-      if (j < 0 || j >= RTOC_MAX_JOINTS + 8) continue;
-      h->dof_body[j] = i;
-      if (ndof == 6) {
-        if (k >= 3) h->dof_axis[j][k - 3] = 1.0;
-      } else {
-        for (int t = 0; t < 3; ++t) h->dof_axis[j][t] = m.axis[i][t];
-      }
-    }
-  }
-  for (int c = 0; c < m.ncontacts; ++c) {
-    unsigned long long mask = 0;
-    for (int i = m.contact_parent[c]; i >= 0 && i < m.njoints; i = m.parent[i]) {
-      const int ndof = m.type[i] == RTOC_JOINT_FREE_FLYER ? 6 : 1;
-      for (int k = 0; k < ndof; ++k)
-        if (m.idx_v[i] + k >= 0 && m.idx_v[i] + k < 64) mask |= 1ull << (m.idx_v[i] + k);
-      if (m.parent[i] == i) break;
-    }
-    h->contact_dofs[c] = mask;
-  }
-  for (int c = 0; c < m.ncontacts; ++c) {
-    double* o = h->contact[c];
-    for (int k = 0; k < 9; ++k) o[k] = m.contact_R[c][k];
-    for (int k = 0; k < 3; ++k) o[9 + k] = m.contact_p[c][k];
-    o[12] = m.contact_kp[c], o[13] = m.contact_kd[c], o[14] = m.contact_parent[c], o[15] = m.contact_type[c];
-  }
-}
-
-struct V3 {
-  double x, y, z;
-};
-struct SV {  // spatial motion or force: linear, angular
-  V3 l, a;
-};
-__device__ __forceinline__ V3 mk(double x, double y, double z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return mk(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ SV operator+(SV a, SV b) { return SV{a.l + b.l, a.a + b.a}; }
-__device__ __forceinline__ SV operator-(SV a, SV b) { return SV{a.l - b.l, a.a - b.a}; }
-__device__ __forceinline__ SV sv0() { return SV{mk(0, 0, 0), mk(0, 0, 0)}; }
-
-struct M3 {  // row-major
-  double m[9];
-};
-__device__ __forceinline__ V3 mul(const M3& R, V3 v) {
-  return mk(R.m[0] * v.x + R.m[1] * v.y + R.m[2] * v.z, R.m[3] * v.x + R.m[4] * v.y + R.m[5] * v.z,
-            R.m[6] * v.x + R.m[7] * v.y + R.m[8] * v.z);
-}
-__device__ __forceinline__ V3 mulT(const M3& R, V3 v) {
-  return mk(R.m[0] * v.x + R.m[3] * v.y + R.m[6] * v.z, R.m[1] * v.x + R.m[4] * v.y + R.m[7] * v.z,
-            R.m[2] * v.x + R.m[5] * v.y + R.m[8] * v.z);
-}
-__device__ __forceinline__ M3 mul(const M3& A, const M3& B) {
-  M3 C;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C.m[3 * i + j] = A.m[3 * i] * B.m[j] + A.m[3 * i + 1] * B.m[3 + j] + A.m[3 * i + 2] * B.m[6 + j];
-  return C;
-}
-// child-frame coordinates of a parent-frame motion, X = (R, p)
-__device__ __forceinline__ SV act_inv(const M3& R, V3 p, SV m) { return SV{mulT(R, m.l - cross(p, m.a)), mulT(R, m.a)}; }
-// parent-frame coordinates of a child-frame force
-__device__ __forceinline__ SV act_f(const M3& R, V3 p, SV f) {
-  const V3 l = mul(R, f.l);
-  return SV{l, mul(R, f.a) + cross(p, l)};
-}
-__device__ __forceinline__ SV mcross(SV v, SV m) { return SV{cross(v.a, m.l) + cross(v.l, m.a), cross(v.a, m.a)}; }   // v x m
-__device__ __forceinline__ SV fcross(SV v, SV f) { return SV{cross(v.a, f.l), cross(v.a, f.a) + cross(v.l, f.l)}; }   // v x* f
-__device__ __forceinline__ SV inertia_mul(double mass, V3 c, const M3& I, SV v) {
-  const V3 l = mass * (v.l - cross(c, v.a));
-  return SV{l, mul(I, v.a) + cross(c, l)};
-}
-__device__ __forceinline__ M3 ldm3(const double* p) {
-  M3 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.m[i] = p[i];
-  return r;
-}
-__device__ __forceinline__ V3 ldv3(const double* p) { return mk(p[0], p[1], p[2]); }
-
-// pinocchio::log6 of X = (R, p) and its derivative along the right perturbation X exp(twist) (what Jlog6 * twist is):
-//   w = log3 R,  lin = p - w x p / 2 + beta w x (w x p),  beta(t) = 1/t^2 - cot(t/2) / (2 t)  (= the Jlog3 coefficient too)
-//   dw = twist.a + w x twist.a / 2 + beta w x (w x twist.a),  dp = R twist.l,  dt = w.dw / t
-__device__ __forceinline__ void log6_fwd(const M3& R, V3 p, SV twist, SV& val, SV& der) {
-  const double tr = R.m[0] + R.m[4] + R.m[8];
-  double c = 0.5 * (tr - 1.0);
-  c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-  const double th = acos(c);
-  const double k = th < 1e-6 ? 0.5 + th * th / 12.0 : th / (2.0 * sin(th));
-  const V3 w = mk(k * (R.m[7] - R.m[5]), k * (R.m[2] - R.m[6]), k * (R.m[3] - R.m[1]));
-  const double t = sqrt(dot(w, w));
-  double beta, dbeta;
-  if (t < 1e-3) {
-    beta = 1.0 / 12.0 + t * t / 720.0;
-    dbeta = t / 360.0 + t * t * t / 7560.0;
-  } else {
-    const double h = 0.5 * t, ct = cos(h) / sin(h), cs2 = 1.0 / (sin(h) * sin(h));
-    beta = 1.0 / (t * t) - ct / (2.0 * t);
-    dbeta = -2.0 / (t * t * t) + ct / (2.0 * t * t) + cs2 / (4.0 * t);
-  }
-  const V3 wxp = cross(w, p), wxwxp = cross(w, wxp);
-  val = SV{p - 0.5 * wxp + beta * wxwxp, w};
-  const V3 ta = twist.a;
-  const V3 dw = ta + 0.5 * cross(w, ta) + beta * cross(w, cross(w, ta));
-  const V3 dp = mul(R, twist.l);
-  const double dt = t > 1e-12 ? dot(w, dw) / t : 0.0;
-  const V3 dlin = dp - 0.5 * (cross(dw, p) + cross(w, dp)) + (dbeta * dt) * wxwxp +
-                  beta * (cross(dw, wxp) + cross(w, cross(dw, p)) + cross(w, cross(w, dp)));
-  der = SV{dlin, dw};
-}
-
-// an int of the device model through the scalar cache: the model is read-only while a kernel runs, but the compiler cannot know
-// (the kernel stores through other pointers) and would issue a vector load + v_readfirstlane on the walk's critical path
-typedef const int __attribute__((address_space(4))) lin_const_int;
-__device__ __forceinline__ int sload_int(const int* p) { return *(lin_const_int*)(unsigned long long)p; }
 
 struct LinArgs {
   RecView rv;           // kkt == nullptr: the multiplier terms of linearizeContactDynamics / linearizeImpactDynamics are left out
@@ -225,87 +46,6 @@ struct LinArgs {
   const double* vals;   // PRE: [batch * nstages][njoints][64] of the dynamics traversal (rbd_values_kernel)
   const double* vals2;  //      the same for the kinematics traversal of impact grids
 };
-
-// per-level storage in LDS
-constexpr int VAL_DOUBLES = 64;  // R 9, p 3, oR 9, op 3, v 6, a 6, g 3, f 6, vpar 6, apar 6 -> 57, padded
-constexpr int TAN_SLOTS = 21;    // dv 6, da 6, dg 3, df 6
-constexpr int FWD_SLOTS = 15;    // dv, da, dg: read by the children only, so the deepest level keeps none
-constexpr int DF_SLOTS = 6;
-__host__ __device__ constexpr int lin_pad8(int n) { return (n + 7) & ~7; }
-// lanes per tangent slot: three per dof of a pass plus a column the idle lanes share, even (quadrupeds: 54 -> 56; 21 dofs: 64)
-__host__ __device__ constexpr int lin_lane_stride(int dpp) { return (3 * dpp + 2) & ~1; }
-constexpr int LIN_MAX_DPP = 21;
-// What decides the speed of this kernel is how many grid points a CU holds at once (the walk is one long dependent
-// instruction stream per wave, issue-bound): only what the walk cannot carry in registers lives in LDS -- the forward tangents
-// (dv, da, dg) of the bodies with two or more children (nbranch slots: a body whose parent was visited just before it takes
-// them from registers) and the force tangents df of the open non-leaf levels (a leaf is closed from registers).  ANYmal:
-// 1 slot + 3 levels = 22 KB (was 4 + 4 levels = 38 KB), iCub: 2 slots + 10 levels (was 11 + 11 = 128 KB); DESIGN.md 3.4.
-// pre: the walk reads the values of the recursion from rbd_values_kernel (PRE): no q, v, a, f, u staging, and of the joint
-// constants only axis .. depth (JP_PRE doubles from JP_PRE_OFF on) -- 20,000 B for ANYmal: EIGHT waves per CU (8 x 20,480 B).
-constexpr int JP_PRE_OFF = 12, JP_PRE = JP - JP_PRE_OFF;
-__host__ __device__ constexpr size_t lin_lds_bytes(int nlevels, int nbranch, int njoints, int ncontacts, int nv, int dpp, bool pre) {
-  return sizeof(double) * ((size_t)nlevels * VAL_DOUBLES + (size_t)(nbranch * FWD_SLOTS + (nlevels > 1 ? nlevels - 1 : 0) * DF_SLOTS) * lin_lane_stride(dpp) +
-                           (pre ? 0 : lin_pad8(nv + 1) + 3 * lin_pad8(nv) + lin_pad8(6 * ncontacts)) + lin_pad8(nv) + 2 * lin_pad8(6 * ncontacts) +
-                           njoints * (pre ? JP_PRE : JP) + ncontacts * CP);
-}
-
-// bodies a pass with the dofs [j0, j1) has to visit
-inline unsigned long long pass_body_mask(const rtoc_robot_model& m, int j0, int j1) {
-  unsigned long long mask = 0;
-  for (int b = 0; b < m.njoints; ++b) {
-    const int ndof = m.type[b] == RTOC_JOINT_FREE_FLYER ? 6 : 1;
-    if (m.idx_v[b] + ndof <= j0 || m.idx_v[b] >= j1) continue;   // no dof of body b in the pass
-    for (int i = 0; i < m.njoints; ++i) {
-      bool up = false, down = false;   // b above-or-at i; b below i
-      for (int k = i; k >= 0; k = m.parent[k]) {
-        if (k == b) up = true;
-        if (m.parent[k] < 0 || m.parent[k] >= k) break;
-      }
-      for (int k = b; k >= 0; k = m.parent[k]) {
-        if (k == i) down = true;
-        if (m.parent[k] < 0 || m.parent[k] >= k) break;
-      }
-      if (up || down) mask |= 1ull << i;
-    }
-  }
-  return mask;
-}
-// dofs per pass: what minimises (bodies visited over all passes) / (waves a CU holds).  The walk is one dependent instruction
-// stream per wave, so a CU's rate is its resident waves -- set by the LDS of the per-lane tangents, i.e. by the lanes of a pass --
-// over the visits per grid point: ANYmal one pass of 18 dofs (8 waves per CU), iCub 3 passes of 12 instead of 2 of 21.
-// max_waves: what the registers of the kernel allow per CU (8; 4 with surface contacts: 256 VGPRs + AGPRs).
-inline int choose_dofs_per_pass(const rtoc_robot_model& m, int nlevels, int nbranch, int max_waves) {
-  const int dmax = m.nv < LIN_MAX_DPP ? m.nv : LIN_MAX_DPP, dmin = dmax < 6 ? dmax : 6;
-  int best = dmax;
-  double best_cost = 1e300;
-  for (int d = dmax; d >= dmin && d >= 1; --d) {   // ties: the larger pass
-    const size_t bytes = (lin_lds_bytes(nlevels, nbranch, m.njoints, m.ncontacts, m.nv, d, true) + 1279) / 1280 * 1280;
-    int waves = (int)(160 * 1024 / bytes);
-    waves = waves > max_waves ? max_waves : waves;
-    if (waves < 1) continue;
-    int visits = m.njoints;   // the first pass visits every body
-    for (int j0 = d; j0 < m.nv; j0 += d) visits += __builtin_popcountll(pass_body_mask(m, j0, j0 + d < m.nv ? j0 + d : m.nv));
-    const double cost = (double)visits / waves;
-    if (cost < best_cost - 1e-9) best_cost = cost, best = d;
-  }
-  return best;
-}
-inline void plan_passes(DevModel* h, int forced_dpp) {
-  const rtoc_robot_model& m = h->m;
-  bool surf = false;
-  for (int c = 0; c < m.ncontacts; ++c) surf = surf || m.contact_type[c] == RTOC_CONTACT_SURFACE;
-  h->dpp = forced_dpp > 0 ? (forced_dpp < m.nv ? forced_dpp : (m.nv < LIN_MAX_DPP ? m.nv : LIN_MAX_DPP)) : choose_dofs_per_pass(m, h->nlevels, h->nbranch, surf ? 4 : 8);
-  for (int p = 0; p < RTOC_MAX_JOINTS + 8; ++p) {
-    h->pass_bodies[p] = 0, h->pass_nvisit[p] = 0;
-    for (int i = 0; i < RTOC_MAX_JOINTS; ++i) h->pass_visit[p][i] = 0;
-  }
-  h->npass = (m.nv + h->dpp - 1) / h->dpp;
-  for (int p = 0; p < h->npass; ++p) h->pass_bodies[p] = pass_body_mask(m, p * h->dpp, (p + 1) * h->dpp < m.nv ? (p + 1) * h->dpp : m.nv);
-  h->pass_bodies[0] |= m.njoints >= 64 ? ~0ull : (1ull << m.njoints) - 1;   // the first pass writes the values of the contact rows: every body
-  for (int p = 0; p < h->npass; ++p)
-    for (int i = 0; i < m.njoints; ++i)
-      if ((h->pass_bodies[p] >> i) & 1ull) h->pass_visit[p][h->pass_nvisit[p]++] = i;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Values of the recursion, ahead of the tangent walk (PRE mode of linearize_contact_dynamics_kernel).

@@ -1,0 +1,102 @@
+// rigid_body_math.hpp -- spatial-vector arithmetic of the rigid-body kernels: 3-vectors, spatial motions / forces, rotations,
+// log6 with its forward-mode derivative, and the scalar-cache load of the device model.  Device functions only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace rtoc {
+namespace rbd {
+
+struct V3 {
+  double x, y, z;
+};
+struct SV {  // spatial motion or force: linear, angular
+  V3 l, a;
+};
+__device__ __forceinline__ V3 mk(double x, double y, double z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator*(double s, V3 a) { return mk(s * a.x, s * a.y, s * a.z); }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ SV operator+(SV a, SV b) { return SV{a.l + b.l, a.a + b.a}; }
+__device__ __forceinline__ SV operator-(SV a, SV b) { return SV{a.l - b.l, a.a - b.a}; }
+__device__ __forceinline__ SV sv0() { return SV{mk(0, 0, 0), mk(0, 0, 0)}; }
+
+struct M3 {  // row-major
+  double m[9];
+};
+__device__ __forceinline__ V3 mul(const M3& R, V3 v) {
+  return mk(R.m[0] * v.x + R.m[1] * v.y + R.m[2] * v.z, R.m[3] * v.x + R.m[4] * v.y + R.m[5] * v.z,
+            R.m[6] * v.x + R.m[7] * v.y + R.m[8] * v.z);
+}
+__device__ __forceinline__ V3 mulT(const M3& R, V3 v) {
+  return mk(R.m[0] * v.x + R.m[3] * v.y + R.m[6] * v.z, R.m[1] * v.x + R.m[4] * v.y + R.m[7] * v.z,
+            R.m[2] * v.x + R.m[5] * v.y + R.m[8] * v.z);
+}
+__device__ __forceinline__ M3 mul(const M3& A, const M3& B) {
+  M3 C;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) C.m[3 * i + j] = A.m[3 * i] * B.m[j] + A.m[3 * i + 1] * B.m[3 + j] + A.m[3 * i + 2] * B.m[6 + j];
+  return C;
+}
+// child-frame coordinates of a parent-frame motion, X = (R, p)
+__device__ __forceinline__ SV act_inv(const M3& R, V3 p, SV m) { return SV{mulT(R, m.l - cross(p, m.a)), mulT(R, m.a)}; }
+// parent-frame coordinates of a child-frame force
+__device__ __forceinline__ SV act_f(const M3& R, V3 p, SV f) {
+  const V3 l = mul(R, f.l);
+  return SV{l, mul(R, f.a) + cross(p, l)};
+}
+__device__ __forceinline__ SV mcross(SV v, SV m) { return SV{cross(v.a, m.l) + cross(v.l, m.a), cross(v.a, m.a)}; }   // v x m
+__device__ __forceinline__ SV fcross(SV v, SV f) { return SV{cross(v.a, f.l), cross(v.a, f.a) + cross(v.l, f.l)}; }   // v x* f
+__device__ __forceinline__ SV inertia_mul(double mass, V3 c, const M3& I, SV v) {
+  const V3 l = mass * (v.l - cross(c, v.a));
+  return SV{l, mul(I, v.a) + cross(c, l)};
+}
+__device__ __forceinline__ M3 ldm3(const double* p) {
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.m[i] = p[i];
+  return r;
+}
+__device__ __forceinline__ V3 ldv3(const double* p) { return mk(p[0], p[1], p[2]); }
+
+// pinocchio::log6 of X = (R, p) and its derivative along the right perturbation X exp(twist) (what Jlog6 * twist is):
+//   w = log3 R,  lin = p - w x p / 2 + beta w x (w x p),  beta(t) = 1/t^2 - cot(t/2) / (2 t)  (= the Jlog3 coefficient too)
+//   dw = twist.a + w x twist.a / 2 + beta w x (w x twist.a),  dp = R twist.l,  dt = w.dw / t
+__device__ __forceinline__ void log6_fwd(const M3& R, V3 p, SV twist, SV& val, SV& der) {
+  const double tr = R.m[0] + R.m[4] + R.m[8];
+  double c = 0.5 * (tr - 1.0);
+  c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+  const double th = acos(c);
+  const double k = th < 1e-6 ? 0.5 + th * th / 12.0 : th / (2.0 * sin(th));
+  const V3 w = mk(k * (R.m[7] - R.m[5]), k * (R.m[2] - R.m[6]), k * (R.m[3] - R.m[1]));
+  const double t = sqrt(dot(w, w));
+  double beta, dbeta;
+  if (t < 1e-3) {
+    beta = 1.0 / 12.0 + t * t / 720.0;
+    dbeta = t / 360.0 + t * t * t / 7560.0;
+  } else {
+    const double h = 0.5 * t, ct = cos(h) / sin(h), cs2 = 1.0 / (sin(h) * sin(h));
+    beta = 1.0 / (t * t) - ct / (2.0 * t);
+    dbeta = -2.0 / (t * t * t) + ct / (2.0 * t * t) + cs2 / (4.0 * t);
+  }
+  const V3 wxp = cross(w, p), wxwxp = cross(w, wxp);
+  val = SV{p - 0.5 * wxp + beta * wxwxp, w};
+  const V3 ta = twist.a;
+  const V3 dw = ta + 0.5 * cross(w, ta) + beta * cross(w, cross(w, ta));
+  const V3 dp = mul(R, twist.l);
+  const double dt = t > 1e-12 ? dot(w, dw) / t : 0.0;
+  const V3 dlin = dp - 0.5 * (cross(dw, p) + cross(w, dp)) + (dbeta * dt) * wxwxp +
+                  beta * (cross(dw, wxp) + cross(w, cross(dw, p)) + cross(w, cross(w, dp)));
+  der = SV{dlin, dw};
+}
+
+// an int of the device model through the scalar cache: the model is read-only while a kernel runs, but the compiler cannot know
+// (the kernel stores through other pointers) and would issue a vector load + v_readfirstlane on the walk's critical path
+typedef const int __attribute__((address_space(4))) lin_const_int;
+__device__ __forceinline__ int sload_int(const int* p) { return *(lin_const_int*)(unsigned long long)p; }
+
+}  // namespace rbd
+}  // namespace rtoc

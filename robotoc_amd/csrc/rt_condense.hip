@@ -1,5 +1,7 @@
 // rt_condense.hip -- condensation, expansion and update of the contact path: constraint rows, cones, state-equation correction.
 #include "rt_context.hpp"
+#include "pdipm_update.hpp"
+#include "state_equation.hpp"
 
 using namespace rtoc;
 

@@ -2,8 +2,10 @@
 // rtoc_capi.hip and the rt_*.hip units alone.  The state of a context is grouped by subsystem; every group that rtoc_clone
 // copies says so itself, in a clone_from directly under its members.  Functions one unit calls in another are declared at
 // the end, in namespace rtoc; everything else in a unit is static.
-// Only the headers the context itself needs are included here.  A header whose kernels one unit alone launches is included by
-// that unit: the device compiler emits every static __global__ function a unit sees, launched from it or not.
+// No header included here defines a kernel: the context needs the descriptor table of a shape with its argument blocks
+// (kernel_table.hpp) and the host half of the rigid-body model (rigid_body_model.hpp).  A kernel header is included by the one
+// unit that launches from it: the device compiler emits every static kernel a unit sees, launched from it or not
+// (tests/test_kernel_units.py reads the objects for it).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,9 +20,9 @@
 #include "../../include/rtoc.h"
 #include "../../include/rtoc_robot.h"
 #include "device_buffer.hpp"
-#include "kernel_set.hpp"
+#include "kernel_table.hpp"
 #include "record_view.hpp"
-#include "rigid_body.hpp"
+#include "rigid_body_model.hpp"
 
 #define HIP_TRY(expr)                                 \
   do {                                                \

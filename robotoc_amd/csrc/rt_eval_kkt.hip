@@ -3,6 +3,9 @@
 #include <mutex>
 
 #include "rt_context.hpp"
+#include "rigid_body.hpp"
+#include "kkt_error.hpp"
+#include "integrate_solution.hpp"
 #include "unconstr_constraints.hpp"
 #include "state_equation_lin.hpp"
 #include "switching_constraint_lin.hpp"

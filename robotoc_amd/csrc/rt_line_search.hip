@@ -1,5 +1,6 @@
 // rt_line_search.hip -- evalOCP's performance index, the filter and the backtracking line search on the device.
 #include "rt_context.hpp"
+#include "line_search.hpp"
 
 using namespace rtoc;
 

@@ -1,6 +1,7 @@
 // rt_sweep.hip -- the Riccati recursion: the backward plan, the backward / forward / sweep launchers, the horizon scan,
 // the unconstrained recursion and dynamics.
 #include "rt_context.hpp"
+#include "fxx_structure.hpp"
 
 using namespace rtoc;
 

@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include "rt_context.hpp"
+#include "device_utils.hpp"  // d2 (stream_probe_kernel)
 
 using namespace rtoc;
 

@@ -10,21 +10,10 @@
 // pure HBM latency, one 64-lane wave per grid point.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // SeArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-struct SeArgs {
-  double* kkt;
-  double* dir;
-  double* dx0;
-  const double* se3;  // [batch][nstages][RTOC_SE3_STRIDE]
-  const rtoc_grid* grid;
-  int nstages, batch;
-  rtoc_record_layout kl, dl;
-  int nx;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
-};
 
 // mode 0: correctLinearize(Impact)StateEquation on every non-terminal grid point
 // mode 1: correctCostateDirection on every grid point

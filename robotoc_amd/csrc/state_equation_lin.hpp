@@ -14,7 +14,10 @@
 // like the reference's SE3JacobianInverse).  Everything else is elementwise.
 // One wave per (instance, grid point).  Records: the un-condensed contact-path convention (la in CDD.la).
 #pragma once
-#include "rigid_body.hpp"
+#include "device_utils.hpp"
+#include "record_view.hpp"
+#include "rigid_body_math.hpp"
+#include "rigid_body_model.hpp"
 
 namespace rtoc {
 

@@ -27,7 +27,10 @@
 // arithmetic, references read from a per-grid-point table (RTOC_REF_TABLE), and the unconstrained path's scaling (dt from the
 // call, no impact kind, hx / h untouched).  The host picks it; EXT = false is the kernel as it was.
 #pragma once
-#include "rigid_body.hpp"
+#include "device_utils.hpp"
+#include "record_view.hpp"
+#include "rigid_body_math.hpp"
+#include "rigid_body_model.hpp"
 
 namespace rtoc {
 

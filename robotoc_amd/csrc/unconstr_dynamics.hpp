@@ -15,18 +15,10 @@
 // O(nv^3) flops on 7x7 blocks: one wave per grid point, VALU only.
 #pragma once
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // UdArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-struct UdArgs {
-  double* kkt;
-  double* cdd;
-  double* dir;
-  int nstages, batch;
-  double dt;
-  rtoc_record_layout kl, cl, dl;
-};
 
 template <int NV>
 __global__ __launch_bounds__(64) void unconstr_condense_kernel(UdArgs a) {

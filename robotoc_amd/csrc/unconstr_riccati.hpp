@@ -13,21 +13,10 @@
 #include <cstdint>
 
 #include "device_utils.hpp"
+#include "kernel_args.hpp"  // UrArgs
 #include "../../include/rtoc.h"
 
 namespace rtoc {
-
-struct UrArgs {
-  const double* kkt;
-  double* kkt_rw;      // writeback of the mutated Qxx, Qxu, Qaa, la (RTOC_OPT_WRITEBACK_KKT), else unused
-  double* ric;
-  double* dir;
-  const double* dx0;   // [batch][nx] or nullptr
-  uint32_t* status;
-  int nstages, batch, writeback;
-  double dt;
-  rtoc_record_layout kl, rl, dl;
-};
 
 template <int NV>
 __global__ __launch_bounds__(64) void unconstr_riccati_backward_lds_kernel(UrArgs a) {
