@@ -273,6 +273,10 @@ int rtoc_solve_loop(const rtoc_solve_options* options, const rtoc_solve_callback
  * (ocp_solver.cpp:133-139) -- rtoc_contact_line_search: every instance backtracks from its maximum primal step until its filter
  * (rtoc_line_search_filter's, cleared by rtoc_line_search_clear) accepts the trial pair; *host_trials = trial evaluations run. */
 int rtoc_contact_eval_ocp(rtoc_ctx* ctx, int trial, double* host_cost, double* host_violation, int count);
+/* What rtoc_contact_eval_ocp sums, grid point by grid point: host_out[count <= batch][nstages] = the value of the stage / impact /
+ * terminal cost (every component of the cost function) as the last rtoc_contact_eval_kkt stored it -- or the last
+ * rtoc_unconstr_eval_kkt with the line search enabled, which is when that path stores them.  RTOC_ERR_NOT_READY before either. */
+int rtoc_get_stage_costs(rtoc_ctx* ctx, double* host_out, int count);
 int rtoc_set_line_search(rtoc_ctx* ctx, int enable, double step_size_reduction_rate, double min_step_size,
                          double filter_cost_reduction_rate, double filter_constraint_violation_reduction_rate);
 int rtoc_contact_line_search(rtoc_ctx* ctx, int* host_trials);
@@ -300,6 +304,24 @@ typedef struct rtoc_configuration_cost {
   double q_weight_impact[RTOC_MAX_JOINTS], v_weight_impact[RTOC_MAX_JOINTS], dv_weight_impact[RTOC_MAX_JOINTS];
 } rtoc_configuration_cost;
 int rtoc_set_configuration_cost(rtoc_ctx* ctx, const rtoc_configuration_cost* cost);
+/* A time-varying q_ref: ConfigurationSpaceCost::set_ref(std::shared_ptr<ConfigurationSpaceRefBase>)
+ * (src/cost/configuration_space_cost.cpp:84-89, include/robotoc/cost/configuration_space_cost.hpp:166-216).  The host asks the
+ * object once per grid point (updateRef / isActive) and hands the answers over: q_ref[nstages][nq] and active[nstages] shared by
+ * the batch (per_instance = 0), or q_ref[batch][nstages][nq] and active[batch][nstages] (per_instance = 1: every instance tracks
+ * its own posture); nq = nv, or nv + 1 with a free-flyer base, a row laid out like rtoc_configuration_cost::q_ref; rows are indexed
+ * by GRID POINT, not by time, like rtoc_set_task_ref_table's; nstages must be the current grid's.  active = NULL: active
+ * everywhere.  Per grid point (configuration_space_cost.cpp:251-442): the q terms -- lq, Qqq, the cost value and, on
+ * intermediate and lift grids, hx[0:nv] and the q share of h -- use that grid point's row (that instance's with per_instance = 1)
+ * and are absent altogether where the row is inactive (enable_q_cost_ && isCostConfigActive); the v, a / dv and u terms are
+ * unchanged: v_ref, u_ref and all weights stay those of rtoc_set_configuration_cost, as in the reference, where only q_ref
+ * varies.  Both rtoc_contact_eval_kkt and rtoc_unconstr_eval_kkt read the table, hence the line search's trial evaluations too.
+ * q_ref = NULL removes the table: the constant q_ref is in force again and both entry points launch exactly what they launched
+ * before.  RTOC_ERR_BAD_ARG: a wrong nstages, a non-finite entry of an ACTIVE row (inactive rows are not inspected, here or on
+ * the device: they may hold anything), per_instance outside {0, 1} -- a refused call leaves the table that was set in force.
+ * rtoc_set_grid forgets the rows but not that a table is in use: until it is set again or removed, both entry points return
+ * RTOC_ERR_NOT_READY before anything is launched, never the constant reference in its place (the rule of the task tables).
+ * rtoc_set_configuration_cost keeps the table, and its q_ref member is ignored while one is in force.  rtoc_clone copies it. */
+int rtoc_set_configuration_ref_table(rtoc_ctx* ctx, const double* q_ref, const int* active, int nstages, int per_instance);
 /* (q, v) of OCPSolver / UnconstrOCPSolver::updateSolution(t, q, v) for every instance: x0[batch][nq + nv], nq = nv, or
  * nv + 1 with a free-flyer base (dims.np == 6: [x y z qx qy qz qw, joints]). */
 int rtoc_set_initial_state(rtoc_ctx* ctx, const double* x0, int count);

@@ -37,6 +37,7 @@ EXPORTS = [
     "rtoc_sto_set_slack_dual", "rtoc_contact_eval_ocp", "rtoc_set_line_search", "rtoc_contact_line_search",
     "rtoc_bandwidth_probe", "rtoc_get_option",
     "rtoc_set_task_costs", "rtoc_set_grid_times", "rtoc_get_grid_times", "rtoc_set_contact_force_cost",
+    "rtoc_set_configuration_ref_table", "rtoc_get_stage_costs",
 ]
 
 
@@ -178,6 +179,8 @@ def lib():
         L.rtoc_set_task_ref_table.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
         L.rtoc_get_grid_times.argtypes = [vp, dp, C.c_int]
         L.rtoc_set_contact_force_cost.argtypes = [vp, vp, C.c_int]
+        L.rtoc_get_stage_costs.argtypes = [vp, dp, C.c_int]
+        L.rtoc_set_configuration_ref_table.argtypes = [vp, dp, C.POINTER(C.c_int), C.c_int, C.c_int]
         _LIB = L
     return _LIB
 
@@ -532,6 +535,32 @@ class Context:
             v = np.asarray(v, dtype=np.float64)
             arr[k, :v.size] = v
         _chk(lib().rtoc_set_configuration_cost(self._h, arr.ctypes.data_as(C.c_void_p)))
+
+    def set_configuration_ref_table(self, q_ref, active=None):
+        """rtoc_set_configuration_ref_table: a time-varying q_ref (ConfigurationSpaceRefBase) -- `q_ref` [nstages, nq] shared by
+        the batch or [batch, nstages, nq] (every instance its own: the shape decides), one row per GRID POINT, and `active` with the
+        same leading shape (isActive per grid point; None: active everywhere).  `costs.configuration_ref_table` fills both from
+        the user's object.  q_ref = None removes the table: the constant q_ref of set_configuration_cost is in force again."""
+        if q_ref is None:
+            _chk(lib().rtoc_set_configuration_ref_table(self._h, None, None, 0, 0))
+            return
+        q = np.ascontiguousarray(q_ref, dtype=np.float64)
+        nq = self.dims.nv + (1 if self.dims.np == 6 else 0)
+        if q.ndim not in (2, 3) or q.shape[-1] != nq or (q.ndim == 3 and q.shape[0] != self.batch):
+            raise ValueError("q_ref must be [nstages, %d] or [%d, nstages, %d], not %s" % (nq, self.batch, nq, q.shape))
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.int32)
+            if act.shape != q.shape[:-1]:
+                raise ValueError("active must have the shape %s, not %s" % (q.shape[:-1], act.shape))
+        _chk(lib().rtoc_set_configuration_ref_table(self._h, _dp(q), act.ctypes.data_as(C.POINTER(C.c_int)) if act is not None else None,
+                                                    q.shape[-2], 1 if q.ndim == 3 else 0))
+
+    def stage_costs(self):
+        """rtoc_get_stage_costs: [batch, nstages] cost value of every grid point as the last evalKKT stored it"""
+        out = np.zeros((self.batch, self.nstages))
+        _chk(lib().rtoc_get_stage_costs(self._h, _dp(out), self.batch))
+        return out
 
     def contact_eval_kkt(self):
         _chk(lib().rtoc_contact_eval_kkt(self._h))

@@ -18,6 +18,10 @@ LocalContactForceCost (src/cost/local_contact_force_cost.cpp) is described here 
 examples with switching-time optimisation, DiscreteTimeSwingFootRef / DiscreteTimeCoMRef (discrete_time_swing_foot_ref.cpp,
 discrete_time_com_ref.cpp): functions of a grid point's place in its contact phase, not of its time, served to the device through
 the table like a user's object.
+
+ConfigurationSpaceRefBase (include/robotoc/cost/configuration_space_ref_base.hpp), a time-varying q_ref of the
+ConfigurationSpaceCost, is the user's object as well: `configuration_ref_table` asks it once per grid point,
+capi.Context.set_configuration_ref_table uploads the rows.
 """
 import collections
 import ctypes as C
@@ -568,3 +572,43 @@ class LocalContactForceCost:
             for i, row in enumerate(getattr(self, name)):
                 getattr(s, name)[i][:] = row
         return s
+
+
+class ConfigurationSpaceRefBase:
+    """include/robotoc/cost/configuration_space_ref_base.hpp: a time-varying q_ref of the ConfigurationSpaceCost
+    (ConfigurationSpaceCost::set_ref).  A protocol: any object with these two methods serves.  The device reads a table with one
+    row per grid point (rtoc_set_configuration_ref_table), which `configuration_ref_table` fills from the object."""
+
+    def update_ref(self, model, grid_info):
+        """q_ref [nq] at the grid point (nq = nv, or nv + 1 with a free-flyer base: [x y z qx qy qz qw, joints])"""
+        raise NotImplementedError
+
+    def is_active(self, grid_info):
+        raise NotImplementedError
+
+
+def configuration_ref_table(ref, model, infos, q_weight=None, q_weight_terminal=None, q_weight_impact=None):
+    """(q_ref, active) for capi.Context.set_configuration_ref_table: `ref` (a ConfigurationSpaceRefBase) asked once per grid point
+    of `infos` (grid_infos) -> q_ref [nstages, nq], active [nstages]; a list of `batch` such objects -> [batch, nstages, nq] and
+    [batch, nstages], every instance its own.  The reference's order of questions (configuration_space_cost.cpp:251-442,
+    configuration_space_cost.hpp:166-216): is_active only where the q weight of the grid point's kind is not all zero
+    (enable_q_cost_ / _terminal_ / _impact_; weights not given, or a grid point that does not say its kind: asked), update_ref only
+    where the reference is active.  Rows that were not asked for stay zero and inactive."""
+    if isinstance(ref, (list, tuple)):
+        tabs = [configuration_ref_table(r, model, infos, q_weight, q_weight_terminal, q_weight_impact) for r in ref]
+        return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+    nq = int(model.nq)
+    q_ref, active = np.zeros((len(infos), nq)), np.zeros(len(infos), dtype=np.int32)
+    for k, g in enumerate(infos):
+        kind = getattr(g, "type", None)
+        w = None if kind is None else (q_weight_terminal if kind == GRID_TERMINAL else (q_weight_impact if kind == GRID_IMPACT else q_weight))
+        if w is not None and not np.any(w):
+            continue
+        active[k] = int(bool(ref.is_active(g)))
+        if active[k]:
+            q = np.asarray(ref.update_ref(model, g), dtype=float).reshape(-1)
+            if q.size != nq:
+                raise ValueError("[ConfigurationSpaceCost] the reference at grid point %d has %d entries, not %d" % (getattr(g, "stage", k), q.size, nq))
+            _checked_ref("ConfigurationSpaceCost", g, k, q)
+            q_ref[k] = q
+    return q_ref, active

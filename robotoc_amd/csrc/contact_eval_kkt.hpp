@@ -10,6 +10,7 @@
 // of the reference.  Records: the un-condensed contact-path convention (Qaa / la / lf ... in RTOC_BUF_CDD).
 // cost table (device): 12 arrays of M = nv + 1 doubles: q_ref | v_ref | u_ref | wq | wv | wa | wu | wq_T | wv_T | wq_I | wv_I | wdv_I
 #pragma once
+#include "kernel_args.hpp"
 #include "state_equation_lin.hpp"
 
 namespace rtoc {
@@ -18,6 +19,7 @@ struct CostArgs {
   RecView rv;
   const double* cost;
   double* cost_out;       // [batch][nstages] value of the stage / impact / terminal cost (evalOCP: line search), or nullptr
+  QRefTable qtab;         // q_ref and isActive per grid point (ConfigurationSpaceRefBase), or q == nullptr: the constant q_ref
 };
 
 // kkt_matrix.setZero() / kkt_residual.setZero() of every grid point as one stream over the (contiguous) KKT records -- 16 B per
@@ -30,6 +32,7 @@ struct CostArgs {
 struct InitArgs {
   RecView rv;
   const double* cost;      // the table of contact_cost_kernel
+  QRefTable qtab;          // of contact_cost_kernel: where its row is inactive the q terms are absent, the joint diagonal of Qqq too
 };
 static __global__ __launch_bounds__(256) void init_records_kernel(InitArgs a) {
   typedef double dbl2 __attribute__((ext_vector_type(2)));
@@ -46,6 +49,8 @@ static __global__ __launch_bounds__(256) void init_records_kernel(InitArgs a) {
     const double* const Wv = terminal ? wvT : impact ? wvI : wv;
     const bool sto = !terminal && !impact;
     const double dt = impact ? 0.0 : scale;   // terminal records: no state equation
+    // enable_q_cost && isCostConfigActive (configuration_space_cost.cpp:274-442): uniform over the record
+    const bool qon = !a.qtab.q || a.qtab.active[a.qtab.row(b, a.rv.nstages, st)] != 0;
     dbl2* const p2 = reinterpret_cast<dbl2*>(a.rv.kkt_at(rec));
     for (int t = threadIdx.x; t < half; t += 256) {
       dbl2 v = {0.0, 0.0};
@@ -53,7 +58,7 @@ static __global__ __launch_bounds__(256) void init_records_kernel(InitArgs a) {
       if (w >= qxx0 && w < qxx1) {
         const int d = w - qxx0, c = d / nx, r = d - c * nx;   // column-major: rows r, r + 1 of column c (nx is even)
         if (r == c || r + 1 == c) {
-          const double dv = c < nv ? (c >= nb ? scale * Wq[c] : 0.0) : scale * Wv[c - nv];   // the base block: contact_cost_kernel
+          const double dv = c < nv ? (c >= nb && qon ? scale * Wq[c] : 0.0) : scale * Wv[c - nv];   // the base block: contact_cost_kernel
           if (r == c) v.x = dv;
           else v.y = dv;
         }
@@ -95,7 +100,17 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   const double* const s = a.rv.sol_at(rec);
   double* const kr = a.rv.kkt_at(rec);
   double* const cr = a.rv.cdd_at(rec);
-  const double *qr = a.cost, *vr = qr + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M, *wqT = wu + M,
+  // the q_ref of this (instance, grid point): its row of the table if there is one.  qon: whether the q terms exist here (isActive
+  // of the row) -- an inactive row is not read (its contents may be anything): the constant q_ref stands in for it, so that every
+  // group of the wave runs the same code up to the barrier below, and what depends on it is neither stored nor summed
+  bool qon = true;
+  const double* qr = a.cost;
+  if (a.qtab.q) {
+    const size_t row = a.qtab.row(b, a.rv.nstages, st);
+    qon = a.qtab.active[row] != 0;
+    if (qon) qr = a.qtab.q + row * a.qtab.nq;
+  }
+  const double *vr = a.cost + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M, *wqT = wu + M,
                *wvT = wqT + M, *wqI = wvT + M, *wvI = wqI + M, *wdvI = wvI + M;
   const double scale = (impact || terminal) ? 1.0 : grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st);
   const double* const Wq = terminal ? wqT : impact ? wqI : wq;
@@ -137,7 +152,7 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   double* const hx = kr + a.rv.kkt_off(RTOC_KKT_HX);
   double hval = 0.0;   // this lane's share of cost / dt (cost itself on impact / terminal grids) = 1/2 sum of weight * difference^2
   for (int i = lane; i < nv; i += COST_LW) {
-    if (i >= nb) {
+    if (i >= nb && qon) {
       const double dq = q[(nb ? 1 : 0) + i] - qr[(nb ? 1 : 0) + i];
       lx[i] = scale * Wq[i] * dq;
       if (sto) hx[i] = Wq[i] * dq;
@@ -182,9 +197,9 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
       double t = 0.0;
 #pragma unroll
       for (int k = 0; k < 6; ++k) t += J[k + 6 * r] * Wq[k] * J[k + 6 * c];
-      Qxx[r + (size_t)c * nx] = scale * t;
+      if (qon) Qxx[r + (size_t)c * nx] = scale * t;
     }
-    if (lane < 6) {
+    if (lane < 6 && qon) {
       double t = 0.0;
 #pragma unroll
       for (int k = 0; k < 6; ++k) t += J[k + 6 * lane] * wd[k];

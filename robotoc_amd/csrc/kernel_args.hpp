@@ -225,6 +225,16 @@ struct IntArgs {
   rtoc_record_layout sl, dl;
 };
 
+// ---- contact_eval_kkt.hpp (init_records_kernel, contact_cost_kernel), rigid_body.hpp (unconstr_eval_kkt_kernel) ----
+// rtoc_set_configuration_ref_table: the q_ref of a ConfigurationSpaceRefBase and its isActive per GRID POINT.  q == nullptr: no
+// table, the constant q_ref of the cost table is the reference of every grid point (and `active` is not read).
+struct QRefTable {
+  const double* q;     // [nstages][nq] or [batch][nstages][nq]; a row has the layout of rtoc_configuration_cost::q_ref
+  const int* active;   // same leading shape: isActive(grid_info)
+  int per_instance, nq;
+  __device__ size_t row(int b, int nstages, int st) const { return (size_t)(per_instance ? b : 0) * nstages + st; }
+};
+
 // ---- fxx_structure.hpp ----
 struct FxxCheckArgs {
   const double* kkt;

@@ -23,6 +23,7 @@
 // The kernels and their argument blocks: rt_eval_kkt.hip launches them and is the one unit that includes this header.  The
 // model they read and the plan of the walk are rigid_body_model.hpp (host), the spatial arithmetic is rigid_body_math.hpp.
 #pragma once
+#include "kernel_args.hpp"
 #include "device_utils.hpp"
 #include "record_view.hpp"
 #include "rigid_body_math.hpp"
@@ -683,6 +684,7 @@ struct UkArgs {
   const double* x0;   // [batch][2 nv] initial state of the horizon (q, v of updateSolution(t, q, v)); may be nullptr
   double dt;
   double* cost_out;   // [batch][nstages] value of the stage / terminal cost (the line search's evalOCP reads it), or nullptr
+  QRefTable qtab;     // q_ref and isActive per grid point (ConfigurationSpaceRefBase), or q == nullptr: the constant q_ref
 };
 
 static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) {
@@ -697,14 +699,23 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
   double* const kr = a.rv.kkt_at(rec);
   double* const cr = a.rv.cdd_at(rec);
   const int M = nv + 1;
-  const double *qr = a.cost, *vr = qr + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M,
-               *wqf = wu + M, *wvf = wqf + M;
+  const double *vr = a.cost + M, *ur = vr + M, *wq = ur + M, *wv = wq + M, *wa = wv + M, *wu = wa + M, *wqf = wu + M, *wvf = wqf + M;
+  // the q_ref of this (instance, grid point): its row of the table if there is one.  An inactive row is not read: the q terms are
+  // absent there (enable_q_cost && isCostConfigActive), i.e. they are the terms of a zero weight on the constant q_ref
+  bool qon = true;
+  const double* qr = a.cost;
+  if (a.qtab.q) {
+    const size_t row = a.qtab.row(b, a.rv.nstages, st);
+    qon = a.qtab.active[row] != 0;
+    if (qon) qr = a.qtab.q + row * a.qtab.nq;
+  }
   const double dt = a.dt;
   // Hessian blocks: zero, then the diagonals (Qqq, Qvv; Qaa in the Quu slot)
   for (int e = lane; e < nx * nx; e += 64) {
     const int r = e % nx, c = e / nx;
     double v = 0.0;
     if (r == c) v = terminal ? (r < nv ? wqf[r] : wvf[r - nv]) : dt * (r < nv ? wq[r] : wv[r - nv]);
+    if (!qon && r < nv) v = 0.0;
     kr[a.rv.kkt_off(RTOC_KKT_QXX) + e] = v;
   }
   for (int e = lane; e < nx * nv; e += 64) kr[a.rv.kkt_off(RTOC_KKT_QXU) + e] = 0.0;
@@ -713,7 +724,7 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
   for (int i = lane; i < nv; i += 64) {
     const double q = s[a.rv.sol_off(RTOC_SOL_Q) + i], v = s[a.rv.sol_off(RTOC_SOL_V) + i], lmd = s[a.rv.sol_off(RTOC_SOL_LMD) + i], gmm = s[a.rv.sol_off(RTOC_SOL_GMM) + i];
     if (terminal) {
-      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = wqf[i] * (q - qr[i]) - lmd;        // evalTerminalCostDerivatives + ...ForwardEulerTerminal
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = (qon ? wqf[i] : 0.0) * (q - qr[i]) - lmd;   // evalTerminalCostDerivatives + ...ForwardEulerTerminal
       kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] = wvf[i] * (v - vr[i]) - gmm;
       kr[a.rv.kkt_off(RTOC_KKT_FX) + i] = 0.0, kr[a.rv.kkt_off(RTOC_KKT_FX) + nv + i] = 0.0;
       kr[a.rv.kkt_off(RTOC_KKT_LU) + i] = 0.0;
@@ -723,7 +734,7 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
       const double qn = sn[a.rv.sol_off(RTOC_SOL_Q) + i], vn = sn[a.rv.sol_off(RTOC_SOL_V) + i], lmdn = sn[a.rv.sol_off(RTOC_SOL_LMD) + i], gmmn = sn[a.rv.sol_off(RTOC_SOL_GMM) + i];
       kr[a.rv.kkt_off(RTOC_KKT_FX) + i] = q + dt * v - qn;                                            // Fq (:60)
       kr[a.rv.kkt_off(RTOC_KKT_FX) + nv + i] = v + dt * acc - vn;                                     // Fv (:61)
-      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = dt * wq[i] * (q - qr[i]) + (lmdn - lmd);                    // lq
+      kr[a.rv.kkt_off(RTOC_KKT_LX) + i] = dt * (qon ? wq[i] : 0.0) * (q - qr[i]) + (lmdn - lmd);      // lq
       kr[a.rv.kkt_off(RTOC_KKT_LX) + nv + i] = dt * wv[i] * (v - vr[i]) + (dt * lmdn + gmmn - gmm);   // lv
       kr[a.rv.kkt_off(RTOC_KKT_LU) + i] = dt * wa[i] * acc + dt * gmmn;                               // la (in the lu slot)
       cr[a.rv.cdd_off(RTOC_CDD_LA) + i] = dt * wu[i] * (u - ur[i]);                                   // lu (in CDD.la)
@@ -736,10 +747,10 @@ static __global__ __launch_bounds__(64) void unconstr_eval_kkt_kernel(UkArgs a) 
     for (int i = lane; i < nv; i += 64) {
       const double dq = s[a.rv.sol_off(RTOC_SOL_Q) + i] - qr[i], dv = s[a.rv.sol_off(RTOC_SOL_V) + i] - vr[i];
       if (terminal) {
-        l += wqf[i] * dq * dq + wvf[i] * dv * dv;
+        l += (qon ? wqf[i] : 0.0) * dq * dq + wvf[i] * dv * dv;
       } else {
         const double acc = s[a.rv.sol_off(RTOC_SOL_A) + i], du = s[a.rv.sol_off(RTOC_SOL_U) + i] - ur[i];
-        l += wq[i] * dq * dq + wv[i] * dv * dv + wa[i] * acc * acc + wu[i] * du * du;
+        l += (qon ? wq[i] : 0.0) * dq * dq + wv[i] * dv * dv + wa[i] * acc * acc + wu[i] * du * du;
       }
     }
 #pragma unroll

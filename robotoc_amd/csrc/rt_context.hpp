@@ -168,6 +168,11 @@ struct ModelState {
   DevBuf<double> d_crot;
   DevBuf<double> d_cost;      // rtoc_set_configuration_cost: 12 (nv + 1) doubles
   DevBuf<double> d_x0;        // rtoc_set_initial_state: [batch][nq + nv]
+  // rtoc_set_configuration_ref_table: q_ref rows of nq doubles and their isActive, [nstages] or [batch][nstages] of them (capacity: the
+  // same at max_stages).  qtab_on: a table is in use; qtab_n: the nstages its rows were set for (0: rtoc_set_grid forgot them)
+  DevBuf<double> d_qtab;
+  DevBuf<int> d_qtab_active;
+  int qtab_on = 0, qtab_n = 0, qtab_inst = 0;
   // false: no memory for the host copy of the model (no HIP error to report)
   bool clone_from(const ModelState& src, CopyChain& dup) {
     if (src.h_model) {
@@ -181,6 +186,9 @@ struct ModelState {
     dup(d_crot, src.d_crot);
     dup(d_cost, src.d_cost);
     dup(d_x0, src.d_x0);
+    qtab_on = src.qtab_on, qtab_n = src.qtab_n, qtab_inst = src.qtab_inst;
+    dup(d_qtab, src.d_qtab);
+    dup(d_qtab_active, src.d_qtab_active);
     return true;
   }
   // not copied: scratch and results of the last evaluation

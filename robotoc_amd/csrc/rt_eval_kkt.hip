@@ -315,6 +315,56 @@ int rtoc_set_configuration_cost(rtoc_ctx* c, const rtoc_configuration_cost* cost
   return RTOC_OK;
 }
 
+// ConfigurationSpaceCost::set_ref(std::shared_ptr<ConfigurationSpaceRefBase>) (configuration_space_cost.cpp:84-89): the answers of
+// the object per grid point.  Everything is checked and staged before the context changes: a refused call leaves the table in force.
+int rtoc_set_configuration_ref_table(rtoc_ctx* c, const double* q_ref, const int* active, int nstages, int per_instance) {
+  if (!c) return RTOC_ERR_BAD_ARG;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!q_ref) {
+    if (c->qtab_on) c->epoch++;   // the kernels' table pointer is baked into captured graphs
+    c->qtab_on = 0, c->qtab_n = 0;
+    return RTOC_OK;
+  }
+  if (c->nstages < 2) return RTOC_ERR_NOT_READY;   // rtoc_set_grid
+  if (nstages != c->nstages || (per_instance != 0 && per_instance != 1)) return RTOC_ERR_BAD_ARG;
+  if (c->dims.np != 0 && c->dims.np != 6) return RTOC_ERR_BAD_ARG;
+  const size_t nq = (size_t)c->dims.nv + (c->dims.np == 6 ? 1 : 0), rows = (size_t)nstages * (per_instance ? c->batch : 1);
+  std::vector<int> flags(rows, 1);
+  for (size_t r = 0; r < rows; ++r) {
+    if (active) flags[r] = active[r] != 0;
+    if (!flags[r]) continue;   // an inactive row is never read, here or on the device
+    for (size_t k = 0; k < nq; ++k)
+      if (!std::isfinite(q_ref[r * nq + k])) return RTOC_ERR_BAD_ARG;
+  }
+  const size_t cap = (size_t)c->max_stages * (per_instance ? c->batch : 1);
+  bool fresh = false, fresh_a = false;
+  if (c->d_qtab.n != cap * nq || c->d_qtab_active.n != cap) {
+    // a new capacity: both allocations first, so that a failure of the second leaves no half of a table behind
+    DevBuf<double> q;
+    DevBuf<int> f;
+    HIP_TRY(q.reserve(cap * nq, &fresh));
+    HIP_TRY(f.reserve(cap, &fresh_a));
+    c->d_qtab = std::move(q), c->d_qtab_active = std::move(f);
+    c->qtab_n = 0;   // whatever was there is gone
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_qtab.p, q_ref, sizeof(double) * rows * nq, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_qtab_active.p, flags.data(), sizeof(int) * rows, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (fresh || fresh_a || !c->qtab_on || c->qtab_inst != per_instance) c->epoch++;
+  c->qtab_on = 1, c->qtab_n = nstages, c->qtab_inst = per_instance;
+  return RTOC_OK;
+}
+// The table for the kernels that read the cost table (q = nullptr without one).  RTOC_ERR_NOT_READY: a table is in use but its rows
+// belong to a grid rtoc_set_grid has replaced -- never the constant q_ref in their place.
+static int configuration_ref_table(const rtoc_ctx* c, QRefTable* t) {
+  t->q = nullptr, t->active = nullptr, t->per_instance = 0, t->nq = 0;
+  if (!c->qtab_on) return RTOC_OK;
+  if (c->qtab_n != c->nstages || !c->d_qtab.p || !c->d_qtab_active.p) return RTOC_ERR_NOT_READY;
+  t->q = c->d_qtab.p, t->active = c->d_qtab_active.p, t->per_instance = c->qtab_inst;
+  t->nq = c->dims.nv + (c->dims.np == 6 ? 1 : 0);
+  return RTOC_OK;
+}
+
 int rtoc_set_initial_state(rtoc_ctx* c, const double* x0, int count) {
   if (!c || !x0 || count != c->batch) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
@@ -392,7 +442,9 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   if (!(dt > 0.0) || c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
   if (!c->h_model || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
-  int rc = c->ntasks > 0 ? task_costs_ready(c, true) : RTOC_OK;   // ahead of the first launch: a refusal leaves the records alone
+  QRefTable qtab;
+  int rc = configuration_ref_table(c, &qtab);   // ahead of the first launch: a refusal leaves the records alone
+  if (!rc && c->ntasks > 0) rc = task_costs_ready(c, true);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_DX0);
@@ -405,6 +457,7 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   a.cost = c->d_cost.p;
   a.x0 = c->d_x0.p;
   a.dt = dt;
+  a.qtab = qtab;
   c->ls_unconstr_dt = dt;
   if (c->ls_on) HIP_TRY(reserve_costval(c));
   a.cost_out = c->ls_on ? c->d_costval.p : nullptr;   // the line search's evalOCP (unconstr_line_search.cpp:56-83)
@@ -460,6 +513,16 @@ int rtoc_kkt_error(rtoc_ctx* c, double* host_out, int count) {
   int rc = launch_kkt_error(c);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(host_out, c->d_kkterr.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RTOC_OK;
+}
+
+// the per-grid-point cost values the last evalKKT stored for evalOCP
+int rtoc_get_stage_costs(rtoc_ctx* c, double* host_out, int count) {
+  CHECK_READY(c);
+  if (!host_out || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
+  if (!c->d_costval.p) return RTOC_ERR_NOT_READY;
+  HIP_TRY(hipMemcpyAsync(host_out, c->d_costval.p, sizeof(double) * count * c->nstages, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RTOC_OK;
 }
@@ -589,7 +652,9 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   CHECK_READY(c);
   if (!c->h_model || !c->d_active.p || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   const bool switching = any_grid_point(c, c->nstages, grid_has_switching);
-  int rc = ensure_buffer(c, RTOC_BUF_KKT);
+  QRefTable qtab;
+  int rc = configuration_ref_table(c, &qtab);   // ahead of the first launch: a refusal leaves the records alone
+  if (!rc) rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
   c->ls_unconstr_dt = 0.0;
@@ -606,13 +671,14 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   a.rv = view(c);
   a.cost = c->d_cost.p;
   a.cost_out = c->d_costval.p;
+  a.qtab = qtab;
   {
     // setZero of the KKT records (+ the constant diagonals of the cost) as one stream on the context's second stream (rtoc_riccati_sweep's), BESIDE
     // the values pre-pass of the rigid-body linearisation (lanes = bodies; writes its scratch and RTOC_CDD_IDC, which nothing
     // here zeroes): the one is bound by HBM writes, the other by latency -- 1.1 ms each per 4096 x 47 grid points, one after the
     // other on one stream.  The cost kernel and everything behind it wait for both.
     InitArgs ia;
-    ia.rv = a.rv, ia.cost = c->d_cost.p;
+    ia.rv = a.rv, ia.cost = c->d_cost.p, ia.qtab = qtab;
     const long long nrec = (long long)c->batch * c->nstages;
     // four workgroups per CU: half of the wave slots, so that the pre-pass's waves are resident beside them
     const int blocks = (int)(nrec < (long long)c->num_cus * 4 ? nrec : (long long)c->num_cus * 4);

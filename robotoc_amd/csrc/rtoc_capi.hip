@@ -285,6 +285,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
   }
   c->h_gt.clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
   for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) c->reftab_n[k] = 0;   // and so do the reference tables: rtoc_set_task_ref_table again
+  c->qtab_n = 0;   // ... and the rows of the q_ref table, not the fact that one is in use: rtoc_set_configuration_ref_table again
   return RTOC_OK;
 }
 

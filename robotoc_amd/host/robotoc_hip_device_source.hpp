@@ -58,6 +58,14 @@ class ConfigurationCostSource : public StageDataSource {
   }
   // a LocalContactForceCost component of the cost (before the solver is constructed); null: none
   void setContactForceCost(const std::shared_ptr<LocalContactForceCost>& force_cost) { force_cost_ = force_cost; }
+  // ConfigurationSpaceCost::set_ref (configuration_space_cost.cpp:84-89): a time-varying q_ref in place of cost.q_ref, asked at every
+  // grid point of the grid in force after every (re-)discretisation -- with switching-time optimisation at the grid's own times,
+  // which the switching times then move without the object being asked again until the next mesh refinement.  nullptr: back to
+  // the constant reference (set_q_ref's use_nonconst_ref_ = false)
+  void setConfigurationRef(const std::shared_ptr<ConfigurationSpaceRefBase>& ref) {
+    config_ref_ = ref;
+    config_ref_dirty_ = true;
+  }
   ContactSequence* contactSequence() override { return cs_.get(); }
   const STOConstraints* stoConstraints() const override { return sto_.get(); }
   double horizonLength() const override { return T_; }
@@ -66,6 +74,7 @@ class ConfigurationCostSource : public StageDataSource {
     return cs_ ? N_ + 1 + cs_->numLiftEvents() + 2 * cs_->numImpactEvents() : td_.size();
   }
   bool discretize(const double t) override {
+    config_ref_dirty_ = true;   // the solver sets the grid again after this, whoever owns the discretisation
     if (!cs_) return false;
     td_ = robotoc::discretize(*cs_, T_, N_, t, static_cast<bool>(sto_));
     contactSchedule(*cs_, td_, active_, cpos_, &crot_);
@@ -134,6 +143,7 @@ class ConfigurationCostSource : public StageDataSource {
       chk(rtoc_set_barrier_param(ctx, barrier_, ftb_), "rtoc_set_barrier_param");
     }
     scheduled_ = false;
+    config_ref_dirty_ = true;
   }
   void initConstraints(rtoc_ctx* ctx, const Solution&) override {
     schedule(ctx);
@@ -161,6 +171,18 @@ class ConfigurationCostSource : public StageDataSource {
         const std::vector<rtoc_task_ref_entry> tab = task_costs_[k]->refTable(grid);
         chk(rtoc_set_task_ref_table(ctx, static_cast<int>(k), tab.data(), static_cast<int>(tab.size()), 0), "rtoc_set_task_ref_table");
       }
+    }
+    // the q_ref table, where the task tables are filled: rtoc_set_grid forgot its rows, and evalKKT refuses to run without them
+    if (config_ref_dirty_) {
+      if (config_ref_) {
+        std::vector<GridInfo> grid(td_.size());
+        for (int i = 0; i < td_.size(); ++i) grid[i] = td_[i];
+        const ConfigurationRefTable tab = configurationRefTable(*config_ref_, model_, cost_, grid);
+        chk(rtoc_set_configuration_ref_table(ctx, tab.q_ref.data(), tab.active.data(), td_.size(), 0), "rtoc_set_configuration_ref_table");
+      } else {
+        chk(rtoc_set_configuration_ref_table(ctx, nullptr, nullptr, 0, 0), "rtoc_set_configuration_ref_table");
+      }
+      config_ref_dirty_ = false;
     }
     chk(rtoc_contact_eval_kkt(ctx), "rtoc_contact_eval_kkt");
   }
@@ -191,6 +213,8 @@ class ConfigurationCostSource : public StageDataSource {
   std::vector<rtoc_task_cost> tasks_;
   std::vector<std::shared_ptr<TaskCostComponent>> task_costs_;
   std::shared_ptr<LocalContactForceCost> force_cost_;
+  std::shared_ptr<ConfigurationSpaceRefBase> config_ref_;
+  bool config_ref_dirty_ = false;   // the device's table (or its absence) is not what config_ref_ says
   std::vector<rtoc_box_row> rows_;
   std::vector<double> bounds_, mu_;
   bool impact_cone_ = false;

@@ -87,6 +87,44 @@ inline void checkFiniteRef(const char* name, const GridInfo& g, const double* x,
 inline double phaseRate(const GridInfo& g) { return static_cast<double>(g.stage_in_phase) / static_cast<double>(g.num_grids_in_phase); }
 }  // namespace detail
 
+// include/robotoc/cost/configuration_space_ref_base.hpp: a time-varying q_ref of the ConfigurationSpaceCost
+// (ConfigurationSpaceCost::set_ref), the model table in place of Robot.  The user's own class: the shells call updateRef /
+// isActive once per grid point when they discretise and hand the device a table (rtoc_set_configuration_ref_table).
+// q_ref arrives sized nq: [x y z qx qy qz qw, joints] with a free-flyer base.
+class ConfigurationSpaceRefBase {
+ public:
+  virtual ~ConfigurationSpaceRefBase() {}
+  virtual void updateRef(const rtoc_robot_model& robot, const GridInfo& grid_info, Vec& q_ref) const = 0;
+  virtual bool isActive(const GridInfo& grid_info) const = 0;
+};
+
+// The table of a ConfigurationSpaceRefBase over `grid`: q_ref[grid point][nq], active[grid point].  The reference's order of
+// questions (configuration_space_cost.cpp:251-442, configuration_space_cost.hpp:166-216): isActive only where the q weight of the
+// grid point's kind is not all zero (enable_q_cost_ / _terminal_ / _impact_), updateRef only where the reference is active; a
+// reference that is not finite is refused.  Rows that were not asked for stay zero and inactive.
+struct ConfigurationRefTable {
+  std::vector<double> q_ref;
+  std::vector<int> active;
+};
+inline ConfigurationRefTable configurationRefTable(const ConfigurationSpaceRefBase& ref, const rtoc_robot_model& robot,
+                                                   const rtoc_configuration_cost& cost, const std::vector<GridInfo>& grid) {
+  ConfigurationRefTable tab;
+  const size_t nq = static_cast<size_t>(robot.nq);
+  tab.q_ref.assign(grid.size() * nq, 0.0), tab.active.assign(grid.size(), 0);
+  for (size_t i = 0; i < grid.size(); ++i) {
+    const GridInfo& g = grid[i];
+    const double* const w = g.type == GridType::Terminal ? cost.q_weight_terminal : (g.type == GridType::Impact ? cost.q_weight_impact : cost.q_weight);
+    if (detail::allZero(w, robot.nv) || !ref.isActive(g)) continue;
+    Vec q(robot.nq);
+    ref.updateRef(robot, g, q);
+    if (q.size() != robot.nq) throw std::invalid_argument("[ConfigurationSpaceCost] the reference at grid point " + std::to_string(g.stage) + " has the wrong size");
+    detail::checkFiniteRef("ConfigurationSpaceCost", g, q.data(), robot.nq);
+    tab.active[i] = 1;
+    for (size_t k = 0; k < nq; ++k) tab.q_ref[i * nq + k] = q(static_cast<int>(k));
+  }
+  return tab;
+}
+
 class PeriodicSwingFootRef : public TaskSpace3DRefBase {
  public:
   PeriodicSwingFootRef(const Vector3d& x3d0, const Vector3d& step_length, const double step_height, const double t0,

@@ -37,6 +37,10 @@ struct UnconstrOCP {
   // the cost function's components beside the ConfigurationSpaceCost (at most RTOC_MAX_TASK_COSTS); a TaskSpace6DRefBase is
   // asked at t + i dt of every grid point when the solver discretises
   std::vector<std::shared_ptr<TaskCostComponent>> task_costs;
+  // ConfigurationSpaceCost::set_ref: a time-varying q_ref in place of cost.q_ref, asked at t + i dt of every grid point when the
+  // solver discretises; null: the constant cost.q_ref
+  std::shared_ptr<ConfigurationSpaceRefBase> configuration_ref;
+  void setConfigurationRef(const std::shared_ptr<ConfigurationSpaceRefBase>& ref) { configuration_ref = ref; }
 };
 
 class UnconstrOCPSolver {
@@ -74,7 +78,7 @@ class UnconstrOCPSolver {
   // value semantics like the reference (unconstr_ocp_solver.hpp:58-73): a copy owns a deep copy of the device context
   // (rtoc_clone: buffers, model, cost, bounds, slack / dual state)
   UnconstrOCPSolver(const UnconstrOCPSolver& o)
-      : ocp_(o.ocp_), dt_(o.dt_), dims_(o.dims_), L_(o.L_), s_(o.s_), lqr_policy_(o.lqr_policy_), solver_options_(o.solver_options_),
+      : ocp_(o.ocp_), dt_(o.dt_), t_(o.t_), dims_(o.dims_), L_(o.L_), s_(o.s_), lqr_policy_(o.lqr_policy_), solver_options_(o.solver_options_),
         solver_statistics_(o.solver_statistics_), kkt_error_(o.kkt_error_), host_solution_valid_(o.host_solution_valid_),
         device_solution_valid_(o.device_solution_valid_) {
     if (o.ctx_) {
@@ -116,7 +120,8 @@ class UnconstrOCPSolver {
       g[i].dt = i == ocp_.N ? 0.0 : dt_;
     }
     check(rtoc_set_grid(ctx_.get(), g.data(), ocp_.N + 1), "rtoc_set_grid");
-    if (ocp_.task_costs.empty()) return;
+    t_ = t;
+    if (ocp_.task_costs.empty() && !ocp_.configuration_ref) return;
     std::vector<double> times(ocp_.N + 1);
     std::vector<GridInfo> grid(ocp_.N + 1);
     for (int i = 0; i <= ocp_.N; ++i) {
@@ -125,12 +130,24 @@ class UnconstrOCPSolver {
       grid[i].t0 = t, grid[i].t = times[i], grid[i].dt = g[i].dt, grid[i].stage = i, grid[i].stage_in_phase = i;
       grid[i].num_grids_in_phase = ocp_.N;
     }
+    if (ocp_.configuration_ref) {   // rtoc_set_grid forgot the rows: evalKKT refuses to run until they are set again
+      const ConfigurationRefTable tab = configurationRefTable(*ocp_.configuration_ref, ocp_.robot, ocp_.cost, grid);
+      check(rtoc_set_configuration_ref_table(ctx_.get(), tab.q_ref.data(), tab.active.data(), ocp_.N + 1, 0), "rtoc_set_configuration_ref_table");
+    }
+    if (ocp_.task_costs.empty()) return;
     check(rtoc_set_grid_times(ctx_.get(), times.data(), ocp_.N + 1), "rtoc_set_grid_times");
     for (size_t k = 0; k < ocp_.task_costs.size(); ++k) {
       if (!ocp_.task_costs[k]->usesTable()) continue;
       const std::vector<rtoc_task_ref_entry> tab = ocp_.task_costs[k]->refTable(grid);
       check(rtoc_set_task_ref_table(ctx_.get(), static_cast<int>(k), tab.data(), static_cast<int>(tab.size()), 0), "rtoc_set_task_ref_table");
     }
+  }
+  // ConfigurationSpaceCost::set_ref on the solver's cost: the table is filled at once, at the times of the last discretize(t);
+  // nullptr goes back to the constant cost.q_ref
+  void setConfigurationRef(const std::shared_ptr<ConfigurationSpaceRefBase>& ref) {
+    ocp_.configuration_ref = ref;
+    if (ref) discretize(t_);
+    else check(rtoc_set_configuration_ref_table(ctx_.get(), nullptr, nullptr, 0, 0), "rtoc_set_configuration_ref_table");
   }
   // initConstraints (:91-93): setSlackAndDual of the joint-limit rows at the current iterate
   void initConstraints() {
@@ -255,7 +272,7 @@ class UnconstrOCPSolver {
   }
 
   UnconstrOCP ocp_;
-  double dt_ = 0.0;
+  double dt_ = 0.0, t_ = 0.0;   // t_: the initial time of the last discretize
   RobotDims dims_;
   std::shared_ptr<rtoc_ctx> ctx_;
   rtoc_layout L_;

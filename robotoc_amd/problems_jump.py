@@ -14,7 +14,7 @@ from .types import Records
 
 def anymal_jump_sto_solver(batch=1, device=0, N=40, dt=0.02, jump_length=0.25, ground_time=0.31, flying_time=0.2,
                            min_dwell=(0.1, 0.1, 0.2), with_limits=True, with_cones=True, max_iter=200, seed=7, x0_noise=0.0,
-                           horizon_scan="off"):
+                           horizon_scan="off", configuration_ref=None):
     m = rm.load_named("anymal")
     nv, nq, nu = m.nv, m.nq, m.nu
     qs = np.array(ANYMAL_Q_STANDING, dtype=float)
@@ -34,7 +34,8 @@ def anymal_jump_sto_solver(batch=1, device=0, N=40, dt=0.02, jump_length=0.25, g
     limits = (np.full(nu, -9.42), np.full(nu, 9.42), np.full(nu, 7.5), np.full(nu, 80.0)) if with_limits else None
     opts = SolverOptions(max_iter=max_iter, kkt_tol=1e-7, kkt_tol_mesh=1.0, max_dt_mesh=T / N, horizon_scan=horizon_scan)
     solver = OCPSolver(m, plan, T, N, cost, joint_limits=limits, friction_coefficients=np.full(4, 0.7) if with_cones else None,
-                       sto_constraints=STOConstraints(list(min_dwell)), options=opts, batch=batch, device=device)
+                       sto_constraints=STOConstraints(list(min_dwell)), options=opts, batch=batch, device=device,
+                       configuration_ref=configuration_ref)
     rng = np.random.default_rng(seed)
     x0 = np.tile(np.concatenate([qs, np.zeros(nv)]), (batch, 1))
     if x0_noise > 0.0:

@@ -13,7 +13,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import capi
-from .costs import grid_infos
+from .costs import configuration_ref_table, grid_infos
 from .grid import ContactSequence, Event, contact_masks, discretize, discretize_structure_preserving, max_time_step
 from .types import BUF_SOL, GRID_IMPACT, GRID_LIFT, GRID_TERMINAL, Dims, Records, joint_limit_rows
 
@@ -155,11 +155,16 @@ def interpolate_configuration(q1, q2, alpha, floating):
 class OCPSolver:
     def __init__(self, model, plan: ContactPlan, T, N, cost, joint_limits=None, friction_coefficients=None, barrier_param=1.0e-3,
                  fraction_to_boundary_rule=0.995, sto_constraints: Optional[STOConstraints] = None, options: Optional[SolverOptions] = None,
-                 batch=1, device=0, impact_cones=False, task_costs=None, force_cost=None):
+                 batch=1, device=0, impact_cones=False, task_costs=None, force_cost=None, configuration_ref=None):
         """cost: keyword arguments of capi.Context.set_configuration_cost; joint_limits: (q_min, q_max, v_max, u_max) over the
         actuated joints or None; friction_coefficients: per contact or None; task_costs: robotoc_amd.costs.TaskSpace3DCost /
         CoMCost / TaskSpace6DCost components added to the configuration cost (a list shared by the batch) or None; force_cost: a
-        robotoc_amd.costs.LocalContactForceCost (shared by the batch) or None."""
+        robotoc_amd.costs.LocalContactForceCost (shared by the batch) or None; configuration_ref: a
+        robotoc_amd.costs.ConfigurationSpaceRefBase -- a time-varying q_ref in place of the cost's constant one
+        (ConfigurationSpaceCost::set_ref) -- shared by the batch, a list of `batch` of them (every instance its own), or None.  The
+        object is asked once per grid point at every (re-)discretisation, mesh refinements included; with switching-time
+        optimisation at the times of the structure the batch shares (those of the mean event times), not at every instance's own
+        -- the rule the task costs' user-object references follow."""
         self.model, self.plan, self.T, self.N = model, plan, float(T), int(N)
         self.options = options or SolverOptions()
         self.sto = sto_constraints
@@ -177,6 +182,9 @@ class OCPSolver:
         c = self.ctx
         c.set_robot_model(model)
         c.set_configuration_cost(**cost)
+        self.cost, self.configuration_ref = cost, configuration_ref
+        if isinstance(configuration_ref, (list, tuple)) and len(configuration_ref) != batch:
+            raise ValueError("a per-instance configuration_ref needs one object per instance")
         self.task_costs = list(task_costs) if task_costs else None
         if self.task_costs:
             c.set_task_costs(self.task_costs)
@@ -218,7 +226,7 @@ class OCPSolver:
         of the mean event times; every instance gets its own time steps from its own event times (rtoc_sto_set_problem)."""
         self.t0 = float(t)
         cs = self._sequence(self.event_times.mean(axis=0))
-        if self.task_costs:
+        if self.task_costs or self.configuration_ref is not None:
             grids, times, structure = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None, times=True, infos=True)
         else:
             grids = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None)
@@ -234,6 +242,12 @@ class OCPSolver:
             # references that are the user's objects: asked once per grid point (rtoc_set_grid has just forgotten the tables); the
             # DiscreteTime* references read the grid point's place in its phase, which the switching times do not move
             c.set_task_ref_tables(self.task_costs, grid_infos(times, [g.dt for g in grids], structure))
+        if self.configuration_ref is not None:
+            # rtoc_set_grid has just forgotten the rows: until they are set again evalKKT refuses to run
+            wqi = self.cost.get("q_weight_impact")   # not given: zero (capi.Context.set_configuration_cost)
+            c.set_configuration_ref_table(*configuration_ref_table(
+                self.configuration_ref, self.model, grid_infos(times, [g.dt for g in grids], structure), self.cost.get("q_weight"),
+                self.cost.get("q_weight_terminal"), np.zeros(self.model.nv) if wqi is None else wqi))
         self.masks = contact_masks(grids, self.plan.phase_masks, self.plan.impact_masks())
         pos, phase = np.zeros((len(grids), self.nc, 3)), 0
         for i, g in enumerate(grids):
