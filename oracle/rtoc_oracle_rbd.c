@@ -120,23 +120,44 @@ static void inertia_mul(double mass, const double* c, const double* I, const sv6
   *out = r;
 }
 
-/* log of a rotation (axis * angle), angle in [0, pi) */
+/* log of a rotation (axis * angle), angle in [0, pi].  Near pi the antisymmetric part vanishes (theta / (2 sin theta) amplifies
+ * its rounding like 1 / (pi - theta)^2, and at pi it is 0 / 0): there 4 q_i (q_x, q_y, q_z, q_w) of the quaternion of R, i the
+ * largest diagonal entry, and w = 2 atan2(|v|, q_w) v / |v|, in which the scale drops out */
 static void log3(const double* R, double* w) {
   const double tr = R[0] + R[4] + R[8];
   double c = 0.5 * (tr - 1.0);
   c = ORC_RE(c) > 1.0 ? 1.0 : (ORC_RE(c) < -1.0 ? -1.0 : c);
-  const double th = acos(c);
   const double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1]; /* vee(R - R^T) */
+  if (ORC_RE(c) < -0.99) {
+    const double sxy = R[1] + R[3], sxz = R[2] + R[6], syz = R[5] + R[7];
+    double v[3], qw;
+    if (ORC_RE(R[0]) >= ORC_RE(R[4]) && ORC_RE(R[0]) >= ORC_RE(R[8])) {
+      v[0] = 1.0 + R[0] - R[4] - R[8], v[1] = sxy, v[2] = sxz, qw = vx;
+    } else if (ORC_RE(R[4]) >= ORC_RE(R[8])) {
+      v[0] = sxy, v[1] = 1.0 + R[4] - R[0] - R[8], v[2] = syz, qw = vy;
+    } else {
+      v[0] = sxz, v[1] = syz, v[2] = 1.0 + R[8] - R[0] - R[4], qw = vz;
+    }
+    const double sg = ORC_RE(qw) < 0.0 ? -1.0 : 1.0;
+    const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    /* atan2(n, |q_w|) = pi/2 - atan(|q_w| / n) for n > 0 (here n >= 4/3): analytic, so the complex-step build differentiates it */
+    const double f = sg * 2.0 * (1.57079632679489661923 - atan(sg * qw / n)) / n;
+    w[0] = f * v[0], w[1] = f * v[1], w[2] = f * v[2];
+    return;
+  }
+  const double th = acos(c);
   const double k = ORC_MAG(th) < 1e-6 ? 0.5 + th * th / 12.0 : th / (2.0 * sin(th));
   w[0] = k * vx, w[1] = k * vy, w[2] = k * vz;
 }
 /* pinocchio::log6 of (R, p): [V^-1 p; log3 R] with V^-1 p = p - w x p / 2 + beta w x (w x p),
- * beta = 1/t^2 - sin t / (2 t (1 - cos t)) */
+ * beta = 1/t^2 - cot(t/2) / (2 t); between 1e-4 and 0.005 its series, where the closed form cancels like 1e-16 / t^2 */
 void orc_rbd_log6(const double* R, const double* p, double* xi) {
   double w[3], wxp[3], wxwxp[3];
   log3(R, w);
-  const double t = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  const double beta = ORC_MAG(t) < 1e-4 ? 1.0 / 12.0 + t * t / 720.0 : 1.0 / (t * t) - sin(t) / (2.0 * t * (1.0 - cos(t)));
+  const double t = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), t2 = t * t;
+  const double beta = ORC_MAG(t) < 1e-4  ? 1.0 / 12.0 + t * t / 720.0
+                      : ORC_MAG(t) < 0.005 ? 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0 + t2 * t2 * t2 / 1209600.0
+                                           : 1.0 / (t * t) - cos(0.5 * t) / (2.0 * t * sin(0.5 * t));
   cross3(w, p, wxp);
   cross3(w, wxp, wxwxp);
   for (int k = 0; k < 3; ++k) xi[k] = p[k] - 0.5 * wxp[k] + beta * wxwxp[k], xi[3 + k] = w[k];

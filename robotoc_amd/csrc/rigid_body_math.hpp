@@ -69,14 +69,45 @@ __device__ __forceinline__ void log6_fwd(const M3& R, V3 p, SV twist, SV& val, S
   const double tr = R.m[0] + R.m[4] + R.m[8];
   double c = 0.5 * (tr - 1.0);
   c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-  const double th = acos(c);
-  const double k = th < 1e-6 ? 0.5 + th * th / 12.0 : th / (2.0 * sin(th));
-  const V3 w = mk(k * (R.m[7] - R.m[5]), k * (R.m[2] - R.m[6]), k * (R.m[3] - R.m[1]));
+  const V3 as = mk(R.m[7] - R.m[5], R.m[2] - R.m[6], R.m[3] - R.m[1]);  // vee(R - R^T) = 4 q_w (q_x, q_y, q_z)
+  V3 w;
+  if (c < -0.99) {
+    // Near pi the antisymmetric part vanishes and theta / (2 sin theta) amplifies its rounding like 1 / (pi - theta)^2; at pi it
+    // is 0 / 0.  Take 4 q_i (q_x, q_y, q_z, q_w) of the quaternion of R instead, i the largest diagonal entry (q_i^2 >= 1/3 here:
+    // no cancellation), and w = 2 atan2(|v|, q_w) v / |v|, in which the scale drops out.  Uniform over the lanes of a call.
+    const double d0 = R.m[0], d1 = R.m[4], d2 = R.m[8];
+    const double sxy = R.m[1] + R.m[3], sxz = R.m[2] + R.m[6], syz = R.m[5] + R.m[7];
+    V3 v;
+    double qw;
+    if (d0 >= d1 && d0 >= d2) {
+      v = mk(1.0 + d0 - d1 - d2, sxy, sxz), qw = as.x;
+    } else if (d1 >= d2) {
+      v = mk(sxy, 1.0 + d1 - d0 - d2, syz), qw = as.y;
+    } else {
+      v = mk(sxz, syz, 1.0 + d2 - d0 - d1), qw = as.z;
+    }
+    // atan2(|v|, |q_w|) = pi/2 - atan x, x = |q_w| / |v| = cot(theta / 2) < 0.071 on this branch: seven terms of the series of atan
+    // (the next one is below 4e-19) instead of the library's atan2, whose registers the rigid-body kernels do not have to spare
+    const double n = sqrt(dot(v, v)), x = fabs(qw) / n, x2 = x * x;
+    const double at = x * (1.0 + x2 * (-1.0 / 3.0 + x2 * (1.0 / 5.0 + x2 * (-1.0 / 7.0 + x2 * (1.0 / 9.0 + x2 * (-1.0 / 11.0 + x2 * (1.0 / 13.0)))))));
+    w = ((qw < 0.0 ? -2.0 : 2.0) * (1.57079632679489661923 - at) / n) * v;
+  } else {
+    const double th = acos(c);
+    const double k = th < 1e-6 ? 0.5 + th * th / 12.0 : th / (2.0 * sin(th));
+    w = mk(k * as.x, k * as.y, k * as.z);
+  }
   const double t = sqrt(dot(w, w));
   double beta, dbeta;
   if (t < 1e-3) {
     beta = 1.0 / 12.0 + t * t / 720.0;
     dbeta = t / 360.0 + t * t * t / 7560.0;
+  } else if (t < 0.005) {
+    // the closed forms below cancel like 1e-16 / t^2 and 1e-16 / t^3, which puts Jlog6 off by about 1.5e-16 |p| / t: the series
+    // above continued (truncated under 1e-22) up to where that is 3e-14 |p|, a third of the 1e-13 the derivatives are held to --
+    // the margin of the near-pi switch; from there on the closed forms, as before
+    const double t2 = t * t;
+    beta = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0 + t2 * t2 * t2 / 1209600.0;
+    dbeta = t / 360.0 + t * t2 / 7560.0 + t * t2 * t2 / 201600.0;
   } else {
     const double h = 0.5 * t, ct = cos(h) / sin(h), cs2 = 1.0 / (sin(h) * sin(h));
     beta = 1.0 / (t * t) - ct / (2.0 * t);

@@ -439,7 +439,22 @@ class SolutionInterpolator {
     for (int a = 0; a < 4; ++a) q[a] /= nrm;
   }
   static void log3(const double* R, double* w) {
-    const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) / 2.0)), th = std::acos(c);
+    const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) / 2.0));
+    if (c < -0.99) {
+      // near pi the antisymmetric part vanishes (0 / 0 at pi): 4 q_i (q_x, q_y, q_z, q_w) of the quaternion of R, i the largest
+      // diagonal entry, and w = 2 atan2(|v|, q_w) v / |v| (the scale drops out)
+      int i = 0;
+      if (R[4] > R[0]) i = 1;
+      if (R[8] > R[4 * i]) i = 2;
+      const int j = (i + 1) % 3, k = (i + 2) % 3;
+      double v[3];
+      v[i] = 1.0 + R[4 * i] - R[4 * j] - R[4 * k], v[j] = R[3 * i + j] + R[3 * j + i], v[k] = R[3 * i + k] + R[3 * k + i];
+      const double qw = R[3 * k + j] - R[3 * j + k], n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      const double g = (qw < 0.0 ? -2.0 : 2.0) * std::atan2(n, std::fabs(qw)) / n;
+      w[0] = g * v[0], w[1] = g * v[1], w[2] = g * v[2];
+      return;
+    }
+    const double th = std::acos(c);
     const double f = th < 1e-10 ? 0.5 : th / (2.0 * std::sin(th));
     w[0] = f * (R[7] - R[5]), w[1] = f * (R[2] - R[6]), w[2] = f * (R[3] - R[1]);
   }

@@ -115,6 +115,18 @@ def _skew(a):
 
 def _log3(R):
     c = min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))
+    if c < -0.99:
+        # near pi the antisymmetric part vanishes (0 / 0 at pi): 4 q_i (q_x, q_y, q_z, q_w) of the quaternion of R, i the largest
+        # diagonal entry, and w = 2 atan2(|v|, q_w) v / |v| (the scale drops out)
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        v = np.zeros(3)
+        v[i], v[j], v[k] = 1.0 + R[i, i] - R[j, j] - R[k, k], R[i, j] + R[j, i], R[i, k] + R[k, i]
+        qw = R[k, j] - R[j, k]
+        if qw < 0.0:
+            v, qw = -v, -qw
+        n = np.linalg.norm(v)
+        return (2.0 * np.arctan2(n, qw) / n) * v
     th = np.arccos(c)
     if th < 1e-10:
         return 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])

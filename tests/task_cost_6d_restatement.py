@@ -20,15 +20,44 @@ def skew(v):
 
 def log3(R):
     c = min(1.0, max(-1.0, 0.5 * (np.trace(R) - 1.0)))
+    if c < -0.99:
+        # near pi the antisymmetric part vanishes: 4 q_i (q_x, q_y, q_z, q_w) of the quaternion of R, i the largest diagonal
+        # entry, and w = 2 atan2(|v|, q_w) v / |v| (the scale drops out)
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        v = np.zeros(3)
+        v[i], v[j], v[k] = 1.0 + R[i, i] - R[j, j] - R[k, k], R[i, j] + R[j, i], R[i, k] + R[k, i]
+        qw = R[k, j] - R[j, k]
+        if qw < 0.0:
+            v, qw = -v, -qw
+        n = np.linalg.norm(v)
+        return (2.0 * np.arctan2(n, qw) / n) * v
     th = np.arccos(c)
     k = 0.5 + th * th / 12.0 if th < 1e-6 else th / (2.0 * np.sin(th))
     return k * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
 
 
+SERIES_T = 0.005  # below: the series of beta and beta' / t (truncated under 1e-22); above: their closed forms, which cancel like 1e-16 / t^3
+
+
 def _beta(t):
     if t < 1e-3:
         return 1.0 / 12.0 + t * t / 720.0
-    return 1.0 / (t * t) - np.sin(t) / (2.0 * t * (1.0 - np.cos(t)))
+    if t < SERIES_T:
+        t2 = t * t
+        return 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0 + t2 * t2 * t2 / 1209600.0
+    return 1.0 / (t * t) - 1.0 / (2.0 * t * np.tan(0.5 * t))
+
+
+def _bdot_t(t):
+    """beta'(t) / t"""
+    if t < 1e-3:
+        return 1.0 / 360.0
+    if t < SERIES_T:
+        t2 = t * t
+        return 1.0 / 360.0 + t2 / 7560.0 + t2 * t2 / 201600.0
+    h = 0.5 * t
+    return (-2.0 / t ** 3 + 1.0 / (2.0 * t * t * np.tan(h)) + 1.0 / (4.0 * t * np.sin(h) ** 2)) / t
 
 
 def log6(R, p):
@@ -52,11 +81,7 @@ def jlog6(R, p):
     t = np.linalg.norm(w)
     A = jlog3(w)
     beta = _beta(t)
-    if t < 1e-3:
-        bdot_t = 1.0 / 360.0
-    else:
-        st, ct = np.sin(t), np.cos(t)
-        bdot_t = -2.0 / t ** 4 + (1.0 + st / t) / (t * t * 2.0 * (1.0 - ct))
+    bdot_t = _bdot_t(t)
     wp = np.dot(w, p)
     v = (bdot_t * wp) * w - (t * t * bdot_t + 2.0 * beta) * p
     Cm = np.outer(v, w) + beta * np.outer(w, p) + wp * beta * np.eye(3) + 0.5 * skew(p)

@@ -156,3 +156,84 @@ def test_switching_constraint_rows_against_the_cpu_restatement(oracle, robot, ex
     assert max(worst[k] for k in ("Phiq", "Phiv", "Phia", "Phit")) < 2e-6   # central differences
     assert max(worst[k] for k in ("lx", "la")) < 1e-10 and max(worst[k] for k in ("h", "hv", "ha", "Qtt")) < 2e-5
     ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot,exact", [("anymal", False), ("anymal", True), ("icub", False), ("icub", True)])
+def test_switching_constraint_with_a_resting_base_transports_by_the_identity(oracle, robot, exact):
+    """Zero base velocity and acceleration: dq_b = 0, exp6(dq_b) is exactly the identity, and both transports of the base block
+    are Tq = Ad_I^-1 = I and Jr = Jlog6(I)^-1 = I (log6 at X = identity, the branch point no random iterate meets).  They are
+    read through what they multiply: Phiq = Pq Tq^T, Phiv = (dt1 + dt2) Pq Jr^T, Phia = dt1 dt2 Pq Jr^T, and hv += 2 Pq^T xi
+    (Pq without a transport).  So Phiv = (dt1 + dt2) Phiq, Phia = dt1 dt2 Phiq and what xi adds to hv is twice what it adds to
+    lq, on the base columns to 1e-14 max(1, |Pq|), with either setting of RTOC_OPT_SWITCHING_TRANSPORT; no NaN.
+    Observed on the MI355X, as error / bound over the three comparisons: 0.011 (anymal), 0.0035 (icub)."""
+    from robotoc_amd.types import icub_dims
+    m = rm.load_named(robot)
+    N, T, batch = 20, 0.4, 2
+    if robot == "anymal":
+        dims, q_stand, ncon, ns = anymal_dims(), Q_STAND, 4, 6
+        cs = ContactSequence([12, 6, 12], [Event("lift", 0.105), Event("impact", 0.265, impact_dimf=6)])
+        phase_masks, impact_masks = [0b1111, 0b1001, 0b1111], [0b0110]
+    else:
+        dims, q_stand, ncon, ns = icub_dims(35), Q_ICUB, 2, 12
+        cs = ContactSequence([12, 0, 12], [Event("lift", 0.105), Event("impact", 0.265, impact_dimf=12)])
+        phase_masks, impact_masks = [0b11, 0b00, 0b11], [0b11]
+    grids = discretize(N, T, 0.0, cs)
+    n, nv, nq, nu = len(grids), m.nv, m.nq, m.nv - 6
+    i0 = [i for i, g in enumerate(grids) if g.switching_constraint][0]
+    masks = trot_masks(grids, phase_masks, impact_masks)
+    rng = np.random.default_rng(6)
+    place = [oracle.rbd_contact_placement(m, q_stand, c) for c in range(ncon)]
+    pos = np.tile(np.array([p for _, p in place])[None], (n, 1, 1)) + 0.01 * rng.uniform(-1, 1, (n, ncon, 3))
+    rot = np.zeros((n, ncon, 3, 3))
+    for i in range(n):
+        for c in range(ncon):
+            rot[i, c] = place[c][0] @ oracle.rbd_exp6(np.concatenate([np.zeros(3), 0.05 * rng.uniform(-1, 1, 3)]))[0]
+    ctx = capi.Context(dims, n, batch, 0)
+    try:
+        ctx.set_grid(grids)
+        ctx.set_robot_model(m)
+        ctx.set_contact_schedule(masks, pos, rot.reshape(n, ncon, 9) if robot == "icub" else None)
+        ctx.set_switching_transport(exact)
+        wq = np.concatenate([np.full(6, 10.0), np.full(nu, 1.0)])
+        ctx.set_configuration_cost(q_stand, np.zeros(nv), np.zeros(nu), wq, np.full(nv, 1.0), np.full(nv, 1e-3), np.full(nu, 1e-3),
+                                   10.0 * wq, np.full(nv, 1.0), q_weight_impact=wq, v_weight_impact=np.full(nv, 1.0), dv_weight_impact=np.full(nv, 1e-3))
+        ctx.set_initial_state(np.tile(np.concatenate([q_stand, np.zeros(nv)]), (batch, 1)))
+        S, K, D = Records(ctx.L, "sol"), Records(ctx.L, "kkt"), Records(ctx.L, "cdd")
+        sol = S.zeros(batch, n)
+        for b in range(batch):
+            for i in range(n):
+                q = q_stand.copy()
+                q[:7] = oracle.se3_integrate(q_stand[:7], 0.1 * rng.uniform(-1, 1, 6))
+                q[7:] += 0.2 * rng.uniform(-1, 1, nu)
+                S.f(sol[b, i], "q")[:nq] = q
+                S.f(sol[b, i], "v")[6:] = rng.uniform(-1, 1, nu)         # the base rests: v[:6] = a[:6] = 0
+                S.f(sol[b, i], "a")[6:] = 3.0 * rng.uniform(-1, 1, nu)
+                S.f(sol[b, i], "lmd")[:] = rng.uniform(-1, 1, nv)
+                S.f(sol[b, i], "gmm")[:] = rng.uniform(-1, 1, nv)
+        ctx.upload(BUF_SOL, sol)
+        ctx.contact_eval_kkt()
+        kkt0 = ctx.download_records(BUF_KKT, "kkt")
+        xi = rng.uniform(-1, 1, (batch, ns))
+        for b in range(batch):
+            S.f(sol[b, i0], "xi")[:ns] = xi[b]
+        ctx.upload(BUF_SOL, sol)
+        ctx.contact_eval_kkt()
+        kkt1, cdd1 = ctx.download_records(BUF_KKT, "kkt"), ctx.download_records(BUF_CDD, "cdd")
+        assert (ctx.status() == 0).all()
+        dt1, dt2 = grids[i0].dt, grids[i0 + 1].dt
+        worst = 0.0
+        for b in range(batch):
+            Phix, Phia = K.f(kkt1[b, i0], "Phix")[:ns], D.f(cdd1[b, i0], "Phia")[:ns]
+            assert np.isfinite(Phix).all() and np.isfinite(Phia).all() and np.abs(Phix[:, :6]).max() > 0.1
+            Pq = Phix[:, :6]
+            tol = 1e-14 * max(1.0, np.abs(Pq).max())
+            dlq = K.f(kkt1[b, i0], "lx")[:6] - K.f(kkt0[b, i0], "lx")[:6]
+            dhv = K.f(kkt1[b, i0], "hx")[nv:nv + 6] - K.f(kkt0[b, i0], "hx")[nv:nv + 6]
+            errs = [np.abs(Phix[:, nv:nv + 6] - (dt1 + dt2) * Pq).max(), np.abs(Phia[:, :6] - dt1 * dt2 * Pq).max(),
+                    np.abs(dhv - 2.0 * dlq).max() / max(1.0, np.abs(xi[b]).sum())]
+            worst = max(worst, max(errs) / tol)
+            assert max(errs) <= tol, errs
+        print("switching constraint with a resting base (%s, exact transport %s): worst error / bound %.2e" % (robot, exact, worst))
+    finally:
+        ctx.close()
