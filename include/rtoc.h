@@ -282,7 +282,16 @@ int rtoc_wrench_cone_matrix(double X, double Y, double mu, double* out);
 
 /* ---- the hot path ---------------------------------------------------------- */
 int rtoc_condense(rtoc_ctx* ctx);
+/* Qxx of every grid point is taken as symmetric, as the reference's cost and condensation leave it (to round-off).  The
+ * register-resident kernel (RTOC_OPT_BACKWARD_REGISTER, riccati_backward_rv.hpp) reads only its lower 16 x 16 tiles -- entries
+ * with floor(row / 16) >= floor(col / 16); the strictly upper tiles are never loaded -- and symmetrises P at the end of the stage
+ * (backward_riccati_recursion_factorizer.cpp:85).  The other backward kernels read Qxx whole.  The terminal Qxx is copied to P
+ * as it is. */
 int rtoc_riccati_backward(rtoc_ctx* ctx);
+/* Applies the factorisation the last backward recursion left in RTOC_BUF_RIC.  P of every grid point but the last is symmetric
+ * as every backward kernel stores it, and the one-wave kernel (2 nv + nu <= 64: riccati_forward.hpp) reads only its lower
+ * triangle, diagonal included; entries above the diagonal are not used.  The terminal P, a copy of the caller's Qxx, is read
+ * in full. */
 int rtoc_riccati_forward(rtoc_ctx* ctx);
 /* backward + forward of the whole batch; same results as the two calls in sequence. */
 int rtoc_riccati_sweep(rtoc_ctx* ctx);

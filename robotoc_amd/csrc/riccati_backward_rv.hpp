@@ -435,8 +435,8 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
     // Qxu^T of this stage -> start values of the PB^T rows (used after the factorisation, like Qxx below; loaded here, not with the
     // DMA of the record: held across the policy / switching-constraint products its registers would be spilled)
     if (!RV_DBG(4)) issue_hq(st);
-    // ---- Qxx of this stage -> accumulators of the F product (upper tiles; off-diagonal ones symmetrised,
-    //      brrf.cpp:85 folded into the start value), used two products from here ----
+    // ---- Qxx of this stage -> accumulators of the F product (upper tiles, each fed from the LOWER tile that mirrors it: Qxx is
+    //      taken as symmetric, rtoc.h; brrf.cpp:85 is the symmetrisation at the end of the stage), used two products from here ----
     d4 f[T][T];
     if (RV_DBG(0)) {
 #pragma unroll
@@ -446,8 +446,7 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
     } else {
       const double* qb_ = kr + KL.off[RTOC_KKT_QXX];
       const unsigned lic = (li < SCOL) ? li : SCOL - 1;                  // last column tile: lanes beyond the matrix read a clamped column
-      const unsigned vx = q + li * NX, vxl = q + lic * NX;               // Qxx[i][j]: i = .. + q, j = .. + li
-      const unsigned vt = li + q * NX, vtl = lic + q * NX;               // Qxx[j][i]
+      const unsigned vt = li + q * NX, vtl = lic + q * NX;               // Qxx[j][i]: i = .. + q, j = .. + li
 #pragma unroll
       for (int c = 0; c < T; ++c)
 #pragma unroll
@@ -460,16 +459,10 @@ __global__ __launch_bounds__(64, 2) void riccati_backward_rv_kernel(BwdArgs a) {
               f[c][t][r] = 0.0;
               continue;
             }
-            // transposed element Qxx[j][i]: li runs along the contiguous index (16 lanes = one 128-byte line); the direct element
-            // Qxx[i][j] puts four lanes on 32 bytes of sixteen different lines.  Diagonal tiles take the transposed one alone: their
-            // upper triangle is mirrored at the end of the stage, so which triangle of a (to round-off) symmetric Qxx feeds it is free
-            const double vt_ = rv_ld(qb_ + ((t < T - 1) ? vt : vtl) + (16 * t + (16 * c + 4 * r) * NX));
-            if (t == c) {
-              f[c][t][r] = vt_;
-            } else {
-              const double v = rv_ld(qb_ + ((t < T - 1) ? vx : vxl) + (16 * c + 4 * r + 16 * t * NX));
-              f[c][t][r] = 0.5 * (v + vt_);
-            }
+            // transposed element Qxx[j][i] alone: li runs along the contiguous index (16 lanes = one 128-byte line), where the
+            // direct element Qxx[i][j] would put four lanes on 32 bytes of sixteen different lines.  The strictly upper tiles of
+            // Qxx are never read; the diagonal tiles are read whole, and their upper triangle is mirrored at the end of the stage
+            f[c][t][r] = rv_ld(qb_ + ((t < T - 1) ? vt : vtl) + (16 * t + (16 * c + 4 * r) * NX));
           }
     }
 

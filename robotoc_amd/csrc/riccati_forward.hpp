@@ -62,6 +62,10 @@ __device__ __forceinline__ void fwd_sync() {
 // before the tail of st (K dx -> du -> Fvu du -> dx+): all instances reach that tail together, and without requests in
 // flight across it the memory system idles once per grid point.  Lanes past G * NV repeat group 0's addresses and drop
 // their sums; a column or K row past the matrix is clamped to a live one and its product is not accumulated.
+// P of a grid point i < N is taken as symmetric (every backward kernel stores it so) and read from its lower triangle: the
+// same 12 load instructions, but a lane whose row pair lies wholly above the diagonal makes no request (ANYmal: 342 of
+// 648 pairs, 5,472 of 10,368 B), and the missing products come from the mirror terms of the live pairs (see pe below).
+// The terminal P_N is a copy of the caller's Qxx_N and is read in full.
 template <int NV, int NU, int NS>
 __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel(FwdArgs a) {
   using C = FwdPairCfg<NV, NU>;
@@ -74,7 +78,9 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
   // writes lets the compiler sink the products, and with them every register the loads landed in, into it)
   __shared__ __attribute__((aligned(16))) double sPa[G + 1][NX];    // Fxx dx, partial over column group c
   __shared__ __attribute__((aligned(16))) double sPp[G + 1][NX];    // P dx, the same
-  __shared__ __attribute__((aligned(16))) double sPk[NU + 1][NVP];  // K dx, partial over row pair p
+  // partials over row pair p, one row per lane of the reduction: rows [0, NX) the mirror terms of P dx (below), rows
+  // [NX, NX + NU) K dx, the last row what is dropped
+  __shared__ __attribute__((aligned(16))) double sPk[NX + NU + 1][NVP];
   __shared__ __attribute__((aligned(16))) double sF[TF * 128];      // Fvu of the grid point, column-major
   __shared__ double sDu[NU + 8];
   __shared__ double sDt[NX];  // dtsdx of an impact grid point with sto_next, requested ahead like the other riders
@@ -137,6 +143,19 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
   auto live = [&](int t) { return NX % G == 0 || t < TX - 1 || G * t + c < NX; };
   auto koff = [&](int t) { return (NU % G == 0 || t < TK - 1 || G * t + c < NU) ? lo + t * (G * NX) : (NU - 1) * NX + 2 * p; };
   auto klive = [&](int t) { return NU % G == 0 || t < TK - 1 || G * t + c < NU; };
+  // P of a grid point i < N is symmetric as every backward kernel stores it, and only its lower triangle is requested: the
+  // lane's pair in load t is live iff it reaches the diagonal, 2p + 1 >= j with j = G t + c (ANYmal: 342 of 648 pairs).  With
+  // dd = j - 2p the pair gives P[2p][j] x[j] (dd <= 0) and P[2p+1][j] x[j] (dd <= 1) to its own rows and the mirror terms
+  // P[2p][j] x[2p] (dd < 0) + P[2p+1][j] x[2p+1] (dd < 1) to row j, a partial over p reduced like K dx.  Every term is
+  // selected, never multiplied by a mask: the upper element of a pair astride the diagonal is data this kernel does not read.
+  // The loads are raw buffer loads through one descriptor over the instance's records: a silent lane's offset lies past
+  // num_records, so the range check drops its request (no fetch, no branch, no wait between the loads) and returns zero.
+  // Lanes past G NV are silent; a column past the matrix cannot be live (2p + 1 < NX).
+  const int pe = lg ? c - 2 * p : (1 << 20);
+  constexpr unsigned P_SILENT = 0x80000000u;
+  const auto prsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(rb), 0, a.nstages * (int)RL.stride * 8, 0x00020000);
+  // row of sPk a lane sums: its own row of P dx's mirror terms, its row of K dx, or the dropped one
+  const int prow = tid < NX + NU ? tid : NX + NU;
   // Fx[r] | k[u] and s[r]: one 8-B load each
   auto vec_ptr = [&](int st) {
     return xrow ? kb + (size_t)st * KL.stride + KL.off[RTOC_KKT_FX] + tid : rb + (size_t)st * RL.stride + RL.off[RTOC_RIC_KV] + u;
@@ -223,7 +242,10 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
     // (the scheduler otherwise hoists every load of the stage to its top)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int t = 0; t < TX; ++t) fp[t] = *(const d2*)(rr + RL.off[RTOC_RIC_P] + moff(t));
+    for (int t = 0; t < TX; ++t) {
+      const unsigned vo = (pe + G * t <= 1) ? (unsigned)(lo + t * (G * NX)) * 8u : P_SILENT;
+      fp[t] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(prsrc, vo, (unsigned)(st * (int)RL.stride + (int)RL.off[RTOC_RIC_P]) * 8u, 0));
+    }
     double pk[TK];
 #pragma unroll
     for (int t = 0; t < TK; ++t) pk[t] = fk[t].x * xq.x + fk[t].y * xq.y;
@@ -233,10 +255,14 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
 #pragma unroll
     for (int t = 0; t < TX; ++t) {
       const double xt = x[t / 2][t % 2];
-      if (live(t)) {
-        q0 += fp[t].x * xt;
-        q1 += fp[t].y * xt;
-      }
+      const int dd = pe + G * t;
+      const double o0 = q0 + fp[t].x * xt, o1 = q1 + fp[t].y * xt;
+      q0 = dd <= 0 ? o0 : q0;
+      q1 = dd <= 1 ? o1 : q1;
+      const double m1 = fp[t].y * xq.y, m01 = m1 + fp[t].x * xq.x;
+      // (every lane writes its entry, zero where it has no mirror term: each [row][p] is written once per grid point; the
+      // readers of the previous grid point are past the fwd_sync that ended it)
+      sPk[lg && live(t) ? G * t + c : NX + NU][p] = dd < 0 ? m01 : (dd < 1 ? m1 : 0.0);
     }
     // ---- the Fxx loads and the two vectors of grid point st + 1, in flight across the tail of this one
     //      (st + 1 <= N: the terminal records exist, what is read there is dropped) ----
@@ -255,7 +281,7 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
       *(d2*)(&sPa[cw][2 * p]) = va;
       *(d2*)(&sPp[cw][2 * p]) = vp;
 #pragma unroll
-      for (int t = 0; t < TK; ++t) sPk[lg && klive(t) ? G * t + c : NU][p] = pk[t];
+      for (int t = 0; t < TK; ++t) sPk[lg && klive(t) ? NX + G * t + c : NX + NU][p] = pk[t];
     }
     fwd_sync<1>();
     double acc_a = sPa[0][r], acc_p = sPp[0][r];
@@ -264,13 +290,14 @@ __global__ __launch_bounds__(64, FWD_WAVES_PER_SIMD) void riccati_forward_kernel
       acc_a += sPa[cc][r];
       acc_p += sPp[cc][r];
     }
-    double kd = 0.0;
+    double kd = 0.0;   // lanes [NX, NX + NU): K dx; lanes [0, NX): the mirror terms of P dx
 #pragma unroll 3
     for (int i = 0; i < NVP / 2; ++i) {
-      const d2 w = *(const d2*)(&sPk[u][2 * i]);
+      const d2 w = *(const d2*)(&sPk[prow][2 * i]);
       kd += w.x;
       if (2 * i + 1 < NV) kd += w.y;
     }
+    acc_p += xrow ? kd : 0.0;
     if (kl && !impact) {
       double du = kd + vec;
       if (sto) {

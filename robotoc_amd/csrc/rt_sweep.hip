@@ -274,8 +274,9 @@ static int launch_forward_range(rtoc_ctx* c, int first, int end, hipStream_t str
   a.nstages = c->nstages;
   a.batch = end;
   a.first = first;
-  // (a structured-Fxx form of this kernel -- top half of Fxx not read, 15 % fewer bytes -- was measured at 1.27 vs
-  // 1.28 ms: the kernel is bound by its load queue, not by the bytes it requests; not kept)
+  // (the kernel reads P from its lower triangle.  A structured-Fxx form -- rows [0, NV) of Fxx not read but for the two corners --
+  // is not built: the bare pattern reads a matrix 11-12 % faster with the top halves silent, against 19 % for the triangle
+  // (profiles/r11_symmetric_reads.txt); the row-walk kernel's 1.27 vs 1.28 ms for that form predates the row-pair lane map)
   launch(c->ks->fwd, dim3(end - first), stream, a, ((a.nstages + 3) & ~3) * (int)sizeof(int));  // grid table in LDS
   HIP_TRY(hipGetLastError());
   return RTOC_OK;

@@ -6,7 +6,9 @@ The kernel reads every matrix of a grid point with 16-byte loads: lane l = c * N
 pair p and column group c and takes, in load t, rows 2p, 2p+1 of column G t + c.  Its partial sums go through LDS and are
 reduced in a fixed order.  This file states that algebra on flat records with explicit 64-lane arrays: the addresses of
 every load (in doubles from the field start), the lane-local sums in load order, the reduction over c (Fxx dx, P dx) and
-over p (K dx), the flat Fvu copy, and the row sums of the tail.  forward_instance() runs it over a whole grid and returns
+over p (K dx), the flat Fvu copy, and the row sums of the tail.  P of a grid point i < N is read from its lower triangle
+only (p_pair_live, sym_matvec_partials, sym_reduce_rows: own-row terms over c, mirror terms over p); the terminal P in
+full.  forward_instance() runs it over a whole grid and returns
 the direction records; tests/test_fwd_pair_model.py holds it against the oracle's forward recursion for every one-wave
 shape, trot and jump-STO grids included.
 """
@@ -97,6 +99,55 @@ def k_times_dx(m, K, dx):
     return out
 
 
+def p_pair_live(m, t):
+    """Which lanes request their pair of load t of P at a grid point i < N: the pair reaches the diagonal, 2p + 1 >= j.
+    Lanes past G NV and columns past the matrix are silent (2p + 1 < NX)."""
+    j = m.G * t + m.c
+    return m.lg & (2 * m.p + 1 >= j)
+
+
+def p_live_pairs(m):
+    """(live, all) 16-B pairs of one P: what the lower triangle takes of the full walk."""
+    return sum(int(p_pair_live(m, t).sum()) for t in range(m.TX)), m.nx * m.nv
+
+
+def sym_matvec_partials(m, P, dx):
+    """P dx from the lower triangle of a symmetric P (flat, column-major).  A live pair gives P[2p][j] x[j] (2p >= j) and
+    P[2p+1][j] x[j] to its own rows, summed over the lane's loads in order, and the mirror terms P[2p][j] x[2p] (2p > j)
+    + P[2p+1][j] x[2p+1] (2p + 1 > j) to row j: mir[j][p], a partial over p.  Silent lanes read nothing (the buffer load
+    returns zero); every term is selected, so an element above the diagonal -- the upper one of a pair astride it --
+    never enters a sum."""
+    q0 = np.zeros(64)
+    q1 = np.zeros(64)
+    mir = np.zeros((m.nx, m.nv))
+    x0, x1 = dx[2 * m.p], dx[2 * m.p + 1]
+    for t in range(m.TX):
+        j = m.G * t + m.c
+        live = p_pair_live(m, t)
+        dd = np.where(m.lg, j - 2 * m.p, 1 << 20)
+        off = np.where(live, j * m.nx + 2 * m.p, 0)
+        lo, hi = pair_load(P, off)
+        lo, hi = np.where(live, lo, 0.0), np.where(live, hi, 0.0)
+        xt = dx[np.minimum(j, m.nx - 1)]
+        q0 = np.where(dd <= 0, q0 + lo * xt, q0)
+        q1 = np.where(dd <= 1, q1 + hi * xt, q1)
+        m1 = hi * x1
+        m01 = m1 + lo * x0
+        mv = np.where(dd < 0, m01, np.where(dd < 1, m1, 0.0))
+        for l in range(m.G * m.nv):
+            if j[l] < m.nx:
+                mir[j[l], m.p[l]] = mv[l]
+    return q0, q1, mir
+
+
+def sym_reduce_rows(m, q0, q1, mir):
+    """Row sums of P dx: the own-row partials over c as reduce_rows, then the mirror partials of the row over p in order."""
+    acc = np.zeros(m.nx)
+    for p in range(m.nv):
+        acc = acc + mir[:, p]
+    return reduce_rows(m, q0, q1) + acc
+
+
 def fvu_copy(m, Fvu_field):
     """The flat 16-B copy of Fvu into LDS (an odd NV NU reads one double of the field's padding, never used)."""
     sF = np.zeros(m.TF * 128)
@@ -146,7 +197,7 @@ def forward_instance(L, grids, kkt, ric, dx0):
                     acc += fr(st, "scal")[5] * dts
                 dtsn = acc
         acc_a = reduce_rows(m, *matvec_partials(m, fk(st, "Fxx"), dx))
-        acc_p = reduce_rows(m, *matvec_partials(m, fr(st, "P"), dx))
+        acc_p = sym_reduce_rows(m, *sym_matvec_partials(m, fr(st, "P"), dx))   # i < N: the lower triangle only
         dxn = fk(st, "Fx") + acc_a
         if not impact:
             du = k_times_dx(m, fr(st, "K"), dx) + fr(st, "k")

@@ -34,7 +34,7 @@ for name, on in (("role-split", 0), ("register", 2), ("role-split", 0), ("regist
     for _ in range(5):
         ctx.riccati_backward()
     ctx.sync()
-    t = [ctx.time_phase(0, 1) for _ in range(20)]
+    t = [ctx.time_phase(0, 1) for _ in range(30)]
     bad = int((ctx.status() != 0).sum())
     res[name] = ric.clone()
     print("%-11s backward ms: min %.3f median %.3f  status!=0: %d" % (name, min(t), sorted(t)[len(t) // 2], bad), flush=True)

@@ -243,16 +243,17 @@ def stage(NV, NU, pp, sv, A, Bv, Qxx, Qxu, Quu, Fx, lx, lu, impact, sc=None, sa=
                         lup[lane, u[lane] // 4] = lu[u[lane]] - bts[u[lane]] + v[lane]   # u = 4 ks + q
     # ---- F = Qxx + A^T W (upper tiles), column NX starts from -lx and ends as w = A^T z - lx ----
     f = [[None] * T for _ in range(T)]
+    stage.qxx_loads = 0   # vector loads of Qxx per lane: one per register of an upper tile that holds rows of the matrix
     for c in range(T):
         for t in range(c, T):
             f[c][t] = z4()
             for r in range(4):
+                if 16 * c + 4 * r < NX:
+                    stage.qxx_loads += 1
                 i, j = 16 * c + 4 * r + Q, 16 * t + LI
                 ok = (i < NX) & (j < NX)
                 ii, jj = np.clip(i, 0, NX - 1), np.clip(j, 0, NX - 1)
-                v = np.where(ok, Qxx[ii, jj], 0.0)
-                if t > c:
-                    v = 0.5 * (v + np.where(ok, Qxx[jj, ii], 0.0))
+                v = np.where(ok, Qxx[jj, ii], 0.0)   # the transposed element: only the lower tiles of Qxx are read
                 if t == T - 1:
                     v = np.where((LI == SCOL) & (i < NX), -lx[ii], v)
                 f[c][t][:, r] = v
@@ -468,13 +469,18 @@ def from_tiles(pp, NX):
     return P
 
 
-def run(stages=(45, 35, 33, 20, 15), sa=True, strip4=None, verbose=True):
+def run(stages=(45, 35, 33, 20, 15), sa=True, strip4=None, verbose=True, config=None, mutate_qxx=None):
     """The stages `stages` of one ANYmal trot instance (47 grid points: 45, 20 regular, 35 an impact, 33 and 15 switching constraints
-    with 6 rows) through stage() from the oracle's value function of the grid point behind; returns {stage: {field: relative error}}."""
+    with 6 rows) through stage() from the oracle's value function of the grid point behind; returns {stage: {field: relative error}}.
+    config = (dims, grids): another grid of the same shape, stages = None: every grid point but the last.  The model carries no
+    switching-time riders: on a grid with them compare the matrix half (P, K, M) only.  mutate_qxx(Qxx) edits the copy of Qxx the
+    MODEL reads (the oracle keeps the record's)."""
     from oracle import oracle as orc
     from robotoc_amd import problems as pr
     from robotoc_amd.types import GRID_IMPACT, Records
-    dims, grids, _ = pr.config_anymal_trot()
+    dims, grids = config if config is not None else pr.config_anymal_trot()[:2]
+    if stages is None:
+        stages = tuple(range(len(grids) - 1))
     L = orc.layout(dims)
     NV, NU, NX = dims.nv, dims.nu, 2 * dims.nv
     kkt = pr.make_kkt_batch_unique(L, grids, 1, seed=3)[0]
@@ -499,7 +505,10 @@ def run(stages=(45, 35, 33, 20, 15), sa=True, strip4=None, verbose=True):
         sc = None
         if g.type != GRID_IMPACT and g.dims > 0:
             sc = (f("Phix")[:g.dims], f("Phiu")[:g.dims], f("Pres")[:g.dims])
-        out_ = stage(NV, NU, to_tiles(P1, NX), sv, f("Fxx"), f("Fvu"), f("Qxx"), f("Qxu"), f("Quu"), f("Fx"), f("lx"), f("lu"),
+        qxx = f("Qxx")
+        if mutate_qxx is not None:
+            mutate_qxx(qxx)
+        out_ = stage(NV, NU, to_tiles(P1, NX), sv, f("Fxx"), f("Fvu"), qxx, f("Qxu"), f("Quu"), f("Fx"), f("lx"), f("lu"),
                      g.type == GRID_IMPACT, sc, sa=SA, strip4=STRIP4)
         pn, svn, K, k = out_[:4]
         P = from_tiles(pn, NX)
