@@ -78,6 +78,11 @@ extern "C" {
                                      * [a I | c I] + two corners (a bound buffer rewritten behind the runtime's back,
                                      * RTOC_OPT_FXX_STRUCTURE): the instance's factorisation is not to be used; call
                                      * rtoc_check_fxx_structure (or set the option to 1) and repeat the sweep */
+#define RTOC_STAT_PARNMPC_H_NOT_SPD 0x20u /* ParNMPC backward correction: LLT(H) of a stage's (a, q, v) Hessian hit a non-positive
+                                     * pivot (llt_H_, unconstr_kkt_matrix_inverter.hxx:46-47) */
+#define RTOC_STAT_PARNMPC_S_NOT_SPD 0x40u /* ... LLT(S), S = F H^-1 F^T (llt_S_, :68-69).  With either bit set (until
+                                     * rtoc_clear_status) rtoc_parnmpc_backward_correction writes a zero direction for the
+                                     * instance and leaves its auxiliary matrices as they were; other instances are untouched */
 
 /* ---- buffers ---------------------------------------------------------------- */
 enum rtoc_buffer {

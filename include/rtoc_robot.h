@@ -363,6 +363,53 @@ int rtoc_unconstr_init_constraints(rtoc_ctx* ctx);
  * rtoc_unconstr_eval_kkt / rtoc_contact_eval_kkt ran last. */
 int rtoc_unconstr_update_solution(rtoc_ctx* ctx, double dt, double* host_kkt_error, int count);
 
+/* ---- UnconstrParNMPCSolver on the device (backward Euler + backward correction; fixed base, no contacts, nu == nv) ----
+ * rtoc_parnmpc_set_horizon: the context's records become the N stages (1 <= N <= max_stages) of UnconstrParNMPCSolver's horizon
+ * (src/solver/unconstr_parnmpc_solver.cpp:10-51) in place of a grid of rtoc_set_grid: record i is the reference's stage i at
+ * t + (i + 1) dt, EVERY record carries dynamics and constraint rows (the last one too: there is no terminal record), and
+ * (q, v) of rtoc_set_initial_state are q_prev, v_prev of stage 0.  A row is active on stage i iff its level is at most the stage
+ * number the reference creates the stage's constraint data with (i + 2, N on the last stage; parnmpc_intermediate_stage.cpp:49,
+ * parnmpc_terminal_stage.cpp:47).  Buffers hold [batch][N] records as on any grid; rtoc_set_grid ends the mode.  While it lasts,
+ * rtoc_unconstr_condense, rtoc_unconstr_expand (expandDual's / dt included), rtoc_update, rtoc_kkt_error and
+ * rtoc_integrate_solution act on all N records; every other entry point that works on a grid (the Riccati recursions, the contact
+ * path, rtoc_unconstr_eval_kkt / _update_solution, switching-time optimisation, the line search, stage dumps) refuses with
+ * RTOC_ERR_BAD_ARG.  rtoc_clone keeps the mode.
+ * RTOC_ERR_BAD_ARG on a shape without the kernels (nu != nv, contacts, a free-flyer, 3 nv outside 17..32 or 2 nv > 16).
+ * rtoc_parnmpc_init_constraints: UnconstrBackwardCorrection::initConstraints (src/parnmpc/unconstr_backward_correction.cpp:74-89) --
+ * setSlackAndDual of the rows of rtoc_set_constraint_rows / rtoc_set_constraint_bounds on all N records.
+ * rtoc_parnmpc_init_backward_correction: initAuxMat (:57-71) -- every auxiliary matrix = the terminal-cost Hessian at the last
+ * stage's iterate (diag(q_weight_terminal, v_weight_terminal) of rtoc_set_configuration_cost).
+ * rtoc_parnmpc_set_aux_mat / rtoc_parnmpc_get_aux_mat: host[count <= batch][N][2nv x 2nv], column-major (tests, warm starts); the
+ * matrices are zero until one of the calls above sets them.
+ * rtoc_parnmpc_eval_kkt: ParNMPCIntermediateStage / ParNMPCTerminalStage::evalKKT of every stage up to, excluding, the
+ * condensations (src/unconstr/parnmpc_terminal_stage.cpp:84-105): the stage cost scaled by dt on every record with the terminal
+ * cost ADDED on the last (:88-93), linearizeUnconstrBackwardEuler / ...Terminal (src/dynamics/unconstr_state_equation.cpp:27-53,
+ * 65-72), linearizeUnconstrDynamics (src/dynamics/unconstr_dynamics.cpp:53-64) and, with rows, linearizeConstraints, in the record
+ * convention of rtoc_unconstr_condense.  rtoc_kkt_error then gives sqrt(sum_i data.KKTError() + kkt_residual.KKTError())
+ * (unconstr_parnmpc_solver.cpp:236-238).
+ * rtoc_parnmpc_backward_correction: coarseUpdate (without its evalKKT) and backwardCorrection (without its expansion)
+ * (unconstr_backward_correction.cpp:154-228; UnconstrSplitBackwardCorrection, unconstr_split_backward_correction.cpp:57-133;
+ * UnconstrKKTMatrixInverter::invert, unconstr_kkt_matrix_inverter.hxx:39-79) on whatever condensed records and solution are on the
+ * device: H of stage i < N - 1 takes the auxiliary matrix i + 1 the previous call left, the four passes run in the reference's
+ * order, aux_mat[i] = -K^-1[0:2nv, 0:2nv] for i > 0, and the direction goes to RTOC_BUF_DIR (dx = (dq, dv), du = da, dlmdgmm).
+ * A non-SPD H or S raises RTOC_STAT_PARNMPC_H_NOT_SPD / RTOC_STAT_PARNMPC_S_NOT_SPD on the instance (rtoc.h).
+ * rtoc_parnmpc_update_solution: UnconstrParNMPCSolver::updateSolution (unconstr_parnmpc_solver.cpp:97-119) as one launch sequence:
+ * rtoc_parnmpc_eval_kkt, the KKT error of the iterate it linearised at (host_kkt_error[count <= batch], may be NULL / 0: then no
+ * host synchronisation), condenseSlackAndDual, rtoc_unconstr_condense, the backward correction, rtoc_unconstr_expand, the
+ * fraction-to-boundary step sizes, updateSlack / updateDual, SplitSolution::integrate.
+ * Refusals of rtoc_parnmpc_eval_kkt and rtoc_parnmpc_update_solution (rtoc_parnmpc_backward_correction, which evaluates nothing,
+ * checks dt, the horizon and the solution alone): RTOC_ERR_BAD_ARG for dt <= 0, a free-flyer model or contacts, and while task-space costs, a
+ * configuration-reference table or the line search are set on the context (not part of this mode); RTOC_ERR_NOT_READY before
+ * rtoc_parnmpc_set_horizon, the model, the cost, the solution or the initial state.  A refused call launches nothing. */
+int rtoc_parnmpc_set_horizon(rtoc_ctx* ctx, int N);
+int rtoc_parnmpc_init_constraints(rtoc_ctx* ctx);
+int rtoc_parnmpc_init_backward_correction(rtoc_ctx* ctx);
+int rtoc_parnmpc_set_aux_mat(rtoc_ctx* ctx, const double* host, int count);
+int rtoc_parnmpc_get_aux_mat(rtoc_ctx* ctx, double* host, int count);
+int rtoc_parnmpc_eval_kkt(rtoc_ctx* ctx, double dt);
+int rtoc_parnmpc_backward_correction(rtoc_ctx* ctx, double dt);
+int rtoc_parnmpc_update_solution(rtoc_ctx* ctx, double dt, double* host_kkt_error, int count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,8 @@ EXPORTS = [
     "rtoc_bandwidth_probe", "rtoc_get_option",
     "rtoc_set_task_costs", "rtoc_set_grid_times", "rtoc_get_grid_times", "rtoc_set_contact_force_cost",
     "rtoc_set_configuration_ref_table", "rtoc_get_stage_costs",
+    "rtoc_parnmpc_set_horizon", "rtoc_parnmpc_init_constraints", "rtoc_parnmpc_init_backward_correction", "rtoc_parnmpc_set_aux_mat",
+    "rtoc_parnmpc_get_aux_mat", "rtoc_parnmpc_eval_kkt", "rtoc_parnmpc_backward_correction", "rtoc_parnmpc_update_solution",
 ]
 
 
@@ -181,6 +183,14 @@ def lib():
         L.rtoc_set_contact_force_cost.argtypes = [vp, vp, C.c_int]
         L.rtoc_get_stage_costs.argtypes = [vp, dp, C.c_int]
         L.rtoc_set_configuration_ref_table.argtypes = [vp, dp, C.POINTER(C.c_int), C.c_int, C.c_int]
+        L.rtoc_parnmpc_set_horizon.argtypes = [vp, C.c_int]
+        L.rtoc_parnmpc_init_constraints.argtypes = [vp]
+        L.rtoc_parnmpc_init_backward_correction.argtypes = [vp]
+        L.rtoc_parnmpc_set_aux_mat.argtypes = [vp, dp, C.c_int]
+        L.rtoc_parnmpc_get_aux_mat.argtypes = [vp, dp, C.c_int]
+        L.rtoc_parnmpc_eval_kkt.argtypes = [vp, C.c_double]
+        L.rtoc_parnmpc_backward_correction.argtypes = [vp, C.c_double]
+        L.rtoc_parnmpc_update_solution.argtypes = [vp, C.c_double, dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -693,6 +703,43 @@ class Context:
         """rtoc_unconstr_update_solution; returns the KKT error of the iterate it linearised at ([batch]) or None"""
         out = np.zeros(self.batch) if want_kkt_error else None
         _chk(lib().rtoc_unconstr_update_solution(self._h, dt, _dp(out) if want_kkt_error else None, self.batch if want_kkt_error else 0))
+        return out
+
+    # ---- UnconstrParNMPCSolver on the device (include/rtoc_robot.h) ----
+    def parnmpc_set_horizon(self, N):
+        """rtoc_parnmpc_set_horizon: the records become the N stages of a ParNMPC horizon (every one with dynamics and rows)"""
+        _chk(lib().rtoc_parnmpc_set_horizon(self._h, int(N)))
+        self.nstages = int(N)
+
+    def parnmpc_init_constraints(self):
+        _chk(lib().rtoc_parnmpc_init_constraints(self._h))
+
+    def parnmpc_init_backward_correction(self):
+        _chk(lib().rtoc_parnmpc_init_backward_correction(self._h))
+
+    def parnmpc_set_aux_mat(self, aux):
+        """aux: [batch, N, 2nv, 2nv] (symmetric; stored column-major)"""
+        nx = 2 * self.dims.nv
+        aux = np.ascontiguousarray(np.swapaxes(np.asarray(aux, dtype=np.float64).reshape(self.batch, self.nstages, nx, nx), 2, 3))
+        _chk(lib().rtoc_parnmpc_set_aux_mat(self._h, _dp(aux), self.batch))
+
+    def parnmpc_get_aux_mat(self):
+        """the auxiliary matrices [batch, N, 2nv, 2nv]"""
+        nx = 2 * self.dims.nv
+        out = np.empty((self.batch, self.nstages, nx, nx))
+        _chk(lib().rtoc_parnmpc_get_aux_mat(self._h, _dp(out), self.batch))
+        return np.ascontiguousarray(np.swapaxes(out, 2, 3))
+
+    def parnmpc_eval_kkt(self, dt):
+        _chk(lib().rtoc_parnmpc_eval_kkt(self._h, dt))
+
+    def parnmpc_backward_correction(self, dt):
+        _chk(lib().rtoc_parnmpc_backward_correction(self._h, dt))
+
+    def parnmpc_update_solution(self, dt, want_kkt_error=True):
+        """rtoc_parnmpc_update_solution; returns the KKT error of the iterate it linearised at ([batch]) or None"""
+        out = np.zeros(self.batch) if want_kkt_error else None
+        _chk(lib().rtoc_parnmpc_update_solution(self._h, dt, _dp(out) if want_kkt_error else None, self.batch if want_kkt_error else 0))
         return out
 
     def linearize_contact_dynamics(self, augment_residual=False):

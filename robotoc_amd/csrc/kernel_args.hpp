@@ -70,6 +70,7 @@ struct UdArgs {
   double* cdd;
   double* dir;
   int nstages, batch;
+  int nlin;   // records per instance with dynamics: nstages - 1, or nstages on a ParNMPC horizon (rtoc_parnmpc_set_horizon)
   double dt;
   rtoc_record_layout kl, cl, dl;
 };
@@ -144,6 +145,7 @@ struct UpdArgs {
   const rtoc_grid* grid;
   const double* steps;
   int nrows, nstages, batch;
+  int nlin;   // records per instance with rows: nstages - 1, or nstages on a ParNMPC horizon
   rtoc_record_layout nl;
 };
 
@@ -199,6 +201,21 @@ struct UrArgs {
   int nstages, batch, writeback;
   double dt;
   rtoc_record_layout kl, rl, dl;
+};
+
+// ---- parnmpc_backward_correction.hpp ----
+struct PbcArgs {
+  const double* kkt;   // condensed records of a ParNMPC horizon: [batch][nstages][kkt stride], every record a stage with dynamics
+  const double* sol;
+  double* dir;
+  double* aux;         // [batch][nstages][2nv x 2nv] auxiliary matrices, column-major (read: the previous call's; written: this call's)
+  double* snew;        // [batch][nstages][5nv] s_new in the order (lmd, gmm, a, q, v)
+  double* xres;        // [batch][nstages][2nv] x_res the last serial pass left at the stage
+  double* kinv;        // [batch][nstages][16 nv^2] K^-1[0:2nv, :] (ld 2nv), then K^-1[2nv:5nv, 3nv:5nv] (ld 3nv)
+  uint32_t* status;    // [batch]
+  int nstages, batch;
+  double dt;
+  rtoc_record_layout kl, sl, dl;
 };
 
 // ---- state_equation.hpp ----

@@ -23,6 +23,7 @@
 #include "riccati_scan.hpp"
 #include "riccati_forward.hpp"
 #include "unconstr_riccati.hpp"
+#include "parnmpc_backward_correction.hpp"
 
 namespace rtoc {
 
@@ -76,6 +77,10 @@ inline KernelSet make_set() {
     if constexpr (NV <= 8) k.ubwd = {unconstr_riccati_backward_kernel<NV>, 64, 0, 1};
     else k.ubwd = {unconstr_riccati_backward_lds_kernel<NV>, 64, 0, 1};
     k.ufwd = {unconstr_riccati_forward_kernel<NV>, 64, 0, 1};
+  }
+  if constexpr (NU == NV && NS == 0 && PbcCfg<NV>::OK) {
+    k.pcoarse = {parnmpc_coarse_kernel<NV>, 64, 0, 1};
+    k.pcorrect = {parnmpc_correct_kernel<NV>, PBC_CORRECT_NT, 0, 1};
   }
   k.ccond = {cone_condense_kernel<NV, NS>, 64, 0, 1};
   k.cexp = {cone_expand_kernel<NV, NS>, 64, 0, 1};

@@ -24,7 +24,7 @@ constexpr size_t kernel_abi_stamp() {
   size_t h = 1469598103934665603ull;
   const size_t parts[] = {sizeof(BwdArgs), sizeof(FwdArgs), sizeof(FillArgs), sizeof(UdArgs), sizeof(ConeArgs), sizeof(CondArgs),
                           sizeof(ExpArgs), sizeof(ScanArgs), sizeof(FwdScanArgs), sizeof(UrArgs), sizeof(StoScanArgs),
-                          sizeof(Kern<BwdArgs>)};
+                          sizeof(PbcArgs), sizeof(Kern<BwdArgs>)};
   for (size_t v : parts) h = (h ^ v) * 1099511628211ull;
   return h;
 }
@@ -64,6 +64,7 @@ struct KernelSet : ShapeInfo {
   Kern<ScanArgs> scan_elt, scan_comb;                  // horizon scan of the backward recursion (riccati_scan.hpp)
   Kern<FwdScanArgs> fscan_elt, fscan_comb, fscan_fin;  // forward recursion as a prefix scan
   Kern<StoScanArgs> sto_prep, sto_vec;                 // scan on grids with switching-time optimisation (riccati_scan_sto.hpp)
+  Kern<PbcArgs> pcoarse, pcorrect;  // ParNMPC backward correction (parnmpc_backward_correction.hpp); null unless nu == nv, ns == 0, 16 < 3nv <= 32, 2nv <= 16
 };
 
 // f(descriptor) for every kernel of the set, null ones included
@@ -75,6 +76,7 @@ constexpr void for_each_kernel(Set& k, F&& f) {
   f(k.ccond), f(k.cexp), f(k.wcond), f(k.wexp);
   f(k.cond), f(k.cond_split), f(k.mjt), f(k.cond_rv), f(k.cond_rv_nc), f(k.expd);
   f(k.scan_elt), f(k.scan_comb), f(k.fscan_elt), f(k.fscan_comb), f(k.fscan_fin), f(k.sto_prep), f(k.sto_vec);
+  f(k.pcoarse), f(k.pcorrect);
 }
 constexpr size_t kernels_visited() {
   KernelSet k{};

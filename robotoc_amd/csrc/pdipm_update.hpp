@@ -10,7 +10,7 @@ namespace rtoc {
 // updateSlack / updateDual (constraints_impl.hxx:167-182) with the per-instance step sizes
 static __global__ __launch_bounds__(64) void pdipm_update_kernel(UpdArgs a) {
   const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.nlin;
   const int b = item / nst1, st = item % nst1;
   if (b >= a.batch) return;
   const rtoc_grid g = a.grid[st];

@@ -38,8 +38,11 @@ struct RecView {
   const double* dt_inst;      // per-instance time steps or nullptr (grid_dt)
   const rbd::DevModel* model;
   int nstages, batch;
+  int all_stages;             // 1: the records are the stages of a ParNMPC horizon (rtoc_parnmpc_set_horizon), none of them terminal
   rtoc_layout L;
 
+  // records per instance that carry dynamics and constraint rows: all but the terminal one, or every stage of a ParNMPC horizon
+  RTOC_HD int nlin() const { return nstages - 1 + all_stages; }
   RTOC_HD int nv() const { return L.dims.nv; }
   RTOC_HD int nu() const { return L.dims.nu; }
   RTOC_HD int floating() const { return L.dims.np == 6; }

@@ -74,7 +74,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];   // [G][njoints][64]
   const int lane = threadIdx.x, GS = a.md.gs, G = 64 / GS, nb = a.md.njoints, ncon = a.md.ncontacts;
   const int grp = lane / GS, i = lane % GS;
-  const int nst1 = a.nsel > 0 ? a.nsel : a.rv.nstages - 1;   // grid points per instance this launch covers
+  const int nst1 = a.nsel > 0 ? a.nsel : a.rv.nlin();   // grid points per instance this launch covers
   const long long item = (long long)blockIdx.x * G + grp, nitems = (long long)a.rv.batch * nst1;
   const bool gvalid = item < nitems;
   const int b = gvalid ? (int)(item / nst1) : 0;
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
-  const int nst1 = a.rv.nstages - 1;
+  const int nst1 = a.rv.nlin();
   const int b = item / nst1, st = item % nst1;
   if (b >= a.rv.batch) return;
   const int nlev = a.md.nlevels, nv = a.rv.nv(), nb = a.md.njoints, ncon = a.md.ncontacts;

@@ -219,7 +219,7 @@ int rtoc_expand(rtoc_ctx* c, double tau) {
 }
 
 int rtoc_update(rtoc_ctx* c) {
-  CHECK_READY(c);
+  CHECK_STAGES(c);
   if (c->cone_contacts > 0) {
     int rc = launch_cones(c, 2, 0.0);
     if (rc) return rc;
@@ -233,8 +233,9 @@ int rtoc_update(rtoc_ctx* c) {
   a.nrows = c->nrows;
   a.nstages = c->nstages;
   a.batch = c->batch;
+  a.nlin = dynamics_records(c);
   a.nl = c->L.con;
-  hipLaunchKernelGGL(pdipm_update_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
+  hipLaunchKernelGGL(pdipm_update_kernel, dim3(c->batch * a.nlin), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }

@@ -35,7 +35,13 @@
 
 #define CHECK_READY(c)                       \
   if (!(c)) return RTOC_ERR_BAD_ARG;         \
+  if ((c)->parnmpc) return RTOC_ERR_BAD_ARG; /* a ParNMPC horizon (no terminal record): CHECK_STAGES, rt_parnmpc.hip */ \
   if ((c)->nstages < 2) return RTOC_ERR_NOT_READY; \
+  HIP_TRY(hipSetDevice((c)->device));
+// ... of the few entry points that serve a grid of rtoc_set_grid and the N stages of rtoc_parnmpc_set_horizon alike
+#define CHECK_STAGES(c)                      \
+  if (!(c)) return RTOC_ERR_BAD_ARG;         \
+  if ((c)->nstages < ((c)->parnmpc ? 1 : 2)) return RTOC_ERR_NOT_READY; \
   HIP_TRY(hipSetDevice((c)->device));
 
 #define RTOC_MAX_CHUNK_EVENTS 16
@@ -287,10 +293,27 @@ struct LineSearchState {
   int ls_trials = 0;           // trial evaluations of the last line search
 };
 
+// ParNMPC (rtoc_parnmpc_set_horizon; parnmpc_backward_correction.hpp; rt_parnmpc.hip).  parnmpc: the context's records are the N
+// stages of a ParNMPC horizon -- every one carries dynamics and rows, none is terminal; 0 again after rtoc_set_grid
+struct ParnmpcState {
+  int parnmpc = 0;
+  DevBuf<double> d_aux;    // [batch][max_stages][2nv x 2nv] auxiliary matrices (in use: [batch][nstages])
+  DevBuf<double> d_snew;   // [batch][max_stages][5nv] s_new
+  DevBuf<double> d_xres;   // [batch][max_stages][2nv] x_res
+  DevBuf<double> d_kinv;   // [batch][max_stages][16 nv^2] the blocks of K^-1 the correction passes read
+  void clone_from(const ParnmpcState& src, CopyChain& dup) {
+    parnmpc = src.parnmpc;
+    dup(d_aux, src.d_aux);
+    dup(d_snew, src.d_snew);
+    dup(d_xres, src.d_xres);
+    dup(d_kinv, src.d_kinv);
+  }
+};
+
 }  // namespace rtoc
 
 struct rtoc_ctx : rtoc::CtxStreams, rtoc::CtxOptions, rtoc::SweepState, rtoc::ConstraintState, rtoc::ModelState, rtoc::TaskState,
-                  rtoc::StoState, rtoc::LineSearchState {
+                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState {
   rtoc_dims dims = {};
   rtoc_layout L = {};
   const rtoc::KernelSet* ks = nullptr;
@@ -394,6 +417,15 @@ void launch_fill_steps(rtoc_ctx* c);
 // rt_eval_kkt.hip
 hipError_t reserve_kkterr(rtoc_ctx* c);
 int launch_kkt_error(rtoc_ctx* c);
+// records per instance that carry dynamics and rows: all but the terminal one, or all of a ParNMPC horizon
+static inline int dynamics_records(const rtoc_ctx* c) { return c->nstages - 1 + (c->parnmpc ? 1 : 0); }
+// the unconstrained path's pieces rt_parnmpc.hip strings together: the all-zero contact schedule, linearizeUnconstrDynamics with
+// its dt-scaled multiplier terms, one phase of the joint-limit rows (unconstr_constraints.hpp: UBOX_*)
+enum UnconstrRowsPhase { ROWS_INIT = 0, ROWS_LINEARIZE = 1, ROWS_CONDENSE = 2, ROWS_EXPAND = 3 };
+int reserve_empty_schedule(rtoc_ctx* c);
+int launch_unconstr_linearize(rtoc_ctx* c, double dt);
+bool unconstr_rows_on(const rtoc_ctx* c);
+int launch_unconstr_rows(rtoc_ctx* c, UnconstrRowsPhase phase);
 // rt_task_costs.hip
 int ensure_grid_times_inst(rtoc_ctx* c);
 int task_costs_ready(rtoc_ctx* c, bool unconstr);

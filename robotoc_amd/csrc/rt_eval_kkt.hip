@@ -82,7 +82,7 @@ hipError_t rtoc::reserve_kkterr(rtoc_ctx* c) { return c->d_kkterr.reserve((size_
 
 // ---- SplitSolution::integrate ---------------------------------------------------------------
 int rtoc_integrate_solution(rtoc_ctx* c) {
-  CHECK_READY(c);
+  CHECK_STAGES(c);
   if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   IntArgs a;
   a.sol = c->buf[RTOC_BUF_SOL].p;
@@ -229,7 +229,7 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   if (!c->h_model || !c->d_active.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  if (c->nstages < 2) return RTOC_OK;
+  if (dynamics_records(c) < 1) return RTOC_OK;
   const bool any_impact = any_grid_point(c, c->nstages - 1, grid_is_impact);
   rc = ensure_rbd_values(c);
   if (rc) return rc;
@@ -237,7 +237,7 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   v.rv = view(c), v.md = model_dims(c);
   v.unconstr = unconstr ? 1 : 0;
   const int G = 64 / v.md.gs;
-  const long long items = (long long)c->batch * (c->nstages - 1);
+  const long long items = (long long)c->batch * dynamics_records(c);
   const size_t vlds = sizeof(double) * G * v.md.njoints * rbd::VAL_SLOTS;
   for (int trav = 0; trav < (any_impact ? 2 : 1); ++trav) {
     v.trav = trav;
@@ -262,7 +262,8 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
   if (!augment_residual) a.rv.kkt = nullptr;
   a.unconstr = unconstr ? 1 : 0;
   a.scale = scale;
-  if (c->nstages < 2) return RTOC_OK;
+  const int nlin = dynamics_records(c);
+  if (nlin < 1) return RTOC_OK;
   const size_t lds = rbd::lin_lds_bytes(c->h_model->nlevels, c->h_model->nbranch, c->h_model->m.njoints, c->h_model->m.ncontacts, c->h_model->m.nv, c->h_model->dpp, !c->linearize_fused);
   const bool surf = model_has_surface_contacts(c->h_model->m);
   a.vals = a.vals2 = nullptr;
@@ -275,13 +276,13 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
     c->vals_fresh = 0;
     a.vals = c->d_vals.p, a.vals2 = c->d_vals2.p;
     if (surf)
-      hipLaunchKernelGGL((rbd::linearize_contact_dynamics_kernel<true, true>), dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
+      hipLaunchKernelGGL((rbd::linearize_contact_dynamics_kernel<true, true>), dim3(c->batch * nlin), dim3(64), lds, c->stream, a);
     else
-      hipLaunchKernelGGL((rbd::linearize_contact_dynamics_kernel<false, true>), dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
+      hipLaunchKernelGGL((rbd::linearize_contact_dynamics_kernel<false, true>), dim3(c->batch * nlin), dim3(64), lds, c->stream, a);
   } else if (surf) {
-    hipLaunchKernelGGL(rbd::linearize_contact_dynamics_kernel<true>, dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
+    hipLaunchKernelGGL(rbd::linearize_contact_dynamics_kernel<true>, dim3(c->batch * nlin), dim3(64), lds, c->stream, a);
   } else {
-    hipLaunchKernelGGL(rbd::linearize_contact_dynamics_kernel<false>, dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
+    hipLaunchKernelGGL(rbd::linearize_contact_dynamics_kernel<false>, dim3(c->batch * nlin), dim3(64), lds, c->stream, a);
   }
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -421,11 +422,23 @@ static int launch_ubox(rtoc_ctx* c, int mode, bool contact = false) {
   a.barrier = c->barrier, a.tau = c->ftb_rule;
   a.contact = contact ? 1 : 0;
   a.q_shift = (contact && c->dims.np == 6) ? 1 : 0;
-  hipLaunchKernelGGL(unconstr_box_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
+  hipLaunchKernelGGL(unconstr_box_kernel, dim3(c->batch * dynamics_records(c)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
 static bool ubox_on(const rtoc_ctx* c) { return c->nrows > 0 && c->d_bounds.p != nullptr; }
+// ... for rt_parnmpc.hip, which runs the same rows and the same dynamics on every stage of its horizon
+static_assert(ROWS_INIT == UBOX_INIT && ROWS_LINEARIZE == UBOX_LINEARIZE && ROWS_CONDENSE == UBOX_CONDENSE && ROWS_EXPAND == UBOX_EXPAND,
+              "UnconstrRowsPhase (rt_context.hpp) names the modes of unconstr_box_kernel");
+bool rtoc::unconstr_rows_on(const rtoc_ctx* c) { return ubox_on(c); }
+int rtoc::launch_unconstr_rows(rtoc_ctx* c, UnconstrRowsPhase phase) { return launch_ubox(c, (int)phase); }
+int rtoc::launch_unconstr_linearize(rtoc_ctx* c, double dt) { return launch_linearize(c, 1, true, dt); }
+int rtoc::reserve_empty_schedule(rtoc_ctx* c) {
+  bool fresh = false;
+  HIP_TRY(reserve_active(c, &fresh));
+  if (fresh) HIP_TRY(hipMemsetAsync(c->d_active.p, 0, sizeof(unsigned) * c->max_stages, c->stream));  // no contacts: an all-zero schedule
+  return RTOC_OK;
+}
 
 // UnconstrOCPSolver::initConstraints (unconstr_ocp_solver.cpp:91-93): setSlackAndDual of every row at the current iterate
 int rtoc_unconstr_init_constraints(rtoc_ctx* c) {
@@ -508,7 +521,7 @@ int rtoc::launch_kkt_error(rtoc_ctx* c) {
 }
 
 int rtoc_kkt_error(rtoc_ctx* c, double* host_out, int count) {
-  CHECK_READY(c);
+  CHECK_STAGES(c);
   if (!host_out || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
   int rc = launch_kkt_error(c);
   if (rc) return rc;

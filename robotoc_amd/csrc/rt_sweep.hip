@@ -393,22 +393,23 @@ static int launch_unconstr_dynamics(rtoc_ctx* c, bool expand, double dt) {
   a.dir = c->buf[RTOC_BUF_DIR].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
+  a.nlin = dynamics_records(c);
   a.dt = dt;
   a.kl = c->L.kkt;
   a.cl = c->L.cdd;
   a.dl = c->L.dir;
-  launch(expand ? c->ks->uexp : c->ks->ucond, dim3(c->batch * (c->nstages - 1)), c->stream, a);
+  launch(expand ? c->ks->uexp : c->ks->ucond, dim3(c->batch * a.nlin), c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }
 
 int rtoc_unconstr_condense(rtoc_ctx* c) {
-  CHECK_READY(c);
+  CHECK_STAGES(c);
   return launch_unconstr_dynamics(c, false, 1.0);
 }
 
 int rtoc_unconstr_expand(rtoc_ctx* c, double dt) {
-  CHECK_READY(c);
+  CHECK_STAGES(c);
   if (!(dt > 0.0)) return RTOC_ERR_BAD_ARG;
   return launch_unconstr_dynamics(c, true, dt);
 }

@@ -212,7 +212,8 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
   rtoc_ctx* n = nullptr;
   int rc = rtoc_create(&c->dims, c->max_stages, c->batch, c->device, &n);
   if (rc) return rc;
-  if (c->nstages >= 2 && !c->h_grid.empty()) rc = rtoc_set_grid(n, c->h_grid.data(), c->nstages);
+  if (c->parnmpc) rc = rtoc_parnmpc_set_horizon(n, c->nstages);
+  else if (c->nstages >= 2 && !c->h_grid.empty()) rc = rtoc_set_grid(n, c->h_grid.data(), c->nstages);
   if (!rc && c->nrows > 0 && !c->h_rows.empty()) rc = rtoc_set_constraint_rows(n, c->h_rows.data(), c->nrows);
   if (!rc && c->cone_contacts > 0)
     rc = c->cone_rows == RTOC_WRENCH_ROWS ? rtoc_set_wrench_cones(n, c->cone_contacts)
@@ -229,6 +230,7 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
     n->LineSearchState::clone_from(*c, dup);
     n->StoState::clone_from(*c, dup);
     n->TaskState::clone_from(*c, dup);
+    n->ParnmpcState::clone_from(*c, dup);
     n->clone_records(*c, dup);
     if (dup.e == hipSuccess) dup.e = hipStreamSynchronize(n->stream);
   }
@@ -275,6 +277,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->h_grid.assign(grid, grid + nstages);
   c->nstages = nstages;
+  c->parnmpc = 0;   // a grid with a terminal point: no longer the stages of rtoc_parnmpc_set_horizon
   c->fxx_state = 0;
   c->epoch++;
   if (c->sto_on) {  // the event times on the device belong to the previous grid structure unless the events are the same
@@ -452,6 +455,7 @@ RecView rtoc::view(const rtoc_ctx* c) {
   v.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   v.model = c->d_model.p;
   v.nstages = c->nstages, v.batch = c->batch;
+  v.all_stages = c->parnmpc ? 1 : 0;
   v.L = c->L;
   return v;
 }

@@ -36,8 +36,8 @@ enum { UBOX_INIT = 0, UBOX_LINEARIZE = 1, UBOX_CONDENSE = 2, UBOX_EXPAND = 3 };
 
 static __global__ __launch_bounds__(64) void unconstr_box_kernel(UboxArgs a) {
   const int lane = threadIdx.x;
-  const int nst1 = a.rv.nstages - 1;
-  const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;  // the terminal grid point has no rows
+  const int nst1 = a.rv.nlin();
+  const int b = blockIdx.x / nst1, st = blockIdx.x % nst1;  // the terminal grid point has no rows (a ParNMPC horizon has none)
   if (b >= a.rv.batch) return;
   const rtoc_grid g = a.rv.grid[st];
   const size_t rec = (size_t)b * a.rv.nstages + st;

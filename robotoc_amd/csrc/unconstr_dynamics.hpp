@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64) void unconstr_condense_kernel(UdArgs a) {
   constexpr int NX = 2 * NV;
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;  // the terminal stage has no dynamics
+  const int nst1 = a.nlin;  // the terminal stage has no dynamics (a ParNMPC horizon has no terminal stage)
   const int b = item / nst1, st = item % nst1;
   if (b >= a.batch) return;
   double* kr = a.kkt + ((size_t)b * a.nstages + st) * a.kl.stride;
@@ -91,7 +91,7 @@ template <int NV>
 __global__ __launch_bounds__(64) void unconstr_expand_kernel(UdArgs a) {
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
-  const int nst1 = a.nstages - 1;
+  const int nst1 = a.nlin;
   const int b = item / nst1, st = item % nst1;
   if (b >= a.batch) return;
   const double* cr = a.cdd + ((size_t)b * a.nstages + st) * a.cl.stride;

@@ -1,0 +1,162 @@
+"""rtoc_parnmpc_backward_correction (robotoc_amd/csrc/parnmpc_backward_correction.hpp) on uploaded synthetic records: random SPD
+H blocks with another scale on every stage, random residuals, random SPD auxiliary matrices, a random solution.
+(a) N = 1: the direction is the dense solve of the one saddle system -- independent of the restatement.
+(b) N in {2, 5}: direction and updated auxiliary matrices against tests/parnmpc_restatement.py, after one call and after two (the
+    second call's H takes the first call's auxiliary matrices: a wrong lag shows here).
+(c) an indefinite Qaa in one instance of three: its status bit, the others as in (b) with status 0.
+(d) nv = 8 through the plug-in shape of the arm tests.
+Tolerance of a case: max(100 e_ref, 1e-12) on the max-norm difference scaled by max(1, |expected|_inf), e_ref the restated
+inverter's own error on that case's matrices (tests/test_parnmpc_restatement.py: reference_error); the factor 100 covers another
+summation order and Cholesky against LU."""
+import numpy as np
+import pytest
+
+import parnmpc_restatement as pn
+from robotoc_amd.types import BUF_DIR, BUF_KKT, BUF_SOL, Dims, Records
+from test_parnmpc_restatement import random_spd, reference_error
+
+pytestmark = pytest.mark.gpu
+
+STAT_PARNMPC_H_NOT_SPD, STAT_PARNMPC_S_NOT_SPD = 0x20, 0x40
+DT = 0.05
+
+
+@pytest.fixture(scope="module")
+def capi8():
+    from robotoc_amd import capi
+    capi.build_plugin(8, 8, 0)
+    return capi
+
+
+def _case(nv, batch, N, seed):
+    """per instance: the condensed records of pn.backward_correction, the solution [N, 5nv], the auxiliary matrices [N, 2nv, 2nv]"""
+    rng = np.random.default_rng(seed)
+    recs, sols, auxs = [], [], []
+    for b in range(batch):
+        rb = []
+        for i in range(N):
+            H = random_spd(rng, 3 * nv, cond=10.0 ** rng.uniform(0.5, 2.0), scale=10.0 ** rng.uniform(-1.0, 1.0))
+            r = rng.standard_normal(5 * nv)
+            rb.append(dict(Qaa=H[:nv, :nv].copy(), Qxa=H[nv:, :nv].copy(), Qxx=H[nv:, nv:].copy(), Fx=r[:2 * nv], la=r[2 * nv:3 * nv], lx=r[3 * nv:]))
+        recs.append(rb)
+        sols.append(rng.standard_normal((N, 5 * nv)))
+        auxs.append(np.array([random_spd(rng, 2 * nv, cond=10.0 ** rng.uniform(0.0, 1.5), scale=10.0 ** rng.uniform(-1.0, 0.5)) for _ in range(N)]))
+    return recs, np.array(sols), np.array(auxs)
+
+
+def _context(capi, nv, batch, N, recs, sols, auxs):
+    dims = Dims(nv, nv, 0, 0, 0, 0)
+    ctx = capi.Context(dims, max(N, 2), batch, 0)
+    ctx.parnmpc_set_horizon(N)
+    K, S = Records(ctx.L, "kkt"), Records(ctx.L, "sol")
+    kkt, sol = K.zeros(batch, N), S.zeros(batch, N)
+    for b in range(batch):
+        for i in range(N):
+            r = recs[b][i]
+            K.f(kkt[b, i], "Quu")[...] = r["Qaa"]
+            K.f(kkt[b, i], "Qxu")[...] = r["Qxa"]
+            K.f(kkt[b, i], "Qxx")[...] = r["Qxx"]
+            K.f(kkt[b, i], "Fx")[...] = r["Fx"]
+            K.f(kkt[b, i], "lu")[...] = r["la"]
+            K.f(kkt[b, i], "lx")[...] = r["lx"]
+            for k, name in enumerate(pn.FIELDS):
+                S.f(sol[b, i], name)[:nv] = sols[b, i, k * nv:(k + 1) * nv]
+    ctx.upload(BUF_KKT, kkt)
+    ctx.upload(BUF_SOL, sol)
+    ctx.parnmpc_set_aux_mat(auxs)
+    return ctx
+
+
+def _direction(ctx, nv):
+    """[batch, N, 5nv] in the order (dlmd, dgmm, da, dq, dv)"""
+    D = Records(ctx.L, "dir")
+    d = ctx.download_records(BUF_DIR, "dir")
+    return np.concatenate([D.f(d, "dlmdgmm")[..., :2 * nv], D.f(d, "du")[..., :nv], D.f(d, "dx")[..., :2 * nv]], axis=-1)
+
+
+def _e_ref(recs_b, aux_b):
+    N = len(recs_b)
+    e = 0.0
+    for i in range(N):
+        H = pn.assemble_H(recs_b[i], aux_b[i + 1] if i < N - 1 else None)
+        r = np.concatenate([recs_b[i]["Fx"], recs_b[i]["la"], recs_b[i]["lx"]])
+        e = max(e, reference_error(DT, H, r)[0])
+    return e
+
+
+def _scaled(got, exp):
+    return np.abs(got - exp).max() / max(1.0, np.abs(exp).max())
+
+
+def _check_against_restatement(ctx, nv, recs, sols, auxs, instances, label):
+    """two calls against two restated iterations; returns the worst observed / tolerance"""
+    worst = 0.0
+    aux_ref = [auxs[b] for b in range(len(recs))]
+    for call in range(2):
+        ctx.parnmpc_backward_correction(DT)
+        d, aux = _direction(ctx, nv), ctx.parnmpc_get_aux_mat()
+        for b in instances:
+            tol = max(100.0 * _e_ref(recs[b], aux_ref[b]), 1e-12)
+            d_ref, aux_new, _ = pn.backward_correction(DT, recs[b], sols[b], aux_ref[b])
+            e_d, e_a = _scaled(d[b], d_ref), _scaled(aux[b], aux_new)
+            print("%s call %d inst %d: direction %.2e aux %.2e tolerance %.2e (observed / tolerance %.3f)" % (label, call, b, e_d, e_a, tol, max(e_d, e_a) / tol))
+            worst = max(worst, max(e_d, e_a) / tol)
+            assert e_d <= tol and e_a <= tol, (label, call, b, e_d, e_a, tol)
+            aux_ref[b] = aux_new
+    return worst
+
+
+def test_single_stage_is_the_dense_saddle_solve():
+    from robotoc_amd import capi
+    nv, batch, N = 7, 3, 1
+    recs, sols, auxs = _case(nv, batch, N, seed=11)
+    ctx = _context(capi, nv, batch, N, recs, sols, auxs)
+    ctx.parnmpc_backward_correction(DT)
+    d = _direction(ctx, nv)
+    for b in range(batch):
+        H = pn.assemble_H(recs[b][0])
+        r = np.concatenate([recs[b][0]["Fx"], recs[b][0]["la"], recs[b][0]["lx"]])
+        x = -np.linalg.solve(pn.saddle_matrix(H, DT), r)
+        tol = max(100.0 * reference_error(DT, H, r)[0], 1e-12)
+        e = _scaled(d[b, 0], x)
+        print("N = 1 inst %d: %.2e / %.2e" % (b, e, tol))
+        assert e <= tol
+    assert (ctx.parnmpc_get_aux_mat() == auxs).all()   # no stage i > 0: nothing is written
+    assert (ctx.status() == 0).all()
+    ctx.close()
+
+
+@pytest.mark.parametrize("N", [2, 5])
+def test_direction_and_aux_matrices_match_the_restatement(N):
+    from robotoc_amd import capi
+    nv, batch = 7, 3
+    recs, sols, auxs = _case(nv, batch, N, seed=20 + N)
+    ctx = _context(capi, nv, batch, N, recs, sols, auxs)
+    worst = _check_against_restatement(ctx, nv, recs, sols, auxs, range(batch), "N = %d" % N)
+    assert (ctx.status() == 0).all()
+    print("worst observed / tolerance:", worst)
+    ctx.close()
+
+
+def test_indefinite_hessian_flags_its_instance_and_no_other():
+    from robotoc_amd import capi
+    nv, batch, N = 7, 3, 5
+    recs, sols, auxs = _case(nv, batch, N, seed=31)
+    recs[1][2]["Qaa"] = -np.eye(nv)
+    ctx = _context(capi, nv, batch, N, recs, sols, auxs)
+    _check_against_restatement(ctx, nv, recs, sols, auxs, [0, 2], "isolation")
+    st = ctx.status()
+    assert st[1] & STAT_PARNMPC_H_NOT_SPD and st[0] == 0 and st[2] == 0, st
+    assert np.isfinite(_direction(ctx, nv)[1]).all() and (_direction(ctx, nv)[1] == 0).all()   # the failed instance: no step
+    assert (ctx.parnmpc_get_aux_mat()[1] == auxs[1]).all()                                       # and its aux matrices as they were
+    ctx.close()
+
+
+def test_eight_joint_plugin_shape(capi8):
+    nv, batch, N = 8, 2, 2
+    recs, sols, auxs = _case(nv, batch, N, seed=41)
+    ctx = _context(capi8, nv, batch, N, recs, sols, auxs)
+    worst = _check_against_restatement(ctx, nv, recs, sols, auxs, range(batch), "nv = 8")
+    assert (ctx.status() == 0).all()
+    print("worst observed / tolerance:", worst)
+    ctx.close()
