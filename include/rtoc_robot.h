@@ -260,6 +260,47 @@ typedef struct rtoc_solve_stats {
 } rtoc_solve_stats;
 int rtoc_solve_loop(const rtoc_solve_options* options, const rtoc_solve_callbacks* callbacks, rtoc_solve_stats* stats);
 
+/* ---- SolutionInterpolator on the device (src/solver/solution_interpolator.cpp:22-230): the warm start of a re-discretised grid ----
+ * What OCPSolver::solve does around a re-discretisation -- store (:22-27), discretize, interpolate (:30-113) -- in the mesh-refinement
+ * branch (ocp_solver.cpp:184-199) and for the receding-horizon warm start of every solve(t, q, v, init_solver = true) (:159-163,
+ * :215-220), for every instance of the batch at once and without the records leaving the device.
+ * rtoc_solution_store(ctx, t0): copies into memory of the context RTOC_BUF_SOL ([batch][nstages] records), the grid's types and time
+ * steps, the masks of rtoc_set_contact_schedule and the grid times t[0] = t0, t[i + 1] = t[i] + dt[i] (summed in this order, in
+ * double).  With an STO problem set (rtoc_sto_set_problem) the time steps and hence the times are every instance's own, as the device
+ * holds them: call rtoc_sto_correct_time_steps first, like ocp_solver.cpp:186-189 and :216-219; without one they are the grid's and
+ * shared by the batch.  A copy, not a view: rtoc_set_grid, rtoc_set_contact_schedule and rtoc_sto_set_problem come between the store
+ * and the interpolation, and the store survives them.  A second store replaces the first.
+ * rtoc_solution_interpolate(ctx, t0): writes EVERY double of every record of RTOC_BUF_SOL for the current grid, schedule and time
+ * steps (times from t0 by the same sum) from the store, one wave per (instance, grid point).  Per new grid point at time t (:33-110):
+ * t at or before the first stored time: stored record 0; at or behind the last: the last stored record; an impact / lift with a stored
+ * event of the same type within 1e-9: that record (:59-72), at an impact with u, the a | dv slot and nu_passive zeroed
+ * (modifyImpactSolution, :201-208) and xi of the new grid point two BEFORE it taken from the stored record two before the stored
+ * impact; an impact / lift without one: initEventSolution (:175-198) between the stored neighbours, or interpolatePartial
+ * (:149-172; plus the impact zeroing) when the later neighbour is the stored terminal point; every other grid point: interpolate
+ * (:119-146) when the later neighbour is an intermediate point, interpolatePartial otherwise; on the last record
+ * modifyTerminalSolution (:211-224).  The earlier neighbour is findStoredGridIndexBeforeTime's, stepped back over stored points
+ * whose dt <= 0 (an impact has no extent in time); alpha = (t - t_a) / dt_a clamped to [0, 1].  The f / mu stacks are compacted by
+ * the active contacts of their own grid point: each is expanded by the stored mask and re-packed by the new grid point's, 3 or 6
+ * rows per contact; stack entries beyond the packed rows, xi of a blended grid point and the padding of a blended record are zero.
+ * q follows Robot::interpolateConfiguration: joints linearly, a free-flyer base along the screw motion q1 (+) alpha (q2 (-) q1), the
+ * quaternion that of the rotation matrix (w > 0 where its trace is positive), normalised.
+ * Not the reference's: at a COPIED impact the a | dv slot is zeroed like at a blended one (the host mirrors do; the reference keeps
+ * dv there) -- INTEGRATION.md.  InterpolationOrder::Zero is not implemented.
+ * With nothing stored rtoc_solution_interpolate returns RTOC_OK and writes nothing (:34) -- in a context it would not refuse: the
+ * refusals come first.  Both calls refuse ahead of their first launch, and a refused call writes nothing: RTOC_ERR_NOT_READY
+ * without a grid, without RTOC_BUF_SOL (store), in a context with dims.nf_max > 0 without rtoc_set_robot_model (the rows per
+ * contact come from its contact_type) or without a contact schedule set since rtoc_set_grid last changed the grid (the masks
+ * belong to a grid; shapes without contact rows need neither), and with an STO problem whose time steps date from before that
+ * (rtoc_sto_set_problem or rtoc_sto_correct_time_steps again; setting the grid in force again changes nothing);
+ * RTOC_ERR_BAD_ARG on a ParNMPC horizon (rtoc_parnmpc_set_horizon), for a non-finite t0, and for a store whose contacts are not
+ * those of the model now set.  Both are asynchronous on the context's stream.
+ * rtoc_solution_stored: *nstages = the grid points of the stored solution, 0 if none.  rtoc_solution_forget: nothing is stored any
+ * more.  rtoc_clone copies the store. */
+int rtoc_solution_store(rtoc_ctx* ctx, double t0);
+int rtoc_solution_interpolate(rtoc_ctx* ctx, double t0);
+int rtoc_solution_stored(const rtoc_ctx* ctx, int* nstages);
+int rtoc_solution_forget(rtoc_ctx* ctx);
+
 /* ---- filter line search on the device (src/line_search/line_search.cpp:31-83, LineSearchSettings) ----
  * rtoc_contact_eval_ocp: DirectMultipleShooting::evalOCP's performance index (direct_multiple_shooting.cpp:100-126) of every
  * instance -- host_cost[count] = cost + cost_barrier, host_violation[count] = primal_feasibility (l1).  trial = 0: of the iterate

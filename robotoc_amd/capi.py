@@ -40,6 +40,7 @@ EXPORTS = [
     "rtoc_set_configuration_ref_table", "rtoc_get_stage_costs",
     "rtoc_parnmpc_set_horizon", "rtoc_parnmpc_init_constraints", "rtoc_parnmpc_init_backward_correction", "rtoc_parnmpc_set_aux_mat",
     "rtoc_parnmpc_get_aux_mat", "rtoc_parnmpc_eval_kkt", "rtoc_parnmpc_backward_correction", "rtoc_parnmpc_update_solution",
+    "rtoc_solution_store", "rtoc_solution_interpolate", "rtoc_solution_stored", "rtoc_solution_forget",
 ]
 
 
@@ -191,6 +192,10 @@ def lib():
         L.rtoc_parnmpc_eval_kkt.argtypes = [vp, C.c_double]
         L.rtoc_parnmpc_backward_correction.argtypes = [vp, C.c_double]
         L.rtoc_parnmpc_update_solution.argtypes = [vp, C.c_double, dp, C.c_int]
+        L.rtoc_solution_store.argtypes = [vp, C.c_double]
+        L.rtoc_solution_interpolate.argtypes = [vp, C.c_double]
+        L.rtoc_solution_stored.argtypes = [vp, C.POINTER(C.c_int)]
+        L.rtoc_solution_forget.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -511,6 +516,26 @@ class Context:
 
     def line_search_clear(self):
         _chk(lib().rtoc_line_search_clear(self._h))
+
+    # ---- SolutionInterpolator on the device (include/rtoc_robot.h: rtoc_solution_*) ----
+    def solution_store(self, t0):
+        """rtoc_solution_store: snapshot RTOC_BUF_SOL with the grid, the contact schedule and the grid times summed from t0 (with an
+        STO problem every instance's own: sto_correct_time_steps first)"""
+        _chk(lib().rtoc_solution_store(self._h, float(t0)))
+
+    def solution_interpolate(self, t0):
+        """rtoc_solution_interpolate: every record of RTOC_BUF_SOL for the current grid, schedule and time steps (times from t0) from
+        the stored solution; nothing happens with nothing stored"""
+        _chk(lib().rtoc_solution_interpolate(self._h, float(t0)))
+
+    def solution_stored(self):
+        """rtoc_solution_stored: the grid points of the stored solution, 0 if there is none"""
+        n = C.c_int(0)
+        _chk(lib().rtoc_solution_stored(self._h, C.byref(n)))
+        return n.value
+
+    def solution_forget(self):
+        _chk(lib().rtoc_solution_forget(self._h))
 
     # ---- rigid-body linearisation (include/rtoc_robot.h) ----
     def set_robot_model(self, model):

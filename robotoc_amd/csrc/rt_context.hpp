@@ -170,6 +170,7 @@ struct ModelState {
   DevBuf<rbd::DevModel> d_model;
   std::unique_ptr<rbd::DevModel> h_model;
   DevBuf<unsigned> d_active;
+  bool active_current = false;  // the schedule was set since the last rtoc_set_grid: its masks belong to the grid in force
   DevBuf<double> d_cpos;
   DevBuf<double> d_crot;
   DevBuf<double> d_cost;      // rtoc_set_configuration_cost: 12 (nv + 1) doubles
@@ -188,6 +189,7 @@ struct ModelState {
       if (dup.e == hipSuccess) dup.e = set_linearize_lds(h_model->m, h_model->nlevels, h_model->nbranch, h_model->dpp);
     }
     dup(d_active, src.d_active);
+    active_current = src.active_current;
     dup(d_cpos, src.d_cpos);
     dup(d_crot, src.d_crot);
     dup(d_cost, src.d_cost);
@@ -246,6 +248,7 @@ struct StoState {
   double sto_t0 = 0.0, sto_T = 0.0, sto_barrier = 0.0, sto_tau = 0.0, sto_reg = 0.0;
   DevBuf<double> d_ts;         // [batch][nev] event times of every instance
   DevBuf<double> d_dt;         // [batch][max_stages] time steps of every instance (grid_dt)
+  bool dt_current = false;     // sto_time_steps_kernel ran since the last rtoc_set_grid: d_dt belongs to the grid in force
   DevBuf<double> d_sto_con;    // [batch][RTOC_STO_CON_STRIDE] dwell-time rows
   DevBuf<double> d_min_dwell;  // [RTOC_STO_MAX_EVENTS + 1]
   DevBuf<double> d_sto_cost;   // [2][batch][nev] STO cost gradient / Hessian diagonal handed over by the host, or unallocated
@@ -255,6 +258,7 @@ struct StoState {
     if (!src.sto_on) return;
     sto_on = 1, sto_nev = src.sto_nev, sto_t0 = src.sto_t0, sto_T = src.sto_T;
     sto_barrier = src.sto_barrier, sto_tau = src.sto_tau, sto_reg = src.sto_reg;
+    dt_current = src.dt_current;
     dup(d_ts, src.d_ts);
     dup(d_dt, src.d_dt);
     dup(d_sto_con, src.d_sto_con);
@@ -310,10 +314,35 @@ struct ParnmpcState {
   }
 };
 
+// SolutionInterpolator on the device (rtoc_solution_store / rtoc_solution_interpolate; solution_interpolate.hpp; rt_interpolate.hip).
+// A copy of everything the interpolation reads of the grid the solution belongs to: rtoc_set_grid, rtoc_set_contact_schedule and
+// rtoc_sto_set_problem come between the store and the interpolation.  Capacities are those of max_stages; in use: isol_n points
+struct InterpState {
+  int isol_n = 0;             // grid points of the stored solution; 0: nothing stored
+  int isol_per_instance = 0;  // the times and time steps are every instance's own (stored with an STO problem set)
+  int isol_ncontacts = 0;     // what packed the stored stacks: the model's contacts and which of them have 6 rows
+  unsigned isol_six_rows = 0;
+  DevBuf<double> d_isol;         // [batch][isol_n] SplitSolution records
+  DevBuf<double> d_isol_t;       // [batch][max_stages] grid times ([isol_n] or [batch][isol_n] in use), then as many time steps
+  DevBuf<int> d_isol_type;       // [max_stages] RTOC_GRID_*
+  DevBuf<unsigned> d_isol_mask;  // [max_stages] contact schedule
+  void clone_from(const InterpState& src, CopyChain& dup) {
+    if (!src.isol_n) return;
+    isol_n = src.isol_n, isol_per_instance = src.isol_per_instance;
+    isol_ncontacts = src.isol_ncontacts, isol_six_rows = src.isol_six_rows;
+    dup(d_isol, src.d_isol);
+    dup(d_isol_t, src.d_isol_t);
+    dup(d_isol_type, src.d_isol_type);
+    dup(d_isol_mask, src.d_isol_mask);
+  }
+  // not copied: the times of the grid being interpolated onto
+  DevBuf<double> d_interp_t;     // [batch][max_stages]
+};
+
 }  // namespace rtoc
 
 struct rtoc_ctx : rtoc::CtxStreams, rtoc::CtxOptions, rtoc::SweepState, rtoc::ConstraintState, rtoc::ModelState, rtoc::TaskState,
-                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState {
+                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState, rtoc::InterpState {
   rtoc_dims dims = {};
   rtoc_layout L = {};
   const rtoc::KernelSet* ks = nullptr;

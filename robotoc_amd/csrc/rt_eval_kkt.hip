@@ -207,6 +207,7 @@ int rtoc_set_contact_schedule(rtoc_ctx* c, const unsigned* active, const double*
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->has_cpos = positions != nullptr;
   c->has_crot = rotations != nullptr;
+  c->active_current = true;
   c->epoch++;
   return RTOC_OK;
 }

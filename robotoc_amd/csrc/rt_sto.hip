@@ -51,6 +51,7 @@ int rtoc::launch_sto(rtoc_ctx* c, StoKernel k) {
     case STO_INTEGRATE: hipLaunchKernelGGL(sto_integrate_kernel, grid, block, 0, c->stream, a); break;
   }
   HIP_TRY(hipGetLastError());
+  if (k == STO_TIME_STEPS) c->dt_current = true;
   return RTOC_OK;
 }
 

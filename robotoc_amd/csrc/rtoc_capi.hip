@@ -231,6 +231,7 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
     n->StoState::clone_from(*c, dup);
     n->TaskState::clone_from(*c, dup);
     n->ParnmpcState::clone_from(*c, dup);
+    n->InterpState::clone_from(*c, dup);
     n->clone_records(*c, dup);
     if (dup.e == hipSuccess) dup.e = hipStreamSynchronize(n->stream);
   }
@@ -275,6 +276,11 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
     HIP_TRY(hipStreamSynchronize(c->stream));   // (the pageable source dies with this scope)
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
+  // the schedule and the STO time steps belong to the previous grid, unless this is the grid in force set again (a shell that
+  // hands the grid over with every iteration)
+  const bool same = !c->parnmpc && (int)c->h_grid.size() == nstages && c->nstages == nstages &&
+                    memcmp(c->h_grid.data(), grid, sizeof(rtoc_grid) * nstages) == 0;
+  if (!same) c->active_current = false, c->dt_current = false;
   c->h_grid.assign(grid, grid + nstages);
   c->nstages = nstages;
   c->parnmpc = 0;   // a grid with a terminal point: no longer the stages of rtoc_parnmpc_set_horizon

@@ -145,6 +145,7 @@ class ConfigurationCostSource : public StageDataSource {
     scheduled_ = false;
     config_ref_dirty_ = true;
   }
+  void setContactSchedule(rtoc_ctx* ctx) override { schedule(ctx); }
   void initConstraints(rtoc_ctx* ctx, const Solution&) override {
     schedule(ctx);
     if (!rows_.empty() || !mu_.empty()) chk(rtoc_contact_init_constraints(ctx), "rtoc_contact_init_constraints");

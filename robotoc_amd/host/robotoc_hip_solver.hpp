@@ -75,6 +75,13 @@ struct SolverOptions {
   bool enable_benchmark = false;
   int horizon_scan = 0;  // not in the reference: RTOC_OPT_BACKWARD_SCAN -- 0 (default) serial kernels, 1 horizon scans, 2 as the
                          // Python shell's "auto": scans for batches of at most 8 OCPs, the latency path of one MPC problem
+  // not in the reference: where SolutionInterpolator runs.  false (default): on the host, in the mesh-refinement branch alone
+  // (download, robotoc_hip_planner.hpp's SolutionInterpolator, upload), and a later solve() starts from the records as they are.
+  // true: on the device (rtoc_solution_store / rtoc_solution_interpolate, no record leaves it), in the mesh-refinement branch and for
+  // the receding-horizon warm start of ocp_solver.cpp:159-163, :215-220 -- every solve() stores its solution at the end, and every
+  // solve(init_solver = true) interpolates the stored one onto the grid it has just discretised.  Both uses are gated by
+  // enable_solution_interpolation, as in the reference, and stay off for a source without contact masks (a stage dump).
+  bool solution_interpolation_on_device = false;
 };
 
 // include/robotoc/solver/solver_statistics.hpp
@@ -141,6 +148,9 @@ class StageDataSource {
   // discretisation): N + 1 + lifts + 2 impacts for a source that owns its contact sequence; the solver reserves that many
   virtual int maxGridPoints() const { return timeDiscretization().size(); }
   virtual const std::vector<unsigned>* contactMasks() const { return nullptr; }
+  // the contact schedule of the current discretisation on the device NOW, not at the next linearize() / initConstraints():
+  // rtoc_solution_interpolate re-packs the f / mu stacks by it (sources with contactMasks())
+  virtual void setContactSchedule(rtoc_ctx*) {}
   virtual void initialSolution(Solution& s) const = 0;
 };
 
@@ -620,8 +630,15 @@ class OCPSolver {
     if (q.size() != s_.at(0).q.size()) throw std::out_of_range("[OCPSolver] invalid argument: q.size() must be " + std::to_string(s_[0].q.size()) + "!");
     if (v.size() != ocp_.robot.dimv) throw std::out_of_range("[OCPSolver] invalid argument: v.size() must be " + std::to_string(ocp_.robot.dimv) + "!");
     const auto t0 = std::chrono::high_resolution_clock::now();
+    const bool warm = solver_options_.solution_interpolation_on_device && solver_options_.enable_solution_interpolation &&
+                      ocp_.source->contactMasks() != nullptr;
     if (init_solver) {
       discretize(t);
+      if (warm) {                                                                               // :159-163
+        ocp_.source->setContactSchedule(dev_->get());
+        chk(rtoc_solution_interpolate(dev_->get(), t_), "rtoc_solution_interpolate");
+        host_solution_valid_ = false;
+      }
       initConstraints();
       chk(rtoc_line_search_clear(dev_->get()), "rtoc_line_search_clear");                       // :166
     }
@@ -675,6 +692,10 @@ class OCPSolver {
     solver_statistics_.convergence = ss.convergence != 0;
     solver_statistics_.iter = ss.iter;
     for (int k = 0; k < ss.num_mesh_refinements && k < RTOC_SOLVE_MAX_REFINEMENTS; ++k) solver_statistics_.mesh_refinement_iter.push_back(ss.mesh_refinement_iter[k]);
+    if (warm) {                                                                                 // :215-220
+      chk(rtoc_sto_correct_time_steps(dev_->get()), "rtoc_sto_correct_time_steps");
+      chk(rtoc_solution_store(dev_->get(), t_), "rtoc_solution_store");
+    }
     if (solver_options_.enable_benchmark)
       solver_statistics_.cpu_time = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
   }
@@ -752,6 +773,18 @@ class OCPSolver {
   void meshRefinement(const double t) {
     const std::vector<unsigned>* masks = ocp_.source->contactMasks();
     const bool interp = solver_options_.enable_solution_interpolation && masks != nullptr;
+    if (interp && solver_options_.solution_interpolation_on_device) {
+      // store, discretize, interpolate (:185-192) without a record leaving the device
+      chk(rtoc_sto_correct_time_steps(dev_->get()), "rtoc_sto_correct_time_steps");
+      chk(rtoc_solution_store(dev_->get(), t_), "rtoc_solution_store");
+      discretize(t);
+      ocp_.source->setContactSchedule(dev_->get());
+      chk(rtoc_solution_interpolate(dev_->get(), t_), "rtoc_solution_interpolate");
+      host_solution_valid_ = false;
+      initConstraints();
+      chk(rtoc_line_search_clear(dev_->get()), "rtoc_line_search_clear");
+      return;
+    }
     if (interp) {
       // correctTimeSteps + store (:186-189): the grid times that belong to the current event times
       // (the device's time steps date from the last evalKKT, BEFORE integrateSolution moved the event times: correct them first,

@@ -33,6 +33,13 @@ class SolverOptions:
     # not in the reference: how the Riccati recursion runs on the device -- "off" (default, as the C API): the serial kernels;
     # "auto": the horizon scans for batches of at most 8 OCPs (RTOC_OPT_BACKWARD_SCAN = 2: latency of one MPC problem); "on": always
     horizon_scan: str = "off"
+    # not in the reference: where SolutionInterpolator runs.  False (default): on the host, in the mesh-refinement branch alone
+    # (download, OCPSolver._interpolate, upload), and a later solve() starts from the records as they are.  True: on the device
+    # (rtoc_solution_store / rtoc_solution_interpolate, no record leaves it), in the mesh-refinement branch and for the
+    # receding-horizon warm start of ocp_solver.cpp:159-163, :215-220 -- every solve() stores its solution at the end, and every
+    # solve(init_solver=True) interpolates the stored one onto the grid it has just discretised.  Both uses are gated by
+    # enable_solution_interpolation, as in the reference.
+    solution_interpolation_on_device: bool = False
     # LineSearchSettings (include/robotoc/line_search/line_search_settings.hpp), filter method
     step_size_reduction_rate: float = 0.75
     min_step_size: float = 0.05
@@ -310,8 +317,11 @@ class OCPSolver:
         o = self.options
         c = self.ctx
         c.set_initial_state(x0)
+        warm = o.solution_interpolation_on_device and o.enable_solution_interpolation
         if init_solver:
             self.discretize(t)
+            if warm:
+                c.solution_interpolate(self.t0)                                                        # :159-163
             self.init_constraints()
             c.line_search_clear()
         st = self.stats = SolverStatistics()
@@ -337,6 +347,9 @@ class OCPSolver:
             max_time_step=max_dt if sto_on else None, mesh_refinement=(lambda: self._mesh_refinement(t)) if sto_on else None)
         if sto_on:
             self.event_times = c.sto_event_times()
+        if warm:                                                                                       # :215-220
+            c.sto_correct_time_steps()
+            c.solution_store(self.t0)
         return st
 
     def kkt_error(self):
@@ -356,6 +369,17 @@ class OCPSolver:
         return float(dt[:, :-1].max())
 
     def _mesh_refinement(self, t):
+        if self.options.solution_interpolation_on_device:
+            # store, discretize, interpolate (ocp_solver.cpp:185-192) without a record leaving the device
+            self.ctx.sto_correct_time_steps()
+            if self.options.enable_solution_interpolation:
+                self.ctx.solution_store(self.t0)
+            self.discretize(t)
+            if self.options.enable_solution_interpolation:
+                self.ctx.solution_interpolate(self.t0)
+            self.init_constraints()
+            self.ctx.line_search_clear()
+            return
         old_grids, old_masks = self.grids, self.masks
         old_sol = self.get_solution()
         # correctTimeSteps(contact_sequence_, t) ahead of solution_interpolator_.store (ocp_solver.cpp:186-189): the device's time
