@@ -7,9 +7,14 @@
 // robot.integrateConfiguration (:62) is Pinocchio's manifold update: joints additively, a free-flyer base by the SE(3)
 // exponential -- M <- M exp6(step dq_base): rotation exp(w), translation R V(w) v, quaternion product and
 // re-normalisation (restated from the Lie-group formulas; Pinocchio absent).  Pure streaming: HBM-bound.
+// The coefficients of V(w) are rbd::exp_coefficients (rigid_body_math.hpp): the series below |w| = 1e-3, 2 sin^2(t/2) / t^2
+// above, since (1 - cos t) / t^2 put the position off by 1e-16 |v| / t -- what step dq_b of a nearly converged iteration meets.
+// Held to a 50-digit reference from angle 0 to 4 (tests/test_lie_exp_branch_points.py): position within 0.0036 of
+// 1e-13 max(1, |p|, |v|) (4.1e+04 of it at 1.01e-8 before), quaternion within 0.22 of 1e-15.
 #pragma once
 #include "device_utils.hpp"
 #include "kernel_args.hpp"  // IntArgs
+#include "rigid_body_math.hpp"  // exp_coefficients
 #include "../../include/rtoc.h"
 
 namespace rtoc {
@@ -41,13 +46,9 @@ static __global__ __launch_bounds__(64) void integrate_solution_kernel(IntArgs a
     // step 0 (instances the convergence mask froze): the iterate is kept bit for bit, no re-normalisation
     if (nb && lane == 0 && step != 0.0) {
       const double vx = step * dx[0], vy = step * dx[1], vz = step * dx[2], wx = step * dx[3], wy = step * dx[4], wz = step * dx[5];
-      const double th = sqrt(wx * wx + wy * wy + wz * wz);
-      double A, B;
-      if (th < 1e-8) {
-        A = 0.5, B = 1.0 / 6.0;
-      } else {
-        A = (1.0 - cos(th)) / (th * th), B = (th - sin(th)) / (th * th * th);
-      }
+      const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+      double S, A, B;
+      rbd::exp_coefficients(th2, th, S, A, B);
       // V(w) v = v + A w x v + B w x (w x v)
       const double cx = wy * vz - wz * vy, cy = wz * vx - wx * vz, cz = wx * vy - wy * vx;
       const double ex = wy * cz - wz * cy, ey = wz * cx - wx * cz, ez = wx * cy - wy * cx;

@@ -124,6 +124,25 @@ __device__ __forceinline__ void log6_fwd(const M3& R, V3 p, SV twist, SV& val, S
   der = SV{dlin, dw};
 }
 
+// The coefficients of exp3 = I + S K + C K^2 and of V = I + C K + B K^2 in exp6([v; w]) = (exp3(w), V(w) v), K = skew w:
+//   S = sin t / t,  C = (1 - cos t) / t^2,  B = (t - sin t) / t^3   at t = |w|, t2 = t^2.
+// 1 - cos t cancels: the quotient is off by about 1e-16 / t^2 and V(w) v by 1e-16 |v| / t -- 1e-9 |v| at t = 1e-7, the angle of
+// a time step of a base that barely turns.  So below 1e-3 three terms of the series in t^2 (the next one is under 3e-22) and
+// above it 2 sin^2(t/2) / t^2, which loses nothing.  t - sin t cancels the same way, B is off by about 1e-16 / t^2 (1e-10
+// relative at 1e-3), but it only ever meets w x (w x v), which is t^2 |v|: 1e-16 |v| at any angle.  Against the 50-digit
+// reference either side of 1e-3 stays under 0.004 of the 1e-13 max(1, |v|) the exponential is held to
+// (tests/test_lie_exp_branch_points*.py).
+__device__ __forceinline__ void exp_coefficients(double t2, double t, double& S, double& C, double& B) {
+  if (t < 1e-3) {
+    S = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
+    C = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+    B = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
+  } else {
+    const double sh = sin(0.5 * t), s = sin(t);
+    S = s / t, C = 2.0 * sh * sh / t2, B = (t - s) / (t2 * t);
+  }
+}
+
 // an int of the device model through the scalar cache: the model is read-only while a kernel runs, but the compiler cannot know
 // (the kernel stores through other pointers) and would issue a vector load + v_readfirstlane on the walk's critical path
 typedef const int __attribute__((address_space(4))) lin_const_int;

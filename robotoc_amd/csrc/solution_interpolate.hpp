@@ -164,14 +164,7 @@ __device__ __forceinline__ BasePose interpolate_base(const double* q1, const dou
   const double th2 = rbd::dot(w, w), th = sqrt(th2);
   // exp3 = I + S K + C K^2, V = I + C K + B K^2 (K = skew w): S = sin t / t, C = (1 - cos t) / t^2, B = (t - sin t) / t^3
   double S, Cc, B;
-  if (th < 1e-3) {
-    S = 1.0 - th2 / 6.0 + th2 * th2 / 120.0;
-    Cc = 0.5 - th2 / 24.0 + th2 * th2 / 720.0;
-    B = 1.0 / 6.0 - th2 / 120.0 + th2 * th2 / 5040.0;
-  } else {
-    const double sh = sin(0.5 * th), s = sin(th);
-    S = s / th, Cc = 2.0 * sh * sh / th2, B = (th - s) / (th2 * th);
-  }
+  rbd::exp_coefficients(th2, th, S, Cc, B);
   const V3 wv = rbd::cross(w, v);
   const V3 pa = v + Cc * wv + B * rbd::cross(w, wv);
   const V3 p = p1 + rbd::mul(R1, pa);

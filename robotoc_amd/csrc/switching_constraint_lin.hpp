@@ -11,6 +11,11 @@
 // dIntegrate_dv = Jexp6(dq_b) = Jlog6(exp6(dq_b))^-1 (six forward-mode evaluations through the log, one 6 x 6 inverse);
 // identities on the joints.  Then the multiplier terms (:52-53) and the STO sensitivities (:54-62).
 // Base-block transport: see RTOC_OPT_SWITCHING_TRANSPORT (rtoc.h) -- the reference's composition by default.
+// exp6(dq_b) takes its coefficients from rbd::exp_coefficients (rigid_body_math.hpp): the series below |w| = 1e-3,
+// 2 sin^2(t/2) / t^2 above.  dq_b of a base that translates and barely turns has |w| of 1e-7 to 1e-5, where (1 - cos t) / t^2
+// put q+, P and, through log6_fwd(E, pe), both transports off by 1e-16 |v| / t.  Held to a 50-digit reference from angle 0 to
+// pi - 1e-3 (tests/test_lie_exp_branch_points.py): P within 0.0044 of 1e-13 max(1, |p|, |v|, |r_c|), Phiq within 0.0089 and
+// Phiv, Phia within 0.073 of their bounds (4.1e+04 and 9.7e+03 of them at 1.01e-8 before).
 // Mapping: one wave per (instance, switching grid point), one lane per dof: the lane carries its column of every body's
 // Jacobian along the depth-first walk (body-frame twist per unit rate of the dof), values once per tree level in LDS.
 #pragma once
@@ -79,17 +84,12 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   V3 pb = rbd::mk(0, 0, 0);
   if (a.md.floating) {
     const V3 vl = rbd::mk(sdq[0], sdq[1], sdq[2]), w = rbd::mk(sdq[3], sdq[4], sdq[5]);
-    const double th = sqrt(rbd::dot(w, w));
-    double A, B;
-    if (th < 1e-8) {
-      A = 0.5, B = 1.0 / 6.0;
-    } else {
-      A = (1.0 - cos(th)) / (th * th), B = (th - sin(th)) / (th * th * th);
-    }
+    const double th2 = rbd::dot(w, w), th = sqrt(th2);
+    double sa, A, B;
+    rbd::exp_coefficients(th2, th, sa, A, B);
     const V3 wxv = rbd::cross(w, vl);
     pe = vl + A * wxv + B * rbd::cross(w, wxv);
     // exp(w) = I + sin t / t [w]x + (1 - cos t) / t^2 [w]x^2
-    const double sa = th < 1e-8 ? 1.0 - th * th / 6.0 : sin(th) / th;
     const double wx[9] = {0, -w.z, w.y, w.z, 0, -w.x, -w.y, w.x, 0};
 #pragma unroll
     for (int r = 0; r < 3; ++r)

@@ -464,19 +464,28 @@ class SolutionInterpolator {
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) K2[3 * i + j] = k[3 * i] * k[j] + k[3 * i + 1] * k[3 + j] + k[3 * i + 2] * k[6 + j];
   }
+  // sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3 at t = |w| as the device computes them (rbd::exp_coefficients,
+  // csrc/rigid_body_math.hpp): (1 - cos t) / t^2 cancels like 1e-16 / t^2, so the series below 1e-3 and 2 sin^2(t/2) / t^2 above
+  static void expCoefficients(const double* w, double& S, double& C, double& B) {
+    const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], t = std::sqrt(t2);
+    if (t < 1e-3) {
+      S = 1.0 - t2 / 6.0 + t2 * t2 / 120.0, C = 0.5 - t2 / 24.0 + t2 * t2 / 720.0, B = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0;
+    } else {
+      const double sh = std::sin(0.5 * t), s = std::sin(t);
+      S = s / t, C = 2.0 * sh * sh / t2, B = (t - s) / (t2 * t);
+    }
+  }
   static void exp3(const double* w, double* R) {
-    const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double K[9], K2[9];
+    double K[9], K2[9], S, C, B;
     skew2(w, K, K2);
-    const double a = th < 1e-10 ? 1.0 : std::sin(th) / th, b = th < 1e-10 ? 0.0 : (1.0 - std::cos(th)) / (th * th);
-    for (int e = 0; e < 9; ++e) R[e] = (e % 4 == 0 ? 1.0 : 0.0) + a * K[e] + b * K2[e];
+    expCoefficients(w, S, C, B);
+    for (int e = 0; e < 9; ++e) R[e] = (e % 4 == 0 ? 1.0 : 0.0) + S * K[e] + C * K2[e];
   }
   static void Vmat(const double* w, double* V) {
-    const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double K[9], K2[9];
+    double K[9], K2[9], S, C, B;
     skew2(w, K, K2);
-    const double a = th < 1e-10 ? 0.5 : (1.0 - std::cos(th)) / (th * th), b = th < 1e-10 ? 0.0 : (th - std::sin(th)) / (th * th * th);
-    for (int e = 0; e < 9; ++e) V[e] = (e % 4 == 0 ? 1.0 : 0.0) + a * K[e] + b * K2[e];
+    expCoefficients(w, S, C, B);
+    for (int e = 0; e < 9; ++e) V[e] = (e % 4 == 0 ? 1.0 : 0.0) + C * K[e] + B * K2[e];
   }
   static void solve3(const double* A, const double* b, double* x) {   // Cramer
     const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);

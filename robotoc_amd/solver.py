@@ -140,20 +140,27 @@ def _log3(R):
     return th / (2.0 * np.sin(th)) * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
 
 
+def _exp_coefficients(w):
+    """sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3 at t = |w| as the device computes them (rbd::exp_coefficients,
+    csrc/rigid_body_math.hpp): (1 - cos t) / t^2 cancels like 1e-16 / t^2, so the series below 1e-3 and 2 sin^2(t/2) / t^2 above"""
+    t2 = float(np.dot(w, w))
+    t = np.sqrt(t2)
+    if t < 1e-3:
+        return 1.0 - t2 / 6.0 + t2 * t2 / 120.0, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
+    sh, s = np.sin(0.5 * t), np.sin(t)
+    return s / t, 2.0 * sh * sh / t2, (t - s) / (t2 * t)
+
+
 def _exp3(w):
-    th = np.linalg.norm(w)
     K = _skew(w)
-    if th < 1e-10:
-        return np.eye(3) + K
-    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
+    S, C, _ = _exp_coefficients(w)
+    return np.eye(3) + S * K + C * K @ K
 
 
 def _V(w):   # exp6: p = V(w) v
-    th = np.linalg.norm(w)
     K = _skew(w)
-    if th < 1e-10:
-        return np.eye(3) + 0.5 * K
-    return np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
+    _, C, B = _exp_coefficients(w)
+    return np.eye(3) + C * K + B * K @ K
 
 
 def interpolate_configuration(q1, q2, alpha, floating):

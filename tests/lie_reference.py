@@ -1,6 +1,7 @@
-"""SE(3) exponential, logarithm and their Jacobians at 50 digits (mpmath) -- the reference the committed fixture
-tests/golden/lie_branch_points.npz is generated from, and what every double-precision copy of the log6 formula in this
-repository (device, oracle, restatement, solver, planner header) is held to.
+"""SE(3) exponential, logarithm and their Jacobians at 50 digits (mpmath) -- the reference the committed fixtures
+tests/golden/lie_branch_points.npz and tests/golden/lie_exp_branch_points.npz are generated from, and what every
+double-precision copy of the log6 and of the exp6 formula in this repository (device, oracle, restatements, solver, planner
+header) is held to.
 
 Conventions are pinocchio's: a twist is [linear; angular], a placement X = (R, p), and Jlog6(X) is the derivative of
 log6(X exp6(xi)) with respect to xi at 0.  A placement enters as a double quaternion (x, y, z, w) and a double position; the
@@ -187,6 +188,48 @@ def dq0_jacobian(q, p, sign=1):
     """-Jlog6(X) Ad_{X^-1}: the derivative of log6(M0^-1 M1) with respect to M0 (X = M0^-1 M1)"""
     qi, pi_ = inverse(q, p)
     return -jlog6(q, p, sign) * Ad(qi, pi_)
+
+
+def jexp6(xi):
+    """Jexp6(xi) = Jlog6(exp6(xi))^-1 (pinocchio's dIntegrate_dv on a free-flyer), for |w| < pi"""
+    q, p = exp6(xi)
+    return jlog6(q, p) ** -1
+
+
+def ad_inv_exp6(xi):
+    """Ad_{exp6(xi)}^-1 (pinocchio's dIntegrate_dq on a free-flyer)"""
+    q, p = exp6(xi)
+    return Ad(*inverse(q, p))
+
+
+def rotation_to_quat(R):
+    """unit quaternion (x, y, z, w) of a rotation matrix, the largest of the four components leading; q_w >= 0 up to that choice"""
+    d = [R[0, 0], R[1, 1], R[2, 2]]
+    tr = d[0] + d[1] + d[2]
+    if tr > 0:
+        s = 2 * mp.sqrt(1 + tr)
+        return [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, s / 4]
+    i = max(range(3), key=lambda k: d[k])
+    j, k = (i + 1) % 3, (i + 2) % 3
+    s = 2 * mp.sqrt(1 + d[i] - d[j] - d[k])
+    q = [mp.mpf(0)] * 4
+    q[i], q[j], q[k], q[3] = s / 4, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s, (R[k, j] - R[j, k]) / s
+    return q
+
+
+def exp6_expm(xi):
+    """(quaternion, position) of exp6([v; w]) by another road: mp.expm of the 4 x 4 twist matrix [[skew w, v], [0, 0]], ten
+    digits over the working precision, its rotation block turned into a quaternion (sign as rotation_to_quat leaves it)"""
+    xi = _vec(xi)
+    with mp.workdps(mp.mp.dps + 10):
+        T = mp.zeros(4, 4)
+        K = skew(xi[3:])
+        for r in range(3):
+            for c in range(3):
+                T[r, c] = K[r, c]
+            T[r, 3] = xi[r]
+        E = mp.expm(T)
+        return rotation_to_quat(E), [E[r, 3] for r in range(3)]
 
 
 def cond2(M):

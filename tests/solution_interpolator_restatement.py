@@ -76,18 +76,27 @@ def log3(R):
     return (0.5 if th < 1e-10 else th / (2.0 * np.sin(th))) * vee
 
 
+def exp_coefficients(w):
+    """sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3 at t = |w|: the series below 1e-3, 2 sin^2(t/2) / t^2 above, where
+    (1 - cos t) / t^2 would cancel like 1e-16 / t^2 (held to 50 digits by tests/test_lie_exp_branch_points_host.py)"""
+    t2 = float(np.dot(w, w))
+    t = np.sqrt(t2)
+    if t < 1e-3:
+        return 1.0 - t2 / 6.0 + t2 * t2 / 120.0, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
+    sh, s = np.sin(0.5 * t), np.sin(t)
+    return s / t, 2.0 * sh * sh / t2, (t - s) / (t2 * t)
+
+
 def exp3(w):
-    th, K = np.linalg.norm(w), skew(w)
-    if th < 1e-10:
-        return np.eye(3) + K
-    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
+    K = skew(w)
+    S, C, _ = exp_coefficients(w)
+    return np.eye(3) + S * K + C * K @ K
 
 
 def V_mat(w):   # exp6: p = V(w) v
-    th, K = np.linalg.norm(w), skew(w)
-    if th < 1e-10:
-        return np.eye(3) + 0.5 * K
-    return np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
+    K = skew(w)
+    _, C, B = exp_coefficients(w)
+    return np.eye(3) + C * K + B * K @ K
 
 
 def linear(a, b, alpha):
