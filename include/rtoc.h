@@ -286,6 +286,23 @@ int rtoc_set_wrench_cones(rtoc_ctx* ctx, int max_contacts);
 int rtoc_wrench_cone_matrix(double X, double Y, double mu, double* out);
 
 /* ---- the hot path ---------------------------------------------------------- */
+/* INACTIVE ENTRIES.  A record has a fixed stride (nf_max, ns_max, nc_max, nu); what a grid point uses of it follows from the
+ * type, sto / sto_next, dimf, dims and time_stage of its rtoc_grid, from rtoc_box_row::level and from the active cone contacts.
+ * No entry point reads the rest: it may hold anything -- NaN, the last contact phase's values, whatever the caller's buffer
+ * held -- and results and status words are bit for bit those of zero padding.  Inactive are:
+ *   - the alignment doubles between fields;
+ *   - rows at and beyond dims of every switching-constraint field (Phix, Phiu, Phit, Pres, Phia; M, m, mt, mt_next; dxi, xi);
+ *   - rows and columns at and beyond dimf of every contact field (dCda, Qff, Qqf, lf, hf; f, mu) and rows at and beyond
+ *     nv + dimf of every stacked one (dIDCdqv, IDC, MJtJinv and its products, laf, haf; daf, dbetamu);
+ *   - on an IMPACT grid point every field of the controls and of the switching constraint;
+ *   - of the TERMINAL grid point all but Qxx, lx (records) and q, v, lmd, gmm (the iterate);
+ *   - for the Riccati recursion fx, hx, hu, scal, Phit on grid points with sto = 0, and scal[3..7] everywhere;
+ *   - every field of a box row on impact and terminal grid points and where time_stage < level;
+ *   - the rows and the RTOC_BUF_CONE entries of cone contact slots at and beyond dimf / contact_dim.
+ * Two exceptions: rtoc_integrate_solution advances every member of the terminal record, like SplitSolution::integrate; and the
+ * switching-time KKT term (rtoc_sto_eval_kkt and its device form) sums scal[H] over every grid point but the last, so scal[H] of
+ * an impact point, where the reference leaves h = 0, is an input there.
+ * tests/inactive_regions.py holds the regions per buffer and entry point. */
 int rtoc_condense(rtoc_ctx* ctx);
 /* Qxx of every grid point is taken as symmetric, as the reference's cost and condensation leave it (to round-off).  The
  * register-resident kernel (RTOC_OPT_BACKWARD_REGISTER, riccati_backward_rv.hpp) reads only its lower 16 x 16 tiles -- entries

@@ -90,6 +90,13 @@ int rtoc_set_contact_schedule(rtoc_ctx* ctx, const unsigned* active, const doubl
  * lq / lv / lu in RTOC_BUF_KKT, la / lf / lu_passive in RTOC_BUF_CDD. */
 int rtoc_linearize_contact_dynamics(rtoc_ctx* ctx, int augment_residual);
 
+/* INACTIVE ENTRIES (include/rtoc.h, ahead of rtoc_condense, lists them): the entry points of this header keep to the same contract.
+ * Of the iterate in RTOC_BUF_SOL they use q, v, lmd, gmm on every grid point; a, beta and f / mu of the dimf stacked rows of the
+ * ACTIVE contacts on every grid point but the last (a foot that lifted leaves its f behind); u, nu_passive and xi[0..dims) where
+ * the grid point has controls.  initConstraints sets slack and dual of the active rows from the iterate alone; the linearisation
+ * reads slack and dual of the active rows; the line search's trial evaluation reads dx, du and daf[0..nv + dimf) of the direction
+ * and slack, dslack of the active rows; rtoc_sto_compute_step_sizes reads dts[0] of the impact and lift grid points. */
+
 /* ---- evalKKT of the contact path on the device (no inequality rows) ----
  * {Intermediate,Impact,Terminal}Stage::evalKKT up to the condensation (src/ocp/intermediate_stage.cpp:94-132,
  * impact_stage.cpp:82-114, terminal_stage.cpp:72-100) for an OCP whose cost is the ConfigurationSpaceCost of
