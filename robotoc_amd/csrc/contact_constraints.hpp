@@ -14,7 +14,10 @@
 // The rows' ConstraintComponentData live where rtoc_set_friction_cones puts them (RTOC_BUF_CON, compacted by active contact).
 // One wave per (instance, grid point), lane j = dof j: the lane carries its column of the bodies' Jacobians down the tree.
 #pragma once
-#include "state_equation_lin.hpp"
+#include "device_utils.hpp"
+#include "record_view.hpp"
+#include "rigid_body_math.hpp"
+#include "rigid_body_model.hpp"
 
 namespace rtoc {
 
@@ -34,9 +37,10 @@ __host__ __device__ constexpr size_t cc_lds_bytes(int nlevels, int njoints, int 
 }
 
 static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
-  using namespace selin;
   using rbd::CP;
   using rbd::JP;
+  using rbd::M3;
+  using rbd::V3;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int nst1 = a.rv.nstages - 1;
@@ -80,25 +84,22 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
     M3 Rj;
     V3 pj = rbd::mk(0, 0, 0);
     if (ff) {
-      Rj = quat_R(sq + iq + 3);
+      Rj = rbd::quat_R(sq + iq + 3);
       pj = rbd::ldv3(sq + iq);
     } else {
-      const V3 ax = rbd::ldv3(&JM(i, 12));
-      const double th = sq[iq], c = cos(th), sn = sin(th), t = 1.0 - c;
-      Rj.m[0] = t * ax.x * ax.x + c, Rj.m[1] = t * ax.x * ax.y - sn * ax.z, Rj.m[2] = t * ax.x * ax.z + sn * ax.y;
-      Rj.m[3] = t * ax.x * ax.y + sn * ax.z, Rj.m[4] = t * ax.y * ax.y + c, Rj.m[5] = t * ax.y * ax.z - sn * ax.x;
-      Rj.m[6] = t * ax.x * ax.z - sn * ax.y, Rj.m[7] = t * ax.y * ax.z + sn * ax.x, Rj.m[8] = t * ax.z * ax.z + c;
+      const double th = sq[iq];
+      Rj = rbd::revolute_R(rbd::ldv3(&JM(i, 12)), sin(th), cos(th));
     }
-    const M3 Rp = rbd::ldm3(&JM(i, 0));
-    const M3 R = rbd::mul(Rp, Rj);
-    const V3 p = rbd::mul(Rp, pj) + rbd::ldv3(&JM(i, 9));
+    M3 R;
+    V3 p;
+    rbd::joint_placement(&JM(i, 0), Rj, pj, R, p);
     M3 oR = R;
     V3 wj = rbd::mk(0, 0, 0);   // body-frame angular velocity of body i per unit rate of dof j
     if (d > 0) {
       oR = rbd::mul(rbd::ldm3(&LV(d - 1, 12)), R);
       wj = rbd::mulT(R, rbd::mk(LT(d - 1, 3), LT(d - 1, 4), LT(d - 1, 5)));
     }
-    if (own) wj = wj + (ff ? unit_twist(j - iv).a : rbd::ldv3(&JM(i, 12)));
+    if (own) wj = wj + (ff ? rbd::unit_twist(j - iv).a : rbd::ldv3(&JM(i, 12)));
 #pragma unroll
     for (int k = 0; k < 9; ++k) LV(d, 12 + k) = oR.m[k];
     LT(d, 3) = wj.x, LT(d, 4) = wj.y, LT(d, 5) = wj.z;
@@ -185,8 +186,9 @@ struct CvArgs {
 };
 
 static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) {
-  using namespace selin;
   using rbd::CP;
+  using rbd::M3;
+  using rbd::V3;
   const CcArgs& a = v.c;
   const int lane = threadIdx.x;
   const int nst1 = a.rv.nstages - 1;

@@ -10,8 +10,10 @@
 // of the reference.  Records: the un-condensed contact-path convention (Qaa / la / lf ... in RTOC_BUF_CDD).
 // cost table (device): 12 arrays of M = nv + 1 doubles: q_ref | v_ref | u_ref | wq | wv | wa | wu | wq_T | wv_T | wq_I | wv_I | wdv_I
 #pragma once
+#include "device_utils.hpp"
 #include "kernel_args.hpp"
-#include "state_equation_lin.hpp"
+#include "record_view.hpp"
+#include "rigid_body_math.hpp"
 
 namespace rtoc {
 
@@ -84,7 +86,6 @@ static __global__ __launch_bounds__(256) void init_records_kernel(InitArgs a) {
 // beyond the batch repeats the last one (identical values to identical addresses).
 constexpr int COST_GP = 4, COST_LW = 64 / COST_GP;
 static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
-  using namespace selin;
   __shared__ double Js[COST_GP][36], wds[COST_GP][8];
   const int lane = threadIdx.x % COST_LW, grp = threadIdx.x / COST_LW;   // `lane`: within the grid point's COST_LW lanes
   double* const J = Js[grp];
@@ -180,12 +181,12 @@ static __global__ __launch_bounds__(64) void contact_cost_kernel(CostArgs a) {
   (void)np;
   // ---- the free-flyer base of q: qdiff = log6(M_ref^-1 M), J = Jlog6 ----
   if (a.rv.floating()) {
-    M3 Rx;
-    V3 px;
-    rel(quat_R(qr + 3), rbd::ldv3(qr), quat_R(q + 3), rbd::ldv3(q), Rx, px);
+    rbd::M3 Rx;
+    rbd::V3 px;
+    rbd::rel(rbd::quat_R(qr + 3), rbd::ldv3(qr), rbd::quat_R(q + 3), rbd::ldv3(q), Rx, px);
     if (lane < 6) {
-      SV val, der;
-      rbd::log6_fwd(Rx, px, unit_twist(lane), val, der);
+      rbd::SV val, der;
+      rbd::log6_fwd(Rx, px, rbd::unit_twist(lane), val, der);
       const double c[6] = {der.l.x, der.l.y, der.l.z, der.a.x, der.a.y, der.a.z}, d[6] = {val.l.x, val.l.y, val.l.z, val.a.x, val.a.y, val.a.z};
 #pragma unroll
       for (int r = 0; r < 6; ++r) J[r + 6 * lane] = c[r];

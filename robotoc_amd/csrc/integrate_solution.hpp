@@ -14,7 +14,7 @@
 #pragma once
 #include "device_utils.hpp"
 #include "kernel_args.hpp"  // IntArgs
-#include "rigid_body_math.hpp"  // exp_coefficients
+#include "rigid_body_math.hpp"
 #include "../../include/rtoc.h"
 
 namespace rtoc {
@@ -45,22 +45,17 @@ static __global__ __launch_bounds__(64) void integrate_solution_kernel(IntArgs a
     for (int i = lane; i < nv - nb; i += 64) q[(nb ? 7 : 0) + i] += step * dx[nb + i];
     // step 0 (instances the convergence mask froze): the iterate is kept bit for bit, no re-normalisation
     if (nb && lane == 0 && step != 0.0) {
-      const double vx = step * dx[0], vy = step * dx[1], vz = step * dx[2], wx = step * dx[3], wy = step * dx[4], wz = step * dx[5];
-      const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+      const rbd::V3 v = step * rbd::ldv3(dx), wv = step * rbd::ldv3(dx + 3);
+      const double th2 = rbd::dot(wv, wv), th = sqrt(th2);
       double S, A, B;
       rbd::exp_coefficients(th2, th, S, A, B);
-      // V(w) v = v + A w x v + B w x (w x v)
-      const double cx = wy * vz - wz * vy, cy = wz * vx - wx * vz, cz = wx * vy - wy * vx;
-      const double ex = wy * cz - wz * cy, ey = wz * cx - wx * cz, ez = wx * cy - wy * cx;
-      const double ux = vx + A * cx + B * ex, uy = vy + A * cy + B * ey, uz = vz + A * cz + B * ez;
       const double x = q[3], y = q[4], z = q[5], w = q[6];
-      // R(quat) (V v)
-      q[0] += (1 - 2 * (y * y + z * z)) * ux + 2 * (x * y - z * w) * uy + 2 * (x * z + y * w) * uz;
-      q[1] += 2 * (x * y + z * w) * ux + (1 - 2 * (x * x + z * z)) * uy + 2 * (y * z - x * w) * uz;
-      q[2] += 2 * (x * z - y * w) * ux + 2 * (y * z + x * w) * uy + (1 - 2 * (x * x + y * y)) * uz;
-      // quat (x) (sin(t/2)/t w, cos(t/2)), normalised
+      // R(quat) (V(w) v)
+      const rbd::V3 dp = rbd::mul(rbd::quat_R(q + 3), rbd::exp6_translation(v, wv, A, B));
+      q[0] += dp.x, q[1] += dp.y, q[2] += dp.z;
+      // quat (x) (sin(t/2)/t w, cos(t/2)), normalised: the product, not the quaternion of R exp3(w), is what holds it to 1e-15
       const double sc = th < 1e-8 ? 0.5 - th * th / 48.0 : sin(0.5 * th) / th, ew = cos(0.5 * th);
-      const double e0 = sc * wx, e1 = sc * wy, e2 = sc * wz;
+      const double e0 = sc * wv.x, e1 = sc * wv.y, e2 = sc * wv.z;
       const double r0 = w * e0 + x * ew + y * e2 - z * e1, r1 = w * e1 - x * e2 + y * ew + z * e0,
                    r2 = w * e2 + x * e1 - y * e0 + z * ew, r3 = w * ew - x * e0 - y * e1 - z * e2;
       const double n = 1.0 / sqrt(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);

@@ -100,28 +100,23 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   V3 pj = mk(0, 0, 0);
   SV vj, aj;
   if (ff) {
-    const double x = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 3], y = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 4], z = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 5], w = sr[a.rv.sol_off(RTOC_SOL_Q) + iq + 6];
-    Rj.m[0] = 1 - 2 * (y * y + z * z), Rj.m[1] = 2 * (x * y - z * w), Rj.m[2] = 2 * (x * z + y * w);
-    Rj.m[3] = 2 * (x * y + z * w), Rj.m[4] = 1 - 2 * (x * x + z * z), Rj.m[5] = 2 * (y * z - x * w);
-    Rj.m[6] = 2 * (x * z - y * w), Rj.m[7] = 2 * (y * z + x * w), Rj.m[8] = 1 - 2 * (x * x + y * y);
+    Rj = quat_R(sr + a.rv.sol_off(RTOC_SOL_Q) + iq + 3);
     pj = ldv3(sr + a.rv.sol_off(RTOC_SOL_Q) + iq);
     vj = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_V) + iv), ldv3(sr + a.rv.sol_off(RTOC_SOL_V) + iv + 3)};
     aj = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_A) + iv), ldv3(sr + a.rv.sol_off(RTOC_SOL_A) + iv + 3)};
     if (impact && !dyn) vj = vj + aj;  // kinematics at v + dv
   } else {
-    const double th = sr[a.rv.sol_off(RTOC_SOL_Q) + iq], c = cos(th), s = sin(th), t = 1.0 - c;
-    Rj.m[0] = t * ax.x * ax.x + c, Rj.m[1] = t * ax.x * ax.y - s * ax.z, Rj.m[2] = t * ax.x * ax.z + s * ax.y;
-    Rj.m[3] = t * ax.x * ax.y + s * ax.z, Rj.m[4] = t * ax.y * ax.y + c, Rj.m[5] = t * ax.y * ax.z - s * ax.x;
-    Rj.m[6] = t * ax.x * ax.z - s * ax.y, Rj.m[7] = t * ax.y * ax.z + s * ax.x, Rj.m[8] = t * ax.z * ax.z + c;
+    const double th = sr[a.rv.sol_off(RTOC_SOL_Q) + iq];
+    Rj = revolute_R(ax, sin(th), cos(th));
     const double vq = (impact && !dyn) ? sr[a.rv.sol_off(RTOC_SOL_V) + iv] + sr[a.rv.sol_off(RTOC_SOL_A) + iv] : sr[a.rv.sol_off(RTOC_SOL_V) + iv];
     vj = SV{mk(0, 0, 0), vq * ax};
     aj = SV{mk(0, 0, 0), sr[a.rv.sol_off(RTOC_SOL_A) + iv] * ax};
   }
   if (impact && dyn) vj = sv0();   // impact model: v = 0
   if (impact && !dyn) aj = sv0();  // velocity-level rows only
-  const M3 Rp = ldm3(jm);
-  const M3 R = mul(Rp, Rj);
-  const V3 p = mul(Rp, pj) + ldv3(jm + 9);
+  M3 R;
+  V3 p;
+  joint_placement(jm, Rj, pj, R, p);
   const double mass = jm[15];
   const V3 com = ldv3(jm + 16);
   const M3 I = ldm3(jm + 19);
@@ -341,8 +336,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
       bool topreg = false;                        // the force tangent of level `top` is cdf (a leaf), not in LDS
       auto JM = [&](int i, int k) -> const double& { return sjm[i * JPW + k - JOFF]; };
       auto unit_twist = [&](int i, int k) -> SV {  // S_k of joint i
-        if ((int)JM(i, 28) == RTOC_JOINT_FREE_FLYER)
-          return SV{mk(k == 0, k == 1, k == 2), mk(k == 3, k == 4, k == 5)};
+        if ((int)JM(i, 28) == RTOC_JOINT_FREE_FLYER) return rbd::unit_twist(k);
         return SV{mk(0, 0, 0), ldv3(&JM(i, 12))};
       };
       auto close = [&](int lev, bool from_reg) {
@@ -441,29 +435,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         V3 pj = mk(0, 0, 0);
         SV aj;  // S aq (vj = S vq)
         if (ff) {
-          const double x = sq[iq + 3], y = sq[iq + 4], z = sq[iq + 5], w = sq[iq + 6];
-          Rj.m[0] = 1 - 2 * (y * y + z * z), Rj.m[1] = 2 * (x * y - z * w), Rj.m[2] = 2 * (x * z + y * w);
-          Rj.m[3] = 2 * (x * y + z * w), Rj.m[4] = 1 - 2 * (x * x + z * z), Rj.m[5] = 2 * (y * z - x * w);
-          Rj.m[6] = 2 * (x * z - y * w), Rj.m[7] = 2 * (y * z + x * w), Rj.m[8] = 1 - 2 * (x * x + y * y);
+          Rj = quat_R(sq + iq + 3);
           pj = mk(sq[iq], sq[iq + 1], sq[iq + 2]);
           vj = SV{mk(sv[iv], sv[iv + 1], sv[iv + 2]), mk(sv[iv + 3], sv[iv + 4], sv[iv + 5])};
           aj = SV{mk(sa[iv], sa[iv + 1], sa[iv + 2]), mk(sa[iv + 3], sa[iv + 4], sa[iv + 5])};
           if (impact && !dyn) vj = vj + aj;  // kinematics at v + dv
         } else {
           const V3 ax = ldv3(&JM(i, 12));
-          const double th = sq[iq], c = cos(th), s = sin(th), t = 1.0 - c;
-          Rj.m[0] = t * ax.x * ax.x + c, Rj.m[1] = t * ax.x * ax.y - s * ax.z, Rj.m[2] = t * ax.x * ax.z + s * ax.y;
-          Rj.m[3] = t * ax.x * ax.y + s * ax.z, Rj.m[4] = t * ax.y * ax.y + c, Rj.m[5] = t * ax.y * ax.z - s * ax.x;
-          Rj.m[6] = t * ax.x * ax.z - s * ax.y, Rj.m[7] = t * ax.y * ax.z + s * ax.x, Rj.m[8] = t * ax.z * ax.z + c;
+          const double th = sq[iq];
+          Rj = revolute_R(ax, sin(th), cos(th));
           const double vq = (impact && !dyn) ? sv[iv] + sa[iv] : sv[iv];
           vj = SV{mk(0, 0, 0), vq * ax};
           aj = SV{mk(0, 0, 0), sa[iv] * ax};
         }
         if (impact && dyn) vj = sv0();   // impact model: v = 0
         if (impact && !dyn) aj = sv0();  // velocity-level rows only
-        const M3 Rp = ldm3(&JM(i, 0));
-        R = mul(Rp, Rj);
-        p = mul(Rp, pj) + ldv3(&JM(i, 9));
+        joint_placement(&JM(i, 0), Rj, pj, R, p);
         oR = R;
         op = p;
         vpar = sv0(), apar = sv0();
@@ -578,11 +565,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
 #pragma unroll
                     for (int e = 0; e < 9; ++e) Rd.m[e] = (e % 4 == 0) ? 1.0 : 0.0;
                   }
-                  M3 Rdt;
-#pragma unroll
-                  for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int cc = 0; cc < 3; ++cc) Rdt.m[3 * r + cc] = Rd.m[3 * cc + r];
+                  const M3 Rdt = transpose(Rd);
                   SV lg, dlg;
                   log6_fwd(mul(Rdt, oRf), mul(Rdt, pw - pr), jc, lg, dlg);
                   C = SV{af.l + kd * vf.l + kp * lg.l, af.a + kd * vf.a + kp * lg.a};

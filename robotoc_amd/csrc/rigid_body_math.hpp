@@ -1,5 +1,8 @@
-// rigid_body_math.hpp -- spatial-vector arithmetic of the rigid-body kernels: 3-vectors, spatial motions / forces, rotations,
-// log6 with its forward-mode derivative, and the scalar-cache load of the device model.  Device functions only.
+// rigid_body_math.hpp -- the one device copy of the rotation and SE(3) arithmetic of the kernels: 3-vectors, spatial motions /
+// forces, rotations (transpose, relative placement A^-1 B, quaternion <-> matrix, the revolute joint's Rodrigues rotation, the
+// placement of a joint from its model row, unit twists), log6 with its forward-mode derivative, exp6 with its coefficients
+// and translation part, the block-triangular 6 x 6 inverse of the SE(3) Jacobians, and the scalar-cache load of the device
+// model.  Device functions only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +64,68 @@ __device__ __forceinline__ M3 ldm3(const double* p) {
   return r;
 }
 __device__ __forceinline__ V3 ldv3(const double* p) { return mk(p[0], p[1], p[2]); }
+__device__ __forceinline__ M3 transpose(const M3& A) {
+  M3 T;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) T.m[3 * r + c] = A.m[3 * c + r];
+  return T;
+}
+// X = A^-1 B for placements A = (Ra, pa), B = (Rb, pb)
+__device__ __forceinline__ void rel(const M3& Ra, V3 pa, const M3& Rb, V3 pb, M3& R, V3& p) {
+  R = mul(transpose(Ra), Rb);
+  p = mulT(Ra, pb - pa);
+}
+// rotation matrix of the unit quaternion q = (x, y, z, w)
+__device__ __forceinline__ M3 quat_R(const double* q) {
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  M3 R;
+  R.m[0] = 1 - 2 * (y * y + z * z), R.m[1] = 2 * (x * y - z * w), R.m[2] = 2 * (x * z + y * w);
+  R.m[3] = 2 * (x * y + z * w), R.m[4] = 1 - 2 * (x * x + z * z), R.m[5] = 2 * (y * z - x * w);
+  R.m[6] = 2 * (x * z - y * w), R.m[7] = 2 * (y * z + x * w), R.m[8] = 1 - 2 * (x * x + y * y);
+  return R;
+}
+// the normalised quaternion q = (x, y, z, w) of a rotation matrix: w > 0 where the trace is positive, else the largest diagonal
+// entry leads.  Out through an array written from locals: with four reference outputs the compiler began the sum of squares
+// below at another term, one ulp in the interpolated quaternion
+__device__ __forceinline__ void R_quat(const M3& R, double* q) {
+  double x, y, z, w;
+  const double tr = R.m[0] + R.m[4] + R.m[8];
+  if (tr > 0.0) {
+    const double s = sqrt(tr + 1.0) * 2.0;
+    w = 0.25 * s, x = (R.m[7] - R.m[5]) / s, y = (R.m[2] - R.m[6]) / s, z = (R.m[3] - R.m[1]) / s;
+  } else if (R.m[0] >= R.m[4] && R.m[0] >= R.m[8]) {
+    const double s = sqrt(fmax(0.0, 1.0 + R.m[0] - R.m[4] - R.m[8])) * 2.0;
+    x = 0.25 * s, y = (R.m[3] + R.m[1]) / s, z = (R.m[6] + R.m[2]) / s, w = (R.m[7] - R.m[5]) / s;
+  } else if (R.m[4] >= R.m[8]) {
+    const double s = sqrt(fmax(0.0, 1.0 + R.m[4] - R.m[8] - R.m[0])) * 2.0;
+    y = 0.25 * s, z = (R.m[7] + R.m[5]) / s, x = (R.m[1] + R.m[3]) / s, w = (R.m[2] - R.m[6]) / s;
+  } else {
+    const double s = sqrt(fmax(0.0, 1.0 + R.m[8] - R.m[0] - R.m[4])) * 2.0;
+    z = 0.25 * s, x = (R.m[2] + R.m[6]) / s, y = (R.m[5] + R.m[7]) / s, w = (R.m[3] - R.m[1]) / s;
+  }
+  const double n = sqrt(x * x + y * y + z * z + w * w);
+  q[0] = x / n, q[1] = y / n, q[2] = z / n, q[3] = w / n;
+}
+// rotation of a revolute joint about its unit axis (Rodrigues), from the sine and cosine of the angle: the caller evaluates them
+__device__ __forceinline__ M3 revolute_R(V3 ax, double sn, double cs) {
+  const double t = 1.0 - cs;
+  M3 R;
+  R.m[0] = t * ax.x * ax.x + cs, R.m[1] = t * ax.x * ax.y - sn * ax.z, R.m[2] = t * ax.x * ax.z + sn * ax.y;
+  R.m[3] = t * ax.x * ax.y + sn * ax.z, R.m[4] = t * ax.y * ax.y + cs, R.m[5] = t * ax.y * ax.z - sn * ax.x;
+  R.m[6] = t * ax.x * ax.z - sn * ax.y, R.m[7] = t * ax.y * ax.z + sn * ax.x, R.m[8] = t * ax.z * ax.z + cs;
+  return R;
+}
+// placement (R, p) of a joint in its parent's frame: the fixed placement of its model row (rotation at 0, offset at 9) times
+// the joint's own transform (Rj, pj)
+__device__ __forceinline__ void joint_placement(const double* row, const M3& Rj, V3 pj, M3& R, V3& p) {
+  const M3 Rp = ldm3(row);
+  R = mul(Rp, Rj);
+  p = mul(Rp, pj) + ldv3(row + 9);
+}
+// S_k of a free-flyer joint: the k-th unit twist (linear 0..2, angular 3..5)
+__device__ __forceinline__ SV unit_twist(int k) { return SV{mk(k == 0, k == 1, k == 2), mk(k == 3, k == 4, k == 5)}; }
 
 // pinocchio::log6 of X = (R, p) and its derivative along the right perturbation X exp(twist) (what Jlog6 * twist is):
 //   w = log3 R,  lin = p - w x p / 2 + beta w x (w x p),  beta(t) = 1/t^2 - cot(t/2) / (2 t)  (= the Jlog3 coefficient too)
@@ -141,6 +206,56 @@ __device__ __forceinline__ void exp_coefficients(double t2, double t, double& S,
     const double sh = sin(0.5 * t), s = sin(t);
     S = s / t, C = 2.0 * sh * sh / t2, B = (t - s) / (t2 * t);
   }
+}
+// V(w) v = v + C w x v + B w x (w x v), C and B from exp_coefficients
+__device__ __forceinline__ V3 exp6_translation(V3 v, V3 w, double C, double B) {
+  const V3 wxv = cross(w, v);
+  return v + C * wxv + B * cross(w, wxv);
+}
+// exp6([v; w]) = (E, p): E = I + S K + C K^2 with K^2 = w w^T - t^2 I written out (no products with the zeros of K)
+__device__ __forceinline__ void exp6(V3 v, V3 w, M3& E, V3& p) {
+  const double t2 = dot(w, w);
+  double S, C, B;
+  exp_coefficients(t2, sqrt(t2), S, C, B);
+  p = exp6_translation(v, w, C, B);
+  E.m[0] = 1.0 - C * (w.y * w.y + w.z * w.z), E.m[1] = C * w.x * w.y - S * w.z, E.m[2] = C * w.x * w.z + S * w.y;
+  E.m[3] = C * w.x * w.y + S * w.z, E.m[4] = 1.0 - C * (w.x * w.x + w.z * w.z), E.m[5] = C * w.y * w.z - S * w.x;
+  E.m[6] = C * w.x * w.z - S * w.y, E.m[7] = C * w.y * w.z + S * w.x, E.m[8] = 1.0 - C * (w.x * w.x + w.y * w.y);
+}
+
+// Inverse of a 6 x 6 block upper-triangular matrix [[A, B], [0, D]] (column-major, 3 x 3 blocks) -- the shape of Jlog6 and
+// of Ad in the (linear, angular) ordering, hence of every SE(3) difference Jacobian here: [[A^-1, -A^-1 B D^-1], [0, D^-1]]
+// with the 3 x 3 inverses by cofactors (what the reference's SE3JacobianInverse exploits, se3_jacobian_inverse.hxx).  All
+// indices are compile-time constants: the arrays stay in registers (a general inverse pivots, i.e. indexes at run time,
+// which puts its 72 doubles into scratch memory).
+__device__ __forceinline__ void inv3(const double (&m)[3][3], double (&o)[3][3]) {
+  const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+  const double id = 1.0 / (m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02);
+  o[0][0] = c00 * id, o[1][0] = c01 * id, o[2][0] = c02 * id;
+  o[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id, o[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id, o[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id;
+  o[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id, o[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id, o[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
+}
+__device__ __forceinline__ void inv6_block_ut(const double* J, double* out) {
+  double A[3][3], B[3][3], D[3][3], Ai[3][3], Di[3][3], T[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) A[r][c] = J[r + 6 * c], B[r][c] = J[r + 6 * (c + 3)], D[r][c] = J[r + 3 + 6 * (c + 3)];
+  inv3(A, Ai);
+  inv3(D, Di);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) T[r][c] = Ai[r][0] * B[0][c] + Ai[r][1] * B[1][c] + Ai[r][2] * B[2][c];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      out[r + 6 * c] = Ai[r][c];
+      out[r + 3 + 6 * c] = 0.0;
+      out[r + 3 + 6 * (c + 3)] = Di[r][c];
+      out[r + 6 * (c + 3)] = -(T[r][0] * Di[0][c] + T[r][1] * Di[1][c] + T[r][2] * Di[2][c]);
+    }
 }
 
 // an int of the device model through the scalar cache: the model is read-only while a kernel runs, but the compiler cannot know

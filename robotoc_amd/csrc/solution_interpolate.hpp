@@ -137,60 +137,23 @@ __device__ inline Branch decide(const StoredSolution& st, const double* T0, cons
   return r;
 }
 
-__device__ __forceinline__ M3 quat_R(const double* q) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  M3 R;
-  R.m[0] = 1 - 2 * (y * y + z * z), R.m[1] = 2 * (x * y - z * w), R.m[2] = 2 * (x * z + y * w);
-  R.m[3] = 2 * (x * y + z * w), R.m[4] = 1 - 2 * (x * x + z * z), R.m[5] = 2 * (y * z - x * w);
-  R.m[6] = 2 * (x * z - y * w), R.m[7] = 2 * (y * z + x * w), R.m[8] = 1 - 2 * (x * x + y * y);
-  return R;
-}
-
 // the free-flyer part [x y z qx qy qz qw] of interpolateConfiguration: M1 exp6(alpha log6(M1^-1 M2))
 struct BasePose {
   double px, py, pz, x, y, z, w;
 };
 __device__ __forceinline__ BasePose interpolate_base(const double* q1, const double* q2, double alpha) {
-  const M3 R1 = quat_R(q1 + 3), R2 = quat_R(q2 + 3);
-  M3 R1t;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R1t.m[3 * r + c] = R1.m[3 * c + r];
+  const M3 R1 = rbd::quat_R(q1 + 3);
   const V3 p1 = rbd::ldv3(q1);
+  M3 Rx, Ra;
+  V3 px, pa;
+  rbd::rel(R1, p1, rbd::quat_R(q2 + 3), rbd::ldv3(q2), Rx, px);
   SV lg, unused;
-  rbd::log6_fwd(rbd::mul(R1t, R2), rbd::mulT(R1, rbd::ldv3(q2) - p1), rbd::sv0(), lg, unused);
-  const V3 w = alpha * lg.a, v = alpha * lg.l;
-  const double th2 = rbd::dot(w, w), th = sqrt(th2);
-  // exp3 = I + S K + C K^2, V = I + C K + B K^2 (K = skew w): S = sin t / t, C = (1 - cos t) / t^2, B = (t - sin t) / t^3
-  double S, Cc, B;
-  rbd::exp_coefficients(th2, th, S, Cc, B);
-  const V3 wv = rbd::cross(w, v);
-  const V3 pa = v + Cc * wv + B * rbd::cross(w, wv);
+  rbd::log6_fwd(Rx, px, rbd::sv0(), lg, unused);
+  rbd::exp6(alpha * lg.l, alpha * lg.a, Ra, pa);
   const V3 p = p1 + rbd::mul(R1, pa);
-  M3 Ra;  // I + S K + C (w w^T - t^2 I)
-  Ra.m[0] = 1.0 - Cc * (w.y * w.y + w.z * w.z), Ra.m[1] = Cc * w.x * w.y - S * w.z, Ra.m[2] = Cc * w.x * w.z + S * w.y;
-  Ra.m[3] = Cc * w.x * w.y + S * w.z, Ra.m[4] = 1.0 - Cc * (w.x * w.x + w.z * w.z), Ra.m[5] = Cc * w.y * w.z - S * w.x;
-  Ra.m[6] = Cc * w.x * w.z - S * w.y, Ra.m[7] = Cc * w.y * w.z + S * w.x, Ra.m[8] = 1.0 - Cc * (w.x * w.x + w.y * w.y);
-  const M3 R = rbd::mul(R1, Ra);
-  // the quaternion of R: w > 0 where the trace is positive, else the largest diagonal entry leads
-  double x, y, z, qw;
-  const double tr = R.m[0] + R.m[4] + R.m[8];
-  if (tr > 0.0) {
-    const double s = sqrt(tr + 1.0) * 2.0;
-    qw = 0.25 * s, x = (R.m[7] - R.m[5]) / s, y = (R.m[2] - R.m[6]) / s, z = (R.m[3] - R.m[1]) / s;
-  } else if (R.m[0] >= R.m[4] && R.m[0] >= R.m[8]) {
-    const double s = sqrt(fmax(0.0, 1.0 + R.m[0] - R.m[4] - R.m[8])) * 2.0;
-    x = 0.25 * s, y = (R.m[3] + R.m[1]) / s, z = (R.m[6] + R.m[2]) / s, qw = (R.m[7] - R.m[5]) / s;
-  } else if (R.m[4] >= R.m[8]) {
-    const double s = sqrt(fmax(0.0, 1.0 + R.m[4] - R.m[8] - R.m[0])) * 2.0;
-    y = 0.25 * s, z = (R.m[7] + R.m[5]) / s, x = (R.m[1] + R.m[3]) / s, qw = (R.m[2] - R.m[6]) / s;
-  } else {
-    const double s = sqrt(fmax(0.0, 1.0 + R.m[8] - R.m[0] - R.m[4])) * 2.0;
-    z = 0.25 * s, x = (R.m[2] + R.m[6]) / s, y = (R.m[5] + R.m[7]) / s, qw = (R.m[3] - R.m[1]) / s;
-  }
-  const double n = sqrt(x * x + y * y + z * z + qw * qw);
-  return BasePose{p.x, p.y, p.z, x / n, y / n, z / n, qw / n};
+  double qt[4];
+  rbd::R_quat(rbd::mul(R1, Ra), qt);
+  return BasePose{p.x, p.y, p.z, qt[0], qt[1], qt[2], qt[3]};
 }
 
 __device__ __forceinline__ int contact_rows(unsigned six_rows, int c) { return 3 + 3 * (int)((six_rows >> c) & 1u); }

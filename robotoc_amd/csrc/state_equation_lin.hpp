@@ -27,98 +27,11 @@ struct SeLinArgs {
   int zeroed;            // the KKT record was initialised just before (init_records_kernel: zeros, Fqq = I, Fqv = dt I): only the base corner is written
 };
 
-namespace selin {
-using rbd::M3;
-using rbd::SV;
-using rbd::V3;
-__device__ __forceinline__ M3 quat_R(const double* q) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  M3 R;
-  R.m[0] = 1 - 2 * (y * y + z * z), R.m[1] = 2 * (x * y - z * w), R.m[2] = 2 * (x * z + y * w);
-  R.m[3] = 2 * (x * y + z * w), R.m[4] = 1 - 2 * (x * x + z * z), R.m[5] = 2 * (y * z - x * w);
-  R.m[6] = 2 * (x * z - y * w), R.m[7] = 2 * (y * z + x * w), R.m[8] = 1 - 2 * (x * x + y * y);
-  return R;
-}
-// X = A^-1 B for placements A = (Ra, pa), B = (Rb, pb)
-__device__ __forceinline__ void rel(const M3& Ra, V3 pa, const M3& Rb, V3 pb, M3& R, V3& p) {
-  M3 Rat;
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) Rat.m[3 * r + c] = Ra.m[3 * c + r];
-  R = rbd::mul(Rat, Rb);
-  p = rbd::mulT(Ra, pb - pa);
-}
-__device__ __forceinline__ SV unit_twist(int k) {
-  return SV{rbd::mk(k == 0, k == 1, k == 2), rbd::mk(k == 3, k == 4, k == 5)};
-}
-// in-place inverse of a 6 x 6 column-major matrix (one lane); returns false if singular to working precision
-__device__ inline bool inv6(double* A) {
-  double B[36];
-#pragma unroll
-  for (int e = 0; e < 36; ++e) B[e] = (e % 7 == 0) ? 1.0 : 0.0;
-  for (int c = 0; c < 6; ++c) {
-    int piv = c;
-    double best = fabs(A[c + 6 * c]);
-    for (int r = c + 1; r < 6; ++r)
-      if (fabs(A[r + 6 * c]) > best) best = fabs(A[r + 6 * c]), piv = r;
-    if (!(best > 1e-300)) return false;
-    if (piv != c)
-      for (int k = 0; k < 6; ++k) {
-        double t = A[c + 6 * k];
-        A[c + 6 * k] = A[piv + 6 * k], A[piv + 6 * k] = t;
-        t = B[c + 6 * k];
-        B[c + 6 * k] = B[piv + 6 * k], B[piv + 6 * k] = t;
-      }
-    const double d = 1.0 / A[c + 6 * c];
-    for (int k = 0; k < 6; ++k) A[c + 6 * k] *= d, B[c + 6 * k] *= d;
-    for (int r = 0; r < 6; ++r) {
-      if (r == c) continue;
-      const double f = A[r + 6 * c];
-      for (int k = 0; k < 6; ++k) A[r + 6 * k] -= f * A[c + 6 * k], B[r + 6 * k] -= f * B[c + 6 * k];
-    }
-  }
-  for (int e = 0; e < 36; ++e) A[e] = B[e];
-  return true;
-}
-// Inverse of a 6 x 6 block upper-triangular matrix [[A, B], [0, D]] (column-major, 3 x 3 blocks) -- the shape of Jlog6 and
-// of Ad in the (linear, angular) ordering, hence of every SE(3) difference Jacobian here: [[A^-1, -A^-1 B D^-1], [0, D^-1]]
-// with the 3 x 3 inverses by cofactors (what the reference's SE3JacobianInverse exploits, se3_jacobian_inverse.hxx).  All
-// indices are compile-time constants: the arrays stay in registers (the general inv6 above pivots, i.e. indexes at run time,
-// which puts its 72 doubles into scratch memory).
-__device__ __forceinline__ void inv3(const double (&m)[3][3], double (&o)[3][3]) {
-  const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-  const double id = 1.0 / (m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02);
-  o[0][0] = c00 * id, o[1][0] = c01 * id, o[2][0] = c02 * id;
-  o[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id, o[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id, o[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id;
-  o[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id, o[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id, o[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
-}
-__device__ __forceinline__ void inv6_block_ut(const double* J, double* out) {
-  double A[3][3], B[3][3], D[3][3], Ai[3][3], Di[3][3], T[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) A[r][c] = J[r + 6 * c], B[r][c] = J[r + 6 * (c + 3)], D[r][c] = J[r + 3 + 6 * (c + 3)];
-  inv3(A, Ai);
-  inv3(D, Di);
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) T[r][c] = Ai[r][0] * B[0][c] + Ai[r][1] * B[1][c] + Ai[r][2] * B[2][c];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      out[r + 6 * c] = Ai[r][c];
-      out[r + 3 + 6 * c] = 0.0;
-      out[r + 3 + 6 * (c + 3)] = Di[r][c];
-      out[r + 6 * (c + 3)] = -(T[r][0] * Di[0][c] + T[r][1] * Di[1][c] + T[r][2] * Di[2][c]);
-    }
-}
-}  // namespace selin
 
 static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs a) {
-  using namespace selin;
+  using rbd::M3;
+  using rbd::SV;
+  using rbd::V3;
   __shared__ double J[3][36];  // Fqq, Fqq_prev, d/dq0 of (q (-) q_next): 6 x 6, column-major
   const int lane = threadIdx.x;
   const int b = blockIdx.x / a.rv.nstages, st = blockIdx.x % a.rv.nstages;
@@ -141,10 +54,10 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
       const double* qp = s - a.rv.L.sol.stride + a.rv.sol_off(RTOC_SOL_Q);
       M3 R0;
       V3 p0;
-      rel(quat_R(q + 3), rbd::ldv3(q), quat_R(qp + 3), rbd::ldv3(qp), R0, p0);
+      rbd::rel(rbd::quat_R(q + 3), rbd::ldv3(q), rbd::quat_R(qp + 3), rbd::ldv3(qp), R0, p0);
       if (lane < 6) {
         SV val, der;
-        rbd::log6_fwd(R0, p0, rbd::sv0() - rbd::act_inv(R0, p0, unit_twist(lane)), val, der);
+        rbd::log6_fwd(R0, p0, rbd::sv0() - rbd::act_inv(R0, p0, rbd::unit_twist(lane)), val, der);
         const double c0[6] = {der.l.x, der.l.y, der.l.z, der.a.x, der.a.y, der.a.z};
 #pragma unroll
         for (int r = 0; r < 6; ++r) J[1][r + 6 * lane] = c0[r];
@@ -159,7 +72,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
       if (lane == 0 && a.rv.se3) {
         double* const se = a.rv.se3 + rec * RTOC_SE3_STRIDE;
         double A[36];
-        inv6_block_ut(J[1], A);
+        rbd::inv6_block_ut(J[1], A);
 #pragma unroll
         for (int e = 0; e < 36; ++e) se[e] = 0.0, se[36 + e] = A[e];
       }
@@ -215,12 +128,12 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     for (int i = lane; i < nx; i += 64) a.rv.dx0[(size_t)b * nx + i] = a.x0[(size_t)b * nx + i] - (i < nv ? q[i] : v[i - nv]);
   if (!a.rv.floating()) return;
   // ---- the free-flyer base: differences on SE(3) ----
-  const M3 R = quat_R(q + 3), Rn = quat_R(qn + 3), Rp = quat_R(qp + 3);
+  const M3 R = rbd::quat_R(q + 3), Rn = rbd::quat_R(qn + 3), Rp = rbd::quat_R(qp + 3);
   const V3 p = rbd::ldv3(q), pn = rbd::ldv3(qn), pp = rbd::ldv3(qp);
   M3 R1, R0;
   V3 p1, p0;
-  rel(Rn, pn, R, p, R1, p1);  // X1 = M_next^-1 M
-  rel(R, p, Rp, pp, R0, p0);  // X0 = M^-1 M_prev
+  rbd::rel(Rn, pn, R, p, R1, p1);  // X1 = M_next^-1 M
+  rbd::rel(R, p, Rp, pp, R0, p0);  // X0 = M^-1 M_prev
   __shared__ double sLog[2][6];  // log6(X1), log6(X0)
   if (lane < 18) {
     // 18 lanes, one forward-mode evaluation through the log each: matrix m, column c
@@ -228,7 +141,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     const int m = lane / 6, c = lane % 6;
     const M3& Rm = m == 1 ? R0 : R1;
     const V3 pm = m == 1 ? p0 : p1;
-    const SV e = unit_twist(c);
+    const SV e = rbd::unit_twist(c);
     const SV tw = m == 0 ? e : rbd::sv0() - rbd::act_inv(Rm, pm, e);
     SV val, der;
     rbd::log6_fwd(Rm, pm, tw, val, der);
@@ -261,7 +174,7 @@ static __global__ __launch_bounds__(64) void state_equation_lin_kernel(SeLinArgs
     const int which = lane - 32;
     double* const se = a.rv.se3 + rec * RTOC_SE3_STRIDE;
     double A[36];
-    inv6_block_ut(J[which == 0 ? 2 : 1], A);
+    rbd::inv6_block_ut(J[which == 0 ? 2 : 1], A);
 #pragma unroll
     for (int e = 0; e < 36; ++e) se[36 * which + e] = A[e];
     if (which == 1 && st == 0 && a.rv.dx0 && a.x0) {

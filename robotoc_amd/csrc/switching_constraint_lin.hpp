@@ -11,7 +11,7 @@
 // dIntegrate_dv = Jexp6(dq_b) = Jlog6(exp6(dq_b))^-1 (six forward-mode evaluations through the log, one 6 x 6 inverse);
 // identities on the joints.  Then the multiplier terms (:52-53) and the STO sensitivities (:54-62).
 // Base-block transport: see RTOC_OPT_SWITCHING_TRANSPORT (rtoc.h) -- the reference's composition by default.
-// exp6(dq_b) takes its coefficients from rbd::exp_coefficients (rigid_body_math.hpp): the series below |w| = 1e-3,
+// exp6(dq_b) is rbd::exp6 (rigid_body_math.hpp), its coefficients rbd::exp_coefficients: the series below |w| = 1e-3,
 // 2 sin^2(t/2) / t^2 above.  dq_b of a base that translates and barely turns has |w| of 1e-7 to 1e-5, where (1 - cos t) / t^2
 // put q+, P and, through log6_fwd(E, pe), both transports off by 1e-16 |v| / t.  Held to a 50-digit reference from angle 0 to
 // pi - 1e-3 (tests/test_lie_exp_branch_points.py): P within 0.0044 of 1e-13 max(1, |p|, |v|, |r_c|), Phiq within 0.0089 and
@@ -19,7 +19,10 @@
 // Mapping: one wave per (instance, switching grid point), one lane per dof: the lane carries its column of every body's
 // Jacobian along the depth-first walk (body-frame twist per unit rate of the dof), values once per tree level in LDS.
 #pragma once
-#include "state_equation_lin.hpp"
+#include "device_utils.hpp"
+#include "record_view.hpp"
+#include "rigid_body_math.hpp"
+#include "rigid_body_model.hpp"
 
 namespace rtoc {
 
@@ -36,9 +39,11 @@ __host__ __device__ constexpr size_t sw_lds_bytes(int nlevels, int njoints, int 
 }
 
 static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwLinArgs a) {
-  using namespace selin;
   using rbd::CP;
   using rbd::JP;
+  using rbd::M3;
+  using rbd::SV;
+  using rbd::V3;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   // launched over the grid points that carry a switching constraint only (sel), or over all of them (nsel == 0)
@@ -83,24 +88,8 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   M3 Rb;    // base rotation at q+
   V3 pb = rbd::mk(0, 0, 0);
   if (a.md.floating) {
-    const V3 vl = rbd::mk(sdq[0], sdq[1], sdq[2]), w = rbd::mk(sdq[3], sdq[4], sdq[5]);
-    const double th2 = rbd::dot(w, w), th = sqrt(th2);
-    double sa, A, B;
-    rbd::exp_coefficients(th2, th, sa, A, B);
-    const V3 wxv = rbd::cross(w, vl);
-    pe = vl + A * wxv + B * rbd::cross(w, wxv);
-    // exp(w) = I + sin t / t [w]x + (1 - cos t) / t^2 [w]x^2
-    const double wx[9] = {0, -w.z, w.y, w.z, 0, -w.x, -w.y, w.x, 0};
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        double w2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) w2 += wx[3 * r + k] * wx[3 * k + c];
-        E.m[3 * r + c] = (r == c ? 1.0 : 0.0) + sa * wx[3 * r + c] + A * w2;
-      }
-    const M3 R0 = quat_R(s + a.rv.sol_off(RTOC_SOL_Q) + 3);
+    rbd::exp6(rbd::ldv3(sdq), rbd::ldv3(sdq + 3), E, pe);
+    const M3 R0 = rbd::quat_R(s + a.rv.sol_off(RTOC_SOL_Q) + 3);
     Rb = rbd::mul(R0, E);
     pb = rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_Q)) + rbd::mul(R0, pe);
   }
@@ -121,15 +110,12 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
       Rj = Rb;
       pj = pb;
     } else {
-      const V3 ax = rbd::ldv3(&JM(i, 12));
-      const double th = sqp[iq], c = cos(th), sn = sin(th), t = 1.0 - c;
-      Rj.m[0] = t * ax.x * ax.x + c, Rj.m[1] = t * ax.x * ax.y - sn * ax.z, Rj.m[2] = t * ax.x * ax.z + sn * ax.y;
-      Rj.m[3] = t * ax.x * ax.y + sn * ax.z, Rj.m[4] = t * ax.y * ax.y + c, Rj.m[5] = t * ax.y * ax.z - sn * ax.x;
-      Rj.m[6] = t * ax.x * ax.z - sn * ax.y, Rj.m[7] = t * ax.y * ax.z + sn * ax.x, Rj.m[8] = t * ax.z * ax.z + c;
+      const double th = sqp[iq];
+      Rj = rbd::revolute_R(rbd::ldv3(&JM(i, 12)), sin(th), cos(th));
     }
-    const M3 Rp = rbd::ldm3(&JM(i, 0));
-    const M3 R = rbd::mul(Rp, Rj);
-    const V3 p = rbd::mul(Rp, pj) + rbd::ldv3(&JM(i, 9));
+    M3 R;
+    V3 p;
+    rbd::joint_placement(&JM(i, 0), Rj, pj, R, p);
     M3 oR = R;
     V3 op = p;
     SV Jc = rbd::sv0();
@@ -139,7 +125,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
       op = rbd::ldv3(&LV(d - 1, 21)) + rbd::mul(oRp, p);
       Jc = rbd::act_inv(R, p, SV{rbd::mk(LT(d - 1, 0), LT(d - 1, 1), LT(d - 1, 2)), rbd::mk(LT(d - 1, 3), LT(d - 1, 4), LT(d - 1, 5))});
     }
-    if (own) Jc = Jc + (ff ? unit_twist(j - iv) : SV{rbd::mk(0, 0, 0), rbd::ldv3(&JM(i, 12))});
+    if (own) Jc = Jc + (ff ? rbd::unit_twist(j - iv) : SV{rbd::mk(0, 0, 0), rbd::ldv3(&JM(i, 12))});
 #pragma unroll
     for (int k = 0; k < 9; ++k) LV(d, k) = R.m[k], LV(d, 12 + k) = oR.m[k];
     LV(d, 9) = p.x, LV(d, 10) = p.y, LV(d, 11) = p.z, LV(d, 21) = op.x, LV(d, 22) = op.y, LV(d, 23) = op.z;
@@ -184,10 +170,10 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   }
   // ---- transports of the base block: Tq = Ad_{exp(dq_b)}^-1, Jr = Jlog6(exp6(dq_b))^-1 ----
   if (a.md.floating && lane < 6) {
-    const SV t = rbd::act_inv(E, pe, unit_twist(lane));
+    const SV t = rbd::act_inv(E, pe, rbd::unit_twist(lane));
     const double tc[6] = {t.l.x, t.l.y, t.l.z, t.a.x, t.a.y, t.a.z};
     SV val, der;
-    rbd::log6_fwd(E, pe, unit_twist(lane), val, der);
+    rbd::log6_fwd(E, pe, rbd::unit_twist(lane), val, der);
     const double jc[6] = {der.l.x, der.l.y, der.l.z, der.a.x, der.a.y, der.a.z};
 #pragma unroll
     for (int r = 0; r < 6; ++r) sT[r + 6 * lane] = tc[r], sT[36 + r + 6 * lane] = jc[r];
@@ -195,7 +181,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   __syncthreads();
   if (a.md.floating && lane == 0) {   // Jlog6 is block upper-triangular in the (linear, angular) ordering: 3 x 3 cofactor inverses
     double A[36];
-    inv6_block_ut(sT + 36, A);
+    rbd::inv6_block_ut(sT + 36, A);
 #pragma unroll
     for (int e = 0; e < 36; ++e) sT[36 + e] = A[e];
   }

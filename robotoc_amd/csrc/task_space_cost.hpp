@@ -156,23 +156,18 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   for (int i = lane; i < nj; i += LW) {
     const double* J = md.joint[i];
     const int type = (int)J[28], iq = (int)J[29];
-    double Rj[9], pj[3] = {0.0, 0.0, 0.0};
+    rbd::M3 Rj;
+    double pj[3] = {0.0, 0.0, 0.0};
     if (type == RTOC_JOINT_FREE_FLYER) {
-      const double x = q[iq + 3], y = q[iq + 4], z = q[iq + 5], w = q[iq + 6];
-      Rj[0] = 1 - 2 * (y * y + z * z), Rj[1] = 2 * (x * y - z * w), Rj[2] = 2 * (x * z + y * w);
-      Rj[3] = 2 * (x * y + z * w), Rj[4] = 1 - 2 * (x * x + z * z), Rj[5] = 2 * (y * z - x * w);
-      Rj[6] = 2 * (x * z - y * w), Rj[7] = 2 * (y * z + x * w), Rj[8] = 1 - 2 * (x * x + y * y);
+      Rj = rbd::quat_R(q + iq + 3);
       pj[0] = q[iq], pj[1] = q[iq + 1], pj[2] = q[iq + 2];
     } else {
       double sn, cs;
       sincos(q[iq], &sn, &cs);
-      const double ax = J[12], ay = J[13], az = J[14], oc = 1.0 - cs;
-      Rj[0] = cs + oc * ax * ax, Rj[1] = oc * ax * ay - sn * az, Rj[2] = oc * ax * az + sn * ay;
-      Rj[3] = oc * ay * ax + sn * az, Rj[4] = cs + oc * ay * ay, Rj[5] = oc * ay * az - sn * ax;
-      Rj[6] = oc * az * ax - sn * ay, Rj[7] = oc * az * ay + sn * ax, Rj[8] = cs + oc * az * az;
+      Rj = rbd::revolute_R(rbd::ldv3(J + 12), sn, cs);
     }
     for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) Rw[9 * i + 3 * r + c] = J[3 * r] * Rj[c] + J[3 * r + 1] * Rj[3 + c] + J[3 * r + 2] * Rj[6 + c];
+      for (int c = 0; c < 3; ++c) Rw[9 * i + 3 * r + c] = J[3 * r] * Rj.m[c] + J[3 * r + 1] * Rj.m[3 + c] + J[3 * r + 2] * Rj.m[6 + c];
       pw[3 * i + r] = J[3 * r] * pj[0] + J[3 * r + 1] * pj[1] + J[3 * r + 2] * pj[2] + J[9 + r];
     }
   }
@@ -223,9 +218,8 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
         const rbd::V3 pr = rbd::ldv3(tab ? tsc::table_entry(a, k, b, st).p : T.x0);
         // X = X_ref^-1 oMf
         rbd::M3 XR;
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c) XR.m[3 * r + c] = Rr.m[r] * Rf.m[c] + Rr.m[3 + r] * Rf.m[3 + c] + Rr.m[6 + r] * Rf.m[6 + c];
-        const rbd::V3 Xp = rbd::mulT(Rr, xf - pr);
+        rbd::V3 Xp;
+        rbd::rel(Rr, pr, Rf, xf, XR, Xp);
         // one inlined log6_fwd: the loop is kept rolled, and its first trip (every lane takes it, with a zero column where the
         // lane has no dof) also yields d
         rbd::SV wd = rbd::sv0();
