@@ -253,6 +253,16 @@ typedef struct rtoc_layout {
 
 static inline RTOC_HD RTOC_CONSTEXPR int rtoc_pad8(int n) { return (n + 7) & ~7; }
 
+/* ---- the record of rtoc_control_policy (rtoc_robot.h), one per instance: ControlPolicy's members
+ *      (include/robotoc/mpc/control_policy.hpp:65-90) [tauJ | qJ | dqJ | Kp | Kd], every field on a 64-byte boundary and its
+ *      padding zero; tauJ, qJ, dqJ nu entries, Kp and Kd nu x nu column-major with leading dimension nu ---- */
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_tauj_off(int nu) { return 0 * nu; }
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_qj_off(int nu) { return rtoc_pad8(nu); }
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_dqj_off(int nu) { return 2 * rtoc_pad8(nu); }
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_kp_off(int nu) { return 3 * rtoc_pad8(nu); }
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_kd_off(int nu) { return 3 * rtoc_pad8(nu) + rtoc_pad8(nu * nu); }
+static inline RTOC_HD RTOC_CONSTEXPR int rtoc_control_policy_stride(int nu) { return 3 * rtoc_pad8(nu) + 2 * rtoc_pad8(nu * nu); }
+
 static inline RTOC_HD RTOC_CONSTEXPR void rtoc_record_finish(rtoc_record_layout* r, const int* sizes, int n) {
   int o = 0;
   for (int i = 0; i < n; ++i) {

@@ -308,6 +308,42 @@ int rtoc_solution_interpolate(rtoc_ctx* ctx, double t0);
 int rtoc_solution_stored(const rtoc_ctx* ctx, int* nstages);
 int rtoc_solution_forget(rtoc_ctx* ctx);
 
+/* ---- ControlPolicy on the device (src/mpc/control_policy.cpp:24-60): what an MPC hands to the robot or the simulator ----
+ * The feed-forward joint torque tauJ, the joint references qJ, dqJ and the gains Kp, Kd cut out of the LQR policy of the Riccati
+ * recursion, of every instance at its own query time, from RTOC_BUF_SOL and RTOC_BUF_RIC as they stand and without either leaving the
+ * device; and the law the simulator applies with them at every control tick, u = tauJ - Kp (qJ - q) - Kd (dqJ - v)
+ * (bindings/python/robotoc_sim/mpc_simulation.py:6-11).
+ * Grid times: tg[0] = t0, tg[i + 1] = tg[i] + dt[i], summed in this order in double (the sum of rtoc_solution_store); with an STO
+ * problem set the time steps are every instance's own, as the device holds them, else the grid's and shared by the batch.
+ * N: the reference's time_discretization.N() (:28), the number of time stages, not of grid points.  Per query time t:
+ * t < tg[0]: record 0 (:31-38); else the first i in 1 .. N - 2 with t < tg[i] whose record i - 1 is no impact grid point (:39-40):
+ * alpha = (tg[i] - t) / (tg[i] - tg[i - 1]), not clamped, and every output alpha rec[i - 1] + (1 - alpha) rec[i] (:41-52); else
+ * record N - 1 (:55-59).  Of a record: tauJ = RTOC_SOL_U; qJ, dqJ = the last nu entries of RTOC_SOL_Q (nq of them: nv + 1 with a
+ * free-flyer) and RTOC_SOL_V; Kp = columns nv - nu .. nv - 1 and Kd = columns 2nv - nu .. 2nv - 1 of RTOC_RIC_K (Kq().rightCols,
+ * Kv().rightCols).  These doubles of the one or two records are read and nothing else.
+ * Not the reference's, which reads u and K of impact grid points there, where they are undefined: where record i of
+ * the chosen interval is an impact grid point the policy is record i - 1 unblended; where the fallback record N - 1 is one, it is
+ * record N - 2.
+ * rtoc_control_policy: out[count][stride] = [tauJ | qJ | dqJ | Kp | Kd] (rtoc_layout.h: rtoc_control_policy_stride and the field offsets;
+ * every field on a 64-byte boundary, Kp and Kd nu x nu column-major with leading dimension nu, the padding zero).
+ * rtoc_control_input: u[count][nu] at the measured states x[count][nq + nv] (laid out as for rtoc_set_initial_state); Kp and Kd are
+ * not written anywhere.
+ * t[1] is shared by the batch (per_instance = 0) or t[count] is given per instance (1); the calls act on the first count <= batch
+ * instances.  flags = 0: host pointers; t (and x) are validated as finite and the call returns with the result on the host.
+ * flags = RTOC_POLICY_DEVICE_PTRS: every pointer is a device pointer, nothing is inspected, the call is asynchronous on the
+ * context's stream, and an instance with a non-finite t gets NaN in all of its outputs.  (The first call of a context, and the
+ * first with an STO problem set, allocates the scratch for the grid times, which synchronises the device; later calls only launch.)
+ * Refusals come ahead of any launch, and a refused call writes nothing: RTOC_ERR_NOT_READY without a grid, without RTOC_BUF_RIC or
+ * RTOC_BUF_SOL, and with an STO problem whose time steps date from before the last change of the grid (the rule of
+ * rtoc_solution_store); RTOC_ERR_BAD_ARG on a ParNMPC horizon, for N < 1 or N > nstages - 1, count outside 1 .. batch, per_instance
+ * outside {0, 1}, a null pointer, an unknown flag bit, a non-finite t0, a shape with dims.nu < 1 and, with host pointers, a
+ * non-finite t or x.
+ * The calls hold no state (rtoc_clone has nothing to copy). */
+#define RTOC_POLICY_DEVICE_PTRS 1
+int rtoc_control_policy(rtoc_ctx* ctx, double t0, const double* t, int per_instance, int N, double* out, int count, int flags);
+int rtoc_control_input(rtoc_ctx* ctx, double t0, const double* t, int per_instance, int N, const double* x, double* u, int count,
+                       int flags);
+
 /* ---- filter line search on the device (src/line_search/line_search.cpp:31-83, LineSearchSettings) ----
  * rtoc_contact_eval_ocp: DirectMultipleShooting::evalOCP's performance index (direct_multiple_shooting.cpp:100-126) of every
  * instance -- host_cost[count] = cost + cost_barrier, host_violation[count] = primal_feasibility (l1).  trial = 0: of the iterate

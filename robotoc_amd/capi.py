@@ -41,6 +41,7 @@ EXPORTS = [
     "rtoc_parnmpc_set_horizon", "rtoc_parnmpc_init_constraints", "rtoc_parnmpc_init_backward_correction", "rtoc_parnmpc_set_aux_mat",
     "rtoc_parnmpc_get_aux_mat", "rtoc_parnmpc_eval_kkt", "rtoc_parnmpc_backward_correction", "rtoc_parnmpc_update_solution",
     "rtoc_solution_store", "rtoc_solution_interpolate", "rtoc_solution_stored", "rtoc_solution_forget",
+    "rtoc_control_policy", "rtoc_control_input",
 ]
 
 
@@ -196,6 +197,8 @@ def lib():
         L.rtoc_solution_interpolate.argtypes = [vp, C.c_double]
         L.rtoc_solution_stored.argtypes = [vp, C.POINTER(C.c_int)]
         L.rtoc_solution_forget.argtypes = [vp]
+        L.rtoc_control_policy.argtypes = [vp, C.c_double, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]
+        L.rtoc_control_input.argtypes = [vp, C.c_double, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]
         _LIB = L
     return _LIB
 
@@ -536,6 +539,43 @@ class Context:
 
     def solution_forget(self):
         _chk(lib().rtoc_solution_forget(self._h))
+
+    # ---- ControlPolicy on the device (include/rtoc_robot.h: rtoc_control_policy / rtoc_control_input) ----
+    def _policy_times(self, t, count):
+        """(t as a contiguous array, per_instance, count): a scalar is shared by the batch, else one time per instance"""
+        t = np.asarray(t, dtype=np.float64)   # (ascontiguousarray would turn a scalar into one time per instance of a batch of 1)
+        if t.ndim == 0:
+            return t.reshape(1), 0, self.batch if count is None else int(count)
+        if t.ndim != 1 or (count is not None and t.size != count):
+            raise ValueError("t must be a scalar or one time per instance, not %s" % (t.shape,))
+        return np.ascontiguousarray(t), 1, t.size
+
+    def control_policy(self, t0, t, N, count=None):
+        """rtoc_control_policy: the policy of the first `count` instances (default: all with a scalar `t`, else len(t)) at time `t`
+        (a scalar shared by the batch, or one time per instance) over the grid times summed from t0, N = the number of time stages.
+        Returns {"tauJ", "qJ", "dqJ": [count, nu], "Kp", "Kd": [count, nu, nu]}."""
+        from .types import control_policy_offsets
+        t, per_instance, count = self._policy_times(t, count)
+        nu = self.dims.nu
+        off, stride = control_policy_offsets(nu)
+        out = np.empty((count, stride))
+        _chk(lib().rtoc_control_policy(self._h, float(t0), t.ctypes.data, per_instance, int(N), out.ctypes.data, count, 0))
+        res = {k: out[:, off[k]:off[k] + nu].copy() for k in ("tauJ", "qJ", "dqJ")}
+        for k in ("Kp", "Kd"):   # column-major, leading dimension nu
+            res[k] = np.ascontiguousarray(out[:, off[k]:off[k] + nu * nu].reshape(count, nu, nu).swapaxes(1, 2))
+        return res
+
+    def control_input(self, t0, t, N, x):
+        """rtoc_control_input: u [count, nu] = tauJ - Kp (qJ - q) - Kd (dqJ - v) of the policy at `t` (as for control_policy) at the
+        measured states x [count, nq + nv] (laid out as for set_initial_state)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nx = 2 * self.dims.nv + (1 if self.dims.np == 6 else 0)
+        if x.ndim != 2 or x.shape[1] != nx:
+            raise ValueError("x must be [count, %d], not %s" % (nx, x.shape))
+        t, per_instance, count = self._policy_times(t, x.shape[0])
+        u = np.empty((count, self.dims.nu))
+        _chk(lib().rtoc_control_input(self._h, float(t0), t.ctypes.data, per_instance, int(N), x.ctypes.data, u.ctypes.data, count, 0))
+        return u
 
     # ---- rigid-body linearisation (include/rtoc_robot.h) ----
     def set_robot_model(self, model):

@@ -339,10 +339,17 @@ struct InterpState {
   DevBuf<double> d_interp_t;     // [batch][max_stages]
 };
 
+// ControlPolicy on the device (rtoc_control_policy / rtoc_control_input; control_policy.hpp; rt_control_policy.hip).  The calls hold
+// no state: nothing here is cloned, all of it is scratch of one call
+struct PolicyState {
+  DevBuf<double> d_policy_tg;     // grid times: [max_stages], with an STO problem [batch][max_stages] ([nstages] or [count][nstages] in use)
+  DevBuf<double> d_policy_stage;  // host-pointer calls: t [batch], x [batch][nq + nv], the result [batch][policy stride]
+};
+
 }  // namespace rtoc
 
 struct rtoc_ctx : rtoc::CtxStreams, rtoc::CtxOptions, rtoc::SweepState, rtoc::ConstraintState, rtoc::ModelState, rtoc::TaskState,
-                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState, rtoc::InterpState {
+                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState, rtoc::InterpState, rtoc::PolicyState {
   rtoc_dims dims = {};
   rtoc_layout L = {};
   const rtoc::KernelSet* ks = nullptr;

@@ -47,14 +47,25 @@ struct GridInfo {
 class TimeDiscretization {
  public:
   TimeDiscretization() {}
-  explicit TimeDiscretization(const std::vector<GridInfo>& grid) : grid_(grid) {}
+  explicit TimeDiscretization(const std::vector<GridInfo>& grid, const int N = 0) : grid_(grid), N_(N) {}
   int size() const { return static_cast<int>(grid_.size()); }
+  // the number of time stages the horizon was cut into (time_discretization.hpp:67-69), which events do not change.  A
+  // discretisation built from a list of grid points alone (a stage dump) was not told it and counts back what discretize adds: one
+  // grid point per lift, two per impact (time_discretization.cpp:45).  That is one short per event that fell on a grid time and
+  // replaced a grid point instead (:95-98, :114-117) -- INTEGRATION.md, "ControlPolicy"
+  int N() const {
+    if (N_ > 0) return N_;
+    int n = size() - 1;
+    for (const GridInfo& g : grid_) n -= g.type == GridType::Impact ? 2 : (g.type == GridType::Lift ? 1 : 0);
+    return n;
+  }
   const GridInfo& operator[](int i) const { return grid_.at(i); }
   const GridInfo& grid(int i) const { return grid_.at(i); }
   std::vector<GridInfo>& grids() { return grid_; }
 
  private:
   std::vector<GridInfo> grid_;
+  int N_ = 0;
 };
 
 class Vec {

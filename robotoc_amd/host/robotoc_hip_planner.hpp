@@ -222,7 +222,7 @@ inline TimeDiscretization discretize(const ContactSequence& cs, const double T, 
     o.dims = o.switching_constraint ? cs.dimf(cs.impactMask(imp_ev[o.impact_index + 1])) : 0;
     o.stage = i;
   }
-  return TimeDiscretization(g);
+  return TimeDiscretization(g, N);
 }
 
 inline double maxTimeStep(const TimeDiscretization& td) {   // time_discretization.hpp:121-127

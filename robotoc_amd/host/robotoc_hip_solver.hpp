@@ -744,6 +744,9 @@ class OCPSolver {
     return cs ? cs->eventTimes() : none;
   }
   const TimeDiscretization& getTimeDiscretization() const { return time_discretization_; }
+  // the t of the last discretize(t): where the grid times the device sums start (rtoc_solution_store, rtoc_control_policy).  Not
+  // GridInfo::t of grid point 0, which a source that replays recorded stage data leaves at zero
+  double discretizationTime() const { return t_; }
   unsigned status() const { return riccati_recursion_.status(); }
   rtoc_ctx* context() const { return dev_ ? dev_->get() : nullptr; }
 

@@ -305,6 +305,25 @@ class OCPSolver:
     def get_solution(self):
         return self.ctx.download_records(BUF_SOL, "sol")
 
+    # ---- what the MPC hands to the controller (src/mpc/control_policy.cpp:24-60; every gait MPC's getControlPolicy(t)) ----
+    def get_control_policy(self, t):
+        """ControlPolicy(ocp_solver, t) of every instance, evaluated on the device (rtoc_control_policy): `t` a scalar or one time
+        per instance; returns {"tauJ", "qJ", "dqJ": [batch, nu], "Kp", "Kd": [batch, nu, nu]}.  The grid times run from the t of the
+        last discretisation, with switching-time optimisation over every instance's own time steps."""
+        return self.ctx.control_policy(self.t0, self._policy_t(t), self.N)
+
+    def get_control_input(self, t, q, v):
+        """u [batch, nu] = tauJ - Kp (qJ - q) - Kd (dqJ - v) of that policy at the measured q [batch, nq], v [batch, nv]
+        (bindings/python/robotoc_sim/mpc_simulation.py:6-11; rtoc_control_input: the gains are never written anywhere)"""
+        x = np.concatenate([np.asarray(q, dtype=float).reshape(self.batch, -1), np.asarray(v, dtype=float).reshape(self.batch, -1)], axis=1)
+        return self.ctx.control_input(self.t0, self._policy_t(t), self.N, x)
+
+    def _policy_t(self, t):
+        t = np.asarray(t, dtype=float)
+        if t.ndim == 1 and t.size != self.batch:
+            raise ValueError("t must be a scalar or one time per instance (%d), not %d values" % (self.batch, t.size))
+        return t
+
     def init_constraints(self):
         """OCPSolver::initConstraints (ocp_solver.cpp:105-108)"""
         if self.has_rows:

@@ -178,6 +178,13 @@ def cone_stride(nv, max_contacts):
 WRENCH_ROWS, FRICTION_ROWS = 17, 5
 
 
+def control_policy_offsets(nu):
+    """include/rtoc_layout.h: rtoc_control_policy_*_off and rtoc_control_policy_stride -- ({field: offset}, stride) of the record
+    [tauJ | qJ | dqJ | Kp | Kd] of rtoc_control_policy"""
+    pad, padm = (nu + 7) & ~7, (nu * nu + 7) & ~7
+    return dict(tauJ=0, qJ=pad, dqJ=2 * pad, Kp=3 * pad, Kd=3 * pad + padm), 3 * pad + 2 * padm
+
+
 def wrench_cone_stride(max_contacts):
     """include/rtoc_layout.h: rtoc_wrench_cone_stride"""
     return (max_contacts * WRENCH_ROWS * 6 + 7) & ~7
