@@ -69,7 +69,11 @@ extern "C" {
 #define RTOC_ERR_RCCL (-6)
 #define RTOC_ERR_IO (-7)
 
-/* ---- per-instance numerical status bits (rtoc_status) --------------------- */
+/* ---- per-instance numerical status bits (rtoc_status) ---------------------
+ * A bit is raised on the instance whose records caused it and on no other: every other instance of the batch keeps status 0,
+ * and its output records are bit for bit those of the same call on well-posed data, whichever kernel runs and whether or not
+ * the instances share a workgroup or a sweep chunk (tests/test_status_bits.py).  What the flagged instance's own output
+ * records hold is unspecified.  Bits are sticky: once set they stay set, through later calls, until rtoc_clear_status. */
 #define RTOC_STAT_QUU_NOT_SPD 0x1u  /* LLT(Quu) hit a non-positive pivot (riccati_factorizer.cpp:49-50) */
 #define RTOC_STAT_S_NOT_SPD 0x2u    /* LLT(S) of the switching-constraint Schur complement (:63-64)   */
 #define RTOC_STAT_NAN 0x4u          /* NaN/Inf in K, k, M, m (:75-79)                                   */
@@ -352,7 +356,8 @@ int rtoc_compute_initial_state_direction(rtoc_ctx* ctx);
  * returns it in *structured (may be NULL).  Synchronises the stream. */
 int rtoc_check_fxx_structure(rtoc_ctx* ctx, int* structured);
 
-/* Per-instance status words (RTOC_STAT_* bits), synchronises the stream. */
+/* Per-instance status words (RTOC_STAT_* bits), synchronises the stream.  The kernels only ever OR bits in: a word keeps what
+ * earlier calls raised until rtoc_clear_status zeroes all of them. */
 int rtoc_status(rtoc_ctx* ctx, uint32_t* host_flags, int count);
 int rtoc_clear_status(rtoc_ctx* ctx);
 int rtoc_sync(rtoc_ctx* ctx);

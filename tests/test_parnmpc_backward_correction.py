@@ -12,12 +12,11 @@ import numpy as np
 import pytest
 
 import parnmpc_restatement as pn
-from robotoc_amd.types import BUF_DIR, BUF_KKT, BUF_SOL, Dims, Records
+from robotoc_amd.types import BUF_DIR, BUF_KKT, BUF_SOL, STAT_PARNMPC_H_NOT_SPD, Dims, Records
 from test_parnmpc_restatement import random_spd, reference_error
 
 pytestmark = pytest.mark.gpu
 
-STAT_PARNMPC_H_NOT_SPD, STAT_PARNMPC_S_NOT_SPD = 0x20, 0x40
 DT = 0.05
 
 
