@@ -16,8 +16,9 @@
 //    the place of A, which is dead by then -- and each wave rebuilds its own copy of P+ = sym(F) from there (direct and transposed reads),
 //    forming z = s+ - P+ Fx of the next grid point as the elements pass.
 //
-// Five workgroup barriers per stage.  Same lane algebra as riccati_backward_rw.hpp, which tests/rw_lane_model.py verifies for this
-// shape (the direct H^T product: direct_ht).  Shared LDS: the dense rows of A / the F exchange, two strips, the grid table, Bv / wave
+// Five workgroup barriers per stage.  The lane algebra is the ONE copy riccati_backward_rw.hpp holds -- RwLanes and the fragments
+// riccati_rw_*.inc, included here with this kernel's places and its split of F --, which tests/rw_lane_model.py verifies for this shape
+// too (the direct H^T product: direct_ht).  Shared LDS: the dense rows of A / the F exchange, two strips, the grid table, Bv / wave
 // 1's column tiles of H^T; per wave: G / Y / scratch / vectors (wave 0), Qxu / wave 0's column tiles of H^T (wave 1) -- the landing
 // zone of the wave's Qxx panels.  79 KB per instance.
 //
@@ -84,6 +85,7 @@ template <int NV, int NU, int NS, int W>
 __device__ __forceinline__ void rw2_body(BwdArgs a) {
   using C = RwCfg<NV, NU>;
   using M = Rw2Lds<NV, NU, NS>;
+  using L = RwLanes<NV, NU>;
   static_assert(C::T == 5 || C::T == 4, "column tiles {0 .. (T-1)/2} | the rest");
   // column tiles of F (and of K, and row tiles of the P stores) this wave owns
   constexpr int TSPLIT = (C::T - 1) / 2;   // T = 5: wave 0 owns {0, 1, 2} (6 upper tiles), wave 1 {3, 4} (9)
@@ -103,12 +105,6 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
   static_assert(NU * LDB <= C::pad8(NV * NU + 1), "H^T of wave 1's column tiles fits the place of Bv");
   static_assert(C::NX * NU <= M::P_Z && KL_QXU_EVEN<NV, NU, NS>(), "Qxu fits wave 1's block ahead of z");
   auto own = [](int t) constexpr { return (t <= TSPLIT) == (W == 0); };
-  constexpr int NX = C::NX, NP_ = C::NP, T = C::T, TU = C::TU, KG = C::KG, KGU = C::KGU, G0 = C::G0, G1 = C::G1, NUC = C::NUC;
-  constexpr int TS = C::TS, LS = C::LS, QS = C::QS, RS = C::RS, LDA = C::LDA, HL = C::HL, SCR_LD = C::SCR_LD, SCR_TILE = C::SCR_TILE;
-  constexpr rtoc_layout SL = StaticLayout<NV, NU, NS>::make();
-  constexpr rtoc_record_layout KL = SL.kkt, RL = SL.ric;
-  static_assert(M::VOFF_LX > 0 && M::VOFF_LU > M::VOFF_LX && M::VOFF_LX % 2 == 0 && M::VOFF_LU % 2 == 0, "Fx, lx, lu lie behind one another in the record");
-  static_assert(KL.off[RTOC_KKT_FXX] % 2 == 0 && KL.off[RTOC_KKT_FX] % 2 == 0 && KL.off[RTOC_KKT_QUU] % 2 == 0 && KL.off[RTOC_KKT_QXX] % 2 == 0 && KL.stride % 2 == 0 && NX % 2 == 0, "16-byte chunks");
   constexpr int ST_LXO = M::VOFF_LX, ST_LUO = M::VOFF_LU;   // offsets inside a strip (Fx at 0)
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const LdsAddr ldsp(smem);   // (32-bit LDS addresses for the DMA destinations)
@@ -128,44 +124,10 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
   double* const sLup = pw_ + M::P_LUP;
   double* const sT = pw_ + M::P_T;
   int* const sGrid = reinterpret_cast<int*>(smem + M::OFF_GRID);
-
-  const int b = a.first + (int)blockIdx.x;
-  if (b >= a.batch) return;
   const int lane0 = threadIdx.x & 63;
-  int lane = lane0 & 63, li = lane & 15, q = lane >> 4;
-  const int N = a.nstages - 1;
-  const size_t kinst = (size_t)b * a.nstages * KL.stride;
-  const size_t rinst = (size_t)b * a.nstages * RL.stride;
-  const int hi = a.seg_hi, lo = a.seg_lo;
-  unsigned stat = 0;
+#include "riccati_rw_scope.inc"
 
-  // compile-time predicates of the k groups
-  auto group_dense = [](int g) { return g < G1 || g >= G0; };
-  auto group_all_dense = [](int g) { return 4 * g + 3 < NP_ || (4 * g >= NV && 4 * g + 3 < NX); };
-  auto qsum = [](double v) __attribute__((always_inline)) {   // sum over the four lanes (li, 0..3)
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-  };
-
-  // ---- DMA: the dense k groups of A (rows [0, 4 G1) and [4 G0, 4 KG) of every column) into the padded compact layout; whole
-  //      padded columns per piece, so that a piece differs from the next by a scalar ----
-  constexpr int NPC_A = (NX + 64 / HL - 1) / (64 / HL);   // DMA instructions of one A
-  auto issue_dma_A = [&](int stage) __attribute__((always_inline)) {
-    const double* kp = a.kkt + kinst + (size_t)stage * KL.stride + KL.off[RTOC_KKT_FXX];
-    constexpr int CPP = 64 / HL, NPC = NPC_A;
-    const unsigned col0 = (unsigned)lane / HL, ch0 = (unsigned)lane - col0 * HL;
-    const unsigned rl = 2 * ch0;                                                        // compact row of the chunk
-    const unsigned srow = (rl < 4 * G1) ? rl : ((rl < 4 * C::NDG) ? rl + 4 * (G0 - G1) : 0);   // (the padding chunk loads anything)
-    const unsigned voff = col0 * NX + srow;
-    if (col0 < CPP) {
-#pragma unroll
-      for (int p = 0; p < NPC; ++p) {
-        if ((p + 1) * CPP <= NX || p * CPP + (int)col0 < NX)
-          __builtin_amdgcn_global_load_lds(kp + p * CPP * NX + voff, ldsp(sA + p * CPP * LDA), 16, 0, 0);
-      }
-    }
-  };
+  // ---- DMA of this kernel alone (the shared loops: riccati_rw_dma.inc): Fvu, flat as in the record, and Qxu ----
   auto issue_dma_bv = [&](int stage) __attribute__((always_inline)) {
     const double* kp = a.kkt + kinst + (size_t)stage * KL.stride + KL.off[RTOC_KKT_FVU];
     constexpr int CBV = (NV * NU + 1) / 2, PBV = (CBV + 63) / 64;
@@ -184,128 +146,37 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
       if (64 * (p + 1) <= CX || n < CX) __builtin_amdgcn_global_load_lds(kp + 2 * n, ldsp(pw1 + 128 * p), 16, 0, 0);
     }
   };
-  auto issue_dma_strip = [&](int stage) __attribute__((always_inline)) {
-    const double* kp = a.kkt + kinst + (size_t)stage * KL.stride + KL.off[RTOC_KKT_FX];
-#pragma unroll
-    for (int p = 0; p < M::PS; ++p) {
-      const int n = lane + 64 * p;
-      if (64 * (p + 1) <= M::CV || n < M::CV)
-        __builtin_amdgcn_global_load_lds(kp + 2 * n, ldsp(smem + M::OFF_ST + (stage & 1) * M::STRIP + 128 * p), 16, 0, 0);
-    }
-  };
 
-  // ---- value function of grid point hi + 1 -> registers / LDS: the terminal one (P_N = Qxx_N, s_N = -lx_N,
-  //      riccati_recursion.cpp:37-38) or the one a previous segment left in the Riccati records ----
-  d4 pp[T][T];
-  {
-    const bool term = (hi == N - 1);
-    const double* psrc = term ? (a.kkt + kinst + (size_t)N * KL.stride + KL.off[RTOC_KKT_QXX])
-                              : (a.ric + rinst + (size_t)(hi + 1) * RL.stride + RL.off[RTOC_RIC_P]);
-    const double* ssrc = term ? (a.kkt + kinst + (size_t)N * KL.stride + KL.off[RTOC_KKT_LX])
-                              : (a.ric + rinst + (size_t)(hi + 1) * RL.stride + RL.off[RTOC_RIC_S]);
-#pragma unroll
-    for (int kt = 0; kt < T; ++kt)
-#pragma unroll
-      for (int mt = 0; mt < T; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = 16 * kt + 4 * r + q, j = 16 * mt + li;
-          const bool ok = i < NX && j < NX;
-          const double v = psrc[ok ? j + i * NX : 0];   // (symmetric: the mirror element, li along the contiguous index)
-          pp[kt][mt][r] = ok ? v : 0.0;
-        }
-    for (int e = lane; e < NX; e += 64) sS[e] = term ? -ssrc[e] : ssrc[e];
-    if (term && W == 0) {
-      double* rr = a.ric + rinst + (size_t)N * RL.stride;
-      const d2* s2 = reinterpret_cast<const d2*>(psrc);
-      d2* t2 = reinterpret_cast<d2*>(rr + RL.off[RTOC_RIC_P]);
-      for (int e = lane; e < NX * NX / 2; e += 64) t2[e] = s2[e];
-      for (int e = lane; e < NX; e += 64) rr[RL.off[RTOC_RIC_S] + e] = -ssrc[e];
-    }
-  }
-  // ---- operands that come straight from HBM, requested one stage ahead: Bv fragments (B operand of PB, A operand of G), Quu in the C
-  //      layout.  RAW: lanes beyond the matrices load a clamped address and are masked where the value is USED ----
+  // what the shared fragments (riccati_rw_*.inc) take from this kernel beside own: the strip by the parity of the grid point,
+  // the panels in this wave's block, wave 0 as the writer of the terminal record; macros (each undefined by its fragment) where a
+  // variable would move instructions
+  auto strip_of = [](int stage) { return smem + M::OFF_ST + (stage & 1) * M::STRIP; };
+  auto qpanel = [&](int p) { return pw_ + M::P_Q + (p & 1) * M::PANEL; };
+  constexpr bool TERM_WRITER = (W == 0);
+#define RW_LDS(p) ldsp(p)
+#define RW_QUU sG
+#define RW_FX_OFF (M::OFF_ST + (hi & 1) * M::STRIP)
+#define RW_LU(u) sStrip[ST_LUO + (u)]
+#define RW_COLUMN_MID panel_slot(1 + 2 * ord)
+  d4 pp[T][T];   // P+: the value function of the grid point behind
+#include "riccati_rw_vload.inc"
+  d4 f[T][T];
+#include "riccati_rw_dma.inc"
   // (Bv is NOT requested a stage ahead here: twenty registers carried over the stage boundary, where P+ is being rebuilt, were spilled
   //  load by load -- each with a full wait; they are requested at the stage top, ahead of z)
-  auto issue_bq = [&](int stage) __attribute__((always_inline)) {
-    const double* kp = a.kkt + kinst + (size_t)stage * KL.stride;
-    // Quu -> the LDS place of G by DMA (flat: G's leading dimension is NU); the G product adds itself onto it
-    constexpr int CQ = (NU * NU + 1) / 2, PQ = (CQ + 63) / 64;
-    const double* gp = kp + KL.off[RTOC_KKT_QUU];
-#pragma unroll
-    for (int p = 0; p < PQ; ++p) {
-      const int n = lane + 64 * p;
-      if (64 * (p + 1) <= CQ || n < CQ) __builtin_amdgcn_global_load_lds(gp + 2 * n, ldsp(sG + 128 * p), 16, 0, 0);
-    }
-  };
-  // Qxx comes in by DMA too, one column tile (16 columns, all rows: 8 KB, contiguous in the record) at a time into one of two padded
-  // panels in the zone that is dead between the policy products and the transposes; F accumulates from zero and takes its start
-  // value panel by panel at the end of the column loop's iterations (the same sum in another order; the symmetrisation of
-  // brrf.cpp:85 folded in): panel p holds the transposed elements of the tiles (p, t >= p) -- read with li along the contiguous
-  // index -- and the direct elements of the tiles (c < p, p).  No registers wait for these 32 KB.
-  constexpr int LDQ = M::LDQ;
-  d4 f[T][T];
-  auto issue_qxx_panel = [&](const double* kr_, int p) __attribute__((always_inline)) {
-    const double* qb_ = kr_ + KL.off[RTOC_KKT_QXX] + (size_t)16 * p * NX;
-    double* dst = pw_ + M::P_Q + (p & 1) * M::PANEL;
-#pragma unroll
-    for (int col = 0; col < 16; ++col) {
-      if (16 * p + col >= NX) continue;
-      if (lane < NX / 2) __builtin_amdgcn_global_load_lds(qb_ + col * NX + 2 * lane, ldsp(dst + col * LDQ), 16, 0, 0);
-    }
-  };
-  auto qxx_seed_panel = [&](int p) __attribute__((always_inline)) {
-    const double* pan = pw_ + M::P_Q + (p & 1) * M::PANEL;
-#pragma unroll
-    for (int t = p; t < T; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {   // tile (p, t): element (16p + 4r + q, 16t + li) <- Qxx[16t + li][16p + 4r + q], column 4r + q of the panel
-        if (!own(t)) continue;
-        const int i = 16 * p + 4 * r + q, j = 16 * t + li;
-        if (16 * p + 4 * r >= NX) continue;
-        const bool ok = ((16 * p + 4 * r + 3 < NX) || i < NX) && ((16 * t + 15 < NX) || j < NX);
-        const double v = pan[(ok ? j : 0) + (ok ? 4 * r + q : 0) * LDQ];
-        f[p][t][r] = __builtin_fma((t == p) ? 1.0 : 0.5, ok ? v : 0.0, f[p][t][r]);
-      }
-#pragma unroll
-    for (int c = 0; c < p; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {   // tile (c, p): element (16c + 4r + q, 16p + li) <- Qxx[16c + 4r + q][16p + li], column li of the panel
-        if (!own(p)) continue;
-        const int j = 16 * p + li;
-        const bool ok = (16 * p + 15 < NX) || j < NX;
-        const double v = pan[16 * c + 4 * r + q + (ok ? li : 0) * LDQ];
-        f[c][p][r] = __builtin_fma(0.5, ok ? v : 0.0, f[c][p][r]);
-      }
-  };
   if (W == 0) {
     issue_dma_strip(hi);
     issue_dma_bv(hi);
     issue_dma_A(hi);
     for (int e = lane; e < a.nstages; e += 64) sGrid[e] = a.grid[e].type | (a.grid[e].dims << 8);   // (the host keeps nstages <= RV_MAX_STAGES)
   }
-  if (W == 0) issue_bq(hi);
+  if (W == 0) issue_dma_quu(hi);
   else issue_dma_qxu(hi);
   // z = s+ - P+ Fx (brrf.cpp:86) of the first grid point of the segment: per-lane partial sums over the rows a lane holds, q-reduction
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   rw2_sync();   // the strip of grid point hi has landed (wave 0's DMA)
   if (W == 0) {
-    double fxr[KG];
-#pragma unroll
-    for (int g = 0; g < KG; ++g) {
-      const double v = smem[M::OFF_ST + (hi & 1) * M::STRIP + 4 * g + q];
-      fxr[g] = (4 * g + 3 < NX || 4 * g + q < NX) ? v : 0.0;
-    }
-#pragma unroll
-    for (int mt = 0; mt < T; ++mt) {
-      double part = 0.0;
-#pragma unroll
-      for (int g = 0; g < KG; ++g) part = __builtin_fma(pp[g / 4][mt][g % 4], fxr[g], part);
-      part = qsum(part);
-      const int j = 16 * mt + li;
-      const double sv = sS[(j < NX) ? j : 0];
-      if (q == 0 && j < NX) sZ[j] = sv - part;
-    }
+#include "riccati_rw_z.inc"
   }
 
   for (int st = hi; st >= lo; --st) {
@@ -359,10 +230,6 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
     }
     RW2_PROF(1);
     // (1. z = s+ - P+ Fx of this grid point was formed where P+ was rebuilt: at the end of the previous stage / in the prologue)
-    auto zrow = [&](int g) __attribute__((always_inline)) -> double {   // z in the row layout: z[4g + q] (re-read where it rides: no registers held)
-      const double v = sZ[4 * g + q];
-      return (4 * g + 3 < NX || 4 * g + q < NX) ? v : 0.0;
-    };
 
     RW2_PROF(2);
     // ---- the O(n^2 nu) part, split by ROLE: wave 0 forms G (it needs the rows v of PB only), factorises it and solves for t, k;
@@ -394,31 +261,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
 #pragma unroll
           for (int c = C0; c < T; ++c) acc[c][tu] = mfma16(pp[g / 4][c][g % 4], bvf[g - G0][tu], acc[c][tu]);
       if constexpr (W == 0) {
-        d4 gacc[TU][TU];
-#pragma unroll
-        for (int tr = 0; tr < TU; ++tr)
-#pragma unroll
-          for (int tu = 0; tu < TU; ++tu) gacc[tr][tu] = zero4();
-#pragma unroll
-        for (int g = G0; g < KG; ++g)
-#pragma unroll
-          for (int tu = 0; tu < TU; ++tu) {
-            double bop = acc[g / 4][tu][g % 4];
-            if (tu == TU - 1) bop = (li == NUC) ? zrow(g) : bop;
-#pragma unroll
-            for (int tr = 0; tr < TU; ++tr) gacc[tr][tu] = mfma16(bvf[g - G0][tr], bop, gacc[tr][tu]);
-          }
-#pragma unroll
-        for (int tr = 0; tr < TU; ++tr)
-#pragma unroll
-          for (int tu = 0; tu < TU; ++tu)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int u0 = 16 * tr + 4 * r + q, u1 = 16 * tu + li;
-              if (u0 < NU && u1 < NU) sG[u0 + u1 * NU] += gacc[tr][tu][r];
-              if (tu == TU - 1 && u0 < NU && li == NUC) sLup[u0] = sStrip[ST_LUO + u0] - gacc[tr][tu][r];   // lu' = lu - Bv^T z_v
-            }
-        rv_lds_sync();
+#include "riccati_rw_g.inc"
       }
     }
     RW2_PROF(3);
@@ -429,64 +272,11 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
       ca = sA[NP_ + NP_ * LDA];
       cc = sA[NP_ + (NV + NP_) * LDA];
     }
-    // structured rows of A^T [.] for one column of C tiles (rows = state rows): dst[k] += ca src[k], dst[NV + k] += cc src[k],
-    // k in [NP, NV); NV + k lies TS tiles, RS registers and QS q-groups below k (tests/rw_lane_model.py: struct_rows_add)
-    auto struct_rows_add = [&](d4(&dst)[T], const d4(&src)[T], int cmax) __attribute__((always_inline)) {
-      d4 rot[T];
-#pragma unroll
-      for (int c = 0; c < T; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int e = 4 * c + r;
-          const bool used = 4 * e + 3 >= NP_ && 4 * e < NV;   // the register holds a row of [NP, NV)
-          rot[c][r] = (QS != 0 && used) ? __shfl(src[c][r], (lane + 16 * (4 - QS)) & 63, 64) : src[c][r];
-        }
-#pragma unroll
-      for (int c = 0; c < T; ++c) {
-        if (c > cmax) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int e = 4 * c + r, i = 4 * e + q;
-          if (4 * e + 3 >= NP_ && 4 * e < NV) {
-            const double coef = (i >= NP_ && i < NV) ? ca : 0.0;
-            dst[c][r] = __builtin_fma(coef, src[c][r], dst[c][r]);
-          }
-          if (4 * e + 3 >= NV + NP_ && 4 * e < NX) {
-            const int ehi = 4 * (c - TS) + r - RS, elo = ehi - 1;
-            const double vhi = (ehi >= 0 && ehi < 4 * T) ? rot[(ehi >= 0 ? ehi : 0) / 4][(ehi >= 0 ? ehi : 0) % 4] : 0.0;
-            const double vlo = (QS != 0 && elo >= 0 && elo < 4 * T) ? rot[(elo >= 0 ? elo : 0) / 4][(elo >= 0 ? elo : 0) % 4] : 0.0;
-            const double got = (QS == 0 || q >= QS) ? vhi : vlo;
-            const int k = i - NV;
-            const double coef = (k >= NP_ && k < NV && i < NX) ? cc : 0.0;
-            dst[c][r] = __builtin_fma(coef, got, dst[c][r]);
-          }
-        }
-      }
-    };
-    // A fragment of k group g, column tile c: A[4g + q][16c + li], the B operand of [.] A and the A operand of A^T [.] alike
-    auto afrag = [&](int g, int c) __attribute__((always_inline)) -> double {
-      const int j = 16 * c + li;
-      const double v = sA[4 * C::cg(g) + q + ((16 * c + 15 < NX || j < NX) ? j : NX - 1) * LDA];
-      const int k = 4 * g + q;
-      const bool rowok = group_all_dense(g) || (k < NP_ || (k >= NV && k < NX));
-      return (rowok && (16 * c + 15 < NX || j < NX)) ? v : 0.0;
-    };
-    // structured rows of k group g as a B fragment of column tile c: B[k = 4g + q][x = 16c + li] = ca (x == k) + cc (x == NV + k), k in [NP, NV)
-    auto struct_hit = [](int g, int c) {
-      const int k0 = (4 * g > NP_) ? 4 * g : NP_, k1 = (4 * g + 3 < NV - 1) ? 4 * g + 3 : NV - 1;
-      if (k0 > k1) return false;
-      return (k0 <= 16 * c + 15 && k1 >= 16 * c) || (NV + k0 <= 16 * c + 15 && NV + k1 >= 16 * c);
-    };
-    auto struct_frag = [&](int g, int c) __attribute__((always_inline)) -> double {
-      const int k = 4 * g + q, x = 16 * c + li;
-      const double v = (x == k) ? ca : (x == NV + k) ? cc : 0.0;
-      return (k >= NP_ && k < NV) ? v : 0.0;
-    };
 
     if constexpr (W == 1) {
       // z into the idle column NU of PB: row NU of H^T = PB^T A is then (A^T z)^T (on an impact grid point PB is that column alone)
 #pragma unroll
-      for (int g = 0; g < KG; ++g) acc[g / 4][TU - 1][g % 4] = (li == NUC) ? zrow(g) : acc[g / 4][TU - 1][g % 4];
+      for (int g = 0; g < KG; ++g) acc[g / 4][TU - 1][g % 4] = (li == NUC) ? ln.zrow(g) : acc[g / 4][TU - 1][g % 4];
       // ================= 4. H^T DIRECTLY in the layout Z^T = Y H^T reads: PB's C tiles are the A operand as they stand, A's fragments
       //                      the B operand; the structured rows k of A (ca e_k | cc e_NV+k) are synthesised fragments that meet at
       //                      most three column tiles.  No transposes, no rotations (tests/rw_lane_model.py: direct_ht).  On an
@@ -501,18 +291,8 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
 #pragma unroll
           for (int c = 0; c < T; ++c) hT[tu][c] = zero4();
         }
-#pragma unroll
-        for (int g = 0; g < KG; ++g) {
-          const double aop = acc[g / 4][tu][g % 4];
-#pragma unroll
-          for (int c = 0; c < T; ++c) {
-            const bool hit = struct_hit(g, c);
-            if (!group_dense(g) && !hit) continue;
-            double bop = group_dense(g) ? afrag(g, c) : 0.0;
-            if (hit) bop += struct_frag(g, c);   // (afrag is zero on the structured rows)
-            hT[tu][c] = mfma16(aop, bop, hT[tu][c]);
-          }
-        }
+        d4(&hrow)[T] = hT[tu];
+#include "riccati_rw_hrow.inc"
         if (tu == TU - 1) {   // the rider: w0 = A^T z; its row leaves H^T (rows u >= NU are zero otherwise: Bv's fragments are masked)
 #pragma unroll
           for (int c = 0; c < T; ++c) {
@@ -552,24 +332,12 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
     //      behind the second one nobody reads the other's block any more (its Qxx panels will land there) ----
     rw2_sync();
     double ya[TU][KGU];   // wave 1's copy of Y's fragments as the A operand of Z^T = Y H^T (five column tiles pass by them)
-    auto yaf = [&](int tu, int gj) __attribute__((always_inline)) -> double {
-      const int m = 16 * tu + li, k = 4 * gj + q;
-      const bool ok = m < NU && k < NU;
-      const double v = sY[(ok ? m : 0) + (ok ? k : 0) * NU];
-      return ok ? v : 0.0;
-    };
-    auto ykf = [&](int tu, int gj) __attribute__((always_inline)) -> double {   // -Y[k][m], the A operand of K = -Y^T Z^T (wave 0)
-      const int m = 16 * tu + li, k = 4 * gj + q;
-      const bool ok = m < NU && k < NU;
-      const double v = sY[(ok ? k : 0) + (ok ? m : 0) * NU];
-      return ok ? -v : 0.0;
-    };
     if constexpr (W == 1) {
       if (!impact) {
 #pragma unroll
         for (int tu = 0; tu < TU; ++tu)
 #pragma unroll
-          for (int gj = 0; gj < KGU; ++gj) ya[tu][gj] = (gj < 4 * (tu + 1)) ? yaf(tu, gj) : 0.0;
+          for (int gj = 0; gj < KGU; ++gj) ya[tu][gj] = (gj < 4 * (tu + 1)) ? ln.yfrag(sY, tu, gj) : 0.0;
         // lu' (wave 0 formed it beside G) -> column NX of H^T: in this wave's registers and in wave 0's copy of the last column tile
 #pragma unroll
         for (int tu = 0; tu < TU; ++tu)
@@ -635,7 +403,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
 #pragma unroll
         for (int gj = 0; gj < KGU; ++gj) {
           if (gj >= 4 * (tu + 1)) continue;
-          zc[tu] = mfma16((W == 1) ? ya[tu][gj] : yaf(tu, gj), hc[gj / 4][gj % 4], zc[tu]);
+          zc[tu] = mfma16((W == 1) ? ya[tu][gj] : ln.yfrag(sY, tu, gj), hc[gj / 4][gj % 4], zc[tu]);
         }
       }
     };
@@ -656,7 +424,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
 #pragma unroll
         for (int gj = 0; gj < KGU; ++gj) {
           if (gj < 4 * tu) continue;
-          kk = mfma16(ykf(tu, gj), zc[gj / 4][gj % 4], kk);
+          kk = mfma16(ln.ytfrag(sY, tu, gj), zc[gj / 4][gj % 4], kk);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -675,7 +443,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
       double part = 0.0;
 #pragma unroll
       for (int gu = 0; gu < KGU; ++gu) part = __builtin_fma(zc[gu / 4][gu % 4], tr_[gu], part);
-      part = qsum(part);
+      part = L::qsum(part);
       const int j = 16 * c + li;
       const int jc = (j < NX) ? j : 0;
       const double sn = sW0[jc] - sStrip[ST_LXO + jc] + part;
@@ -832,69 +600,15 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
       if (!own(t)) continue;   // this wave's column tiles of F
       constexpr int T0 = (W == 0) ? 0 : TSPLIT + 1;
       const int ord = t - T0;   // which of this wave's iterations
-      d4 w[T];
-#pragma unroll
-      for (int tm = 0; tm < T; ++tm) w[tm] = zero4();
-#pragma unroll
-      for (int g = 0; g < KG; ++g) {
-        if (!group_dense(g)) continue;
-        const double bv = afrag(g, t);
-#pragma unroll
-        for (int tm = 0; tm < T; ++tm) w[tm] = mfma16(pp[g / 4][tm][g % 4], bv, w[tm]);
-      }
-      {
-        // structured rows k of A: W[:, k] += ca P+[:, k] (same tile / lane), W[:, NV + k] += cc P+[:, k] (TS tiles, LS lanes to the left)
-        const int j = 16 * t + li, k = j - NV;
-        const double ca_l = (j >= NP_ && j < NV) ? ca : 0.0;
-        const double cc_l = (k >= NP_ && k < NV && j < NX) ? cc : 0.0;
-#pragma unroll
-        for (int tm = 0; tm < T; ++tm)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (16 * t + 15 >= NP_ && 16 * t < NV) w[tm][r] = __builtin_fma(ca_l, pp[tm][t][r], w[tm][r]);
-            if (16 * t + 15 >= NV + NP_ && 16 * t < NX) {
-              double src = 0.0;
-              if constexpr (LS == 0) {
-                if (t - TS >= 0) src = pp[tm][(t - TS >= 0) ? t - TS : 0][r];
-              } else {
-                if (t - TS >= 0) src = dpp_from_left<LS>(pp[tm][(t - TS >= 0) ? t - TS : 0][r]);
-                if (t - TS - 1 >= 0) src += dpp_from_right<16 - LS>(pp[tm][(t - TS - 1 >= 0) ? t - TS - 1 : 0][r]);
-              }
-              w[tm][r] = __builtin_fma(cc_l, src, w[tm][r]);
-            }
-          }
-      }
-      panel_slot(1 + 2 * ord);
-#pragma unroll
-      for (int g = 0; g < KG; ++g) {
-        if (!group_dense(g)) continue;
-        const double bw = w[g / 4][g % 4];
-#pragma unroll
-        for (int c = 0; c <= t; ++c) f[c][t] = mfma16(afrag(g, c), bw, f[c][t]);
-      }
-      {
-        d4 col[T];
-#pragma unroll
-        for (int c = 0; c < T; ++c) col[c] = (c <= t) ? f[c][t] : zero4();
-        struct_rows_add(col, w, t);
-#pragma unroll
-        for (int c = 0; c <= t; ++c) f[c][t] = col[c];
-      }
+#include "riccati_rw_column.inc"
       panel_slot(2 + 2 * ord);
     }
     RW2_PROF(11);
     // ================= 10. the fifteen tiles of F meet in LDS, in the place of A; each wave rebuilds P+ = sym(F) from there ==========
-    auto masked = [&](int c, int t, int r, double v) -> double {
-      const int i = 16 * c + 4 * r + q, j = 16 * t + li;
-      if (16 * c + 4 * r >= NX) return 0.0;
-      const bool rowok = (16 * c + 4 * r + 3 < NX) || i < NX;
-      const bool colok = (16 * t + 15 < NX) || j < NX;
-      return (rowok && colok) ? v : 0.0;
-    };
     auto tile_at = [](int c, int t) constexpr { return c * T - c * (c - 1) / 2 + (t - c); };   // index of the upper tile (c, t), c <= t
     if (W == 0 && st > lo) {   // Bv and Quu of the next grid point: their places (wave 1's H^T, this wave's last panel) have been read
       issue_dma_bv(st - 1);
-      issue_bq(st - 1);
+      issue_dma_quu(st - 1);
     }
     rw2_sync();   // both waves have read A -- and the strip -- for the last time
 #pragma unroll
@@ -904,7 +618,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
         if (!own(t)) continue;
         double* x_ = sA + tile_at(c, t) * SCR_TILE;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) x_[(q + 4 * r) * SCR_LD + li] = masked(c, t, r, f[c][t][r]);
+        for (int r = 0; r < 4; ++r) x_[(q + 4 * r) * SCR_LD + li] = ln.masked(c, t, r, f[c][t][r]);
       }
     RW2_PROF(12);
     rw2_sync();   // all of F is in LDS, and the next strip
@@ -925,11 +639,11 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
           // from their upper triangle (P exactly symmetric)
           double pv;
           if (kt < mt) {
-            pv = own(mt) ? masked(kt, mt, r, f[kt][mt][r]) : x_[(q + 4 * r) * SCR_LD + li];
+            pv = own(mt) ? ln.masked(kt, mt, r, f[kt][mt][r]) : x_[(q + 4 * r) * SCR_LD + li];
           } else if (kt > mt) {
             pv = x_[li * SCR_LD + q + 4 * r];
           } else {
-            const double dv = own(mt) ? masked(kt, mt, r, f[kt][mt][r]) : x_[(q + 4 * r) * SCR_LD + li];
+            const double dv = own(mt) ? ln.masked(kt, mt, r, f[kt][mt][r]) : x_[(q + 4 * r) * SCR_LD + li];
             const double tv = x_[li * SCR_LD + q + 4 * r];
             pv = (q + 4 * r <= li) ? dv : tv;
           }
@@ -944,7 +658,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
 #pragma unroll
       for (int mt = 0; mt < T; ++mt) {
         if (!own(mt)) continue;
-        const double part = qsum(zpart[mt]);
+        const double part = L::qsum(zpart[mt]);
         const int j = 16 * mt + li;
         const double sv = sS[(j < NX) ? j : 0];
         if (q == 0 && j < NX) sZ[j] = sv - part;
@@ -963,20 +677,7 @@ __device__ __forceinline__ void rw2_body(BwdArgs a) {
     RW2_PROF(13);
   }
 
-  // ---- P of the last grid point of the segment ----
-  {
-    double* pw = a.ric + rinst + (size_t)lo * RL.stride + RL.off[RTOC_RIC_P];
-#pragma unroll
-    for (int kt = 0; kt < T; ++kt)
-#pragma unroll
-      for (int mt = 0; mt < T; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = 16 * kt + 4 * r + q, j = 16 * mt + li;
-          if (own(kt) && i < NX && j < NX) pw[j + i * NX] = pp[kt][mt][r];
-        }
-  }
-  if (stat) atomicOr(&a.status[b], stat);
+#include "riccati_rw_end.inc"
 }
 
 template <int NV, int NU, int NS>

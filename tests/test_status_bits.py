@@ -19,8 +19,8 @@ What a dropped `stat |=` line does to these tests (each line replaced by a no-op
 against it).  Noticed line by line: riccati_sc_block.inc:52 (phiu-row on the tile-split and both role-split paths),
 condense_mjtjinv.inc:80 (every dCda case of the three ANYmal pipelines), condense_mjtjinv.inc:28 (the flight cases: with contacts LLT(J
 M^-1 J^T) fails after LLT(dIDda) did and raises the same bit), riccati_backward.hpp:762 (lu-nan on the tile-split path and the scan),
-riccati_backward_rv.hpp:897 and :985, riccati_backward_rs.hpp:770, riccati_backward_rw.hpp:478 (lu-nan) and :526 (qxu-nan0),
-riccati_backward_rw2.hpp:719, condense_mjtjinv.inc:39 (the iCub flight case), unconstr_riccati.hpp:265 and :333.  Not noticed:
+riccati_backward_rv.hpp:897 and :985, riccati_backward_rs.hpp:770, riccati_backward_rw.hpp:387 (lu-nan) and :427 (qxu-nan0),
+riccati_backward_rw2.hpp:487, condense_mjtjinv.inc:39 (the iCub flight case), unconstr_riccati.hpp:265 and :333.  Not noticed:
 riccati_backward_rv.hpp:944 (m of the switching constraint: whatever makes m NaN makes k of the same grid point NaN, which :985
 reports).  Not noticed line by line, by
 construction: the scans factorise every grid point twice -- in the element / preparation kernels (riccati_scan_core.hpp:372-373,
