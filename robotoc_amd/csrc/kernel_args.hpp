@@ -173,6 +173,7 @@ struct StoScanArgs {
   int nstages, batch, first;
   double max_dts0;
   long long* prof;    // phase stamps of instance 0 (RTOC_ENABLE_PROF builds), else nullptr
+  double* kkt_rw;     // RTOC_OPT_WRITEBACK_KKT: the KKT records, writable (the vector pass writes the mutated lu), else nullptr
 };
 constexpr int SCAN_STO_MAX_STAGES = 512;   // = scan::StoVecCfg::MAX_STAGES (grids beyond take the serial kernel)
 

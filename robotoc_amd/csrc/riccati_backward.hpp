@@ -913,7 +913,23 @@ __global__ __launch_bounds__(64 * NW) void riccati_backward_kernel(BwdArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int i = (wave + c * NW) * 16 + drow(q, r), j = t * 16 + li;
-            if (i < NX && j < NX) kw[KL.off[RTOC_KKT_QXX] + i + j * NX] = f[c][t][r];
+            if (i < NX && j < NX) {
+              double v = f[c][t][r];
+              if (NS > 0 && ns > 0) {
+                // the reference's Qxx stops at Qxx - K^T G K (brrf.cpp:83); KtDtM and its transpose leave P alone
+                // (riccati_factorizer.cpp:84-87).  Here they are folded into GK above: F holds -2 K^T Phiu^T M, taken out again
+                double ktdtm = 0.0;
+#pragma unroll 1
+                for (int u = 0; u < NU; ++u) {
+                  double dtm = 0.0;
+#pragma unroll 1
+                  for (int l = 0; l < ns; ++l) dtm += smem[C::S_PHIU + l + u * C::NSP] * smem[C::S_M + l + j * C::NSP];
+                  ktdtm += sKt[i + u * LDP] * dtm;
+                }
+                v += 2.0 * ktdtm;
+              }
+              kw[KL.off[RTOC_KKT_QXX] + i + j * NX] = v;
+            }
           }
     }
 

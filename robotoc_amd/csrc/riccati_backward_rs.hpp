@@ -982,8 +982,17 @@ __device__ __forceinline__ void riccati_backward_rs_body(const BwdArgs& a, const
             for (int r = 0; r < 4; ++r) {
               const int i = c * 16 + drow(q, r), j = t * 16 + li;
               if (i < NX && j < NX) {
-                kw[KL.off[RTOC_KKT_QXX] + i + j * NX] = f[c][t][r];
-                if (t > c) kw[KL.off[RTOC_KKT_QXX] + j + i * NX] = f[c][t][r];
+                double v = f[c][t][r];
+                if (NS > 0 && ns > 0) {
+                  // the reference's Qxx stops at Qxx - K^T G K (brrf.cpp:83): K^T D + D^T K (D = Phiu^T M, still in sGK), which
+                  // riccati_factorizer.cpp:84-87 takes from P alone, is taken out of F again
+                  double kd = 0.0;
+#pragma unroll 1
+                  for (int u = 0; u < NU; ++u) kd += sKt[i + u * LDP] * sGK[u + j * NU] + sGK[u + i * NU] * sKt[j + u * LDP];
+                  v += kd;
+                }
+                kw[KL.off[RTOC_KKT_QXX] + i + j * NX] = v;
+                if (t > c) kw[KL.off[RTOC_KKT_QXX] + j + i * NX] = v;
               }
             }
       }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(SCAN_STO_VEC_NT) void scan_sto_vector_kernel(StoSca
   const size_t inst = (size_t)b * a.nstages;
   const unsigned stat = scan::sto_vector_body<NV, NU, NS, SCAN_STO_VEC_NT>(
       a.grid, a.nstages, a.kkt + inst * SL.kkt.stride, a.ric + inst * SL.ric.stride, a.scr + inst * scan::StoScratch<NV, NU, NS>::STRIDE,
-      a.max_dts0, smem, threadIdx.x, b == 0 ? a.prof : nullptr);
+      a.max_dts0, smem, threadIdx.x, b == 0 ? a.prof : nullptr, a.kkt_rw ? a.kkt_rw + inst * SL.kkt.stride : nullptr);
   if (stat) atomicOr(&a.status[b], stat);
 }
 

@@ -337,7 +337,7 @@ constexpr int sto_lanes_needed(int nx, int nu, int nsp, int parts) {
 // record by the last wave during P1 of step st (from LDS, where they stay untouched until the barrier that ends P1).
 template <int NV, int NU, int NS, int NT>
 RTOC_SCAN_DEV unsigned sto_vector_body(const rtoc_grid* grid, int nstages, const double* kkt, double* ric, const double* scr, double max_dts0,
-                                       double* smem, int tid, long long* prof = nullptr) {
+                                       double* smem, int tid, long long* prof = nullptr, double* kkt_rw = nullptr) {
   using C = StoVecCfg<NV, NU, NS>;
   using W = StoScratch<NV, NU, NS>;
   constexpr int NX = 2 * NV, NSP = C::NSP;
@@ -555,6 +555,8 @@ RTOC_SCAN_DEV unsigned sto_vector_body(const rtoc_grid* grid, int nstages, const
         a0 = sto_parts_sum<PARTS>(a0), a1 = sto_parts_sum<PARTS>(a1), a2 = sto_parts_sum<PARTS>(a2);
         if (part == 0) {
           lup[u] = smem[W::O_LU + u] + a0;
+          // RTOC_OPT_WRITEBACK_KKT: the mutated lu (brrf.cpp:43-44) is formed here, on the chain -- the policy workgroups have no s+
+          if (kkt_rw) kkt_rw[(size_t)st * SL.kkt.stride + SL.kkt.off[RTOC_KKT_LU] + u] = lup[u];
           psu[u] = sto ? smem[W::O_HU + u] + a1 : 0.0;
           phu[u] = (sto && sto_next) ? a2 : 0.0;
         }

@@ -91,6 +91,7 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
     t.kkt = c->buf[RTOC_BUF_KKT].p, t.ric = c->buf[RTOC_BUF_RIC].p, t.grid = c->d_grid.p, t.status = c->d_status.p;
     t.ps = c->d_scan[2].p, t.scr = c->d_scan_sto.p;
     t.nstages = n, t.batch = end, t.first = first, t.max_dts0 = c->max_dts0, t.prof = c->d_prof.p;
+    t.kkt_rw = c->writeback ? c->buf[RTOC_BUF_KKT].p : nullptr;   // the policy workgroups have no s+: lu is written by the vector pass
     if (!ride) launch(ks->sto_prep, dim3(n - 1, nb), stream, t);
   }
   a.sto_scr = ride ? c->d_scan_sto.p : nullptr;

@@ -50,6 +50,14 @@ def record_parity(label, observed, tol):
                                "tests/golden/parity_pins.json; asserted tolerance %.1e)" % (label, observed, bound, tol))
 
 
+def _record_with_fields(label, observed, tol, bad):
+    """record_parity; a failure names the (stage, field, rel_err) beyond the tolerance, not only the worst error."""
+    try:
+        record_parity(label, observed, tol)
+    except AssertionError as e:
+        raise AssertionError("%s; (stage, field, rel_err) beyond %.1e: %s" % (e, tol, bad[:12])) from None
+
+
 def check_parity(label, observed, tol):
     """Register an observed error and assert it against its tolerance."""
     record_parity(label, observed, tol)
@@ -109,7 +117,7 @@ def compare_riccati(L, grids, ric_gpu, ric_ref, tol, what="", check_sto=True):
             worst = max(worst, e)
             if not (e <= tol):
                 bad.append((i, "scal", e))
-    record_parity("riccati " + what, worst, tol)
+    _record_with_fields("riccati " + what, worst, tol, bad)
     assert not bad, "%s riccati mismatch (stage, field, rel_err): %s" % (what, bad[:12])
     return worst
 
@@ -139,7 +147,7 @@ def compare_direction(L, grids, d_gpu, d_ref, tol, what=""):
         worst = max(worst, e)
         if not (e <= tol):
             bad.append((i, "dts", e))
-    record_parity("direction " + what, worst, tol)
+    _record_with_fields("direction " + what, worst, tol, bad)
     assert not bad, "%s direction mismatch (stage, field, rel_err): %s" % (what, bad[:12])
     return worst
 

@@ -1,8 +1,8 @@
 """RTOC_OPT_BACKWARD_REGISTER: the register-resident backward kernel (riccati_backward_rv.hpp: one wavefront per OCP instance,
 P+ / s+ in MFMA accumulators, the stage record by LDS-DMA) against the CPU oracle and against the role-split kernel, on the
-GPU through the C ABI.  The horizon of the trot has every grid-point kind the kernel meets or hands over: regular, lift and
-impact grid points (the kernel's own), two switching-constraint grid points (one-stage launches of the tile-split kernel, P+ / s+
-handed over through the Riccati records in both directions) and the terminal record.
+GPU through the C ABI.  The horizon of the trot has every grid-point kind the kernel meets: regular, lift and impact grid points,
+two switching-constraint grid points (the kernel's own as well, in the factorised Schur form: one launch covers the whole
+horizon, launch_backward_rv in rt_sweep.hip) and the terminal record.
 
 Tolerance: SURVEY 8c's 1e-9 per stage and field, as tests/test_gpu_parity.py (both kernels re-associate the products of
 backward_riccati_recursion_factorizer.cpp:31-91 on the f64 matrix cores; observed errors are printed)."""
@@ -76,8 +76,9 @@ def test_register_kernel_reproduces_the_oracle_on_the_trot(oracle, mode):
 
 
 def test_register_kernel_on_grids_that_start_or_end_with_a_switching_constraint(oracle):
-    """Segment boundaries at both ends of the horizon: a switching constraint on the last control grid point (the terminal record is
-    then written by the one-stage launch) and on grid point 0 (no register segment behind it); and a grid of impacts only."""
+    """Switching constraints at both ends of the horizon: on the last control grid point (the kernel's constrained form is then the
+    first stage behind the terminal record) and on grid point 0 (the last stage of the launch); and a grid with no switching
+    constraint at all.  The kernel owns the constrained grid points: one launch per horizon (launch_backward_rv in rt_sweep.hip)."""
     from robotoc_amd import capi
     dims, grids0, _ = pr.config_anymal_trot()
     n = len(grids0)
