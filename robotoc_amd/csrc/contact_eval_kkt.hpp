@@ -11,7 +11,6 @@
 // cost table (device): 12 arrays of M = nv + 1 doubles: q_ref | v_ref | u_ref | wq | wv | wa | wu | wq_T | wv_T | wq_I | wv_I | wdv_I
 #pragma once
 #include "device_utils.hpp"
-#include "kernel_args.hpp"
 #include "record_view.hpp"
 #include "rigid_body_math.hpp"
 

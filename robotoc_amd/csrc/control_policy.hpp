@@ -18,7 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "../../include/rtoc_layout.h"
+#include "record_view.hpp"
 
 namespace rtoc {
 
@@ -45,17 +45,15 @@ static __global__ __launch_bounds__(64) void policy_times_kernel(PolicyTimesArgs
 }
 
 struct PolicyArgs {
-  const double* sol;      // RTOC_BUF_SOL: [batch][nstages][sol stride]
-  const double* ric;      // RTOC_BUF_RIC: [batch][nstages][ric stride]
-  const rtoc_grid* grid;  // [nstages]
+  RecView rv;             // sol: RTOC_BUF_SOL, [batch][nstages][sol stride]
+  const double* ric;      // RTOC_BUF_RIC: [batch][nstages][ric stride] (the view has no Riccati records)
   const double* tg;       // grid times, [nstages] or [count][nstages]
   const double* t;        // query times, [1] or [count]
   const double* x;        // control_input_kernel: measured states [count][nq + nv]
   double* out;            // control_policy_kernel: [count][rtoc_control_policy_stride(nu)]; control_input_kernel: [count][nu]
-  int nstages, count, N;
+  int count, N;
   int tg_per_instance, t_per_instance;
-  int nv, nu, nq;
-  int sol_stride, ric_stride, off_q, off_v, off_u, off_k;
+  int nq;
 };
 
 namespace policy {
@@ -74,19 +72,19 @@ __device__ inline Pick pick(const PolicyArgs& p, const double* tg, double t, int
   if (t < tg[0]) return r;
   for (int base = 1; base <= p.N - 2; base += 64) {
     const int i = base + lane;
-    const bool hit = i <= p.N - 2 && t < tg[i] && p.grid[i - 1].type != RTOC_GRID_IMPACT;
+    const bool hit = i <= p.N - 2 && t < tg[i] && p.rv.grid[i - 1].type != RTOC_GRID_IMPACT;
     const unsigned long long m = __ballot(hit);
     if (m) {
       const int k = base + __ffsll((long long)m) - 1;
       r.a = k - 1;
-      if (p.grid[k].type == RTOC_GRID_IMPACT) return r;   // hold: the impact's u and K are not defined
+      if (p.rv.grid[k].type == RTOC_GRID_IMPACT) return r;   // hold: the impact's u and K are not defined
       r.b = k;
       r.alpha = (tg[k] - t) / (tg[k] - tg[k - 1]);
       return r;
     }
   }
   r.a = p.N - 1;
-  if (r.a > 0 && p.grid[r.a].type == RTOC_GRID_IMPACT) r.a = p.N - 2;   // (rtoc_set_grid takes no impact at grid point 0)
+  if (r.a > 0 && p.rv.grid[r.a].type == RTOC_GRID_IMPACT) r.a = p.N - 2;   // (rtoc_set_grid takes no impact at grid point 0)
   return r;
 }
 
@@ -99,7 +97,7 @@ static __global__ __launch_bounds__(64) void control_policy_kernel(PolicyArgs p)
   using namespace policy;
   const int lane = threadIdx.x, b = blockIdx.x;
   if (b >= p.count) return;
-  const int nu = p.nu, nv = p.nv, nx = 2 * nv, nn = nu * nu;
+  const int nu = p.rv.nu(), nv = p.rv.nv(), nx = 2 * nv, nn = nu * nu;
   const int stride = rtoc_control_policy_stride(nu);
   double* __restrict__ out = p.out + (size_t)b * stride;
   const double t = p.t[p.t_per_instance ? b : 0];
@@ -107,22 +105,22 @@ static __global__ __launch_bounds__(64) void control_policy_kernel(PolicyArgs p)
     for (int e = lane; e < stride; e += 64) out[e] = __builtin_nan("");
     return;
   }
-  const Pick k = pick(p, p.tg + (p.tg_per_instance ? (size_t)b * p.nstages : 0), t, lane);
+  const Pick k = pick(p, p.tg + (p.tg_per_instance ? (size_t)b * p.rv.nstages : 0), t, lane);
   const bool two = k.b >= 0;
-  const size_t r0 = (size_t)b * p.nstages + k.a, r1 = (size_t)b * p.nstages + (two ? k.b : k.a);
-  const double* __restrict__ sa = p.sol + r0 * p.sol_stride;
-  const double* __restrict__ sb = p.sol + r1 * p.sol_stride;
-  const double* __restrict__ ka = p.ric + r0 * p.ric_stride + p.off_k;
-  const double* __restrict__ kb = p.ric + r1 * p.ric_stride + p.off_k;
+  const size_t r0 = (size_t)b * p.rv.nstages + k.a, r1 = (size_t)b * p.rv.nstages + (two ? k.b : k.a);
+  const double* __restrict__ sa = p.rv.sol_at(r0);
+  const double* __restrict__ sb = p.rv.sol_at(r1);
+  const double* __restrict__ ka = p.ric + r0 * p.rv.L.ric.stride + p.rv.L.ric.off[RTOC_RIC_K];
+  const double* __restrict__ kb = p.ric + r1 * p.rv.L.ric.stride + p.rv.L.ric.off[RTOC_RIC_K];
   const int pad = rtoc_pad8(nu);
-  const int oq = p.off_q + p.nq - nu, ov = p.off_v + nv - nu;
+  const int oq = p.rv.sol_off(RTOC_SOL_Q) + p.nq - nu, ov = p.rv.sol_off(RTOC_SOL_V) + nv - nu, ou = p.rv.sol_off(RTOC_SOL_U);
   // tauJ, qJ, dqJ and their padding
   for (int c = lane; c < pad; c += 64) {
     double u = 0.0, q = 0.0, v = 0.0;
     if (c < nu) {
-      u = sa[p.off_u + c], q = sa[oq + c], v = sa[ov + c];
+      u = sa[ou + c], q = sa[oq + c], v = sa[ov + c];
       if (two) {
-        const double u1 = sb[p.off_u + c], q1 = sb[oq + c], v1 = sb[ov + c];
+        const double u1 = sb[ou + c], q1 = sb[oq + c], v1 = sb[ov + c];
         u = blend(k.alpha, u, u1), q = blend(k.alpha, q, q1), v = blend(k.alpha, v, v1);
       }
     }
@@ -152,22 +150,22 @@ static __global__ __launch_bounds__(64) void control_input_kernel(PolicyArgs p) 
   extern __shared__ double err[];   // [nu] qJ - q, then [nu] dqJ - v
   const int lane = threadIdx.x, b = blockIdx.x;
   if (b >= p.count) return;
-  const int nu = p.nu, nv = p.nv, nx = 2 * nv;
+  const int nu = p.rv.nu(), nv = p.rv.nv(), nx = 2 * nv;
   double* __restrict__ out = p.out + (size_t)b * nu;
   const double t = p.t[p.t_per_instance ? b : 0];
   if (!isfinite(t)) {
     for (int e = lane; e < nu; e += 64) out[e] = __builtin_nan("");
     return;
   }
-  const Pick k = pick(p, p.tg + (p.tg_per_instance ? (size_t)b * p.nstages : 0), t, lane);
+  const Pick k = pick(p, p.tg + (p.tg_per_instance ? (size_t)b * p.rv.nstages : 0), t, lane);
   const bool two = k.b >= 0;
-  const size_t r0 = (size_t)b * p.nstages + k.a, r1 = (size_t)b * p.nstages + (two ? k.b : k.a);
-  const double* __restrict__ sa = p.sol + r0 * p.sol_stride;
-  const double* __restrict__ sb = p.sol + r1 * p.sol_stride;
-  const double* __restrict__ ka = p.ric + r0 * p.ric_stride + p.off_k;
-  const double* __restrict__ kb = p.ric + r1 * p.ric_stride + p.off_k;
+  const size_t r0 = (size_t)b * p.rv.nstages + k.a, r1 = (size_t)b * p.rv.nstages + (two ? k.b : k.a);
+  const double* __restrict__ sa = p.rv.sol_at(r0);
+  const double* __restrict__ sb = p.rv.sol_at(r1);
+  const double* __restrict__ ka = p.ric + r0 * p.rv.L.ric.stride + p.rv.L.ric.off[RTOC_RIC_K];
+  const double* __restrict__ kb = p.ric + r1 * p.rv.L.ric.stride + p.rv.L.ric.off[RTOC_RIC_K];
   const double* __restrict__ x = p.x + (size_t)b * (p.nq + nv);
-  const int oq = p.off_q + p.nq - nu, ov = p.off_v + nv - nu;
+  const int oq = p.rv.sol_off(RTOC_SOL_Q) + p.nq - nu, ov = p.rv.sol_off(RTOC_SOL_V) + nv - nu, ou = p.rv.sol_off(RTOC_SOL_U);
   for (int c = lane; c < nu; c += 64) {
     double q = sa[oq + c], v = sa[ov + c];
     const double xq = x[p.nq - nu + c], xv = x[p.nq + nv - nu + c];
@@ -197,8 +195,8 @@ static __global__ __launch_bounds__(64) void control_input_kernel(PolicyArgs p) 
     }
     for (int m = P >> 1; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
     if (r < nu && j == 0) {
-      double u = sa[p.off_u + r];
-      if (two) u = blend(k.alpha, u, sb[p.off_u + r]);
+      double u = sa[ou + r];
+      if (two) u = blend(k.alpha, u, sb[ou + r]);
       out[r] = u - acc;
     }
   }

@@ -13,35 +13,38 @@
 // 1e-13 max(1, |p|, |v|) (4.1e+04 of it at 1.01e-8 before), quaternion within 0.22 of 1e-15.
 #pragma once
 #include "device_utils.hpp"
-#include "kernel_args.hpp"  // IntArgs
+#include "record_view.hpp"
 #include "rigid_body_math.hpp"
-#include "../../include/rtoc.h"
 
 namespace rtoc {
+
+struct IntArgs {
+  RecView rv;  // sol: the one kernel that writes the iterate; steps: [batch][2] doubles, the primal one is read
+};
 
 static __global__ __launch_bounds__(64) void integrate_solution_kernel(IntArgs a) {
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
-  const int b = item / a.nstages, st = item % a.nstages;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  const int b = item / a.rv.nstages, st = item % a.rv.nstages;
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   const bool impact = g.type == RTOC_GRID_IMPACT;
-  const double step = a.steps[2 * b];
-  double* s = a.sol + (size_t)item * a.sl.stride;
-  const double* d = a.dir + (size_t)item * a.dl.stride;
-  const int nv = a.nv, nvf = nv + a.nf_max;
+  const double step = reinterpret_cast<const double*>(a.rv.steps)[2 * b];
+  double* s = const_cast<double*>(a.rv.sol_at(item));
+  const double* d = a.rv.dir_at(item);
+  const int nv = a.rv.nv(), nu = a.rv.nu(), np = a.rv.L.dims.np;
   auto axpy = [&](int sfield, int n, const double* dv) {
-    double* dst = s + a.sl.off[sfield];
+    double* dst = s + a.rv.sol_off(sfield);
     for (int i = lane; i < n; i += 64) dst[i] += step * dv[i];
   };
-  const double* dx = d + a.dl.off[RTOC_DIR_DX];
-  const double* dl = d + a.dl.off[RTOC_DIR_DLMDGMM];
-  const double* daf = d + a.dl.off[RTOC_DIR_DAF];
-  const double* dbm = d + a.dl.off[RTOC_DIR_DBETAMU];
+  const double* dx = d + a.rv.dir_off(RTOC_DIR_DX);
+  const double* dl = d + a.rv.dir_off(RTOC_DIR_DLMDGMM);
+  const double* daf = d + a.rv.dir_off(RTOC_DIR_DAF);
+  const double* dbm = d + a.rv.dir_off(RTOC_DIR_DBETAMU);
   // q (:62): fixed base q += step dq; floating base: q[7+j] += step dq[6+j] and the base by the SE(3) exponential
   {
-    double* q = s + a.sl.off[RTOC_SOL_Q];
-    const int nb = a.np == 6 ? 6 : 0;
+    double* q = s + a.rv.sol_off(RTOC_SOL_Q);
+    const int nb = np == 6 ? 6 : 0;
     for (int i = lane; i < nv - nb; i += 64) q[(nb ? 7 : 0) + i] += step * dx[nb + i];
     // step 0 (instances the convergence mask froze): the iterate is kept bit for bit, no re-normalisation
     if (nb && lane == 0 && step != 0.0) {
@@ -65,21 +68,20 @@ static __global__ __launch_bounds__(64) void integrate_solution_kernel(IntArgs a
   axpy(RTOC_SOL_V, nv, dx + nv);                                   // (:63)
   if (!impact) {
     axpy(RTOC_SOL_A, nv, daf);                                     // a += step da (:65)
-    axpy(RTOC_SOL_U, a.nu, d + a.dl.off[RTOC_DIR_DU]);             // (:67)
+    axpy(RTOC_SOL_U, nu, d + a.rv.dir_off(RTOC_DIR_DU));           // (:67)
   } else {
     axpy(RTOC_SOL_A, nv, daf);                                     // dv += step ddv (:71); slot A holds dv
-    for (int i = lane; i < a.nu; i += 64) s[a.sl.off[RTOC_SOL_U] + i] = 0.0;  // u.setZero() (:72)
+    for (int i = lane; i < nu; i += 64) s[a.rv.sol_off(RTOC_SOL_U) + i] = 0.0;  // u.setZero() (:72)
   }
   axpy(RTOC_SOL_LMD, nv, dl);                                      // (:74)
   axpy(RTOC_SOL_GMM, nv, dl + nv);                                 // (:75)
   axpy(RTOC_SOL_BETA, nv, dbm);                                    // (:76)
-  if (a.np == 6 && !impact) axpy(RTOC_SOL_NUP, a.np, d + a.dl.off[RTOC_DIR_DNUP]);  // (:77-79)
+  if (np == 6 && !impact) axpy(RTOC_SOL_NUP, np, d + a.rv.dir_off(RTOC_DIR_DNUP));  // (:77-79)
   if (g.dimf > 0) {
     axpy(RTOC_SOL_F, g.dimf, daf + nv);                            // (:81)
     axpy(RTOC_SOL_MU, g.dimf, dbm + nv);                           // (:83)
   }
-  if (g.dims > 0 && !impact) axpy(RTOC_SOL_XI, g.dims, d + a.dl.off[RTOC_DIR_DXI]);  // (:86-89)
-  (void)nvf;
+  if (g.dims > 0 && !impact) axpy(RTOC_SOL_XI, g.dims, d + a.rv.dir_off(RTOC_DIR_DXI));  // (:86-89)
 }
 
 }  // namespace rtoc

@@ -1,7 +1,9 @@
-// kernel_args.hpp -- the argument blocks the host runtime fills for the kernels of a robot shape (kernel_table.hpp), and for the
-// few runtime kernels that take the same kind of block.  Plain structs and no kernel: the host units see these through
-// rt_context.hpp, a kernel header includes this one and defines the kernel beside its own configuration.  The blocks are part of
-// what a shape plugin must agree on with the runtime that loads it (kernel_abi_stamp).
+// kernel_args.hpp -- the argument blocks the host runtime fills for the kernels of a robot shape (kernel_table.hpp): the ones
+// kernel_abi_stamp() names, with the limits the host checks for them, and nothing of a runtime kernel (a runtime kernel's block is
+// defined beside the kernel and starts with the view of record_view.hpp).  Plain structs and no kernel: the host units see these
+// through rt_context.hpp, a kernel header includes this one and defines the kernel beside its own configuration.  The blocks are
+// part of what a shape plugin must agree on with the runtime that loads it: no field is added, removed or reordered without the
+// plugins being rebuilt, and the host fills them field by field, from zero.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,17 +140,6 @@ struct ExpArgs {
   long long* prof;        // optional cycle stamps (slots 32..39) of the work item in the middle of the launch (tuning aid)
 };
 
-// ---- pdipm_update.hpp ----
-struct UpdArgs {
-  double* con;
-  const rtoc_box_row* rows;
-  const rtoc_grid* grid;
-  const double* steps;
-  int nrows, nstages, batch;
-  int nlin;   // records per instance with rows: nstages - 1, or nstages on a ParNMPC horizon
-  rtoc_record_layout nl;
-};
-
 // ---- riccati_scan.hpp ----
 struct ScanArgs {
   const double* kkt;      // [batch][nstages][kkt stride]
@@ -217,48 +208,6 @@ struct PbcArgs {
   int nstages, batch;
   double dt;
   rtoc_record_layout kl, sl, dl;
-};
-
-// ---- state_equation.hpp ----
-struct SeArgs {
-  double* kkt;
-  double* dir;
-  double* dx0;
-  const double* se3;  // [batch][nstages][RTOC_SE3_STRIDE]
-  const rtoc_grid* grid;
-  int nstages, batch;
-  rtoc_record_layout kl, dl;
-  int nx;
-  const double* dt_inst;  // per-instance time steps or nullptr (grid_dt)
-};
-
-// ---- integrate_solution.hpp ----
-struct IntArgs {
-  double* sol;
-  const double* dir;
-  const double* steps;  // [batch][2]: primal, dual
-  const rtoc_grid* grid;
-  int nstages, batch;
-  int nv, nu, np, nf_max, ns_max;
-  rtoc_record_layout sl, dl;
-};
-
-// ---- contact_eval_kkt.hpp (init_records_kernel, contact_cost_kernel), rigid_body.hpp (unconstr_eval_kkt_kernel) ----
-// rtoc_set_configuration_ref_table: the q_ref of a ConfigurationSpaceRefBase and its isActive per GRID POINT.  q == nullptr: no
-// table, the constant q_ref of the cost table is the reference of every grid point (and `active` is not read).
-struct QRefTable {
-  const double* q;     // [nstages][nq] or [batch][nstages][nq]; a row has the layout of rtoc_configuration_cost::q_ref
-  const int* active;   // same leading shape: isActive(grid_info)
-  int per_instance, nq;
-  __device__ size_t row(int b, int nstages, int st) const { return (size_t)(per_instance ? b : 0) * nstages + st; }
-};
-
-// ---- fxx_structure.hpp ----
-struct FxxCheckArgs {
-  const double* kkt;
-  const rtoc_grid* grid;
-  int* flag;
-  int nstages, batch, nv, np, fxx_off, stride;
 };
 
 }  // namespace rtoc

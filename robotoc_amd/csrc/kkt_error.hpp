@@ -12,21 +12,16 @@
 // order and a butterfly at the end: deterministic.  Pure streaming read (HBM-bound, ~11 KB/stage).
 #pragma once
 #include "device_utils.hpp"
-#include "../../include/rtoc.h"
+#include "record_view.hpp"
 
 namespace rtoc {
 
 struct KktErrArgs {
-  const double* kkt;
-  const double* cdd;   // may be null (no contact-dynamics terms)
-  const double* con;   // may be null (no constraint rows)
+  RecView rv;          // cdd == nullptr: no contact-dynamics terms; con == nullptr: neither box rows nor cone rows
   const rtoc_box_row* rows;
-  const rtoc_grid* grid;
-  double* out;         // [batch] sqrt of the sum
   double* partial;     // [batch][nstages] squared residual per grid point
-  int nstages, batch, nrows, cone_contacts, cone_dim, cone_rows, nc_max, impact_cones;
-  int nv, nu, np, nx;
-  rtoc_record_layout kl, cl, nl;
+  int nrows;
+  ConeRows cone;
 };
 
 // One wave per (grid point, instance): the squared residual of that grid point into partial[b][st]; the second kernel
@@ -35,7 +30,9 @@ struct KktErrArgs {
 static __global__ __launch_bounds__(64) void kkt_error_kernel(KktErrArgs a) {
   const int lane = threadIdx.x;
   const int st = blockIdx.x, b = blockIdx.y;
-  if (b >= a.batch || st >= a.nstages) return;
+  if (b >= a.rv.batch || st >= a.rv.nstages) return;
+  const rtoc_record_layout &kl = a.rv.L.kkt, &cl = a.rv.L.cdd, &nl = a.rv.L.con;
+  const int nv = a.rv.nv(), nx = a.rv.L.nx;
   double acc = 0.0;
   auto sq = [&](const double* p, int n) {
     for (int i = lane; i < n; i += 64) {
@@ -44,36 +41,36 @@ static __global__ __launch_bounds__(64) void kkt_error_kernel(KktErrArgs a) {
     }
   };
   {
-    const rtoc_grid g = a.grid[st];
-    const size_t rec = (size_t)b * a.nstages + st;
-    const double* kr = a.kkt + rec * a.kl.stride;
+    const rtoc_grid g = a.rv.grid[st];
+    const size_t rec = (size_t)b * a.rv.nstages + st;
+    const double* kr = a.rv.kkt_at(rec);
     const bool terminal = g.type == RTOC_GRID_TERMINAL, impact = g.type == RTOC_GRID_IMPACT;
-    sq(kr + a.kl.off[RTOC_KKT_LX], a.nx);
+    sq(kr + kl.off[RTOC_KKT_LX], nx);
     if (!terminal) {
-      sq(kr + a.kl.off[RTOC_KKT_FX], a.nx);
+      sq(kr + kl.off[RTOC_KKT_FX], nx);
       if (!impact) {
-        sq(kr + a.kl.off[RTOC_KKT_LU], a.nu);
-        if (g.dims > 0) sq(kr + a.kl.off[RTOC_KKT_PRES], g.dims);
+        sq(kr + kl.off[RTOC_KKT_LU], a.rv.nu());
+        if (g.dims > 0) sq(kr + kl.off[RTOC_KKT_PRES], g.dims);
       }
-      if (a.cdd) {
-        const double* cr = a.cdd + rec * a.cl.stride;
-        sq(cr + a.cl.off[RTOC_CDD_LA], a.nv);  // la (contact grids) / ldv (impact grids)
-        sq(cr + a.cl.off[RTOC_CDD_LF], g.dimf);
-        sq(cr + a.cl.off[RTOC_CDD_IDC], a.nv + g.dimf);
-        if (!impact) sq(cr + a.cl.off[RTOC_CDD_LUP], a.np);
+      if (a.rv.cdd) {
+        const double* cr = a.rv.cdd_at(rec);
+        sq(cr + cl.off[RTOC_CDD_LA], nv);  // la (contact grids) / ldv (impact grids)
+        sq(cr + cl.off[RTOC_CDD_LF], g.dimf);
+        sq(cr + cl.off[RTOC_CDD_IDC], nv + g.dimf);
+        if (!impact) sq(cr + cl.off[RTOC_CDD_LUP], a.rv.L.dims.np);
       }
-      if (a.con) {
-        const double* nr = a.con + rec * a.nl.stride;
+      if (a.rv.con) {
+        const double* nr = a.rv.con_at(rec);
         if (!impact)
           for (int r = lane; r < a.nrows; r += 64)
             if (g.time_stage >= a.rows[r].level) {
-              const double x = nr[a.nl.off[RTOC_CON_RESIDUAL] + r], y = nr[a.nl.off[RTOC_CON_CMPL] + r];
+              const double x = nr[nl.off[RTOC_CON_RESIDUAL] + r], y = nr[nl.off[RTOC_CON_CMPL] + r];
               acc += x * x + y * y;
             }
-        if (a.cone_contacts > 0 && (!impact || a.impact_cones)) {
-          const int row0 = a.nc_max - a.cone_rows * a.cone_contacts, n = a.cone_rows * (g.dimf / a.cone_dim);
+        if (a.cone.contacts > 0 && (!impact || a.cone.impact)) {
+          const int row0 = a.cone.row0, n = a.cone.rows * (g.dimf / a.cone.dim);
           for (int r = lane; r < n; r += 64) {
-            const double x = nr[a.nl.off[RTOC_CON_RESIDUAL] + row0 + r], y = nr[a.nl.off[RTOC_CON_CMPL] + row0 + r];
+            const double x = nr[nl.off[RTOC_CON_RESIDUAL] + row0 + r], y = nr[nl.off[RTOC_CON_CMPL] + row0 + r];
             acc += x * x + y * y;
           }
         }
@@ -82,7 +79,7 @@ static __global__ __launch_bounds__(64) void kkt_error_kernel(KktErrArgs a) {
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) a.partial[(size_t)b * a.nstages + st] = acc;
+  if (lane == 0) a.partial[(size_t)b * a.rv.nstages + st] = acc;
 }
 
 static __global__ void kkt_error_reduce_kernel(const double* partial, double* out, int nstages, int batch) {

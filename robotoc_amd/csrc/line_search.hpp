@@ -3,7 +3,7 @@
 // per shape): rt_line_search.hip launches them and is the one unit that includes this header.
 #pragma once
 #include "device_utils.hpp"
-#include "../../include/rtoc.h"
+#include "record_view.hpp"
 
 namespace rtoc {
 
@@ -15,49 +15,46 @@ namespace rtoc {
 // of Fx, P (split_kkt_residual.hxx:109-115); the terminal grid point carries its cost only.  On records linearised and NOT yet
 // condensed.  partial: [batch][nstages][2] = (cost + barrier, violation); the reduction adds them in grid order.
 struct EvalOcpArgs {
-  const double* kkt;
-  const double* cdd;
-  const double* con;      // may be null
+  RecView rv;             // con == nullptr: neither box rows nor cone rows
   const double* costval;  // [batch][nstages]
   const rtoc_box_row* rows;
-  const rtoc_grid* grid;
   double* partial;
-  int nstages, batch, nrows, cone_contacts, cone_dim, cone_rows, nc_max, impact_cones;
-  int nv, nx;
+  int nrows;
+  ConeRows cone;
   double barrier;
-  rtoc_record_layout kl, cl, nl;
 };
 
 static __global__ __launch_bounds__(64) void eval_ocp_kernel(EvalOcpArgs a) {
   const int lane = threadIdx.x;
   const int st = blockIdx.x, b = blockIdx.y;
-  if (b >= a.batch || st >= a.nstages) return;
+  if (b >= a.rv.batch || st >= a.rv.nstages) return;
+  const rtoc_record_layout &kl = a.rv.L.kkt, &cl = a.rv.L.cdd, &nl = a.rv.L.con;
   double viol = 0.0, bar = 0.0;
   auto l1 = [&](const double* p, int n) {
     for (int i = lane; i < n; i += 64) viol += fabs(p[i]);
   };
-  const rtoc_grid g = a.grid[st];
-  const size_t rec = (size_t)b * a.nstages + st;
+  const rtoc_grid g = a.rv.grid[st];
+  const size_t rec = (size_t)b * a.rv.nstages + st;
   const bool terminal = g.type == RTOC_GRID_TERMINAL, impact = g.type == RTOC_GRID_IMPACT;
   if (!terminal) {
-    const double* kr = a.kkt + rec * a.kl.stride;
-    const double* cr = a.cdd + rec * a.cl.stride;
-    l1(kr + a.kl.off[RTOC_KKT_FX], a.nx);
-    if (!impact && g.dims > 0) l1(kr + a.kl.off[RTOC_KKT_PRES], g.dims);
-    l1(cr + a.cl.off[RTOC_CDD_IDC], a.nv + g.dimf);
-    if (a.con) {
-      const double* nr = a.con + rec * a.nl.stride;
+    const double* kr = a.rv.kkt_at(rec);
+    const double* cr = a.rv.cdd_at(rec);
+    l1(kr + kl.off[RTOC_KKT_FX], a.rv.L.nx);
+    if (!impact && g.dims > 0) l1(kr + kl.off[RTOC_KKT_PRES], g.dims);
+    l1(cr + cl.off[RTOC_CDD_IDC], a.rv.nv() + g.dimf);
+    if (a.rv.con) {
+      const double* nr = a.rv.con_at(rec);
       if (!impact)
         for (int r = lane; r < a.nrows; r += 64)
           if (g.time_stage >= a.rows[r].level) {
-            viol += fabs(nr[a.nl.off[RTOC_CON_RESIDUAL] + r]);
-            bar -= log(nr[a.nl.off[RTOC_CON_SLACK] + r]);
+            viol += fabs(nr[nl.off[RTOC_CON_RESIDUAL] + r]);
+            bar -= log(nr[nl.off[RTOC_CON_SLACK] + r]);
           }
-      if (a.cone_contacts > 0 && (!impact || a.impact_cones)) {
-        const int row0 = a.nc_max - a.cone_rows * a.cone_contacts, n = a.cone_rows * (g.dimf / a.cone_dim);
+      if (a.cone.contacts > 0 && (!impact || a.cone.impact)) {
+        const int row0 = a.cone.row0, n = a.cone.rows * (g.dimf / a.cone.dim);
         for (int r = lane; r < n; r += 64) {
-          viol += fabs(nr[a.nl.off[RTOC_CON_RESIDUAL] + row0 + r]);
-          bar -= log(nr[a.nl.off[RTOC_CON_SLACK] + row0 + r]);
+          viol += fabs(nr[nl.off[RTOC_CON_RESIDUAL] + row0 + r]);
+          bar -= log(nr[nl.off[RTOC_CON_SLACK] + row0 + r]);
         }
       }
     }
@@ -127,33 +124,32 @@ static __global__ void ls_advance_kernel(LsArgs a) {
 // (split_solution.cpp:126-134: lmd, gmm, beta, nu_passive of a floating base, mu of the active contact dimensions, xi of the active
 // switching-constraint rows).  One wave per instance.
 struct LsPenaltyArgs {
-  const double* sol;
-  const rtoc_grid* grid;
+  RecView rv;
   double* penalty;   // [batch]
-  int nstages, batch, nv, np;
-  rtoc_record_layout sl;
   double margin;
 };
 static __global__ __launch_bounds__(64) void ls_penalty_kernel(LsPenaltyArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.rv.batch) return;
+  const rtoc_record_layout& sl = a.rv.L.sol;
+  const int nv = a.rv.nv(), np = a.rv.L.dims.np;
   double m = 0.0;
   auto linf = [&](const double* p, int n) {
     for (int i = lane; i < n; i += 64) m = fmax(m, fabs(p[i]));
   };
-  for (int st = 0; st < a.nstages; ++st) {
-    const rtoc_grid g = a.grid[st];
-    const double* s = a.sol + ((size_t)b * a.nstages + st) * a.sl.stride;
-    linf(s + a.sl.off[RTOC_SOL_LMD], a.nv);
-    linf(s + a.sl.off[RTOC_SOL_GMM], a.nv);
+  for (int st = 0; st < a.rv.nstages; ++st) {
+    const rtoc_grid g = a.rv.grid[st];
+    const double* s = a.rv.sol_at((size_t)b * a.rv.nstages + st);
+    linf(s + sl.off[RTOC_SOL_LMD], nv);
+    linf(s + sl.off[RTOC_SOL_GMM], nv);
     // (the terminal record too: SplitSolution::lagrangeMultiplierLinfNorm of s[N] takes every field, line_search.cpp:120-128 --
     //  beta, nu_passive are zero there unless the caller uploaded something else; the terminal stage has no contact forces, mu of
     //  s[N] is never written by the solver and stays out)
-    linf(s + a.sl.off[RTOC_SOL_BETA], a.nv);
-    if (a.np > 0) linf(s + a.sl.off[RTOC_SOL_NUP], a.np);
+    linf(s + sl.off[RTOC_SOL_BETA], nv);
+    if (np > 0) linf(s + sl.off[RTOC_SOL_NUP], np);
     if (g.type == RTOC_GRID_TERMINAL) continue;
-    linf(s + a.sl.off[RTOC_SOL_MU], g.dimf);
-    if (g.type != RTOC_GRID_IMPACT && g.switching_constraint) linf(s + a.sl.off[RTOC_SOL_XI], g.dims);
+    linf(s + sl.off[RTOC_SOL_MU], g.dimf);
+    if (g.type != RTOC_GRID_IMPACT && g.switching_constraint) linf(s + sl.off[RTOC_SOL_XI], g.dims);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));

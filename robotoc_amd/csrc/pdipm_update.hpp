@@ -2,22 +2,29 @@
 // rows and of the cone rows, and the reset of the step buffer.  Runtime kernels (not per shape): rt_condense.hip launches
 // them and is the one unit that includes this header.
 #pragma once
-#include "friction_cone.hpp"  // cone_nact
-#include "kernel_args.hpp"
+#include "friction_cone.hpp"  // cone_nact, ConeArgs
+#include "record_view.hpp"
 
 namespace rtoc {
+
+struct UpdArgs {
+  RecView rv;  // steps: [batch][2] doubles
+  const rtoc_box_row* rows;
+  int nrows;
+};
 
 // updateSlack / updateDual (constraints_impl.hxx:167-182) with the per-instance step sizes
 static __global__ __launch_bounds__(64) void pdipm_update_kernel(UpdArgs a) {
   const int item = blockIdx.x;
-  const int nst1 = a.nlin;
+  const int nst1 = a.rv.nlin();
   const int b = item / nst1, st = item % nst1;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
   if (g.type == RTOC_GRID_IMPACT) return;
-  double* nr = a.con + ((size_t)b * a.nstages + st) * a.nl.stride;
-  const int* no = a.nl.off;
-  const double ps = a.steps[2 * b], ds = a.steps[2 * b + 1];
+  double* nr = a.rv.con_at((size_t)b * a.rv.nstages + st);
+  const int* no = a.rv.L.con.off;
+  const double* steps = reinterpret_cast<const double*>(a.rv.steps);
+  const double ps = steps[2 * b], ds = steps[2 * b + 1];
   for (int r = threadIdx.x; r < a.nrows; r += 64) {
     if (g.time_stage >= a.rows[r].level) {
       nr[no[RTOC_CON_SLACK] + r] += ps * nr[no[RTOC_CON_DSLACK] + r];

@@ -1,9 +1,11 @@
 // record_view.hpp -- what a kernel may read of a context: the record buffers, the grid, the contact schedule, the model and
-// the record layout (include/rtoc_layout.h), as ONE value.  The evalKKT-side kernels (cost, constraints, state equation,
-// rigid-body linearisation, switching constraint, task costs) take it as the first member of their argument struct and name
-// a field by its RTOC_SOL_* / RTOC_KKT_* / RTOC_CDD_* / RTOC_CON_* / RTOC_DIR_* enum; what else such a struct holds belongs
-// to the launch alone.  The runtime fills a view at every launch (view() in rtoc_capi.hip) and never keeps one: buffers are
-// rebound (rtoc_bind) and swapped for the trial iterate of the line search between launches.
+// the record layout (include/rtoc_layout.h), as ONE value.  Every runtime kernel that reads a record takes it as the first
+// member `rv` of its argument struct (takes_view below holds the launchers to it) and names a field by its RTOC_SOL_* /
+// RTOC_KKT_* / RTOC_CDD_* / RTOC_CON_* / RTOC_DIR_* enum; what else such a struct holds belongs to the launch alone.  The
+// runtime fills a view at every launch (view() in rtoc_capi.hip, through view_args() of rt_context.hpp) and never keeps
+// one: buffers are rebound (rtoc_bind) and swapped for the trial iterate of the line search between launches.
+// Filled by hand, on purpose: the blocks of a robot shape (kernel_args.hpp: their layout is part of what a plugin agrees
+// on, and their kernels bake the record layout into immediates), and Ls*Args / FilterArgs / *TimesArgs, which read no record.
 //
 // Record conventions the enums do not tell:
 //   * contact path: Qaa / la / lf / ha ... live in RTOC_BUF_CDD until the condensation; on impact grids the A slot of the
@@ -15,6 +17,8 @@
 #include "../../include/rtoc_layout.h"
 #include "../../include/rtoc.h"
 #include <stddef.h>
+
+#include <type_traits>
 
 namespace rtoc {
 namespace rbd {
@@ -59,6 +63,24 @@ struct RecView {
   RTOC_HD const double* dir_at(size_t rec) const { return dir + rec * L.dir.stride; }
 };
 
+// The convention, held by the compiler where a launcher names its block: the view comes first, and the block is copied into
+// the kernarg segment as it stands.
+template <class A>
+constexpr bool takes_view = offsetof(A, rv) == 0 && std::is_same_v<decltype(A::rv), RecView> && std::is_trivially_copyable_v<A>;
+
+// The friction / wrench cone rows of a context (rtoc_set_friction_cones, rtoc_set_wrench_cones) as a kernel walks them: a member
+// of the runtime blocks that do (kkt_error.hpp, line_search.hpp), and what the fillers of the shape blocks copy their cone
+// numbers from.  Filled by view_cones() (rt_condense.hip) alone.  contacts == 0: no cone rows.
+struct ConeRows {
+  int contacts;  // most contacts that carry cones
+  int dim;       // force components of a contact (3 or 6): a grid point has g.dimf / dim active ones; 3 where none is set
+  int rows;      // PDIPM rows per contact: RTOC_FRICTION_ROWS, RTOC_WRENCH_ROWS
+  int row0;      // the first cone row of a constraint record: nc_max - rows * contacts
+  int stride;    // doubles of a RTOC_BUF_CONE record
+  int dgdf_off;  // of dg_df within it (friction cones)
+  int impact;    // RTOC_OPT_IMPACT_CONES: 0 = no rows on impact grids
+};
+
 // The numbers of the robot model a kernel's control flow and LDS carving depend on, as kernel arguments (the tangent walk
 // of rigid_body.hpp reads them on its critical path: not from memory).  nv and nu are the view's: rtoc_set_robot_model
 // accepts a model only if they agree with the context's dimensions.
@@ -67,6 +89,16 @@ struct ModelDims {
   int gs;        // lanes per grid point of rbd_values_kernel: the next power of two >= njoints
   int floating;  // the root joint is a free-flyer
   double gx, gy, gz;  // gravity
+};
+
+// rtoc_set_configuration_ref_table: the q_ref of a ConfigurationSpaceRefBase and its isActive per GRID POINT, for the kernels that
+// read the cost table (contact_eval_kkt.hpp, rigid_body.hpp).  q == nullptr: no table, the constant q_ref of the cost table is the
+// reference of every grid point (and `active` is not read).
+struct QRefTable {
+  const double* q;     // [nstages][nq] or [batch][nstages][nq]; a row has the layout of rtoc_configuration_cost::q_ref
+  const int* active;   // same leading shape: isActive(grid_info)
+  int per_instance, nq;
+  RTOC_HD size_t row(int b, int nstages, int st) const { return (size_t)(per_instance ? b : 0) * nstages + st; }
 };
 
 }  // namespace rtoc

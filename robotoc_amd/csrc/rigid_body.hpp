@@ -23,7 +23,6 @@
 // The kernels and their argument blocks: rt_eval_kkt.hip launches them and is the one unit that includes this header.  The
 // model they read and the plan of the walk are rigid_body_model.hpp (host), the spatial arithmetic is rigid_body_math.hpp.
 #pragma once
-#include "kernel_args.hpp"
 #include "device_utils.hpp"
 #include "record_view.hpp"
 #include "rigid_body_math.hpp"

@@ -19,12 +19,23 @@ static bool cond_register_applies(const rtoc_ctx* c) {
   return c->n_stage_contact + c->n_stage_impact == c->nstages - 1;
 }
 
+// The cone rows as the kernels see them (record_view.hpp): the one place their row numbers and record strides are worked out
+ConeRows rtoc::view_cones(const rtoc_ctx* c) {
+  ConeRows r{};
+  r.dim = 3;
+  if (c->cone_contacts <= 0) return r;
+  r.contacts = c->cone_contacts, r.dim = c->cone_dim, r.rows = c->cone_rows;
+  r.row0 = c->dims.nc_max - c->cone_rows * c->cone_contacts;
+  r.stride = c->cone_rows == RTOC_WRENCH_ROWS ? rtoc_wrench_cone_stride(c->cone_contacts) : rtoc_cone_stride(c->dims.nv, c->cone_contacts);
+  r.dgdf_off = rtoc_cone_dgdf_off(c->dims.nv, c->cone_contacts);
+  r.impact = c->impact_cones;
+  return r;
+}
+
 static int launch_condense(rtoc_ctx* c) {
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  CondArgs a;
-  a.stage_list = nullptr;
-  a.nlist = 0;
+  CondArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.cdd = c->buf[RTOC_BUF_CDD].p;
   a.grid = c->d_grid.p;
@@ -42,22 +53,16 @@ static int launch_condense(rtoc_ctx* c) {
   a.kl = c->L.kkt;
   a.cl = c->L.cdd;
   const int nblocks = c->batch * (c->nstages - 1);
-  a.cone_rows = 0;
   a.keep_qaf = c->keep_qaf;
   a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   const bool rv = cond_register_applies(c);
   if ((rv ? cond_rv_fuses_cones(c) : (c->condense_split || c->ks->cond_fuses_cones)) && c->cone_contacts > 0) {  // the cone rows ride with the MJtJinv kernel / in wave 1 of the fused kernel / inside condense_rv_kernel
     if (!c->buf[RTOC_BUF_CONE].p || !c->buf[RTOC_BUF_CON].p) return RTOC_ERR_NOT_READY;
-    const bool wrench = c->cone_rows == RTOC_WRENCH_ROWS;
-    a.cone_rows = c->cone_rows;
+    const ConeRows cone = view_cones(c);
     a.cone_con = c->buf[RTOC_BUF_CON].p;
     a.cone = c->buf[RTOC_BUF_CONE].p;
-    a.cone_contacts = c->cone_contacts;
-    a.cone_dim = c->cone_dim;
-    a.cone_row0 = c->dims.nc_max - c->cone_rows * c->cone_contacts;
-    a.cone_stride = wrench ? rtoc_wrench_cone_stride(c->cone_contacts) : rtoc_cone_stride(c->dims.nv, c->cone_contacts);
-    a.cone_dgdf_off = rtoc_cone_dgdf_off(c->dims.nv, c->cone_contacts);
-    a.cone_impact = c->impact_cones;
+    a.cone_rows = cone.rows, a.cone_contacts = cone.contacts, a.cone_dim = cone.dim, a.cone_row0 = cone.row0;
+    a.cone_stride = cone.stride, a.cone_dgdf_off = cone.dgdf_off, a.cone_impact = cone.impact;
   }
   if (rv) {
     a.stage_list = c->d_stage_list.p;
@@ -94,7 +99,7 @@ void rtoc::launch_fill_steps(rtoc_ctx* c) {
 static int launch_expand(rtoc_ctx* c, double tau) {
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  ExpArgs a;
+  ExpArgs a{};
   a.cdd = c->buf[RTOC_BUF_CDD].p;
   a.dir = c->buf[RTOC_BUF_DIR].p;
   a.grid = c->d_grid.p;
@@ -121,7 +126,8 @@ static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 
   if (!c->buf[RTOC_BUF_CONE].p || !c->buf[RTOC_BUF_CON].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  ConeArgs a;
+  const ConeRows cone = view_cones(c);
+  ConeArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.cdd = c->buf[RTOC_BUF_CDD].p;
   a.con = c->buf[RTOC_BUF_CON].p;
@@ -131,15 +137,9 @@ static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 
   a.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
-  a.max_contacts = c->cone_contacts;
-  a.contact_dim = c->cone_dim;
-  a.prof = nullptr;
-  const bool wrench = c->cone_rows == RTOC_WRENCH_ROWS;
-  a.rows_per_contact = c->cone_rows;
-  a.row0 = c->dims.nc_max - c->cone_rows * c->cone_contacts;
-  a.cone_stride = wrench ? rtoc_wrench_cone_stride(c->cone_contacts) : rtoc_cone_stride(c->dims.nv, c->cone_contacts);
-  a.dgdf_off = rtoc_cone_dgdf_off(c->dims.nv, c->cone_contacts);
-  a.impact_cones = c->impact_cones;
+  a.max_contacts = cone.contacts, a.contact_dim = cone.dim, a.rows_per_contact = cone.rows, a.row0 = cone.row0;
+  a.cone_stride = cone.stride, a.dgdf_off = cone.dgdf_off, a.impact_cones = cone.impact;
+  const bool wrench = cone.rows == RTOC_WRENCH_ROWS;
   a.tau = tau;
   a.kl = c->L.kkt;
   a.cl = c->L.cdd;
@@ -158,18 +158,7 @@ static int launch_cones(rtoc_ctx* c, int phase, double tau) {  // 0 condense, 1 
 
 static int launch_state_correction(rtoc_ctx* c, int mode) {
   if (!c->buf[RTOC_BUF_SE3].p) return RTOC_ERR_BAD_ARG;
-  SeArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.dir = c->buf[RTOC_BUF_DIR].p;
-  a.dx0 = c->buf[RTOC_BUF_DX0].p;
-  a.se3 = c->buf[RTOC_BUF_SE3].p;
-  a.grid = c->d_grid.p;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.kl = c->L.kkt;
-  a.dl = c->L.dir;
-  a.nx = c->L.nx;
-  a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
+  const auto a = view_args<SeArgs>(c);
   const int nblocks = (mode == 2) ? c->batch : c->batch * c->nstages;
   if (mode == 0)
     hipLaunchKernelGGL(state_correction_kernel<0>, dim3(nblocks), dim3(64), 0, c->stream, a);
@@ -225,17 +214,9 @@ int rtoc_update(rtoc_ctx* c) {
     if (rc) return rc;
   }
   if (c->nrows == 0) return RTOC_OK;
-  UpdArgs a;
-  a.con = c->buf[RTOC_BUF_CON].p;
-  a.rows = c->d_rows.p;
-  a.grid = c->d_grid.p;
-  a.steps = c->buf[RTOC_BUF_STEP].p;
-  a.nrows = c->nrows;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.nlin = dynamics_records(c);
-  a.nl = c->L.con;
-  hipLaunchKernelGGL(pdipm_update_kernel, dim3(c->batch * a.nlin), dim3(64), 0, c->stream, a);
+  auto a = view_args<UpdArgs>(c);
+  a.rows = c->d_rows.p, a.nrows = c->nrows;
+  hipLaunchKernelGGL(pdipm_update_kernel, dim3(c->batch * a.rv.nlin()), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
 }

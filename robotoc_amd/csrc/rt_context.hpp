@@ -442,6 +442,15 @@ const KernelSet* find_set(const rtoc_dims* d);
 // rtoc_capi.hip
 int ensure_buffer(rtoc_ctx* c, int b);
 RecView view(const rtoc_ctx* c);
+// The argument block of a kernel that takes the view (record_view.hpp), as its launcher starts it: every field zero, the view as
+// the context stands now.  Called at the launch, never earlier: rtoc_bind and eval_ocp_trial change the pointers between launches
+template <class A>
+static A view_args(const rtoc_ctx* c) {
+  static_assert(takes_view<A>, "a runtime kernel's block starts with `RecView rv` and is copied into the kernarg segment as it stands");
+  A a{};
+  a.rv = view(c);
+  return a;
+}
 // rt_sweep.hip
 int ensure_scan_buffers(rtoc_ctx* c);
 int plan_backward(rtoc_ctx* c, BwdPlan* out);
@@ -449,6 +458,7 @@ int launch_backward(rtoc_ctx* c, const BwdPlan& p);
 int launch_forward(rtoc_ctx* c);
 int launch_sweep(rtoc_ctx* c, const BwdPlan& p);
 // rt_condense.hip
+ConeRows view_cones(const rtoc_ctx* c);
 void launch_fill_steps(rtoc_ctx* c);
 // rt_eval_kkt.hip
 hipError_t reserve_kkterr(rtoc_ctx* c);

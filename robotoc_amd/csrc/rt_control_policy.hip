@@ -31,7 +31,7 @@ static int run_policy(rtoc_ctx* c, double t0, const double* t, int per_instance,
 
   // scratch that only grows: the first call of a context (or the first with an STO problem) allocates, later ones only launch
   HIP_TRY(c->d_policy_tg.grow(c->sto_on ? (size_t)c->batch * c->max_stages : (size_t)c->max_stages));
-  PolicyArgs a;
+  auto a = view_args<PolicyArgs>(c);
   a.t = t, a.x = x, a.out = out;
   if (host) {
     const size_t cap_x = (size_t)c->batch * (nq + nv);
@@ -41,18 +41,15 @@ static int run_policy(rtoc_ctx* c, double t0, const double* t, int per_instance,
     if (input) HIP_TRY(hipMemcpyAsync(d + c->batch, x, sizeof(double) * nx, hipMemcpyHostToDevice, c->stream));
     a.t = d, a.x = d + c->batch, a.out = d + c->batch + cap_x;
   }
-  PolicyTimesArgs ta;
+  PolicyTimesArgs ta{};
   ta.grid = c->d_grid.p, ta.dt_inst = c->sto_on ? c->d_dt.p : nullptr, ta.t = c->d_policy_tg.p;
   ta.nstages = c->nstages, ta.count = count, ta.t0 = t0;
   hipLaunchKernelGGL(policy_times_kernel, dim3(((c->sto_on ? count : 1) + 63) / 64), dim3(64), 0, c->stream, ta);
   HIP_TRY(hipGetLastError());
-  a.sol = c->buf[RTOC_BUF_SOL].p, a.ric = c->buf[RTOC_BUF_RIC].p, a.grid = c->d_grid.p, a.tg = c->d_policy_tg.p;
-  a.nstages = c->nstages, a.count = count, a.N = N;
+  a.ric = c->buf[RTOC_BUF_RIC].p, a.tg = c->d_policy_tg.p;
+  a.count = count, a.N = N;
   a.tg_per_instance = c->sto_on ? 1 : 0, a.t_per_instance = per_instance;
-  a.nv = nv, a.nu = nu, a.nq = nq;
-  a.sol_stride = c->L.sol.stride, a.ric_stride = c->L.ric.stride;
-  a.off_q = c->L.sol.off[RTOC_SOL_Q], a.off_v = c->L.sol.off[RTOC_SOL_V], a.off_u = c->L.sol.off[RTOC_SOL_U];
-  a.off_k = c->L.ric.off[RTOC_RIC_K];
+  a.nq = nq;
   if (input) hipLaunchKernelGGL(control_input_kernel, dim3(count), dim3(64), sizeof(double) * 2 * (size_t)nu, c->stream, a);
   else hipLaunchKernelGGL(control_policy_kernel, dim3(count), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());

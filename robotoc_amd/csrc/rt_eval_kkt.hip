@@ -46,7 +46,7 @@ hipError_t rtoc::set_linearize_lds(const rtoc_robot_model& m, int nlevels, int n
 // (c->h_model is set)
 static ModelDims model_dims(const rtoc_ctx* c) {
   const rtoc_robot_model& m = c->h_model->m;
-  ModelDims d;
+  ModelDims d{};
   d.nq = m.nq, d.njoints = m.njoints, d.ncontacts = m.ncontacts;
   d.nlevels = c->h_model->nlevels, d.nbranch = c->h_model->nbranch, d.dpp = c->h_model->dpp;
   d.gs = 1;
@@ -84,20 +84,7 @@ hipError_t rtoc::reserve_kkterr(rtoc_ctx* c) { return c->d_kkterr.reserve((size_
 int rtoc_integrate_solution(rtoc_ctx* c) {
   CHECK_STAGES(c);
   if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
-  IntArgs a;
-  a.sol = c->buf[RTOC_BUF_SOL].p;
-  a.dir = c->buf[RTOC_BUF_DIR].p;
-  a.steps = c->buf[RTOC_BUF_STEP].p;
-  a.grid = c->d_grid.p;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.nv = c->dims.nv;
-  a.nu = c->dims.nu;
-  a.np = c->dims.np;
-  a.nf_max = c->dims.nf_max;
-  a.ns_max = c->dims.ns_max;
-  a.sl = c->L.sol;
-  a.dl = c->L.dir;
+  const auto a = view_args<IntArgs>(c);
   hipLaunchKernelGGL(integrate_solution_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -234,8 +221,8 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   const bool any_impact = any_grid_point(c, c->nstages - 1, grid_is_impact);
   rc = ensure_rbd_values(c);
   if (rc) return rc;
-  rbd::ValArgs v;
-  v.rv = view(c), v.md = model_dims(c);
+  auto v = view_args<rbd::ValArgs>(c);
+  v.md = model_dims(c);
   v.unconstr = unconstr ? 1 : 0;
   const int G = 64 / v.md.gs;
   const long long items = (long long)c->batch * dynamics_records(c);
@@ -258,8 +245,8 @@ static int launch_linearize(rtoc_ctx* c, int augment_residual, bool unconstr, do
   if (augment_residual && !c->buf[RTOC_BUF_KKT].p) return RTOC_ERR_NOT_READY;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  rbd::LinArgs a;
-  a.rv = view(c), a.md = model_dims(c);
+  auto a = view_args<rbd::LinArgs>(c);
+  a.md = model_dims(c);
   if (!augment_residual) a.rv.kkt = nullptr;
   a.unconstr = unconstr ? 1 : 0;
   a.scale = scale;
@@ -390,8 +377,7 @@ static int launch_state_equation(rtoc_ctx* c, bool zeroed) {
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_DX0);
   if (!rc && c->dims.np == 6) rc = ensure_buffer(c, RTOC_BUF_SE3);
   if (rc) return rc;
-  SeLinArgs a;
-  a.rv = view(c);
+  auto a = view_args<SeLinArgs>(c);
   a.x0 = c->d_x0.p;
   a.zeroed = zeroed ? 1 : 0;
   hipLaunchKernelGGL(state_equation_lin_kernel, dim3(c->batch * c->nstages), dim3(64), 0, c->stream, a);
@@ -414,8 +400,7 @@ int rtoc_set_constraint_bounds(rtoc_ctx* c, const double* bounds, int nrows, dou
 }
 
 static int launch_ubox(rtoc_ctx* c, int mode, bool contact = false) {
-  UboxArgs a;
-  a.rv = view(c);
+  auto a = view_args<UboxArgs>(c);
   a.rows = c->d_rows.p;
   a.entry = c->d_entry.p;
   a.bounds = c->d_bounds.p;
@@ -456,7 +441,7 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   if (!(dt > 0.0) || c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
   if (!c->h_model || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
-  QRefTable qtab;
+  QRefTable qtab{};
   int rc = configuration_ref_table(c, &qtab);   // ahead of the first launch: a refusal leaves the records alone
   if (!rc && c->ntasks > 0) rc = task_costs_ready(c, true);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_KKT);
@@ -466,8 +451,7 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
   bool fresh = false;
   HIP_TRY(reserve_active(c, &fresh));
   if (fresh) HIP_TRY(hipMemsetAsync(c->d_active.p, 0, sizeof(unsigned) * c->max_stages, c->stream));  // no contacts: an all-zero schedule
-  rbd::UkArgs a;
-  a.rv = view(c);
+  auto a = view_args<rbd::UkArgs>(c);
   a.cost = c->d_cost.p;
   a.x0 = c->d_x0.p;
   a.dt = dt;
@@ -491,28 +475,10 @@ int rtoc_unconstr_eval_kkt(rtoc_ctx* c, double dt) {
 // ---- KKT error ------------------------------------------------------------------------------
 int rtoc::launch_kkt_error(rtoc_ctx* c) {
   HIP_TRY(reserve_kkterr(c));
-  KktErrArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
-  a.rows = c->d_rows.p;
-  a.grid = c->d_grid.p;
-  a.out = c->d_kkterr.p;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.nrows = c->nrows;
-  a.cone_contacts = c->cone_contacts;
-  a.cone_dim = c->cone_dim > 0 ? c->cone_dim : 3;
-  a.cone_rows = c->cone_rows;
-  a.impact_cones = c->impact_cones;
-  a.nc_max = c->dims.nc_max;
-  a.nv = c->dims.nv;
-  a.nu = c->dims.nu;
-  a.np = c->dims.np;
-  a.nx = c->L.nx;
-  a.kl = c->L.kkt;
-  a.cl = c->L.cdd;
-  a.nl = c->L.con;
+  auto a = view_args<KktErrArgs>(c);
+  if (!(c->nrows > 0 || c->cone_contacts > 0)) a.rv.con = nullptr;   // the constraint records may exist: nothing of them counts
+  a.rows = c->d_rows.p, a.nrows = c->nrows;
+  a.cone = view_cones(c);
   a.partial = c->d_kkterr.p + c->batch;
   hipLaunchKernelGGL(kkt_error_kernel, dim3(c->nstages, c->batch), dim3(64), 0, c->stream, a);
   hipLaunchKernelGGL(kkt_error_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a.partial, c->d_kkterr.p,
@@ -587,12 +553,12 @@ static int launch_wrench_cones(rtoc_ctx* c, int mode) {
   if (m.ncontacts > c->cone_contacts) return RTOC_ERR_BAD_ARG;
   for (int k = 0; k < m.ncontacts; ++k)
     if (m.contact_type[k] != RTOC_CONTACT_SURFACE) return RTOC_ERR_BAD_ARG;
-  WcArgs a;
-  a.rv = view(c), a.md = model_dims(c);
+  const ConeRows cone = view_cones(c);
+  auto a = view_args<WcArgs>(c);
+  a.md = model_dims(c);
   a.table = c->d_wcone.p;
   a.mode = mode;
-  a.row0 = c->dims.nc_max - RTOC_WRENCH_ROWS * c->cone_contacts, a.cone_stride = rtoc_wrench_cone_stride(c->cone_contacts);
-  a.impact_cones = c->impact_cones;
+  a.row0 = cone.row0, a.cone_stride = cone.stride, a.impact_cones = cone.impact;
   a.barrier = c->barrier;
   hipLaunchKernelGGL(wrench_cone_eval_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
@@ -605,17 +571,16 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
   if (c->n_mu < m.ncontacts) return RTOC_ERR_NOT_READY;  // a friction coefficient for every contact of the model
   for (int k = 0; k < m.ncontacts; ++k)
     if ((m.contact_type[k] == RTOC_CONTACT_SURFACE ? 6 : 3) != c->cone_dim) return RTOC_ERR_BAD_ARG;
-  CcArgs a;
-  a.rv = view(c), a.md = model_dims(c);
+  const ConeRows cone = view_cones(c);
+  auto a = view_args<CcArgs>(c);
+  a.md = model_dims(c);
   a.mu = c->d_mu.p;
   a.mode = mode;
-  a.contact_dim = c->cone_dim, a.row0 = c->dims.nc_max - RTOC_FRICTION_ROWS * c->cone_contacts;
-  a.cone_stride = rtoc_cone_stride(c->dims.nv, c->cone_contacts), a.dgdf_off = rtoc_cone_dgdf_off(c->dims.nv, c->cone_contacts);
-  a.impact_cones = c->impact_cones;
+  a.contact_dim = cone.dim, a.row0 = cone.row0, a.cone_stride = cone.stride, a.dgdf_off = cone.dgdf_off, a.impact_cones = cone.impact;
   a.exact_jacobian = c->exact_cone_jacobian;
   a.barrier = c->barrier;
   if (mode == CC_LINEARIZE && c->vals_fresh && c->d_vals.p) {   // kinematics already there: no tree walk (contact_cone_vals_kernel)
-    CvArgs v;
+    CvArgs v{};
     v.c = a;
     v.vals = c->d_vals.p;
     hipLaunchKernelGGL(contact_cone_vals_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, v);
@@ -648,8 +613,8 @@ int rtoc_contact_init_constraints(rtoc_ctx* c) {
 
 // linearizeSwitchingConstraint (src/dynamics/switching_constraint.cpp:26-70) on the grids that carry one
 static int launch_switching_constraint(rtoc_ctx* c) {
-  SwLinArgs a;
-  a.rv = view(c), a.md = model_dims(c);
+  auto a = view_args<SwLinArgs>(c);
+  a.md = model_dims(c);
   a.exact_transport = c->exact_transport;
   for (int i = 0; i < c->nstages; ++i)
     if (c->h_grid[i].switching_constraint && c->h_grid[i].dims > c->dims.ns_max) return RTOC_ERR_BAD_ARG;
@@ -666,7 +631,7 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   CHECK_READY(c);
   if (!c->h_model || !c->d_active.p || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
   const bool switching = any_grid_point(c, c->nstages, grid_has_switching);
-  QRefTable qtab;
+  QRefTable qtab{};
   int rc = configuration_ref_table(c, &qtab);   // ahead of the first launch: a refusal leaves the records alone
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_KKT);
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
@@ -681,8 +646,7 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
   if (c->sto_on) rc = launch_sto(c, STO_TIME_STEPS);
   if (rc) return rc;
   HIP_TRY(reserve_costval(c));
-  CostArgs a;
-  a.rv = view(c);
+  auto a = view_args<CostArgs>(c);
   a.cost = c->d_cost.p;
   a.cost_out = c->d_costval.p;
   a.qtab = qtab;
@@ -691,8 +655,8 @@ int rtoc_contact_eval_kkt(rtoc_ctx* c) {
     // the values pre-pass of the rigid-body linearisation (lanes = bodies; writes its scratch and RTOC_CDD_IDC, which nothing
     // here zeroes): the one is bound by HBM writes, the other by latency -- 1.1 ms each per 4096 x 47 grid points, one after the
     // other on one stream.  The cost kernel and everything behind it wait for both.
-    InitArgs ia;
-    ia.rv = a.rv, ia.cost = c->d_cost.p, ia.qtab = qtab;
+    auto ia = view_args<InitArgs>(c);
+    ia.cost = c->d_cost.p, ia.qtab = qtab;
     const long long nrec = (long long)c->batch * c->nstages;
     // four workgroups per CU: half of the wave slots, so that the pre-pass's waves are resident beside them
     const int blocks = (int)(nrec < (long long)c->num_cus * 4 ? nrec : (long long)c->num_cus * 4);

@@ -22,7 +22,7 @@ static int interp_ready(rtoc_ctx* c, int* ncontacts, unsigned* six_rows) {
 }
 
 static int launch_times(rtoc_ctx* c, double t0, double* t, double* dt_out, int* type_out) {
-  InterpTimesArgs a;
+  InterpTimesArgs a{};
   a.grid = c->d_grid.p, a.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   a.t = t, a.dt_out = dt_out, a.type_out = type_out;
   a.nstages = c->nstages, a.batch = c->batch, a.t0 = t0;
@@ -70,8 +70,7 @@ int rtoc_solution_interpolate(rtoc_ctx* c, double t0) {
   if (rc) return rc;
   rc = launch_times(c, t0, c->d_interp_t.p, nullptr, nullptr);
   if (rc) return rc;
-  InterpArgs a;
-  a.rv = view(c);
+  auto a = view_args<InterpArgs>(c);
   a.st.sol = c->d_isol.p, a.st.t = c->d_isol_t.p, a.st.dt = c->d_isol_t.p + cap;
   a.st.type = c->d_isol_type.p, a.st.mask = ncontacts > 0 ? c->d_isol_mask.p : nullptr;
   a.st.n = c->isol_n, a.st.per_instance = c->isol_per_instance;

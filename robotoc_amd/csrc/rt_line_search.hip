@@ -35,7 +35,7 @@ int rtoc_line_search_filter(rtoc_ctx* c, const double* cost, const double* viola
   HIP_TRY(hipMemcpyAsync(c->d_ls_in.p, cost, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_ls_in.p + c->batch, violation, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
   if (mask) HIP_TRY(hipMemcpyAsync(c->d_ls_flags.p, mask, sizeof(int) * count, hipMemcpyHostToDevice, c->stream));
-  FilterArgs a;
+  FilterArgs a{};
   a.filt = c->d_filter.p;
   a.nfilt = c->d_nfilter.p;
   a.cost = c->d_ls_in.p;
@@ -70,20 +70,13 @@ int rtoc::ensure_line_search(rtoc_ctx* c) {
 // (pre-condensation) into out[2][batch]
 int rtoc::launch_eval_ocp(rtoc_ctx* c, double* out) {
   if (!c->d_costval.p || !c->buf[RTOC_BUF_KKT].p || !c->buf[RTOC_BUF_CDD].p) return RTOC_ERR_NOT_READY;
-  EvalOcpArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.cdd = c->buf[RTOC_BUF_CDD].p;
-  a.con = (c->nrows > 0 || c->cone_contacts > 0) ? c->buf[RTOC_BUF_CON].p : nullptr;
+  auto a = view_args<EvalOcpArgs>(c);
+  if (!(c->nrows > 0 || c->cone_contacts > 0)) a.rv.con = nullptr;   // the constraint records may exist: nothing of them counts
   a.costval = c->d_costval.p;
-  a.rows = c->d_rows.p;
-  a.grid = c->d_grid.p;
+  a.rows = c->d_rows.p, a.nrows = c->nrows;
+  a.cone = view_cones(c);
   a.partial = c->d_eval_part.p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nrows = c->nrows;
-  a.cone_contacts = c->cone_contacts, a.cone_dim = c->cone_dim > 0 ? c->cone_dim : 3, a.cone_rows = c->cone_rows;
-  a.nc_max = c->dims.nc_max, a.impact_cones = c->impact_cones;
-  a.nv = c->dims.nv, a.nx = c->L.nx;
   a.barrier = c->barrier;
-  a.kl = c->L.kkt, a.cl = c->L.cdd, a.nl = c->L.con;
   hipLaunchKernelGGL(eval_ocp_kernel, dim3(c->nstages, c->batch), dim3(64), 0, c->stream, a);
   hipLaunchKernelGGL(eval_ocp_reduce_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, c->d_eval_part.p, out, c->nstages, c->batch);
   HIP_TRY(hipGetLastError());
@@ -147,7 +140,7 @@ int rtoc_contact_eval_ocp(rtoc_ctx* c, int trial, double* host_cost, double* hos
 }
 
 static int launch_filter_device(rtoc_ctx* c, const double* eval, const int* mask, int seed_empty) {
-  FilterArgs a;
+  FilterArgs a{};
   a.filt = c->d_filter.p, a.nfilt = c->d_nfilter.p;
   a.cost = eval, a.viol = eval + c->batch;
   a.mask = mask;
@@ -197,7 +190,7 @@ int rtoc_contact_line_search(rtoc_ctx* c, int* host_trials) {
   // UnconstrLineSearch (src/line_search/unconstr_line_search.cpp) has the filter method only and ignores line_search_method: an
   // unconstrained context takes the filter path whatever rtoc_set_line_search_method said (its SOL records have no beta / mu / xi)
   const bool merit = c->ls_method == 1 && !(c->ls_unconstr_dt > 0.0);
-  LsMeritArgs ma;
+  LsMeritArgs ma{};
   if (!merit) {
     rc = launch_filter_device(c, c->d_eval.p, nullptr, 1);   // an empty filter is seeded with the current iterate (:58-62)
     if (rc) return rc;
@@ -205,9 +198,8 @@ int rtoc_contact_line_search(rtoc_ctx* c, int* host_trials) {
     // meritBacktrackingLineSearch (:87-109): penalty parameter from the multipliers of the iterate, directional derivative of the
     // merit function from ONE more trial at step eps for every instance
     if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
-    LsPenaltyArgs pa;
-    pa.sol = c->buf[RTOC_BUF_SOL].p, pa.grid = c->d_grid.p, pa.penalty = c->d_ls_merit.p;
-    pa.nstages = c->nstages, pa.batch = c->batch, pa.nv = c->dims.nv, pa.np = c->dims.np, pa.sl = c->L.sol, pa.margin = c->ls_margin;
+    auto pa = view_args<LsPenaltyArgs>(c);
+    pa.penalty = c->d_ls_merit.p, pa.margin = c->ls_margin;
     hipLaunchKernelGGL(ls_penalty_kernel, dim3(c->batch), dim3(64), 0, c->stream, pa);
     ma.cur = c->d_eval.p, ma.trial = c->d_eval.p + 2 * c->batch, ma.penalty = c->d_ls_merit.p, ma.dd = c->d_ls_merit.p + c->batch;
     ma.trial_steps = c->d_ls_steps.p, ma.alpha = c->d_ls_steps.p + 2 * c->batch, ma.active = c->d_ls_active.p, ma.accepted = c->d_ls_flags.p + c->batch;
@@ -220,7 +212,7 @@ int rtoc_contact_line_search(rtoc_ctx* c, int* host_trials) {
     hipLaunchKernelGGL(ls_merit_kernel, dim3((c->batch + 255) / 256), dim3(256), 0, c->stream, ma);
     HIP_TRY(hipGetLastError());
   }
-  LsArgs a;
+  LsArgs a{};
   a.steps = c->buf[RTOC_BUF_STEP].p;
   a.trial_steps = c->d_ls_steps.p;
   a.alpha = c->d_ls_steps.p + 2 * c->batch;

@@ -127,8 +127,7 @@ int rtoc_parnmpc_eval_kkt(rtoc_ctx* c, double dt) {
   if (!rc) rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (!rc) rc = reserve_empty_schedule(c);
   if (rc) return rc;
-  PnStageArgs a;
-  a.rv = view(c);
+  auto a = view_args<PnStageArgs>(c);
   a.cost = c->d_cost.p;
   a.x0 = c->d_x0.p;
   a.dt = dt;
@@ -144,7 +143,7 @@ int rtoc_parnmpc_eval_kkt(rtoc_ctx* c, double dt) {
 static int launch_backward_correction(rtoc_ctx* c, double dt) {
   int rc = reserve_parnmpc(c);
   if (rc) return rc;
-  PbcArgs a;
+  PbcArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.sol = c->buf[RTOC_BUF_SOL].p;
   a.dir = c->buf[RTOC_BUF_DIR].p;

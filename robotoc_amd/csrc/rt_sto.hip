@@ -13,12 +13,8 @@ static int sto_count_events(const rtoc_ctx* c) {
 }
 
 static StoDevArgs sto_args(rtoc_ctx* c) {
-  StoDevArgs a;
-  memset(&a, 0, sizeof(a));
+  auto a = view_args<StoDevArgs>(c);
   const size_t ne = (size_t)c->batch * (c->sto_nev > 0 ? c->sto_nev : 1);
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.dir = c->buf[RTOC_BUF_DIR].p;
-  a.grid = c->d_grid.p;
   a.ts = c->d_ts.p;
   a.dt_inst = c->d_dt.p;
   a.t_inst = c->d_gt_inst.p;
@@ -30,10 +26,7 @@ static StoDevArgs sto_args(rtoc_ctx* c) {
   a.qtt = c->d_sto_out.p + ne;
   a.err = c->d_sto_out.p + 2 * ne;
   a.kkterr = c->d_kkterr.p;
-  a.steps = c->buf[RTOC_BUF_STEP].p;
-  a.nstages = c->nstages, a.batch = c->batch, a.nev = c->sto_nev;
-  a.kkt_stride = c->L.kkt.stride, a.scal_off = c->L.kkt.off[RTOC_KKT_SCAL];
-  a.dir_stride = c->L.dir.stride, a.dts_off = c->L.dir.off[RTOC_DIR_DTS];
+  a.nev = c->sto_nev;
   a.t0 = c->sto_t0, a.T = c->sto_T, a.barrier = c->sto_barrier, a.tau = c->sto_tau, a.sto_reg = c->sto_reg;
   return a;
 }
@@ -68,17 +61,9 @@ int rtoc_sto_eval_kkt(rtoc_ctx* c, const double* host_lt, const double* host_qtt
     HIP_TRY(hipMemcpyAsync(d_lt, host_lt, (size_t)c->batch * nev * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_qtt, host_qtt, (size_t)c->batch * nev * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  StoArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.grid = c->d_grid.p;
-  a.lt = d_lt;
-  a.qtt = d_qtt;
-  a.err = d_err;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
+  auto a = view_args<StoArgs>(c);
+  a.lt = d_lt, a.qtt = d_qtt, a.err = d_err;
   a.nev = nev;
-  a.stride = c->L.kkt.stride;
-  a.scal_off = c->L.kkt.off[RTOC_KKT_SCAL];
   hipLaunchKernelGGL(sto_eval_kkt_kernel, dim3((c->batch + 63) / 64), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   if (host_err_sq && count > 0)

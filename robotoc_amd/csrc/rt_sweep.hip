@@ -35,8 +35,7 @@ int rtoc::ensure_scan_buffers(rtoc_ctx* c) {
 // the arguments every backward launch shares (the register-resident and register-wide paths run only without
 // RTOC_OPT_WRITEBACK_KKT: writeback is set on the tile-split and scan paths alone)
 static BwdArgs bwd_args(const rtoc_ctx* c, int first, int end) {
-  BwdArgs a;
-  memset(&a, 0, sizeof(a));
+  BwdArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.kkt_rw = c->buf[RTOC_BUF_KKT].p;
   a.ric = c->buf[RTOC_BUF_RIC].p;
@@ -56,7 +55,7 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   int rc0 = ensure_scan_buffers(c);
   if (rc0) return rc0;
   const int n = c->nstages, nb = end - first;
-  ScanArgs s;
+  ScanArgs s{};
   s.kkt = c->buf[RTOC_BUF_KKT].p;
   s.grid = c->d_grid.p;
   s.status = c->d_status.p;
@@ -82,7 +81,7 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
   a.scan_ps_stride = ks->scan_ps_stride;
   a.scan_ps_soff = ks->scan_ps_soff;
   const bool sto = grid_has_sto(c);
-  StoScanArgs t;
+  StoScanArgs t{};
   // Grids with switching-time optimisation: the bundles of the vector pass (everything of the vector recursion that does not depend
   // on the chain) are prepared by n - 1 more workgroups per instance of the SAME launch -- unless the policy workgroups write the
   // mutated Quu, lu back into the KKT records (RTOC_OPT_WRITEBACK_KKT), which the preparation reads: then it runs first, by itself.
@@ -105,16 +104,8 @@ static int launch_backward_scan(rtoc_ctx* c, const BwdPlan& p, int first, int en
 static int check_fxx(rtoc_ctx* c) {
   HIP_TRY(c->d_fxx_flag.reserve(1));
   HIP_TRY(hipMemsetAsync(c->d_fxx_flag.p, 0, sizeof(int), c->stream));
-  FxxCheckArgs a;
-  a.kkt = c->buf[RTOC_BUF_KKT].p;
-  a.grid = c->d_grid.p;
+  auto a = view_args<FxxCheckArgs>(c);
   a.flag = c->d_fxx_flag.p;
-  a.nstages = c->nstages;
-  a.batch = c->batch;
-  a.nv = c->dims.nv;
-  a.np = c->dims.np;
-  a.fxx_off = c->L.kkt.off[RTOC_KKT_FXX];
-  a.stride = c->L.kkt.stride;
   hipLaunchKernelGGL(fxx_structure_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   int bad = 1;
@@ -238,7 +229,7 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
   int rc0 = ensure_scan_buffers(c);
   if (rc0) return rc0;
   const int n = c->nstages, nb = end - first, N = n - 1;
-  FwdScanArgs s;
+  FwdScanArgs s{};
   s.kkt = c->buf[RTOC_BUF_KKT].p;
   s.ric = c->buf[RTOC_BUF_RIC].p;
   s.dir = c->buf[RTOC_BUF_DIR].p;
@@ -266,7 +257,7 @@ static int launch_forward_scan(rtoc_ctx* c, int first, int end, hipStream_t stre
 
 static int launch_forward_range(rtoc_ctx* c, int first, int end, hipStream_t stream) {
   if (forward_scan_applies(c)) return launch_forward_scan(c, first, end, stream);
-  FwdArgs a;
+  FwdArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.ric = c->buf[RTOC_BUF_RIC].p;
   a.dir = c->buf[RTOC_BUF_DIR].p;
@@ -338,7 +329,7 @@ int rtoc_riccati_sweep(rtoc_ctx* c) {
 }
 
 static int launch_fill(rtoc_ctx* c, double dt) {
-  FillArgs a;
+  FillArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.nstages = c->nstages;
   a.batch = c->batch;
@@ -359,7 +350,7 @@ static int launch_unconstr_riccati(rtoc_ctx* c, double dt, bool forward) {
   if (!rc && forward) rc = ensure_buffer(c, RTOC_BUF_DIR);
   if (rc) return rc;
   if (!c->buf[RTOC_BUF_KKT].p) return RTOC_ERR_NOT_READY;
-  UrArgs a;
+  UrArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.kkt_rw = c->buf[RTOC_BUF_KKT].p;
   a.ric = c->buf[RTOC_BUF_RIC].p;
@@ -388,7 +379,7 @@ static int launch_unconstr_dynamics(rtoc_ctx* c, bool expand, double dt) {
   if (c->dims.nu != c->dims.nv || c->dims.nf_max != 0) return RTOC_ERR_BAD_ARG;
   int rc = ensure_buffer(c, RTOC_BUF_CDD);
   if (rc) return rc;
-  UdArgs a;
+  UdArgs a{};
   a.kkt = c->buf[RTOC_BUF_KKT].p;
   a.cdd = c->buf[RTOC_BUF_CDD].p;
   a.dir = c->buf[RTOC_BUF_DIR].p;

@@ -139,8 +139,7 @@ int rtoc::launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out) {
   int rc = task_costs_ready(c, unconstr);
   if (rc) return rc;
   const bool sto = c->sto_on && !unconstr;
-  TaskCostArgs a;
-  a.rv = view(c);
+  auto a = view_args<TaskCostArgs>(c);
   a.cost_out = cost_out;
   a.terms = c->d_tasks.p;
   a.t_fixed = sto ? nullptr : c->d_gt.p;
@@ -200,8 +199,7 @@ int rtoc_set_contact_force_cost(rtoc_ctx* c, const rtoc_contact_force_cost* cost
 int rtoc::launch_force_cost(rtoc_ctx* c, double* cost_out) {
   if (!c->h_model || !c->d_fcost.p || !c->d_active.p) return RTOC_ERR_NOT_READY;
   const rtoc_robot_model& m = c->h_model->m;
-  ForceCostArgs a;
-  a.rv = view(c);
+  auto a = view_args<ForceCostArgs>(c);
   a.cost = c->d_fcost.p;
   a.cost_out = cost_out;
   a.per_instance = c->fcost_per_instance;

@@ -449,10 +449,10 @@ int rtoc::ensure_buffer(rtoc_ctx* c, int b) {
   return RTOC_OK;
 }
 
-// The context as the evalKKT-side kernels see it (record_view.hpp).  Taken at every launch and never kept: rtoc_bind and the
+// The context as the runtime kernels see it (record_view.hpp).  Taken at every launch and never kept: rtoc_bind and the
 // trial iterate of the line search (eval_ocp_trial) change the pointers between launches.
 RecView rtoc::view(const rtoc_ctx* c) {
-  RecView v;
+  RecView v{};
   v.sol = c->buf[RTOC_BUF_SOL].p, v.kkt = c->buf[RTOC_BUF_KKT].p, v.cdd = c->buf[RTOC_BUF_CDD].p, v.con = c->buf[RTOC_BUF_CON].p;
   v.dir = c->buf[RTOC_BUF_DIR].p, v.cone = c->buf[RTOC_BUF_CONE].p, v.se3 = c->buf[RTOC_BUF_SE3].p, v.dx0 = c->buf[RTOC_BUF_DX0].p;
   v.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;

@@ -10,10 +10,13 @@
 // pure HBM latency, one 64-lane wave per grid point.
 #pragma once
 #include "device_utils.hpp"
-#include "kernel_args.hpp"  // SeArgs
-#include "../../include/rtoc.h"
+#include "record_view.hpp"
 
 namespace rtoc {
+
+struct SeArgs {
+  RecView rv;  // se3: [batch][nstages][RTOC_SE3_STRIDE]
+};
 
 // mode 0: correctLinearize(Impact)StateEquation on every non-terminal grid point
 // mode 1: correctCostateDirection on every grid point
@@ -25,9 +28,9 @@ __global__ __launch_bounds__(64) void state_correction_kernel(SeArgs a) {
   __shared__ double sIn[64];
   if (MODE == 2) {
     const int b = blockIdx.x;
-    if (b >= a.batch) return;
-    const double* inv = a.se3 + ((size_t)b * a.nstages) * RTOC_SE3_STRIDE + RTOC_SE3_FQQ_PREV_INV;
-    double* dq = a.dx0 + (size_t)b * a.nx;
+    if (b >= a.rv.batch) return;
+    const double* inv = a.rv.se3 + ((size_t)b * a.rv.nstages) * RTOC_SE3_STRIDE + RTOC_SE3_FQQ_PREV_INV;
+    double* dq = a.rv.dx0 + (size_t)b * a.rv.L.nx;
     if (lane < 6) sIn[lane] = dq[lane];
     __syncthreads();
     if (lane < 6) {
@@ -39,12 +42,13 @@ __global__ __launch_bounds__(64) void state_correction_kernel(SeArgs a) {
     return;
   }
   const int item = blockIdx.x;
-  const int b = item / a.nstages, st = item % a.nstages;
-  if (b >= a.batch) return;
-  const rtoc_grid g = a.grid[st];
-  const double* se = a.se3 + (size_t)item * RTOC_SE3_STRIDE;
+  const int b = item / a.rv.nstages, st = item % a.rv.nstages;
+  if (b >= a.rv.batch) return;
+  const rtoc_grid g = a.rv.grid[st];
+  const double* se = a.rv.se3 + (size_t)item * RTOC_SE3_STRIDE;
   if (MODE == 1) {
-    double* dl = a.dir + (size_t)item * a.dl.stride + a.dl.off[RTOC_DIR_DLMDGMM];
+    // (the one write into the direction records outside the shape kernels: the view's dir is theirs to read)
+    double* dl = const_cast<double*>(a.rv.dir_at(item)) + a.rv.dir_off(RTOC_DIR_DLMDGMM);
     const double* inv = se + RTOC_SE3_FQQ_PREV_INV;
     if (lane < 6) sIn[lane] = dl[lane];
     __syncthreads();
@@ -58,11 +62,11 @@ __global__ __launch_bounds__(64) void state_correction_kernel(SeArgs a) {
   }
   if (g.type == RTOC_GRID_TERMINAL) return;
   const bool impact = g.type == RTOC_GRID_IMPACT;
-  const int nx = a.nx, nv = nx / 2;
-  double* kr = a.kkt + (size_t)item * a.kl.stride;
-  double* Fxx = kr + a.kl.off[RTOC_KKT_FXX];
-  double* Fx = kr + a.kl.off[RTOC_KKT_FX];
-  double* fx = kr + a.kl.off[RTOC_KKT_FFX];
+  const int nx = a.rv.L.nx, nv = nx / 2;
+  double* kr = a.rv.kkt_at(item);
+  double* Fxx = kr + a.rv.kkt_off(RTOC_KKT_FXX);
+  double* Fx = kr + a.rv.kkt_off(RTOC_KKT_FX);
+  double* fx = kr + a.rv.kkt_off(RTOC_KKT_FFX);
   const double* inv = se + RTOC_SE3_FQQ_INV;
   // Fqq_tmp = Fqq.topLeftCorner<6,6>(), Fq_tmp, fq_tmp
   if (lane < 36) sIn[lane] = Fxx[i + (size_t)j * nx];
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(64) void state_correction_kernel(SeArgs a) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) acc += inv[i + 6 * k] * sIn[k + 6 * j];
     Fxx[i + (size_t)j * nx] = -acc;                                        // Fqq corner (:81 / impact :69)
-    if (!impact) Fxx[i + (size_t)(nv + j) * nx] = -grid_dt(a.grid, a.dt_inst, b, a.nstages, st) * inv[i + 6 * j];  // Fqv corner (:82)
+    if (!impact) Fxx[i + (size_t)(nv + j) * nx] = -grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st) * inv[i + 6 * j];  // Fqv corner (:82)
   } else if (lane < 42) {
     const int r = lane - 36;
     double acc = 0.0;

@@ -21,7 +21,7 @@
 // (rtoc_sto_set_cost_terms), like rtoc_sto_eval_kkt always did.
 #pragma once
 #include "device_utils.hpp"
-#include "../../include/rtoc.h"
+#include "record_view.hpp"
 
 namespace rtoc {
 
@@ -31,11 +31,9 @@ namespace rtoc {
 #define RTOC_STO_CON_STRIDE (6 * (RTOC_STO_MAX_EVENTS + 1))
 
 struct StoDevArgs {
-  double* kkt;
-  const double* dir;
-  const rtoc_grid* grid;
+  RecView rv;               // kkt: the scalars of RTOC_KKT_SCAL; dir: RTOC_DIR_DTS; steps: [batch][2] max primal / dual step (doubles)
   double* ts;               // [batch][nev] event times
-  double* dt_inst;          // [batch][nstages]
+  double* dt_inst;          // [batch][nstages], written here: the view's dt_inst is for the kernels that read it
   double* t_inst;           // [batch][nstages] grid times (GridInfo::t), or nullptr: not kept
   double* con;              // [batch][RTOC_STO_CON_STRIDE]
   const double* min_dwell;  // [nev + 1]
@@ -45,10 +43,8 @@ struct StoDevArgs {
   double* qtt;              // [batch][nev] out: Hessian diagonal handed to the scatter
   double* err;              // [batch] squared STO KKT term
   double* kkterr;           // [batch] OCPSolver::KKTError() (sqrt), updated in place
-  double* steps;            // [batch][2] max primal / dual step
   const int* active;        // [batch] or nullptr: 0 = the instance has converged and keeps its iterate
-  int nstages, batch, nev;
-  int kkt_stride, scal_off, dir_stride, dts_off;
+  int nev;
   double t0, T, barrier, tau, sto_reg;
 };
 
@@ -67,18 +63,18 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
   // no fused multiply-adds: prev_event_time + (j - prev_event_stage) * dt rounded twice, as the reference's host code rounds it
 #pragma clang fp contract(off)
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
-  const int N = a.nstages - 1;
+  if (b >= a.rv.batch) return;
+  const int N = a.rv.nstages - 1;
   const double* ts = a.ts + (size_t)b * a.nev;
-  double* dt = a.dt_inst + (size_t)b * a.nstages;
-  double* const tg = a.t_inst ? a.t_inst + (size_t)b * a.nstages : nullptr;
+  double* dt = a.dt_inst + (size_t)b * a.rv.nstages;
+  double* const tg = a.t_inst ? a.t_inst + (size_t)b * a.rv.nstages : nullptr;
   int prev_stage = 0, e = 0;
   double prev_t = a.t0;
   for (int i = 0; i < N; ++i) {
-    const int ty = a.grid[i].type, tn = a.grid[i + 1].type;
+    const int ty = a.rv.grid[i].type, tn = a.rv.grid[i + 1].type;
     if (ty == RTOC_GRID_IMPACT) {
       const double te = e < a.nev ? ts[e] : prev_t;
-      const double d = (te - prev_t) / (double)a.grid[i - 1].num_grids_in_phase;
+      const double d = (te - prev_t) / (double)a.rv.grid[i - 1].num_grids_in_phase;
       for (int j = prev_stage; j <= i - 1; ++j) dt[j] = d;
       if (tg) {
         for (int j = prev_stage; j <= i - 1; ++j) tg[j] = prev_t + (j - prev_stage) * d;
@@ -91,7 +87,7 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
       ++i;  // (:197: the grid point after an impact is not examined)
     } else if (tn == RTOC_GRID_LIFT) {
       const double te = e < a.nev ? ts[e] : prev_t;
-      const double d = (te - prev_t) / (double)a.grid[i].num_grids_in_phase;
+      const double d = (te - prev_t) / (double)a.rv.grid[i].num_grids_in_phase;
       for (int j = prev_stage; j <= i; ++j) dt[j] = d;
       if (tg)
         for (int j = prev_stage; j <= i; ++j) tg[j] = prev_t + (j - prev_stage) * d;
@@ -99,7 +95,7 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
       prev_stage = i + 1;
       ++e;
     } else if (tn == RTOC_GRID_TERMINAL) {
-      const double d = (a.t0 + a.T - prev_t) / (double)a.grid[i].num_grids_in_phase;
+      const double d = (a.t0 + a.T - prev_t) / (double)a.rv.grid[i].num_grids_in_phase;
       for (int j = prev_stage; j <= i; ++j) dt[j] = d;
       if (tg)
         for (int j = prev_stage; j <= i; ++j) tg[j] = prev_t + (j - prev_stage) * d;
@@ -112,7 +108,7 @@ static __global__ void sto_time_steps_kernel(StoDevArgs a) {
 // SwitchingTimeOptimization::initConstraints -> STOConstraints::setSlackAndDual (sto_constraints.cpp:148-172)
 static __global__ void sto_init_kernel(StoDevArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.rv.batch) return;
   constexpr int NP = RTOC_STO_MAX_EVENTS + 1;
   double dwell[NP];
   sto_dwell_times(a, a.ts + (size_t)b * a.nev, dwell);
@@ -132,9 +128,9 @@ static __global__ void sto_init_kernel(StoDevArgs a) {
 // OCPSolver::KKTError() = sqrt(dms kkt_error + sto kkt_error) (ocp_solver.cpp:429-431) in place of the dms-only value.
 static __global__ void sto_eval_kkt_dev_kernel(StoDevArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.rv.batch) return;
   constexpr int NP = RTOC_STO_MAX_EVENTS + 1, MAXP = NP + 1;
-  const int N = a.nstages - 1, nev = a.nev;
+  const int N = a.rv.nstages - 1, nev = a.nev;
   double dwell[NP], lt[NP], qtt[NP];
   sto_dwell_times(a, a.ts + (size_t)b * nev, dwell);
   double* c = a.con + (size_t)b * RTOC_STO_CON_STRIDE;
@@ -161,12 +157,13 @@ static __global__ void sto_eval_kkt_dev_kernel(StoDevArgs a) {
     qtt[e] += dos[e] + dos[e + 1];     // diag(J^T diag(dual / slack) J)
   }
   // scatter (:105-118)
-  double* k = a.kkt + (size_t)b * a.nstages * a.kkt_stride + a.scal_off;
+  double* k = a.rv.kkt_at((size_t)b * a.rv.nstages) + a.rv.kkt_off(RTOC_KKT_SCAL);
+  const int kkt_stride = a.rv.L.kkt.stride;
   int ev = 0;
   for (int i = 0; i < N && ev < nev; ++i) {
-    const int ty = a.grid[i].type;
+    const int ty = a.rv.grid[i].type;
     if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) {
-      double* sc = k + (size_t)(ty == RTOC_GRID_IMPACT ? i + 1 : i) * a.kkt_stride;
+      double* sc = k + (size_t)(ty == RTOC_GRID_IMPACT ? i + 1 : i) * kkt_stride;
       sc[RTOC_KKT_SCAL_H] -= lt[ev];
       sc[RTOC_KKT_SCAL_QTT] += qtt[ev];
       ++ev;
@@ -179,14 +176,14 @@ static __global__ void sto_eval_kkt_dev_kernel(StoDevArgs a) {
   for (int p = 0; p < MAXP; ++p) h[p] = 0.0;
   int phase = 0;
   for (int i = 0; i < N; ++i) {
-    const int ty = a.grid[i].type;
+    const int ty = a.rv.grid[i].type;
     if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) ++phase;
-    if (phase < MAXP) h[phase] += k[(size_t)i * a.kkt_stride + RTOC_KKT_SCAL_H];
+    if (phase < MAXP) h[phase] += k[(size_t)i * kkt_stride + RTOC_KKT_SCAL_H];
   }
   int e2 = 0;
   for (int i = 0; i < N; ++i) {
-    const rtoc_grid g = a.grid[i];
-    if ((g.type == RTOC_GRID_IMPACT && a.grid[i + 1].sto) || (g.type == RTOC_GRID_LIFT && g.sto)) {
+    const rtoc_grid g = a.rv.grid[i];
+    if ((g.type == RTOC_GRID_IMPACT && a.rv.grid[i + 1].sto) || (g.type == RTOC_GRID_LIFT && g.sto)) {
       if (e2 + 1 < MAXP) {
         const double hd = h[e2] - h[e2 + 1];
         err += hd * hd;
@@ -205,15 +202,16 @@ static __global__ void sto_eval_kkt_dev_kernel(StoDevArgs a) {
 // expandSlackAndDual, fraction-to-boundary, min-ed into the step sizes the stages left in RTOC_BUF_STEP (ocp_solver.cpp:129-132)
 static __global__ void sto_step_sizes_kernel(StoDevArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.rv.batch) return;
   constexpr int NP = RTOC_STO_MAX_EVENTS + 1;
-  const int N = a.nstages - 1, nev = a.nev;
+  const int N = a.rv.nstages - 1, nev = a.nev;
   double dts[NP];
   int ev = 0;
-  const double* d = a.dir + (size_t)b * a.nstages * a.dir_stride + a.dts_off;
+  const double* d = a.rv.dir_at((size_t)b * a.rv.nstages) + a.rv.dir_off(RTOC_DIR_DTS);
+  const int dir_stride = a.rv.L.dir.stride;
   for (int i = 0; i < N && ev < nev; ++i) {
-    const int ty = a.grid[i].type;
-    if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) dts[ev++] = d[(size_t)i * a.dir_stride];
+    const int ty = a.rv.grid[i].type;
+    if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) dts[ev++] = d[(size_t)i * dir_stride];
   }
   double* c = a.con + (size_t)b * RTOC_STO_CON_STRIDE;
   double ps = 1.0, ds = 1.0;
@@ -231,7 +229,7 @@ static __global__ void sto_step_sizes_kernel(StoDevArgs a) {
     if (fs > 0.0 && fs < 1.0 && fs < ps) ps = fs;
     if (fd > 0.0 && fd < 1.0 && fd < ds) ds = fd;
   }
-  double* st = a.steps + 2 * (size_t)b;
+  double* st = reinterpret_cast<double*>(a.rv.steps) + 2 * (size_t)b;
   if (ps < st[0]) st[0] = ps;
   if (ds < st[1]) st[1] = ds;
 }
@@ -239,17 +237,19 @@ static __global__ void sto_step_sizes_kernel(StoDevArgs a) {
 // SwitchingTimeOptimization::integrateSolution (:181-206): ts += primal step x dts, slack / dual updates
 static __global__ void sto_integrate_kernel(StoDevArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
+  if (b >= a.rv.batch) return;
   constexpr int NP = RTOC_STO_MAX_EVENTS + 1;
-  const int N = a.nstages - 1, nev = a.nev;
-  const double ps = a.steps[2 * (size_t)b], ds = a.steps[2 * (size_t)b + 1];
-  const double* d = a.dir + (size_t)b * a.nstages * a.dir_stride + a.dts_off;
+  const int N = a.rv.nstages - 1, nev = a.nev;
+  const double* st = reinterpret_cast<const double*>(a.rv.steps) + 2 * (size_t)b;
+  const double ps = st[0], ds = st[1];
+  const double* d = a.rv.dir_at((size_t)b * a.rv.nstages) + a.rv.dir_off(RTOC_DIR_DTS);
+  const int dir_stride = a.rv.L.dir.stride;
   double* ts = a.ts + (size_t)b * nev;
   int ev = 0;
   for (int i = 0; i < N && ev < nev; ++i) {
-    const int ty = a.grid[i].type;
+    const int ty = a.rv.grid[i].type;
     if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) {
-      ts[ev] += ps * d[(size_t)i * a.dir_stride];
+      ts[ev] += ps * d[(size_t)i * dir_stride];
       ++ev;
     }
   }
@@ -265,24 +265,24 @@ static __global__ void sto_integrate_kernel(StoDevArgs a) {
 // point after an impact / the lift grid point, then the STO term of the KKT error (squared differences of the per-phase
 // Hamiltonian sums across STO-enabled events).  One thread per instance: O(#grid points) scalar work.
 struct StoArgs {
-  double* kkt;
-  const rtoc_grid* grid;
+  RecView rv;
   const double* lt;    // [batch][nev]
   const double* qtt;   // [batch][nev]
   double* err;         // [batch] squared STO KKT error
-  int nstages, batch, nev, stride, scal_off;
+  int nev;
 };
 
 static __global__ void sto_eval_kkt_kernel(StoArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.batch) return;
-  const int N = a.nstages - 1;
-  double* k = a.kkt + (size_t)b * a.nstages * a.stride + a.scal_off;
+  if (b >= a.rv.batch) return;
+  const int N = a.rv.nstages - 1;
+  double* k = a.rv.kkt_at((size_t)b * a.rv.nstages) + a.rv.kkt_off(RTOC_KKT_SCAL);
+  const int kkt_stride = a.rv.L.kkt.stride;
   int ev = 0;
   for (int i = 0; i < N && ev < a.nev; ++i) {
-    const int ty = a.grid[i].type;
+    const int ty = a.rv.grid[i].type;
     if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) {
-      double* sc = k + (size_t)(ty == RTOC_GRID_IMPACT ? i + 1 : i) * a.stride;
+      double* sc = k + (size_t)(ty == RTOC_GRID_IMPACT ? i + 1 : i) * kkt_stride;
       sc[RTOC_KKT_SCAL_H] -= a.lt[(size_t)b * a.nev + ev];
       sc[RTOC_KKT_SCAL_QTT] += a.qtt[(size_t)b * a.nev + ev];
       ++ev;
@@ -295,15 +295,15 @@ static __global__ void sto_eval_kkt_kernel(StoArgs a) {
   for (int p = 0; p < MAXP; ++p) h[p] = 0.0;
   int phase = 0;
   for (int i = 0; i < N; ++i) {
-    const int ty = a.grid[i].type;
+    const int ty = a.rv.grid[i].type;
     if (ty == RTOC_GRID_IMPACT || ty == RTOC_GRID_LIFT) ++phase;
-    if (phase < MAXP) h[phase] += k[(size_t)i * a.stride + RTOC_KKT_SCAL_H];
+    if (phase < MAXP) h[phase] += k[(size_t)i * kkt_stride + RTOC_KKT_SCAL_H];
   }
   double err = 0.0;
   int e2 = 0;
   for (int i = 0; i < N; ++i) {
-    const rtoc_grid g = a.grid[i];
-    if ((g.type == RTOC_GRID_IMPACT && a.grid[i + 1].sto) || (g.type == RTOC_GRID_LIFT && g.sto)) {
+    const rtoc_grid g = a.rv.grid[i];
+    if ((g.type == RTOC_GRID_IMPACT && a.rv.grid[i + 1].sto) || (g.type == RTOC_GRID_LIFT && g.sto)) {
       if (e2 + 1 < MAXP) {
         const double hd = h[e2] - h[e2 + 1];
         err += hd * hd;
