@@ -70,8 +70,47 @@ int rtoc_robot_model_plan(const rtoc_robot_model* model, int forced_dofs_per_pas
 /* Per grid point: bit k of active[i] = contact k is active (ContactStatus::isContactActive; on impact grids:
  * ImpactStatus::isImpactActive), positions[i][k][0..2] = ContactStatus::contactPosition(k) (world frame; NULL: zeros),
  * rotations[i][k][0..8] = ContactStatus::contactRotation(k) (row-major; only read for surface contacts; NULL: identity).
- * The rows of the active contacts (3 per point, 6 per surface contact) must add up to the grid's dimf. */
+ * The rows of the active contacts (3 per point, 6 per surface contact) must add up to the grid's dimf.
+ * The placements given here are SHARED by the batch, and a per-instance table ends with this call; every instance on its own
+ * footholds: see rtoc_set_contact_placements / rtoc_hold_contact_placements below. */
 int rtoc_set_contact_schedule(rtoc_ctx* ctx, const unsigned* active, const double* positions, const double* rotations);
+
+/* ---- contact placements of every instance: each OCP of a batch on its own footholds ----
+ * rtoc_set_contact_placements replaces the placements of the schedule in force and keeps its `active` masks.
+ * per_instance = 0: positions[nstages][ncontacts][3], rotations[nstages][ncontacts][9], as for rtoc_set_contact_schedule;
+ * per_instance = 1: the same with a leading [batch].  rotations = NULL: identity; positions = NULL: zeros.  Every kernel that reads
+ * a placement (the Baumgarte rows of rtoc_linearize_contact_dynamics, the switching constraint's impact grid two points ahead, the
+ * cone rows in the contact surface's frame; hence rtoc_contact_eval_kkt, rtoc_contact_eval_ocp and the trial evaluations of the
+ * line searches) reads the table of its own instance.  Entries of INACTIVE contacts are never read, on the host or on the device
+ * (INACTIVE ENTRIES below).  A refused call launches nothing and leaves the table in force: RTOC_ERR_NOT_READY without
+ * rtoc_set_robot_model or before a rtoc_set_contact_schedule that belongs to the grid in force (rtoc_set_grid with another grid
+ * invalidates the placements with the schedule); RTOC_ERR_BAD_ARG for a non-finite entry of an ACTIVE contact at its grid point,
+ * for per_instance outside {0, 1}, for a model without contacts and on a ParNMPC horizon.  rtoc_clone copies the table and its
+ * mode; rtoc_set_robot_model ends a per-instance table (it is sized by batch * max_stages * the model's contacts).
+ * Not per instance: the `active` masks (the grid's dimf is shared structure), friction coefficients and wrench-cone sizes.
+ *
+ * rtoc_contact_frame_placements: Robot::updateFrameKinematics + frameRotation / framePosition / CoM of every instance on the
+ * device -- world rotation (row-major) and position of every contact frame of the model and the centre of mass, at the q of
+ * rtoc_set_initial_state (source = 0; grid_point ignored) or at q of grid point `grid_point` of RTOC_BUF_SOL (source = 1).
+ * host_R[count][ncontacts][9], host_p[count][ncontacts][3], host_com[count][3], count <= batch; any of them may be NULL.
+ *
+ * rtoc_hold_contact_placements: the same kinematics, but the result never leaves the device -- for every instance the placements
+ * of the contacts in the bit mask `contacts` are written into grid points [first, last) of the per-instance table: what the
+ * reference's foot-step planners do with the feet on the ground (src/mpc/trot_foot_step_planner.cpp:94-98, :138-141), for a batch.
+ * A shared table becomes per instance first, every instance starting from the shared values.  Rotations are written for surface
+ * contacts only, into the rotation table if there is one; if there is none and the mask holds a surface contact, one is created,
+ * identity elsewhere.  An empty mask holds nothing.  RTOC_ERR_BAD_ARG: an empty or out-of-range [first, last), mask bits at or
+ * beyond ncontacts, source outside {0, 1}, grid_point outside the grid (source = 1), a ParNMPC horizon; RTOC_ERR_NOT_READY without
+ * the model, the schedule of the grid in force, or the source (no initial state / no RTOC_BUF_SOL).
+ *
+ * rtoc_get_contact_placements: the table as the instances read it -- host_positions[count][nstages][ncontacts][3],
+ * host_rotations[count][nstages][ncontacts][9], count <= batch (a shared table repeated, zeros / identities where none was set;
+ * either may be NULL) and *per_instance (may be NULL) = the mode in force. */
+int rtoc_get_contact_placements(rtoc_ctx* ctx, double* host_positions, double* host_rotations, int count, int* per_instance);
+int rtoc_set_contact_placements(rtoc_ctx* ctx, const double* positions, const double* rotations, int per_instance);
+int rtoc_contact_frame_placements(rtoc_ctx* ctx, int source, int grid_point, double* host_R, double* host_p, double* host_com,
+                                  int count);
+int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int first, int last, unsigned contacts);
 
 /* linearizeContactDynamics (src/dynamics/contact_dynamics.cpp:12-33) on intermediate / lift grids and
  * linearizeImpactDynamics (src/dynamics/impact_dynamics.cpp:12-27) on impact grids, for every (instance, grid point)

@@ -42,6 +42,7 @@ EXPORTS = [
     "rtoc_parnmpc_get_aux_mat", "rtoc_parnmpc_eval_kkt", "rtoc_parnmpc_backward_correction", "rtoc_parnmpc_update_solution",
     "rtoc_solution_store", "rtoc_solution_interpolate", "rtoc_solution_stored", "rtoc_solution_forget",
     "rtoc_control_policy", "rtoc_control_input",
+    "rtoc_set_contact_placements", "rtoc_contact_frame_placements", "rtoc_hold_contact_placements", "rtoc_get_contact_placements",
 ]
 
 
@@ -199,6 +200,10 @@ def lib():
         L.rtoc_solution_forget.argtypes = [vp]
         L.rtoc_control_policy.argtypes = [vp, C.c_double, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]
         L.rtoc_control_input.argtypes = [vp, C.c_double, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]
+        L.rtoc_set_contact_placements.argtypes = [vp, dp, dp, C.c_int]
+        L.rtoc_contact_frame_placements.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.c_int]
+        L.rtoc_hold_contact_placements.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]
+        L.rtoc_get_contact_placements.argtypes = [vp, dp, dp, C.c_int, C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -596,6 +601,56 @@ class Context:
             rot = np.ascontiguousarray(rotations, dtype=np.float64).reshape(self.nstages, self._model_ncontacts, 9)
         _chk(lib().rtoc_set_contact_schedule(self._h, act.ctypes.data_as(C.POINTER(C.c_uint)), _dp(pos) if pos is not None else None,
                                              _dp(rot) if rot is not None else None))
+
+    def set_contact_placements(self, positions, rotations=None):
+        """rtoc_set_contact_placements: the placements of the schedule in force, its masks kept -- positions [nstages, ncontacts, 3]
+        shared by the batch or [batch, nstages, ncontacts, 3] (every instance its own footholds: the leading dimension decides) or
+        None (zeros), rotations with the same leading shape and [..., 3, 3] or [..., 9] (row-major) or None (identity)"""
+        n, nc = self.nstages, self._model_ncontacts
+        pos = rot = None
+        lead = None
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.float64)
+            if pos.shape not in ((n, nc, 3), (self.batch, n, nc, 3)):
+                raise ValueError("positions must be [%d, %d, 3] or [%d, %d, %d, 3], not %s" % (n, nc, self.batch, n, nc, pos.shape))
+            lead = pos.shape[:-3]
+        if rotations is not None:
+            rot = np.ascontiguousarray(rotations, dtype=np.float64)
+            if rot.shape[-2:] == (3, 3):
+                rot = rot.reshape(rot.shape[:-2] + (9,))
+            if rot.shape not in ((n, nc, 9), (self.batch, n, nc, 9)):
+                raise ValueError("rotations must be [%d, %d, 3, 3] or [%d, %d, %d, 3, 3], not %s" % (n, nc, self.batch, n, nc, rot.shape))
+            if lead is not None and rot.shape[:-3] != lead:
+                raise ValueError("positions and rotations must both be shared or both per instance")
+            lead = rot.shape[:-3]
+        _chk(lib().rtoc_set_contact_placements(self._h, _dp(pos) if pos is not None else None, _dp(rot) if rot is not None else None,
+                                               1 if lead else 0))
+
+    def contact_placements(self):
+        """rtoc_get_contact_placements: (positions [batch, nstages, ncontacts, 3], rotations [batch, nstages, ncontacts, 3, 3],
+        per_instance) -- the table as the instances read it (a shared one repeated; zeros / identities where none was set)"""
+        n, nc = self.nstages, self._model_ncontacts
+        pos, rot, inst = np.zeros((self.batch, n, nc, 3)), np.zeros((self.batch, n, nc, 9)), C.c_int(0)
+        _chk(lib().rtoc_get_contact_placements(self._h, _dp(pos), _dp(rot), self.batch, C.byref(inst)))
+        return pos, rot.reshape(self.batch, n, nc, 3, 3), bool(inst.value)
+
+    _PLACEMENT_SOURCES = {"x0": 0, "sol": 1}
+
+    def contact_frame_placements(self, source="x0", grid_point=0):
+        """rtoc_contact_frame_placements: (R [batch, ncontacts, 3, 3], p [batch, ncontacts, 3], com [batch, 3]) -- world rotation
+        and position of every contact frame and the centre of mass of every instance, at the q of set_initial_state (source "x0")
+        or at q of grid point `grid_point` of BUF_SOL (source "sol")"""
+        nc = self._model_ncontacts
+        R, p, com = np.zeros((self.batch, nc, 9)), np.zeros((self.batch, nc, 3)), np.zeros((self.batch, 3))
+        _chk(lib().rtoc_contact_frame_placements(self._h, self._PLACEMENT_SOURCES[source], int(grid_point), _dp(R), _dp(p), _dp(com), self.batch))
+        return R.reshape(self.batch, nc, 3, 3), p, com
+
+    def hold_contact_placements(self, contacts, first=0, last=None, source="x0", grid_point=0):
+        """rtoc_hold_contact_placements: on the device, write where the contact frames in the bit mask `contacts` are now (at the q
+        of `source`, as for contact_frame_placements) into grid points [first, last) of every instance's own placement table (last =
+        None: to the end of the grid).  A shared table becomes per instance, every instance starting from the shared values."""
+        _chk(lib().rtoc_hold_contact_placements(self._h, self._PLACEMENT_SOURCES[source], int(grid_point), int(first),
+                                                self.nstages if last is None else int(last), int(contacts)))
 
     def set_configuration_cost(self, q_ref, v_ref, u_ref, q_weight, v_weight, a_weight, u_weight, q_weight_terminal, v_weight_terminal,
                                q_weight_impact=None, v_weight_impact=None, dv_weight_impact=None):

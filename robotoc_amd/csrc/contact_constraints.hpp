@@ -111,7 +111,7 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
         const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
         M3 Rs;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
+        for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[a.rv.placement(b, st, ncon, c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
         const double m = a.mu[c] * 0.70710678118654752440;
         // rows of cone_local = cone_world R_surface^T: row r = R_surface * (row r of cone_world)
         V3 row[5];
@@ -224,7 +224,7 @@ static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) 
     const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
     M3 Rs;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
+    for (int e = 0; e < 9; ++e) Rs.m[e] = a.rv.rotations ? a.rv.rotations[a.rv.placement(b, st, ncon, c) * 9 + e] : ((e % 4 == 0) ? 1.0 : 0.0);
     const double m = a.mu[c] * 0.70710678118654752440;
     V3 row[5];
     row[0] = rbd::mul(Rs, rbd::mk(0, 0, -1));

@@ -37,13 +37,22 @@ struct RecView {
   unsigned long long* steps;  // RTOC_BUF_STEP: [batch][2] bit patterns
   const rtoc_grid* grid;
   const unsigned* active;     // [nstages] contact schedule
-  const double* positions;    // [nstages][ncontacts][3] or nullptr
-  const double* rotations;    // [nstages][ncontacts][9] or nullptr (surface contacts: desired rotation)
+  // the desired contact placements (rtoc_set_contact_schedule: shared by the batch; rtoc_set_contact_placements /
+  // rtoc_hold_contact_placements: every instance its own), one row per (grid point, contact): read through placement() alone
+  const double* positions;    // [nstages][ncontacts][3] or [batch][nstages][ncontacts][3] or nullptr (zeros)
+  const double* rotations;    // the same with [9] (row-major; surface contacts: desired rotation) or nullptr (identity)
   const double* dt_inst;      // per-instance time steps or nullptr (grid_dt)
   const rbd::DevModel* model;
   int nstages, batch;
   int all_stages;             // 1: the records are the stages of a ParNMPC horizon (rtoc_parnmpc_set_horizon), none of them terminal
+  int placement_stride;       // grid points between the placement tables of two instances: nstages, or 0 for a table the batch shares
   rtoc_layout L;
+
+  // row of `positions` (x 3 doubles) and of `rotations` (x 9) that holds the placement of contact c at grid point st of instance b.
+  // A shared table is the per-instance one with a stride of zero: one multiply-add, no branch
+  RTOC_HD size_t placement(int b, int st, int ncontacts, int c) const {
+    return ((size_t)b * (size_t)placement_stride + (size_t)st) * (size_t)ncontacts + (size_t)c;
+  }
 
   // records per instance that carry dynamics and constraint rows: all but the terminal one, or every stage of a ParNMPC horizon
   RTOC_HD int nlin() const { return nstages - 1 + all_stages; }

@@ -209,7 +209,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
           const SV af = act_inv(Rf, pf, acc);
           const double kp = cm[12], kd = cm[13];
           const V3 pw = op + mul(oR, pf);
-          const V3 pr = a.rv.positions ? ldv3(a.rv.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
+          const V3 pr = a.rv.positions ? ldv3(a.rv.positions + a.rv.placement(b, st, ncon, c) * 3) : mk(0, 0, 0);
           if (!surf) {
             C.l = af.l + cross(vf.a, vf.l) + kd * vf.l + kp * (pw - pr);
           } else {
@@ -217,7 +217,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
-              for (int cc = 0; cc < 3; ++cc) Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[((size_t)st * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
+              for (int cc = 0; cc < 3; ++cc) Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[a.rv.placement(b, st, ncon, c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
             SV lg, dlg;
             log6_fwd(mul(Rdt, mul(oR, Rf)), mul(Rdt, pw - pr), sv0(), lg, dlg);
             C = SV{af.l + kd * vf.l + kp * lg.l, af.a + kd * vf.a + kp * lg.a};
@@ -545,7 +545,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
                 const double kp = scm[c * CP + 12], kd = scm[c * CP + 13];
                 const M3 oRf = mul(oR, Rf);
                 const V3 pw = op + mul(oR, pf);
-                const V3 pr = a.rv.positions ? ldv3(a.rv.positions + ((size_t)st * ncon + c) * 3) : mk(0, 0, 0);
+                const V3 pr = a.rv.positions ? ldv3(a.rv.positions + a.rv.placement(b, st, ncon, c) * 3) : mk(0, 0, 0);
                 // the frame Jacobian column of dof j is the v-tangent of vf, one lane up (kind 0 lanes only use it)
                 const SV jc = SV{mk(__shfl_down(dvf.l.x, 1, 64), __shfl_down(dvf.l.y, 1, 64), __shfl_down(dvf.l.z, 1, 64)),
                                  mk(__shfl_down(dvf.a.x, 1, 64), __shfl_down(dvf.a.y, 1, 64), __shfl_down(dvf.a.z, 1, 64))};
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
                   // spatial acceleration + kd v + kp Log6(X_desired^-1 X_frame)   (surface_contact.hxx:12-29, :31-68)
                   M3 Rd;
                   if (a.rv.rotations) {
-                    Rd = ldm3(a.rv.rotations + ((size_t)st * ncon + c) * 9);
+                    Rd = ldm3(a.rv.rotations + a.rv.placement(b, st, ncon, c) * 9);
                   } else {
 #pragma unroll
                     for (int e = 0; e < 9; ++e) Rd.m[e] = (e % 4 == 0) ? 1.0 : 0.0;

@@ -115,6 +115,7 @@ struct CtxOptions {
   double barrier = 0.0, ftb_rule = 0.0;
   int n_mu = 0;                 // how many of d_mu's RTOC_MAX_CONTACTS entries the caller set
   bool has_cpos = false, has_crot = false;
+  int cplace_inst = 0;          // 1: d_cpos / d_crot hold a table per instance (rtoc_set_contact_placements, rtoc_hold_contact_placements)
   // filter line search on the device (rtoc_set_line_search, rtoc_contact_line_search)
   int ls_on = 0;
   double ls_rate = 0.0, ls_min_step = 0.0, ls_cost_rate = 0.0, ls_viol_rate = 0.0;
@@ -171,6 +172,9 @@ struct ModelState {
   std::unique_ptr<rbd::DevModel> h_model;
   DevBuf<unsigned> d_active;
   bool active_current = false;  // the schedule was set since the last rtoc_set_grid: its masks belong to the grid in force
+  std::vector<unsigned> h_active;  // host copy of the masks (which placements rtoc_set_contact_placements checks)
+  // desired contact placements: [max_stages][RTOC_MAX_CONTACTS][3 | 9] shared by the batch, or [batch] of them (cplace_inst);
+  // in use [nstages][ncontacts][3 | 9] or [batch][nstages][ncontacts][3 | 9], dense
   DevBuf<double> d_cpos;
   DevBuf<double> d_crot;
   DevBuf<double> d_cost;      // rtoc_set_configuration_cost: 12 (nv + 1) doubles
@@ -190,6 +194,7 @@ struct ModelState {
     }
     dup(d_active, src.d_active);
     active_current = src.active_current;
+    h_active = src.h_active;
     dup(d_cpos, src.d_cpos);
     dup(d_crot, src.d_crot);
     dup(d_cost, src.d_cost);
@@ -205,6 +210,7 @@ struct ModelState {
   DevBuf<double> d_costval;      // [batch][max_stages] cost values of the last rtoc_contact_eval_kkt (rtoc_contact_eval_ocp)
   DevBuf<double> d_kkterr;       // [batch] + [batch][max_stages] partial sums
   DevBuf<int> d_nconv;           // instances found converged by the last rtoc_newton_iteration
+  DevBuf<double> d_fk;           // rtoc_contact_frame_placements: [batch][RTOC_MAX_CONTACTS][9 + 3] + [batch][3] ahead of the download
 };
 
 // task-space cost components (rtoc_set_task_costs; task_space_cost.hpp; rt_task_costs.hip)

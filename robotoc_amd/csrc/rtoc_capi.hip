@@ -458,6 +458,7 @@ RecView rtoc::view(const rtoc_ctx* c) {
   v.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
   v.grid = c->d_grid.p, v.active = c->d_active.p;
   v.positions = c->has_cpos ? c->d_cpos.p : nullptr, v.rotations = c->has_crot ? c->d_crot.p : nullptr;
+  v.placement_stride = c->cplace_inst ? c->nstages : 0;
   v.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   v.model = c->d_model.p;
   v.nstages = c->nstages, v.batch = c->batch;

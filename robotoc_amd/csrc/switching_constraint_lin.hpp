@@ -140,7 +140,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
         const V3 pf = rbd::ldv3(&scm[c * CP + 9]);
         const M3 oRf = rbd::mul(oR, Rf);
         const V3 pw = op + rbd::mul(oR, pf);
-        const V3 pr = a.rv.positions ? rbd::ldv3(a.rv.positions + ((size_t)(st + 2) * ncon + c) * 3) : rbd::mk(0, 0, 0);
+        const V3 pr = a.rv.positions ? rbd::ldv3(a.rv.positions + a.rv.placement(b, st + 2, ncon, c) * 3) : rbd::mk(0, 0, 0);
         const SV jf = rbd::act_inv(Rf, pf, Jc);   // this lane's column of the LOCAL frame Jacobian
         double* const Pres = spq + 6 * RTOC_MAX_CONTACTS * 4;
         if (!surf) {
@@ -154,7 +154,7 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
           for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc)
-              Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[((size_t)(st + 2) * ncon + c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
+              Rdt.m[3 * r + cc] = a.rv.rotations ? a.rv.rotations[a.rv.placement(b, st + 2, ncon, c) * 9 + 3 * cc + r] : (r == cc ? 1.0 : 0.0);
           SV lg, dlg;
           rbd::log6_fwd(rbd::mul(Rdt, oRf), rbd::mul(Rdt, pw - pr), jf, lg, dlg);
           const double pv[6] = {lg.l.x, lg.l.y, lg.l.z, lg.a.x, lg.a.y, lg.a.z}, dv6[6] = {dlg.l.x, dlg.l.y, dlg.l.z, dlg.a.x, dlg.a.y, dlg.a.z};

@@ -66,6 +66,17 @@ class ConfigurationCostSource : public StageDataSource {
     config_ref_ = ref;
     config_ref_dirty_ = true;
   }
+  // Every instance of the context's batch on its own footholds (rtoc_set_contact_placements, per_instance = 1), in place of the
+  // placements the batch shares: positions [batch][grid point][contact][3], rotations the same with [9] (row-major) or empty
+  // (identity), for the grid in force; the contact masks stay those of the schedule.  batch = 0: back to the shared placements.
+  // A source that owns its discretisation forgets them at the next discretize(): they belong to the grid they were given for.
+  void setContactPlacements(const std::vector<double>& positions, const std::vector<double>& rotations, const int batch) {
+    const size_t rows = static_cast<size_t>(batch < 0 ? 0 : batch) * td_.size() * static_cast<size_t>(model_.ncontacts);
+    if (batch < 0 || positions.size() != rows * 3 || (!rotations.empty() && rotations.size() != rows * 9))
+      throw std::invalid_argument("[ConfigurationCostSource] per-instance placements: batch x grid points x ncontacts positions (x 3) and rotations (x 9) or none");
+    cpos_inst_ = positions, crot_inst_ = rotations, batch_inst_ = batch;
+    scheduled_ = false;
+  }
   ContactSequence* contactSequence() override { return cs_.get(); }
   const STOConstraints* stoConstraints() const override { return sto_.get(); }
   double horizonLength() const override { return T_; }
@@ -78,6 +89,7 @@ class ConfigurationCostSource : public StageDataSource {
     if (!cs_) return false;
     td_ = robotoc::discretize(*cs_, T_, N_, t, static_cast<bool>(sto_));
     contactSchedule(*cs_, td_, active_, cpos_, &crot_);
+    cpos_inst_.clear(), crot_inst_.clear(), batch_inst_ = 0;
     scheduled_ = false;
     return true;
   }
@@ -199,6 +211,8 @@ class ConfigurationCostSource : public StageDataSource {
   void schedule(rtoc_ctx* ctx) {
     if (scheduled_) return;  // needs the grid, which the solver sets after configure()
     chk(rtoc_set_contact_schedule(ctx, active_.data(), cpos_.data(), crot_.empty() ? nullptr : crot_.data()), "rtoc_set_contact_schedule");
+    if (batch_inst_ > 0)   // the masks above, the placements of every instance here
+      chk(rtoc_set_contact_placements(ctx, cpos_inst_.data(), crot_inst_.empty() ? nullptr : crot_inst_.data(), 1), "rtoc_set_contact_placements");
     scheduled_ = true;
   }
   static void chk(const int rc, const char* what) {
@@ -210,6 +224,8 @@ class ConfigurationCostSource : public StageDataSource {
   std::vector<unsigned> active_;
   std::vector<double> cpos_;
   std::vector<double> crot_;   // [grid point][contact][9] or empty (surface contacts: ContactSequence rotations)
+  std::vector<double> cpos_inst_, crot_inst_;   // setContactPlacements: the same with a leading [batch_inst_]; batch_inst_ = 0: none
+  int batch_inst_ = 0;
   Solution s0_;
   std::vector<rtoc_task_cost> tasks_;
   std::vector<std::shared_ptr<TaskCostComponent>> task_costs_;

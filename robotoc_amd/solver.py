@@ -79,6 +79,45 @@ class ContactPlan:
         return out
 
 
+def placement_tables(plan, grids, ncontacts, batch):
+    """The contact placements of a plan per GRID POINT, as the device takes them: (positions, rotations or None, per_instance).
+    A plan whose phase_positions[p] are [ncontacts, 3] (phase_rotations[p] [ncontacts, 3, 3]) is shared by the batch and gives
+    [nstages, ncontacts, 3] ([nstages, ncontacts, 3, 3]); one whose entries are [batch, ncontacts, 3] ([batch, ncontacts, 3, 3])
+    puts every instance on its own footholds and gives the same with a leading [batch].  A plan that mixes the two raises
+    ValueError.  Phases advance at lift and impact grid points."""
+    if ncontacts == 0:   # nothing to place
+        return np.zeros((len(grids), 0, 3)), None, False
+
+    def shapes(entries, tail):
+        lead = set()
+        for e in entries:
+            s = np.shape(e)
+            if s == (ncontacts,) + tail:
+                lead.add(False)
+            elif s == (batch, ncontacts) + tail:
+                lead.add(True)
+            else:
+                raise ValueError("a phase's placements must be %s or %s, not %s" % ((ncontacts,) + tail, (batch, ncontacts) + tail, s))
+        return lead
+    lead = shapes(plan.phase_positions, (3,))
+    if plan.phase_rotations is not None:
+        lead |= shapes(plan.phase_rotations, (3, 3))
+    if len(lead) > 1:
+        raise ValueError("a ContactPlan is shared by the batch or per instance: its phases mix [ncontacts, ...] and [batch, ncontacts, ...]")
+    per_instance = bool(lead and lead.pop())
+
+    def table(entries, tail):
+        out, phase = np.zeros((len(grids), batch if per_instance else 1, ncontacts) + tail), 0
+        for i, g in enumerate(grids):
+            if g.type in (GRID_IMPACT, GRID_LIFT):
+                phase += 1
+            out[i] = entries[min(phase, len(entries) - 1)]
+        return np.ascontiguousarray(out.swapaxes(0, 1)) if per_instance else out[:, 0]
+    pos = table(plan.phase_positions, (3,))
+    rot = table(plan.phase_rotations, (3, 3)) if plan.phase_rotations is not None else None
+    return pos, rot, per_instance
+
+
 @dataclass
 class STOConstraints:
     """src/sto/sto_constraints.cpp:12-59"""
@@ -275,19 +314,13 @@ class OCPSolver:
                 self.configuration_ref, self.model, grid_infos(times, [g.dt for g in grids], structure), self.cost.get("q_weight"),
                 self.cost.get("q_weight_terminal"), np.zeros(self.model.nv) if wqi is None else wqi))
         self.masks = contact_masks(grids, self.plan.phase_masks, self.plan.impact_masks())
-        pos, phase = np.zeros((len(grids), self.nc, 3)), 0
-        for i, g in enumerate(grids):
-            if g.type in (GRID_IMPACT, GRID_LIFT):
-                phase += 1
-            pos[i] = self.plan.phase_positions[min(phase, len(self.plan.phase_positions) - 1)]
-        rot = None
-        if self.plan.phase_rotations is not None:
-            rot, phase = np.zeros((len(grids), self.nc, 3, 3)), 0
-            for i, g in enumerate(grids):
-                if g.type in (GRID_IMPACT, GRID_LIFT):
-                    phase += 1
-                rot[i] = self.plan.phase_rotations[min(phase, len(self.plan.phase_rotations) - 1)]
-        c.set_contact_schedule(self.masks, pos, rot)
+        pos, rot, per_instance = placement_tables(self.plan, grids, self.nc, self.batch)
+        if per_instance:
+            # every instance on its own footholds: the schedule's masks first, then the placements of the batch
+            c.set_contact_schedule(self.masks)
+            c.set_contact_placements(pos, rot)
+        else:
+            c.set_contact_schedule(self.masks, pos, rot)
         if self.sto is not None and len(self.plan.events) > 0:
             c.sto_set_problem(self.t0, self.T, self.event_times, self.sto.minimum_dwell_times, self.sto.barrier_param,
                               self.sto.fraction_to_boundary_rule)
