@@ -112,6 +112,117 @@ int rtoc_contact_frame_placements(rtoc_ctx* ctx, int source, int grid_point, dou
                                   int count);
 int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int first, int last, unsigned contacts);
 
+/* ---- TrotFootStepPlanner and the MPC references of every instance on the device ----
+ * What MPCTrot::resetContactPlacements does per control tick (src/mpc/mpc_trot.cpp:357-372) for a batch, each instance with its own
+ * command: TrotFootStepPlanner::plan (src/mpc/trot_foot_step_planner.cpp) with RaibertHeuristic (src/mpc/raibert_heuristic.cpp) and
+ * MovingWindowFilter<2> (include/robotoc/mpc/moving_window_filter.hpp), the placements of every contact phase, and
+ * MPCPeriodicSwingFootRef x 4, MPCPeriodicCoMRef, MPCPeriodicConfigurationRef (src/mpc/mpc_periodic_*_ref.cpp).  The plan, the
+ * placement table and the reference tables are written on the device and stay there.  The gait wrapper itself (addStep, pop_front,
+ * the solve call) stays with the caller: the contact sequence is structure the batch shares.  Not here: the other gaits' planners,
+ * contact surfaces (point contacts have no rotation in the table), grids with switching-time optimisation, ParNMPC horizons (every
+ * entry point below refuses one with RTOC_ERR_BAD_ARG).
+ *
+ * rtoc_set_foot_step_planner: setGaitPattern (mode RTOC_FOOT_STEP_FIXED: step_length, step_yaw, enable_stance_phase) or
+ * setRaibertGaitPattern (RTOC_FOOT_STEP_RAIBERT: vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain; enable_stance_phase is
+ * stance_time > 0 as in :86 and the member is ignored), p[1] for the batch (per_instance = 0) or p[batch].  step_length, step_yaw,
+ * vcom_cmd and yaw_rate_cmd are each instance's own; mode, projection, swing_time, stance_time, gain and enable_stance_phase decide
+ * the step-case sequence, which is shared structure like the grid, and must agree across the instances.  RTOC_ERR_BAD_ARG: they do
+ * not; an unknown mode or projection; enable_stance_phase outside {0, 1}; per_instance outside {0, 1}; in Raibert mode the checks of
+ * the reference's setters (:63-76, raibert_heuristic.cpp:38-47): swing_time <= 0, stance_time < 0, gain <= 0; a model that has not
+ * exactly four contacts, all of them point contacts, in the reference's order LF, LH, RF, RH = contacts 0..3.  RTOC_ERR_NOT_READY
+ * without rtoc_set_robot_model.  p = NULL removes the planner with its state and plan (rtoc_foot_step_planner_init again after the next one is set).  A refused call leaves the planner in force.  Setting a planner keeps
+ * the state of rtoc_foot_step_planner_init (the reference's setters do not touch it either).
+ *
+ * BASE-ROTATION PROJECTION.  rotation::ProjectRotationMatrix(R, Z) of the reference (include/robotoc/utils/rotation.hpp:103-111)
+ * divides R by R00^2 + R01 + R01, not by the norm of the row.  For a pure yaw theta that is cos^2 theta - 2 sin theta: 1 at
+ * theta = 0, zero at sin theta = sqrt(2) - 1 (theta = 0.427 rad), where the planner's rotation and with it the plan become non-finite.  Parity with the
+ * reference is this project's definition of correct: RTOC_PROJECT_AS_REFERENCE (0, the default of a zeroed struct) reproduces that
+ * arithmetic literally; RTOC_PROJECT_YAW is the rotation about z by atan2(R10, R00).  An instance whose plan went non-finite shows
+ * in ok[] of rtoc_foot_step_plan_get; no status bit is raised.
+ *
+ * rtoc_foot_step_planner_init: TrotFootStepPlanner::init(q) (:91-106) of every instance at the q of rtoc_set_initial_state -- the
+ * projected base rotation, com_to_contact_position_local_[4], com_ref_[0], a cleared filter, and a copy of q (the configuration
+ * reference starts from it); current_step_ = 0 is kept once, on the host.  The plan's size is 0 afterwards.
+ *
+ * rtoc_foot_step_plan: plan(t, q, v, contact_status, planning_steps) (:125-284) of every instance from the q, v of
+ * rtoc_set_initial_state as it stands now.  contact_status0: the active contacts of the first phase, 0b1111, 0b1001 (LF + RH) or
+ * 0b0110 (LH + RF) -- the reference returns false otherwise, here RTOC_ERR_BAD_ARG and nothing is launched; planning_steps in
+ * [0, RTOC_MAX_PLAN_STEPS], else RTOC_ERR_BAD_ARG.  The plan has planning_steps + 2 steps: contactPositions(step)[4][3], CoM(step)[3],
+ * R(step)[9] per instance.  Every instance's planner state (R_.front(), the filter) advances; the host's current_step_ advances by
+ * the reference's rules.  RTOC_ERR_NOT_READY without a planner, its init or an initial state.
+ *
+ * rtoc_foot_step_plan_get: the plan of the first count <= batch instances -- positions[count][size][4][3], com[count][size][3],
+ * R[count][size][9] (row-major), step_length[count][3] (the length in force; Raibert mode: what the heuristic planned),
+ * ok[count] (1 iff every number of that instance's plan is finite), *size, *current_step.  Any pointer may be NULL; the arrays must
+ * hold RTOC_MAX_PLAN_STEPS + 2 steps unless the caller knows the size.
+ *
+ * rtoc_foot_step_place: the loop of resetContactPlacements (mpc_trot.cpp:361-365) -- grid point i of instance b gets
+ * contactPositions(phase_of_grid_point[i] + 1) of b's plan, all four contacts, as the reference writes them.  phase_of_grid_point:
+ * GridInfo::phase relative to the first grid point.  The target is the per-instance placement table; a shared one is converted
+ * first, exactly as rtoc_hold_contact_placements does.  RTOC_ERR_BAD_ARG: nstages is not the grid's, a phase outside [0, size - 2];
+ * RTOC_ERR_NOT_READY without a plan or the schedule of the grid in force.
+ *
+ * rtoc_foot_step_refs: the three references at every (instance, grid point), written where the cost kernels read them: the
+ * per-instance forms of the tables of rtoc_set_task_ref_table and rtoc_set_configuration_ref_table (tables that were shared become
+ * per instance).  phase_masks[nphases]: the active contacts of every contact phase (what setSwingFootRef / setCoMRef keep as
+ * is_contact_active_ / has_inactive_contacts_).  Swing foot k (r->foot_term[k] >= 0: the index of its RTOC_TASK_FRAME_3D term):
+ * isActive = t > swing_start_time and the foot is in the air; then cycle = floor((t - start) / (period_swing + period_stance)),
+ * rate = (t - start - cycle period) / period_swing, p = (1 - rate) contactPositions(phase)[k] + rate contactPositions(phase +
+ * num_phases_in_period)[k] with the swing height added (mpc_periodic_swing_foot_ref.cpp:90-110); the reference leaves an inactive
+ * entry as it was, here it is contactPositions(phase)[k] with active = 0.  CoM (r->com_term >= 0, a RTOC_TASK_COM term): the same
+ * blend of CoM(phase) and CoM(phase + num_phases_in_period) where t > swing_start_time and some foot is in the air, else the else
+ * branch of updateRef, CoM(phase), with active = 0 (mpc_periodic_com_ref.cpp:90-110).  Configuration (r->configuration != 0): q of
+ * rtoc_foot_step_planner_init with the quaternion replaced by Quaterniond(R(phase)).slerp(rate, Quaterniond(R(phase +
+ * num_phases_in_period))) under the same condition, else Quaterniond(R(phase)); active everywhere
+ * (mpc_periodic_configuration_ref.cpp:92-115); Eigen's matrix-to-quaternion conversion and Eigen's slerp with its sign flip and
+ * near-parallel branch.  Entries are written whole: R = identity, pad = 0.  Times: rtoc_set_grid_times.
+ * RTOC_ERR_BAD_ARG: nstages is not the grid's; a phase outside [0, nphases) or at or beyond the plan's size; phase +
+ * num_phases_in_period at or beyond the plan's size at a grid point that reads it; a term outside the terms set, named twice, whose
+ * ref_kind is not RTOC_REF_TABLE, or whose kind is not RTOC_TASK_FRAME_3D (a foot) / RTOC_TASK_COM (the CoM) in every instance; nphases outside [1, RTOC_MAX_PLAN_STEPS + 2]; the arguments the reference's constructors refuse (swing_height < 0, period_swing or
+ * period_stance <= 0, a negative period of the CoM or configuration reference, num_phases_in_period < 1); a grid with switching-time
+ * optimisation (per-instance times are out of scope).  RTOC_ERR_NOT_READY without a plan or the grid times.
+ *
+ * rtoc_get_task_ref_table / rtoc_get_configuration_ref_table: the tables as the instances read them, entries[count][nstages],
+ * q_ref[count][nstages][nq] and active[count][nstages], count <= batch (a shared table repeated; any pointer may be NULL) and
+ * *per_instance = the mode in force.  RTOC_ERR_NOT_READY where no table is set for the grid in force.
+ *
+ * rtoc_set_grid leaves the planner, its state and the plan alone (the plan does not depend on the grid), but forgets the tables:
+ * place and refs again.  rtoc_set_robot_model ends the planner.  rtoc_clone copies planner, state and plan. */
+#define RTOC_MAX_PLAN_STEPS 32
+#define RTOC_FOOT_STEP_FIXED 0          /* TrotFootStepPlanner::setGaitPattern        */
+#define RTOC_FOOT_STEP_RAIBERT 1        /* TrotFootStepPlanner::setRaibertGaitPattern */
+#define RTOC_PROJECT_AS_REFERENCE 0     /* BASE-ROTATION PROJECTION above             */
+#define RTOC_PROJECT_YAW 1
+typedef struct rtoc_foot_step_planner {
+  int mode;                    /* RTOC_FOOT_STEP_*                                                       */
+  int projection;              /* RTOC_PROJECT_*: the reference's ProjectRotationMatrix divides by R00^2 + 2 R01, which is
+                                * NOT the row's norm and crosses zero at a yaw of 0.427 rad (see above); 0 keeps it */
+  int enable_stance_phase;     /* fixed mode                                                             */
+  int pad;
+  double swing_time, stance_time, gain;   /* Raibert mode (gait timing; shared by the batch)             */
+  double step_length[3], step_yaw;        /* fixed mode, per instance                                    */
+  double vcom_cmd[3], yaw_rate_cmd;       /* Raibert mode, per instance                                  */
+} rtoc_foot_step_planner;
+typedef struct rtoc_foot_step_ref_params {
+  int foot_term[4];            /* index of the RTOC_TASK_FRAME_3D term of LF, LH, RF, RH; negative: left out */
+  int com_term;                /* index of the RTOC_TASK_COM term; negative: left out                       */
+  int configuration;           /* != 0: the configuration reference                                         */
+  double swing_height[4], swing_start_time[4], period_swing[4], period_stance[4];   /* MPCPeriodicSwingFootRef */
+  int swing_num_phases_in_period[4];
+  double com_swing_start_time, com_period_active, com_period_inactive;              /* MPCPeriodicCoMRef */
+  int com_num_phases_in_period, pad0;
+  double q_swing_start_time, q_period_active, q_period_inactive;                    /* MPCPeriodicConfigurationRef */
+  int q_num_phases_in_period, pad1;
+} rtoc_foot_step_ref_params;
+int rtoc_set_foot_step_planner(rtoc_ctx* ctx, const rtoc_foot_step_planner* p, int per_instance);
+int rtoc_foot_step_planner_init(rtoc_ctx* ctx);
+int rtoc_foot_step_plan(rtoc_ctx* ctx, double t, unsigned contact_status0, int planning_steps);
+int rtoc_foot_step_plan_get(rtoc_ctx* ctx, double* positions, double* com, double* R, double* step_length, int* ok, int count,
+                            int* size, int* current_step);
+int rtoc_foot_step_place(rtoc_ctx* ctx, const int* phase_of_grid_point, int nstages);
+int rtoc_foot_step_refs(rtoc_ctx* ctx, const rtoc_foot_step_ref_params* r, const int* phase_of_grid_point, const unsigned* phase_masks,
+                        int nphases, int nstages);
+
 /* linearizeContactDynamics (src/dynamics/contact_dynamics.cpp:12-33) on intermediate / lift grids and
  * linearizeImpactDynamics (src/dynamics/impact_dynamics.cpp:12-27) on impact grids, for every (instance, grid point)
  * but the terminal one: from RTOC_BUF_SOL (q, v, a | dv, f_stack, u) to RTOC_BUF_CDD
@@ -226,6 +337,8 @@ int rtoc_set_grid_times(rtoc_ctx* ctx, const double* t, int nstages);
  * table, as it forgets the grid times; rtoc_set_task_costs keeps them (a table belongs to the term INDEX).  Evaluating a
  * RTOC_REF_TABLE term without a table returns RTOC_ERR_NOT_READY.  rtoc_clone copies the tables. */
 int rtoc_set_task_ref_table(rtoc_ctx* ctx, int term, const rtoc_task_ref_entry* entries, int nstages, int per_instance);
+/* the table of term `term` as the instances read it (see rtoc_foot_step_refs above, which fills such tables on the device) */
+int rtoc_get_task_ref_table(rtoc_ctx* ctx, int term, rtoc_task_ref_entry* entries, int count, int* per_instance);
 int rtoc_get_grid_times(rtoc_ctx* ctx, double* host_out, int count);
 /* LocalContactForceCost (src/cost/local_contact_force_cost.cpp) evaluated by rtoc_contact_eval_kkt behind the terms above and
  * ahead of the constraints and the dynamics.  Per contact i active at the grid point, d = f_i[0:3] - f_ref[i], o_i its offset
@@ -445,6 +558,8 @@ int rtoc_set_configuration_cost(rtoc_ctx* ctx, const rtoc_configuration_cost* co
  * RTOC_ERR_NOT_READY before anything is launched, never the constant reference in its place (the rule of the task tables).
  * rtoc_set_configuration_cost keeps the table, and its q_ref member is ignored while one is in force.  rtoc_clone copies it. */
 int rtoc_set_configuration_ref_table(rtoc_ctx* ctx, const double* q_ref, const int* active, int nstages, int per_instance);
+/* the table as the instances read it: q_ref[count][nstages][nq], active[count][nstages] (see rtoc_foot_step_refs above) */
+int rtoc_get_configuration_ref_table(rtoc_ctx* ctx, double* q_ref, int* active, int count, int* per_instance);
 /* (q, v) of OCPSolver / UnconstrOCPSolver::updateSolution(t, q, v) for every instance: x0[batch][nq + nv], nq = nv, or
  * nv + 1 with a free-flyer base (dims.np == 6: [x y z qx qy qz qw, joints]). */
 int rtoc_set_initial_state(rtoc_ctx* ctx, const double* x0, int count);

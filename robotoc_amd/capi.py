@@ -43,14 +43,40 @@ EXPORTS = [
     "rtoc_solution_store", "rtoc_solution_interpolate", "rtoc_solution_stored", "rtoc_solution_forget",
     "rtoc_control_policy", "rtoc_control_input",
     "rtoc_set_contact_placements", "rtoc_contact_frame_placements", "rtoc_hold_contact_placements", "rtoc_get_contact_placements",
+    "rtoc_set_foot_step_planner", "rtoc_foot_step_planner_init", "rtoc_foot_step_plan", "rtoc_foot_step_plan_get", "rtoc_foot_step_place",
+    "rtoc_foot_step_refs", "rtoc_get_task_ref_table", "rtoc_get_configuration_ref_table",
 ]
 
 
 LINE_SEARCH_FILTER_CAPACITY = 32  # RTOC_LINE_SEARCH_FILTER_CAPACITY
+MAX_PLAN_STEPS = 32  # RTOC_MAX_PLAN_STEPS
+FOOT_STEP_FIXED, FOOT_STEP_RAIBERT = 0, 1  # RTOC_FOOT_STEP_*
+PROJECT_AS_REFERENCE, PROJECT_YAW = 0, 1  # RTOC_PROJECT_*
+
+
+class FootStepPlanner(C.Structure):
+    """include/rtoc_robot.h rtoc_foot_step_planner"""
+    _fields_ = [("mode", C.c_int), ("projection", C.c_int), ("enable_stance_phase", C.c_int), ("pad", C.c_int),
+                ("swing_time", C.c_double), ("stance_time", C.c_double), ("gain", C.c_double),
+                ("step_length", C.c_double * 3), ("step_yaw", C.c_double), ("vcom_cmd", C.c_double * 3), ("yaw_rate_cmd", C.c_double)]
+
+
+class FootStepRefs(C.Structure):
+    """include/rtoc_robot.h rtoc_foot_step_ref_params"""
+    _fields_ = [("foot_term", C.c_int * 4), ("com_term", C.c_int), ("configuration", C.c_int),
+                ("swing_height", C.c_double * 4), ("swing_start_time", C.c_double * 4), ("period_swing", C.c_double * 4),
+                ("period_stance", C.c_double * 4), ("swing_num_phases_in_period", C.c_int * 4),
+                ("com_swing_start_time", C.c_double), ("com_period_active", C.c_double), ("com_period_inactive", C.c_double),
+                ("com_num_phases_in_period", C.c_int), ("pad0", C.c_int),
+                ("q_swing_start_time", C.c_double), ("q_period_active", C.c_double), ("q_period_inactive", C.c_double),
+                ("q_num_phases_in_period", C.c_int), ("pad1", C.c_int)]
 
 
 class RtocError(RuntimeError):
-    pass
+    code = 0   # the RTOC_ERR_* the library returned
+
+
+ERR_BAD_ARG, ERR_UNSUPPORTED_DIMS, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_READY = -1, -2, -3, -4, -5  # include/rtoc.h
 
 
 def lib_path():
@@ -204,6 +230,15 @@ def lib():
         L.rtoc_contact_frame_placements.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.c_int]
         L.rtoc_hold_contact_placements.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]
         L.rtoc_get_contact_placements.argtypes = [vp, dp, dp, C.c_int, C.POINTER(C.c_int)]
+        ip = C.POINTER(C.c_int)
+        L.rtoc_set_foot_step_planner.argtypes = [vp, vp, C.c_int]
+        L.rtoc_foot_step_planner_init.argtypes = [vp]
+        L.rtoc_foot_step_plan.argtypes = [vp, C.c_double, C.c_uint, C.c_int]
+        L.rtoc_foot_step_plan_get.argtypes = [vp, dp, dp, dp, dp, ip, C.c_int, ip, ip]
+        L.rtoc_foot_step_place.argtypes = [vp, ip, C.c_int]
+        L.rtoc_foot_step_refs.argtypes = [vp, vp, ip, C.POINTER(C.c_uint), C.c_int, C.c_int]
+        L.rtoc_get_task_ref_table.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+        L.rtoc_get_configuration_ref_table.argtypes = [vp, dp, ip, C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -216,7 +251,9 @@ def layout_for(dims):
 
 def _chk(rc):
     if rc != 0:
-        raise RtocError("rtoc error %d: %s" % (rc, lib().rtoc_error_string(rc).decode()))
+        e = RtocError("rtoc error %d: %s" % (rc, lib().rtoc_error_string(rc).decode()))
+        e.code = rc
+        raise e
 
 
 def _dp(a):
@@ -651,6 +688,79 @@ class Context:
         None: to the end of the grid).  A shared table becomes per instance, every instance starting from the shared values."""
         _chk(lib().rtoc_hold_contact_placements(self._h, self._PLACEMENT_SOURCES[source], int(grid_point), int(first),
                                                 self.nstages if last is None else int(last), int(contacts)))
+
+    def clone(self):
+        """rtoc_clone: a second context with the same configuration, state and records"""
+        h = C.c_void_p()
+        _chk(lib().rtoc_clone(self._h, C.byref(h)))
+        twin = Context.__new__(Context)
+        twin.__dict__.update(self.__dict__)
+        twin._h = h
+        return twin
+
+    # ---- TrotFootStepPlanner and the MPC references on the device (include/rtoc_robot.h) ----
+    def set_foot_step_planner(self, planner):
+        """rtoc_set_foot_step_planner: `planner` = a FootStepPlanner struct for the batch, a list of `batch` of them (every instance its
+        own command), or None (removes the planner)"""
+        if planner is None:
+            _chk(lib().rtoc_set_foot_step_planner(self._h, None, 0))
+            return
+        per_instance = not isinstance(planner, FootStepPlanner)
+        rows = list(planner) if per_instance else [planner]
+        if per_instance and len(rows) != self.batch:
+            raise ValueError("per-instance commands need one planner struct per instance")
+        arr = (FootStepPlanner * len(rows))(*rows)
+        _chk(lib().rtoc_set_foot_step_planner(self._h, C.cast(arr, C.c_void_p), 1 if per_instance else 0))
+
+    def foot_step_planner_init(self):
+        """rtoc_foot_step_planner_init: TrotFootStepPlanner::init at the q of set_initial_state, every instance"""
+        _chk(lib().rtoc_foot_step_planner_init(self._h))
+
+    def foot_step_plan(self, t, contact_status0, planning_steps):
+        """rtoc_foot_step_plan: TrotFootStepPlanner::plan from the q, v of set_initial_state; contact_status0 = the bit mask of the
+        contacts active in the first phase"""
+        _chk(lib().rtoc_foot_step_plan(self._h, float(t), int(contact_status0), int(planning_steps)))
+
+    def foot_step_plan_get(self):
+        """rtoc_foot_step_plan_get: a dict -- positions [batch, size, 4, 3], com [batch, size, 3], R [batch, size, 3, 3],
+        step_length [batch, 3], ok [batch] (bool), size, current_step"""
+        B, S = self.batch, MAX_PLAN_STEPS + 2
+        pos, com, R, sl = np.zeros((B, S * 12)), np.zeros((B, S * 3)), np.zeros((B, S * 9)), np.zeros((B, 3))
+        ok, size, cur = np.zeros(B, dtype=np.int32), C.c_int(0), C.c_int(0)
+        _chk(lib().rtoc_foot_step_plan_get(self._h, _dp(pos), _dp(com), _dp(R), _dp(sl), ok.ctypes.data_as(C.POINTER(C.c_int)), B,
+                                           C.byref(size), C.byref(cur)))
+        n = size.value   # the library packs [count][size][...] densely at the front of the arrays
+        return dict(positions=pos.reshape(-1)[:B * n * 12].reshape(B, n, 4, 3).copy(), com=com.reshape(-1)[:B * n * 3].reshape(B, n, 3).copy(),
+                    R=R.reshape(-1)[:B * n * 9].reshape(B, n, 3, 3).copy(), step_length=sl, ok=ok != 0, size=n, current_step=cur.value)
+
+    def foot_step_place(self, phase_of_grid_point):
+        """rtoc_foot_step_place: grid point i of every instance <- contactPositions(phase_of_grid_point[i] + 1) of its plan"""
+        ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
+        _chk(lib().rtoc_foot_step_place(self._h, ph.ctypes.data_as(C.POINTER(C.c_int)), ph.size))
+
+    def foot_step_refs(self, refs, phase_of_grid_point, phase_masks):
+        """rtoc_foot_step_refs: `refs` = a FootStepRefs struct; the swing-foot, CoM and configuration references of every
+        (instance, grid point) into the per-instance reference tables"""
+        ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
+        mk = np.ascontiguousarray(phase_masks, dtype=np.uint32)
+        _chk(lib().rtoc_foot_step_refs(self._h, C.cast(C.pointer(refs), C.c_void_p), ph.ctypes.data_as(C.POINTER(C.c_int)),
+                                       mk.ctypes.data_as(C.POINTER(C.c_uint)), mk.size, ph.size))
+
+    def task_ref_table(self, term):
+        """rtoc_get_task_ref_table: (R [batch, nstages, 3, 3], p [batch, nstages, 3], active [batch, nstages] (bool), per_instance)
+        -- the table of term `term` as the instances read it"""
+        raw = np.zeros((self.batch, self.nstages, 13))
+        inst = C.c_int(0)
+        _chk(lib().rtoc_get_task_ref_table(self._h, int(term), raw.ctypes.data_as(C.c_void_p), self.batch, C.byref(inst)))
+        flags = np.ascontiguousarray(raw[..., 12]).view(np.int32).reshape(self.batch, self.nstages, 2)
+        return raw[..., :9].reshape(self.batch, self.nstages, 3, 3).copy(), raw[..., 9:12].copy(), flags[..., 0] != 0, bool(inst.value)
+
+    def configuration_ref_table(self):
+        """rtoc_get_configuration_ref_table: (q_ref [batch, nstages, nq], active [batch, nstages] (bool), per_instance)"""
+        nq = self.dims.nv + (1 if self.dims.np == 6 else 0)
+        q, act, inst = np.zeros((self.batch, self.nstages, nq)), np.zeros((self.batch, self.nstages), dtype=np.int32), C.c_int(0)
+        _chk(lib().rtoc_get_configuration_ref_table(self._h, _dp(q), act.ctypes.data_as(C.POINTER(C.c_int)), self.batch, C.byref(inst)))
+        return q, act != 0, bool(inst.value)
 
     def set_configuration_cost(self, q_ref, v_ref, u_ref, q_weight, v_weight, a_weight, u_weight, q_weight_terminal, v_weight_terminal,
                                q_weight_impact=None, v_weight_impact=None, dv_weight_impact=None):

@@ -218,6 +218,7 @@ struct TaskState {
   DevBuf<rtoc_task_cost> d_tasks;  // capacity [batch][RTOC_MAX_TASK_COSTS]; in use [ntasks] or [batch][ntasks]
   int ntasks = 0, tasks_per_instance = 0;
   unsigned h_task_table = 0;       // bit k: term k (of some instance) has ref_kind RTOC_REF_TABLE
+  unsigned h_task_3d = 0, h_task_com = 0;   // bit k: term k of EVERY instance is a RTOC_TASK_FRAME_3D / a RTOC_TASK_COM term
   DevBuf<double> d_gt;             // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
   std::vector<double> h_gt;        // host copy of the same, its size = the grid it belongs to (empty: none)
   // reference tables of RTOC_REF_TABLE terms (rtoc_set_task_ref_table), by term index: capacity [max_stages] or [batch][max_stages],
@@ -237,6 +238,7 @@ struct TaskState {
     dup(d_gt, src.d_gt);
     h_gt = src.h_gt;
     task_rows = src.task_rows, task_ext = src.task_ext, reftab_inst = src.reftab_inst, h_task_table = src.h_task_table;
+    h_task_3d = src.h_task_3d, h_task_com = src.h_task_com;
     for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) {
       reftab_n[k] = src.reftab_n[k];
       dup(d_reftab[k], src.d_reftab[k]);
@@ -352,10 +354,35 @@ struct PolicyState {
   DevBuf<double> d_policy_stage;  // host-pointer calls: t [batch], x [batch][nq + nv], the result [batch][policy stride]
 };
 
+// TrotFootStepPlanner and the MPC references on the device (rtoc_set_foot_step_planner ..; foot_step_planner.hpp; rt_foot_steps.hip).
+// The device layouts ([slot][batch]) are the kernel header's
+struct FootStepState {
+  int fs_on = 0;             // a planner is set
+  int fs_init = 0;           // rtoc_foot_step_planner_init ran since
+  rtoc_foot_step_planner fs_shared = {};   // mode, projection, timing, gain, enable_stance_phase: what the batch shares
+  int fs_current_step = 0;   // current_step_: kept once, on the host
+  int fs_size = 0;           // steps of the plan on the device; 0: none
+  DevBuf<double> d_fs_cmd;   // [FS_CMD_SLOTS][batch] commands
+  DevBuf<double> d_fs_state; // [FS_STATE_SLOTS][batch] rotation, local offsets, filter
+  DevBuf<double> d_fs_plan;  // [RTOC_MAX_PLAN_STEPS + 2][FS_PLAN_SLOTS][batch]
+  DevBuf<double> d_fs_q0;    // [batch][nq] the q of the init
+  void clone_from(const FootStepState& src, CopyChain& dup) {
+    if (!src.fs_on) return;
+    fs_on = 1, fs_init = src.fs_init, fs_shared = src.fs_shared, fs_current_step = src.fs_current_step, fs_size = src.fs_size;
+    dup(d_fs_cmd, src.d_fs_cmd);
+    dup(d_fs_state, src.d_fs_state);
+    dup(d_fs_plan, src.d_fs_plan);
+    dup(d_fs_q0, src.d_fs_q0);
+  }
+  // not copied: the scratch of one call
+  DevBuf<double> d_fs_fk;    // [batch][4][3] foot positions + [batch][3] centre of mass (contact_frame_placements_kernel)
+  DevBuf<int> d_fs_phase;    // [max_stages] phase of every grid point + [RTOC_MAX_PLAN_STEPS + 2] masks of the phases
+};
+
 }  // namespace rtoc
 
 struct rtoc_ctx : rtoc::CtxStreams, rtoc::CtxOptions, rtoc::SweepState, rtoc::ConstraintState, rtoc::ModelState, rtoc::TaskState,
-                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState, rtoc::InterpState, rtoc::PolicyState {
+                  rtoc::StoState, rtoc::LineSearchState, rtoc::ParnmpcState, rtoc::InterpState, rtoc::PolicyState, rtoc::FootStepState {
   rtoc_dims dims = {};
   rtoc_layout L = {};
   const rtoc::KernelSet* ks = nullptr;
@@ -469,6 +496,13 @@ void launch_fill_steps(rtoc_ctx* c);
 // rt_eval_kkt.hip
 hipError_t reserve_kkterr(rtoc_ctx* c);
 int launch_kkt_error(rtoc_ctx* c);
+// what rt_foot_steps.hip shares with the contact placements: a schedule that belongs to the grid in force (else RTOC_ERR_NOT_READY);
+// the per-instance placement table from whatever is in force, every instance starting from the shared values (need_rot: a rotation
+// table too, created if there is none); contact_frame_placements_kernel at the q of rtoc_set_initial_state into device memory,
+// out_p[batch][ncontacts][3] and out_com[batch][3]
+int placements_ready(const rtoc_ctx* c);
+int placements_per_instance(rtoc_ctx* c, bool need_rot);
+int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com);
 // records per instance that carry dynamics and rows: all but the terminal one, or all of a ParNMPC horizon
 static inline int dynamics_records(const rtoc_ctx* c) { return c->nstages - 1 + (c->parnmpc ? 1 : 0); }
 // the unconstrained path's pieces rt_parnmpc.hip strings together: the all-zero contact schedule, linearizeUnconstrDynamics with

@@ -168,6 +168,7 @@ int rtoc_set_robot_model(rtoc_ctx* c, const rtoc_robot_model* m) {
     c->d_cpos.release(), c->d_crot.release();
     c->cplace_inst = 0, c->has_cpos = c->has_crot = false;
   }
+  c->fs_on = 0, c->fs_init = 0, c->fs_size = 0;   // a foot-step planner belongs to the feet of the model it was set for
   c->h_model = std::move(h);
   HIP_TRY(hipMemcpyAsync(c->d_model.p, c->h_model.get(), sizeof(rbd::DevModel), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -214,7 +215,7 @@ static size_t placement_capacity(const rtoc_ctx* c, int per_instance, int unit) 
   return per_instance ? (size_t)c->batch * c->max_stages * c->h_model->m.ncontacts * unit : (size_t)c->max_stages * RTOC_MAX_CONTACTS * unit;
 }
 // a schedule that belongs to the grid in force, of a model with contacts
-static int placements_ready(const rtoc_ctx* c) {
+int rtoc::placements_ready(const rtoc_ctx* c) {
   if (!c->h_model || !c->d_active.p || !c->active_current || (int)c->h_active.size() != c->nstages) return RTOC_ERR_NOT_READY;
   return RTOC_OK;
 }
@@ -327,22 +328,10 @@ int rtoc_contact_frame_placements(rtoc_ctx* c, int source, int grid_point, doubl
   return RTOC_OK;
 }
 
-int rtoc_hold_contact_placements(rtoc_ctx* c, int source, int grid_point, int first, int last, unsigned contacts) {
-  CHECK_READY(c);
-  int rc = placements_ready(c);
-  if (rc) return rc;
-  const rtoc_robot_model& m = c->h_model->m;
-  const int nc = m.ncontacts;
-  if (nc < 1 || first < 0 || last > c->nstages || first >= last || (nc < 32 && (contacts >> nc) != 0)) return RTOC_ERR_BAD_ARG;
-  FkArgs a{};
-  rc = placement_source(c, source, grid_point, &a.q, &a.q_stride);
-  if (rc) return rc;
-  if (contacts == 0) return RTOC_OK;   // no foot on the ground: nothing to hold
-  bool need_rot = false;
-  for (int k = 0; k < nc; ++k)
-    if (((contacts >> k) & 1u) && m.contact_type[k] == RTOC_CONTACT_SURFACE) need_rot = true;
-  // a table per instance, every instance starting from what the batch shared (zeros / identities where nothing was set).  Both
-  // allocations ahead of any change: a failure leaves the table in force
+// A table per instance, every instance starting from what the batch shared (zeros / identities where nothing was set).  Both
+// allocations ahead of any change: a failure leaves the table in force
+int rtoc::placements_per_instance(rtoc_ctx* c, bool need_rot) {
+  const int nc = c->h_model->m.ncontacts;
   const bool new_p = !(c->cplace_inst && c->has_cpos), new_r = c->has_crot ? !c->cplace_inst : need_rot;
   DevBuf<double> pos, rot;
   if (new_p) HIP_TRY(pos.reserve(placement_capacity(c, 1, 3)));
@@ -363,6 +352,33 @@ int rtoc_hold_contact_placements(rtoc_ctx* c, int source, int grid_point, int fi
     c->has_cpos = true, c->has_crot = c->has_crot || new_r, c->cplace_inst = 1;
     c->epoch++;
   }
+  return RTOC_OK;
+}
+// the kinematics at the q of rtoc_set_initial_state, the result left on the device (rt_foot_steps.hip)
+int rtoc::launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com) {
+  FkArgs a{};
+  const int rc = placement_source(c, 0, 0, &a.q, &a.q_stride);
+  if (rc) return rc;
+  a.out_p = out_p, a.out_com = out_com;
+  return launch_frame_placements(c, a);
+}
+
+int rtoc_hold_contact_placements(rtoc_ctx* c, int source, int grid_point, int first, int last, unsigned contacts) {
+  CHECK_READY(c);
+  int rc = placements_ready(c);
+  if (rc) return rc;
+  const rtoc_robot_model& m = c->h_model->m;
+  const int nc = m.ncontacts;
+  if (nc < 1 || first < 0 || last > c->nstages || first >= last || (nc < 32 && (contacts >> nc) != 0)) return RTOC_ERR_BAD_ARG;
+  FkArgs a{};
+  rc = placement_source(c, source, grid_point, &a.q, &a.q_stride);
+  if (rc) return rc;
+  if (contacts == 0) return RTOC_OK;   // no foot on the ground: nothing to hold
+  bool need_rot = false;
+  for (int k = 0; k < nc; ++k)
+    if (((contacts >> k) & 1u) && m.contact_type[k] == RTOC_CONTACT_SURFACE) need_rot = true;
+  rc = placements_per_instance(c, need_rot);
+  if (rc) return rc;
   a.tab_pos = c->d_cpos.p, a.tab_rot = c->has_crot ? c->d_crot.p : nullptr;
   a.first = first, a.last = last, a.contacts = contacts;
   c->vals_fresh = 0;
@@ -511,6 +527,22 @@ int rtoc_set_configuration_ref_table(rtoc_ctx* c, const double* q_ref, const int
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (fresh || fresh_a || !c->qtab_on || c->qtab_inst != per_instance) c->epoch++;
   c->qtab_on = 1, c->qtab_n = nstages, c->qtab_inst = per_instance;
+  return RTOC_OK;
+}
+int rtoc_get_configuration_ref_table(rtoc_ctx* c, double* q_ref, int* active, int count, int* per_instance) {
+  CHECK_READY(c);
+  if (count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
+  if (!c->qtab_on || c->qtab_n != c->nstages || !c->d_qtab.p || !c->d_qtab_active.p) return RTOC_ERR_NOT_READY;
+  if (per_instance) *per_instance = c->qtab_inst;
+  const size_t nq = (size_t)c->dims.nv + (c->dims.np == 6 ? 1 : 0), n = c->nstages, rows = n * (c->qtab_inst ? count : 1);
+  if (count == 0) return RTOC_OK;
+  if (q_ref) HIP_TRY(hipMemcpyAsync(q_ref, c->d_qtab.p, sizeof(double) * rows * nq, hipMemcpyDeviceToHost, c->stream));
+  if (active) HIP_TRY(hipMemcpyAsync(active, c->d_qtab_active.p, sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int b = 1; !c->qtab_inst && b < count; ++b) {   // a shared table repeated
+    if (q_ref) memcpy(q_ref + b * n * nq, q_ref, sizeof(double) * n * nq);
+    if (active) memcpy(active + b * n, active, sizeof(int) * n);
+  }
   return RTOC_OK;
 }
 // The table for the kernels that read the cost table (q = nullptr without one).  RTOC_ERR_NOT_READY: a table is in use but its rows

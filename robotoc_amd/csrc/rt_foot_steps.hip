@@ -1,0 +1,306 @@
+// rt_foot_steps.hip -- TrotFootStepPlanner and the MPC references of every instance on the device: planner and commands, init,
+// plan, the read-back of the plan, the placements of every contact phase, the three periodic references (foot_step_planner.hpp).
+#include <cmath>
+
+#include "rt_context.hpp"
+#include "foot_step_planner.hpp"
+
+using namespace rtoc;
+
+#define CHECK_NO_PARNMPC(c)          \
+  if (!(c)) return RTOC_ERR_BAD_ARG; \
+  if ((c)->parnmpc) return RTOC_ERR_BAD_ARG;
+
+static constexpr int FS_MAX_STEPS = RTOC_MAX_PLAN_STEPS + 2;
+
+// the gait of the reference's quadrupeds: exactly four point contacts (LF, LH, RF, RH = contacts 0..3)
+static bool four_point_feet(const rtoc_ctx* c) {
+  const rtoc_robot_model& m = c->h_model->m;
+  if (m.ncontacts != 4) return false;
+  for (int k = 0; k < 4; ++k)
+    if (m.contact_type[k] != RTOC_CONTACT_POINT) return false;
+  return true;
+}
+// setGaitPattern has no checks; setRaibertGaitPattern: trot_foot_step_planner.cpp:68-76 (the period of raibert_heuristic.cpp:39 is
+// positive with them, its gain check is the same one)
+static bool planner_valid(const rtoc_foot_step_planner& p) {
+  if (p.mode != RTOC_FOOT_STEP_FIXED && p.mode != RTOC_FOOT_STEP_RAIBERT) return false;
+  if (p.projection != RTOC_PROJECT_AS_REFERENCE && p.projection != RTOC_PROJECT_YAW) return false;
+  if (p.enable_stance_phase != 0 && p.enable_stance_phase != 1) return false;
+  if (p.mode == RTOC_FOOT_STEP_RAIBERT && (!(p.swing_time > 0.0) || !(p.stance_time >= 0.0) || !(p.gain > 0.0))) return false;
+  return true;
+}
+// what decides the step-case sequence: shared structure, like the grid
+static bool same_structure(const rtoc_foot_step_planner& a, const rtoc_foot_step_planner& b) {
+  return a.mode == b.mode && a.projection == b.projection && a.enable_stance_phase == b.enable_stance_phase && a.swing_time == b.swing_time &&
+         a.stance_time == b.stance_time && a.gain == b.gain;
+}
+static bool stance_phase_enabled(const rtoc_foot_step_planner& p) {
+  return p.mode == RTOC_FOOT_STEP_RAIBERT ? p.stance_time > 0.0 : p.enable_stance_phase != 0;   // :58, :86
+}
+
+int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int per_instance) {
+  CHECK_NO_PARNMPC(c);
+  if (!p) {
+    c->fs_on = 0, c->fs_init = 0, c->fs_size = 0;   // the state goes with the planner: init again after the next one is set
+    return RTOC_OK;
+  }
+  if (per_instance != 0 && per_instance != 1) return RTOC_ERR_BAD_ARG;
+  if (!c->h_model) return RTOC_ERR_NOT_READY;
+  if (!four_point_feet(c)) return RTOC_ERR_BAD_ARG;
+  const int B = c->batch, n = per_instance ? B : 1;
+  for (int b = 0; b < n; ++b)
+    if (!planner_valid(p[b]) || !same_structure(p[b], p[0])) return RTOC_ERR_BAD_ARG;
+  std::vector<double> cmd((size_t)FS_CMD_SLOTS * B, 0.0);
+  for (int b = 0; b < B; ++b) {
+    const rtoc_foot_step_planner& q = p[per_instance ? b : 0];
+    const bool raibert = q.mode == RTOC_FOOT_STEP_RAIBERT;
+    for (int k = 0; k < 3; ++k) cmd[(size_t)(FS_CMD_STEP + k) * B + b] = raibert ? 0.0 : q.step_length[k];
+    cmd[(size_t)FS_CMD_YAW * B + b] = raibert ? q.yaw_rate_cmd * (q.swing_time + q.stance_time) : q.step_yaw;   // :81
+    for (int k = 0; k < 2; ++k) cmd[(size_t)(FS_CMD_VCOM + k) * B + b] = raibert ? q.vcom_cmd[k] : 0.0;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(c->d_fs_cmd.reserve(cmd.size()));
+  HIP_TRY(hipMemcpyAsync(c->d_fs_cmd.p, cmd.data(), sizeof(double) * cmd.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->fs_shared = p[0];
+  c->fs_on = 1;
+  return RTOC_OK;
+}
+
+static int reserve_planner(rtoc_ctx* c) {
+  const size_t B = c->batch, nq = c->h_model->m.nq;
+  HIP_TRY(c->d_fs_fk.reserve(B * 15));
+  HIP_TRY(c->d_fs_state.reserve(B * FS_STATE_SLOTS));
+  HIP_TRY(c->d_fs_plan.reserve(B * FS_PLAN_SLOTS * FS_MAX_STEPS));
+  HIP_TRY(c->d_fs_q0.reserve(B * nq));
+  return RTOC_OK;
+}
+
+int rtoc_foot_step_planner_init(rtoc_ctx* c) {
+  CHECK_READY(c);
+  if (!c->fs_on || !c->h_model || !c->d_x0.p) return RTOC_ERR_NOT_READY;
+  int rc = reserve_planner(c);
+  if (rc) return rc;
+  const int B = c->batch;
+  rc = launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
+  if (rc) return rc;
+  FsInitArgs a{};
+  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.com = c->d_fs_fk.p + (size_t)B * 12;
+  a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p, a.q0 = c->d_fs_q0.p;
+  a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
+  a.projection = c->fs_shared.projection;
+  hipLaunchKernelGGL(foot_step_init_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  c->fs_init = 1, c->fs_current_step = 0, c->fs_size = 0;
+  return RTOC_OK;
+}
+
+// The case chain of plan() (:145-277): current_step_ and the contact status are shared by the batch, so the host walks it once.
+// false: a contact status the reference answers with `return false`
+static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int planning_steps, int* current_step, FsPlanArgs* a) {
+  const bool stance = stance_phase_enabled(p);
+  int cur = *current_step;
+  a->stance = status, a->pre_rotate = 0;
+  if (status == 0b1111u) {
+    if (stance) {
+      if (cur % 2 != 0) ++cur;
+    } else {
+      cur = 0;
+    }
+  } else if (status == 0b1001u) {
+    if (stance ? cur % 4 != 1 : cur % 2 != 1) ++cur, a->pre_rotate = 1;
+  } else if (status == 0b0110u) {
+    if (stance ? cur % 4 != 3 : cur % 2 != 0) ++cur, a->pre_rotate = 1;
+  } else {
+    return false;
+  }
+  a->nloop = planning_steps + 1, a->first_at = -1;
+  a->first_scale = p.mode == RTOC_FOOT_STEP_RAIBERT ? 0.5 : 0.25;   // :219-224
+  for (int s = 0; s <= planning_steps; ++s) {
+    const int step = cur + s;
+    unsigned char mv = 0;
+    if (step == 0) mv = 0;
+    else if (cur == 0 && step == 1) mv = 0b0110, a->first_at = s;
+    else if (stance) mv = step % 4 == 1 ? 0b0110 : step % 4 == 3 ? 0b1001 : 0;
+    else mv = step % 2 == 1 ? 0b0110 : 0b1001;
+    a->move[s] = mv;
+  }
+  *current_step = cur;
+  return true;
+}
+
+int rtoc_foot_step_plan(rtoc_ctx* c, double t, unsigned contact_status0, int planning_steps) {
+  CHECK_READY(c);
+  if (!c->fs_on || !c->fs_init || !c->h_model || !c->d_x0.p || !c->d_fs_state.p || !c->d_fs_plan.p || !c->d_fs_cmd.p) return RTOC_ERR_NOT_READY;
+  if (planning_steps < 0 || planning_steps > RTOC_MAX_PLAN_STEPS || !std::isfinite(t)) return RTOC_ERR_BAD_ARG;
+  FsPlanArgs a{};
+  int cur = c->fs_current_step;
+  if (!plan_cases(c->fs_shared, contact_status0, planning_steps, &cur, &a)) return RTOC_ERR_BAD_ARG;
+  const int B = c->batch;
+  HIP_TRY(c->d_fs_fk.reserve((size_t)B * 15));   // scratch: a clone starts without it
+  int rc = launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
+  if (rc) return rc;
+  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.cmd = c->d_fs_cmd.p, a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p;
+  a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
+  a.raibert = c->fs_shared.mode == RTOC_FOOT_STEP_RAIBERT;
+  a.t = t;
+  a.period = 2.0 * (c->fs_shared.swing_time + c->fs_shared.stance_time);   // :77-79
+  a.min_period = 0.1 * a.period, a.gain = c->fs_shared.gain;
+  hipLaunchKernelGGL(foot_step_plan_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  c->fs_current_step = cur, c->fs_size = planning_steps + 2;
+  return RTOC_OK;
+}
+
+int rtoc_foot_step_plan_get(rtoc_ctx* c, double* positions, double* com, double* R, double* step_length, int* ok, int count, int* size,
+                            int* current_step) {
+  CHECK_READY(c);
+  if (count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
+  if (!c->fs_on || !c->fs_init || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;
+  if (size) *size = c->fs_size;
+  if (current_step) *current_step = c->fs_current_step;
+  const size_t B = c->batch, ns = c->fs_size;
+  std::vector<double> h(ns * FS_PLAN_SLOTS * B), sl(3 * B);
+  if (ns) HIP_TRY(hipMemcpyAsync(h.data(), c->d_fs_plan.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sl.data(), c->d_fs_state.p + (size_t)FS_ST_STEP * B, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b < (size_t)count; ++b) {
+    bool fin = true;
+    for (size_t s = 0; s < ns; ++s) {
+      const double* const src = h.data() + s * FS_PLAN_SLOTS * B + b;
+      for (int k = 0; k < FS_PLAN_SLOTS; ++k) fin = fin && std::isfinite(src[(size_t)k * B]);
+      for (int k = 0; positions && k < 12; ++k) positions[(b * ns + s) * 12 + k] = src[(size_t)(FS_PLAN_POS + k) * B];
+      for (int k = 0; com && k < 3; ++k) com[(b * ns + s) * 3 + k] = src[(size_t)(FS_PLAN_COM + k) * B];
+      for (int k = 0; R && k < 9; ++k) R[(b * ns + s) * 9 + k] = src[(size_t)(FS_PLAN_R + k) * B];
+    }
+    for (int k = 0; step_length && k < 3; ++k) step_length[b * 3 + k] = sl[(size_t)k * B + b];
+    if (ok) ok[b] = fin ? 1 : 0;
+  }
+  return RTOC_OK;
+}
+
+// the phases of the grid points (and the masks of the phases behind them) where the kernels read them
+static int upload_phases(rtoc_ctx* c, const int* phase, int nstages, const unsigned* masks, int nphases) {
+  HIP_TRY(c->d_fs_phase.reserve((size_t)c->max_stages + FS_MAX_STEPS));
+  HIP_TRY(hipMemcpyAsync(c->d_fs_phase.p, phase, sizeof(int) * nstages, hipMemcpyHostToDevice, c->stream));
+  if (masks) HIP_TRY(hipMemcpyAsync(c->d_fs_phase.p + c->max_stages, masks, sizeof(unsigned) * nphases, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (pageable sources of the caller)
+  return RTOC_OK;
+}
+static unsigned blocks_for(size_t total) { return (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096); }
+
+int rtoc_foot_step_place(rtoc_ctx* c, const int* phase_of_grid_point, int nstages) {
+  CHECK_READY(c);
+  if (!phase_of_grid_point) return RTOC_ERR_BAD_ARG;
+  if (!c->fs_on || !c->fs_init || c->fs_size < 2 || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;
+  int rc = placements_ready(c);
+  if (rc) return rc;
+  if (nstages != c->nstages || !four_point_feet(c)) return RTOC_ERR_BAD_ARG;
+  for (int i = 0; i < nstages; ++i)
+    if (phase_of_grid_point[i] < 0 || phase_of_grid_point[i] > c->fs_size - 2) return RTOC_ERR_BAD_ARG;
+  rc = upload_phases(c, phase_of_grid_point, nstages, nullptr, 0);
+  if (rc) return rc;
+  rc = placements_per_instance(c, false);
+  if (rc) return rc;
+  auto a = view_args<FsPlaceArgs>(c);
+  a.plan = c->d_fs_plan.p, a.phase = c->d_fs_phase.p, a.tab_pos = c->d_cpos.p;
+  hipLaunchKernelGGL(foot_step_place_kernel, dim3(blocks_for((size_t)c->batch * nstages * 12)), dim3(256), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  c->vals_fresh = 0;   // the contact rows of the values pre-pass belong to the previous placements
+  return RTOC_OK;
+}
+
+int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const int* phase_of_grid_point, const unsigned* phase_masks,
+                        int nphases, int nstages) {
+  CHECK_READY(c);
+  if (!r || !phase_of_grid_point || !phase_masks) return RTOC_ERR_BAD_ARG;
+  if (c->sto_on) return RTOC_ERR_BAD_ARG;   // every instance its own grid times: out of scope
+  if (!c->fs_on || !c->fs_init || c->fs_size < 1 || !c->d_fs_q0.p || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;
+  if (nstages != c->nstages || nphases < 1 || nphases > FS_MAX_STEPS) return RTOC_ERR_BAD_ARG;
+  if ((int)c->h_gt.size() != c->nstages || !c->d_gt.p) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
+  // ---- the six references as the kernel takes them; the arguments the reference's constructors refuse ----
+  FsRefsArgs a{};
+  int term_of[5];
+  unsigned named = 0;
+  for (int k = 0; k < 5; ++k) {
+    const int term = k < 4 ? r->foot_term[k] : r->com_term;
+    term_of[k] = term;
+    if (term < 0) continue;
+    if (term >= c->ntasks || !((c->h_task_table >> term) & 1u) || ((named >> term) & 1u)) return RTOC_ERR_BAD_ARG;
+    if (!(((k < 4 ? c->h_task_3d : c->h_task_com) >> term) & 1u)) return RTOC_ERR_BAD_ARG;   // a foot: TaskSpace3DCost; the CoM: CoMCost
+    named |= 1u << term;
+    FsPeriod& p = a.per[k];
+    p.on = 1;
+    if (k < 4) {
+      p.t0 = r->swing_start_time[k], p.period_active = r->period_swing[k], p.period_inactive = r->period_stance[k];
+      p.height = r->swing_height[k], p.nph = r->swing_num_phases_in_period[k];
+      if (!(p.height >= 0.0) || !(p.period_active > 0.0) || !(p.period_inactive > 0.0)) return RTOC_ERR_BAD_ARG;
+    } else {
+      p.t0 = r->com_swing_start_time, p.period_active = r->com_period_active, p.period_inactive = r->com_period_inactive;
+      p.nph = r->com_num_phases_in_period;
+      if (!(p.period_active >= 0.0) || !(p.period_inactive >= 0.0)) return RTOC_ERR_BAD_ARG;
+    }
+    if (p.nph < 1 || !std::isfinite(p.t0)) return RTOC_ERR_BAD_ARG;
+  }
+  if (r->configuration) {
+    FsPeriod& p = a.per[5];
+    p.on = 1, p.t0 = r->q_swing_start_time, p.period_active = r->q_period_active, p.period_inactive = r->q_period_inactive;
+    p.nph = r->q_num_phases_in_period;
+    if (!(p.period_active >= 0.0) || !(p.period_inactive >= 0.0) || p.nph < 1 || !std::isfinite(p.t0)) return RTOC_ERR_BAD_ARG;
+    if (c->dims.np != 6) return RTOC_ERR_BAD_ARG;
+  }
+  // ---- every plan step a grid point reads lies inside the plan ----
+  for (int i = 0; i < nstages; ++i) {
+    const int ph = phase_of_grid_point[i];
+    if (ph < 0 || ph >= nphases || ph >= c->fs_size) return RTOC_ERR_BAD_ARG;
+    const unsigned mask = phase_masks[ph];
+    for (int k = 0; k < 6; ++k) {
+      const FsPeriod& p = a.per[k];
+      if (!p.on) continue;
+      const bool reads_ahead = c->h_gt[i] > p.t0 && (k < 4 ? !((mask >> k) & 1u) : (mask & 0xFu) != 0xFu);
+      if (reads_ahead && ph + p.nph >= c->fs_size) return RTOC_ERR_BAD_ARG;
+    }
+  }
+  // ---- the per-instance tables: allocations first ----
+  const size_t cap = (size_t)c->max_stages * c->batch, nq = c->h_model->m.nq;
+  bool changed = false;
+  for (int k = 0; k < 5; ++k) {
+    if (term_of[k] < 0) continue;
+    bool fresh = false;
+    HIP_TRY(c->d_reftab[term_of[k]].reserve(cap, &fresh));
+    changed = changed || fresh;
+  }
+  if (r->configuration && (c->d_qtab.n != cap * nq || c->d_qtab_active.n != cap)) {
+    DevBuf<double> q;
+    DevBuf<int> f;
+    HIP_TRY(q.reserve(cap * nq));
+    HIP_TRY(f.reserve(cap));
+    c->d_qtab = std::move(q), c->d_qtab_active = std::move(f);
+    c->qtab_n = 0;
+    changed = true;
+  }
+  int rc = upload_phases(c, phase_of_grid_point, nstages, phase_masks, nphases);
+  if (rc) return rc;
+  a.plan = c->d_fs_plan.p, a.q0 = c->d_fs_q0.p, a.t = c->d_gt.p;
+  a.phase = c->d_fs_phase.p, a.masks = (const unsigned*)(c->d_fs_phase.p + c->max_stages);
+  for (int k = 0; k < 5; ++k) a.tab[k] = term_of[k] >= 0 ? c->d_reftab[term_of[k]].p : nullptr;
+  a.qtab = r->configuration ? c->d_qtab.p : nullptr, a.qtab_active = r->configuration ? c->d_qtab_active.p : nullptr;
+  a.batch = c->batch, a.nstages = nstages, a.nq = (int)nq;
+  const size_t most = (size_t)c->batch * nstages * (nq > (size_t)FS_ENTRY_WORDS ? nq : (size_t)FS_ENTRY_WORDS);
+  hipLaunchKernelGGL(foot_step_refs_kernel, dim3(blocks_for(most), 6), dim3(256), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  // the tables are per instance and belong to the grid in force (captured graphs bake pointer and mode in)
+  for (int k = 0; k < 5; ++k) {
+    if (term_of[k] < 0) continue;
+    const unsigned bit = 1u << term_of[k];
+    changed = changed || c->reftab_n[term_of[k]] != nstages || !(c->reftab_inst & bit);
+    c->reftab_n[term_of[k]] = nstages, c->reftab_inst |= bit;
+  }
+  if (r->configuration) {
+    changed = changed || !c->qtab_on || !c->qtab_inst || c->qtab_n != nstages;
+    c->qtab_on = 1, c->qtab_n = nstages, c->qtab_inst = 1;
+  }
+  if (changed) c->epoch++;
+  return RTOC_OK;
+}

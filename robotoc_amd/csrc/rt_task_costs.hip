@@ -53,9 +53,13 @@ int rtoc_set_task_costs(rtoc_ctx* c, const rtoc_task_cost* terms, int nterms, in
     }
     if (rows > c->task_rows) c->task_rows = rows;
   }
-  c->h_task_table = 0;
-  for (size_t i = 0; i < n; ++i)
-    if (terms[i].ref_kind == RTOC_REF_TABLE) c->h_task_table |= 1u << (i % nterms);
+  c->h_task_table = 0, c->h_task_3d = c->h_task_com = (1u << nterms) - 1u;
+  for (size_t i = 0; i < n; ++i) {
+    const unsigned bit = 1u << (i % nterms);
+    if (terms[i].ref_kind == RTOC_REF_TABLE) c->h_task_table |= bit;
+    if (terms[i].kind != RTOC_TASK_FRAME_3D) c->h_task_3d &= ~bit;
+    if (terms[i].kind != RTOC_TASK_COM) c->h_task_com &= ~bit;
+  }
   c->epoch++;   // launch parameters baked into captured graphs
   return RTOC_OK;
 }
@@ -81,6 +85,20 @@ int rtoc_set_task_ref_table(rtoc_ctx* c, int term, const rtoc_task_ref_entry* en
   if (fresh || c->reftab_n[term] != nstages || (c->reftab_inst & bit) != inst) c->epoch++;
   c->reftab_n[term] = nstages;
   c->reftab_inst = (c->reftab_inst & ~bit) | inst;
+  return RTOC_OK;
+}
+
+int rtoc_get_task_ref_table(rtoc_ctx* c, int term, rtoc_task_ref_entry* entries, int count, int* per_instance) {
+  CHECK_READY(c);
+  if (term < 0 || term >= RTOC_MAX_TASK_COSTS || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
+  if (c->reftab_n[term] != c->nstages || !c->d_reftab[term].p) return RTOC_ERR_NOT_READY;
+  const int inst = (c->reftab_inst >> term) & 1u;
+  if (per_instance) *per_instance = inst;
+  if (!entries || count == 0) return RTOC_OK;
+  const size_t n = c->nstages;
+  HIP_TRY(hipMemcpyAsync(entries, c->d_reftab[term].p, sizeof(rtoc_task_ref_entry) * n * (inst ? count : 1), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int b = 1; !inst && b < count; ++b) memcpy(entries + b * n, entries, sizeof(rtoc_task_ref_entry) * n);   // a shared table repeated
   return RTOC_OK;
 }
 

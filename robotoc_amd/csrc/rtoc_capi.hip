@@ -232,6 +232,7 @@ int rtoc_clone(rtoc_ctx* c, rtoc_ctx** out) {
     n->TaskState::clone_from(*c, dup);
     n->ParnmpcState::clone_from(*c, dup);
     n->InterpState::clone_from(*c, dup);
+    n->FootStepState::clone_from(*c, dup);
     n->clone_records(*c, dup);
     if (dup.e == hipSuccess) dup.e = hipStreamSynchronize(n->stream);
   }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "robotoc_hip.hpp"
+#include "../../include/rtoc_robot.h"
 
 namespace robotoc {
 
@@ -500,6 +501,91 @@ class SolutionInterpolator {
   std::vector<unsigned> masks_;
   std::vector<double> sol_;
   bool has_ = false;
+};
+
+// robotoc::TrotFootStepPlanner (src/mpc/trot_foot_step_planner.cpp) for the batch of a context: a thin mirror over
+// rtoc_set_foot_step_planner / rtoc_foot_step_planner_init / rtoc_foot_step_plan / rtoc_foot_step_plan_get (include/rtoc_robot.h).
+// The planning runs on the device from the q, v of rtoc_set_initial_state; commands are one for the batch or one per instance.
+class TrotFootStepPlanner {
+ public:
+  TrotFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : ctx_(ctx), batch_(batch), projection_(projection), size_(0), current_step_(0), fresh_(false) {
+    if (!ctx || batch < 1) throw std::invalid_argument("[TrotFootStepPlanner] a context and its batch size");
+  }
+  // step_length: 3 doubles for the batch or 3 per instance; step_yaw: one or one per instance
+  void setGaitPattern(const std::vector<double>& step_length, const std::vector<double>& step_yaw, const bool enable_stance_phase) {
+    const bool inst = perInstance(step_length.size(), 3, "step_length") | perInstance(step_yaw.size(), 1, "step_yaw");
+    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
+    for (size_t b = 0; b < p.size(); ++b) {
+      p[b].mode = RTOC_FOOT_STEP_FIXED, p[b].projection = projection_, p[b].enable_stance_phase = enable_stance_phase ? 1 : 0;
+      for (int k = 0; k < 3; ++k) p[b].step_length[k] = step_length[step_length.size() == 3 ? k : 3 * b + k];
+      p[b].step_yaw = step_yaw[step_yaw.size() == 1 ? 0 : b];
+    }
+    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
+    fresh_ = false;
+  }
+  void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double swing_time,
+                             const double stance_time, const double gain) {
+    if (swing_time <= 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'swing_time' must be positive!");
+    if (stance_time < 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'stance_time' must be non-negative!");
+    if (gain <= 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'gain' must be positive!");
+    const bool inst = perInstance(vcom_cmd.size(), 3, "vcom_cmd") | perInstance(yaw_rate_cmd.size(), 1, "yaw_rate_cmd");
+    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
+    for (size_t b = 0; b < p.size(); ++b) {
+      p[b].mode = RTOC_FOOT_STEP_RAIBERT, p[b].projection = projection_;
+      p[b].swing_time = swing_time, p[b].stance_time = stance_time, p[b].gain = gain;
+      for (int k = 0; k < 3; ++k) p[b].vcom_cmd[k] = vcom_cmd[vcom_cmd.size() == 3 ? k : 3 * b + k];
+      p[b].yaw_rate_cmd = yaw_rate_cmd[yaw_rate_cmd.size() == 1 ? 0 : b];
+    }
+    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
+    fresh_ = false;
+  }
+  // init(q) / plan(t, q, v, ..) at the initial state of the context (rtoc_set_initial_state)
+  void init() {
+    chk(rtoc_foot_step_planner_init(ctx_), "rtoc_foot_step_planner_init");
+    fresh_ = false;
+  }
+  bool plan(const double t, const unsigned contact_status, const int planning_steps) {
+    if (contact_status != 0xFu && contact_status != 0x9u && contact_status != 0x6u) return false;   // :203-205
+    chk(rtoc_foot_step_plan(ctx_, t, contact_status, planning_steps), "rtoc_foot_step_plan");
+    fresh_ = false;
+    return true;
+  }
+  // the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365) for every instance
+  void place(const std::vector<int>& phase_of_grid_point) {
+    chk(rtoc_foot_step_place(ctx_, phase_of_grid_point.data(), static_cast<int>(phase_of_grid_point.size())), "rtoc_foot_step_place");
+  }
+  int size() { return get(), size_; }
+  int currentStep() { return get(), current_step_; }
+  // of instance b: [4][3], [3], [9] row-major
+  const double* contactPositions(const int b, const int step) { return get(), &pos_[(static_cast<size_t>(b) * size_ + step) * 12]; }
+  const double* CoM(const int b, const int step) { return get(), &com_[(static_cast<size_t>(b) * size_ + step) * 3]; }
+  const double* R(const int b, const int step) { return get(), &R_[(static_cast<size_t>(b) * size_ + step) * 9]; }
+  const double* stepLength(const int b) { return get(), &sl_[static_cast<size_t>(b) * 3]; }
+  bool ok(const int b) { return get(), ok_[b] != 0; }
+
+ private:
+  bool perInstance(const size_t n, const size_t width, const char* what) const {
+    if (n == width && batch_ > 1) return false;
+    if (n == width * batch_) return true;
+    throw std::invalid_argument(std::string("[TrotFootStepPlanner] ") + what + ": one command for the batch or one per instance");
+  }
+  void get() {
+    if (fresh_) return;
+    const size_t B = batch_, S = RTOC_MAX_PLAN_STEPS + 2;
+    pos_.assign(B * S * 12, 0.0), com_.assign(B * S * 3, 0.0), R_.assign(B * S * 9, 0.0), sl_.assign(B * 3, 0.0), ok_.assign(B, 0);
+    chk(rtoc_foot_step_plan_get(ctx_, pos_.data(), com_.data(), R_.data(), sl_.data(), ok_.data(), batch_, &size_, &current_step_),
+        "rtoc_foot_step_plan_get");
+    fresh_ = true;
+  }
+  static void chk(const int rc, const char* what) {
+    if (rc != RTOC_OK) throw std::runtime_error(std::string(what) + ": " + rtoc_error_string(rc));
+  }
+  rtoc_ctx* ctx_;
+  int batch_, projection_, size_, current_step_;
+  bool fresh_;
+  std::vector<double> pos_, com_, R_, sl_;
+  std::vector<int> ok_;
 };
 
 }  // namespace robotoc

@@ -1,0 +1,117 @@
+"""TrotFootStepPlanner over a capi.Context: the surface of the reference's class (src/mpc/trot_foot_step_planner.cpp) for a batch,
+every instance with its own command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); this shell holds
+no state of its own beyond the commands it was given."""
+import numpy as np
+
+from . import capi
+
+
+class TrotFootStepPlanner:
+    def __init__(self, ctx, projection=capi.PROJECT_AS_REFERENCE):
+        """`ctx`: a capi.Context with a robot model of four point contacts (LF, LH, RF, RH).  `projection`: how init projects the
+        base rotation onto the z axis -- PROJECT_AS_REFERENCE repeats the reference's arithmetic, which divides by
+        R00^2 + 2 R01 and fails near a yaw of 0.427 rad (include/rtoc_robot.h); PROJECT_YAW is the rotation about z"""
+        self.ctx, self.projection = ctx, projection
+        self._plan = None
+
+    def _per_instance(self, name, a, width):
+        a = np.asarray(a, dtype=np.float64)
+        shape = (width,) if width else ()
+        if a.shape == shape:
+            return np.broadcast_to(a, (self.ctx.batch,) + shape), False
+        if a.shape == (self.ctx.batch,) + shape:
+            return a, True
+        raise ValueError("%s must have the shape %s or %s, not %s" % (name, shape, (self.ctx.batch,) + shape, a.shape))
+
+    def _set(self, structs, per_instance):
+        self.ctx.set_foot_step_planner(structs if per_instance else structs[0])
+        self._plan = None
+
+    def set_gait_pattern(self, step_length, step_yaw, enable_stance_phase):
+        """setGaitPattern: step_length [3] or [batch, 3], step_yaw a scalar or [batch]"""
+        sl, inst_l = self._per_instance("step_length", step_length, 3)
+        yaw, inst_y = self._per_instance("step_yaw", step_yaw, 0)
+        structs = []
+        for b in range(self.ctx.batch):
+            p = capi.FootStepPlanner()
+            p.mode, p.projection, p.enable_stance_phase = capi.FOOT_STEP_FIXED, self.projection, int(bool(enable_stance_phase))
+            p.step_length[:], p.step_yaw = [float(x) for x in sl[b]], float(yaw[b])
+            structs.append(p)
+        self._set(structs, inst_l or inst_y)
+
+    def set_raibert_gait_pattern(self, vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain):
+        """setRaibertGaitPattern: vcom_cmd [3] or [batch, 3], yaw_rate_cmd a scalar or [batch]; the gait timing and the gain are
+        shared by the batch"""
+        if swing_time <= 0.0:
+            raise ValueError("'swing_time' must be positive")
+        if stance_time < 0.0:
+            raise ValueError("'stance_time' must be non-negative")
+        if gain <= 0.0:
+            raise ValueError("'gain' must be positive")
+        vc, inst_v = self._per_instance("vcom_cmd", vcom_cmd, 3)
+        yr, inst_y = self._per_instance("yaw_rate_cmd", yaw_rate_cmd, 0)
+        structs = []
+        for b in range(self.ctx.batch):
+            p = capi.FootStepPlanner()
+            p.mode, p.projection = capi.FOOT_STEP_RAIBERT, self.projection
+            p.swing_time, p.stance_time, p.gain = float(swing_time), float(stance_time), float(gain)
+            p.vcom_cmd[:], p.yaw_rate_cmd = [float(x) for x in vc[b]], float(yr[b])
+            structs.append(p)
+        self._set(structs, inst_v or inst_y)
+
+    def init(self, x0=None):
+        """init(q) of every instance; x0 [batch, nq + nv]: set as the context's initial state first (None: as it stands)"""
+        if x0 is not None:
+            self.ctx.set_initial_state(x0)
+        self.ctx.foot_step_planner_init()
+        self._plan = None
+
+    def plan(self, t, contact_status, planning_steps, x0=None):
+        """plan(t, q, v, contact_status, planning_steps) of every instance; contact_status: the bit mask of the active contacts of
+        the first contact phase.  False where the reference returns false (a status that is no trot stance)."""
+        if x0 is not None:
+            self.ctx.set_initial_state(x0)
+        if int(contact_status) not in (0b1111, 0b1001, 0b0110):
+            return False
+        self.ctx.foot_step_plan(t, contact_status, planning_steps)
+        self._plan = None
+        return True
+
+    def _get(self):
+        if self._plan is None:
+            self._plan = self.ctx.foot_step_plan_get()
+        return self._plan
+
+    def size(self):
+        return self._get()["size"]
+
+    def contact_positions(self, step):
+        """[batch, 4, 3]"""
+        return self._get()["positions"][:, step]
+
+    def com(self, step):
+        """[batch, 3]"""
+        return self._get()["com"][:, step]
+
+    def R(self, step):
+        """[batch, 3, 3]"""
+        return self._get()["R"][:, step]
+
+    def step_length(self):
+        """[batch, 3]: the step length in force (with the heuristic: what it planned at the last plan)"""
+        return self._get()["step_length"]
+
+    def ok(self):
+        """[batch] bool: every number of the instance's plan is finite"""
+        return self._get()["ok"]
+
+    def reset_contact_placements(self, t, contact_status, phase_of_grid_point, phase_masks, refs, x0=None):
+        """What MPCTrot::resetContactPlacements does per control tick (src/mpc/mpc_trot.cpp:357-372): plan with planning_steps =
+        the number of contact phases, the placements of every phase into the per-instance table, the three references into their
+        tables.  phase_of_grid_point: GridInfo::phase of every grid point relative to the first; phase_masks: the active contacts
+        of every phase; refs: a capi.FootStepRefs.  Returns what plan returns."""
+        if not self.plan(t, contact_status, len(phase_masks), x0):
+            return False
+        self.ctx.foot_step_place(phase_of_grid_point)
+        self.ctx.foot_step_refs(refs, phase_of_grid_point, phase_masks)
+        return True
