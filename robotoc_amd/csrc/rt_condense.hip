@@ -224,6 +224,7 @@ int rtoc_update(rtoc_ctx* c) {
 static int set_cones(rtoc_ctx* c, int max_contacts, int contact_dim, int rows_per_contact, size_t stride) {
   if (!c || max_contacts < 0) return RTOC_ERR_BAD_ARG;
   if (max_contacts == 0) {
+    if (c->cone_contacts > 0) c->epoch++;   // the cone kernels leave the captured launch sequence
     c->cone_contacts = 0;
     c->cone_rows = 0;
     return RTOC_OK;

@@ -547,6 +547,7 @@ extern "C" int rtoc_debug_profile(rtoc_ctx* c, long long* host_out) {
   if (!c->d_prof.p) {
     HIP_TRY(c->d_prof.reserve(n));
     HIP_TRY(hipMemsetAsync(c->d_prof.p, 0, n * sizeof(long long), c->stream));
+    c->epoch++;   // the condensation, expansion and backward launches carry the pointer: a graph captured before holds nullptr
     return RTOC_OK;
   }
   if (host_out) {
