@@ -118,16 +118,18 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * MovingWindowFilter<2> (include/robotoc/mpc/moving_window_filter.hpp), the placements of every contact phase, and
  * MPCPeriodicSwingFootRef x 4, MPCPeriodicCoMRef, MPCPeriodicConfigurationRef (src/mpc/mpc_periodic_*_ref.cpp).  The plan, the
  * placement table and the reference tables are written on the device and stay there.  The gait wrapper itself (addStep, pop_front,
- * the solve call) stays with the caller: the contact sequence is structure the batch shares.  Not here: the other gaits' planners,
+ * the solve call) stays with the caller: the contact sequence is structure the batch shares.  The crawl, the pace and the flying
+ * trot (MPCCrawl, MPCPace, MPCFlyingTrot: their resetContactPlacements is the trot's line for line) plan through the same entry
+ * points, chosen by rtoc_foot_step_planner::gait -- THE OTHER GAITS below.  Not here:
  * contact surfaces (point contacts have no rotation in the table), grids with switching-time optimisation, ParNMPC horizons (every
  * entry point below refuses one with RTOC_ERR_BAD_ARG).
  *
  * rtoc_set_foot_step_planner: setGaitPattern (mode RTOC_FOOT_STEP_FIXED: step_length, step_yaw, enable_stance_phase) or
  * setRaibertGaitPattern (RTOC_FOOT_STEP_RAIBERT: vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain; enable_stance_phase is
  * stance_time > 0 as in :86 and the member is ignored), p[1] for the batch (per_instance = 0) or p[batch].  step_length, step_yaw,
- * vcom_cmd and yaw_rate_cmd are each instance's own; mode, projection, swing_time, stance_time, gain and enable_stance_phase decide
+ * vcom_cmd and yaw_rate_cmd are each instance's own; gait, mode, projection, swing_time, stance_time, gain and enable_stance_phase decide
  * the step-case sequence, which is shared structure like the grid, and must agree across the instances.  RTOC_ERR_BAD_ARG: they do
- * not; an unknown mode or projection; enable_stance_phase outside {0, 1}; per_instance outside {0, 1}; in Raibert mode the checks of
+ * not; an unknown gait, mode or projection; enable_stance_phase outside {0, 1}; per_instance outside {0, 1}; in Raibert mode the checks of
  * the reference's setters (:63-76, raibert_heuristic.cpp:38-47): swing_time <= 0, stance_time < 0, gain <= 0; a model that has not
  * exactly four contacts, all of them point contacts, in the reference's order LF, LH, RF, RH = contacts 0..3.  RTOC_ERR_NOT_READY
  * without rtoc_set_robot_model.  p = NULL removes the planner with its state and plan (rtoc_foot_step_planner_init again after the next one is set).  A refused call leaves the planner in force.  Setting a planner keeps
@@ -150,6 +152,31 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * [0, RTOC_MAX_PLAN_STEPS], else RTOC_ERR_BAD_ARG.  The plan has planning_steps + 2 steps: contactPositions(step)[4][3], CoM(step)[3],
  * R(step)[9] per instance.  Every instance's planner state (R_.front(), the filter) advances; the host's current_step_ advances by
  * the reference's rules.  RTOC_ERR_NOT_READY without a planner, its init or an initial state.
+ *
+ * THE OTHER GAITS (rtoc_foot_step_planner::gait; line numbers: src/mpc/{pace,crawl,flying_trot}_foot_step_planner.cpp).  Init, the
+ * filter, the heuristic, the plan's layout, place and refs are the trot's.  A contact status is matched exactly against the
+ * gait's own set; any other, another gait's legal ones included, is RTOC_ERR_BAD_ARG and nothing is launched.
+ *   RTOC_GAIT_PACE: the trot with the pairs (LF, LH) = 0b0011 and (RF, RH) = 0b1100.  Statuses 0b1111, 0b0011, 0b1100.  With the
+ *   stance phase 0b0011 is the step with current_step_ % 4 == 1 and 0b1100 the one with % 4 == 3, without it % 2 == 1 and
+ *   % 2 == 0 (:160-201); feet 2 and 3 move first (:216-226).  Raibert period 2 (swing_time + stance_time) (:77).
+ *   RTOC_GAIT_CRAWL: three feet stand.  Statuses 0b1111, 0b0111 (RH swings), 0b1011 (RF), 0b1101 (LH), 0b1110 (LF): the steps with
+ *   current_step_ % 8 == 1, 3, 5, 7 with the stance phase, % 4 == 1, 2, 3, 0 without (:143-253).  The CoM is the sum over the three
+ *   stance feet divided by 3.0, the swing foot is placed at com + R (local - 0.5 step_length).  The loop (:260-359) is incremental:
+ *   a moving foot advances by p += s R step_length and the CoM by c R step_length with s = 1, c = 0.25, except on step == 1 and
+ *   step == 3 (with the stance phase; step == 2 without), where s = 0.5 and c = 0.125 without the heuristic, 0.25 with it.  Those
+ *   two steps are tested on `step` alone, not on current_step_ == 0, as in the reference.  With the stance phase nothing moves or
+ *   turns on even steps.  Raibert period 4 (swing_time + stance_time) (:77); the yaw per step is yaw_rate_cmd (swing_time +
+ *   stance_time).
+ *   RTOC_GAIT_FLYING_TROT: statuses 0b1111 (current_step_ = 0, :140), 0b1001 (advances and turns unless current_step_ % 4 == 1),
+ *   0b0110 (unless % 4 == 3) and 0b0000, the flight (:176-183): current_step_ goes to the next even number without a rotation, the
+ *   CoM is the previous plan's CoM(0) and the footholds are the previous plan's contactPositions(0).  A flight as the first plan
+ *   after rtoc_foot_step_planner_init is RTOC_ERR_BAD_ARG (the reference reads an empty vector there).  Loop (:190-230): nothing
+ *   moves on step == 0, on current_step_ == 0 && step == 1, or on odd step % 4; current_step_ == 0 && step == 2 moves feet 1 and 2
+ *   with the first-step scale (0.5 with the heuristic, 0.25 without); % 4 == 2 moves feet 1 and 2, % 4 == 0 feet 0 and 3, placed
+ *   absolutely as in the trot.  :231-233 push one more copy of the last step: the plan has planning_steps + 3 steps, and
+ *   planning_steps is limited to [0, RTOC_MAX_PLAN_STEPS - 1] so that it fits the arrays of rtoc_foot_step_plan_get.  There is no
+ *   stance-phase option (enable_stance_phase is ignored).  In Raibert mode swing_time carries flying_time and stance_time <= 0 is
+ *   refused by rtoc_set_foot_step_planner (:66); period 2 (flying_time + stance_time).
  *
  * rtoc_foot_step_plan_get: the plan of the first count <= batch instances -- positions[count][size][4][3], com[count][size][3],
  * R[count][size][9] (row-major), step_length[count][3] (the length in force; Raibert mode: what the heuristic planned),
@@ -193,12 +220,16 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
 #define RTOC_FOOT_STEP_RAIBERT 1        /* TrotFootStepPlanner::setRaibertGaitPattern */
 #define RTOC_PROJECT_AS_REFERENCE 0     /* BASE-ROTATION PROJECTION above             */
 #define RTOC_PROJECT_YAW 1
+#define RTOC_GAIT_TROT 0                /* TrotFootStepPlanner                        */
+#define RTOC_GAIT_CRAWL 1               /* CrawlFootStepPlanner                       */
+#define RTOC_GAIT_PACE 2                /* PaceFootStepPlanner                        */
+#define RTOC_GAIT_FLYING_TROT 3         /* FlyingTrotFootStepPlanner                  */
 typedef struct rtoc_foot_step_planner {
   int mode;                    /* RTOC_FOOT_STEP_*                                                       */
   int projection;              /* RTOC_PROJECT_*: the reference's ProjectRotationMatrix divides by R00^2 + 2 R01, which is
                                 * NOT the row's norm and crosses zero at a yaw of 0.427 rad (see above); 0 keeps it */
-  int enable_stance_phase;     /* fixed mode                                                             */
-  int pad;
+  int enable_stance_phase;     /* fixed mode (ignored by the flying trot)                                */
+  int gait;                    /* RTOC_GAIT_*: 0, the value of a zeroed struct, is the trot              */
   double swing_time, stance_time, gain;   /* Raibert mode (gait timing; shared by the batch)             */
   double step_length[3], step_yaw;        /* fixed mode, per instance                                    */
   double vcom_cmd[3], yaw_rate_cmd;       /* Raibert mode, per instance                                  */

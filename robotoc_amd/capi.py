@@ -52,11 +52,12 @@ LINE_SEARCH_FILTER_CAPACITY = 32  # RTOC_LINE_SEARCH_FILTER_CAPACITY
 MAX_PLAN_STEPS = 32  # RTOC_MAX_PLAN_STEPS
 FOOT_STEP_FIXED, FOOT_STEP_RAIBERT = 0, 1  # RTOC_FOOT_STEP_*
 PROJECT_AS_REFERENCE, PROJECT_YAW = 0, 1  # RTOC_PROJECT_*
+GAIT_TROT, GAIT_CRAWL, GAIT_PACE, GAIT_FLYING_TROT = 0, 1, 2, 3  # RTOC_GAIT_*
 
 
 class FootStepPlanner(C.Structure):
     """include/rtoc_robot.h rtoc_foot_step_planner"""
-    _fields_ = [("mode", C.c_int), ("projection", C.c_int), ("enable_stance_phase", C.c_int), ("pad", C.c_int),
+    _fields_ = [("mode", C.c_int), ("projection", C.c_int), ("enable_stance_phase", C.c_int), ("gait", C.c_int),
                 ("swing_time", C.c_double), ("stance_time", C.c_double), ("gain", C.c_double),
                 ("step_length", C.c_double * 3), ("step_yaw", C.c_double), ("vcom_cmd", C.c_double * 3), ("yaw_rate_cmd", C.c_double)]
 
@@ -713,12 +714,12 @@ class Context:
         _chk(lib().rtoc_set_foot_step_planner(self._h, C.cast(arr, C.c_void_p), 1 if per_instance else 0))
 
     def foot_step_planner_init(self):
-        """rtoc_foot_step_planner_init: TrotFootStepPlanner::init at the q of set_initial_state, every instance"""
+        """rtoc_foot_step_planner_init: the planner's init (the same in all four gaits) at the q of set_initial_state, every instance"""
         _chk(lib().rtoc_foot_step_planner_init(self._h))
 
     def foot_step_plan(self, t, contact_status0, planning_steps):
-        """rtoc_foot_step_plan: TrotFootStepPlanner::plan from the q, v of set_initial_state; contact_status0 = the bit mask of the
-        contacts active in the first phase"""
+        """rtoc_foot_step_plan: plan() of the planner's gait (FootStepPlanner.gait, GAIT_*) from the q, v of set_initial_state;
+        contact_status0 = the bit mask of the contacts active in the first phase"""
         _chk(lib().rtoc_foot_step_plan(self._h, float(t), int(contact_status0), int(planning_steps)))
 
     def foot_step_plan_get(self):

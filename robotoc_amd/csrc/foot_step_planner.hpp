@@ -2,7 +2,8 @@
 // (src/mpc/raibert_heuristic.cpp) and MovingWindowFilter<2> (include/robotoc/mpc/moving_window_filter.hpp), and what
 // MPCTrot::resetContactPlacements (src/mpc/mpc_trot.cpp:357-372) does with the plan -- the placements of every contact phase,
 // MPCPeriodicSwingFootRef x 4, MPCPeriodicCoMRef, MPCPeriodicConfigurationRef -- for every instance of a batch, each with its own
-// command.  Nothing here leaves the device: the plan is read by the two kernels behind it, which write the per-instance table of
+// command; and the plan recurrences of PaceFootStepPlanner, CrawlFootStepPlanner and FlyingTrotFootStepPlanner
+// (src/mpc/{pace,crawl,flying_trot}_foot_step_planner.cpp), whose MPC shells build the same references.  Nothing here leaves the device: the plan is read by the two kernels behind it, which write the per-instance table of
 // contact placements and the per-instance reference tables where the cost kernels read them.
 //
 // foot_step_init_kernel / foot_step_plan_kernel.  Mapping: one lane per (instance, foot), FOOT-MAJOR within the wave -- lane l is
@@ -11,7 +12,10 @@
 // gathered across the four 16-lane groups by __shfl and added in the reference's order; R <- R_yaw R and the centre of mass are
 // held redundantly by the four lanes of an instance.  The recurrence over the steps is serial per instance and its case chain
 // (:145-277) depends on current_step_ and the contact status alone, which the batch shares: the host decides it once and passes
-// it in as arguments (FsPlanArgs::stance / pre_rotate / move[] / first_at), so no lane branches on its own data.  No LDS, no atomics.
+// it in as arguments (FsPlanArgs::stance / pre_rotate / move[] / com_scale[] / foot_scale[]), so no lane branches on its own data.
+// No LDS, no atomics.  The same kernel plans the pace (other pairs), the crawl (three stance feet, feet advanced incrementally:
+// FsPlanArgs::incremental) and the flying trot (a flight phase, FsPlanArgs::flight: foot and CoM come from step 0 of the previous
+// plan, 6 more doubles per lane loaded ahead of every store, in runs of 16 like the rest); both flags are wave-uniform.
 // Loads: 24 doubles of state, at most 12 x 3 of the filter ring, 3 of the foot position, 8 of the command per lane, each a run
 // of 16 consecutive doubles per foot group.  Stores: per step every lane writes its foot's position (3) and a quarter of
 // [CoM | R] (3), again 16 consecutive doubles per group and slot; the lanes of foot 0 write the planner state back.
@@ -78,13 +82,16 @@ struct FsPlanArgs {
   int raibert;           // 1: the filter and the heuristic run first
   double t;              // Raibert mode: the sampling time, time_length = period, min_sampling_period = 0.1 period, gain
   double period, min_period, gain;
-  // the case chain of :145-277 as the host resolved it
-  unsigned stance;       // feet on the ground now: 0b1111, 0b1001 or 0b0110
-  int pre_rotate;        // 1: R = R_yaw R ahead of the stance centre of mass (:165, :171, :186, :192)
-  int nloop;             // planning_steps + 1 passes of the loop
-  int first_at;          // the pass that is the first step of all (current_step_ == 0 && step == 1), or -1
-  double first_scale;    // ... and its share of step_length_: 0.5 with the heuristic, 0.25 without (:219-224)
-  unsigned char move[RTOC_MAX_PLAN_STEPS + 4];   // per pass: the feet that step (0b0110, 0b1001) or 0 (nothing moves, nothing turns)
+  // the case chain of the gait's plan() as the host resolved it (trot :145-277; plan_cases in rt_foot_steps.hip walks the gait's table)
+  unsigned stance;       // feet on the ground now: two of a trot or pace, three of a crawl, all four, or none (flight)
+  int pre_rotate;        // 1: R = R_yaw R ahead of the stance centre of mass (trot :165, :171, :186, :192)
+  int nloop;             // passes of the loop: planning_steps + 1 (the flying trot: one more, which repeats the last step, :231-233)
+  int incremental;       // 1: a stepping foot advances from where it is, p += foot_scale R step_length (the crawl); 0: p = com + R local
+  int flight;            // 1: nothing on the ground (the flying trot, :176-183): the CoM and the footholds are step 0 of the previous plan
+  unsigned char move[RTOC_MAX_PLAN_STEPS + 4];   // per pass: the feet that step, or 0 (nothing moves, nothing turns)
+  double com_scale[RTOC_MAX_PLAN_STEPS + 4];     // per pass: the CoM's share of step_length_ (trot: 0.5; on the first step of all 0.5 with
+                                                 // the heuristic, 0.25 without, :219-224)
+  double foot_scale[RTOC_MAX_PLAN_STEPS + 4];    // per pass, incremental alone: the stepping foot's share (crawl: 1, 0.5 on its two first steps)
 };
 
 static __device__ __forceinline__ rbd::M3 fs_yaw_times(double s, double c, const rbd::M3& R) {
@@ -141,7 +148,8 @@ static __global__ __launch_bounds__(64) void foot_step_init_kernel(FsInitArgs a)
   for (int k = f; k < a.nq; k += 4) a.q0[(size_t)b * a.nq + k] = q[k];
 }
 
-// TrotFootStepPlanner::plan (:125-284)
+// TrotFootStepPlanner::plan (:125-284), and with other arguments PaceFootStepPlanner::plan (:124-283), CrawlFootStepPlanner::plan
+// (:123-366) and FlyingTrotFootStepPlanner::plan (:118-240): the filter, the heuristic, the stance sum and the stores are shared
 static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a) {
   using namespace rbd;
   const int lane = threadIdx.x, f = lane >> 4, B = a.batch;
@@ -189,10 +197,15 @@ static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a)
     sl = mk(a.period * f_ax + pg * (cmd[(size_t)FS_CMD_VCOM * B] - f_ax), a.period * f_ay + pg * (cmd[(size_t)(FS_CMD_VCOM + 1) * B] - f_ay), 0.0);
   }
   V3 p = ldv3(a.feet + (size_t)b * 12 + 3 * f);
-  // ---- the feet on the ground fix the centre of mass (:145-202) ----
-  if (a.pre_rotate) R = fs_yaw_times(sy, cy, R);
   V3 com = mk(0, 0, 0);
-  {
+  if (a.flight) {
+    // ---- nothing on the ground: carried over from step 0 of the previous plan, loaded ahead of every store of this call ----
+    const double* const s0 = a.plan + b;
+    p = mk(s0[(size_t)(FS_PLAN_POS + 3 * f) * B], s0[(size_t)(FS_PLAN_POS + 3 * f + 1) * B], s0[(size_t)(FS_PLAN_POS + 3 * f + 2) * B]);
+    com = mk(s0[(size_t)FS_PLAN_COM * B], s0[(size_t)(FS_PLAN_COM + 1) * B], s0[(size_t)(FS_PLAN_COM + 2) * B]);
+  } else {
+    // ---- the feet on the ground fix the centre of mass (:145-202) ----
+    if (a.pre_rotate) R = fs_yaw_times(sy, cy, R);
     const V3 r = mul(R, local);
     int n = 0;
 #pragma unroll
@@ -224,8 +237,9 @@ static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a)
     const unsigned mv = a.move[s];
     if (mv) {
       R = fs_yaw_times(sy, cy, R);
-      com = com + (s == a.first_at ? a.first_scale : 0.5) * mul(R, sl);
-      if ((mv >> f) & 1u) p = com + mul(R, local);
+      const V3 d = mul(R, sl);
+      com = com + a.com_scale[s] * d;
+      if ((mv >> f) & 1u) p = a.incremental ? p + a.foot_scale[s] * d : com + mul(R, local);
     }
     if (valid) fs_store_step(a.plan, s + 1, B, b, f, p, com, R);
   }

@@ -1,4 +1,4 @@
-// rt_foot_steps.hip -- TrotFootStepPlanner and the MPC references of every instance on the device: planner and commands, init,
+// rt_foot_steps.hip -- the foot-step planners (trot, crawl, pace, flying trot) and the MPC references of every instance on the device: planner and commands, init,
 // plan, the read-back of the plan, the placements of every contact phase, the three periodic references (foot_step_planner.hpp).
 #include <cmath>
 
@@ -24,20 +24,51 @@ static bool four_point_feet(const rtoc_ctx* c) {
 // setGaitPattern has no checks; setRaibertGaitPattern: trot_foot_step_planner.cpp:68-76 (the period of raibert_heuristic.cpp:39 is
 // positive with them, its gain check is the same one)
 static bool planner_valid(const rtoc_foot_step_planner& p) {
+  if (p.gait < RTOC_GAIT_TROT || p.gait > RTOC_GAIT_FLYING_TROT) return false;
   if (p.mode != RTOC_FOOT_STEP_FIXED && p.mode != RTOC_FOOT_STEP_RAIBERT) return false;
   if (p.projection != RTOC_PROJECT_AS_REFERENCE && p.projection != RTOC_PROJECT_YAW) return false;
   if (p.enable_stance_phase != 0 && p.enable_stance_phase != 1) return false;
   if (p.mode == RTOC_FOOT_STEP_RAIBERT && (!(p.swing_time > 0.0) || !(p.stance_time >= 0.0) || !(p.gain > 0.0))) return false;
+  // flying_trot_foot_step_planner.cpp:66: the flying trot has no gait without a stance
+  if (p.gait == RTOC_GAIT_FLYING_TROT && p.mode == RTOC_FOOT_STEP_RAIBERT && !(p.stance_time > 0.0)) return false;
   return true;
 }
 // what decides the step-case sequence: shared structure, like the grid
 static bool same_structure(const rtoc_foot_step_planner& a, const rtoc_foot_step_planner& b) {
-  return a.mode == b.mode && a.projection == b.projection && a.enable_stance_phase == b.enable_stance_phase && a.swing_time == b.swing_time &&
-         a.stance_time == b.stance_time && a.gain == b.gain;
+  return a.gait == b.gait && a.mode == b.mode && a.projection == b.projection && a.enable_stance_phase == b.enable_stance_phase &&
+         a.swing_time == b.swing_time && a.stance_time == b.stance_time && a.gain == b.gain;
 }
 static bool stance_phase_enabled(const rtoc_foot_step_planner& p) {
+  if (p.gait == RTOC_GAIT_FLYING_TROT) return false;   // no such option: one step sequence (flying_trot_foot_step_planner.cpp:190-230)
   return p.mode == RTOC_FOOT_STEP_RAIBERT ? p.stance_time > 0.0 : p.enable_stance_phase != 0;   // :58, :86
 }
+
+// What tells the four gaits' plan() apart, by RTOC_GAIT_*.  Index [0]: without the stance phase, [1]: with it.
+struct GaitSwing {
+  unsigned status;   // a contact status with feet in the air ...
+  int at[2];         // ... is the step with current_step_ % cycle == at: otherwise current_step_ advances and R turns
+};
+struct GaitRules {
+  int cycle[2];                // the steps repeat with this period
+  unsigned char move[2][8];    // the feet that step at step % cycle (0: nothing moves, nothing turns)
+  GaitSwing swing[4];
+  int nswing;
+  int flight;                  // 1: 0b0000 is a status (current_step_ to the next even number, no rotation)
+  int incremental;             // 1: feet advance from where they are
+  double com_scale;            // the CoM's share of step_length_ per moving step
+  double periods;              // the Raibert period in units of swing_time + stance_time
+};
+static const GaitRules GAITS[4] = {
+    // trot (trot_foot_step_planner.cpp:161-202, :212-277): LH + RF first
+    {{2, 4}, {{0b1001, 0b0110}, {0, 0b0110, 0, 0b1001}}, {{0b1001u, {1, 1}}, {0b0110u, {0, 3}}}, 2, 0, 0, 0.5, 2.0},
+    // crawl (crawl_foot_step_planner.cpp:159-250, :260-359): RH, RF, LH, LF
+    {{4, 8}, {{0b0001, 0b1000, 0b0100, 0b0010}, {0, 0b1000, 0, 0b0100, 0, 0b0010, 0, 0b0001}},
+     {{0b0111u, {1, 1}}, {0b1011u, {2, 3}}, {0b1101u, {3, 5}}, {0b1110u, {0, 7}}}, 4, 0, 1, 0.25, 4.0},
+    // pace (pace_foot_step_planner.cpp:160-201, :211-276): RF + RH first
+    {{2, 4}, {{0b0011, 0b1100}, {0, 0b1100, 0, 0b0011}}, {{0b0011u, {1, 1}}, {0b1100u, {0, 3}}}, 2, 0, 0, 0.5, 2.0},
+    // flying trot (flying_trot_foot_step_planner.cpp:148-183, :190-230): a flight on every odd step
+    {{4, 4}, {{0b1001, 0, 0b0110, 0}, {0b1001, 0, 0b0110, 0}}, {{0b1001u, {1, 1}}, {0b0110u, {3, 3}}}, 2, 1, 0, 0.5, 2.0},
+};
 
 int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int per_instance) {
   CHECK_NO_PARNMPC(c);
@@ -98,33 +129,50 @@ int rtoc_foot_step_planner_init(rtoc_ctx* c) {
 
 // The case chain of plan() (:145-277): current_step_ and the contact status are shared by the batch, so the host walks it once.
 // false: a contact status the reference answers with `return false`
-static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int planning_steps, int* current_step, FsPlanArgs* a) {
-  const bool stance = stance_phase_enabled(p);
+// The gait's rules are a table walk (GAITS); what is left to code are the first steps of all, which every gait scales its own way.
+// false: a contact status the reference answers with `return false`, or a flight with no plan behind it
+static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int planning_steps, bool has_plan, int* current_step, FsPlanArgs* a) {
+  const GaitRules& g = GAITS[p.gait];
+  const int sp = stance_phase_enabled(p) ? 1 : 0;
+  const bool raibert = p.mode == RTOC_FOOT_STEP_RAIBERT;
   int cur = *current_step;
-  a->stance = status, a->pre_rotate = 0;
+  a->stance = status, a->pre_rotate = 0, a->flight = 0, a->incremental = g.incremental;
   if (status == 0b1111u) {
-    if (stance) {
+    if (sp) {
       if (cur % 2 != 0) ++cur;
     } else {
       cur = 0;
     }
-  } else if (status == 0b1001u) {
-    if (stance ? cur % 4 != 1 : cur % 2 != 1) ++cur, a->pre_rotate = 1;
-  } else if (status == 0b0110u) {
-    if (stance ? cur % 4 != 3 : cur % 2 != 0) ++cur, a->pre_rotate = 1;
+  } else if (status == 0u && g.flight) {
+    if (!has_plan) return false;   // contact_position_ref_[0] of a planner that has not planned (flying_trot_foot_step_planner.cpp:181)
+    if (cur % 2 != 0) ++cur;
+    a->flight = 1;
   } else {
-    return false;
+    int k = 0;
+    while (k < g.nswing && g.swing[k].status != status) ++k;
+    if (k == g.nswing) return false;
+    if (cur % g.cycle[sp] != g.swing[k].at[sp]) ++cur, a->pre_rotate = 1;
   }
-  a->nloop = planning_steps + 1, a->first_at = -1;
-  a->first_scale = p.mode == RTOC_FOOT_STEP_RAIBERT ? 0.5 : 0.25;   // :219-224
+  a->nloop = planning_steps + 1;
   for (int s = 0; s <= planning_steps; ++s) {
     const int step = cur + s;
-    unsigned char mv = 0;
-    if (step == 0) mv = 0;
-    else if (cur == 0 && step == 1) mv = 0b0110, a->first_at = s;
-    else if (stance) mv = step % 4 == 1 ? 0b0110 : step % 4 == 3 ? 0b1001 : 0;
-    else mv = step % 2 == 1 ? 0b0110 : 0b1001;
-    a->move[s] = mv;
+    const unsigned char mv = step == 0 ? 0 : g.move[sp][step % g.cycle[sp]];
+    double cs = g.com_scale, fs = 1.0;
+    if (p.gait == RTOC_GAIT_CRAWL) {
+      // crawl_foot_step_planner.cpp:265-284, :315-334: tested on `step` alone
+      if (step == 1 || step == (sp ? 3 : 2)) cs = raibert ? 0.25 : 0.125, fs = 0.5;
+    } else if (p.gait == RTOC_GAIT_FLYING_TROT) {
+      // flying_trot_foot_step_planner.cpp:194-207: the first flight moves nothing (as every odd step), the step behind it is the first of all
+      if (cur == 0 && step == 2) cs = raibert ? 0.5 : 0.25;
+    } else if (cur == 0 && step == 1) {
+      cs = raibert ? 0.5 : 0.25;   // trot_foot_step_planner.cpp:217-227, pace_foot_step_planner.cpp:216-226
+    }
+    a->move[s] = mv, a->com_scale[s] = cs, a->foot_scale[s] = fs;
+  }
+  if (p.gait == RTOC_GAIT_FLYING_TROT) {
+    // flying_trot_foot_step_planner.cpp:231-233: the last step once more
+    a->move[a->nloop] = 0, a->com_scale[a->nloop] = 0.0, a->foot_scale[a->nloop] = 0.0;
+    ++a->nloop;
   }
   *current_step = cur;
   return true;
@@ -133,10 +181,11 @@ static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int pla
 int rtoc_foot_step_plan(rtoc_ctx* c, double t, unsigned contact_status0, int planning_steps) {
   CHECK_READY(c);
   if (!c->fs_on || !c->fs_init || !c->h_model || !c->d_x0.p || !c->d_fs_state.p || !c->d_fs_plan.p || !c->d_fs_cmd.p) return RTOC_ERR_NOT_READY;
-  if (planning_steps < 0 || planning_steps > RTOC_MAX_PLAN_STEPS || !std::isfinite(t)) return RTOC_ERR_BAD_ARG;
+  const bool flying = c->fs_shared.gait == RTOC_GAIT_FLYING_TROT;   // its plan is one step longer
+  if (planning_steps < 0 || planning_steps > RTOC_MAX_PLAN_STEPS - (flying ? 1 : 0) || !std::isfinite(t)) return RTOC_ERR_BAD_ARG;
   FsPlanArgs a{};
   int cur = c->fs_current_step;
-  if (!plan_cases(c->fs_shared, contact_status0, planning_steps, &cur, &a)) return RTOC_ERR_BAD_ARG;
+  if (!plan_cases(c->fs_shared, contact_status0, planning_steps, c->fs_size > 0, &cur, &a)) return RTOC_ERR_BAD_ARG;
   const int B = c->batch;
   HIP_TRY(c->d_fs_fk.reserve((size_t)B * 15));   // scratch: a clone starts without it
   int rc = launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
@@ -145,11 +194,11 @@ int rtoc_foot_step_plan(rtoc_ctx* c, double t, unsigned contact_status0, int pla
   a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
   a.raibert = c->fs_shared.mode == RTOC_FOOT_STEP_RAIBERT;
   a.t = t;
-  a.period = 2.0 * (c->fs_shared.swing_time + c->fs_shared.stance_time);   // :77-79
+  a.period = GAITS[c->fs_shared.gait].periods * (c->fs_shared.swing_time + c->fs_shared.stance_time);   // :77-79 (of every gait)
   a.min_period = 0.1 * a.period, a.gain = c->fs_shared.gain;
   hipLaunchKernelGGL(foot_step_plan_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  c->fs_current_step = cur, c->fs_size = planning_steps + 2;
+  c->fs_current_step = cur, c->fs_size = a.nloop + 1;
   return RTOC_OK;
 }
 

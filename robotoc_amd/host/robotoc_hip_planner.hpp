@@ -19,6 +19,7 @@
 #include <cmath>
 #include <limits>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "robotoc_hip.hpp"
@@ -503,55 +504,25 @@ class SolutionInterpolator {
   bool has_ = false;
 };
 
-// robotoc::TrotFootStepPlanner (src/mpc/trot_foot_step_planner.cpp) for the batch of a context: a thin mirror over
+// robotoc::TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner
+// (src/mpc/{trot,crawl,pace,flying_trot}_foot_step_planner.cpp) for the batch of a context: thin mirrors over
 // rtoc_set_foot_step_planner / rtoc_foot_step_planner_init / rtoc_foot_step_plan / rtoc_foot_step_plan_get (include/rtoc_robot.h).
 // The planning runs on the device from the q, v of rtoc_set_initial_state; commands are one for the batch or one per instance.
-class TrotFootStepPlanner {
+// FootStepPlannerBase is what the four share; a gait's class names its RTOC_GAIT_*, its legal contact statuses and its setters.
+class FootStepPlannerBase {
  public:
-  TrotFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
-      : ctx_(ctx), batch_(batch), projection_(projection), size_(0), current_step_(0), fresh_(false) {
-    if (!ctx || batch < 1) throw std::invalid_argument("[TrotFootStepPlanner] a context and its batch size");
-  }
-  // step_length: 3 doubles for the batch or 3 per instance; step_yaw: one or one per instance
-  void setGaitPattern(const std::vector<double>& step_length, const std::vector<double>& step_yaw, const bool enable_stance_phase) {
-    const bool inst = perInstance(step_length.size(), 3, "step_length") | perInstance(step_yaw.size(), 1, "step_yaw");
-    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
-    for (size_t b = 0; b < p.size(); ++b) {
-      p[b].mode = RTOC_FOOT_STEP_FIXED, p[b].projection = projection_, p[b].enable_stance_phase = enable_stance_phase ? 1 : 0;
-      for (int k = 0; k < 3; ++k) p[b].step_length[k] = step_length[step_length.size() == 3 ? k : 3 * b + k];
-      p[b].step_yaw = step_yaw[step_yaw.size() == 1 ? 0 : b];
-    }
-    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
-    fresh_ = false;
-  }
-  void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double swing_time,
-                             const double stance_time, const double gain) {
-    if (swing_time <= 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'swing_time' must be positive!");
-    if (stance_time < 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'stance_time' must be non-negative!");
-    if (gain <= 0.0) throw std::out_of_range("[TrotFootStepPlanner] invalid argument: 'gain' must be positive!");
-    const bool inst = perInstance(vcom_cmd.size(), 3, "vcom_cmd") | perInstance(yaw_rate_cmd.size(), 1, "yaw_rate_cmd");
-    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
-    for (size_t b = 0; b < p.size(); ++b) {
-      p[b].mode = RTOC_FOOT_STEP_RAIBERT, p[b].projection = projection_;
-      p[b].swing_time = swing_time, p[b].stance_time = stance_time, p[b].gain = gain;
-      for (int k = 0; k < 3; ++k) p[b].vcom_cmd[k] = vcom_cmd[vcom_cmd.size() == 3 ? k : 3 * b + k];
-      p[b].yaw_rate_cmd = yaw_rate_cmd[yaw_rate_cmd.size() == 1 ? 0 : b];
-    }
-    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
-    fresh_ = false;
-  }
   // init(q) / plan(t, q, v, ..) at the initial state of the context (rtoc_set_initial_state)
   void init() {
     chk(rtoc_foot_step_planner_init(ctx_), "rtoc_foot_step_planner_init");
     fresh_ = false;
   }
   bool plan(const double t, const unsigned contact_status, const int planning_steps) {
-    if (contact_status != 0xFu && contact_status != 0x9u && contact_status != 0x6u) return false;   // :203-205
+    if (std::find(statuses_.begin(), statuses_.end(), contact_status) == statuses_.end()) return false;   // the reference's `return false`
     chk(rtoc_foot_step_plan(ctx_, t, contact_status, planning_steps), "rtoc_foot_step_plan");
     fresh_ = false;
     return true;
   }
-  // the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365) for every instance
+  // the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365; the same in MPCCrawl, MPCPace, MPCFlyingTrot) for every instance
   void place(const std::vector<int>& phase_of_grid_point) {
     chk(rtoc_foot_step_place(ctx_, phase_of_grid_point.data(), static_cast<int>(phase_of_grid_point.size())), "rtoc_foot_step_place");
   }
@@ -564,11 +535,51 @@ class TrotFootStepPlanner {
   const double* stepLength(const int b) { return get(), &sl_[static_cast<size_t>(b) * 3]; }
   bool ok(const int b) { return get(), ok_[b] != 0; }
 
+ protected:
+  FootStepPlannerBase(rtoc_ctx* ctx, const int batch, const int projection, const int gait, const char* name,
+                      const std::vector<unsigned>& statuses)
+      : ctx_(ctx), batch_(batch), projection_(projection), gait_(gait), size_(0), current_step_(0), fresh_(false),
+        tag_(std::string("[") + name + "]"), statuses_(statuses) {
+    if (!ctx || batch < 1) throw std::invalid_argument(tag_ + " a context and its batch size");
+  }
+  // step_length: 3 doubles for the batch or 3 per instance; step_yaw: one or one per instance
+  void setFixed(const std::vector<double>& step_length, const std::vector<double>& step_yaw, const bool enable_stance_phase) {
+    const bool inst = perInstance(step_length.size(), 3, "step_length") | perInstance(step_yaw.size(), 1, "step_yaw");
+    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
+    for (size_t b = 0; b < p.size(); ++b) {
+      p[b].gait = gait_;
+      p[b].mode = RTOC_FOOT_STEP_FIXED, p[b].projection = projection_, p[b].enable_stance_phase = enable_stance_phase ? 1 : 0;
+      for (int k = 0; k < 3; ++k) p[b].step_length[k] = step_length[step_length.size() == 3 ? k : 3 * b + k];
+      p[b].step_yaw = step_yaw[step_yaw.size() == 1 ? 0 : b];
+    }
+    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
+    fresh_ = false;
+  }
+  // air_name: what the gait calls the time in the air; stance_may_be_zero: the trot's check (:71) or the flying trot's (:66)
+  void setRaibert(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double air_time, const char* air_name,
+                  const double stance_time, const bool stance_may_be_zero, const double gain) {
+    if (air_time <= 0.0) throw std::out_of_range(tag_ + " invalid argument: '" + air_name + "' must be positive!");
+    if (stance_may_be_zero && stance_time < 0.0) throw std::out_of_range(tag_ + " invalid argument: 'stance_time' must be non-negative!");
+    if (!stance_may_be_zero && stance_time <= 0.0) throw std::out_of_range(tag_ + " invalid argument: 'stance_time' must be positive!");
+    if (gain <= 0.0) throw std::out_of_range(tag_ + " invalid argument: 'gain' must be positive!");
+    const bool inst = perInstance(vcom_cmd.size(), 3, "vcom_cmd") | perInstance(yaw_rate_cmd.size(), 1, "yaw_rate_cmd");
+    std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
+    for (size_t b = 0; b < p.size(); ++b) {
+      p[b].gait = gait_;
+      p[b].mode = RTOC_FOOT_STEP_RAIBERT, p[b].projection = projection_;
+      p[b].swing_time = air_time, p[b].stance_time = stance_time, p[b].gain = gain;
+      for (int k = 0; k < 3; ++k) p[b].vcom_cmd[k] = vcom_cmd[vcom_cmd.size() == 3 ? k : 3 * b + k];
+      p[b].yaw_rate_cmd = yaw_rate_cmd[yaw_rate_cmd.size() == 1 ? 0 : b];
+    }
+    chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
+    fresh_ = false;
+  }
+
  private:
   bool perInstance(const size_t n, const size_t width, const char* what) const {
     if (n == width && batch_ > 1) return false;
     if (n == width * batch_) return true;
-    throw std::invalid_argument(std::string("[TrotFootStepPlanner] ") + what + ": one command for the batch or one per instance");
+    throw std::invalid_argument(tag_ + " " + what + ": one command for the batch or one per instance");
   }
   void get() {
     if (fresh_) return;
@@ -582,10 +593,54 @@ class TrotFootStepPlanner {
     if (rc != RTOC_OK) throw std::runtime_error(std::string(what) + ": " + rtoc_error_string(rc));
   }
   rtoc_ctx* ctx_;
-  int batch_, projection_, size_, current_step_;
+  int batch_, projection_, gait_, size_, current_step_;
   bool fresh_;
+  std::string tag_;
+  std::vector<unsigned> statuses_;
   std::vector<double> pos_, com_, R_, sl_;
   std::vector<int> ok_;
+};
+
+// the gaits whose setters are the trot's (trot_foot_step_planner.cpp:51-88): trot, crawl, pace
+class StancePhaseFootStepPlanner : public FootStepPlannerBase {
+ public:
+  void setGaitPattern(const std::vector<double>& step_length, const std::vector<double>& step_yaw, const bool enable_stance_phase) {
+    setFixed(step_length, step_yaw, enable_stance_phase);
+  }
+  void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double swing_time,
+                             const double stance_time, const double gain) {
+    setRaibert(vcom_cmd, yaw_rate_cmd, swing_time, "swing_time", stance_time, true, gain);
+  }
+
+ protected:
+  using FootStepPlannerBase::FootStepPlannerBase;
+};
+class TrotFootStepPlanner : public StancePhaseFootStepPlanner {
+ public:
+  TrotFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : StancePhaseFootStepPlanner(ctx, batch, projection, RTOC_GAIT_TROT, "TrotFootStepPlanner", {0xFu, 0x9u, 0x6u}) {}
+};
+class CrawlFootStepPlanner : public StancePhaseFootStepPlanner {
+ public:
+  CrawlFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : StancePhaseFootStepPlanner(ctx, batch, projection, RTOC_GAIT_CRAWL, "CrawlFootStepPlanner", {0xFu, 0x7u, 0xBu, 0xDu, 0xEu}) {}
+};
+class PaceFootStepPlanner : public StancePhaseFootStepPlanner {
+ public:
+  PaceFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : StancePhaseFootStepPlanner(ctx, batch, projection, RTOC_GAIT_PACE, "PaceFootStepPlanner", {0xFu, 0x3u, 0xCu}) {}
+};
+// flying_trot_foot_step_planner.cpp:50-82: no stance-phase option; a flight (contact status 0) between the pairs; the plan has
+// planning_steps + 3 steps, planning_steps at most RTOC_MAX_PLAN_STEPS - 1
+class FlyingTrotFootStepPlanner : public FootStepPlannerBase {
+ public:
+  FlyingTrotFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : FootStepPlannerBase(ctx, batch, projection, RTOC_GAIT_FLYING_TROT, "FlyingTrotFootStepPlanner", {0xFu, 0x9u, 0x6u, 0x0u}) {}
+  void setGaitPattern(const std::vector<double>& step_length, const std::vector<double>& step_yaw) { setFixed(step_length, step_yaw, false); }
+  void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double flying_time,
+                             const double stance_time, const double gain) {
+    setRaibert(vcom_cmd, yaw_rate_cmd, flying_time, "flying_time", stance_time, false, gain);
+  }
 };
 
 }  // namespace robotoc

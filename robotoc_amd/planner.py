@@ -1,12 +1,17 @@
-"""TrotFootStepPlanner over a capi.Context: the surface of the reference's class (src/mpc/trot_foot_step_planner.cpp) for a batch,
-every instance with its own command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); this shell holds
-no state of its own beyond the commands it was given."""
+"""TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner and FlyingTrotFootStepPlanner over a capi.Context: the surface
+of the reference's classes (src/mpc/{trot,crawl,pace,flying_trot}_foot_step_planner.cpp) for a batch, every instance with its own
+command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); these shells hold no state of their own beyond
+the commands they were given.  The four share one body; a class names its gait, its legal contact statuses and what its setters
+check."""
 import numpy as np
 
 from . import capi
 
 
 class TrotFootStepPlanner:
+    GAIT = capi.GAIT_TROT
+    STATUSES = (0b1111, 0b1001, 0b0110)   # the contact statuses plan() accepts; the reference returns false for any other
+
     def __init__(self, ctx, projection=capi.PROJECT_AS_REFERENCE):
         """`ctx`: a capi.Context with a robot model of four point contacts (LF, LH, RF, RH).  `projection`: how init projects the
         base rotation onto the z axis -- PROJECT_AS_REFERENCE repeats the reference's arithmetic, which divides by
@@ -34,7 +39,7 @@ class TrotFootStepPlanner:
         structs = []
         for b in range(self.ctx.batch):
             p = capi.FootStepPlanner()
-            p.mode, p.projection, p.enable_stance_phase = capi.FOOT_STEP_FIXED, self.projection, int(bool(enable_stance_phase))
+            p.gait, p.mode, p.projection, p.enable_stance_phase = self.GAIT, capi.FOOT_STEP_FIXED, self.projection, int(bool(enable_stance_phase))
             p.step_length[:], p.step_yaw = [float(x) for x in sl[b]], float(yaw[b])
             structs.append(p)
         self._set(structs, inst_l or inst_y)
@@ -42,22 +47,26 @@ class TrotFootStepPlanner:
     def set_raibert_gait_pattern(self, vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain):
         """setRaibertGaitPattern: vcom_cmd [3] or [batch, 3], yaw_rate_cmd a scalar or [batch]; the gait timing and the gain are
         shared by the batch"""
+        self._check_timing(swing_time, stance_time, gain)
+        vc, inst_v = self._per_instance("vcom_cmd", vcom_cmd, 3)
+        yr, inst_y = self._per_instance("yaw_rate_cmd", yaw_rate_cmd, 0)
+        structs = []
+        for b in range(self.ctx.batch):
+            p = capi.FootStepPlanner()
+            p.gait, p.mode, p.projection = self.GAIT, capi.FOOT_STEP_RAIBERT, self.projection
+            p.swing_time, p.stance_time, p.gain = float(swing_time), float(stance_time), float(gain)
+            p.vcom_cmd[:], p.yaw_rate_cmd = [float(x) for x in vc[b]], float(yr[b])
+            structs.append(p)
+        self._set(structs, inst_v or inst_y)
+
+    @staticmethod
+    def _check_timing(swing_time, stance_time, gain):
         if swing_time <= 0.0:
             raise ValueError("'swing_time' must be positive")
         if stance_time < 0.0:
             raise ValueError("'stance_time' must be non-negative")
         if gain <= 0.0:
             raise ValueError("'gain' must be positive")
-        vc, inst_v = self._per_instance("vcom_cmd", vcom_cmd, 3)
-        yr, inst_y = self._per_instance("yaw_rate_cmd", yaw_rate_cmd, 0)
-        structs = []
-        for b in range(self.ctx.batch):
-            p = capi.FootStepPlanner()
-            p.mode, p.projection = capi.FOOT_STEP_RAIBERT, self.projection
-            p.swing_time, p.stance_time, p.gain = float(swing_time), float(stance_time), float(gain)
-            p.vcom_cmd[:], p.yaw_rate_cmd = [float(x) for x in vc[b]], float(yr[b])
-            structs.append(p)
-        self._set(structs, inst_v or inst_y)
 
     def init(self, x0=None):
         """init(q) of every instance; x0 [batch, nq + nv]: set as the context's initial state first (None: as it stands)"""
@@ -68,10 +77,10 @@ class TrotFootStepPlanner:
 
     def plan(self, t, contact_status, planning_steps, x0=None):
         """plan(t, q, v, contact_status, planning_steps) of every instance; contact_status: the bit mask of the active contacts of
-        the first contact phase.  False where the reference returns false (a status that is no trot stance)."""
+        the first contact phase.  False where the reference returns false (a status outside the gait's STATUSES)."""
         if x0 is not None:
             self.ctx.set_initial_state(x0)
-        if int(contact_status) not in (0b1111, 0b1001, 0b0110):
+        if int(contact_status) not in self.STATUSES:
             return False
         self.ctx.foot_step_plan(t, contact_status, planning_steps)
         self._plan = None
@@ -106,7 +115,8 @@ class TrotFootStepPlanner:
         return self._get()["ok"]
 
     def reset_contact_placements(self, t, contact_status, phase_of_grid_point, phase_masks, refs, x0=None):
-        """What MPCTrot::resetContactPlacements does per control tick (src/mpc/mpc_trot.cpp:357-372): plan with planning_steps =
+        """What MPCTrot::resetContactPlacements does per control tick (src/mpc/mpc_trot.cpp:357-372; MPCCrawl, MPCPace and
+        MPCFlyingTrot repeat it line for line): plan with planning_steps =
         the number of contact phases, the placements of every phase into the per-instance table, the three references into their
         tables.  phase_of_grid_point: GridInfo::phase of every grid point relative to the first; phase_masks: the active contacts
         of every phase; refs: a capi.FootStepRefs.  Returns what plan returns."""
@@ -115,3 +125,39 @@ class TrotFootStepPlanner:
         self.ctx.foot_step_place(phase_of_grid_point)
         self.ctx.foot_step_refs(refs, phase_of_grid_point, phase_masks)
         return True
+
+
+class CrawlFootStepPlanner(TrotFootStepPlanner):
+    """src/mpc/crawl_foot_step_planner.cpp: three feet stand while RH, RF, LH, LF swing in turn; the setters are the trot's"""
+    GAIT = capi.GAIT_CRAWL
+    STATUSES = (0b1111, 0b0111, 0b1011, 0b1101, 0b1110)
+
+
+class PaceFootStepPlanner(TrotFootStepPlanner):
+    """src/mpc/pace_foot_step_planner.cpp: the trot with the pairs (LF, LH) and (RF, RH); the setters are the trot's"""
+    GAIT = capi.GAIT_PACE
+    STATUSES = (0b1111, 0b0011, 0b1100)
+
+
+class FlyingTrotFootStepPlanner(TrotFootStepPlanner):
+    """src/mpc/flying_trot_foot_step_planner.cpp: a trot with a flight (contact status 0) between the pairs; the plan is
+    planning_steps + 3 steps long, planning_steps at most capi.MAX_PLAN_STEPS - 1, and there is no stance-phase option"""
+    GAIT = capi.GAIT_FLYING_TROT
+    STATUSES = (0b1111, 0b1001, 0b0110, 0b0000)
+
+    def set_gait_pattern(self, step_length, step_yaw):
+        """setGaitPattern: step_length [3] or [batch, 3], step_yaw a scalar or [batch]"""
+        super().set_gait_pattern(step_length, step_yaw, False)
+
+    def set_raibert_gait_pattern(self, vcom_cmd, yaw_rate_cmd, flying_time, stance_time, gain):
+        """setRaibertGaitPattern: as the trot's, with flying_time where that has swing_time"""
+        super().set_raibert_gait_pattern(vcom_cmd, yaw_rate_cmd, flying_time, stance_time, gain)
+
+    @staticmethod
+    def _check_timing(flying_time, stance_time, gain):
+        if flying_time <= 0.0:
+            raise ValueError("'flying_time' must be positive")
+        if stance_time <= 0.0:
+            raise ValueError("'stance_time' must be positive")
+        if gain <= 0.0:
+            raise ValueError("'gain' must be positive")

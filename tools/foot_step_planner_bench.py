@@ -6,11 +6,26 @@
     rtoc_set_configuration_ref_table).  The loop is timed over the first `host_instances` instances and scaled to the batch (the
     figure says so); the uploads are timed at the full batch.
 Wall clock around `reps` asynchronous ticks, synchronised once, after a warm-up; three rounds each.
-Usage: foot_step_planner_bench.py [batch] [out.json] [host_instances]"""
+With --gait the plan alone is timed instead, per gait named (trot, crawl, pace, flying_trot, or all): rtoc_foot_step_plan -- the
+kinematics launch and foot_step_plan_kernel -- at the gait's own swing status, 200 asynchronous calls synchronised once, five
+rounds; the host path is left out.  A trot leaves the struct's gait member alone, so the same file times a library from before
+the member had a meaning.
+Usage: foot_step_planner_bench.py [batch] [out.json] [host_instances] [--gait NAME[,NAME...]]"""
 import json
 import os
 import sys
 import time
+
+gaits = None
+if "--gait" in sys.argv:
+    at = sys.argv.index("--gait")
+    gaits = sys.argv[at + 1].split(",")
+    del sys.argv[at:at + 2]
+    if gaits == ["all"]:
+        gaits = ["trot", "crawl", "pace", "flying_trot"]
+    GAIT_STATUS = {"trot": (0, 0b1001), "crawl": (1, 0b0111), "pace": (2, 0b0011), "flying_trot": (3, 0b1001)}   # RTOC_GAIT_*, a swing status
+    if any(g not in GAIT_STATUS for g in gaits):
+        sys.exit("--gait: trot, crawl, pace, flying_trot or all")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -74,6 +89,41 @@ for b in range(batch):
     s.swing_time, s.stance_time, s.gain = SWING, STANCE, GAIN
     s.vcom_cmd[:], s.yaw_rate_cmd = list(vcmd[b]), float(yaw_rate[b])
     structs.append(s)
+if gaits is not None:
+    # ---- the plan alone, per gait ----
+    out = {"batch": batch, "contact_phases": nphases, "reps": 200, "plan_ms": {}, "plans_finite": {}}
+    for gait in gaits:
+        gait_id, status = GAIT_STATUS[gait]
+        for s in structs:
+            if gait_id or hasattr(s, "gait"):
+                s.gait = gait_id
+        ctx.set_foot_step_planner(structs)
+        ctx.foot_step_planner_init()
+        ctx.foot_step_plan(0.0, 0b1111, nphases)
+        tick_t = [0.0]
+
+        def plan_alone():
+            tick_t[0] += 0.0025
+            ctx.foot_step_plan(tick_t[0], status, nphases)
+
+        rounds = []
+        for rnd in range(5):
+            for _ in range(10):
+                plan_alone()
+            ctx.sync()
+            t0 = time.perf_counter()
+            for _ in range(out["reps"]):
+                plan_alone()
+            ctx.sync()
+            rounds.append((time.perf_counter() - t0) / out["reps"] * 1e3)
+        out["plan_ms"][gait] = rounds
+        out["plans_finite"][gait] = bool(ctx.foot_step_plan_get()["ok"].all())
+    ctx.close()
+    print(json.dumps(out))
+    if len(sys.argv) > 2:
+        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[2])), exist_ok=True)
+        json.dump(out, open(sys.argv[2], "w"), indent=1)
+    sys.exit(0)
 ctx.set_foot_step_planner(structs)
 ctx.foot_step_planner_init()
 refs = capi.FootStepRefs()
