@@ -11,7 +11,7 @@
 // of nq doubles.  Every body lane loads its own joint coordinate and nothing else -- the revolute lanes of an instance read one
 // contiguous run, the root lane its seven -- so each double is fetched once and nothing is staged: no value is used by a second lane.
 //
-// Included by rt_eval_kkt.hip alone (a kernel header belongs to the unit that launches from it).
+// Included by rt_placements.hip alone (a kernel header belongs to the unit that launches from it).
 #pragma once
 #include "device_utils.hpp"
 #include "record_view.hpp"

@@ -20,6 +20,7 @@
 #include "../../include/rtoc.h"
 #include "../../include/rtoc_robot.h"
 #include "device_buffer.hpp"
+#include "grid_table.hpp"
 #include "kernel_table.hpp"
 #include "record_view.hpp"
 #include "rigid_body_model.hpp"
@@ -114,8 +115,6 @@ struct CtxOptions {
   int lin_dpp = 0;              // RTOC_OPT_LINEARIZE_DOFS_PER_PASS (0 = per model)
   double barrier = 0.0, ftb_rule = 0.0;
   int n_mu = 0;                 // how many of d_mu's RTOC_MAX_CONTACTS entries the caller set
-  bool has_cpos = false, has_crot = false;
-  int cplace_inst = 0;          // 1: d_cpos / d_crot hold a table per instance (rtoc_set_contact_placements, rtoc_hold_contact_placements)
   // filter line search on the device (rtoc_set_line_search, rtoc_contact_line_search)
   int ls_on = 0;
   double ls_rate = 0.0, ls_min_step = 0.0, ls_cost_rate = 0.0, ls_viol_rate = 0.0;
@@ -173,17 +172,15 @@ struct ModelState {
   DevBuf<unsigned> d_active;
   bool active_current = false;  // the schedule was set since the last rtoc_set_grid: its masks belong to the grid in force
   std::vector<unsigned> h_active;  // host copy of the masks (which placements rtoc_set_contact_placements checks)
-  // desired contact placements: [max_stages][RTOC_MAX_CONTACTS][3 | 9] shared by the batch, or [batch] of them (cplace_inst);
-  // in use [nstages][ncontacts][3 | 9] or [batch][nstages][ncontacts][3 | 9], dense
-  DevBuf<double> d_cpos;
-  DevBuf<double> d_crot;
+  // desired contact placements (rt_placements.hip), rows of [ncontacts][3 | 9]: always committed together -- one mode, one grid, that
+  // of the schedule (active_current); on: positions / rotations were given (else zeros / identities)
+  GridTable<double> cpos, crot;
   DevBuf<double> d_cost;      // rtoc_set_configuration_cost: 12 (nv + 1) doubles
   DevBuf<double> d_x0;        // rtoc_set_initial_state: [batch][nq + nv]
-  // rtoc_set_configuration_ref_table: q_ref rows of nq doubles and their isActive, [nstages] or [batch][nstages] of them (capacity: the
-  // same at max_stages).  qtab_on: a table is in use; qtab_n: the nstages its rows were set for (0: rtoc_set_grid forgot them)
-  DevBuf<double> d_qtab;
-  DevBuf<int> d_qtab_active;
-  int qtab_on = 0, qtab_n = 0, qtab_inst = 0;
+  // rtoc_set_configuration_ref_table: q_ref rows of nq doubles and their isActive (capacity: max_stages rows, or [batch] of them),
+  // always committed together; qtab.on: a table is in use
+  GridTable<double> qtab;
+  GridTable<int> qtab_active;
   // false: no memory for the host copy of the model (no HIP error to report)
   bool clone_from(const ModelState& src, CopyChain& dup) {
     if (src.h_model) {
@@ -195,13 +192,12 @@ struct ModelState {
     dup(d_active, src.d_active);
     active_current = src.active_current;
     h_active = src.h_active;
-    dup(d_cpos, src.d_cpos);
-    dup(d_crot, src.d_crot);
+    cpos.clone_from(src.cpos, dup);
+    crot.clone_from(src.crot, dup);
     dup(d_cost, src.d_cost);
     dup(d_x0, src.d_x0);
-    qtab_on = src.qtab_on, qtab_n = src.qtab_n, qtab_inst = src.qtab_inst;
-    dup(d_qtab, src.d_qtab);
-    dup(d_qtab_active, src.d_qtab_active);
+    qtab.clone_from(src.qtab, dup);
+    qtab_active.clone_from(src.qtab_active, dup);
     return true;
   }
   // not copied: scratch and results of the last evaluation
@@ -221,11 +217,8 @@ struct TaskState {
   unsigned h_task_3d = 0, h_task_com = 0;   // bit k: term k of EVERY instance is a RTOC_TASK_FRAME_3D / a RTOC_TASK_COM term
   DevBuf<double> d_gt;             // [max_stages] GridInfo::t of a fixed grid (rtoc_set_grid_times)
   std::vector<double> h_gt;        // host copy of the same, its size = the grid it belongs to (empty: none)
-  // reference tables of RTOC_REF_TABLE terms (rtoc_set_task_ref_table), by term index: capacity [max_stages] or [batch][max_stages],
-  // in use [nstages] or [batch][nstages]; reftab_n[k] = the nstages table k was set for (0: none), bit k of reftab_inst: per instance
-  DevBuf<rtoc_task_ref_entry> d_reftab[RTOC_MAX_TASK_COSTS];
-  int reftab_n[RTOC_MAX_TASK_COSTS] = {};
-  unsigned reftab_inst = 0;
+  // reference tables of RTOC_REF_TABLE terms (rtoc_set_task_ref_table), by term index: capacity [max_stages] or [batch][max_stages] entries
+  GridTable<rtoc_task_ref_entry> reftab[RTOC_MAX_TASK_COSTS];
   int task_rows = 0, task_ext = 0; // LDS rows of the term lists (the largest instance), 1: a 6D term or a table reference among them
   // LocalContactForceCost (rtoc_set_contact_force_cost; contact_force_cost.hpp): capacity [batch]; in use [1] or [batch]
   DevBuf<rtoc_contact_force_cost> d_fcost;
@@ -237,12 +230,9 @@ struct TaskState {
     }
     dup(d_gt, src.d_gt);
     h_gt = src.h_gt;
-    task_rows = src.task_rows, task_ext = src.task_ext, reftab_inst = src.reftab_inst, h_task_table = src.h_task_table;
+    task_rows = src.task_rows, task_ext = src.task_ext, h_task_table = src.h_task_table;
     h_task_3d = src.h_task_3d, h_task_com = src.h_task_com;
-    for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) {
-      reftab_n[k] = src.reftab_n[k];
-      dup(d_reftab[k], src.d_reftab[k]);
-    }
+    for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) reftab[k].clone_from(src.reftab[k], dup);
     if (src.fcost_on) {
       fcost_on = 1, fcost_per_instance = src.fcost_per_instance;
       dup(d_fcost, src.d_fcost);
@@ -420,6 +410,19 @@ template <class A>
 static void launch(const Kern<A>& k, dim3 grid, hipStream_t stream, const A& a, int extra_lds = 0) {
   hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), (size_t)(k.lds + extra_lds), stream, a);
 }
+// nq of the context's robot: a free-flyer base carries a quaternion
+static inline int config_dim(const rtoc_ctx* c) { return c->dims.nv + (c->dims.np == 6 ? 1 : 0); }
+// A table writer's two steps around filling t.target(), on the host or on the device: an allocation of `row` elements per grid point
+// of the largest grid (per instance: of each); then the rows are the table of the grid in force -- a new epoch where commit says so
+template <class T>
+static inline hipError_t stage_rows(const rtoc_ctx* c, GridTable<T>& t, size_t row, int inst) { return t.stage((size_t)c->max_stages * (inst ? c->batch : 1) * row); }
+template <class T>
+static inline void commit_rows(rtoc_ctx* c, GridTable<T>& t, int inst, int on = 1) { c->epoch += t.commit(c->nstages, inst, on) ? 1 : 0; }
+// The tables a new grid outdates (rtoc_set_grid, rtoc_parnmpc_set_horizon).  The placements go with the schedule: active_current
+static inline void forget_grid_tables(rtoc_ctx* c) {
+  for (auto& t : c->reftab) t.forget();
+  c->qtab.forget(), c->qtab_active.forget();
+}
 // role-split kernel where it exists
 static inline int default_bwd_variant(const KernelSet* ks) { return (ks->nvariants >= 3) ? ks->nvariants - 1 : 0; }
 
@@ -494,15 +497,10 @@ int launch_sweep(rtoc_ctx* c, const BwdPlan& p);
 ConeRows view_cones(const rtoc_ctx* c);
 void launch_fill_steps(rtoc_ctx* c);
 // rt_eval_kkt.hip
+hipError_t reserve_active(rtoc_ctx* c, bool* fresh = nullptr);
+ModelDims model_dims(const rtoc_ctx* c);   // (c->h_model is set)
 hipError_t reserve_kkterr(rtoc_ctx* c);
 int launch_kkt_error(rtoc_ctx* c);
-// what rt_foot_steps.hip shares with the contact placements: a schedule that belongs to the grid in force (else RTOC_ERR_NOT_READY);
-// the per-instance placement table from whatever is in force, every instance starting from the shared values (need_rot: a rotation
-// table too, created if there is none); contact_frame_placements_kernel at the q of rtoc_set_initial_state into device memory,
-// out_p[batch][ncontacts][3] and out_com[batch][3]
-int placements_ready(const rtoc_ctx* c);
-int placements_per_instance(rtoc_ctx* c, bool need_rot);
-int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com);
 // records per instance that carry dynamics and rows: all but the terminal one, or all of a ParNMPC horizon
 static inline int dynamics_records(const rtoc_ctx* c) { return c->nstages - 1 + (c->parnmpc ? 1 : 0); }
 // the unconstrained path's pieces rt_parnmpc.hip strings together: the all-zero contact schedule, linearizeUnconstrDynamics with
@@ -512,6 +510,12 @@ int reserve_empty_schedule(rtoc_ctx* c);
 int launch_unconstr_linearize(rtoc_ctx* c, double dt);
 bool unconstr_rows_on(const rtoc_ctx* c);
 int launch_unconstr_rows(rtoc_ctx* c, UnconstrRowsPhase phase);
+// rt_placements.hip, for rt_foot_steps.hip: a schedule that belongs to the grid in force (else RTOC_ERR_NOT_READY); the per-instance
+// placement table from whatever is in force, every instance starting from the shared values (need_rot: a rotation table too, created
+// if there is none); contact_frame_placements_kernel at the q of rtoc_set_initial_state, out_p[batch][ncontacts][3], out_com[batch][3]
+int placements_ready(const rtoc_ctx* c);
+int placements_per_instance(rtoc_ctx* c, bool need_rot);
+int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com);
 // rt_task_costs.hip
 int ensure_grid_times_inst(rtoc_ctx* c);
 int task_costs_ready(rtoc_ctx* c, bool unconstr);

@@ -24,7 +24,7 @@ static int run_policy(rtoc_ctx* c, double t0, const double* t, int per_instance,
   if (N < 1 || N > c->nstages - 1 || count < 1 || count > c->batch || (per_instance != 0 && per_instance != 1)) return RTOC_ERR_BAD_ARG;
   if (!t || !out || (input && !x) || (flags & ~RTOC_POLICY_DEVICE_PTRS) || !std::isfinite(t0)) return RTOC_ERR_BAD_ARG;
   const bool host = !(flags & RTOC_POLICY_DEVICE_PTRS);
-  const int nv = c->dims.nv, nu = c->dims.nu, nq = nv + (c->dims.np == 6 ? 1 : 0);
+  const int nv = c->dims.nv, nu = c->dims.nu, nq = config_dim(c);
   const size_t nt = per_instance ? (size_t)count : 1, nx = input ? (size_t)count * (nq + nv) : 0;
   const size_t nout = (size_t)count * (input ? nu : rtoc_control_policy_stride(nu));
   if (host && (!all_finite(t, nt) || !all_finite(x, nx))) return RTOC_ERR_BAD_ARG;

@@ -1,5 +1,7 @@
-// rt_eval_kkt.hip -- evalKKT on the device: rigid-body model and contact schedule, linearisation, cost, constraint rows and
-// cones at the iterate, KKT error, SplitSolution::integrate; updateSolution of the unconstrained path.
+// rt_eval_kkt.hip -- evalKKT on the device: rigid-body model, linearisation, cost and its q_ref table, constraint rows and
+// cones at the iterate, KKT error, SplitSolution::integrate; updateSolution of the unconstrained path.  (The contact schedule
+// and the contact placements: rt_placements.hip.)
+#include <cmath>
 #include <mutex>
 
 #include "rt_context.hpp"
@@ -11,7 +13,6 @@
 #include "switching_constraint_lin.hpp"
 #include "contact_constraints.hpp"
 #include "contact_eval_kkt.hpp"
-#include "contact_frame_placements.hpp"
 
 using namespace rtoc;
 
@@ -44,8 +45,7 @@ hipError_t rtoc::set_linearize_lds(const rtoc_robot_model& m, int nlevels, int n
   return e;
 }
 
-// (c->h_model is set)
-static ModelDims model_dims(const rtoc_ctx* c) {
+ModelDims rtoc::model_dims(const rtoc_ctx* c) {
   const rtoc_robot_model& m = c->h_model->m;
   ModelDims d{};
   d.nq = m.nq, d.njoints = m.njoints, d.ncontacts = m.ncontacts;
@@ -77,7 +77,7 @@ static int select_grid_points(const rtoc_ctx* c, bool (*has)(const rtoc_grid&), 
 }
 
 // the buffers that more than one entry point allocates on first use
-static hipError_t reserve_active(rtoc_ctx* c, bool* fresh = nullptr) { return c->d_active.reserve(c->max_stages, fresh); }
+hipError_t rtoc::reserve_active(rtoc_ctx* c, bool* fresh) { return c->d_active.reserve(c->max_stages, fresh); }
 static hipError_t reserve_costval(rtoc_ctx* c) { return c->d_costval.reserve((size_t)c->batch * c->max_stages); }
 hipError_t rtoc::reserve_kkterr(rtoc_ctx* c) { return c->d_kkterr.reserve((size_t)c->batch * (1 + c->max_stages)); }
 
@@ -163,10 +163,9 @@ int rtoc_set_robot_model(rtoc_ctx* c, const rtoc_robot_model* m) {
     return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(c->d_model.reserve(1));
-  if (c->cplace_inst) {
+  if (c->cpos.per_instance) {
     // a per-instance placement table is sized by the contacts of the model it was set for: it goes with that model
-    c->d_cpos.release(), c->d_crot.release();
-    c->cplace_inst = 0, c->has_cpos = c->has_crot = false;
+    c->cpos = {}, c->crot = {};
   }
   c->fs_on = 0, c->fs_init = 0, c->fs_size = 0;   // a foot-step planner belongs to the feet of the model it was set for
   c->h_model = std::move(h);
@@ -175,214 +174,6 @@ int rtoc_set_robot_model(rtoc_ctx* c, const rtoc_robot_model* m) {
   HIP_TRY(set_linearize_lds(*m, c->h_model->nlevels, c->h_model->nbranch, c->h_model->dpp));
   c->epoch++;
   return RTOC_OK;
-}
-
-int rtoc_set_contact_schedule(rtoc_ctx* c, const unsigned* active, const double* positions, const double* rotations) {
-  CHECK_READY(c);
-  if (!c->h_model || !active) return RTOC_ERR_BAD_ARG;
-  const rtoc_robot_model& m = c->h_model->m;
-  const int nc = m.ncontacts;
-  for (int i = 0; i < c->nstages; ++i) {
-    if (nc < 32 && (active[i] >> nc) != 0) return RTOC_ERR_BAD_ARG;
-    int rows = 0;
-    for (int k = 0; k < nc; ++k)
-      if ((active[i] >> k) & 1u) rows += m.contact_type[k] == RTOC_CONTACT_SURFACE ? 6 : 3;
-    if (i < c->nstages - 1 && rows != c->h_grid[i].dimf) return RTOC_ERR_BAD_ARG;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(reserve_active(c));
-  HIP_TRY(c->d_cpos.reserve((size_t)c->max_stages * RTOC_MAX_CONTACTS * 3));
-  if (rotations) HIP_TRY(c->d_crot.reserve((size_t)c->max_stages * RTOC_MAX_CONTACTS * 9));
-  HIP_TRY(hipMemcpyAsync(c->d_active.p, active, sizeof(unsigned) * c->nstages, hipMemcpyHostToDevice, c->stream));
-  if (positions)
-    HIP_TRY(hipMemcpyAsync(c->d_cpos.p, positions, sizeof(double) * c->nstages * nc * 3, hipMemcpyHostToDevice, c->stream));
-  if (rotations)
-    HIP_TRY(hipMemcpyAsync(c->d_crot.p, rotations, sizeof(double) * c->nstages * nc * 9, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->has_cpos = positions != nullptr;
-  c->has_crot = rotations != nullptr;
-  c->cplace_inst = 0;   // the batch shares these placements: a per-instance table ends here
-  c->h_active.assign(active, active + c->nstages);
-  c->active_current = true;
-  c->epoch++;
-  return RTOC_OK;
-}
-
-// ---- contact placements of every instance (rtoc_set_contact_placements, rtoc_contact_frame_placements,
-//      rtoc_hold_contact_placements; contact_frame_placements.hpp) ----
-// doubles of a placement table: the shared one is sized for any model, a per-instance one for the contacts of the model in force
-static size_t placement_capacity(const rtoc_ctx* c, int per_instance, int unit) {
-  return per_instance ? (size_t)c->batch * c->max_stages * c->h_model->m.ncontacts * unit : (size_t)c->max_stages * RTOC_MAX_CONTACTS * unit;
-}
-// a schedule that belongs to the grid in force, of a model with contacts
-int rtoc::placements_ready(const rtoc_ctx* c) {
-  if (!c->h_model || !c->d_active.p || !c->active_current || (int)c->h_active.size() != c->nstages) return RTOC_ERR_NOT_READY;
-  return RTOC_OK;
-}
-
-int rtoc_set_contact_placements(rtoc_ctx* c, const double* positions, const double* rotations, int per_instance) {
-  CHECK_READY(c);
-  int rc = placements_ready(c);
-  if (rc) return rc;
-  if (per_instance != 0 && per_instance != 1) return RTOC_ERR_BAD_ARG;
-  const int nc = c->h_model->m.ncontacts, ninst = per_instance ? c->batch : 1;
-  if (nc < 1) return RTOC_ERR_BAD_ARG;
-  // the entries of the ACTIVE contacts, the only ones a kernel reads, must be finite; the others are not looked at
-  for (int b = 0; b < ninst; ++b)
-    for (int i = 0; i < c->nstages; ++i)
-      for (int k = 0; k < nc; ++k) {
-        if (!((c->h_active[i] >> k) & 1u)) continue;
-        const size_t row = ((size_t)b * c->nstages + i) * nc + k;
-        for (int e = 0; positions && e < 3; ++e)
-          if (!std::isfinite(positions[row * 3 + e])) return RTOC_ERR_BAD_ARG;
-        for (int e = 0; rotations && e < 9; ++e)
-          if (!std::isfinite(rotations[row * 9 + e])) return RTOC_ERR_BAD_ARG;
-      }
-  // new capacities first: a failed allocation leaves the table in force
-  const size_t cap_p = placement_capacity(c, per_instance, 3), cap_r = placement_capacity(c, per_instance, 9);
-  DevBuf<double> pos, rot;
-  const bool new_p = positions && c->d_cpos.n != cap_p, new_r = rotations && c->d_crot.n != cap_r;
-  if (new_p) HIP_TRY(pos.reserve(cap_p));
-  if (new_r) HIP_TRY(rot.reserve(cap_r));
-  if (new_p) c->d_cpos = std::move(pos);
-  if (new_r) c->d_crot = std::move(rot);
-  const size_t rows = (size_t)ninst * c->nstages * nc;
-  if (positions) HIP_TRY(hipMemcpyAsync(c->d_cpos.p, positions, sizeof(double) * rows * 3, hipMemcpyHostToDevice, c->stream));
-  if (rotations) HIP_TRY(hipMemcpyAsync(c->d_crot.p, rotations, sizeof(double) * rows * 9, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->has_cpos = positions != nullptr;
-  c->has_crot = rotations != nullptr;
-  c->cplace_inst = per_instance;
-  c->vals_fresh = 0;   // the contact rows of the values pre-pass belong to the previous placements
-  c->epoch++;   // the kernels' table pointers and stride are baked into captured graphs
-  return RTOC_OK;
-}
-
-int rtoc_get_contact_placements(rtoc_ctx* c, double* host_positions, double* host_rotations, int count, int* per_instance) {
-  CHECK_READY(c);
-  int rc = placements_ready(c);
-  if (rc) return rc;
-  if (count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
-  const size_t per = (size_t)c->nstages * c->h_model->m.ncontacts;
-  if (per_instance) *per_instance = c->cplace_inst;
-  // the table as an instance reads it: a shared one repeated, zeros / identities where nothing was set
-  auto fetch = [&](double* host, const DevBuf<double>& d, bool set, int unit) -> int {
-    if (!host || per == 0) return RTOC_OK;
-    const size_t n = per * unit;
-    if (!set) {
-      for (size_t e = 0; e < n * count; ++e) host[e] = (unit == 9 && (e % 9) % 4 == 0) ? 1.0 : 0.0;
-      return RTOC_OK;
-    }
-    if (count > 0) HIP_TRY(hipMemcpyAsync(host, d.p, sizeof(double) * n * (c->cplace_inst ? count : 1), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int b = 1; !c->cplace_inst && b < count; ++b) memcpy(host + b * n, host, sizeof(double) * n);
-    return RTOC_OK;
-  };
-  rc = fetch(host_positions, c->d_cpos, c->has_cpos, 3);
-  if (!rc) rc = fetch(host_rotations, c->d_crot, c->has_crot, 9);
-  return rc;
-}
-
-// where the kinematics are evaluated: q of instance 0 and the doubles between two instances
-static int placement_source(const rtoc_ctx* c, int source, int grid_point, const double** q, size_t* stride) {
-  const rtoc_robot_model& m = c->h_model->m;
-  if (source == 0) {
-    if (!c->d_x0.p) return RTOC_ERR_NOT_READY;
-    *q = c->d_x0.p, *stride = (size_t)m.nq + m.nv;
-  } else if (source == 1) {
-    if (grid_point < 0 || grid_point >= c->nstages) return RTOC_ERR_BAD_ARG;
-    if (!c->buf[RTOC_BUF_SOL].p) return RTOC_ERR_NOT_READY;
-    *q = c->buf[RTOC_BUF_SOL].p + (size_t)grid_point * c->L.sol.stride + c->L.sol.off[RTOC_SOL_Q];
-    *stride = (size_t)c->nstages * c->L.sol.stride;
-  } else {
-    return RTOC_ERR_BAD_ARG;
-  }
-  return RTOC_OK;
-}
-static int launch_frame_placements(rtoc_ctx* c, FkArgs a) {
-  a.rv = view(c);
-  a.md = model_dims(c);
-  const int G = 64 / a.md.gs;
-  const size_t lds = sizeof(double) * G * (a.md.njoints + a.md.ncontacts) * FK_SLOTS;
-  hipLaunchKernelGGL(contact_frame_placements_kernel, dim3((unsigned)((c->batch + G - 1) / G)), dim3(64), lds, c->stream, a);
-  HIP_TRY(hipGetLastError());
-  return RTOC_OK;
-}
-
-int rtoc_contact_frame_placements(rtoc_ctx* c, int source, int grid_point, double* host_R, double* host_p, double* host_com, int count) {
-  CHECK_READY(c);
-  if (count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
-  if (!c->h_model) return RTOC_ERR_NOT_READY;
-  FkArgs a{};
-  int rc = placement_source(c, source, grid_point, &a.q, &a.q_stride);
-  if (rc) return rc;
-  const size_t nc = c->h_model->m.ncontacts, B = c->batch;
-  HIP_TRY(c->d_fk.reserve(B * (RTOC_MAX_CONTACTS * FK_SLOTS + 3)));
-  a.out_R = c->d_fk.p, a.out_p = a.out_R + B * RTOC_MAX_CONTACTS * 9, a.out_com = a.out_p + B * RTOC_MAX_CONTACTS * 3;
-  rc = launch_frame_placements(c, a);
-  if (rc) return rc;
-  if (host_R && nc > 0) HIP_TRY(hipMemcpyAsync(host_R, a.out_R, sizeof(double) * count * nc * 9, hipMemcpyDeviceToHost, c->stream));
-  if (host_p && nc > 0) HIP_TRY(hipMemcpyAsync(host_p, a.out_p, sizeof(double) * count * nc * 3, hipMemcpyDeviceToHost, c->stream));
-  if (host_com) HIP_TRY(hipMemcpyAsync(host_com, a.out_com, sizeof(double) * count * 3, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RTOC_OK;
-}
-
-// A table per instance, every instance starting from what the batch shared (zeros / identities where nothing was set).  Both
-// allocations ahead of any change: a failure leaves the table in force
-int rtoc::placements_per_instance(rtoc_ctx* c, bool need_rot) {
-  const int nc = c->h_model->m.ncontacts;
-  const bool new_p = !(c->cplace_inst && c->has_cpos), new_r = c->has_crot ? !c->cplace_inst : need_rot;
-  DevBuf<double> pos, rot;
-  if (new_p) HIP_TRY(pos.reserve(placement_capacity(c, 1, 3)));
-  if (new_r) HIP_TRY(rot.reserve(placement_capacity(c, 1, 9)));
-  const size_t per = (size_t)c->nstages * nc;
-  auto spread = [&](double* dst, const double* src, int unit) {
-    const size_t total = (size_t)c->batch * per * unit;
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(placements_broadcast_kernel, dim3(blocks), dim3(256), 0, c->stream, dst, src, per * unit, total, unit);
-  };
-  if (new_p) spread(pos.p, (c->has_cpos && !c->cplace_inst) ? c->d_cpos.p : nullptr, 3);
-  if (new_r) spread(rot.p, c->has_crot ? c->d_crot.p : nullptr, 9);
-  if (new_p || new_r) {
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));   // the shared tables are read before they are freed
-    if (new_p) c->d_cpos = std::move(pos);
-    if (new_r) c->d_crot = std::move(rot);
-    c->has_cpos = true, c->has_crot = c->has_crot || new_r, c->cplace_inst = 1;
-    c->epoch++;
-  }
-  return RTOC_OK;
-}
-// the kinematics at the q of rtoc_set_initial_state, the result left on the device (rt_foot_steps.hip)
-int rtoc::launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com) {
-  FkArgs a{};
-  const int rc = placement_source(c, 0, 0, &a.q, &a.q_stride);
-  if (rc) return rc;
-  a.out_p = out_p, a.out_com = out_com;
-  return launch_frame_placements(c, a);
-}
-
-int rtoc_hold_contact_placements(rtoc_ctx* c, int source, int grid_point, int first, int last, unsigned contacts) {
-  CHECK_READY(c);
-  int rc = placements_ready(c);
-  if (rc) return rc;
-  const rtoc_robot_model& m = c->h_model->m;
-  const int nc = m.ncontacts;
-  if (nc < 1 || first < 0 || last > c->nstages || first >= last || (nc < 32 && (contacts >> nc) != 0)) return RTOC_ERR_BAD_ARG;
-  FkArgs a{};
-  rc = placement_source(c, source, grid_point, &a.q, &a.q_stride);
-  if (rc) return rc;
-  if (contacts == 0) return RTOC_OK;   // no foot on the ground: nothing to hold
-  bool need_rot = false;
-  for (int k = 0; k < nc; ++k)
-    if (((contacts >> k) & 1u) && m.contact_type[k] == RTOC_CONTACT_SURFACE) need_rot = true;
-  rc = placements_per_instance(c, need_rot);
-  if (rc) return rc;
-  a.tab_pos = c->d_cpos.p, a.tab_rot = c->has_crot ? c->d_crot.p : nullptr;
-  a.first = first, a.last = last, a.contacts = contacts;
-  c->vals_fresh = 0;
-  return launch_frame_placements(c, a);
 }
 
 // rbd_values_kernel for the iterate in RTOC_BUF_SOL: the lane-invariant values of the rigid-body recursion per body (and the
@@ -478,7 +269,7 @@ int rtoc_set_configuration_cost(rtoc_ctx* c, const rtoc_configuration_cost* cost
                            cost->q_weight_terminal, cost->v_weight_terminal, cost->q_weight_impact, cost->v_weight_impact,
                            cost->dv_weight_impact};
   for (int k = 0; k < 12; ++k) {
-    const int n = k == 0 ? nv + (c->dims.np == 6 ? 1 : 0) : (k == 2 || k == 6 ? c->dims.nu : nv);
+    const int n = k == 0 ? config_dim(c) : (k == 2 || k == 6 ? c->dims.nu : nv);
     for (int i = 0; i < n; ++i) {
       if (k >= 3 && !(src[k][i] >= 0.0)) return RTOC_ERR_BAD_ARG;  // configuration_space_cost.cpp: weights must be non-negative
       h[(size_t)k * M + i] = src[k][i];
@@ -496,14 +287,14 @@ int rtoc_set_configuration_ref_table(rtoc_ctx* c, const double* q_ref, const int
   if (!c) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
   if (!q_ref) {
-    if (c->qtab_on) c->epoch++;   // the kernels' table pointer is baked into captured graphs
-    c->qtab_on = 0, c->qtab_n = 0;
+    (void)c->qtab.stage(0), (void)c->qtab_active.stage(0);   // (nothing staged)
+    commit_rows(c, c->qtab, c->qtab.per_instance, 0), commit_rows(c, c->qtab_active, c->qtab.per_instance, 0);
     return RTOC_OK;
   }
   if (c->nstages < 2) return RTOC_ERR_NOT_READY;   // rtoc_set_grid
   if (nstages != c->nstages || (per_instance != 0 && per_instance != 1)) return RTOC_ERR_BAD_ARG;
   if (c->dims.np != 0 && c->dims.np != 6) return RTOC_ERR_BAD_ARG;
-  const size_t nq = (size_t)c->dims.nv + (c->dims.np == 6 ? 1 : 0), rows = (size_t)nstages * (per_instance ? c->batch : 1);
+  const size_t nq = config_dim(c), rows = (size_t)nstages * (per_instance ? c->batch : 1);
   std::vector<int> flags(rows, 1);
   for (size_t r = 0; r < rows; ++r) {
     if (active) flags[r] = active[r] != 0;
@@ -511,56 +302,39 @@ int rtoc_set_configuration_ref_table(rtoc_ctx* c, const double* q_ref, const int
     for (size_t k = 0; k < nq; ++k)
       if (!std::isfinite(q_ref[r * nq + k])) return RTOC_ERR_BAD_ARG;
   }
-  const size_t cap = (size_t)c->max_stages * (per_instance ? c->batch : 1);
-  bool fresh = false, fresh_a = false;
-  if (c->d_qtab.n != cap * nq || c->d_qtab_active.n != cap) {
-    // a new capacity: both allocations first, so that a failure of the second leaves no half of a table behind
-    DevBuf<double> q;
-    DevBuf<int> f;
-    HIP_TRY(q.reserve(cap * nq, &fresh));
-    HIP_TRY(f.reserve(cap, &fresh_a));
-    c->d_qtab = std::move(q), c->d_qtab_active = std::move(f);
-    c->qtab_n = 0;   // whatever was there is gone
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_qtab.p, q_ref, sizeof(double) * rows * nq, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_qtab_active.p, flags.data(), sizeof(int) * rows, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(stage_rows(c, c->qtab, nq, per_instance));   // both halves staged, then both committed
+  HIP_TRY(stage_rows(c, c->qtab_active, 1, per_instance));
+  HIP_TRY(hipMemcpyAsync(c->qtab.target(), q_ref, sizeof(double) * rows * nq, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->qtab_active.target(), flags.data(), sizeof(int) * rows, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (fresh || fresh_a || !c->qtab_on || c->qtab_inst != per_instance) c->epoch++;
-  c->qtab_on = 1, c->qtab_n = nstages, c->qtab_inst = per_instance;
+  commit_rows(c, c->qtab, per_instance), commit_rows(c, c->qtab_active, per_instance);
   return RTOC_OK;
 }
 int rtoc_get_configuration_ref_table(rtoc_ctx* c, double* q_ref, int* active, int count, int* per_instance) {
   CHECK_READY(c);
   if (count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
-  if (!c->qtab_on || c->qtab_n != c->nstages || !c->d_qtab.p || !c->d_qtab_active.p) return RTOC_ERR_NOT_READY;
-  if (per_instance) *per_instance = c->qtab_inst;
-  const size_t nq = (size_t)c->dims.nv + (c->dims.np == 6 ? 1 : 0), n = c->nstages, rows = n * (c->qtab_inst ? count : 1);
-  if (count == 0) return RTOC_OK;
-  if (q_ref) HIP_TRY(hipMemcpyAsync(q_ref, c->d_qtab.p, sizeof(double) * rows * nq, hipMemcpyDeviceToHost, c->stream));
-  if (active) HIP_TRY(hipMemcpyAsync(active, c->d_qtab_active.p, sizeof(int) * rows, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int b = 1; !c->qtab_inst && b < count; ++b) {   // a shared table repeated
-    if (q_ref) memcpy(q_ref + b * n * nq, q_ref, sizeof(double) * n * nq);
-    if (active) memcpy(active + b * n, active, sizeof(int) * n);
-  }
+  if (!c->qtab.in_force(c->nstages) || !c->qtab_active.in_force(c->nstages)) return RTOC_ERR_NOT_READY;
+  if (per_instance) *per_instance = c->qtab.per_instance;
+  HIP_TRY(c->qtab.download(q_ref, config_dim(c), count, c->stream));
+  HIP_TRY(c->qtab_active.download(active, 1, count, c->stream));
   return RTOC_OK;
 }
 // The table for the kernels that read the cost table (q = nullptr without one).  RTOC_ERR_NOT_READY: a table is in use but its rows
 // belong to a grid rtoc_set_grid has replaced -- never the constant q_ref in their place.
 static int configuration_ref_table(const rtoc_ctx* c, QRefTable* t) {
   t->q = nullptr, t->active = nullptr, t->per_instance = 0, t->nq = 0;
-  if (!c->qtab_on) return RTOC_OK;
-  if (c->qtab_n != c->nstages || !c->d_qtab.p || !c->d_qtab_active.p) return RTOC_ERR_NOT_READY;
-  t->q = c->d_qtab.p, t->active = c->d_qtab_active.p, t->per_instance = c->qtab_inst;
-  t->nq = c->dims.nv + (c->dims.np == 6 ? 1 : 0);
+  if (!c->qtab.on) return RTOC_OK;
+  if (!c->qtab.in_force(c->nstages) || !c->qtab_active.in_force(c->nstages)) return RTOC_ERR_NOT_READY;
+  t->q = c->qtab.buf.p, t->active = c->qtab_active.buf.p, t->per_instance = c->qtab.per_instance;
+  t->nq = config_dim(c);
   return RTOC_OK;
 }
+
 
 int rtoc_set_initial_state(rtoc_ctx* c, const double* x0, int count) {
   if (!c || !x0 || count != c->batch) return RTOC_ERR_BAD_ARG;
   HIP_TRY(hipSetDevice(c->device));
-  const int nq = c->dims.nv + (c->dims.np == 6 ? 1 : 0);  // a free-flyer base carries a quaternion
-  const size_t n = (size_t)c->batch * (nq + c->dims.nv);
+  const size_t n = (size_t)c->batch * (config_dim(c) + c->dims.nv);
   HIP_TRY(c->d_x0.reserve(n));
   HIP_TRY(hipMemcpyAsync(c->d_x0.p, x0, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -253,7 +253,7 @@ int rtoc_foot_step_place(rtoc_ctx* c, const int* phase_of_grid_point, int nstage
   rc = placements_per_instance(c, false);
   if (rc) return rc;
   auto a = view_args<FsPlaceArgs>(c);
-  a.plan = c->d_fs_plan.p, a.phase = c->d_fs_phase.p, a.tab_pos = c->d_cpos.p;
+  a.plan = c->d_fs_plan.p, a.phase = c->d_fs_phase.p, a.tab_pos = c->cpos.rows();
   hipLaunchKernelGGL(foot_step_place_kernel, dim3(blocks_for((size_t)c->batch * nstages * 12)), dim3(256), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->vals_fresh = 0;   // the contact rows of the values pre-pass belong to the previous placements
@@ -311,45 +311,25 @@ int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const i
       if (reads_ahead && ph + p.nph >= c->fs_size) return RTOC_ERR_BAD_ARG;
     }
   }
-  // ---- the per-instance tables: allocations first ----
-  const size_t cap = (size_t)c->max_stages * c->batch, nq = c->h_model->m.nq;
-  bool changed = false;
-  for (int k = 0; k < 5; ++k) {
-    if (term_of[k] < 0) continue;
-    bool fresh = false;
-    HIP_TRY(c->d_reftab[term_of[k]].reserve(cap, &fresh));
-    changed = changed || fresh;
-  }
-  if (r->configuration && (c->d_qtab.n != cap * nq || c->d_qtab_active.n != cap)) {
-    DevBuf<double> q;
-    DevBuf<int> f;
-    HIP_TRY(q.reserve(cap * nq));
-    HIP_TRY(f.reserve(cap));
-    c->d_qtab = std::move(q), c->d_qtab_active = std::move(f);
-    c->qtab_n = 0;
-    changed = true;
-  }
+  // ---- the per-instance tables the kernel writes: all of them staged first ----
+  for (int k = 0; k < 5; ++k)
+    if (term_of[k] >= 0) HIP_TRY(stage_rows(c, c->reftab[term_of[k]], 1, 1));
+  const size_t nq = c->h_model->m.nq;
+  if (r->configuration) HIP_TRY(stage_rows(c, c->qtab, nq, 1));
+  if (r->configuration) HIP_TRY(stage_rows(c, c->qtab_active, 1, 1));
   int rc = upload_phases(c, phase_of_grid_point, nstages, phase_masks, nphases);
   if (rc) return rc;
   a.plan = c->d_fs_plan.p, a.q0 = c->d_fs_q0.p, a.t = c->d_gt.p;
   a.phase = c->d_fs_phase.p, a.masks = (const unsigned*)(c->d_fs_phase.p + c->max_stages);
-  for (int k = 0; k < 5; ++k) a.tab[k] = term_of[k] >= 0 ? c->d_reftab[term_of[k]].p : nullptr;
-  a.qtab = r->configuration ? c->d_qtab.p : nullptr, a.qtab_active = r->configuration ? c->d_qtab_active.p : nullptr;
+  for (int k = 0; k < 5; ++k) a.tab[k] = term_of[k] >= 0 ? c->reftab[term_of[k]].target() : nullptr;
+  a.qtab = r->configuration ? c->qtab.target() : nullptr, a.qtab_active = r->configuration ? c->qtab_active.target() : nullptr;
   a.batch = c->batch, a.nstages = nstages, a.nq = (int)nq;
   const size_t most = (size_t)c->batch * nstages * (nq > (size_t)FS_ENTRY_WORDS ? nq : (size_t)FS_ENTRY_WORDS);
   hipLaunchKernelGGL(foot_step_refs_kernel, dim3(blocks_for(most), 6), dim3(256), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
-  // the tables are per instance and belong to the grid in force (captured graphs bake pointer and mode in)
-  for (int k = 0; k < 5; ++k) {
-    if (term_of[k] < 0) continue;
-    const unsigned bit = 1u << term_of[k];
-    changed = changed || c->reftab_n[term_of[k]] != nstages || !(c->reftab_inst & bit);
-    c->reftab_n[term_of[k]] = nstages, c->reftab_inst |= bit;
-  }
-  if (r->configuration) {
-    changed = changed || !c->qtab_on || !c->qtab_inst || c->qtab_n != nstages;
-    c->qtab_on = 1, c->qtab_n = nstages, c->qtab_inst = 1;
-  }
-  if (changed) c->epoch++;
+  // the tables are per instance and belong to the grid in force
+  for (int k = 0; k < 5; ++k)
+    if (term_of[k] >= 0) commit_rows(c, c->reftab[term_of[k]], 1);
+  if (r->configuration) commit_rows(c, c->qtab, 1), commit_rows(c, c->qtab_active, 1);
   return RTOC_OK;
 }

@@ -57,8 +57,7 @@ int rtoc_parnmpc_set_horizon(rtoc_ctx* c, int N) {
   c->vals_fresh = 0;
   c->sto_on = 0;
   c->h_gt.clear();
-  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) c->reftab_n[k] = 0;
-  c->qtab_n = 0;
+  forget_grid_tables(c);
   c->epoch++;
   return reserve_parnmpc(c);
 }
@@ -92,7 +91,7 @@ static int parnmpc_problem_ready(rtoc_ctx* c, double dt) {
   if (!(dt > 0.0)) return RTOC_ERR_BAD_ARG;
   if (!c->h_model || !c->d_cost.p || !c->buf[RTOC_BUF_SOL].p || !c->d_x0.p) return RTOC_ERR_NOT_READY;
   if (c->h_model->m.type[0] == RTOC_JOINT_FREE_FLYER || c->h_model->m.ncontacts != 0) return RTOC_ERR_BAD_ARG;  // unconstr_dynamics.cpp:22-29
-  if (c->ntasks > 0 || c->qtab_on || c->ls_on) return RTOC_ERR_BAD_ARG;   // task-space costs, a q_ref table, the line search: not in this mode
+  if (c->ntasks > 0 || c->qtab.on || c->ls_on) return RTOC_ERR_BAD_ARG;   // task-space costs, a q_ref table, the line search: not in this mode
   return RTOC_OK;
 }
 

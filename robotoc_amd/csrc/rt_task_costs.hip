@@ -76,29 +76,19 @@ int rtoc_set_task_ref_table(rtoc_ctx* c, int term, const rtoc_task_ref_entry* en
       if (!std::isfinite(entries[i].p[k])) return RTOC_ERR_BAD_ARG;
   }
   HIP_TRY(hipSetDevice(c->device));
-  bool fresh = false;
-  HIP_TRY(c->d_reftab[term].reserve((size_t)c->max_stages * (per_instance ? c->batch : 1), &fresh));
-  HIP_TRY(hipMemcpyAsync(c->d_reftab[term].p, entries, sizeof(rtoc_task_ref_entry) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(stage_rows(c, c->reftab[term], 1, per_instance));
+  HIP_TRY(hipMemcpyAsync(c->reftab[term].target(), entries, sizeof(rtoc_task_ref_entry) * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const unsigned bit = 1u << term, inst = per_instance ? bit : 0u;
-  // captured graphs bake the pointer and the per-instance flag in
-  if (fresh || c->reftab_n[term] != nstages || (c->reftab_inst & bit) != inst) c->epoch++;
-  c->reftab_n[term] = nstages;
-  c->reftab_inst = (c->reftab_inst & ~bit) | inst;
+  commit_rows(c, c->reftab[term], per_instance ? 1 : 0);
   return RTOC_OK;
 }
 
 int rtoc_get_task_ref_table(rtoc_ctx* c, int term, rtoc_task_ref_entry* entries, int count, int* per_instance) {
   CHECK_READY(c);
   if (term < 0 || term >= RTOC_MAX_TASK_COSTS || count < 0 || count > c->batch) return RTOC_ERR_BAD_ARG;
-  if (c->reftab_n[term] != c->nstages || !c->d_reftab[term].p) return RTOC_ERR_NOT_READY;
-  const int inst = (c->reftab_inst >> term) & 1u;
-  if (per_instance) *per_instance = inst;
-  if (!entries || count == 0) return RTOC_OK;
-  const size_t n = c->nstages;
-  HIP_TRY(hipMemcpyAsync(entries, c->d_reftab[term].p, sizeof(rtoc_task_ref_entry) * n * (inst ? count : 1), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int b = 1; !inst && b < count; ++b) memcpy(entries + b * n, entries, sizeof(rtoc_task_ref_entry) * n);   // a shared table repeated
+  if (!c->reftab[term].in_force(c->nstages)) return RTOC_ERR_NOT_READY;
+  if (per_instance) *per_instance = c->reftab[term].per_instance;
+  HIP_TRY(c->reftab[term].download(entries, 1, count, c->stream));
   return RTOC_OK;
 }
 
@@ -147,7 +137,7 @@ int rtoc::task_costs_ready(rtoc_ctx* c, bool unconstr) {
   if (!sto && (int)c->h_gt.size() != c->nstages) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
   if (sto && !c->d_gt_inst.p) return RTOC_ERR_NOT_READY;   // allocated by rtoc_contact_eval_kkt ahead of the time steps
   for (int k = 0; k < c->ntasks; ++k)
-    if (((c->h_task_table >> k) & 1u) && (c->reftab_n[k] != c->nstages || !c->d_reftab[k].p)) return RTOC_ERR_NOT_READY;   // rtoc_set_task_ref_table
+    if (((c->h_task_table >> k) & 1u) && !c->reftab[k].in_force(c->nstages)) return RTOC_ERR_NOT_READY;   // rtoc_set_task_ref_table
   return RTOC_OK;
 }
 
@@ -163,8 +153,8 @@ int rtoc::launch_task_costs(rtoc_ctx* c, double unconstr_dt, double* cost_out) {
   a.t_fixed = sto ? nullptr : c->d_gt.p;
   a.t_inst = sto ? c->d_gt_inst.p : nullptr;
   a.nterms = c->ntasks, a.per_instance = c->tasks_per_instance;
-  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) a.tab[k] = (k < c->ntasks && ((c->h_task_table >> k) & 1u)) ? c->d_reftab[k].p : nullptr;
-  a.tab_inst = c->reftab_inst;
+  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) a.tab[k] = (k < c->ntasks && ((c->h_task_table >> k) & 1u)) ? c->reftab[k].buf.p : nullptr;
+  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) a.tab_inst |= (unsigned)c->reftab[k].per_instance << k;
   a.nrows = c->task_rows;
   a.unconstr_dt = unconstr ? unconstr_dt : 0.0;
   // the 16-byte row pairs of Qqq need an even record stride and column length and an even field offset

@@ -294,8 +294,7 @@ int rtoc_set_grid(rtoc_ctx* c, const rtoc_grid* grid, int nstages) {
     if (nev != c->sto_nev) c->sto_on = 0;   // rtoc_sto_set_problem again
   }
   c->h_gt.clear();   // the grid times belong to the previous grid: rtoc_set_grid_times again
-  for (int k = 0; k < RTOC_MAX_TASK_COSTS; ++k) c->reftab_n[k] = 0;   // and so do the reference tables: rtoc_set_task_ref_table again
-  c->qtab_n = 0;   // ... and the rows of the q_ref table, not the fact that one is in use: rtoc_set_configuration_ref_table again
+  forget_grid_tables(c);   // and so do the reference tables and the rows of the q_ref table (not the fact that one is in use)
   return RTOC_OK;
 }
 
@@ -458,8 +457,8 @@ RecView rtoc::view(const rtoc_ctx* c) {
   v.dir = c->buf[RTOC_BUF_DIR].p, v.cone = c->buf[RTOC_BUF_CONE].p, v.se3 = c->buf[RTOC_BUF_SE3].p, v.dx0 = c->buf[RTOC_BUF_DX0].p;
   v.steps = (unsigned long long*)c->buf[RTOC_BUF_STEP].p;
   v.grid = c->d_grid.p, v.active = c->d_active.p;
-  v.positions = c->has_cpos ? c->d_cpos.p : nullptr, v.rotations = c->has_crot ? c->d_crot.p : nullptr;
-  v.placement_stride = c->cplace_inst ? c->nstages : 0;
+  v.positions = c->cpos.rows(), v.rotations = c->crot.rows();
+  v.placement_stride = c->cpos.per_instance ? c->cpos.nstages : 0;   // (the grid the rows were set for)
   v.dt_inst = c->sto_on ? c->d_dt.p : nullptr;
   v.model = c->d_model.p;
   v.nstages = c->nstages, v.batch = c->batch;

@@ -3,6 +3,7 @@ and by no other).  The device compiler emits every static __global__ function a 
 kernel header that reaches a second unit shows up as a second definition: read off the kernel-descriptor symbols (<name>.kd)
 of the gfx950 code object in every object file.  Symbol names only; no GPU."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -12,7 +13,18 @@ from robotoc_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "robotoc_amd", "csrc", "build")
-RUNTIME_UNITS = ["rtoc_capi", "rt_shapes", "rt_sweep", "rt_condense", "rt_eval_kkt", "rt_task_costs", "rt_sto", "rt_line_search", "rt_solve"]
+
+
+def _runtime_units():
+    """the units of the host runtime as the Makefile links them: the names on its RT_OBJS line"""
+    with open(os.path.join(ROOT, "robotoc_amd", "csrc", "Makefile")) as f:
+        line = next(ln for ln in f if ln.startswith("RT_OBJS"))
+    units = re.findall(r"\b(rtoc_capi|rt_\w+)\b", line)
+    assert len(units) >= 14 and len(set(units)) == len(units), line
+    return units
+
+
+RUNTIME_UNITS = _runtime_units()
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
