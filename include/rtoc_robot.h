@@ -120,9 +120,10 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * placement table and the reference tables are written on the device and stay there.  The gait wrapper itself (addStep, pop_front,
  * the solve call) stays with the caller: the contact sequence is structure the batch shares.  The crawl, the pace and the flying
  * trot (MPCCrawl, MPCPace, MPCFlyingTrot: their resetContactPlacements is the trot's line for line) plan through the same entry
- * points, chosen by rtoc_foot_step_planner::gait -- THE OTHER GAITS below.  Not here:
- * contact surfaces (point contacts have no rotation in the table), grids with switching-time optimisation, ParNMPC horizons (every
- * entry point below refuses one with RTOC_ERR_BAD_ARG).
+ * points, chosen by rtoc_foot_step_planner::gait -- THE OTHER GAITS below.  So does BipedWalkFootStepPlanner with what
+ * MPCBipedWalk::resetContactPlacements does (src/mpc/mpc_biped_walk.cpp:347-359), on a model of two contact surfaces, whose
+ * placements carry rotations -- THE BIPED WALK below.  Not here:
+ * grids with switching-time optimisation, ParNMPC horizons (every entry point below refuses one with RTOC_ERR_BAD_ARG).
  *
  * rtoc_set_foot_step_planner: setGaitPattern (mode RTOC_FOOT_STEP_FIXED: step_length, step_yaw, enable_stance_phase) or
  * setRaibertGaitPattern (RTOC_FOOT_STEP_RAIBERT: vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain; enable_stance_phase is
@@ -131,7 +132,8 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * the step-case sequence, which is shared structure like the grid, and must agree across the instances.  RTOC_ERR_BAD_ARG: they do
  * not; an unknown gait, mode or projection; enable_stance_phase outside {0, 1}; per_instance outside {0, 1}; in Raibert mode the checks of
  * the reference's setters (:63-76, raibert_heuristic.cpp:38-47): swing_time <= 0, stance_time < 0, gain <= 0; a model that has not
- * exactly four contacts, all of them point contacts, in the reference's order LF, LH, RF, RH = contacts 0..3.  RTOC_ERR_NOT_READY
+ * exactly four contacts, all of them point contacts, in the reference's order LF, LH, RF, RH = contacts 0..3 (RTOC_GAIT_BIPED_WALK:
+ * that has not exactly two contacts, both contact surfaces; it is refused on four point feet as they are on two surfaces).  RTOC_ERR_NOT_READY
  * without rtoc_set_robot_model.  p = NULL removes the planner with its state and plan (rtoc_foot_step_planner_init again after the next one is set).  A refused call leaves the planner in force.  Setting a planner keeps
  * the state of rtoc_foot_step_planner_init (the reference's setters do not touch it either).
  *
@@ -177,6 +179,33 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  *   planning_steps is limited to [0, RTOC_MAX_PLAN_STEPS - 1] so that it fits the arrays of rtoc_foot_step_plan_get.  There is no
  *   stance-phase option (enable_stance_phase is ignored).  In Raibert mode swing_time carries flying_time and stance_time <= 0 is
  *   refused by rtoc_set_foot_step_planner (:66); period 2 (flying_time + stance_time).
+ *
+ * THE BIPED WALK (gait = RTOC_GAIT_BIPED_WALK; line numbers: src/mpc/biped_walk_foot_step_planner.cpp).  The model has exactly two
+ * contacts, both RTOC_CONTACT_SURFACE: contact 0 is the left foot and contact 1 the right one (surfaceContactFrames()[0], [1]).
+ * enable_stance_phase carries enable_double_support_phase and stance_time double_support_time (checks :66-74, period
+ * 2 (swing_time + double_support_time), step yaw yaw_rate_cmd (swing_time + double_support_time), :75-84).
+ *   init (:89-108): the projected base rotation (BASE-ROTATION PROJECTION applies as above), left_to_right_leg_distance_ and
+ *   foot_height_to_com_height_, the feet measured relative to q.head<3>(), the base -- not to the centre of mass --, a cleared
+ *   filter and the copy of q.
+ *   plan (:111-277): statuses 0b11, 0b01 (the left foot stands, the right one swings) and 0b10; any other is RTOC_ERR_BAD_ARG and
+ *   nothing is launched.  0b11: current_step_ to the next even number with double support, to 0 without.  0b01 advances and turns
+ *   unless current_step_ % 4 == 1 (% 2 == 1 without double support), 0b10 unless % 4 == 3 (% 2 == 0).  Step 0: both feet from this
+ *   tick's kinematics with their full frame rotations; in single support the swing foot is placed at
+ *   R (local_stance - 0.5 R_yaw^T step_length -/+ distance e_y) + q.head<3>() with rotation R, local_stance measured in R_.front()
+ *   before the turn; the CoM is the midpoint of the two translations plus the stored height.  The loop is incremental: the moving
+ *   foot advances by p += s R step_length and takes the rotation R, the CoM by c R step_length, s = 1, c = 0.5; the right foot
+ *   moves on step % 4 == 1 and the left on % 4 == 3 with double support (nothing moves or turns on even steps), on odd and even
+ *   steps without; the first step of all (current_step_ == 0 && step == 1) has s = 0.5, and c = 0.5 with the heuristic, 0.25
+ *   without.  The plan has planning_steps + 2 steps: contactPositions(step)[2][3], contactSurfaces(step)[2][9], CoM(step)[3],
+ *   R(step)[9] per instance.
+ *   rtoc_foot_step_plan_get: `positions` holds 24 doubles per (instance, step), the [2][3] translations and then the [2][9]
+ *   rotations, row-major; the caller's array holds (RTOC_MAX_PLAN_STEPS + 2) * 24 doubles per instance; ok[] covers the rotations.
+ *   rtoc_foot_step_place: contactPlacements(phase + 1) of both feet -- the translations into the per-instance position table, the
+ *   rotations into the per-instance rotation table, which is created, or converted from a shared one, exactly as
+ *   rtoc_hold_contact_placements does it.
+ *   rtoc_foot_step_refs: foot_term[0..1] are the two feet; foot_term[2..3] must be negative.  "Some contact is inactive"
+ *   (mpc_periodic_com_ref.cpp:69-79, the configuration reference alike) is judged against the model's two contacts: 0b11 is every
+ *   contact.  A bit at or beyond 2 in any of phase_masks[nphases] is RTOC_ERR_BAD_ARG.
  *
  * rtoc_foot_step_plan_get: the plan of the first count <= batch instances -- positions[count][size][4][3], com[count][size][3],
  * R[count][size][9] (row-major), step_length[count][3] (the length in force; Raibert mode: what the heuristic planned),
@@ -224,18 +253,20 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
 #define RTOC_GAIT_CRAWL 1               /* CrawlFootStepPlanner                       */
 #define RTOC_GAIT_PACE 2                /* PaceFootStepPlanner                        */
 #define RTOC_GAIT_FLYING_TROT 3         /* FlyingTrotFootStepPlanner                  */
+#define RTOC_GAIT_BIPED_WALK 4          /* BipedWalkFootStepPlanner: two contact surfaces */
 typedef struct rtoc_foot_step_planner {
   int mode;                    /* RTOC_FOOT_STEP_*                                                       */
   int projection;              /* RTOC_PROJECT_*: the reference's ProjectRotationMatrix divides by R00^2 + 2 R01, which is
                                 * NOT the row's norm and crosses zero at a yaw of 0.427 rad (see above); 0 keeps it */
-  int enable_stance_phase;     /* fixed mode (ignored by the flying trot)                                */
+  int enable_stance_phase;     /* fixed mode (ignored by the flying trot; the biped walk: enable_double_support_phase) */
   int gait;                    /* RTOC_GAIT_*: 0, the value of a zeroed struct, is the trot              */
   double swing_time, stance_time, gain;   /* Raibert mode (gait timing; shared by the batch)             */
   double step_length[3], step_yaw;        /* fixed mode, per instance                                    */
   double vcom_cmd[3], yaw_rate_cmd;       /* Raibert mode, per instance                                  */
 } rtoc_foot_step_planner;
 typedef struct rtoc_foot_step_ref_params {
-  int foot_term[4];            /* index of the RTOC_TASK_FRAME_3D term of LF, LH, RF, RH; negative: left out */
+  int foot_term[4];            /* index of the RTOC_TASK_FRAME_3D term of LF, LH, RF, RH; negative: left out
+                                * (the biped walk: of the left and the right foot; [2..3] negative)        */
   int com_term;                /* index of the RTOC_TASK_COM term; negative: left out                       */
   int configuration;           /* != 0: the configuration reference                                         */
   double swing_height[4], swing_start_time[4], period_swing[4], period_stance[4];   /* MPCPeriodicSwingFootRef */

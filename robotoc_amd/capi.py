@@ -53,6 +53,7 @@ MAX_PLAN_STEPS = 32  # RTOC_MAX_PLAN_STEPS
 FOOT_STEP_FIXED, FOOT_STEP_RAIBERT = 0, 1  # RTOC_FOOT_STEP_*
 PROJECT_AS_REFERENCE, PROJECT_YAW = 0, 1  # RTOC_PROJECT_*
 GAIT_TROT, GAIT_CRAWL, GAIT_PACE, GAIT_FLYING_TROT = 0, 1, 2, 3  # RTOC_GAIT_*
+GAIT_BIPED_WALK = 4  # on two contact surfaces; the others on four point contacts
 
 
 class FootStepPlanner(C.Structure):
@@ -264,6 +265,7 @@ def _dp(a):
 
 class Context:
     """Thin RAII wrapper over rtoc_ctx: one context per (device, problem shape, batch)."""
+    _fs_gait = GAIT_TROT   # the gait of the foot-step planner in force: it decides the layout of rtoc_foot_step_plan_get's positions
 
     def __init__(self, dims, max_stages, batch, device=0):
         self.dims = dims
@@ -712,9 +714,10 @@ class Context:
             raise ValueError("per-instance commands need one planner struct per instance")
         arr = (FootStepPlanner * len(rows))(*rows)
         _chk(lib().rtoc_set_foot_step_planner(self._h, C.cast(arr, C.c_void_p), 1 if per_instance else 0))
+        self._fs_gait = rows[0].gait   # (a refused call raised above and leaves the planner in force)
 
     def foot_step_planner_init(self):
-        """rtoc_foot_step_planner_init: the planner's init (the same in all four gaits) at the q of set_initial_state, every instance"""
+        """rtoc_foot_step_planner_init: the planner's init (one for the four quadruped gaits, the biped walk's own) at the q of set_initial_state, every instance"""
         _chk(lib().rtoc_foot_step_planner_init(self._h))
 
     def foot_step_plan(self, t, contact_status0, planning_steps):
@@ -724,18 +727,28 @@ class Context:
 
     def foot_step_plan_get(self):
         """rtoc_foot_step_plan_get: a dict -- positions [batch, size, 4, 3], com [batch, size, 3], R [batch, size, 3, 3],
-        step_length [batch, 3], ok [batch] (bool), size, current_step"""
+        step_length [batch, 3], ok [batch] (bool), size, current_step.  The biped walk (a planner with gait = GAIT_BIPED_WALK was set
+        last): positions [batch, size, 2, 3] and one more key, surfaces [batch, size, 2, 3, 3]"""
         B, S = self.batch, MAX_PLAN_STEPS + 2
-        pos, com, R, sl = np.zeros((B, S * 12)), np.zeros((B, S * 3)), np.zeros((B, S * 9)), np.zeros((B, 3))
+        two = self._fs_gait == GAIT_BIPED_WALK
+        w = 24 if two else 12   # the library's `positions` per (instance, step): [4][3], or [2][3] and [2][9] behind them
+        pos, com, R, sl = np.zeros((B, S * w)), np.zeros((B, S * 3)), np.zeros((B, S * 9)), np.zeros((B, 3))
         ok, size, cur = np.zeros(B, dtype=np.int32), C.c_int(0), C.c_int(0)
         _chk(lib().rtoc_foot_step_plan_get(self._h, _dp(pos), _dp(com), _dp(R), _dp(sl), ok.ctypes.data_as(C.POINTER(C.c_int)), B,
                                            C.byref(size), C.byref(cur)))
         n = size.value   # the library packs [count][size][...] densely at the front of the arrays
-        return dict(positions=pos.reshape(-1)[:B * n * 12].reshape(B, n, 4, 3).copy(), com=com.reshape(-1)[:B * n * 3].reshape(B, n, 3).copy(),
-                    R=R.reshape(-1)[:B * n * 9].reshape(B, n, 3, 3).copy(), step_length=sl, ok=ok != 0, size=n, current_step=cur.value)
+        out = dict(com=com.reshape(-1)[:B * n * 3].reshape(B, n, 3).copy(),
+                   R=R.reshape(-1)[:B * n * 9].reshape(B, n, 3, 3).copy(), step_length=sl, ok=ok != 0, size=n, current_step=cur.value)
+        pos = pos.reshape(-1)[:B * n * w].reshape(B, n, w)
+        if two:
+            out["positions"], out["surfaces"] = pos[:, :, :6].reshape(B, n, 2, 3).copy(), pos[:, :, 6:].reshape(B, n, 2, 3, 3).copy()
+        else:
+            out["positions"] = pos.reshape(B, n, 4, 3).copy()
+        return out
 
     def foot_step_place(self, phase_of_grid_point):
-        """rtoc_foot_step_place: grid point i of every instance <- contactPositions(phase_of_grid_point[i] + 1) of its plan"""
+        """rtoc_foot_step_place: grid point i of every instance <- contactPositions(phase_of_grid_point[i] + 1) of its plan (the
+        biped walk: contactPlacements, the rotations into the per-instance rotation table)"""
         ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
         _chk(lib().rtoc_foot_step_place(self._h, ph.ctypes.data_as(C.POINTER(C.c_int)), ph.size))
 

@@ -22,12 +22,32 @@
 // The filter ring: 12 slots of (t, x, y) per instance, summed front to back as the deque of the reference is (:129-131), the new
 // sample last; all four lanes of an instance evaluate it from the same loads, the stores come after the last load.
 //
+// biped_walk_init_kernel / biped_walk_plan_kernel.  BipedWalkFootStepPlanner (src/mpc/biped_walk_foot_step_planner.cpp:89-277) on two
+// surface contacts (left = contact 0, right = contact 1).  Its step 0 places the swing foot from the STANCE foot's base-relative
+// offset (:161-166, :183-188), its feet carry a rotation each, and its centre of mass is the midpoint of the feet plus a stored
+// height: none of that is the quadrupeds' recurrence, so it has kernels of its own.  Mapping: one lane per (instance, foot),
+// FOOT-MAJOR within the wave -- lane l is foot l / 32 of instance 32 blockIdx.x + l % 32 -- so that the 32 lanes of a foot write 32
+// consecutive doubles (256 bytes) of every [slot][batch] array.  The other foot's translation arrives by __shfl across the two
+// halves (lane ^ 32), once as measured and once more after the swing foot is placed; R and the centre of mass are held by both
+// lanes of an instance.  The case chain comes in as the same FsPlanArgs the quadrupeds use (stance, pre_rotate, move[], com_scale[],
+// foot_scale[]): wave-uniform, no lane branches on its own data.  No LDS, no atomics.  The filter ring and the heuristic are
+// fs_filter_step_length / fs_filter_store, shared with foot_step_plan_kernel.
+// Loads per lane: 11 doubles of state (R, leg distance, CoM height), at most 12 x 3 of the filter ring and 8 of the command, each
+// a run of 32 consecutive doubles per half; 3 of the base position and (Raibert) 2 of the base velocity from x0, a state apart; 3 + 9
+// of its foot's frame placement from the kinematics' [batch][2][3 | 9], i.e. runs of 3 and 9 doubles 6 and 18 apart.  Stores per
+// step and lane: its foot's translation (3), its foot's rotation (9) and its half of [CoM | R] (6), all runs of 32 consecutive
+// doubles per half and slot; the lanes of foot 0 write the planner state back after the last load.  Lanes beyond the batch follow
+// the last instance and store nothing.
+//
 // foot_step_place_kernel / foot_step_refs_kernel.  Mapping: one lane per DOUBLE written, the doubles of an (instance, grid point)
 // pair adjacent and the pairs in table order, so that a wave writes one contiguous run of 512 bytes whatever the record size: 12
 // doubles per pair of the placement table (through RecView::placement), 13 per rtoc_task_ref_entry (its two ints as one 8-byte
 // word), nq per row of the configuration reference.  The lanes of a pair recompute its few scalars (cycle, rate) from the same
 // grid time.  Loads of the plan are gathers with the batch stride; the plan of a wave's instances is a few hundred bytes and
-// stays in L2.  blockIdx.y of the refs kernel selects the table (wave-uniform).  No LDS, no atomics.
+// stays in L2.  blockIdx.y of the refs kernel selects the table (wave-uniform).  No LDS, no atomics.  Both are templates over the
+// number of feet (FsPlanLayout): <4> is the quadrupeds' form; <2> reads the biped walk's plan, tests "some contact is inactive"
+// against 0b11, and its place form writes 6 + 18 doubles per pair, the translations into the position table and the rotations
+// into the rotation table (two runs per wave, one per table).
 //
 // Included by rt_foot_steps.hip alone (a kernel header belongs to the unit that launches from it).
 #pragma once
@@ -44,9 +64,27 @@ constexpr int FS_PLAN_POS = 0;     // contactPositions(step)[4][3]
 constexpr int FS_PLAN_COM = 12;    // CoM(step)[3]
 constexpr int FS_PLAN_R = 15;      // R(step)[9] row-major
 constexpr int FS_PLAN_SLOTS = 24;
+// the biped walk's plan: [step][FS_BIPED_SLOTS][batch]
+constexpr int FS_BIPED_POS = 0;    // contactPositions(step)[2][3]
+constexpr int FS_BIPED_SURF = 6;   // contactSurfaces(step)[2][9] row-major
+constexpr int FS_BIPED_COM = 24;   // CoM(step)[3]
+constexpr int FS_BIPED_R = 27;     // R(step)[9] row-major (behind the CoM: the two lanes of an instance halve [CoM | R])
+constexpr int FS_BIPED_SLOTS = 36;
+// where the place and refs kernels find a gait's plan, by the number of feet
+template <int NF> struct FsPlanLayout;
+template <> struct FsPlanLayout<4> {
+  static constexpr int POS = FS_PLAN_POS, COM = FS_PLAN_COM, R = FS_PLAN_R, SLOTS = FS_PLAN_SLOTS;
+  static constexpr unsigned FULL = 0xFu;
+};
+template <> struct FsPlanLayout<2> {
+  static constexpr int POS = FS_BIPED_POS, SURF = FS_BIPED_SURF, COM = FS_BIPED_COM, R = FS_BIPED_R, SLOTS = FS_BIPED_SLOTS;
+  static constexpr unsigned FULL = 0x3u;
+};
 // planner state: [FS_STATE_SLOTS][batch]
 constexpr int FS_ST_R = 0;         // R_.front(): the projected base rotation, advanced by every plan
 constexpr int FS_ST_LOCAL = 9;     // com_to_contact_position_local_[4][3]
+constexpr int FS_ST_LEGS = 9;      // the biped walk, in their place: left_to_right_leg_distance_, foot_height_to_com_height_
+constexpr int FS_ST_HEIGHT = 10;
 constexpr int FS_ST_LAST = 21;     // MovingWindowFilter: last_sampling_time_
 constexpr int FS_ST_AVG = 22;      // average_[2]
 constexpr int FS_ST_COUNT = 24;    // samples in the ring, and the slot of the oldest (both as doubles)
@@ -64,7 +102,7 @@ constexpr int FS_CMD_SLOTS = 8;
 struct FsInitArgs {
   const double* x0;      // [batch][nq + nv]
   const double* feet;    // [batch][4][3] world positions of the contact frames, com [batch][3] (contact_frame_placements_kernel)
-  const double* com;
+  const double* com;     // (the biped walk: feet [batch][2][3])
   double* state;         // [FS_STATE_SLOTS][batch]
   double* plan;          // step 0 receives com_ref_[0] and R_[0]
   double* q0;            // [batch][nq]: the q the configuration reference starts from
@@ -75,6 +113,7 @@ struct FsInitArgs {
 struct FsPlanArgs {
   const double* x0;
   const double* feet;
+  const double* feet_R;  // the biped walk alone: [batch][2][9] world rotations of the contact frames, row-major
   const double* cmd;     // [FS_CMD_SLOTS][batch]
   double* state;
   double* plan;
@@ -115,15 +154,11 @@ static __device__ __forceinline__ void fs_store_step(double* plan, int step, int
   s[(size_t)(FS_PLAN_COM + 3 * f) * B] = w0, s[(size_t)(FS_PLAN_COM + 3 * f + 1) * B] = w1, s[(size_t)(FS_PLAN_COM + 3 * f + 2) * B] = w2;
 }
 
-// TrotFootStepPlanner::init(q) (:91-106) at the q of rtoc_set_initial_state
-static __global__ __launch_bounds__(64) void foot_step_init_kernel(FsInitArgs a) {
+// the base rotation of q projected onto the z axis, as every planner's init does first (RTOC_PROJECT_*)
+static __device__ __forceinline__ rbd::M3 fs_projected_base_rotation(const double* q, int projection) {
   using namespace rbd;
-  const int lane = threadIdx.x, f = lane >> 4, B = a.batch;
-  const int b = blockIdx.x * 16 + (lane & 15);
-  if (b >= B) return;
-  const double* const q = a.x0 + (size_t)b * a.nx;
   M3 R = quat_R(q + 3);
-  if (a.projection == RTOC_PROJECT_YAW) {
+  if (projection == RTOC_PROJECT_YAW) {
     const double th = atan2(R.m[3], R.m[0]), s = sin(th), c = cos(th);
     R.m[0] = c, R.m[1] = -s, R.m[3] = s, R.m[4] = c;
   } else {
@@ -133,6 +168,17 @@ static __global__ __launch_bounds__(64) void foot_step_init_kernel(FsInitArgs a)
     for (int k = 0; k < 9; ++k) R.m[k] /= norm;
   }
   R.m[2] = 0.0, R.m[5] = 0.0, R.m[6] = 0.0, R.m[7] = 0.0, R.m[8] = 1.0;
+  return R;
+}
+
+// TrotFootStepPlanner::init(q) (:91-106) at the q of rtoc_set_initial_state
+static __global__ __launch_bounds__(64) void foot_step_init_kernel(FsInitArgs a) {
+  using namespace rbd;
+  const int lane = threadIdx.x, f = lane >> 4, B = a.batch;
+  const int b = blockIdx.x * 16 + (lane & 15);
+  if (b >= B) return;
+  const double* const q = a.x0 + (size_t)b * a.nx;
+  const M3 R = fs_projected_base_rotation(q, a.projection);
   const V3 com = ldv3(a.com + (size_t)b * 3);
   const V3 foot = ldv3(a.feet + (size_t)b * 12 + 3 * f);
   const V3 local = mulT(R, foot - com);
@@ -146,6 +192,48 @@ static __global__ __launch_bounds__(64) void foot_step_init_kernel(FsInitArgs a)
   // com_ref_[0] and R_[0] (:101-103) where the plan keeps them (beside them: where the feet are now; the plan's size stays 0)
   fs_store_step(a.plan, 0, B, b, f, foot, com, R);
   for (int k = f; k < a.nq; k += 4) a.q0[(size_t)b * a.nq + k] = q[k];
+}
+
+// ---- MovingWindowFilter::push_back (:113-135), RaibertHeuristic::planStepLength (raibert_heuristic.cpp:50-55), the head of every
+// gait's plan(): one copy for foot_step_plan_kernel and biped_walk_plan_kernel.  st, cmd: the state and the command at instance b ----
+struct FsFilter {
+  double last = 0.0, ax = 0.0, ay = 0.0, t = 0.0, x = 0.0, y = 0.0;
+  int count = 0, head = 0, slot = 0;
+  bool push = false;
+};
+static __device__ __forceinline__ rbd::V3 fs_filter_step_length(const FsPlanArgs& a, const double* st, const double* cmd, int b, FsFilter& F) {
+  const int B = a.batch;
+  const double* const v = a.x0 + (size_t)b * a.nx + a.nq;   // vcom_ = v.head<3>() (:131)
+  F.t = a.t, F.x = v[0], F.y = v[1];
+  F.last = st[(size_t)FS_ST_LAST * B], F.ax = st[(size_t)FS_ST_AVG * B], F.ay = st[(size_t)(FS_ST_AVG + 1) * B];
+  F.count = (int)st[(size_t)FS_ST_COUNT * B], F.head = (int)st[(size_t)FS_ST_HEAD * B];
+  if (F.count == 0) {
+    F.push = true, F.slot = 0, F.head = 0, F.count = 1;
+    F.ax = F.x, F.ay = F.y, F.last = F.t;
+  } else if (F.t - F.last >= a.min_period) {
+    F.push = true;
+    if (F.count == FS_RING) F.head = (F.head + 1) % FS_RING, --F.count;   // cannot happen with the window's own spacing
+    F.slot = (F.head + F.count) % FS_RING;
+    // pop_front while the front is older than the window (the new sample is never popped: t - t = 0)
+    while (F.count > 0 && F.t - st[(size_t)(FS_ST_RING + 3 * F.head) * B] > a.period) F.head = (F.head + 1) % FS_RING, --F.count;
+    double sx = 0.0, sy2 = 0.0;
+    for (int k = 0; k < F.count; ++k) {
+      const int slot = (F.head + k) % FS_RING;
+      sx += st[(size_t)(FS_ST_RING + 3 * slot + 1) * B], sy2 += st[(size_t)(FS_ST_RING + 3 * slot + 2) * B];
+    }
+    sx += F.x, sy2 += F.y;
+    ++F.count;
+    F.ax = sx / F.count, F.ay = sy2 / F.count, F.last = F.t;
+  }
+  const double pg = a.period * a.gain;
+  return rbd::mk(a.period * F.ax + pg * (cmd[(size_t)FS_CMD_VCOM * B] - F.ax), a.period * F.ay + pg * (cmd[(size_t)(FS_CMD_VCOM + 1) * B] - F.ay), 0.0);
+}
+// the filter's part of the state the next tick starts from; after the last load of the call
+static __device__ __forceinline__ void fs_filter_store(double* st, int B, const FsFilter& F) {
+  if (!F.push) return;
+  st[(size_t)(FS_ST_RING + 3 * F.slot) * B] = F.t, st[(size_t)(FS_ST_RING + 3 * F.slot + 1) * B] = F.x, st[(size_t)(FS_ST_RING + 3 * F.slot + 2) * B] = F.y;
+  st[(size_t)FS_ST_LAST * B] = F.last, st[(size_t)FS_ST_AVG * B] = F.ax, st[(size_t)(FS_ST_AVG + 1) * B] = F.ay;
+  st[(size_t)FS_ST_COUNT * B] = (double)F.count, st[(size_t)FS_ST_HEAD * B] = (double)F.head;
 }
 
 // TrotFootStepPlanner::plan (:125-284), and with other arguments PaceFootStepPlanner::plan (:124-283), CrawlFootStepPlanner::plan
@@ -166,36 +254,8 @@ static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a)
   V3 sl = mk(cmd[(size_t)FS_CMD_STEP * B], cmd[(size_t)(FS_CMD_STEP + 1) * B], cmd[(size_t)(FS_CMD_STEP + 2) * B]);
   const double yaw = cmd[(size_t)FS_CMD_YAW * B];
   const double sy = sin(yaw), cy = cos(yaw);
-  // ---- MovingWindowFilter::push_back (:113-135), RaibertHeuristic::planStepLength (raibert_heuristic.cpp:50-55) ----
-  double f_last = 0.0, f_ax = 0.0, f_ay = 0.0, f_t = 0.0, f_x = 0.0, f_y = 0.0;
-  int f_count = 0, f_head = 0, f_slot = 0;
-  bool f_push = false;
-  if (a.raibert) {
-    const double* const v = a.x0 + (size_t)b * a.nx + a.nq;   // vcom_ = v.head<3>() (:131)
-    f_t = a.t, f_x = v[0], f_y = v[1];
-    f_last = st[(size_t)FS_ST_LAST * B], f_ax = st[(size_t)FS_ST_AVG * B], f_ay = st[(size_t)(FS_ST_AVG + 1) * B];
-    f_count = (int)st[(size_t)FS_ST_COUNT * B], f_head = (int)st[(size_t)FS_ST_HEAD * B];
-    if (f_count == 0) {
-      f_push = true, f_slot = 0, f_head = 0, f_count = 1;
-      f_ax = f_x, f_ay = f_y, f_last = f_t;
-    } else if (f_t - f_last >= a.min_period) {
-      f_push = true;
-      if (f_count == FS_RING) f_head = (f_head + 1) % FS_RING, --f_count;   // cannot happen with the window's own spacing
-      f_slot = (f_head + f_count) % FS_RING;
-      // pop_front while the front is older than the window (the new sample is never popped: t - t = 0)
-      while (f_count > 0 && f_t - st[(size_t)(FS_ST_RING + 3 * f_head) * B] > a.period) f_head = (f_head + 1) % FS_RING, --f_count;
-      double sx = 0.0, sy2 = 0.0;
-      for (int k = 0; k < f_count; ++k) {
-        const int slot = (f_head + k) % FS_RING;
-        sx += st[(size_t)(FS_ST_RING + 3 * slot + 1) * B], sy2 += st[(size_t)(FS_ST_RING + 3 * slot + 2) * B];
-      }
-      sx += f_x, sy2 += f_y;
-      ++f_count;
-      f_ax = sx / f_count, f_ay = sy2 / f_count, f_last = f_t;
-    }
-    const double pg = a.period * a.gain;
-    sl = mk(a.period * f_ax + pg * (cmd[(size_t)FS_CMD_VCOM * B] - f_ax), a.period * f_ay + pg * (cmd[(size_t)(FS_CMD_VCOM + 1) * B] - f_ay), 0.0);
-  }
+  FsFilter flt;
+  if (a.raibert) sl = fs_filter_step_length(a, st, cmd, b, flt);
   V3 p = ldv3(a.feet + (size_t)b * 12 + 3 * f);
   V3 com = mk(0, 0, 0);
   if (a.flight) {
@@ -225,11 +285,7 @@ static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a)
 #pragma unroll
       for (int k = 0; k < 9; ++k) st[(size_t)(FS_ST_R + k) * B] = R.m[k];
       st[(size_t)FS_ST_STEP * B] = sl.x, st[(size_t)(FS_ST_STEP + 1) * B] = sl.y, st[(size_t)(FS_ST_STEP + 2) * B] = sl.z;
-      if (f_push) {
-        st[(size_t)(FS_ST_RING + 3 * f_slot) * B] = f_t, st[(size_t)(FS_ST_RING + 3 * f_slot + 1) * B] = f_x, st[(size_t)(FS_ST_RING + 3 * f_slot + 2) * B] = f_y;
-        st[(size_t)FS_ST_LAST * B] = f_last, st[(size_t)FS_ST_AVG * B] = f_ax, st[(size_t)(FS_ST_AVG + 1) * B] = f_ay;
-        st[(size_t)FS_ST_COUNT * B] = (double)f_count, st[(size_t)FS_ST_HEAD * B] = (double)f_head;
-      }
+      fs_filter_store(st, B, flt);
     }
   }
   // ---- the steps ahead (:212-277) ----
@@ -245,20 +301,135 @@ static __global__ __launch_bounds__(64) void foot_step_plan_kernel(FsPlanArgs a)
   }
 }
 
-// the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365): grid point i <- contactPositions(phase_i + 1)
+// ---- BipedWalkFootStepPlanner (src/mpc/biped_walk_foot_step_planner.cpp) ----
+// what the lane of foot f stores of a plan step: its foot's translation and rotation, and its half of [CoM | R]
+static __device__ __forceinline__ void fs_store_biped_step(double* plan, int step, int B, int b, int f, rbd::V3 p, const rbd::M3& S, rbd::V3 com,
+                                                           const rbd::M3& R) {
+  double* const s = plan + (size_t)step * FS_BIPED_SLOTS * B + b;
+  s[(size_t)(FS_BIPED_POS + 3 * f) * B] = p.x, s[(size_t)(FS_BIPED_POS + 3 * f + 1) * B] = p.y, s[(size_t)(FS_BIPED_POS + 3 * f + 2) * B] = p.z;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s[(size_t)(FS_BIPED_SURF + 9 * f + k) * B] = S.m[k];
+  // (selects, not an index into R: the rotation stays in registers)
+  const double w[6] = {f == 0 ? com.x : R.m[3], f == 0 ? com.y : R.m[4], f == 0 ? com.z : R.m[5],
+                       f == 0 ? R.m[0] : R.m[6], f == 0 ? R.m[1] : R.m[7], f == 0 ? R.m[2] : R.m[8]};
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[(size_t)(FS_BIPED_COM + 6 * f + k) * B] = w[k];
+}
+
+// init(q) (:89-108) at the q of rtoc_set_initial_state.  The plan is left alone: com_ref_ is cleared there, not seeded
+static __global__ __launch_bounds__(64) void biped_walk_init_kernel(FsInitArgs a) {
+  using namespace rbd;
+  const int lane = threadIdx.x, f = lane >> 5, B = a.batch;
+  const int b_raw = blockIdx.x * 32 + (lane & 31);
+  const bool valid = b_raw < B;
+  const int b = valid ? b_raw : B - 1;   // the lanes beyond the batch follow the last instance (the shuffles need every lane) and store nothing
+  const double* const q = a.x0 + (size_t)b * a.nx;
+  const M3 R = fs_projected_base_rotation(q, a.projection);
+  const V3 foot = ldv3(a.feet + (size_t)b * 6 + 3 * f);
+  const V3 local = mulT(R, foot - ldv3(q));   // relative to the base, q.head<3>() (:94-95)
+  const double other_y = __shfl(local.y, lane ^ 32, 64), other_z = __shfl(foot.z, lane ^ 32, 64);
+  const double distance = f == 0 ? local.y - other_y : other_y - local.y;                        // :96-97: left - right
+  const double foot_height = 0.5 * (f == 0 ? foot.z + other_z : other_z + foot.z);               // :98-99
+  const double height = a.com[(size_t)b * 3 + 2] - foot_height;                                  // :100
+  if (!valid) return;
+  if (f == 0) {
+    double* const st = a.state + b;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) st[(size_t)(FS_ST_R + k) * B] = R.m[k];
+    st[(size_t)FS_ST_LEGS * B] = distance, st[(size_t)FS_ST_HEIGHT * B] = height;
+    for (int k = FS_ST_LAST; k < FS_ST_RING; ++k) st[(size_t)k * B] = 0.0;   // vcom_moving_window_filter_.clear(); no step length yet
+  }
+  for (int k = f; k < a.nq; k += 2) a.q0[(size_t)b * a.nq + k] = q[k];
+}
+
+// plan (:111-277)
+static __global__ __launch_bounds__(64) void biped_walk_plan_kernel(FsPlanArgs a) {
+  using namespace rbd;
+  const int lane = threadIdx.x, f = lane >> 5, B = a.batch;
+  const int other = lane ^ 32;
+  const int b_raw = blockIdx.x * 32 + (lane & 31);
+  const bool valid = b_raw < B;
+  const int b = valid ? b_raw : B - 1;
+  double* const st = a.state + b;
+  M3 R;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R.m[k] = st[(size_t)(FS_ST_R + k) * B];
+  const double distance = st[(size_t)FS_ST_LEGS * B], height = st[(size_t)FS_ST_HEIGHT * B];
+  const double* const cmd = a.cmd + b;
+  V3 sl = mk(cmd[(size_t)FS_CMD_STEP * B], cmd[(size_t)(FS_CMD_STEP + 1) * B], cmd[(size_t)(FS_CMD_STEP + 2) * B]);
+  const double yaw = cmd[(size_t)FS_CMD_YAW * B];
+  const double sy = sin(yaw), cy = cos(yaw);
+  FsFilter flt;
+  if (a.raibert) sl = fs_filter_step_length(a, st, cmd, b, flt);   // :116-123
+  // ---- this tick's kinematics: both feet with their full frame rotations (:124-128) ----
+  const V3 base = ldv3(a.x0 + (size_t)b * a.nx);
+  V3 p = ldv3(a.feet + (size_t)b * 6 + 3 * f);
+  M3 S = ldm3(a.feet_R + (size_t)b * 18 + 9 * f);
+  V3 po = mk(__shfl(p.x, other, 64), __shfl(p.y, other, 64), __shfl(p.z, other, 64));
+  if (a.stance != 0x3u) {
+    // ---- single support (:148-191): the swing foot from the stance foot's offset in R_.front() (:131-135), then the turn ----
+    V3 loc = mulT(R, po - base);
+    if (a.pre_rotate) R = fs_yaw_times(sy, cy, R);
+    const V3 back = mk(cy * sl.x + sy * sl.y, cy * sl.y - sy * sl.x, sl.z);   // R_yaw^T step_length_
+    loc = loc - 0.5 * back;
+    loc.y += f == 1 ? -distance : distance;   // :163 the right foot, :185 the left
+    if (!((a.stance >> f) & 1u)) p = mul(R, loc) + base, S = R;
+    po = mk(__shfl(p.x, other, 64), __shfl(p.y, other, 64), __shfl(p.z, other, 64));
+  }
+  // com = 0.5 (left + right), the stored height on top (:145-146, :167-168, :189-190)
+  V3 com = 0.5 * (f == 0 ? p + po : po + p);
+  com.z += height;
+  if (valid) {
+    fs_store_biped_step(a.plan, 0, B, b, f, p, S, com, R);
+    if (f == 0) {
+      // the state the next tick starts from: R_.front(), the filter, the step length in force
+#pragma unroll
+      for (int k = 0; k < 9; ++k) st[(size_t)(FS_ST_R + k) * B] = R.m[k];
+      st[(size_t)FS_ST_STEP * B] = sl.x, st[(size_t)(FS_ST_STEP + 1) * B] = sl.y, st[(size_t)(FS_ST_STEP + 2) * B] = sl.z;
+      fs_filter_store(st, B, flt);
+    }
+  }
+  // ---- the steps ahead (:201-266): the moving foot advances from where it is and takes R ----
+  for (int s = 0; s < a.nloop; ++s) {
+    const unsigned mv = a.move[s];
+    if (mv) {
+      R = fs_yaw_times(sy, cy, R);
+      const V3 d = mul(R, sl);
+      com = com + a.com_scale[s] * d;
+      if ((mv >> f) & 1u) p = p + a.foot_scale[s] * d, S = R;
+    }
+    if (valid) fs_store_biped_step(a.plan, s + 1, B, b, f, p, S, com, R);
+  }
+}
+
+// the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365): grid point i <- contactPositions(phase_i + 1); NF = 2, the
+// loop of MPCBipedWalk::resetContactPlacements (mpc_biped_walk.cpp:347-359): contactPlacements(phase_i + 1), rotations included
 struct FsPlaceArgs {
   RecView rv;            // placement() of the per-instance table
   const double* plan;
   const int* phase;      // [nstages] GridInfo::phase relative to the first grid point
-  double* tab_pos;       // [batch][nstages][4][3]
+  double* tab_pos;       // [batch][nstages][NF][3]
+  double* tab_rot;       // NF = 2 alone: [batch][nstages][2][9]
 };
+template <int NF>
 static __global__ __launch_bounds__(256) void foot_step_place_kernel(FsPlaceArgs a) {
+  using L = FsPlanLayout<NF>;
+  constexpr int PER = NF == 4 ? 12 : 24;   // doubles per (instance, grid point): [NF][3], and for surface contacts [NF][9] behind them
   const int B = a.rv.batch, n = a.rv.nstages;
-  const size_t total = (size_t)B * n * 12;
+  const size_t total = (size_t)B * n * PER;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-    const int k = (int)(e % 12), st = (int)((e / 12) % n), b = (int)(e / 12 / n);
+    const int k = (int)(e % PER), st = (int)((e / PER) % n), b = (int)(e / PER / n);
     const int step = a.phase[st] + 1;
-    a.tab_pos[a.rv.placement(b, st, 4, k / 3) * 3 + k % 3] = a.plan[((size_t)step * FS_PLAN_SLOTS + FS_PLAN_POS + k) * B + b];
+    const double* const src = a.plan + (size_t)step * L::SLOTS * B + b;
+    if constexpr (NF == 4) {
+      a.tab_pos[a.rv.placement(b, st, 4, k / 3) * 3 + k % 3] = src[(size_t)(L::POS + k) * B];
+    } else {
+      const int r = k - 3 * NF;
+      if (r < 0)
+        a.tab_pos[a.rv.placement(b, st, NF, k / 3) * 3 + k % 3] = src[(size_t)(L::POS + k) * B];
+      else
+        a.tab_rot[a.rv.placement(b, st, NF, r / 9) * 9 + r % 9] = src[(size_t)(L::SURF + r) * B];
+    }
   }
 }
 
@@ -274,7 +445,7 @@ struct FsRefsArgs {
   const double* t;           // [nstages] grid times
   const int* phase;          // [nstages]
   const unsigned* masks;     // [nphases] active contacts of every contact phase
-  rtoc_task_ref_entry* tab[5];   // feet 0..3, CoM: [batch][nstages] or nullptr
+  rtoc_task_ref_entry* tab[5];   // feet 0..3 (the biped walk: 0..1), CoM: [batch][nstages] or nullptr
   double* qtab;              // [batch][nstages][nq] or nullptr
   int* qtab_active;          // [batch][nstages]
   FsPeriod per[6];           // feet 0..3, CoM, configuration
@@ -319,7 +490,9 @@ static __device__ __forceinline__ void fs_eigen_quat(const double* plan_R, size_
   }
 }
 
+template <int NF>
 static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a) {
+  using L = FsPlanLayout<NF>;
   const int which = blockIdx.y, B = a.batch, n = a.nstages;
   const FsPeriod pr = a.per[which];
   if (!pr.on) return;
@@ -334,20 +507,20 @@ static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a
       const double t = a.t[st];
       const unsigned mask = a.masks[ph];
       // isActive: the foot swings (:107-110) / some foot is in the air (mpc_periodic_com_ref.cpp:106-108)
-      const bool active = t > pr.t0 && (which < 4 ? !((mask >> which) & 1u) : (mask & 0xFu) != 0xFu);
+      const bool active = t > pr.t0 && (which < 4 ? !((mask >> which) & 1u) : (mask & L::FULL) != L::FULL);
       if (w < 9) {
         out[e] = (unsigned long long)__double_as_longlong((w % 4 == 0) ? 1.0 : 0.0);
       } else if (w == 12) {
         out[e] = active ? 1ull : 0ull;   // little endian: active in the low word, pad = 0
       } else {
         const int k = w - 9;
-        const int slot = which < 4 ? FS_PLAN_POS + 3 * which + k : FS_PLAN_COM + k;
-        const double x0 = a.plan[((size_t)ph * FS_PLAN_SLOTS + slot) * B + b];
+        const int slot = which < 4 ? L::POS + 3 * which + k : L::COM + k;
+        const double x0 = a.plan[((size_t)ph * L::SLOTS + slot) * B + b];
         double x = x0;   // inactive: the CoM reference's else branch (:100-102); a swing-foot reference is not updated, this stands in
         if (active) {
           const int cycle = (int)floor((t - pr.t0) / period);
           const double rate = (t - pr.t0 - cycle * period) / pr.period_active;
-          const double x1 = a.plan[((size_t)(ph + pr.nph) * FS_PLAN_SLOTS + slot) * B + b];
+          const double x1 = a.plan[((size_t)(ph + pr.nph) * L::SLOTS + slot) * B + b];
           x = (1.0 - rate) * x0 + rate * x1;
           if (which < 4 && k == 2) x += (rate < 0.5) ? 2 * rate * pr.height : 2 * (1 - rate) * pr.height;
         }
@@ -367,15 +540,15 @@ static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a
       const int ph = a.phase[st];
       const double t = a.t[st];
       double qa[4];
-      fs_eigen_quat(a.plan + ((size_t)ph * FS_PLAN_SLOTS + FS_PLAN_R) * B + b, B, qa);
+      fs_eigen_quat(a.plan + ((size_t)ph * L::SLOTS + L::R) * B + b, B, qa);
       const int c = k - 3;
       const double xa = c == 0 ? qa[0] : c == 1 ? qa[1] : c == 2 ? qa[2] : qa[3];
       x = xa;
-      if (t > pr.t0 && (a.masks[ph] & 0xFu) != 0xFu) {
+      if (t > pr.t0 && (a.masks[ph] & L::FULL) != L::FULL) {
         const int cycle = (int)floor((t - pr.t0) / period);
         const double rate = (t - pr.t0 - cycle * period) / pr.period_active;
         double qb[4];
-        fs_eigen_quat(a.plan + ((size_t)(ph + pr.nph) * FS_PLAN_SLOTS + FS_PLAN_R) * B + b, B, qb);
+        fs_eigen_quat(a.plan + ((size_t)(ph + pr.nph) * L::SLOTS + L::R) * B + b, B, qb);
         // Eigen's slerp (QuaternionBase::slerp): the near-parallel branch, the sign flip of the shorter arc
         const double one = 1.0 - 2.220446049250313e-16;
         const double d = qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2] + qa[3] * qb[3];

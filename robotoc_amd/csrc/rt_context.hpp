@@ -353,8 +353,8 @@ struct FootStepState {
   int fs_current_step = 0;   // current_step_: kept once, on the host
   int fs_size = 0;           // steps of the plan on the device; 0: none
   DevBuf<double> d_fs_cmd;   // [FS_CMD_SLOTS][batch] commands
-  DevBuf<double> d_fs_state; // [FS_STATE_SLOTS][batch] rotation, local offsets, filter
-  DevBuf<double> d_fs_plan;  // [RTOC_MAX_PLAN_STEPS + 2][FS_PLAN_SLOTS][batch]
+  DevBuf<double> d_fs_state; // [FS_STATE_SLOTS][batch] rotation, local offsets (the biped walk: leg distance, CoM height), filter
+  DevBuf<double> d_fs_plan;  // [RTOC_MAX_PLAN_STEPS + 2][FS_PLAN_SLOTS | FS_BIPED_SLOTS][batch]
   DevBuf<double> d_fs_q0;    // [batch][nq] the q of the init
   void clone_from(const FootStepState& src, CopyChain& dup) {
     if (!src.fs_on) return;
@@ -365,7 +365,8 @@ struct FootStepState {
     dup(d_fs_q0, src.d_fs_q0);
   }
   // not copied: the scratch of one call
-  DevBuf<double> d_fs_fk;    // [batch][4][3] foot positions + [batch][3] centre of mass (contact_frame_placements_kernel)
+  DevBuf<double> d_fs_fk;    // [batch][4][3] foot positions + [batch][3] centre of mass (contact_frame_placements_kernel); the biped
+                             // walk: [batch][2][3] + [batch][3] + [batch][2][9] frame rotations
   DevBuf<int> d_fs_phase;    // [max_stages] phase of every grid point + [RTOC_MAX_PLAN_STEPS + 2] masks of the phases
 };
 
@@ -513,9 +514,10 @@ int launch_unconstr_rows(rtoc_ctx* c, UnconstrRowsPhase phase);
 // rt_placements.hip, for rt_foot_steps.hip: a schedule that belongs to the grid in force (else RTOC_ERR_NOT_READY); the per-instance
 // placement table from whatever is in force, every instance starting from the shared values (need_rot: a rotation table too, created
 // if there is none); contact_frame_placements_kernel at the q of rtoc_set_initial_state, out_p[batch][ncontacts][3], out_com[batch][3]
+// (nullptr: left out) and, for the contact surfaces of the biped walk, out_R[batch][ncontacts][9] row-major
 int placements_ready(const rtoc_ctx* c);
 int placements_per_instance(rtoc_ctx* c, bool need_rot);
-int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com);
+int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com, double* out_R = nullptr);
 // rt_task_costs.hip
 int ensure_grid_times_inst(rtoc_ctx* c);
 int task_costs_ready(rtoc_ctx* c, bool unconstr);

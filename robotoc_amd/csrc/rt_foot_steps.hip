@@ -1,4 +1,4 @@
-// rt_foot_steps.hip -- the foot-step planners (trot, crawl, pace, flying trot) and the MPC references of every instance on the device: planner and commands, init,
+// rt_foot_steps.hip -- the foot-step planners (trot, crawl, pace, flying trot; the biped walk on two contact surfaces) and the MPC references of every instance on the device: planner and commands, init,
 // plan, the read-back of the plan, the placements of every contact phase, the three periodic references (foot_step_planner.hpp).
 #include <cmath>
 
@@ -12,6 +12,8 @@ using namespace rtoc;
   if ((c)->parnmpc) return RTOC_ERR_BAD_ARG;
 
 static constexpr int FS_MAX_STEPS = RTOC_MAX_PLAN_STEPS + 2;
+// the kinematics' scratch per instance: [4][3] + the centre of mass, or the biped walk's [2][3] + [3] + [2][9]
+static constexpr int FS_FK_DOUBLES = 27;
 
 // the gait of the reference's quadrupeds: exactly four point contacts (LF, LH, RF, RH = contacts 0..3)
 static bool four_point_feet(const rtoc_ctx* c) {
@@ -21,10 +23,19 @@ static bool four_point_feet(const rtoc_ctx* c) {
     if (m.contact_type[k] != RTOC_CONTACT_POINT) return false;
   return true;
 }
+// the biped of the reference's walk: exactly two surface contacts (left, right = contacts 0, 1 = surfaceContactFrames()[0], [1])
+static bool two_surface_feet(const rtoc_ctx* c) {
+  const rtoc_robot_model& m = c->h_model->m;
+  return m.ncontacts == 2 && m.contact_type[0] == RTOC_CONTACT_SURFACE && m.contact_type[1] == RTOC_CONTACT_SURFACE;
+}
+static bool biped(const rtoc_ctx* c) { return c->fs_shared.gait == RTOC_GAIT_BIPED_WALK; }
+// doubles per (instance, step) of the plan on the device, and feet
+static int plan_slots(const rtoc_ctx* c) { return biped(c) ? FS_BIPED_SLOTS : FS_PLAN_SLOTS; }
+static int plan_feet(const rtoc_ctx* c) { return biped(c) ? 2 : 4; }
 // setGaitPattern has no checks; setRaibertGaitPattern: trot_foot_step_planner.cpp:68-76 (the period of raibert_heuristic.cpp:39 is
-// positive with them, its gain check is the same one)
+// positive with them, its gain check is the same one; biped_walk_foot_step_planner.cpp:66-74 are the same three)
 static bool planner_valid(const rtoc_foot_step_planner& p) {
-  if (p.gait < RTOC_GAIT_TROT || p.gait > RTOC_GAIT_FLYING_TROT) return false;
+  if (p.gait < RTOC_GAIT_TROT || p.gait > RTOC_GAIT_BIPED_WALK) return false;
   if (p.mode != RTOC_FOOT_STEP_FIXED && p.mode != RTOC_FOOT_STEP_RAIBERT) return false;
   if (p.projection != RTOC_PROJECT_AS_REFERENCE && p.projection != RTOC_PROJECT_YAW) return false;
   if (p.enable_stance_phase != 0 && p.enable_stance_phase != 1) return false;
@@ -43,7 +54,7 @@ static bool stance_phase_enabled(const rtoc_foot_step_planner& p) {
   return p.mode == RTOC_FOOT_STEP_RAIBERT ? p.stance_time > 0.0 : p.enable_stance_phase != 0;   // :58, :86
 }
 
-// What tells the four gaits' plan() apart, by RTOC_GAIT_*.  Index [0]: without the stance phase, [1]: with it.
+// What tells the gaits' case chains apart, by RTOC_GAIT_*.  Index [0]: without the stance phase, [1]: with it.
 struct GaitSwing {
   unsigned status;   // a contact status with feet in the air ...
   int at[2];         // ... is the step with current_step_ % cycle == at: otherwise current_step_ advances and R turns
@@ -57,8 +68,9 @@ struct GaitRules {
   int incremental;             // 1: feet advance from where they are
   double com_scale;            // the CoM's share of step_length_ per moving step
   double periods;              // the Raibert period in units of swing_time + stance_time
+  unsigned full = 0b1111u;     // every foot on the ground
 };
-static const GaitRules GAITS[4] = {
+static const GaitRules GAITS[5] = {
     // trot (trot_foot_step_planner.cpp:161-202, :212-277): LH + RF first
     {{2, 4}, {{0b1001, 0b0110}, {0, 0b0110, 0, 0b1001}}, {{0b1001u, {1, 1}}, {0b0110u, {0, 3}}}, 2, 0, 0, 0.5, 2.0},
     // crawl (crawl_foot_step_planner.cpp:159-250, :260-359): RH, RF, LH, LF
@@ -68,6 +80,9 @@ static const GaitRules GAITS[4] = {
     {{2, 4}, {{0b0011, 0b1100}, {0, 0b1100, 0, 0b0011}}, {{0b0011u, {1, 1}}, {0b1100u, {0, 3}}}, 2, 0, 0, 0.5, 2.0},
     // flying trot (flying_trot_foot_step_planner.cpp:148-183, :190-230): a flight on every odd step
     {{4, 4}, {{0b1001, 0, 0b0110, 0}, {0b1001, 0, 0b0110, 0}}, {{0b1001u, {1, 1}}, {0b0110u, {3, 3}}}, 2, 1, 0, 0.5, 2.0},
+    // biped walk (biped_walk_foot_step_planner.cpp:136-191, :201-266): two feet, the right one (contact 1) first; 0b01: the left stands.
+    // Only the chain is shared with the quadrupeds: the recurrence itself is biped_walk_plan_kernel
+    {{2, 4}, {{0b01, 0b10}, {0, 0b10, 0, 0b01}}, {{0b01u, {1, 1}}, {0b10u, {0, 3}}}, 2, 0, 1, 0.5, 2.0, 0b11u},
 };
 
 int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int per_instance) {
@@ -78,10 +93,11 @@ int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int
   }
   if (per_instance != 0 && per_instance != 1) return RTOC_ERR_BAD_ARG;
   if (!c->h_model) return RTOC_ERR_NOT_READY;
-  if (!four_point_feet(c)) return RTOC_ERR_BAD_ARG;
   const int B = c->batch, n = per_instance ? B : 1;
   for (int b = 0; b < n; ++b)
     if (!planner_valid(p[b]) || !same_structure(p[b], p[0])) return RTOC_ERR_BAD_ARG;
+  // a gait and the feet it is written for: the quadrupeds' on four point contacts, the biped walk on two contact surfaces
+  if (!(p[0].gait == RTOC_GAIT_BIPED_WALK ? two_surface_feet(c) : four_point_feet(c))) return RTOC_ERR_BAD_ARG;
   std::vector<double> cmd((size_t)FS_CMD_SLOTS * B, 0.0);
   for (int b = 0; b < B; ++b) {
     const rtoc_foot_step_planner& q = p[per_instance ? b : 0];
@@ -101,9 +117,9 @@ int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int
 
 static int reserve_planner(rtoc_ctx* c) {
   const size_t B = c->batch, nq = c->h_model->m.nq;
-  HIP_TRY(c->d_fs_fk.reserve(B * 15));
+  HIP_TRY(c->d_fs_fk.reserve(B * FS_FK_DOUBLES));
   HIP_TRY(c->d_fs_state.reserve(B * FS_STATE_SLOTS));
-  HIP_TRY(c->d_fs_plan.reserve(B * FS_PLAN_SLOTS * FS_MAX_STEPS));
+  HIP_TRY(c->d_fs_plan.reserve(B * plan_slots(c) * FS_MAX_STEPS));
   HIP_TRY(c->d_fs_q0.reserve(B * nq));
   return RTOC_OK;
 }
@@ -113,15 +129,19 @@ int rtoc_foot_step_planner_init(rtoc_ctx* c) {
   if (!c->fs_on || !c->h_model || !c->d_x0.p) return RTOC_ERR_NOT_READY;
   int rc = reserve_planner(c);
   if (rc) return rc;
-  const int B = c->batch;
-  rc = launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
+  const int B = c->batch, nf = plan_feet(c);
+  double* const com = c->d_fs_fk.p + (size_t)B * nf * 3;
+  rc = launch_frame_positions(c, c->d_fs_fk.p, com);
   if (rc) return rc;
   FsInitArgs a{};
-  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.com = c->d_fs_fk.p + (size_t)B * 12;
+  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.com = com;
   a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p, a.q0 = c->d_fs_q0.p;
   a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
   a.projection = c->fs_shared.projection;
-  hipLaunchKernelGGL(foot_step_init_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
+  if (biped(c))
+    hipLaunchKernelGGL(biped_walk_init_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(foot_step_init_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fs_init = 1, c->fs_current_step = 0, c->fs_size = 0;
   return RTOC_OK;
@@ -137,7 +157,7 @@ static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int pla
   const bool raibert = p.mode == RTOC_FOOT_STEP_RAIBERT;
   int cur = *current_step;
   a->stance = status, a->pre_rotate = 0, a->flight = 0, a->incremental = g.incremental;
-  if (status == 0b1111u) {
+  if (status == g.full) {
     if (sp) {
       if (cur % 2 != 0) ++cur;
     } else {
@@ -166,6 +186,7 @@ static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int pla
       if (cur == 0 && step == 2) cs = raibert ? 0.5 : 0.25;
     } else if (cur == 0 && step == 1) {
       cs = raibert ? 0.5 : 0.25;   // trot_foot_step_planner.cpp:217-227, pace_foot_step_planner.cpp:216-226
+      if (p.gait == RTOC_GAIT_BIPED_WALK) fs = 0.5;   // biped_walk_foot_step_planner.cpp:206-216, :239-249: the right foot by half a step
     }
     a->move[s] = mv, a->com_scale[s] = cs, a->foot_scale[s] = fs;
   }
@@ -187,16 +208,22 @@ int rtoc_foot_step_plan(rtoc_ctx* c, double t, unsigned contact_status0, int pla
   int cur = c->fs_current_step;
   if (!plan_cases(c->fs_shared, contact_status0, planning_steps, c->fs_size > 0, &cur, &a)) return RTOC_ERR_BAD_ARG;
   const int B = c->batch;
-  HIP_TRY(c->d_fs_fk.reserve((size_t)B * 15));   // scratch: a clone starts without it
-  int rc = launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
+  HIP_TRY(c->d_fs_fk.reserve((size_t)B * FS_FK_DOUBLES));   // scratch: a clone starts without it
+  // the biped walk reads the frames' rotations, behind the centre of mass (which its plan() does not read)
+  double* const fk_R = biped(c) ? c->d_fs_fk.p + (size_t)B * 9 : nullptr;
+  int rc = biped(c) ? launch_frame_positions(c, c->d_fs_fk.p, nullptr, fk_R)
+                    : launch_frame_positions(c, c->d_fs_fk.p, c->d_fs_fk.p + (size_t)B * 12);
   if (rc) return rc;
-  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.cmd = c->d_fs_cmd.p, a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p;
+  a.x0 = c->d_x0.p, a.feet = c->d_fs_fk.p, a.feet_R = fk_R, a.cmd = c->d_fs_cmd.p, a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p;
   a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
   a.raibert = c->fs_shared.mode == RTOC_FOOT_STEP_RAIBERT;
   a.t = t;
   a.period = GAITS[c->fs_shared.gait].periods * (c->fs_shared.swing_time + c->fs_shared.stance_time);   // :77-79 (of every gait)
   a.min_period = 0.1 * a.period, a.gain = c->fs_shared.gain;
-  hipLaunchKernelGGL(foot_step_plan_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
+  if (biped(c))
+    hipLaunchKernelGGL(biped_walk_plan_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(foot_step_plan_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->fs_current_step = cur, c->fs_size = a.nloop + 1;
   return RTOC_OK;
@@ -210,18 +237,24 @@ int rtoc_foot_step_plan_get(rtoc_ctx* c, double* positions, double* com, double*
   if (size) *size = c->fs_size;
   if (current_step) *current_step = c->fs_current_step;
   const size_t B = c->batch, ns = c->fs_size;
-  std::vector<double> h(ns * FS_PLAN_SLOTS * B), sl(3 * B);
+  // where the gait's plan keeps what: the quadrupeds' positions are [4][3]; the biped walk's 24 doubles are contactPositions(step)[2][3]
+  // and contactSurfaces(step)[2][9] behind them, adjacent in the plan too
+  const bool two = biped(c);
+  const size_t slots = plan_slots(c);
+  const int npos = two ? 24 : 12, at_pos = two ? FS_BIPED_POS : FS_PLAN_POS, at_com = two ? FS_BIPED_COM : FS_PLAN_COM, at_R = two ? FS_BIPED_R : FS_PLAN_R;
+  static_assert(FS_BIPED_SURF == FS_BIPED_POS + 6, "translations and rotations are read back as one run");
+  std::vector<double> h(ns * slots * B), sl(3 * B);
   if (ns) HIP_TRY(hipMemcpyAsync(h.data(), c->d_fs_plan.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(sl.data(), c->d_fs_state.p + (size_t)FS_ST_STEP * B, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (size_t b = 0; b < (size_t)count; ++b) {
     bool fin = true;
     for (size_t s = 0; s < ns; ++s) {
-      const double* const src = h.data() + s * FS_PLAN_SLOTS * B + b;
-      for (int k = 0; k < FS_PLAN_SLOTS; ++k) fin = fin && std::isfinite(src[(size_t)k * B]);
-      for (int k = 0; positions && k < 12; ++k) positions[(b * ns + s) * 12 + k] = src[(size_t)(FS_PLAN_POS + k) * B];
-      for (int k = 0; com && k < 3; ++k) com[(b * ns + s) * 3 + k] = src[(size_t)(FS_PLAN_COM + k) * B];
-      for (int k = 0; R && k < 9; ++k) R[(b * ns + s) * 9 + k] = src[(size_t)(FS_PLAN_R + k) * B];
+      const double* const src = h.data() + s * slots * B + b;
+      for (size_t k = 0; k < slots; ++k) fin = fin && std::isfinite(src[k * B]);
+      for (int k = 0; positions && k < npos; ++k) positions[(b * ns + s) * npos + k] = src[(size_t)(at_pos + k) * B];
+      for (int k = 0; com && k < 3; ++k) com[(b * ns + s) * 3 + k] = src[(size_t)(at_com + k) * B];
+      for (int k = 0; R && k < 9; ++k) R[(b * ns + s) * 9 + k] = src[(size_t)(at_R + k) * B];
     }
     for (int k = 0; step_length && k < 3; ++k) step_length[b * 3 + k] = sl[(size_t)k * B + b];
     if (ok) ok[b] = fin ? 1 : 0;
@@ -245,16 +278,20 @@ int rtoc_foot_step_place(rtoc_ctx* c, const int* phase_of_grid_point, int nstage
   if (!c->fs_on || !c->fs_init || c->fs_size < 2 || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;
   int rc = placements_ready(c);
   if (rc) return rc;
-  if (nstages != c->nstages || !four_point_feet(c)) return RTOC_ERR_BAD_ARG;
+  const bool two = biped(c);
+  if (nstages != c->nstages || !(two ? two_surface_feet(c) : four_point_feet(c))) return RTOC_ERR_BAD_ARG;
   for (int i = 0; i < nstages; ++i)
     if (phase_of_grid_point[i] < 0 || phase_of_grid_point[i] > c->fs_size - 2) return RTOC_ERR_BAD_ARG;
   rc = upload_phases(c, phase_of_grid_point, nstages, nullptr, 0);
   if (rc) return rc;
-  rc = placements_per_instance(c, false);
+  rc = placements_per_instance(c, two);   // contact surfaces: a rotation table too, as rtoc_hold_contact_placements has it
   if (rc) return rc;
   auto a = view_args<FsPlaceArgs>(c);
-  a.plan = c->d_fs_plan.p, a.phase = c->d_fs_phase.p, a.tab_pos = c->cpos.rows();
-  hipLaunchKernelGGL(foot_step_place_kernel, dim3(blocks_for((size_t)c->batch * nstages * 12)), dim3(256), 0, c->stream, a);
+  a.plan = c->d_fs_plan.p, a.phase = c->d_fs_phase.p, a.tab_pos = c->cpos.rows(), a.tab_rot = two ? c->crot.rows() : nullptr;
+  if (two)
+    hipLaunchKernelGGL(foot_step_place_kernel<2>, dim3(blocks_for((size_t)c->batch * nstages * 24)), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(foot_step_place_kernel<4>, dim3(blocks_for((size_t)c->batch * nstages * 12)), dim3(256), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   c->vals_fresh = 0;   // the contact rows of the values pre-pass belong to the previous placements
   return RTOC_OK;
@@ -268,6 +305,13 @@ int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const i
   if (!c->fs_on || !c->fs_init || c->fs_size < 1 || !c->d_fs_q0.p || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;
   if (nstages != c->nstages || nphases < 1 || nphases > FS_MAX_STEPS) return RTOC_ERR_BAD_ARG;
   if ((int)c->h_gt.size() != c->nstages || !c->d_gt.p) return RTOC_ERR_NOT_READY;   // rtoc_set_grid_times
+  // ---- the feet of the gait: a biped has no third and fourth swing-foot reference, and no mask bit for them ----
+  const int nf = plan_feet(c);
+  const unsigned full = nf == 2 ? 0x3u : 0xFu;
+  for (int k = nf; k < 4; ++k)
+    if (r->foot_term[k] >= 0) return RTOC_ERR_BAD_ARG;
+  for (int k = 0; nf == 2 && k < nphases; ++k)
+    if (phase_masks[k] & ~full) return RTOC_ERR_BAD_ARG;
   // ---- the six references as the kernel takes them; the arguments the reference's constructors refuse ----
   FsRefsArgs a{};
   int term_of[5];
@@ -307,7 +351,7 @@ int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const i
     for (int k = 0; k < 6; ++k) {
       const FsPeriod& p = a.per[k];
       if (!p.on) continue;
-      const bool reads_ahead = c->h_gt[i] > p.t0 && (k < 4 ? !((mask >> k) & 1u) : (mask & 0xFu) != 0xFu);
+      const bool reads_ahead = c->h_gt[i] > p.t0 && (k < 4 ? !((mask >> k) & 1u) : (mask & full) != full);
       if (reads_ahead && ph + p.nph >= c->fs_size) return RTOC_ERR_BAD_ARG;
     }
   }
@@ -325,7 +369,10 @@ int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const i
   a.qtab = r->configuration ? c->qtab.target() : nullptr, a.qtab_active = r->configuration ? c->qtab_active.target() : nullptr;
   a.batch = c->batch, a.nstages = nstages, a.nq = (int)nq;
   const size_t most = (size_t)c->batch * nstages * (nq > (size_t)FS_ENTRY_WORDS ? nq : (size_t)FS_ENTRY_WORDS);
-  hipLaunchKernelGGL(foot_step_refs_kernel, dim3(blocks_for(most), 6), dim3(256), 0, c->stream, a);
+  if (nf == 2)
+    hipLaunchKernelGGL(foot_step_refs_kernel<2>, dim3(blocks_for(most), 6), dim3(256), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(foot_step_refs_kernel<4>, dim3(blocks_for(most), 6), dim3(256), 0, c->stream, a);
   HIP_TRY(hipGetLastError());
   // the tables are per instance and belong to the grid in force
   for (int k = 0; k < 5; ++k)

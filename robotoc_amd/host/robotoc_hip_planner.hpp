@@ -16,6 +16,7 @@
 #define ROBOTOC_HIP_PLANNER_HPP_
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <limits>
 #include <stdexcept>
@@ -504,11 +505,11 @@ class SolutionInterpolator {
   bool has_ = false;
 };
 
-// robotoc::TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner
-// (src/mpc/{trot,crawl,pace,flying_trot}_foot_step_planner.cpp) for the batch of a context: thin mirrors over
+// robotoc::TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner, BipedWalkFootStepPlanner
+// (src/mpc/{trot,crawl,pace,flying_trot,biped_walk}_foot_step_planner.cpp) for the batch of a context: thin mirrors over
 // rtoc_set_foot_step_planner / rtoc_foot_step_planner_init / rtoc_foot_step_plan / rtoc_foot_step_plan_get (include/rtoc_robot.h).
 // The planning runs on the device from the q, v of rtoc_set_initial_state; commands are one for the batch or one per instance.
-// FootStepPlannerBase is what the four share; a gait's class names its RTOC_GAIT_*, its legal contact statuses and its setters.
+// FootStepPlannerBase is what the five share; a gait's class names its RTOC_GAIT_*, its legal contact statuses and its setters.
 class FootStepPlannerBase {
  public:
   // init(q) / plan(t, q, v, ..) at the initial state of the context (rtoc_set_initial_state)
@@ -528,8 +529,8 @@ class FootStepPlannerBase {
   }
   int size() { return get(), size_; }
   int currentStep() { return get(), current_step_; }
-  // of instance b: [4][3], [3], [9] row-major
-  const double* contactPositions(const int b, const int step) { return get(), &pos_[(static_cast<size_t>(b) * size_ + step) * 12]; }
+  // of instance b: [4][3] (the biped walk: [2][3]), [3], [9] row-major
+  const double* contactPositions(const int b, const int step) { return get(), &pos_[(static_cast<size_t>(b) * size_ + step) * width_]; }
   const double* CoM(const int b, const int step) { return get(), &com_[(static_cast<size_t>(b) * size_ + step) * 3]; }
   const double* R(const int b, const int step) { return get(), &R_[(static_cast<size_t>(b) * size_ + step) * 9]; }
   const double* stepLength(const int b) { return get(), &sl_[static_cast<size_t>(b) * 3]; }
@@ -537,8 +538,8 @@ class FootStepPlannerBase {
 
  protected:
   FootStepPlannerBase(rtoc_ctx* ctx, const int batch, const int projection, const int gait, const char* name,
-                      const std::vector<unsigned>& statuses)
-      : ctx_(ctx), batch_(batch), projection_(projection), gait_(gait), size_(0), current_step_(0), fresh_(false),
+                      const std::vector<unsigned>& statuses, const int width = 12)
+      : ctx_(ctx), batch_(batch), projection_(projection), gait_(gait), size_(0), current_step_(0), width_(width), fresh_(false),
         tag_(std::string("[") + name + "]"), statuses_(statuses) {
     if (!ctx || batch < 1) throw std::invalid_argument(tag_ + " a context and its batch size");
   }
@@ -557,10 +558,10 @@ class FootStepPlannerBase {
   }
   // air_name: what the gait calls the time in the air; stance_may_be_zero: the trot's check (:71) or the flying trot's (:66)
   void setRaibert(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double air_time, const char* air_name,
-                  const double stance_time, const bool stance_may_be_zero, const double gain) {
+                  const double stance_time, const bool stance_may_be_zero, const double gain, const char* stance_name = "stance_time") {
     if (air_time <= 0.0) throw std::out_of_range(tag_ + " invalid argument: '" + air_name + "' must be positive!");
-    if (stance_may_be_zero && stance_time < 0.0) throw std::out_of_range(tag_ + " invalid argument: 'stance_time' must be non-negative!");
-    if (!stance_may_be_zero && stance_time <= 0.0) throw std::out_of_range(tag_ + " invalid argument: 'stance_time' must be positive!");
+    if (stance_may_be_zero && stance_time < 0.0) throw std::out_of_range(tag_ + " invalid argument: '" + stance_name + "' must be non-negative!");
+    if (!stance_may_be_zero && stance_time <= 0.0) throw std::out_of_range(tag_ + " invalid argument: '" + stance_name + "' must be positive!");
     if (gain <= 0.0) throw std::out_of_range(tag_ + " invalid argument: 'gain' must be positive!");
     const bool inst = perInstance(vcom_cmd.size(), 3, "vcom_cmd") | perInstance(yaw_rate_cmd.size(), 1, "yaw_rate_cmd");
     std::vector<rtoc_foot_step_planner> p(inst ? batch_ : 1, rtoc_foot_step_planner());
@@ -584,7 +585,7 @@ class FootStepPlannerBase {
   void get() {
     if (fresh_) return;
     const size_t B = batch_, S = RTOC_MAX_PLAN_STEPS + 2;
-    pos_.assign(B * S * 12, 0.0), com_.assign(B * S * 3, 0.0), R_.assign(B * S * 9, 0.0), sl_.assign(B * 3, 0.0), ok_.assign(B, 0);
+    pos_.assign(B * S * width_, 0.0), com_.assign(B * S * 3, 0.0), R_.assign(B * S * 9, 0.0), sl_.assign(B * 3, 0.0), ok_.assign(B, 0);
     chk(rtoc_foot_step_plan_get(ctx_, pos_.data(), com_.data(), R_.data(), sl_.data(), ok_.data(), batch_, &size_, &current_step_),
         "rtoc_foot_step_plan_get");
     fresh_ = true;
@@ -594,6 +595,7 @@ class FootStepPlannerBase {
   }
   rtoc_ctx* ctx_;
   int batch_, projection_, gait_, size_, current_step_;
+  int width_;   // doubles of rtoc_foot_step_plan_get's `positions` per (instance, step): 12, the biped walk's 24
   bool fresh_;
   std::string tag_;
   std::vector<unsigned> statuses_;
@@ -640,6 +642,33 @@ class FlyingTrotFootStepPlanner : public FootStepPlannerBase {
   void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double flying_time,
                              const double stance_time, const double gain) {
     setRaibert(vcom_cmd, yaw_rate_cmd, flying_time, "flying_time", stance_time, false, gain);
+  }
+};
+
+// biped_walk_foot_step_planner.cpp:49-86 on a model of two contact surfaces (left = contact 0, right = contact 1): statuses 0b11,
+// 0b01 (the left foot stands) and 0b10; every foot of the plan carries a rotation.  place() writes contactPlacements(phase + 1),
+// the loop of MPCBipedWalk::resetContactPlacements (mpc_biped_walk.cpp:347-359), translations and rotations
+class BipedWalkFootStepPlanner : public FootStepPlannerBase {
+ public:
+  // a placement as contactPlacements(step)[foot] gives it: translation[3] and rotation[9] row-major, pointers into the read-back
+  struct Placement {
+    const double* translation;
+    const double* rotation;
+  };
+  BipedWalkFootStepPlanner(rtoc_ctx* ctx, const int batch, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : FootStepPlannerBase(ctx, batch, projection, RTOC_GAIT_BIPED_WALK, "BipedWalkFootStepPlanner", {0x3u, 0x1u, 0x2u}, 24) {}
+  void setGaitPattern(const std::vector<double>& step_length, const std::vector<double>& step_yaw, const bool enable_double_support_phase) {
+    setFixed(step_length, step_yaw, enable_double_support_phase);
+  }
+  void setRaibertGaitPattern(const std::vector<double>& vcom_cmd, const std::vector<double>& yaw_rate_cmd, const double swing_time,
+                             const double double_support_time, const double gain) {
+    setRaibert(vcom_cmd, yaw_rate_cmd, swing_time, "swing_time", double_support_time, true, gain, "double_support_time");
+  }
+  // of instance b: [2][9] row-major, behind the [2][3] translations in the read-back
+  const double* contactSurfaces(const int b, const int step) { return contactPositions(b, step) + 6; }
+  std::array<Placement, 2> contactPlacements(const int b, const int step) {
+    const double* const p = contactPositions(b, step);
+    return {Placement{p, p + 6}, Placement{p + 3, p + 15}};
   }
 };
 

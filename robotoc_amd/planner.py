@@ -1,7 +1,7 @@
-"""TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner and FlyingTrotFootStepPlanner over a capi.Context: the surface
-of the reference's classes (src/mpc/{trot,crawl,pace,flying_trot}_foot_step_planner.cpp) for a batch, every instance with its own
-command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); these shells hold no state of their own beyond
-the commands they were given.  The four share one body; a class names its gait, its legal contact statuses and what its setters
+"""TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner and BipedWalkFootStepPlanner over a
+capi.Context: the surface of the reference's classes (src/mpc/{trot,crawl,pace,flying_trot,biped_walk}_foot_step_planner.cpp) for a
+batch, every instance with its own command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); these shells
+hold no state of their own beyond the commands they were given.  The five share one body; a class names its gait, its legal contact statuses and what its setters
 check."""
 import numpy as np
 
@@ -137,6 +137,45 @@ class PaceFootStepPlanner(TrotFootStepPlanner):
     """src/mpc/pace_foot_step_planner.cpp: the trot with the pairs (LF, LH) and (RF, RH); the setters are the trot's"""
     GAIT = capi.GAIT_PACE
     STATUSES = (0b1111, 0b0011, 0b1100)
+
+
+class BipedWalkFootStepPlanner(TrotFootStepPlanner):
+    """src/mpc/biped_walk_foot_step_planner.cpp on a robot model of two contact surfaces (left = contact 0, right = contact 1):
+    one foot stands while the other swings, the right one first; every foot of the plan carries a rotation, which
+    reset_contact_placements writes into the per-instance rotation table beside the translations
+    (MPCBipedWalk::resetContactPlacements, src/mpc/mpc_biped_walk.cpp:347-359).  refs.foot_term[2:] must be negative and the
+    phase masks have two bits."""
+    GAIT = capi.GAIT_BIPED_WALK
+    STATUSES = (0b11, 0b01, 0b10)   # both feet, the left foot alone (the right one swings), the right foot alone
+
+    def set_gait_pattern(self, step_length, step_yaw, enable_double_support_phase):
+        """setGaitPattern (:49-58): step_length [3] or [batch, 3], step_yaw a scalar or [batch]"""
+        super().set_gait_pattern(step_length, step_yaw, enable_double_support_phase)
+
+    def set_raibert_gait_pattern(self, vcom_cmd, yaw_rate_cmd, swing_time, double_support_time, gain):
+        """setRaibertGaitPattern (:61-86): as the trot's, with double_support_time where that has stance_time"""
+        super().set_raibert_gait_pattern(vcom_cmd, yaw_rate_cmd, swing_time, double_support_time, gain)
+
+    @staticmethod
+    def _check_timing(swing_time, double_support_time, gain):   # :66-74
+        if swing_time <= 0.0:
+            raise ValueError("'swing_time' must be positive")
+        if double_support_time < 0.0:
+            raise ValueError("'double_support_time' must be non-negative")
+        if gain <= 0.0:
+            raise ValueError("'gain' must be positive")
+
+    def contact_positions(self, step):
+        """[batch, 2, 3]"""
+        return self._get()["positions"][:, step]
+
+    def contact_surfaces(self, step):
+        """[batch, 2, 3, 3]"""
+        return self._get()["surfaces"][:, step]
+
+    def contact_placements(self, step):
+        """(rotations [batch, 2, 3, 3], translations [batch, 2, 3]): contactPlacements(step) as SE3's two parts"""
+        return self.contact_surfaces(step), self.contact_positions(step)
 
 
 class FlyingTrotFootStepPlanner(TrotFootStepPlanner):
