@@ -32,13 +32,13 @@ struct CcArgs {
 };
 enum { CC_INIT = 0, CC_LINEARIZE = 1 };
 
+// LDS: the per-level carve (rbd::LevelCarve), then q
 __host__ __device__ constexpr size_t cc_lds_bytes(int nlevels, int njoints, int ncontacts) {
-  return sizeof(double) * ((size_t)nlevels * (32 + 6 * 64) + njoints * rbd::JP + ncontacts * rbd::CP + (RTOC_MAX_JOINTS + 8));
+  return sizeof(double) * (rbd::LevelCarve(nlevels, njoints, ncontacts).doubles() + (RTOC_MAX_JOINTS + 8));
 }
 
 static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
-  using rbd::CP;
-  using rbd::JP;
+  using namespace rbd::slots;
   using rbd::M3;
   using rbd::V3;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -50,11 +50,12 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
   if (g.dimf == 0 || (g.type == RTOC_GRID_IMPACT && !a.impact_cones)) return;
   const unsigned act = a.rv.active[st];
   const int nv = a.rv.nv(), nb = a.md.njoints, ncon = a.md.ncontacts, nlev = a.md.nlevels, cd = a.contact_dim;
+  const rbd::LevelCarve carve(nlev, nb, ncon);
   double* const lval = smem;
-  double* const ltan = lval + (size_t)nlev * 32;
-  double* const sjm = ltan + (size_t)nlev * 6 * 64;
-  double* const scm = sjm + nb * JP;
-  double* const sq = scm + ncon * CP;
+  double* const ltan = lval + carve.val;
+  double* const sjm = ltan + carve.tan;
+  double* const scm = sjm + carve.joint;
+  double* const sq = scm + carve.contact;
   const size_t rec = (size_t)b * a.rv.nstages + st;
   const double* const s = a.rv.sol_at(rec);
   double* const lx = a.rv.kkt ? a.rv.kkt_at(rec) + a.rv.kkt_off(RTOC_KKT_LX) : nullptr;
@@ -73,41 +74,32 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
   const int j = lane;
   const bool lane_on = j < nv;
   const bool lin = a.mode == CC_LINEARIZE;
-  auto LV = [&](int lev, int k) -> double& { return lval[lev * 32 + k]; };
-  auto LT = [&](int lev, int k) -> double& { return ltan[((size_t)lev * 6 + k) * 64 + lane]; };
+  auto LV = [&](int lev, int k) -> double& { return lval[lev * LVL_VAL + k]; };
+  auto LT = [&](int lev, int k) -> double& { return ltan[((size_t)lev * LVL_TAN + k) * LVL_LANES + lane]; };   // 0: linear, 3: angular
   auto JM = [&](int i, int k) -> const double& { return sjm[i * JP + k]; };
   double lq = 0.0;
   for (int i = 0; i < nb; ++i) {
-    const int d = (int)JM(i, 31), iq = (int)JM(i, 29), iv = (int)JM(i, 30);
-    const bool ff = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER;
+    const int d = (int)JM(i, J_DEPTH), iq = (int)JM(i, J_IDXQ), iv = (int)JM(i, J_IDXV);
+    const bool ff = (int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER;
     const bool own = lane_on && j >= iv && j < iv + (ff ? 6 : 1);
-    M3 Rj;
-    V3 pj = rbd::mk(0, 0, 0);
-    if (ff) {
-      Rj = rbd::quat_R(sq + iq + 3);
-      pj = rbd::ldv3(sq + iq);
-    } else {
-      const double th = sq[iq];
-      Rj = rbd::revolute_R(rbd::ldv3(&JM(i, 12)), sin(th), cos(th));
-    }
     M3 R;
     V3 p;
-    rbd::joint_placement(&JM(i, 0), Rj, pj, R, p);
+    rbd::joint_placement_at(sjm + i * JP, ff, sq + iq, R, p);
     M3 oR = R;
     V3 wj = rbd::mk(0, 0, 0);   // body-frame angular velocity of body i per unit rate of dof j
     if (d > 0) {
-      oR = rbd::mul(rbd::ldm3(&LV(d - 1, 12)), R);
+      oR = rbd::mul(rbd::ldm3(&LV(d - 1, V_OR)), R);
       wj = rbd::mulT(R, rbd::mk(LT(d - 1, 3), LT(d - 1, 4), LT(d - 1, 5)));
     }
-    if (own) wj = wj + (ff ? rbd::unit_twist(j - iv).a : rbd::ldv3(&JM(i, 12)));
+    if (own) wj = wj + (ff ? rbd::unit_twist(j - iv).a : rbd::ldv3(&JM(i, J_AXIS)));
 #pragma unroll
-    for (int k = 0; k < 9; ++k) LV(d, 12 + k) = oR.m[k];
+    for (int k = 0; k < 9; ++k) LV(d, V_OR + k) = oR.m[k];
     LT(d, 3) = wj.x, LT(d, 4) = wj.y, LT(d, 5) = wj.z;
     int k = 0;  // index among the active contacts
     for (int c = 0; c < ncon; ++c) {
       const bool on = (act >> c) & 1u;
-      if (on && (int)scm[c * CP + 14] == i) {
-        const M3 Rwf = rbd::mul(oR, rbd::ldm3(&scm[c * CP]));
+      if (on && (int)scm[c * CP + C_PARENT] == i) {
+        const M3 Rwf = rbd::mul(oR, rbd::ldm3(&scm[c * CP + C_R]));
         const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
         M3 Rs;
 #pragma unroll
@@ -156,7 +148,7 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
           if (lane_on) {    // column j of dg/dq
             // the reference crosses the LOCAL-frame angular Jacobian column with the WORLD-frame force (robot.hxx:247-253,
             // 275-287: getFrameJacobian(..., pinocchio::LOCAL, ...)); the derivative of R_wf f is w_world x f_W
-            const V3 wxf = rbd::cross(a.exact_jacobian ? rbd::mul(oR, wj) : rbd::mulT(rbd::ldm3(&scm[c * CP]), wj), fW);
+            const V3 wxf = rbd::cross(a.exact_jacobian ? rbd::mul(oR, wj) : rbd::mulT(rbd::ldm3(&scm[c * CP + C_R]), wj), fW);
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
               const double e = rbd::dot(row[r], wxf);
@@ -177,16 +169,16 @@ static __global__ __launch_bounds__(64) void contact_cone_kernel(CcArgs a) {
 namespace rtoc {
 
 // The same rows (LINEARIZE) from the kinematics the rigid-body pre-pass has already computed (rbd_values_kernel: the world
-// rotation of every body, slots 12..20 of its block): no tree walk.  The world-aligned angular Jacobian column of a contact
+// rotation of every body, V_OR of its value block): no tree walk.  The world-aligned angular Jacobian column of a contact
 // frame for dof j is oR_body(j) axis_j if the dof lies on the path from the root to the contact's body, else zero.
 // One wave per (instance, grid point), lane j = dof j.
 struct CvArgs {
   CcArgs c;
-  const double* vals;   // [batch * nstages][njoints][64]
+  const double* vals;   // [batch * nstages][njoints][VAL_DOUBLES]
 };
 
 static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) {
-  using rbd::CP;
+  using namespace rbd::slots;
   using rbd::M3;
   using rbd::V3;
   const CcArgs& a = v.c;
@@ -204,23 +196,23 @@ static __global__ __launch_bounds__(64) void contact_cone_vals_kernel(CvArgs v) 
   double* const cr = a.rv.cdd_at(rec);
   double* const nr = a.rv.con_at(rec);
   double* const gr = a.rv.cone + rec * a.cone_stride;
-  const double* const vb = v.vals + rec * (size_t)nb * rbd::VAL_SLOTS;
+  const double* const vb = v.vals + rec * (size_t)nb * VAL_DOUBLES;
   const int* const no = a.rv.L.con.off;
   const int j = lane;
   const bool lane_on = j < nv;
   // this dof's rotation axis in the world frame
   V3 wj = rbd::mk(0, 0, 0);
   if (lane_on) {
-    const double* const blk = vb + (size_t)a.rv.model->dof_body[j] * rbd::VAL_SLOTS;
-    wj = rbd::mul(rbd::ldm3(blk + 12), rbd::ldv3(a.rv.model->dof_axis[j]));
+    const double* const blk = vb + (size_t)a.rv.model->dof_body[j] * VAL_DOUBLES;
+    wj = rbd::mul(rbd::ldm3(blk + V_OR), rbd::ldv3(a.rv.model->dof_axis[j]));
   }
   double lq = 0.0;
   int k = 0;
   for (int c = 0; c < ncon; ++c) {
     if (!((act >> c) & 1u)) continue;
     const double* const cm = &a.rv.model->contact[c][0];
-    const double* const blk = vb + (size_t)(int)cm[14] * rbd::VAL_SLOTS;
-    const M3 Rwf = rbd::mul(rbd::ldm3(blk + 12), rbd::ldm3(cm));
+    const double* const blk = vb + (size_t)(int)cm[C_PARENT] * VAL_DOUBLES;
+    const M3 Rwf = rbd::mul(rbd::ldm3(blk + V_OR), rbd::ldm3(cm + C_R));
     const V3 fW = rbd::mul(Rwf, rbd::ldv3(s + a.rv.sol_off(RTOC_SOL_F) + k * cd));
     M3 Rs;
 #pragma unroll

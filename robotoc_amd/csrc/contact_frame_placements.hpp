@@ -5,7 +5,7 @@
 //
 // Mapping: the geometry of rbd_values_kernel (rigid_body.hpp) -- lanes = the bodies of one instance, one pass down the levels of
 // the tree, 64 / gs instances per wave (gs: the next power of two >= njoints).  LDS: the world placement of every body (a child
-// reads its parent's) and of every contact frame (the lanes of an instance then share the stores), 12 doubles each.  The centre
+// reads its parent's) and of every contact frame (the lanes of an instance then share the stores), FK_SLOTS doubles each.  The centre
 // of mass is a butterfly over the gs lanes of an instance, in registers.  No atomics.
 // Loads of q: the configurations lie a record (source 1) or a state (source 0) apart, so a wave touches 64 / gs separate runs
 // of nq doubles.  Every body lane loads its own joint coordinate and nothing else -- the revolute lanes of an instance read one
@@ -34,7 +34,9 @@ struct FkArgs {
   int first, last;       // grid points [first, last) the hold form writes
   unsigned contacts;     // ... and the contacts, as a bit mask
 };
-constexpr int FK_SLOTS = 12;   // R (row-major) at 0, p at 9
+// world placement of a body or a contact frame in LDS: rotation (row-major), position
+enum : int { FK_R = 0, FK_P = 9, FK_SLOTS = 12 };
+static_assert(FK_R == 0 && FK_P == FK_R + 9 && FK_SLOTS == FK_P + 3 && FK_SLOTS % 2 == 0, "placement slots");
 
 static __global__ __launch_bounds__(64) void contact_frame_placements_kernel(FkArgs a) {
   using namespace rbd;
@@ -51,21 +53,12 @@ static __global__ __launch_bounds__(64) void contact_frame_placements_kernel(FkA
   double* const F = W + (size_t)nb * FK_SLOTS;
   // ---- this body's constants and joint coordinate ----
   const double* const jm = &a.rv.model->joint[ib][0];
-  const int type = (int)jm[28], iq = (int)jm[29], depth = (int)jm[31];
+  const int type = (int)jm[J_TYPE], iq = (int)jm[J_IDXQ], depth = (int)jm[J_DEPTH];
   const int par = a.rv.model->m.parent[ib];
   const double* const q = a.q + (size_t)b * a.q_stride;
-  M3 Rj;
-  V3 pj = mk(0, 0, 0);
-  if (type == RTOC_JOINT_FREE_FLYER) {
-    Rj = quat_R(q + iq + 3);
-    pj = ldv3(q + iq);
-  } else {
-    const double th = q[iq];
-    Rj = revolute_R(ldv3(jm + 12), sin(th), cos(th));
-  }
   M3 R;
   V3 p;
-  joint_placement(jm, Rj, pj, R, p);
+  joint_placement_at(jm, type == RTOC_JOINT_FREE_FLYER, q + iq, R, p);
   // ---- down the levels: world placements ----
   M3 oR = R;
   V3 op = p;
@@ -73,20 +66,20 @@ static __global__ __launch_bounds__(64) void contact_frame_placements_kernel(FkA
     if (on && depth == d) {
       if (d > 0) {
         const double* const pa = W + (size_t)par * FK_SLOTS;
-        const M3 oRp = ldm3(pa);
+        const M3 oRp = ldm3(pa + FK_R);
         oR = mul(oRp, R);
-        op = ldv3(pa + 9) + mul(oRp, p);
+        op = ldv3(pa + FK_P) + mul(oRp, p);
       }
 #pragma unroll
-      for (int k = 0; k < 9; ++k) me[k] = oR.m[k];
-      me[9] = op.x, me[10] = op.y, me[11] = op.z;
+      for (int k = 0; k < 9; ++k) me[FK_R + k] = oR.m[k];
+      stv3(me + FK_P, op);
     }
     __syncthreads();
   }
   // ---- centre of mass: sum of m_i (op_i + oR_i c_i) over the lanes of the instance / total mass ----
   {
-    const double mass = on ? jm[15] : 0.0;
-    const V3 cw = op + mul(oR, ldv3(jm + 16));
+    const double mass = on ? jm[J_MASS] : 0.0;
+    const V3 cw = op + mul(oR, ldv3(jm + J_COM));
     double s[4] = {mass * cw.x, mass * cw.y, mass * cw.z, mass};
     for (int off = GS >> 1; off > 0; off >>= 1)
 #pragma unroll
@@ -96,33 +89,33 @@ static __global__ __launch_bounds__(64) void contact_frame_placements_kernel(FkA
   // ---- the contact frames this body carries ----
   for (int c = 0; c < ncon; ++c) {
     const double* const cm = &a.rv.model->contact[c][0];
-    if (on && (int)cm[14] == ib) {
-      const M3 oRf = mul(oR, ldm3(cm));
-      const V3 pw = op + mul(oR, ldv3(cm + 9));
+    if (on && (int)cm[C_PARENT] == ib) {
+      const M3 oRf = mul(oR, ldm3(cm + C_R));
+      const V3 pw = op + mul(oR, ldv3(cm + C_P));
       double* const f = F + (size_t)c * FK_SLOTS;
 #pragma unroll
-      for (int k = 0; k < 9; ++k) f[k] = oRf.m[k];
-      f[9] = pw.x, f[10] = pw.y, f[11] = pw.z;
+      for (int k = 0; k < 9; ++k) f[FK_R + k] = oRf.m[k];
+      stv3(f + FK_P, pw);
     }
   }
   __syncthreads();
   if (!gvalid) return;
   // ---- out: the lanes of an instance share its entries, consecutive lanes consecutive doubles ----
   if (a.out_R)
-    for (int e = i; e < ncon * 9; e += GS) a.out_R[(size_t)b * ncon * 9 + e] = F[(e / 9) * FK_SLOTS + e % 9];
+    for (int e = i; e < ncon * 9; e += GS) a.out_R[(size_t)b * ncon * 9 + e] = F[(e / 9) * FK_SLOTS + FK_R + e % 9];
   if (a.out_p)
-    for (int e = i; e < ncon * 3; e += GS) a.out_p[(size_t)b * ncon * 3 + e] = F[(e / 3) * FK_SLOTS + 9 + e % 3];
+    for (int e = i; e < ncon * 3; e += GS) a.out_p[(size_t)b * ncon * 3 + e] = F[(e / 3) * FK_SLOTS + FK_P + e % 3];
   if (a.tab_pos) {
     const int n = (a.last - a.first) * ncon;
     for (int e = i; e < n * 3; e += GS) {
       const int st = a.first + (e / 3) / ncon, c = (e / 3) % ncon;
-      if ((a.contacts >> c) & 1u) a.tab_pos[a.rv.placement(b, st, ncon, c) * 3 + e % 3] = F[c * FK_SLOTS + 9 + e % 3];
+      if ((a.contacts >> c) & 1u) a.tab_pos[a.rv.placement(b, st, ncon, c) * 3 + e % 3] = F[c * FK_SLOTS + FK_P + e % 3];
     }
     if (a.tab_rot)
       for (int e = i; e < n * 9; e += GS) {
         const int st = a.first + (e / 9) / ncon, c = (e / 9) % ncon;
-        const bool surf = (int)a.rv.model->contact[c][15] == RTOC_CONTACT_SURFACE;
-        if (surf && ((a.contacts >> c) & 1u)) a.tab_rot[a.rv.placement(b, st, ncon, c) * 9 + e % 9] = F[c * FK_SLOTS + e % 9];
+        const bool surf = (int)a.rv.model->contact[c][C_TYPE] == RTOC_CONTACT_SURFACE;
+        if (surf && ((a.contacts >> c) & 1u)) a.tab_rot[a.rv.placement(b, st, ncon, c) * 9 + e % 9] = F[c * FK_SLOTS + FK_R + e % 9];
       }
   }
 }

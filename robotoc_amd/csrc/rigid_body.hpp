@@ -43,7 +43,7 @@ struct LinArgs {
   // records follow the convention of rtoc_unconstr_condense (la lives in KKT.lu, lu in CDD.la)
   int unconstr;
   double scale;
-  const double* vals;   // PRE: [batch * nstages][njoints][64] of the dynamics traversal (rbd_values_kernel)
+  const double* vals;   // PRE: [batch * nstages][njoints][VAL_DOUBLES] of the dynamics traversal (rbd_values_kernel)
   const double* vals2;  //      the same for the kinematics traversal of impact grids
 };
 
@@ -54,23 +54,20 @@ struct LinArgs {
 // transforms incl. a sincos per joint, placements, velocities, accelerations, forces) were ~40 % of it, recomputed by every
 // lane, body after body.  They are level-parallel instead: here lanes = bodies, one pass down the levels of the tree
 // (placements, v, a, own force) and one pass up the bodies in reverse depth-first order (forces of the children), several
-// grid points per wave (64 / next power of two >= njoints).  Out: 64 doubles per body --
-//   0 R, 9 p, 12 oR, 21 op, 24 v, 30 a, 36 g, 39 f (TOTAL: own + children - contact forces), 45 body index,
-//   46 v_parent in body coordinates, 52 a_parent likewise, 58 h = I v
-// the block the walk copies into its per-level value slots when it visits the body -- and the inverse-dynamics residual ID
+// grid points per wave (64 / next power of two >= njoints).  Out: the value block of every body (V_R .. V_H, VAL_DOUBLES doubles:
+// rigid_body_model.hpp) -- the block the walk copies into its per-level value slots when it visits the body -- and the inverse-dynamics residual ID
 // (the value part of RTOC_CDD_IDC).  trav: 0 = the dynamics traversal, 1 = the kinematics traversal at v + dv of impact
 // grids (impact_stage.cpp:61), other grids idle.
 struct ValArgs {
   RecView rv;           // positions / rotations: the desired contact placements (the value rows of C below)
   ModelDims md;
-  double* vals;         // [batch * nstages][njoints][64]
+  double* vals;         // [batch * nstages][njoints][VAL_DOUBLES]
   int trav, unconstr;
   int nsel, sel[16];    // nsel > 0: only the grid points sel[0..nsel) of every instance (the impact grids of trav 1)
 };
-constexpr int VAL_SLOTS = 64;
 
 static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];   // [G][njoints][64]
+  extern __shared__ __attribute__((aligned(16))) double smem[];   // [G][njoints][VAL_DOUBLES]
   const int lane = threadIdx.x, GS = a.md.gs, G = 64 / GS, nb = a.md.njoints, ncon = a.md.ncontacts;
   const int grp = lane / GS, i = lane % GS;
   const int nst1 = a.nsel > 0 ? a.nsel : a.rv.nlin();   // grid points per instance this launch covers
@@ -83,18 +80,18 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   const bool dyn = a.trav == 0;
   const bool on = gvalid && i < nb && (dyn || impact);
   const int ib = i < nb ? i : 0;
-  double* const V = smem + (size_t)grp * nb * VAL_SLOTS;
-  double* const me = V + (size_t)ib * VAL_SLOTS;
+  double* const V = smem + (size_t)grp * nb * VAL_DOUBLES;
+  double* const me = V + (size_t)ib * VAL_DOUBLES;
   const size_t rec = (size_t)b * a.rv.nstages + st;
   const double* const sr = a.rv.sol_at(rec);
   const unsigned active = a.rv.active[st];
   const int nv = a.rv.nv(), nu = a.rv.nu();
   // ---- this body's constants and joint state ----
   const double* const jm = &a.rv.model->joint[ib][0];
-  const int type = (int)jm[28], iq = (int)jm[29], iv = (int)jm[30], depth = (int)jm[31];
+  const int type = (int)jm[J_TYPE], iq = (int)jm[J_IDXQ], iv = (int)jm[J_IDXV], depth = (int)jm[J_DEPTH];
   const int par = a.rv.model->m.parent[ib];
   const bool ff = type == RTOC_JOINT_FREE_FLYER;
-  const V3 ax = ldv3(jm + 12);
+  const V3 ax = ldv3(jm + J_AXIS);
   M3 Rj;
   V3 pj = mk(0, 0, 0);
   SV vj, aj;
@@ -115,13 +112,10 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   if (impact && !dyn) aj = sv0();  // velocity-level rows only
   M3 R;
   V3 p;
-  joint_placement(jm, Rj, pj, R, p);
-  const double mass = jm[15];
-  const V3 com = ldv3(jm + 16);
-  const M3 I = ldm3(jm + 19);
-  auto st_v3 = [&](double* d, V3 x) { d[0] = x.x, d[1] = x.y, d[2] = x.z; };
-  auto st_sv6 = [&](double* d, SV x) { st_v3(d, x.l), st_v3(d + 3, x.a); };
-  auto ld_sv6 = [&](const double* d) { return SV{ldv3(d), ldv3(d + 3)}; };
+  joint_placement(jm + J_R, Rj, pj, R, p);
+  const double mass = jm[J_MASS];
+  const V3 com = ldv3(jm + J_COM);
+  const M3 I = ldm3(jm + J_INERTIA);
   // ---- down the levels: placements, velocities, accelerations, own forces ----
   for (int d = 0; d < a.md.nlevels; ++d) {
     if (on && depth == d) {
@@ -130,13 +124,13 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
       SV vpar = sv0(), apar = sv0();
       V3 gi = mulT(R, mk(-a.md.gx, -a.md.gy, -a.md.gz));
       if (d > 0) {
-        const double* const pa = V + (size_t)par * VAL_SLOTS;
-        const M3 oRp = ldm3(pa + 12);
+        const double* const pa = V + (size_t)par * VAL_DOUBLES;
+        const M3 oRp = ldm3(pa + V_OR);
         oR = mul(oRp, R);
-        op = ldv3(pa + 21) + mul(oRp, p);
-        vpar = act_inv(R, p, ld_sv6(pa + 24));
-        apar = act_inv(R, p, ld_sv6(pa + 30));
-        gi = mulT(R, ldv3(pa + 36));
+        op = ldv3(pa + V_OP) + mul(oRp, p);
+        vpar = act_inv(R, p, ldsv(pa + V_V));
+        apar = act_inv(R, p, ldsv(pa + V_A));
+        gi = mulT(R, ldv3(pa + V_G));
       }
       if (impact) gi = mk(0, 0, 0);  // the impact model has no gravity
       const SV v = vpar + vj;
@@ -147,21 +141,21 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
       for (int c = 0; c < ncon; ++c) {
         const double* const cm = &a.rv.model->contact[c][0];
         const bool con_on = (active >> c) & 1u;
-        const bool surf = (int)cm[15] == RTOC_CONTACT_SURFACE;
-        if (con_on && (int)cm[14] == ib) {
+        const bool surf = (int)cm[C_TYPE] == RTOC_CONTACT_SURFACE;
+        if (con_on && (int)cm[C_PARENT] == ib) {
           const SV fc = SV{ldv3(sr + a.rv.sol_off(RTOC_SOL_F) + roff), surf ? ldv3(sr + a.rv.sol_off(RTOC_SOL_F) + roff + 3) : mk(0, 0, 0)};
-          f = f - act_f(ldm3(cm), ldv3(cm + 9), fc);
+          f = f - act_f(ldm3(cm + C_R), ldv3(cm + C_P), fc);
         }
         roff += con_on ? (surf ? 6 : 3) : 0;
       }
 #pragma unroll
-      for (int k = 0; k < 9; ++k) me[k] = R.m[k], me[12 + k] = oR.m[k];
-      st_v3(me + 9, p), st_v3(me + 21, op);
-      st_sv6(me + 24, v), st_sv6(me + 30, acc);
-      st_v3(me + 36, gi);
-      st_sv6(me + 39, f);
-      me[45] = (double)ib;
-      st_sv6(me + 46, vpar), st_sv6(me + 52, apar), st_sv6(me + 58, h);
+      for (int k = 0; k < 9; ++k) me[V_R + k] = R.m[k], me[V_OR + k] = oR.m[k];
+      stv3(me + V_P, p), stv3(me + V_OP, op);
+      stsv(me + V_V, v), stsv(me + V_A, acc);
+      stv3(me + V_G, gi);
+      stsv(me + V_F, f);
+      me[V_BODY] = (double)ib;
+      stsv(me + V_VPAR, vpar), stsv(me + V_APAR, apar), stsv(me + V_H, h);
     }
     __syncthreads();
   }
@@ -169,15 +163,15 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   for (int k = nb - 1; k >= 1; --k) {
     const int pk = a.rv.model->m.parent[k];
     if (on && ib == pk) {
-      const double* const ch = V + (size_t)k * VAL_SLOTS;
-      st_sv6(me + 39, ld_sv6(me + 39) + act_f(ldm3(ch), ldv3(ch + 9), ld_sv6(ch + 39)));
+      const double* const ch = V + (size_t)k * VAL_DOUBLES;
+      stsv(me + V_F, ldsv(me + V_F) + act_f(ldm3(ch + V_R), ldv3(ch + V_P), ldsv(ch + V_F)));
     }
     __syncthreads();
   }
   // ---- ID = S^T f - [0; u] (the value rows of RTOC_CDD_IDC; contact_dynamics.cpp:21-24, impact_dynamics.cpp:12-14) ----
   if (on && dyn) {
     double* const cr = a.rv.cdd_at(rec);
-    const SV f = ld_sv6(me + 39);
+    const SV f = ldsv(me + V_F);
     if (ff) {
       const double fv[6] = {f.l.x, f.l.y, f.l.z, f.a.x, f.a.y, f.a.z};
 #pragma unroll
@@ -191,23 +185,23 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
   //      nv.. of RTOC_CDD_IDC.  Lane-invariant in the tangent walk, which used to evaluate them in every lane. ----
   if (on && (impact ? !dyn : dyn)) {
     double* const cr = a.rv.cdd_at(rec);
-    const SV v = ld_sv6(me + 24), acc = ld_sv6(me + 30);
-    const M3 oR = ldm3(me + 12);
-    const V3 op = ldv3(me + 21);
+    const SV v = ldsv(me + V_V), acc = ldsv(me + V_A);
+    const M3 oR = ldm3(me + V_OR);
+    const V3 op = ldv3(me + V_OP);
     int roff = 0;
     for (int c = 0; c < ncon; ++c) {
       const double* const cm = &a.rv.model->contact[c][0];
       const bool con_on = (active >> c) & 1u;
-      const bool surf = (int)cm[15] == RTOC_CONTACT_SURFACE;
+      const bool surf = (int)cm[C_TYPE] == RTOC_CONTACT_SURFACE;
       const int nr = surf ? 6 : 3;
-      if (con_on && (int)cm[14] == ib) {
-        const M3 Rf = ldm3(cm);
-        const V3 pf = ldv3(cm + 9);
+      if (con_on && (int)cm[C_PARENT] == ib) {
+        const M3 Rf = ldm3(cm + C_R);
+        const V3 pf = ldv3(cm + C_P);
         const SV vf = act_inv(Rf, pf, v);
         SV C = vf;
         if (!impact) {
           const SV af = act_inv(Rf, pf, acc);
-          const double kp = cm[12], kd = cm[13];
+          const double kp = cm[C_KP], kd = cm[C_KD];
           const V3 pw = op + mul(oR, pf);
           const V3 pr = a.rv.positions ? ldv3(a.rv.positions + a.rv.placement(b, st, ncon, c) * 3) : mk(0, 0, 0);
           if (!surf) {
@@ -230,7 +224,7 @@ static __global__ __launch_bounds__(64) void rbd_values_kernel(ValArgs a) {
     }
   }
   // ---- the blocks out, coalesced ----
-  const int per = nb * VAL_SLOTS;
+  const int per = nb * VAL_DOUBLES;
   for (int e = lane; e < G * per; e += 64) {
     const int g2 = e / per;
     const long long it2 = (long long)blockIdx.x * G + g2;
@@ -318,33 +312,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
       const int ln = lane < LW ? lane : LW - 1;
       auto FT = [&](int slot, int k) -> double& { return lfwd[((size_t)slot * FWD_SLOTS + k) * LW + ln]; };
       auto DT = [&](int lev, int k) -> double& { return ldf[((size_t)lev * DF_SLOTS + k) * LW + ln]; };
-      auto ld_sv = [&](int lev, int k0) { return SV{mk(LV(lev, k0), LV(lev, k0 + 1), LV(lev, k0 + 2)), mk(LV(lev, k0 + 3), LV(lev, k0 + 4), LV(lev, k0 + 5))}; };
-      auto st_sv = [&](int lev, int k0, SV x) {
-        LV(lev, k0) = x.l.x, LV(lev, k0 + 1) = x.l.y, LV(lev, k0 + 2) = x.l.z, LV(lev, k0 + 3) = x.a.x, LV(lev, k0 + 4) = x.a.y, LV(lev, k0 + 5) = x.a.z;
-      };
+      auto ld_sv = [&](int lev, int k0) { return ldsv(&LV(lev, k0)); };
+      auto st_sv = [&](int lev, int k0, SV x) { stsv(&LV(lev, k0), x); };
       auto ld_ft = [&](int slot, int k0) { return SV{mk(FT(slot, k0), FT(slot, k0 + 1), FT(slot, k0 + 2)), mk(FT(slot, k0 + 3), FT(slot, k0 + 4), FT(slot, k0 + 5))}; };
       auto st_ft = [&](int slot, int k0, SV x) {
         FT(slot, k0) = x.l.x, FT(slot, k0 + 1) = x.l.y, FT(slot, k0 + 2) = x.l.z, FT(slot, k0 + 3) = x.a.x, FT(slot, k0 + 4) = x.a.y, FT(slot, k0 + 5) = x.a.z;
       };
       auto ld_dt = [&](int lev) { return SV{mk(DT(lev, 0), DT(lev, 1), DT(lev, 2)), mk(DT(lev, 3), DT(lev, 4), DT(lev, 5))}; };
       auto st_dt = [&](int lev, SV x) { DT(lev, 0) = x.l.x, DT(lev, 1) = x.l.y, DT(lev, 2) = x.l.z, DT(lev, 3) = x.a.x, DT(lev, 4) = x.a.y, DT(lev, 5) = x.a.z; };
-      // value slots: 0 R, 9 p, 12 oR, 21 op, 24 v, 30 a, 36 g, 39 f, 45 body index
-      // forward-tangent slots: 0 dv, 6 da, 12 dg
+      // value slots: V_R .. V_BODY (PRE: the whole block, .. V_H) of rigid_body_model.hpp; forward-tangent slots: 0 dv, 6 da, 12 dg
       SV tdv = sv0(), tda = sv0(), cdf = sv0();   // forward tangents of the body visited last; force tangent of an open leaf
       V3 tdg = mk(0, 0, 0);
       bool topreg = false;                        // the force tangent of level `top` is cdf (a leaf), not in LDS
       auto JM = [&](int i, int k) -> const double& { return sjm[i * JPW + k - JOFF]; };
       auto unit_twist = [&](int i, int k) -> SV {  // S_k of joint i
-        if ((int)JM(i, 28) == RTOC_JOINT_FREE_FLYER) return rbd::unit_twist(k);
-        return SV{mk(0, 0, 0), ldv3(&JM(i, 12))};
+        if ((int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER) return rbd::unit_twist(k);
+        return SV{mk(0, 0, 0), ldv3(&JM(i, J_AXIS))};
       };
       auto close = [&](int lev, bool from_reg) {
-        const int i = (int)LV(lev, 45);
-        const M3 R = ldm3(&LV(lev, 0));
-        const V3 p = ldv3(&LV(lev, 9));
-        const SV f = ld_sv(lev, 39), df = from_reg ? cdf : ld_dt(lev);
-        const int iv = (int)JM(i, 30);
-        const bool cff = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER;
+        const int i = (int)LV(lev, V_BODY);
+        const M3 R = ldm3(&LV(lev, V_R));
+        const V3 p = ldv3(&LV(lev, V_P));
+        const SV f = ld_sv(lev, V_F), df = from_reg ? cdf : ld_dt(lev);
+        const int iv = (int)JM(i, J_IDXV);
+        const bool cff = (int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER;
         const bool own = lane_on && j >= iv && j < iv + (cff ? 6 : 1);
         if (dyn) {
           // tau = S^T f: value (lane 0) and this lane's column
@@ -358,7 +349,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
               if (aug) wsum += dv6[k] * sbeta[iv + k];
             }
           } else {
-            const V3 ax = ldv3(&JM(i, 12));
+            const V3 ax = ldv3(&JM(i, J_AXIS));
             if (!PRE && lane == 0 && j0 == 0) cr[a.rv.cdd_off(RTOC_CDD_IDC) + iv] = dot(ax, f.a) - ((!impact && iv >= nv - nu) ? su[iv - (nv - nu)] : 0.0);
             if (lane_on) dcol[iv] = dot(ax, df.a);
             if (aug) wsum += dot(ax, df.a) * sbeta[iv];
@@ -367,10 +358,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         if (lev > 0) {
           SV dfp = act_f(R, p, df);
           if (own && kind == 0) {   // a body with a parent is a revolute joint: S = (0, axis)
-            const V3 ax = ldv3(&JM(i, 12));
+            const V3 ax = ldv3(&JM(i, J_AXIS));
             dfp = dfp + act_f(R, p, SV{cross(ax, f.l), cross(ax, f.a)});
           }
-          if (!PRE) st_sv(lev - 1, 39, ld_sv(lev - 1, 39) + act_f(R, p, f));   // PRE: the block already holds the total force
+          if (!PRE) st_sv(lev - 1, V_F, ld_sv(lev - 1, V_F) + act_f(R, p, f));   // PRE: the block already holds the total force
           st_dt(lev - 1, ld_dt(lev - 1) + dfp);
         }
       };
@@ -378,18 +369,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
       if (PRE && ps > 0)
         for (int i = 0; i < nb; ++i) {
           if ((visit_mask >> i) & 1ull) continue;
-          const int iv = (int)JM(i, 30);
+          const int iv = (int)JM(i, J_IDXV);
           if (dyn && lane_on) {
             double* const dcol = kind == 2 ? cr + a.rv.cdd_off(RTOC_CDD_DIDDA) + (size_t)j * nv : cr + a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max;
-            const int ndof = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER ? 6 : 1;
+            const int ndof = (int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER ? 6 : 1;
             for (int k = 0; k < ndof; ++k) dcol[iv + k] = 0.0;
           }
           if (rows) {
             int roff = 0;
             for (int c = 0; c < ncon; ++c) {
               const bool on = (active >> c) & 1u;
-              const int nr = (SURF && (int)scm[c * CP + 15] == RTOC_CONTACT_SURFACE) ? 6 : 3;
-              if (on && (int)scm[c * CP + 14] == i && lane_on)
+              const int nr = (SURF && (int)scm[c * CP + C_TYPE] == RTOC_CONTACT_SURFACE) ? 6 : 3;
+              if (on && (int)scm[c * CP + C_PARENT] == i && lane_on)
                 for (int t = 0; t < nr; ++t) {
                   if (kind == 2 || (impact && kind == 1)) cr[a.rv.cdd_off(RTOC_CDD_DCDA) + (size_t)j * a.rv.L.dims.nf_max + roff + t] = 0.0;
                   if (kind != 2) cr[a.rv.cdd_off(RTOC_CDD_DIDCDQV) + (size_t)(kind == 1 ? nv + j : j) * a.rv.L.nvf_max + nv + roff + t] = 0.0;
@@ -398,13 +389,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
             }
           }
         }
-      const double* const vblk = PRE ? (dyn ? a.vals : a.vals2) + rec * (size_t)nb * VAL_SLOTS : nullptr;
+      const double* const vblk = PRE ? (dyn ? a.vals : a.vals2) + rec * (size_t)nb * VAL_DOUBLES : nullptr;
       double pv = PRE ? vblk[lane] : 0.0;   // body 0 is in every pass
       const int* const vlist = a.rv.model->pass_visit[ps];
       const int nvisit = PRE ? sload_int(a.rv.model->pass_nvisit + ps) : nb;
       for (int t = 0; t < nvisit; ++t) {
         const int i = PRE ? sload_int(vlist + t) : t;   // the bodies a direction of this pass moves or loads, depth first
-        const int d = (int)JM(i, 31);
+        const int d = (int)JM(i, J_DEPTH);
         while (top >= d) {
           close(top, topreg);
           topreg = false;
@@ -414,8 +405,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         const int wk = sload_int(a.rv.model->walk + i);
         const bool chain = wk & 1, leaf = wk & 2;
         const int sslot = ((wk >> 4) & 15) - 1, pslot = ((wk >> 8) & 15) - 1;
-        const int iq = (int)JM(i, 29), iv = (int)JM(i, 30);
-        const bool ff = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER;
+        const int iq = (int)JM(i, J_IDXQ), iv = (int)JM(i, J_IDXV);
+        const bool ff = (int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER;
         const bool own = lane_on && j >= iv && j < iv + (ff ? 6 : 1);
         M3 R, oR;
         V3 p, op, gi;
@@ -423,11 +414,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         if constexpr (PRE) {
           // the body's block from rbd_values_kernel (requested one body ahead) into the level's value slots
           LV(d, lane) = pv;
-          if (t + 1 < nvisit) pv = vblk[(size_t)sload_int(vlist + t + 1) * VAL_SLOTS + lane];
+          if (t + 1 < nvisit) pv = vblk[(size_t)sload_int(vlist + t + 1) * VAL_DOUBLES + lane];
           __builtin_amdgcn_wave_barrier();
-          R = ldm3(&LV(d, 0)), oR = ldm3(&LV(d, 12));
-          p = ldv3(&LV(d, 9)), op = ldv3(&LV(d, 21)), gi = ldv3(&LV(d, 36));
-          v = ld_sv(d, 24), acc = ld_sv(d, 30), vpar = ld_sv(d, 46), apar = ld_sv(d, 52);
+          R = ldm3(&LV(d, V_R)), oR = ldm3(&LV(d, V_OR));
+          p = ldv3(&LV(d, V_P)), op = ldv3(&LV(d, V_OP)), gi = ldv3(&LV(d, V_G));
+          v = ld_sv(d, V_V), acc = ld_sv(d, V_A), vpar = ld_sv(d, V_VPAR), apar = ld_sv(d, V_APAR);
           vj = v - vpar;
         } else {
         M3 Rj;
@@ -440,7 +431,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
           aj = SV{mk(sa[iv], sa[iv + 1], sa[iv + 2]), mk(sa[iv + 3], sa[iv + 4], sa[iv + 5])};
           if (impact && !dyn) vj = vj + aj;  // kinematics at v + dv
         } else {
-          const V3 ax = ldv3(&JM(i, 12));
+          const V3 ax = ldv3(&JM(i, J_AXIS));
           const double th = sq[iq];
           Rj = revolute_R(ax, sin(th), cos(th));
           const double vq = (impact && !dyn) ? sv[iv] + sa[iv] : sv[iv];
@@ -449,18 +440,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         }
         if (impact && dyn) vj = sv0();   // impact model: v = 0
         if (impact && !dyn) aj = sv0();  // velocity-level rows only
-        joint_placement(&JM(i, 0), Rj, pj, R, p);
+        joint_placement(&JM(i, J_R), Rj, pj, R, p);
         oR = R;
         op = p;
         vpar = sv0(), apar = sv0();
         gi = mulT(R, mk(-grav.x, -grav.y, -grav.z));
         if (d > 0) {
-          const M3 oRp = ldm3(&LV(d - 1, 12));
+          const M3 oRp = ldm3(&LV(d - 1, V_OR));
           oR = mul(oRp, R);
-          op = ldv3(&LV(d - 1, 21)) + mul(oRp, p);
-          vpar = act_inv(R, p, ld_sv(d - 1, 24));
-          apar = act_inv(R, p, ld_sv(d - 1, 30));
-          gi = mulT(R, ldv3(&LV(d - 1, 36)));
+          op = ldv3(&LV(d - 1, V_OP)) + mul(oRp, p);
+          vpar = act_inv(R, p, ld_sv(d - 1, V_V));
+          apar = act_inv(R, p, ld_sv(d - 1, V_A));
+          gi = mulT(R, ldv3(&LV(d - 1, V_G)));
         }
         if (impact) gi = mk(0, 0, 0);  // the impact model has no gravity
         v = vpar + vj;
@@ -499,7 +490,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
           if (own && vdir) da = da + mcross(v, unit_twist(i, j - iv));
         } else {
           // revolute joint: S = (0, axis), so S x m = (axis x m.l, axis x m.a) and m x S = (m.l x axis, m.a x axis)
-          const V3 ax = ldv3(&JM(i, 12));
+          const V3 ax = ldv3(&JM(i, J_AXIS));
           if (own) {
             if (kind == 0) {
               dv = dv - SV{cross(ax, vpar.l), cross(ax, vpar.a)};
@@ -516,21 +507,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
           if (own && vdir) da = da + SV{cross(v.l, ax), cross(v.a, ax)};
         }
         // own force and its tangent
-        const double mass = JM(i, 15);
-        const V3 com = ldv3(&JM(i, 16));
-        const M3 I = ldm3(&JM(i, 19));
-        const SV h = PRE ? ld_sv(d, 58) : inertia_mul(mass, com, I, v);
+        const double mass = JM(i, J_MASS);
+        const V3 com = ldv3(&JM(i, J_COM));
+        const M3 I = ldm3(&JM(i, J_INERTIA));
+        const SV h = PRE ? ld_sv(d, V_H) : inertia_mul(mass, com, I, v);
         SV f = PRE ? sv0() : inertia_mul(mass, com, I, SV{acc.l + gi, acc.a}) + fcross(v, h);   // PRE: the block holds the total force
         const SV df = inertia_mul(mass, com, I, SV{da.l + dg, da.a}) + fcross(dv, h) + fcross(v, inertia_mul(mass, com, I, dv));
         // contacts carried by this body; roff = rows of the active contacts before c (3 per point, 6 per surface contact)
         int roff = 0;
         for (int c = 0; c < ncon; ++c) {
           const bool on = (active >> c) & 1u;
-          const bool surf = SURF && (int)scm[c * CP + 15] == RTOC_CONTACT_SURFACE;
+          const bool surf = SURF && (int)scm[c * CP + C_TYPE] == RTOC_CONTACT_SURFACE;
           const int nr = surf ? 6 : 3;
-          if (on && (int)scm[c * CP + 14] == i) {
-            const M3 Rf = ldm3(&scm[c * CP]);
-            const V3 pf = ldv3(&scm[c * CP + 9]);
+          if (on && (int)scm[c * CP + C_PARENT] == i) {
+            const M3 Rf = ldm3(&scm[c * CP + C_R]);
+            const V3 pf = ldv3(&scm[c * CP + C_P]);
             // the contact force / wrench is given in the LOCAL contact frame (point_contact.cpp:55-60, surface_contact.cpp)
             const SV fc = PRE ? sv0() : SV{mk(sf[roff], sf[roff + 1], sf[roff + 2]), surf ? mk(sf[roff + 3], sf[roff + 4], sf[roff + 5]) : mk(0, 0, 0)};
             if (!PRE) f = f - act_f(Rf, pf, fc);
@@ -542,7 +533,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
                 dC = dvf;
               } else {
                 const SV af = act_inv(Rf, pf, acc), daf = act_inv(Rf, pf, da);
-                const double kp = scm[c * CP + 12], kd = scm[c * CP + 13];
+                const double kp = scm[c * CP + C_KP], kd = scm[c * CP + C_KD];
                 const M3 oRf = mul(oR, Rf);
                 const V3 pw = op + mul(oR, pf);
                 const V3 pr = a.rv.positions ? ldv3(a.rv.positions + a.rv.placement(b, st, ncon, c) * 3) : mk(0, 0, 0);
@@ -606,14 +597,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((PRE && !SUR
         // ---- store the level ----
         if constexpr (!PRE) {
 #pragma unroll
-          for (int k = 0; k < 9; ++k) LV(d, k) = R.m[k], LV(d, 12 + k) = oR.m[k];
-          LV(d, 9) = p.x, LV(d, 10) = p.y, LV(d, 11) = p.z;
-          LV(d, 21) = op.x, LV(d, 22) = op.y, LV(d, 23) = op.z;
-          st_sv(d, 24, v);
-          st_sv(d, 30, acc);
-          LV(d, 36) = gi.x, LV(d, 37) = gi.y, LV(d, 38) = gi.z;
-          st_sv(d, 39, f);
-          LV(d, 45) = (double)i;
+          for (int k = 0; k < 9; ++k) LV(d, V_R + k) = R.m[k], LV(d, V_OR + k) = oR.m[k];
+          stv3(&LV(d, V_P), p), stv3(&LV(d, V_OP), op);
+          st_sv(d, V_V, v);
+          st_sv(d, V_A, acc);
+          stv3(&LV(d, V_G), gi);
+          st_sv(d, V_F, f);
+          LV(d, V_BODY) = (double)i;
         }
         tdv = dv, tda = da, tdg = dg;
         if (sslot >= 0) {

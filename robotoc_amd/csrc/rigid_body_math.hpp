@@ -1,10 +1,12 @@
 // rigid_body_math.hpp -- the one device copy of the rotation and SE(3) arithmetic of the kernels: 3-vectors, spatial motions /
 // forces, rotations (transpose, relative placement A^-1 B, quaternion <-> matrix, the revolute joint's Rodrigues rotation, the
-// placement of a joint from its model row, unit twists), log6 with its forward-mode derivative, exp6 with its coefficients
-// and translation part, the block-triangular 6 x 6 inverse of the SE(3) Jacobians, and the scalar-cache load of the device
-// model.  Device functions only.
+// placement of a joint from its joint record and the configuration, unit twists), log6 with its forward-mode derivative, exp6
+// with its coefficients and translation part, the block-triangular 6 x 6 inverse of the SE(3) Jacobians, and the scalar-cache
+// load of the device model.  Device functions only; the slot names of the joint record come from rigid_body_model.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "rigid_body_model.hpp"
 
 namespace rtoc {
 namespace rbd {
@@ -64,6 +66,9 @@ __device__ __forceinline__ M3 ldm3(const double* p) {
   return r;
 }
 __device__ __forceinline__ V3 ldv3(const double* p) { return mk(p[0], p[1], p[2]); }
+__device__ __forceinline__ void stv3(double* d, V3 x) { d[0] = x.x, d[1] = x.y, d[2] = x.z; }
+__device__ __forceinline__ SV ldsv(const double* p) { return SV{ldv3(p), ldv3(p + 3)}; }
+__device__ __forceinline__ void stsv(double* d, SV x) { stv3(d, x.l), stv3(d + 3, x.a); }
 __device__ __forceinline__ M3 transpose(const M3& A) {
   M3 T;
 #pragma unroll
@@ -117,12 +122,26 @@ __device__ __forceinline__ M3 revolute_R(V3 ax, double sn, double cs) {
   R.m[6] = t * ax.x * ax.z - sn * ax.y, R.m[7] = t * ax.y * ax.z + sn * ax.x, R.m[8] = t * ax.z * ax.z + cs;
   return R;
 }
-// placement (R, p) of a joint in its parent's frame: the fixed placement of its model row (rotation at 0, offset at 9) times
-// the joint's own transform (Rj, pj)
-__device__ __forceinline__ void joint_placement(const double* row, const M3& Rj, V3 pj, M3& R, V3& p) {
-  const M3 Rp = ldm3(row);
+// placement (R, p) of a joint in its parent's frame: the fixed placement of its joint record (`fixed` points at its J_R, the
+// offset J_P follows) times the joint's own transform (Rj, pj)
+__device__ __forceinline__ void joint_placement(const double* fixed, const M3& Rj, V3 pj, M3& R, V3& p) {
+  const M3 Rp = ldm3(fixed);
   R = mul(Rp, Rj);
-  p = mul(Rp, pj) + ldv3(row + 9);
+  p = mul(Rp, pj) + ldv3(fixed + (J_P - J_R));
+}
+// the same at the configuration q: `jm` the joint record, `qj` the joint's coordinates in q (at J_IDXQ) -- a free-flyer's position
+// and quaternion, a revolute joint's angle about J_AXIS
+__device__ __forceinline__ void joint_placement_at(const double* jm, bool free_flyer, const double* qj, M3& R, V3& p) {
+  M3 Rj;
+  V3 pj = mk(0, 0, 0);
+  if (free_flyer) {
+    Rj = quat_R(qj + 3);
+    pj = ldv3(qj);
+  } else {
+    const double th = qj[0];
+    Rj = revolute_R(ldv3(jm + J_AXIS), sin(th), cos(th));
+  }
+  joint_placement(jm + J_R, Rj, pj, R, p);
 }
 // S_k of a free-flyer joint: the k-th unit twist (linear 0..2, angular 3..5)
 __device__ __forceinline__ SV unit_twist(int k) { return SV{mk(k == 0, k == 1, k == 2), mk(k == 3, k == 4, k == 5)}; }

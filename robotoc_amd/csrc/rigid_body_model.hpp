@@ -10,10 +10,73 @@
 namespace rtoc {
 namespace rbd {
 
-// per-joint / per-contact constants as the kernel reads them, packed by rtoc_set_robot_model: one coalesced copy into
-// LDS per grid point instead of ~30 dependent L2 round trips per visited body
-constexpr int JP = 32;  // doubles per joint: R 9, p 3, axis 3, mass 1, com 3, I 9 (28), type, idx_q, idx_v, depth
-constexpr int CP = 16;  // doubles per contact: R 9, p 3, kp, kd, parent, type
+// The three packed records of the rigid-body kernels.  This is the one place their layouts are written down: every reader and
+// writer (pack_model below, rigid_body.hpp, contact_constraints.hpp, switching_constraint_lin.hpp, contact_frame_placements.hpp,
+// task_space_cost.hpp and their launchers) goes through these names, and the asserts hold what that code relies on.
+//
+// Joint record, DevModel::joint[i][JP], and contact record, DevModel::contact[c][CP]: the per-joint / per-contact constants as
+// the kernel reads them, packed by rtoc_set_robot_model: one coalesced copy into LDS per grid point instead of ~30 dependent L2
+// round trips per visited body.  Rotations are 9 doubles row-major, vectors 3; the integers are stored as doubles.
+// (An inline namespace: rbd::JP as before, and a kernel outside rbd takes the slot names alone with `using namespace rbd::slots`.)
+inline namespace slots {
+enum : int {
+  J_R = 0,         // placement in the parent's frame: rotation
+  J_P = 9,         //   and offset
+  J_AXIS = 12,     // axis of a revolute joint
+  J_MASS = 15,
+  J_COM = 16,
+  J_INERTIA = 19,  // rotational inertia at the joint's origin (9)
+  J_TYPE = 28,     // RTOC_JOINT_*
+  J_IDXQ = 29,
+  J_IDXV = 30,
+  J_DEPTH = 31,    // level of the body in the tree
+  JP = 32,         // doubles per joint
+};
+enum : int {
+  C_R = 0,         // placement of the contact frame in its body's frame: rotation
+  C_P = 9,         //   and offset
+  C_KP = 12,       // Baumgarte gains
+  C_KD = 13,
+  C_PARENT = 14,   // the body that carries the frame
+  C_TYPE = 15,     // RTOC_CONTACT_*
+  CP = 16,         // doubles per contact
+};
+// Value block of a body, VAL_DOUBLES doubles: what rbd_values_kernel writes per (grid point, body), what the tangent walk copies
+// lane for lane into the value slots of a tree level (and, without the pre-pass, fills itself up to V_BODY), and what
+// contact_cone_vals_kernel reads the world rotations from.
+enum : int {
+  V_R = 0,         // placement in the parent's frame
+  V_P = 9,
+  V_OR = 12,       // placement in the world frame
+  V_OP = 21,
+  V_V = 24,        // spatial velocity, acceleration (6 each: linear, angular)
+  V_A = 30,
+  V_G = 36,        // gravity in body coordinates
+  V_F = 39,        // TOTAL force: own + children - contact forces (6)
+  V_BODY = 45,     // index of the body
+  V_VPAR = 46,     // the parent's velocity and acceleration in body coordinates
+  V_APAR = 52,
+  V_H = 58,        // h = I v
+  VAL_DOUBLES = 64,
+};
+// what contact_cone_kernel and switching_constraint_lin_kernel keep per tree level (LevelCarve below): the head of a value block
+// through V_OP, and a twist per lane
+enum : int { LVL_VAL = 32, LVL_TAN = 6, LVL_LANES = 64 };
+}  // namespace slots
+// Every record is contiguous and ends at its size: a slot moved, grown or added has to be carried through here.
+static_assert(J_R == 0 && J_P == J_R + 9 && J_AXIS == J_P + 3 && J_MASS == J_AXIS + 3 && J_COM == J_MASS + 1 && J_INERTIA == J_COM + 3 &&
+                  J_TYPE == J_INERTIA + 9 && J_IDXQ == J_TYPE + 1 && J_IDXV == J_IDXQ + 1 && J_DEPTH == J_IDXV + 1 && JP == J_DEPTH + 1,
+              "joint record");
+static_assert(C_R == 0 && C_P == C_R + 9 && C_KP == C_P + 3 && C_KD == C_KP + 1 && C_PARENT == C_KD + 1 && C_TYPE == C_PARENT + 1 && CP == C_TYPE + 1,
+              "contact record");
+static_assert(V_R == 0 && V_P == V_R + 9 && V_OR == V_P + 3 && V_OP == V_OR + 9 && V_V == V_OP + 3 && V_A == V_V + 6 && V_G == V_A + 6 &&
+                  V_F == V_G + 3 && V_BODY == V_F + 6 && V_VPAR == V_BODY + 1 && V_APAR == V_VPAR + 6 && V_H == V_APAR + 6 && VAL_DOUBLES == V_H + 6,
+              "value block");
+// the walk's level-slot copy is one double per lane of a wave
+static_assert(VAL_DOUBLES == 64, "LV(d, lane) = pv covers a value block with 64 lanes");
+// records follow one another in arrays and LDS carves that start 16-byte aligned, and the compiler pairs the doubles of an ldm3 /
+// ldv3 / ldsv into 16-byte accesses where it can prove the address even: an even record size and even slots for what is read most
+static_assert(JP % 2 == 0 && CP % 2 == 0 && VAL_DOUBLES % 2 == 0 && J_AXIS % 2 == 0 && V_OR % 2 == 0 && V_V % 2 == 0 && V_A % 2 == 0, "16-byte alignment");
 struct DevModel {
   rtoc_robot_model m;
   int depth[RTOC_MAX_JOINTS];
@@ -65,10 +128,10 @@ inline void pack_model(DevModel* h) {
   plan_passes(h);
   for (int i = 0; i < m.njoints; ++i) {
     double* o = h->joint[i];
-    for (int k = 0; k < 9; ++k) o[k] = m.placement_R[i][k], o[19 + k] = m.inertia[i][k];
-    for (int k = 0; k < 3; ++k) o[9 + k] = m.placement_p[i][k], o[12 + k] = m.axis[i][k], o[16 + k] = m.com[i][k];
-    o[15] = m.mass[i];
-    o[28] = m.type[i], o[29] = m.idx_q[i], o[30] = m.idx_v[i], o[31] = h->depth[i];
+    for (int k = 0; k < 9; ++k) o[J_R + k] = m.placement_R[i][k], o[J_INERTIA + k] = m.inertia[i][k];
+    for (int k = 0; k < 3; ++k) o[J_P + k] = m.placement_p[i][k], o[J_AXIS + k] = m.axis[i][k], o[J_COM + k] = m.com[i][k];
+    o[J_MASS] = m.mass[i];
+    o[J_TYPE] = m.type[i], o[J_IDXQ] = m.idx_q[i], o[J_IDXV] = m.idx_v[i], o[J_DEPTH] = h->depth[i];
   }
   for (int j = 0; j < RTOC_MAX_JOINTS + 8; ++j) h->dof_body[j] = 0, h->dof_axis[j][0] = h->dof_axis[j][1] = h->dof_axis[j][2] = 0.0;
   for (int i = 0; i < m.njoints; ++i) {
@@ -96,14 +159,13 @@ inline void pack_model(DevModel* h) {
   }
   for (int c = 0; c < m.ncontacts; ++c) {
     double* o = h->contact[c];
-    for (int k = 0; k < 9; ++k) o[k] = m.contact_R[c][k];
-    for (int k = 0; k < 3; ++k) o[9 + k] = m.contact_p[c][k];
-    o[12] = m.contact_kp[c], o[13] = m.contact_kd[c], o[14] = m.contact_parent[c], o[15] = m.contact_type[c];
+    for (int k = 0; k < 9; ++k) o[C_R + k] = m.contact_R[c][k];
+    for (int k = 0; k < 3; ++k) o[C_P + k] = m.contact_p[c][k];
+    o[C_KP] = m.contact_kp[c], o[C_KD] = m.contact_kd[c], o[C_PARENT] = m.contact_parent[c], o[C_TYPE] = m.contact_type[c];
   }
 }
 
-// per-level storage in LDS
-constexpr int VAL_DOUBLES = 64;  // R 9, p 3, oR 9, op 3, v 6, a 6, g 3, f 6, vpar 6, apar 6 -> 57, padded
+// per-level storage in LDS of the tangent walk: a value block (VAL_DOUBLES) and, per lane,
 constexpr int TAN_SLOTS = 21;    // dv 6, da 6, dg 3, df 6
 constexpr int FWD_SLOTS = 15;    // dv, da, dg: read by the children only, so the deepest level keeps none
 constexpr int DF_SLOTS = 6;
@@ -118,12 +180,26 @@ constexpr int LIN_MAX_DPP = 21;
 // 1 slot + 3 levels = 22 KB (was 4 + 4 levels = 38 KB), iCub: 2 slots + 10 levels (was 11 + 11 = 128 KB); DESIGN.md 3.4.
 // pre: the walk reads the values of the recursion from rbd_values_kernel (PRE): no q, v, a, f, u staging, and of the joint
 // constants only axis .. depth (JP_PRE doubles from JP_PRE_OFF on) -- 20,000 B for ANYmal: EIGHT waves per CU (8 x 20,480 B).
-constexpr int JP_PRE_OFF = 12, JP_PRE = JP - JP_PRE_OFF;
+constexpr int JP_PRE_OFF = J_AXIS, JP_PRE = JP - JP_PRE_OFF;
+static_assert(JP_PRE_OFF == J_AXIS && J_R < J_AXIS && J_P < J_AXIS, "with the pre-pass the walk stages the joint record without its placement");
 __host__ __device__ constexpr size_t lin_lds_bytes(int nlevels, int nbranch, int njoints, int ncontacts, int nv, int dpp, bool pre) {
   return sizeof(double) * ((size_t)nlevels * VAL_DOUBLES + (size_t)(nbranch * FWD_SLOTS + (nlevels > 1 ? nlevels - 1 : 0) * DF_SLOTS) * lin_lane_stride(dpp) +
                            (pre ? 0 : lin_pad8(nv + 1) + 3 * lin_pad8(nv) + lin_pad8(6 * ncontacts)) + lin_pad8(nv) + 2 * lin_pad8(6 * ncontacts) +
                            njoints * (pre ? JP_PRE : JP) + ncontacts * CP);
 }
+
+// Per-level storage of the kernels that walk the tree with one Jacobian column per lane (contact_cone_kernel,
+// switching_constraint_lin_kernel): the head of a value block through V_OP, then this lane's twist (6 doubles x 64 lanes).
+// The pieces of the carve in their order, in doubles: levels' values | levels' twists | joint records | contact records; what
+// follows is the kernel's own.  The size functions sum them, the kernels step their pointers by them.
+static_assert(V_OP + 3 <= LVL_VAL && LVL_VAL % 2 == 0, "a level keeps R, p, oR, op");
+struct LevelCarve {
+  size_t val, tan;
+  int joint, contact;
+  __host__ __device__ constexpr LevelCarve(int nlevels, int njoints, int ncontacts)
+      : val((size_t)nlevels * LVL_VAL), tan((size_t)nlevels * LVL_TAN * LVL_LANES), joint(njoints * JP), contact(ncontacts * CP) {}
+  __host__ __device__ constexpr size_t doubles() const { return val + tan + joint + contact; }
+};
 
 // bodies a pass with the dofs [j0, j1) has to visit
 inline unsigned long long pass_body_mask(const rtoc_robot_model& m, int j0, int j1) {

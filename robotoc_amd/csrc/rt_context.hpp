@@ -201,7 +201,7 @@ struct ModelState {
     return true;
   }
   // not copied: scratch and results of the last evaluation
-  DevBuf<double> d_vals, d_vals2;  // rbd_values_kernel -> linearize_contact_dynamics_kernel<.., PRE>: [batch * max_stages][njoints][64]
+  DevBuf<double> d_vals, d_vals2;  // rbd_values_kernel -> linearize_contact_dynamics_kernel<.., PRE>: [batch * max_stages][njoints][rbd::VAL_DOUBLES]
   int vals_fresh = 0;            // the values in d_vals belong to the iterate in RTOC_BUF_SOL (consumed by the next launch_linearize)
   DevBuf<double> d_costval;      // [batch][max_stages] cost values of the last rtoc_contact_eval_kkt (rtoc_contact_eval_ocp)
   DevBuf<double> d_kkterr;       // [batch] + [batch][max_stages] partial sums

@@ -22,27 +22,30 @@ static bool model_has_surface_contacts(const rtoc_robot_model& m) {
   return false;
 }
 // hipFuncAttributeMaxDynamicSharedMemorySize is per function and process-wide, not per context: two live contexts with
-// different models (iCub: 11 tree levels, ANYmal: 4) share it, so it only ever grows (the launch passes its own size)
+// different models (iCub: 11 tree levels, ANYmal: 4) share it, so it only ever grows (the launch passes its own size).
+// Every rigid-body kernel whose LDS is sized by the model is granted it here, once per model.
 hipError_t rtoc::set_linearize_lds(const rtoc_robot_model& m, int nlevels, int nbranch, int dpp) {
+  const size_t lin = rbd::lin_lds_bytes(nlevels, nbranch, m.njoints, m.ncontacts, m.nv, dpp, false);   // the larger of the two modes
+  const struct { const void* kernel; size_t bytes; bool may_not_fit; } want[] = {
+      {(const void*)rbd::linearize_contact_dynamics_kernel<true>, lin, false},       {(const void*)rbd::linearize_contact_dynamics_kernel<false>, lin, false},
+      {(const void*)rbd::linearize_contact_dynamics_kernel<true, true>, lin, false}, {(const void*)rbd::linearize_contact_dynamics_kernel<false, true>, lin, false},
+      {(const void*)rbd::rbd_values_kernel, 64 * rbd::VAL_DOUBLES * sizeof(double), false},
+      // over the per-level carve: a tree too deep for them is accepted as long as the walk fits -- they fail where they are launched
+      {(const void*)contact_cone_kernel, cc_lds_bytes(nlevels, m.njoints, m.ncontacts), true},
+      {(const void*)switching_constraint_lin_kernel, sw_lds_bytes(nlevels, m.njoints, m.ncontacts), true}};
+  constexpr int N = sizeof(want) / sizeof(want[0]);
   static std::mutex mu;
-  static int max_bytes_of[64] = {};   // the attribute is per DEVICE: one running maximum for each (the current one: callers hipSetDevice first)
+  static size_t granted_of[64][N] = {};   // the attribute is per DEVICE: one running maximum for each (the current one: callers hipSetDevice first)
   std::lock_guard<std::mutex> lock(mu);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int& max_bytes = max_bytes_of[dev];
-  int bytes = (int)rbd::lin_lds_bytes(nlevels, nbranch, m.njoints, m.ncontacts, m.nv, dpp, false);   // the larger of the two modes
-  if (bytes <= max_bytes) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute((const void*)rbd::linearize_contact_dynamics_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)rbd::linearize_contact_dynamics_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)rbd::linearize_contact_dynamics_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)rbd::linearize_contact_dynamics_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)rbd::rbd_values_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * rbd::VAL_SLOTS * (int)sizeof(double));
-  if (e == hipSuccess) max_bytes = bytes;
-  return e;
+  for (int k = 0; k < N; ++k) {
+    if (want[k].bytes <= granted_of[dev][k] || (want[k].may_not_fit && want[k].bytes > 160 * 1024)) continue;
+    const hipError_t e = hipFuncSetAttribute(want[k].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want[k].bytes);
+    if (e != hipSuccess) return e;
+    granted_of[dev][k] = want[k].bytes;
+  }
+  return hipSuccess;
 }
 
 ModelDims rtoc::model_dims(const rtoc_ctx* c) {
@@ -183,7 +186,7 @@ static int ensure_rbd_values(rtoc_ctx* c) {
   if (!c->h_model) return RTOC_ERR_NOT_READY;
   const rtoc_robot_model& m = c->h_model->m;
   const bool any_impact = any_grid_point(c, c->nstages - 1, grid_is_impact);
-  const size_t need = (size_t)c->batch * c->max_stages * m.njoints * rbd::VAL_SLOTS;
+  const size_t need = (size_t)c->batch * c->max_stages * m.njoints * rbd::VAL_DOUBLES;
   if (c->d_vals.n < need) c->d_vals2.release();   // both grow together: the second one only on grids with an impact
   HIP_TRY(c->d_vals.grow(need));
   if (any_impact) HIP_TRY(c->d_vals2.reserve(c->d_vals.n));
@@ -203,7 +206,7 @@ static int launch_rbd_values(rtoc_ctx* c, bool unconstr) {
   v.unconstr = unconstr ? 1 : 0;
   const int G = 64 / v.md.gs;
   const long long items = (long long)c->batch * dynamics_records(c);
-  const size_t vlds = sizeof(double) * G * v.md.njoints * rbd::VAL_SLOTS;
+  const size_t vlds = sizeof(double) * G * v.md.njoints * rbd::VAL_DOUBLES;
   for (int trav = 0; trav < (any_impact ? 2 : 1); ++trav) {
     v.trav = trav;
     v.vals = trav == 0 ? c->d_vals.p : c->d_vals2.p;
@@ -564,7 +567,6 @@ static int launch_contact_cones(rtoc_ctx* c, int mode) {
     return RTOC_OK;
   }
   const size_t lds = cc_lds_bytes(a.md.nlevels, a.md.njoints, a.md.ncontacts);
-  HIP_TRY(hipFuncSetAttribute((const void*)contact_cone_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(contact_cone_kernel, dim3(c->batch * (c->nstages - 1)), dim3(64), lds, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;
@@ -597,7 +599,6 @@ static int launch_switching_constraint(rtoc_ctx* c) {
   a.nsel = select_grid_points(c, grid_has_switching, a.sel);
   const int per = a.nsel > 0 ? a.nsel : c->nstages - 1;
   const size_t lds = sw_lds_bytes(a.md.nlevels, a.md.njoints, a.md.ncontacts);
-  HIP_TRY(hipFuncSetAttribute((const void*)switching_constraint_lin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(switching_constraint_lin_kernel, dim3(c->batch * per), dim3(64), lds, c->stream, a);
   HIP_TRY(hipGetLastError());
   return RTOC_OK;

@@ -34,13 +34,12 @@ struct SwLinArgs {
 };
 
 __host__ __device__ constexpr size_t sw_lds_bytes(int nlevels, int njoints, int ncontacts) {
-  return sizeof(double) * ((size_t)nlevels * (32 + 6 * 64) + njoints * rbd::JP + ncontacts * rbd::CP + 3 * (RTOC_MAX_JOINTS + 8) +
+  return sizeof(double) * (rbd::LevelCarve(nlevels, njoints, ncontacts).doubles() + 3 * (RTOC_MAX_JOINTS + 8) +
                            6 * RTOC_MAX_CONTACTS * 8 + 2 * 36 + 6 * RTOC_MAX_CONTACTS * (RTOC_MAX_JOINTS + 8));
 }
 
 static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwLinArgs a) {
-  using rbd::CP;
-  using rbd::JP;
+  using namespace rbd::slots;
   using rbd::M3;
   using rbd::SV;
   using rbd::V3;
@@ -55,11 +54,12 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   const int nv = a.rv.nv(), nx = 2 * nv, nb = a.md.njoints, ncon = a.md.ncontacts, nlev = a.md.nlevels, ns = g.dims, LDSW = a.rv.L.dims.ns_max;
   const double dt1 = grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st), dt2 = grid_dt(a.rv.grid, a.rv.dt_inst, b, a.rv.nstages, st + 1);
   const unsigned impact = a.rv.active[st + 2];  // ImpactStatus of the impact two grid points ahead
-  double* const lval = smem;                               // [nlev][32]: R 9, p 3, oR 9, op 3, body index
-  double* const ltan = lval + (size_t)nlev * 32;           // [nlev][6][64]
-  double* const sjm = ltan + (size_t)nlev * 6 * 64;
-  double* const scm = sjm + nb * JP;
-  double* const sqp = scm + ncon * CP;                     // q+
+  const rbd::LevelCarve carve(nlev, nb, ncon);
+  double* const lval = smem;                               // [nlev][LVL_VAL]: V_R .. V_OP of a value block
+  double* const ltan = lval + carve.val;                   // [nlev][LVL_TAN][LVL_LANES]
+  double* const sjm = ltan + carve.tan;
+  double* const scm = sjm + carve.joint;
+  double* const sqp = scm + carve.contact;                 // q+
   double* const sdq = sqp + RTOC_MAX_JOINTS + 8;           // dq
   double* const sxi = sdq + RTOC_MAX_JOINTS + 8;
   double* const spq = sxi + RTOC_MAX_JOINTS + 8;           // Pq base block [rows][8], then P residual etc.
@@ -97,12 +97,12 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
   // ---- depth-first walk at q+: values per level, this lane's Jacobian column (body-frame twist per unit rate of dof j) ----
   const int j = lane;
   const bool lane_on = j < nv;
-  auto LV = [&](int lev, int k) -> double& { return lval[lev * 32 + k]; };
-  auto LT = [&](int lev, int k) -> double& { return ltan[((size_t)lev * 6 + k) * 64 + lane]; };
+  auto LV = [&](int lev, int k) -> double& { return lval[lev * LVL_VAL + k]; };
+  auto LT = [&](int lev, int k) -> double& { return ltan[((size_t)lev * LVL_TAN + k) * LVL_LANES + lane]; };   // 0: linear, 3: angular
   auto JM = [&](int i, int k) -> const double& { return sjm[i * JP + k]; };
   for (int i = 0; i < nb; ++i) {
-    const int d = (int)JM(i, 31), iq = (int)JM(i, 29), iv = (int)JM(i, 30);
-    const bool ff = (int)JM(i, 28) == RTOC_JOINT_FREE_FLYER;
+    const int d = (int)JM(i, J_DEPTH), iq = (int)JM(i, J_IDXQ), iv = (int)JM(i, J_IDXV);
+    const bool ff = (int)JM(i, J_TYPE) == RTOC_JOINT_FREE_FLYER;
     const bool own = lane_on && j >= iv && j < iv + (ff ? 6 : 1);
     M3 Rj;
     V3 pj = rbd::mk(0, 0, 0);
@@ -111,33 +111,33 @@ static __global__ __launch_bounds__(64) void switching_constraint_lin_kernel(SwL
       pj = pb;
     } else {
       const double th = sqp[iq];
-      Rj = rbd::revolute_R(rbd::ldv3(&JM(i, 12)), sin(th), cos(th));
+      Rj = rbd::revolute_R(rbd::ldv3(&JM(i, J_AXIS)), sin(th), cos(th));
     }
     M3 R;
     V3 p;
-    rbd::joint_placement(&JM(i, 0), Rj, pj, R, p);
+    rbd::joint_placement(&JM(i, J_R), Rj, pj, R, p);
     M3 oR = R;
     V3 op = p;
     SV Jc = rbd::sv0();
     if (d > 0) {
-      const M3 oRp = rbd::ldm3(&LV(d - 1, 12));
+      const M3 oRp = rbd::ldm3(&LV(d - 1, V_OR));
       oR = rbd::mul(oRp, R);
-      op = rbd::ldv3(&LV(d - 1, 21)) + rbd::mul(oRp, p);
+      op = rbd::ldv3(&LV(d - 1, V_OP)) + rbd::mul(oRp, p);
       Jc = rbd::act_inv(R, p, SV{rbd::mk(LT(d - 1, 0), LT(d - 1, 1), LT(d - 1, 2)), rbd::mk(LT(d - 1, 3), LT(d - 1, 4), LT(d - 1, 5))});
     }
-    if (own) Jc = Jc + (ff ? rbd::unit_twist(j - iv) : SV{rbd::mk(0, 0, 0), rbd::ldv3(&JM(i, 12))});
+    if (own) Jc = Jc + (ff ? rbd::unit_twist(j - iv) : SV{rbd::mk(0, 0, 0), rbd::ldv3(&JM(i, J_AXIS))});
 #pragma unroll
-    for (int k = 0; k < 9; ++k) LV(d, k) = R.m[k], LV(d, 12 + k) = oR.m[k];
-    LV(d, 9) = p.x, LV(d, 10) = p.y, LV(d, 11) = p.z, LV(d, 21) = op.x, LV(d, 22) = op.y, LV(d, 23) = op.z;
+    for (int k = 0; k < 9; ++k) LV(d, V_R + k) = R.m[k], LV(d, V_OR + k) = oR.m[k];
+    rbd::stv3(&LV(d, V_P), p), rbd::stv3(&LV(d, V_OP), op);
     LT(d, 0) = Jc.l.x, LT(d, 1) = Jc.l.y, LT(d, 2) = Jc.l.z, LT(d, 3) = Jc.a.x, LT(d, 4) = Jc.a.y, LT(d, 5) = Jc.a.z;
     // impacting contacts carried by this body: P rows and this lane's column of Pq
     int r0 = 0;
     for (int c = 0; c < ncon; ++c) {
       const bool on = (impact >> c) & 1u;
-      const bool surf = (int)scm[c * CP + 15] == RTOC_CONTACT_SURFACE;
-      if (on && (int)scm[c * CP + 14] == i) {
-        const M3 Rf = rbd::ldm3(&scm[c * CP]);
-        const V3 pf = rbd::ldv3(&scm[c * CP + 9]);
+      const bool surf = (int)scm[c * CP + C_TYPE] == RTOC_CONTACT_SURFACE;
+      if (on && (int)scm[c * CP + C_PARENT] == i) {
+        const M3 Rf = rbd::ldm3(&scm[c * CP + C_R]);
+        const V3 pf = rbd::ldv3(&scm[c * CP + C_P]);
         const M3 oRf = rbd::mul(oR, Rf);
         const V3 pw = op + rbd::mul(oR, pf);
         const V3 pr = a.rv.positions ? rbd::ldv3(a.rv.positions + a.rv.placement(b, st + 2, ncon, c) * 3) : rbd::mk(0, 0, 0);

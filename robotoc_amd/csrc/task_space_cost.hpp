@@ -155,7 +155,7 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   // ---- local placements (lane per joint), then the tree level by level ----
   for (int i = lane; i < nj; i += LW) {
     const double* J = md.joint[i];
-    const int type = (int)J[28], iq = (int)J[29];
+    const int type = (int)J[rbd::J_TYPE], iq = (int)J[rbd::J_IDXQ];
     rbd::M3 Rj;
     double pj[3] = {0.0, 0.0, 0.0};
     if (type == RTOC_JOINT_FREE_FLYER) {
@@ -164,11 +164,11 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
     } else {
       double sn, cs;
       sincos(q[iq], &sn, &cs);
-      Rj = rbd::revolute_R(rbd::ldv3(J + 12), sn, cs);
+      Rj = rbd::revolute_R(rbd::ldv3(J + rbd::J_AXIS), sn, cs);
     }
     for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) Rw[9 * i + 3 * r + c] = J[3 * r] * Rj.m[c] + J[3 * r + 1] * Rj.m[3 + c] + J[3 * r + 2] * Rj.m[6 + c];
-      pw[3 * i + r] = J[3 * r] * pj[0] + J[3 * r + 1] * pj[1] + J[3 * r + 2] * pj[2] + J[9 + r];
+      for (int c = 0; c < 3; ++c) Rw[9 * i + 3 * r + c] = J[rbd::J_R + 3 * r] * Rj.m[c] + J[rbd::J_R + 3 * r + 1] * Rj.m[3 + c] + J[rbd::J_R + 3 * r + 2] * Rj.m[6 + c];
+      pw[3 * i + r] = J[rbd::J_R + 3 * r] * pj[0] + J[rbd::J_R + 3 * r + 1] * pj[1] + J[rbd::J_R + 3 * r + 2] * pj[2] + J[rbd::J_P + r];
     }
   }
   __syncthreads();
@@ -189,15 +189,15 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
   }
   for (int i = lane; i < nj; i += LW) {
     const double* J = md.joint[i];
-    const double m = J[15];
+    const double m = J[rbd::J_MASS];
     for (int r = 0; r < 3; ++r)
-      mc[3 * i + r] = m * (Rw[9 * i + 3 * r] * J[16] + Rw[9 * i + 3 * r + 1] * J[17] + Rw[9 * i + 3 * r + 2] * J[18] + pw[3 * i + r]);
+      mc[3 * i + r] = m * (Rw[9 * i + 3 * r] * J[rbd::J_COM] + Rw[9 * i + 3 * r + 1] * J[rbd::J_COM + 1] + Rw[9 * i + 3 * r + 2] * J[rbd::J_COM + 2] + pw[3 * i + r]);
   }
   __syncthreads();
   // ---- per dof j (lane): its body, the end of that body's subtree, its world axis ----
   double mtot = 0.0, S[3] = {0.0, 0.0, 0.0};
   for (int k = 0; k < nj; ++k) {
-    mtot += md.joint[k][15];
+    mtot += md.joint[k][rbd::J_MASS];
     for (int r = 0; r < 3; ++r) S[r] += mc[3 * k + r];
   }
   double lq[2] = {0.0, 0.0}, cost = 0.0;   // lane j's J^T W diff (lq[0]: dof lane, lq[1]: dof lane + LW), 1/2 sum W diff^2
@@ -231,12 +231,12 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
           if (j < nv) {
             const int bj = md.dof_body[j];
             const double* Jb = md.joint[bj];
-            const bool lin = (int)Jb[28] == RTOC_JOINT_FREE_FLYER && j - (int)Jb[30] < 3;
+            const bool lin = (int)Jb[rbd::J_TYPE] == RTOC_JOINT_FREE_FLYER && j - (int)Jb[rbd::J_IDXV] < 3;
             int end = bj + 1;
             while (end < nj && md.depth[end] > md.depth[bj]) ++end;
             if (f >= bj && f < end) {
               if (lin) {
-                const int e = j - (int)Jb[30];
+                const int e = j - (int)Jb[rbd::J_IDXV];
                 col.l = rbd::mulT(Rf, rbd::mk(Rw[9 * bj + e], Rw[9 * bj + 3 + e], Rw[9 * bj + 6 + e]));
               } else {
                 const rbd::V3 wv = rbd::mul(rbd::ldm3(Rw + 9 * bj), rbd::ldv3(md.dof_axis[j]));
@@ -285,15 +285,15 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
       const int bj = md.dof_body[j];
       const double* Jb = md.joint[bj];
       const double* Rb = Rw + 9 * bj;
-      const bool lin = (int)Jb[28] == RTOC_JOINT_FREE_FLYER && j - (int)Jb[30] < 3;
+      const bool lin = (int)Jb[rbd::J_TYPE] == RTOC_JOINT_FREE_FLYER && j - (int)Jb[rbd::J_IDXV] < 3;
       int end = bj + 1;
       while (end < nj && md.depth[end] > md.depth[bj]) ++end;
       double col[3] = {0.0, 0.0, 0.0};
       if (lin) {
-        const int e = j - (int)Jb[30];
+        const int e = j - (int)Jb[rbd::J_IDXV];
         double msub = 0.0;
         if (com)
-          for (int kk = bj; kk < end; ++kk) msub += md.joint[kk][15];
+          for (int kk = bj; kk < end; ++kk) msub += md.joint[kk][rbd::J_MASS];
         const double f = com ? msub / mtot : 1.0;
         for (int r = 0; r < 3; ++r) col[r] = f * Rb[3 * r + e];
       } else {
@@ -303,7 +303,7 @@ static __global__ __launch_bounds__(64) void task_space_cost_kernel(TaskCostArgs
         if (com) {
           double msub = 0.0, Ss[3] = {0.0, 0.0, 0.0};
           for (int kk = bj; kk < end; ++kk) {
-            msub += md.joint[kk][15];
+            msub += md.joint[kk][rbd::J_MASS];
             for (int r = 0; r < 3; ++r) Ss[r] += mc[3 * kk + r];
           }
           for (int r = 0; r < 3; ++r) d[r] = (Ss[r] - msub * pw[3 * bj + r]) / mtot;
