@@ -122,8 +122,9 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * trot (MPCCrawl, MPCPace, MPCFlyingTrot: their resetContactPlacements is the trot's line for line) plan through the same entry
  * points, chosen by rtoc_foot_step_planner::gait -- THE OTHER GAITS below.  So does BipedWalkFootStepPlanner with what
  * MPCBipedWalk::resetContactPlacements does (src/mpc/mpc_biped_walk.cpp:347-359), on a model of two contact surfaces, whose
- * placements carry rotations -- THE BIPED WALK below.  Not here:
- * grids with switching-time optimisation, ParNMPC horizons (every entry point below refuses one with RTOC_ERR_BAD_ARG).
+ * placements carry rotations -- THE BIPED WALK below -- and JumpFootStepPlanner with what MPCJump::init and
+ * MPCJump::resetContactPlacements do (src/mpc/mpc_jump.cpp:141-145, :301-317), on either kind of feet -- THE JUMP below.  Not here:
+ * the periodic references on grids with switching-time optimisation, ParNMPC horizons (every entry point below refuses one with RTOC_ERR_BAD_ARG).
  *
  * rtoc_set_foot_step_planner: setGaitPattern (mode RTOC_FOOT_STEP_FIXED: step_length, step_yaw, enable_stance_phase) or
  * setRaibertGaitPattern (RTOC_FOOT_STEP_RAIBERT: vcom_cmd, yaw_rate_cmd, swing_time, stance_time, gain; enable_stance_phase is
@@ -207,6 +208,45 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  *   (mpc_periodic_com_ref.cpp:69-79, the configuration reference alike) is judged against the model's two contacts: 0b11 is every
  *   contact.  A bit at or beyond 2 in any of phase_masks[nphases] is RTOC_ERR_BAD_ARG.
  *
+ * THE JUMP (gait = RTOC_GAIT_JUMP; line numbers: src/mpc/jump_foot_step_planner.cpp, and src/mpc/mpc_jump.cpp where named).  The
+ * model has exactly four point contacts (the quadruped form) or exactly two contact surfaces (is_biped_, :29-31); the feet choose
+ * the plan's layout: the quadrupeds' for four, the biped walk's, with rotations, for two.
+ *   rtoc_set_foot_step_planner: setJumpPattern(jump_length, step_yaw) (:43-49) -- step_length[3] carries jump_length and step_yaw
+ *   the yaw, each instance's own.  mode must be RTOC_FOOT_STEP_FIXED: the reference has no Raibert form of a jump, and
+ *   RTOC_FOOT_STEP_RAIBERT is RTOC_ERR_BAD_ARG.  projection applies as above; enable_stance_phase must be 0 or 1 and is ignored, as
+ *   are swing_time, stance_time and gain.  Going to or from this gait ends the state of rtoc_foot_step_planner_init.
+ *   rtoc_foot_step_planner_init: init(q) (:68-124).  R = the projected base rotation; local_k = (R^T R_k, R^T (p_k - q.head<3>()))
+ *   of every contact frame; R_goal = R_yaw R; q_goal = q with head<3>() += R_yaw jump_length and the quaternion
+ *   Quaterniond(R_goal).coeffs() (Eigen's conversion, not normalised); goal_k = (R_goal Rl_k, q.head<3>() + R_goal tl_k + R_yaw
+ *   jump_length).  The plan holds three steps: steps 0 and 1 are the placements the kinematics measured at q, step 2 the goal; on
+ *   four point feet every rotation is the identity (:99-105); CoM(0) = CoM(1) is the centre of mass at q and CoM(2) the one at
+ *   q_goal (a second kinematics pass); R(0) = R(1) = R, R(2) = R_goal.  Init also stores the q_ref of MPCJump::init
+ *   (mpc_jump.cpp:141-145) per instance: q with head<3>() += CoM(2) - CoM(0) and the quaternion Quaterniond(R(2)).coeffs().
+ *   current_step_ = 0 and the plan's size is 3 afterwards (every other gait: 0): MPCJump::init reads CoM(2) and R(2) before it plans.
+ *   rtoc_foot_step_plan: plan() (:127-170).  t, v and planning_steps are not read (planning_steps keeps its range check).
+ *   contact_status0 != 0 (hasActiveContacts): current_step_ 1 becomes 2; step 1 takes this tick's kinematics at q -- the full
+ *   frame placement on two surfaces, the translation alone on four point feet --, step 0 becomes a copy of step 1, step 2, if still
+ *   there, is untouched.  contact_status0 == 0: at current_step_ == 0 it becomes 1, step 1 takes placements, CoM and R of step 2
+ *   and the plan shrinks to size 2; at any other current_step_ nothing changes.  A bit at or beyond the model's contacts is
+ *   RTOC_ERR_BAD_ARG and nothing is launched.
+ *   rtoc_foot_step_plan_get: the layout of the feet, as above; step_length returns jump_length; size is 3 or 2.
+ *   rtoc_foot_step_place: unchanged -- grid point i gets step phase_of_grid_point[i] + 1.  MPCJump::resetContactPlacements
+ *   (mpc_jump.cpp:301-317) maps phase 0 to step 1 and phases 1 and 2 to step 2 before the flight, every phase to step 1 after it:
+ *   the caller passes min(phase, size - 2).  Grids with switching-time optimisation are served.
+ *   rtoc_foot_step_refs: the configuration reference alone.  r->configuration must be non-zero, every foot_term and com_term
+ *   negative, else RTOC_ERR_BAD_ARG; dims.np must be 6; nstages the grid's.  phase_of_grid_point and phase_masks may be NULL;
+ *   nphases and the periods are not read.  Every grid row of the per-instance q_ref table receives the stored q_ref, active
+ *   everywhere.  The reference does not depend on time: for this gait alone the call serves a grid with switching-time
+ *   optimisation, and needs no rtoc_set_grid_times.  RTOC_ERR_NOT_READY before rtoc_foot_step_planner_init.
+ *   The receding horizon of MPCJump::updateSolution (mpc_jump.cpp:206-222: it pops an event and re-sizes the problem) stays with the
+ *   caller, as the gait wrappers above do.
+ *   Where this departs from the reference.  (1) init never clears com_ref_ there (:115-118 push onto whatever is there), so a
+ *   planner initialised twice keeps answering with the first init's centres of mass; here a second init starts over.
+ *   (2) contact_position_ref_ and contact_surface_ref_ hold feet 0 and 1 alone there (:110-113, :163-166), for quadrupeds as well;
+ *   here contactPositions and contactSurfaces are the two parts of contactPlacements for every foot (MPCJump reads
+ *   contactPlacements).  (3) The reference takes any robot with at least four point contacts or at least two surfaces; here the
+ *   counts are exact, as for the other gaits.
+ *
  * rtoc_foot_step_plan_get: the plan of the first count <= batch instances -- positions[count][size][4][3], com[count][size][3],
  * R[count][size][9] (row-major), step_length[count][3] (the length in force; Raibert mode: what the heuristic planned),
  * ok[count] (1 iff every number of that instance's plan is finite), *size, *current_step.  Any pointer may be NULL; the arrays must
@@ -243,7 +283,8 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
  * *per_instance = the mode in force.  RTOC_ERR_NOT_READY where no table is set for the grid in force.
  *
  * rtoc_set_grid leaves the planner, its state and the plan alone (the plan does not depend on the grid), but forgets the tables:
- * place and refs again.  rtoc_set_robot_model ends the planner.  rtoc_clone copies planner, state and plan. */
+ * place and refs again (the jump's stored q_ref stays).  rtoc_set_robot_model ends the planner.  rtoc_clone copies planner, state,
+ * plan and the jump's q_goal and q_ref. */
 #define RTOC_MAX_PLAN_STEPS 32
 #define RTOC_FOOT_STEP_FIXED 0          /* TrotFootStepPlanner::setGaitPattern        */
 #define RTOC_FOOT_STEP_RAIBERT 1        /* TrotFootStepPlanner::setRaibertGaitPattern */
@@ -254,6 +295,7 @@ int rtoc_hold_contact_placements(rtoc_ctx* ctx, int source, int grid_point, int 
 #define RTOC_GAIT_PACE 2                /* PaceFootStepPlanner                        */
 #define RTOC_GAIT_FLYING_TROT 3         /* FlyingTrotFootStepPlanner                  */
 #define RTOC_GAIT_BIPED_WALK 4          /* BipedWalkFootStepPlanner: two contact surfaces */
+#define RTOC_GAIT_JUMP 5                /* JumpFootStepPlanner: four point feet or two contact surfaces */
 typedef struct rtoc_foot_step_planner {
   int mode;                    /* RTOC_FOOT_STEP_*                                                       */
   int projection;              /* RTOC_PROJECT_*: the reference's ProjectRotationMatrix divides by R00^2 + 2 R01, which is
@@ -261,7 +303,7 @@ typedef struct rtoc_foot_step_planner {
   int enable_stance_phase;     /* fixed mode (ignored by the flying trot; the biped walk: enable_double_support_phase) */
   int gait;                    /* RTOC_GAIT_*: 0, the value of a zeroed struct, is the trot              */
   double swing_time, stance_time, gain;   /* Raibert mode (gait timing; shared by the batch)             */
-  double step_length[3], step_yaw;        /* fixed mode, per instance                                    */
+  double step_length[3], step_yaw;        /* fixed mode, per instance (the jump: jump_length, step_yaw)  */
   double vcom_cmd[3], yaw_rate_cmd;       /* Raibert mode, per instance                                  */
 } rtoc_foot_step_planner;
 typedef struct rtoc_foot_step_ref_params {

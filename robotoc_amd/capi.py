@@ -54,6 +54,7 @@ FOOT_STEP_FIXED, FOOT_STEP_RAIBERT = 0, 1  # RTOC_FOOT_STEP_*
 PROJECT_AS_REFERENCE, PROJECT_YAW = 0, 1  # RTOC_PROJECT_*
 GAIT_TROT, GAIT_CRAWL, GAIT_PACE, GAIT_FLYING_TROT = 0, 1, 2, 3  # RTOC_GAIT_*
 GAIT_BIPED_WALK = 4  # on two contact surfaces; the others on four point contacts
+GAIT_JUMP = 5  # JumpFootStepPlanner: on four point contacts or on two contact surfaces
 
 
 class FootStepPlanner(C.Structure):
@@ -265,7 +266,8 @@ def _dp(a):
 
 class Context:
     """Thin RAII wrapper over rtoc_ctx: one context per (device, problem shape, batch)."""
-    _fs_gait = GAIT_TROT   # the gait of the foot-step planner in force: it decides the layout of rtoc_foot_step_plan_get's positions
+    _fs_gait = GAIT_TROT   # the gait of the foot-step planner in force and the contacts of the model it was set for: the feet decide
+    _fs_ncontacts = 4      # the layout of rtoc_foot_step_plan_get's positions
 
     def __init__(self, dims, max_stages, batch, device=0):
         self.dims = dims
@@ -715,6 +717,7 @@ class Context:
         arr = (FootStepPlanner * len(rows))(*rows)
         _chk(lib().rtoc_set_foot_step_planner(self._h, C.cast(arr, C.c_void_p), 1 if per_instance else 0))
         self._fs_gait = rows[0].gait   # (a refused call raised above and leaves the planner in force)
+        self._fs_ncontacts = self._model_ncontacts
 
     def foot_step_planner_init(self):
         """rtoc_foot_step_planner_init: the planner's init (one for the four quadruped gaits, the biped walk's own) at the q of set_initial_state, every instance"""
@@ -727,10 +730,10 @@ class Context:
 
     def foot_step_plan_get(self):
         """rtoc_foot_step_plan_get: a dict -- positions [batch, size, 4, 3], com [batch, size, 3], R [batch, size, 3, 3],
-        step_length [batch, 3], ok [batch] (bool), size, current_step.  The biped walk (a planner with gait = GAIT_BIPED_WALK was set
-        last): positions [batch, size, 2, 3] and one more key, surfaces [batch, size, 2, 3, 3]"""
+        step_length [batch, 3], ok [batch] (bool), size, current_step.  A planner on two feet (gait = GAIT_BIPED_WALK was set last, or
+        GAIT_JUMP on a model of two contact surfaces): positions [batch, size, 2, 3] and one more key, surfaces [batch, size, 2, 3, 3]"""
         B, S = self.batch, MAX_PLAN_STEPS + 2
-        two = self._fs_gait == GAIT_BIPED_WALK
+        two = self._fs_gait == GAIT_BIPED_WALK or (self._fs_gait == GAIT_JUMP and self._fs_ncontacts == 2)
         w = 24 if two else 12   # the library's `positions` per (instance, step): [4][3], or [2][3] and [2][9] behind them
         pos, com, R, sl = np.zeros((B, S * w)), np.zeros((B, S * 3)), np.zeros((B, S * 9)), np.zeros((B, 3))
         ok, size, cur = np.zeros(B, dtype=np.int32), C.c_int(0), C.c_int(0)
@@ -752,13 +755,21 @@ class Context:
         ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
         _chk(lib().rtoc_foot_step_place(self._h, ph.ctypes.data_as(C.POINTER(C.c_int)), ph.size))
 
-    def foot_step_refs(self, refs, phase_of_grid_point, phase_masks):
+    def foot_step_refs(self, refs, phase_of_grid_point=None, phase_masks=None):
         """rtoc_foot_step_refs: `refs` = a FootStepRefs struct; the swing-foot, CoM and configuration references of every
-        (instance, grid point) into the per-instance reference tables"""
-        ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
-        mk = np.ascontiguousarray(phase_masks, dtype=np.uint32)
-        _chk(lib().rtoc_foot_step_refs(self._h, C.cast(C.pointer(refs), C.c_void_p), ph.ctypes.data_as(C.POINTER(C.c_int)),
-                                       mk.ctypes.data_as(C.POINTER(C.c_uint)), mk.size, ph.size))
+        (instance, grid point) into the per-instance reference tables.  The jump (GAIT_JUMP) writes its one configuration reference on
+        every row of the grid in force and reads no phases: both may be None, which passes NULL"""
+        if phase_of_grid_point is None:
+            ph_p, nstages = None, self.nstages
+        else:
+            ph = np.ascontiguousarray(phase_of_grid_point, dtype=np.int32)
+            ph_p, nstages = ph.ctypes.data_as(C.POINTER(C.c_int)), ph.size
+        if phase_masks is None:
+            mk_p, nphases = None, 0
+        else:
+            mk = np.ascontiguousarray(phase_masks, dtype=np.uint32)
+            mk_p, nphases = mk.ctypes.data_as(C.POINTER(C.c_uint)), mk.size
+        _chk(lib().rtoc_foot_step_refs(self._h, C.cast(C.pointer(refs), C.c_void_p), ph_p, mk_p, nphases, nstages))
 
     def task_ref_table(self, term):
         """rtoc_get_task_ref_table: (R [batch, nstages, 3, 3], p [batch, nstages, 3], active [batch, nstages] (bool), per_instance)

@@ -3,7 +3,8 @@
 // MPCTrot::resetContactPlacements (src/mpc/mpc_trot.cpp:357-372) does with the plan -- the placements of every contact phase,
 // MPCPeriodicSwingFootRef x 4, MPCPeriodicCoMRef, MPCPeriodicConfigurationRef -- for every instance of a batch, each with its own
 // command; and the plan recurrences of PaceFootStepPlanner, CrawlFootStepPlanner and FlyingTrotFootStepPlanner
-// (src/mpc/{pace,crawl,flying_trot}_foot_step_planner.cpp), whose MPC shells build the same references.  Nothing here leaves the device: the plan is read by the two kernels behind it, which write the per-instance table of
+// (src/mpc/{pace,crawl,flying_trot}_foot_step_planner.cpp), whose MPC shells build the same references; JumpFootStepPlanner
+// (src/mpc/jump_foot_step_planner.cpp) with the q_ref of MPCJump::init.  Nothing here leaves the device: the plan is read by the two kernels behind it, which write the per-instance table of
 // contact placements and the per-instance reference tables where the cost kernels read them.
 //
 // foot_step_init_kernel / foot_step_plan_kernel.  Mapping: one lane per (instance, foot), FOOT-MAJOR within the wave -- lane l is
@@ -38,6 +39,22 @@
 // step and lane: its foot's translation (3), its foot's rotation (9) and its half of [CoM | R] (6), all runs of 32 consecutive
 // doubles per half and slot; the lanes of foot 0 write the planner state back after the last load.  Lanes beyond the batch follow
 // the last instance and store nothing.
+//
+// jump_init_kernel<NF> / jump_plan_kernel<NF>.  JumpFootStepPlanner (src/mpc/jump_foot_step_planner.cpp:68-170) on four point feet (NF = 4,
+// the quadrupeds' 24-slot plan) or two contact surfaces (NF = 2, the biped walk's 36-slot plan with its rotations).  Mapping: one
+// lane per (instance, foot), FOOT-MAJOR within the wave -- lane l is foot l / (64 / NF) of instance (64 / NF) blockIdx.x + l % (64 / NF),
+// 16 instances per wave for four feet and 32 for two -- so that a foot group's lanes write consecutive doubles of every [slot][batch]
+// array.  What an instance shares across its feet (R, R_goal, R_yaw jump_length, the quaternion of R_goal) is computed redundantly by
+// its lanes: no __shfl, no LDS, no atomics, and a lane beyond the batch returns at once and stores nothing.  The init runs in two
+// phases around the second kinematics pass (JumpInitArgs::phase, wave-uniform): phase 0 writes q_goal[batch][nq], the kinematics
+// then give CoM at q_goal, phase 1 writes the three steps and the q_ref of MPCJump::init (mpc_jump.cpp:141-145).  Every case of
+// plan() is one wave-uniform flag (JumpPlanArgs::landed) the host decides; a tick that changes nothing launches nothing.
+// Loads per lane, init: 7 doubles of q (a state apart) and 4 of the command (runs of 16 | 32 consecutive doubles); phase 1: 3 of
+// its foot's position, NF = 2 also 9 of its rotation, from the kinematics' [batch][NF][3 | 9], and 3 + 3 of the two centres of
+// mass; the nq / NF entries of q a lane copies lie NF apart.  Stores, phase 0: nq / NF doubles of q_goal; phase 1: per step what
+// fs_store_step / fs_store_biped_step write (runs of 16 | 32 consecutive doubles per group and slot), three steps, and nq / NF
+// doubles of q_ref.  Plan, landed: 3 (NF = 2: 12) doubles loaded from the kinematics and stored into steps 1 and 0; take-off: the
+// 6 (NF = 2: 18) slots a lane owns of step 2 loaded and stored into step 1.
 //
 // foot_step_place_kernel / foot_step_refs_kernel.  Mapping: one lane per DOUBLE written, the doubles of an (instance, grid point)
 // pair adjacent and the pairs in table order, so that a wave writes one contiguous run of 512 bytes whatever the record size: 12
@@ -169,6 +186,49 @@ static __device__ __forceinline__ rbd::M3 fs_projected_base_rotation(const doubl
   }
   R.m[2] = 0.0, R.m[5] = 0.0, R.m[6] = 0.0, R.m[7] = 0.0, R.m[8] = 1.0;
   return R;
+}
+
+// Quaterniond(R): Eigen's conversion (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>), q = (x, y, z, w)
+// One copy for the refs kernel (R(phase) of the plan) and the jump's init (R_goal)
+static __device__ __forceinline__ void fs_eigen_quat(const rbd::M3& M, double* q) {
+  const double* const m = M.m;
+  double t = m[0] + m[4] + m[8];
+  if (t > 0.0) {
+    t = sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
+  } else {
+    // i = the largest diagonal entry as Eigen picks it, j = (i + 1) % 3, k = (j + 1) % 3; the three cases written out, so that
+    // nothing is indexed by a register
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > (i == 1 ? m[4] : m[0])) i = 2;
+    if (i == 0) {
+      t = sqrt(m[0] - m[4] - m[8] + 1.0);
+      q[0] = 0.5 * t;
+      t = 0.5 / t;
+      q[3] = (m[7] - m[5]) * t, q[1] = (m[3] + m[1]) * t, q[2] = (m[6] + m[2]) * t;
+    } else if (i == 1) {
+      t = sqrt(m[4] - m[8] - m[0] + 1.0);
+      q[1] = 0.5 * t;
+      t = 0.5 / t;
+      q[3] = (m[2] - m[6]) * t, q[2] = (m[7] + m[5]) * t, q[0] = (m[1] + m[3]) * t;
+    } else {
+      t = sqrt(m[8] - m[0] - m[4] + 1.0);
+      q[2] = 0.5 * t;
+      t = 0.5 / t;
+      q[3] = (m[3] - m[1]) * t, q[0] = (m[2] + m[6]) * t, q[1] = (m[5] + m[7]) * t;
+    }
+  }
+}
+
+// R(step) of a plan: nine doubles a batch apart
+static __device__ __forceinline__ rbd::M3 fs_load_plan_R(const double* plan_R, size_t B) {
+  rbd::M3 M;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) M.m[k] = plan_R[(size_t)k * B];
+  return M;
 }
 
 // TrotFootStepPlanner::init(q) (:91-106) at the q of rtoc_set_initial_state
@@ -402,6 +462,142 @@ static __global__ __launch_bounds__(64) void biped_walk_plan_kernel(FsPlanArgs a
   }
 }
 
+// ---- JumpFootStepPlanner (src/mpc/jump_foot_step_planner.cpp) ----
+struct JumpInitArgs {
+  const double* x0;        // [batch][nq + nv]
+  const double* cmd;       // [FS_CMD_SLOTS][batch]: jump_length in FS_CMD_STEP, the yaw in FS_CMD_YAW
+  const double* feet;      // phase 1: [batch][NF][3] world positions of the contact frames at q
+  const double* feet_R;    // phase 1, NF = 2: [batch][2][9] their rotations, row-major
+  const double* com;       // phase 1: [batch][3] the centre of mass at q ...
+  const double* com_goal;  // ... and at q_goal (the second kinematics pass)
+  double* plan;            // phase 1: steps 0, 1, 2
+  double* qgoal;           // phase 0: [batch][nq] q_goal, which the second kinematics pass reads
+  double* qref;            // phase 1: [batch][nq] the q_ref of MPCJump::init (mpc_jump.cpp:141-145)
+  int batch, nq, nx;       // nx = nq + nv
+  int projection;          // RTOC_PROJECT_*
+  int phase;               // 0: q_goal alone; 1: the plan and q_ref (wave-uniform)
+};
+// init(q) (:68-124) at the q of rtoc_set_initial_state, around the second kinematics pass.  Both phases derive R, R_goal = R_yaw R,
+// R_yaw jump_length and Quaterniond(R_goal) from the same loads by the same arithmetic, so q_goal and the plan agree to the bit
+template <int NF>
+static __global__ __launch_bounds__(64) void jump_init_kernel(JumpInitArgs a) {
+  using namespace rbd;
+  constexpr int PER = 64 / NF;   // instances per wave
+  const int lane = threadIdx.x, f = lane / PER, B = a.batch;
+  const int b = blockIdx.x * PER + lane % PER;
+  if (b >= B) return;   // no lane reads another's registers
+  const double* const q = a.x0 + (size_t)b * a.nx;
+  const double* const cmd = a.cmd + b;
+  const V3 jl = mk(cmd[(size_t)FS_CMD_STEP * B], cmd[(size_t)(FS_CMD_STEP + 1) * B], cmd[(size_t)(FS_CMD_STEP + 2) * B]);
+  const double yaw = cmd[(size_t)FS_CMD_YAW * B];
+  const double sy = sin(yaw), cy = cos(yaw);
+  const M3 R = fs_projected_base_rotation(q, a.projection);   // :69-70
+  const M3 Rg = fs_yaw_times(sy, cy, R);                       // R_goal (:82)
+  const V3 hop = mk(cy * jl.x - sy * jl.y, sy * jl.x + cy * jl.y, jl.z);   // R_yaw_ jump_length_
+  double qg[4];
+  fs_eigen_quat(Rg, qg);   // :83, and Quaterniond(R(2)) of mpc_jump.cpp:144: the same matrix
+  V3 shift = hop;          // what the head<3>() of q moves by: q_goal (:85); q_ref: CoM(2) - CoM(0)
+  V3 com0 = mk(0, 0, 0), com2 = mk(0, 0, 0);
+  if (a.phase == 1) {
+    com0 = ldv3(a.com + (size_t)b * 3), com2 = ldv3(a.com_goal + (size_t)b * 3);
+    shift = com2 - com0;
+  }
+  // ---- q_goal or q_ref: q with the head moved and the quaternion replaced (not normalised, as in the reference) ----
+  double* const qout = (a.phase == 0 ? a.qgoal : a.qref) + (size_t)b * a.nq;
+  for (int k = f; k < a.nq; k += NF) {
+    double x = q[k];
+    if (k < 3)
+      x += k == 0 ? shift.x : k == 1 ? shift.y : shift.z;
+    else if (k < 7)
+      x = k == 3 ? qg[0] : k == 4 ? qg[1] : k == 5 ? qg[2] : qg[3];
+    qout[k] = x;
+  }
+  if (a.phase == 0) return;
+  // ---- the three steps (:72-122): where the feet are, twice, and the goal ----
+  const V3 base = ldv3(q);
+  const V3 p = ldv3(a.feet + ((size_t)b * NF + f) * 3);
+  const V3 local = mulT(R, p - base);            // :80
+  const V3 goal = (base + mul(Rg, local)) + hop; // :92-93
+  if constexpr (NF == 4) {
+    // point feet: every rotation is the identity (:99-105), which the 24-slot layout leaves unwritten
+    fs_store_step(a.plan, 0, B, b, f, p, com0, R);
+    fs_store_step(a.plan, 1, B, b, f, p, com0, R);
+    fs_store_step(a.plan, 2, B, b, f, goal, com2, Rg);
+  } else {
+    const M3 S = ldm3(a.feet_R + ((size_t)b * NF + f) * 9);
+    const M3 Sg = mul(Rg, mul(transpose(R), S));   // R_goal (R^T R_k) (:79, :91)
+    fs_store_biped_step(a.plan, 0, B, b, f, p, S, com0, R);
+    fs_store_biped_step(a.plan, 1, B, b, f, p, S, com0, R);
+    fs_store_biped_step(a.plan, 2, B, b, f, goal, Sg, com2, Rg);
+  }
+}
+
+struct JumpPlanArgs {
+  const double* feet;    // landed: [batch][NF][3] this tick's kinematics at q
+  const double* feet_R;  // landed, NF = 2: [batch][2][9]
+  double* plan;
+  int batch;
+  int landed;            // 1: feet on the ground (:132-148); 0: the first tick of the flight (:150-158).  Wave-uniform
+};
+// plan (:127-170).  The host resolved the case; a tick that changes nothing launches nothing
+template <int NF>
+static __global__ __launch_bounds__(64) void jump_plan_kernel(JumpPlanArgs a) {
+  using L = FsPlanLayout<NF>;
+  constexpr int PER = 64 / NF;
+  constexpr int SHARE = NF == 4 ? 3 : 6;   // a lane's part of [CoM | R]
+  const int lane = threadIdx.x, f = lane / PER, B = a.batch;
+  const int b = blockIdx.x * PER + lane % PER;
+  if (b >= B) return;
+  double* const s0 = a.plan + b;
+  double* const s1 = s0 + (size_t)L::SLOTS * B;
+  if (a.landed) {
+    // step 1 <- the kinematics (a biped: the frame placement; a quadruped: the translation, its rotation stays); step 0 <- step 1
+    const double* const p = a.feet + ((size_t)b * NF + f) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double x = p[k];
+      s1[(size_t)(L::POS + 3 * f + k) * B] = x, s0[(size_t)(L::POS + 3 * f + k) * B] = x;
+    }
+    if constexpr (NF == 2) {
+      const double* const S = a.feet_R + ((size_t)b * NF + f) * 9;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double x = S[k];
+        s1[(size_t)(L::SURF + 9 * f + k) * B] = x, s0[(size_t)(L::SURF + 9 * f + k) * B] = x;
+      }
+    }
+  } else {
+    // step 1 <- step 2: placements, CoM and R (:152-157); the host shrinks the plan to two steps.  A lane moves the slots it owns
+    const double* const s2 = s1 + (size_t)L::SLOTS * B;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s1[(size_t)(L::POS + 3 * f + k) * B] = s2[(size_t)(L::POS + 3 * f + k) * B];
+    if constexpr (NF == 2) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s1[(size_t)(L::SURF + 9 * f + k) * B] = s2[(size_t)(L::SURF + 9 * f + k) * B];
+    }
+#pragma unroll
+    for (int k = 0; k < SHARE; ++k) s1[(size_t)(L::COM + SHARE * f + k) * B] = s2[(size_t)(L::COM + SHARE * f + k) * B];
+  }
+}
+
+// rtoc_foot_step_refs of the jump: every grid row of the per-instance q_ref table <- the stored q_ref, active everywhere.  One lane
+// per double written, as foot_step_refs_kernel has it
+struct JumpRefsArgs {
+  const double* qref;    // [batch][nq]
+  double* qtab;          // [batch][nstages][nq]
+  int* qtab_active;      // [batch][nstages]
+  int batch, nstages, nq;
+};
+static __global__ __launch_bounds__(256) void jump_refs_kernel(JumpRefsArgs a) {
+  const int n = a.nstages, nq = a.nq;
+  const size_t total = (size_t)a.batch * n * nq;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int k = (int)(e % nq), st = (int)((e / nq) % n), b = (int)(e / nq / n);
+    if (k == 0) a.qtab_active[(size_t)b * n + st] = 1;
+    a.qtab[e] = a.qref[(size_t)b * nq + k];
+  }
+}
+
 // the loop of MPCTrot::resetContactPlacements (mpc_trot.cpp:361-365): grid point i <- contactPositions(phase_i + 1); NF = 2, the
 // loop of MPCBipedWalk::resetContactPlacements (mpc_biped_walk.cpp:347-359): contactPlacements(phase_i + 1), rotations included
 struct FsPlaceArgs {
@@ -454,42 +650,6 @@ struct FsRefsArgs {
 constexpr int FS_ENTRY_WORDS = (int)(sizeof(rtoc_task_ref_entry) / 8);   // 9 R, 3 p, 1 (active, pad)
 static_assert(sizeof(rtoc_task_ref_entry) == 13 * 8, "an entry is written as 13 eight-byte words");
 
-// Quaterniond(R): Eigen's conversion (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>), q = (x, y, z, w)
-static __device__ __forceinline__ void fs_eigen_quat(const double* plan_R, size_t B, double* q) {
-  double m[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) m[k] = plan_R[(size_t)k * B];
-  double t = m[0] + m[4] + m[8];
-  if (t > 0.0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
-  } else {
-    // i = the largest diagonal entry as Eigen picks it, j = (i + 1) % 3, k = (j + 1) % 3; the three cases written out, so that
-    // nothing is indexed by a register
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > (i == 1 ? m[4] : m[0])) i = 2;
-    if (i == 0) {
-      t = sqrt(m[0] - m[4] - m[8] + 1.0);
-      q[0] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[7] - m[5]) * t, q[1] = (m[3] + m[1]) * t, q[2] = (m[6] + m[2]) * t;
-    } else if (i == 1) {
-      t = sqrt(m[4] - m[8] - m[0] + 1.0);
-      q[1] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[2] - m[6]) * t, q[2] = (m[7] + m[5]) * t, q[0] = (m[1] + m[3]) * t;
-    } else {
-      t = sqrt(m[8] - m[0] - m[4] + 1.0);
-      q[2] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[3] - m[1]) * t, q[0] = (m[2] + m[6]) * t, q[1] = (m[5] + m[7]) * t;
-    }
-  }
-}
-
 template <int NF>
 static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a) {
   using L = FsPlanLayout<NF>;
@@ -540,7 +700,7 @@ static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a
       const int ph = a.phase[st];
       const double t = a.t[st];
       double qa[4];
-      fs_eigen_quat(a.plan + ((size_t)ph * L::SLOTS + L::R) * B + b, B, qa);
+      fs_eigen_quat(fs_load_plan_R(a.plan + ((size_t)ph * L::SLOTS + L::R) * B + b, B), qa);
       const int c = k - 3;
       const double xa = c == 0 ? qa[0] : c == 1 ? qa[1] : c == 2 ? qa[2] : qa[3];
       x = xa;
@@ -548,7 +708,7 @@ static __global__ __launch_bounds__(256) void foot_step_refs_kernel(FsRefsArgs a
         const int cycle = (int)floor((t - pr.t0) / period);
         const double rate = (t - pr.t0 - cycle * period) / pr.period_active;
         double qb[4];
-        fs_eigen_quat(a.plan + ((size_t)(ph + pr.nph) * L::SLOTS + L::R) * B + b, B, qb);
+        fs_eigen_quat(fs_load_plan_R(a.plan + ((size_t)(ph + pr.nph) * L::SLOTS + L::R) * B + b, B), qb);
         // Eigen's slerp (QuaternionBase::slerp): the near-parallel branch, the sign flip of the shorter arc
         const double one = 1.0 - 2.220446049250313e-16;
         const double d = qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2] + qa[3] * qb[3];

@@ -356,6 +356,8 @@ struct FootStepState {
   DevBuf<double> d_fs_state; // [FS_STATE_SLOTS][batch] rotation, local offsets (the biped walk: leg distance, CoM height), filter
   DevBuf<double> d_fs_plan;  // [RTOC_MAX_PLAN_STEPS + 2][FS_PLAN_SLOTS | FS_BIPED_SLOTS][batch]
   DevBuf<double> d_fs_q0;    // [batch][nq] the q of the init
+  DevBuf<double> d_fs_qgoal; // the jump: [batch][nq] q_goal of init(q), which the second kinematics pass reads
+  DevBuf<double> d_fs_qref;  // the jump: [batch][nq] the q_ref of MPCJump::init
   void clone_from(const FootStepState& src, CopyChain& dup) {
     if (!src.fs_on) return;
     fs_on = 1, fs_init = src.fs_init, fs_shared = src.fs_shared, fs_current_step = src.fs_current_step, fs_size = src.fs_size;
@@ -363,6 +365,8 @@ struct FootStepState {
     dup(d_fs_state, src.d_fs_state);
     dup(d_fs_plan, src.d_fs_plan);
     dup(d_fs_q0, src.d_fs_q0);
+    dup(d_fs_qgoal, src.d_fs_qgoal);
+    dup(d_fs_qref, src.d_fs_qref);
   }
   // not copied: the scratch of one call
   DevBuf<double> d_fs_fk;    // [batch][4][3] foot positions + [batch][3] centre of mass (contact_frame_placements_kernel); the biped
@@ -517,7 +521,7 @@ int launch_unconstr_rows(rtoc_ctx* c, UnconstrRowsPhase phase);
 // (nullptr: left out) and, for the contact surfaces of the biped walk, out_R[batch][ncontacts][9] row-major
 int placements_ready(const rtoc_ctx* c);
 int placements_per_instance(rtoc_ctx* c, bool need_rot);
-int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com, double* out_R = nullptr);
+int launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com, double* out_R = nullptr, const double* q = nullptr, size_t q_stride = 0);
 // rt_task_costs.hip
 int ensure_grid_times_inst(rtoc_ctx* c);
 int task_costs_ready(rtoc_ctx* c, bool unconstr);

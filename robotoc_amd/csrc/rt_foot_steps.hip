@@ -1,4 +1,4 @@
-// rt_foot_steps.hip -- the foot-step planners (trot, crawl, pace, flying trot; the biped walk on two contact surfaces) and the MPC references of every instance on the device: planner and commands, init,
+// rt_foot_steps.hip -- the foot-step planners (trot, crawl, pace, flying trot; the biped walk on two contact surfaces; the jump on either kind of feet) and the MPC references of every instance on the device: planner and commands, init,
 // plan, the read-back of the plan, the placements of every contact phase, the three periodic references (foot_step_planner.hpp).
 #include <cmath>
 
@@ -12,8 +12,9 @@ using namespace rtoc;
   if ((c)->parnmpc) return RTOC_ERR_BAD_ARG;
 
 static constexpr int FS_MAX_STEPS = RTOC_MAX_PLAN_STEPS + 2;
-// the kinematics' scratch per instance: [4][3] + the centre of mass, or the biped walk's [2][3] + [3] + [2][9]
-static constexpr int FS_FK_DOUBLES = 27;
+// the kinematics' scratch per instance: [4][3] + the centre of mass, or the biped walk's [2][3] + [3] + [2][9]; the jump's init
+// keeps a second centre of mass (at q_goal) behind them
+static constexpr int FS_FK_DOUBLES = 30;
 
 // the gait of the reference's quadrupeds: exactly four point contacts (LF, LH, RF, RH = contacts 0..3)
 static bool four_point_feet(const rtoc_ctx* c) {
@@ -28,15 +29,22 @@ static bool two_surface_feet(const rtoc_ctx* c) {
   const rtoc_robot_model& m = c->h_model->m;
   return m.ncontacts == 2 && m.contact_type[0] == RTOC_CONTACT_SURFACE && m.contact_type[1] == RTOC_CONTACT_SURFACE;
 }
-static bool biped(const rtoc_ctx* c) { return c->fs_shared.gait == RTOC_GAIT_BIPED_WALK; }
-// doubles per (instance, step) of the plan on the device, and feet
+static bool jump(const rtoc_ctx* c) { return c->fs_shared.gait == RTOC_GAIT_JUMP; }
+// the feet of the planner in force, which choose the plan's layout and the kernels' form: the biped walk has two, the jump as many as
+// the model it was set for (a planner does not outlive its model), every other gait four
+static int plan_feet(const rtoc_ctx* c) {
+  if (c->fs_shared.gait == RTOC_GAIT_BIPED_WALK) return 2;
+  return jump(c) && two_surface_feet(c) ? 2 : 4;
+}
+static bool biped(const rtoc_ctx* c) { return plan_feet(c) == 2; }
+// doubles per (instance, step) of the plan on the device
 static int plan_slots(const rtoc_ctx* c) { return biped(c) ? FS_BIPED_SLOTS : FS_PLAN_SLOTS; }
-static int plan_feet(const rtoc_ctx* c) { return biped(c) ? 2 : 4; }
 // setGaitPattern has no checks; setRaibertGaitPattern: trot_foot_step_planner.cpp:68-76 (the period of raibert_heuristic.cpp:39 is
 // positive with them, its gain check is the same one; biped_walk_foot_step_planner.cpp:66-74 are the same three)
 static bool planner_valid(const rtoc_foot_step_planner& p) {
-  if (p.gait < RTOC_GAIT_TROT || p.gait > RTOC_GAIT_BIPED_WALK) return false;
+  if (p.gait < RTOC_GAIT_TROT || p.gait > RTOC_GAIT_JUMP) return false;
   if (p.mode != RTOC_FOOT_STEP_FIXED && p.mode != RTOC_FOOT_STEP_RAIBERT) return false;
+  if (p.gait == RTOC_GAIT_JUMP && p.mode != RTOC_FOOT_STEP_FIXED) return false;   // setJumpPattern alone: there is no Raibert form of a jump
   if (p.projection != RTOC_PROJECT_AS_REFERENCE && p.projection != RTOC_PROJECT_YAW) return false;
   if (p.enable_stance_phase != 0 && p.enable_stance_phase != 1) return false;
   if (p.mode == RTOC_FOOT_STEP_RAIBERT && (!(p.swing_time > 0.0) || !(p.stance_time >= 0.0) || !(p.gain > 0.0))) return false;
@@ -97,7 +105,11 @@ int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int
   for (int b = 0; b < n; ++b)
     if (!planner_valid(p[b]) || !same_structure(p[b], p[0])) return RTOC_ERR_BAD_ARG;
   // a gait and the feet it is written for: the quadrupeds' on four point contacts, the biped walk on two contact surfaces
-  if (!(p[0].gait == RTOC_GAIT_BIPED_WALK ? two_surface_feet(c) : four_point_feet(c))) return RTOC_ERR_BAD_ARG;
+  // (the jump on either: jump_foot_step_planner.cpp:25-31, with exact counts here)
+  const bool feet_fit = p[0].gait == RTOC_GAIT_BIPED_WALK ? two_surface_feet(c)
+                        : p[0].gait == RTOC_GAIT_JUMP     ? two_surface_feet(c) || four_point_feet(c)
+                                                          : four_point_feet(c);
+  if (!feet_fit) return RTOC_ERR_BAD_ARG;
   std::vector<double> cmd((size_t)FS_CMD_SLOTS * B, 0.0);
   for (int b = 0; b < B; ++b) {
     const rtoc_foot_step_planner& q = p[per_instance ? b : 0];
@@ -110,6 +122,8 @@ int rtoc_set_foot_step_planner(rtoc_ctx* c, const rtoc_foot_step_planner* p, int
   HIP_TRY(c->d_fs_cmd.reserve(cmd.size()));
   HIP_TRY(hipMemcpyAsync(c->d_fs_cmd.p, cmd.data(), sizeof(double) * cmd.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  // the jump's plan is its init's and nobody else's: going to or from it ends the state (among the other gaits init is one and the same)
+  if (c->fs_on && c->fs_shared.gait != p[0].gait && (jump(c) || p[0].gait == RTOC_GAIT_JUMP)) c->fs_init = 0, c->fs_size = 0;
   c->fs_shared = p[0];
   c->fs_on = 1;
   return RTOC_OK;
@@ -124,11 +138,49 @@ static int reserve_planner(rtoc_ctx* c) {
   return RTOC_OK;
 }
 
+// JumpFootStepPlanner::init(q) (:68-124) and the q_ref of MPCJump::init (mpc_jump.cpp:141-145): the kinematics at q, q_goal, the
+// kinematics at q_goal, then the three steps of the plan
+static int jump_init(rtoc_ctx* c) {
+  if (!c->d_fs_cmd.p) return RTOC_ERR_NOT_READY;
+  const size_t B = c->batch, nf = plan_feet(c), nq = c->h_model->m.nq;
+  HIP_TRY(c->d_fs_qgoal.reserve(B * nq));
+  HIP_TRY(c->d_fs_qref.reserve(B * nq));
+  double* const feet = c->d_fs_fk.p;
+  double* const com = feet + B * nf * 3;
+  double* const com_goal = com + B * 3;
+  double* const feet_R = nf == 2 ? com_goal + B * 3 : nullptr;
+  JumpInitArgs a{};
+  a.x0 = c->d_x0.p, a.cmd = c->d_fs_cmd.p, a.feet = feet, a.feet_R = feet_R, a.com = com, a.com_goal = com_goal;
+  a.plan = c->d_fs_plan.p, a.qgoal = c->d_fs_qgoal.p, a.qref = c->d_fs_qref.p;
+  a.batch = (int)B, a.nq = (int)nq, a.nx = (int)nq + c->h_model->m.nv;
+  a.projection = c->fs_shared.projection;
+  const unsigned per = 64 / (unsigned)nf;
+  const dim3 grid((unsigned)((B + per - 1) / per));
+  auto launch = [&](int phase) {
+    a.phase = phase;
+    if (nf == 2)
+      hipLaunchKernelGGL(jump_init_kernel<2>, grid, dim3(64), 0, c->stream, a);
+    else
+      hipLaunchKernelGGL(jump_init_kernel<4>, grid, dim3(64), 0, c->stream, a);
+  };
+  int rc = launch_frame_positions(c, feet, com, feet_R);
+  if (rc) return rc;
+  launch(0);
+  HIP_TRY(hipGetLastError());
+  rc = launch_frame_positions(c, nullptr, com_goal, nullptr, c->d_fs_qgoal.p, nq);
+  if (rc) return rc;
+  launch(1);
+  HIP_TRY(hipGetLastError());
+  c->fs_init = 1, c->fs_current_step = 0, c->fs_size = 3;   // MPCJump::init reads CoM(2) and R(2) before it plans
+  return RTOC_OK;
+}
+
 int rtoc_foot_step_planner_init(rtoc_ctx* c) {
   CHECK_READY(c);
   if (!c->fs_on || !c->h_model || !c->d_x0.p) return RTOC_ERR_NOT_READY;
   int rc = reserve_planner(c);
   if (rc) return rc;
+  if (jump(c)) return jump_init(c);
   const int B = c->batch, nf = plan_feet(c);
   double* const com = c->d_fs_fk.p + (size_t)B * nf * 3;
   rc = launch_frame_positions(c, c->d_fs_fk.p, com);
@@ -138,7 +190,7 @@ int rtoc_foot_step_planner_init(rtoc_ctx* c) {
   a.state = c->d_fs_state.p, a.plan = c->d_fs_plan.p, a.q0 = c->d_fs_q0.p;
   a.batch = B, a.nq = c->h_model->m.nq, a.nx = c->h_model->m.nq + c->h_model->m.nv;
   a.projection = c->fs_shared.projection;
-  if (biped(c))
+  if (nf == 2)
     hipLaunchKernelGGL(biped_walk_init_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, c->stream, a);
   else
     hipLaunchKernelGGL(foot_step_init_kernel, dim3((unsigned)((B + 15) / 16)), dim3(64), 0, c->stream, a);
@@ -199,11 +251,42 @@ static bool plan_cases(const rtoc_foot_step_planner& p, unsigned status, int pla
   return true;
 }
 
+// JumpFootStepPlanner::plan (:127-170): current_step_ and the contact status are shared by the batch, the host walks the cases
+static int jump_plan(rtoc_ctx* c, unsigned status) {
+  const int B = c->batch, nf = plan_feet(c);
+  if (status >> nf) return RTOC_ERR_BAD_ARG;   // a contact the model does not have
+  JumpPlanArgs a{};
+  a.plan = c->d_fs_plan.p, a.batch = B;
+  int cur = c->fs_current_step, size = c->fs_size;
+  if (status) {
+    // hasActiveContacts (:132-148)
+    if (cur == 1) cur = 2;
+    HIP_TRY(c->d_fs_fk.reserve((size_t)B * FS_FK_DOUBLES));   // scratch: a clone starts without it
+    double* const feet_R = nf == 2 ? c->d_fs_fk.p + (size_t)B * 6 : nullptr;
+    const int rc = launch_frame_positions(c, c->d_fs_fk.p, nullptr, feet_R);
+    if (rc) return rc;
+    a.feet = c->d_fs_fk.p, a.feet_R = feet_R, a.landed = 1;
+  } else {
+    if (cur != 0) return RTOC_OK;   // in the air or landed: nothing changes (:150)
+    cur = 1, size = 2;
+  }
+  const unsigned per = 64 / (unsigned)nf;
+  const dim3 grid((unsigned)((B + per - 1) / per));
+  if (nf == 2)
+    hipLaunchKernelGGL(jump_plan_kernel<2>, grid, dim3(64), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(jump_plan_kernel<4>, grid, dim3(64), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  c->fs_current_step = cur, c->fs_size = size;
+  return RTOC_OK;
+}
+
 int rtoc_foot_step_plan(rtoc_ctx* c, double t, unsigned contact_status0, int planning_steps) {
   CHECK_READY(c);
   if (!c->fs_on || !c->fs_init || !c->h_model || !c->d_x0.p || !c->d_fs_state.p || !c->d_fs_plan.p || !c->d_fs_cmd.p) return RTOC_ERR_NOT_READY;
   const bool flying = c->fs_shared.gait == RTOC_GAIT_FLYING_TROT;   // its plan is one step longer
   if (planning_steps < 0 || planning_steps > RTOC_MAX_PLAN_STEPS - (flying ? 1 : 0) || !std::isfinite(t)) return RTOC_ERR_BAD_ARG;
+  if (jump(c)) return jump_plan(c, contact_status0);   // t, v and planning_steps are not read (:127-131)
   FsPlanArgs a{};
   int cur = c->fs_current_step;
   if (!plan_cases(c->fs_shared, contact_status0, planning_steps, c->fs_size > 0, &cur, &a)) return RTOC_ERR_BAD_ARG;
@@ -237,7 +320,7 @@ int rtoc_foot_step_plan_get(rtoc_ctx* c, double* positions, double* com, double*
   if (size) *size = c->fs_size;
   if (current_step) *current_step = c->fs_current_step;
   const size_t B = c->batch, ns = c->fs_size;
-  // where the gait's plan keeps what: the quadrupeds' positions are [4][3]; the biped walk's 24 doubles are contactPositions(step)[2][3]
+  // where the plan keeps what, by the feet: four point feet's positions are [4][3]; two surfaces' 24 doubles are contactPositions(step)[2][3]
   // and contactSurfaces(step)[2][9] behind them, adjacent in the plan too
   const bool two = biped(c);
   const size_t slots = plan_slots(c);
@@ -245,7 +328,9 @@ int rtoc_foot_step_plan_get(rtoc_ctx* c, double* positions, double* com, double*
   static_assert(FS_BIPED_SURF == FS_BIPED_POS + 6, "translations and rotations are read back as one run");
   std::vector<double> h(ns * slots * B), sl(3 * B);
   if (ns) HIP_TRY(hipMemcpyAsync(h.data(), c->d_fs_plan.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(sl.data(), c->d_fs_state.p + (size_t)FS_ST_STEP * B, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
+  // the length in force: the planner state's; a jump has none but its command, jump_length_
+  const double* const sl_src = jump(c) ? c->d_fs_cmd.p + (size_t)FS_CMD_STEP * B : c->d_fs_state.p + (size_t)FS_ST_STEP * B;
+  HIP_TRY(hipMemcpyAsync(sl.data(), sl_src, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (size_t b = 0; b < (size_t)count; ++b) {
     bool fin = true;
@@ -297,9 +382,29 @@ int rtoc_foot_step_place(rtoc_ctx* c, const int* phase_of_grid_point, int nstage
   return RTOC_OK;
 }
 
+// The jump's configuration reference: the q_ref of MPCJump::init (mpc_jump.cpp:141-145) on every grid row.  It does not depend on
+// the grid times, so a grid with switching-time optimisation is served and rtoc_set_grid_times is not needed
+static int jump_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, int nstages) {
+  if (!c->fs_init || !c->h_model || !c->d_fs_qref.p) return RTOC_ERR_NOT_READY;
+  if (nstages != c->nstages || !r->configuration || r->com_term >= 0 || c->dims.np != 6) return RTOC_ERR_BAD_ARG;
+  for (int k = 0; k < 4; ++k)
+    if (r->foot_term[k] >= 0) return RTOC_ERR_BAD_ARG;   // MPCJump has no swing-foot or CoM reference
+  const size_t nq = c->h_model->m.nq;
+  HIP_TRY(stage_rows(c, c->qtab, nq, 1));
+  HIP_TRY(stage_rows(c, c->qtab_active, 1, 1));
+  JumpRefsArgs a{};
+  a.qref = c->d_fs_qref.p, a.qtab = c->qtab.target(), a.qtab_active = c->qtab_active.target();
+  a.batch = c->batch, a.nstages = nstages, a.nq = (int)nq;
+  hipLaunchKernelGGL(jump_refs_kernel, dim3(blocks_for((size_t)c->batch * nstages * nq)), dim3(256), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  commit_rows(c, c->qtab, 1), commit_rows(c, c->qtab_active, 1);
+  return RTOC_OK;
+}
+
 int rtoc_foot_step_refs(rtoc_ctx* c, const rtoc_foot_step_ref_params* r, const int* phase_of_grid_point, const unsigned* phase_masks,
                         int nphases, int nstages) {
   CHECK_READY(c);
+  if (r && c->fs_on && jump(c)) return jump_refs(c, r, nstages);
   if (!r || !phase_of_grid_point || !phase_masks) return RTOC_ERR_BAD_ARG;
   if (c->sto_on) return RTOC_ERR_BAD_ARG;   // every instance its own grid times: out of scope
   if (!c->fs_on || !c->fs_init || c->fs_size < 1 || !c->d_fs_q0.p || !c->d_fs_plan.p) return RTOC_ERR_NOT_READY;

@@ -162,11 +162,16 @@ int rtoc::placements_per_instance(rtoc_ctx* c, bool need_rot) {
   }
   return RTOC_OK;
 }
-// the kinematics at the q of rtoc_set_initial_state, the result left on the device (rt_foot_steps.hip)
-int rtoc::launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com, double* out_R) {
+// the kinematics at the q of rtoc_set_initial_state, or at q[batch] a q_stride apart (FkArgs::q takes any source), the result left on
+// the device (rt_foot_steps.hip)
+int rtoc::launch_frame_positions(rtoc_ctx* c, double* out_p, double* out_com, double* out_R, const double* q, size_t q_stride) {
   FkArgs a{};
-  const int rc = placement_source(c, 0, 0, &a.q, &a.q_stride);
-  if (rc) return rc;
+  if (q) {
+    a.q = q, a.q_stride = q_stride;
+  } else {
+    const int rc = placement_source(c, 0, 0, &a.q, &a.q_stride);
+    if (rc) return rc;
+  }
   a.out_p = out_p, a.out_com = out_com, a.out_R = out_R;
   return launch_frame_placements(c, a);
 }

@@ -505,11 +505,11 @@ class SolutionInterpolator {
   bool has_ = false;
 };
 
-// robotoc::TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner, BipedWalkFootStepPlanner
-// (src/mpc/{trot,crawl,pace,flying_trot,biped_walk}_foot_step_planner.cpp) for the batch of a context: thin mirrors over
+// robotoc::TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner, BipedWalkFootStepPlanner,
+// JumpFootStepPlanner (src/mpc/{trot,crawl,pace,flying_trot,biped_walk,jump}_foot_step_planner.cpp) for the batch of a context: thin mirrors over
 // rtoc_set_foot_step_planner / rtoc_foot_step_planner_init / rtoc_foot_step_plan / rtoc_foot_step_plan_get (include/rtoc_robot.h).
 // The planning runs on the device from the q, v of rtoc_set_initial_state; commands are one for the batch or one per instance.
-// FootStepPlannerBase is what the five share; a gait's class names its RTOC_GAIT_*, its legal contact statuses and its setters.
+// FootStepPlannerBase is what the six share; a gait's class names its RTOC_GAIT_*, its legal contact statuses and its setters.
 class FootStepPlannerBase {
  public:
   // init(q) / plan(t, q, v, ..) at the initial state of the context (rtoc_set_initial_state)
@@ -575,6 +575,10 @@ class FootStepPlannerBase {
     chk(rtoc_set_foot_step_planner(ctx_, p.data(), inst ? 1 : 0), "rtoc_set_foot_step_planner");
     fresh_ = false;
   }
+  rtoc_ctx* ctx() const { return ctx_; }
+  static void chk(const int rc, const char* what) {
+    if (rc != RTOC_OK) throw std::runtime_error(std::string(what) + ": " + rtoc_error_string(rc));
+  }
 
  private:
   bool perInstance(const size_t n, const size_t width, const char* what) const {
@@ -589,9 +593,6 @@ class FootStepPlannerBase {
     chk(rtoc_foot_step_plan_get(ctx_, pos_.data(), com_.data(), R_.data(), sl_.data(), ok_.data(), batch_, &size_, &current_step_),
         "rtoc_foot_step_plan_get");
     fresh_ = true;
-  }
-  static void chk(const int rc, const char* what) {
-    if (rc != RTOC_OK) throw std::runtime_error(std::string(what) + ": " + rtoc_error_string(rc));
   }
   rtoc_ctx* ctx_;
   int batch_, projection_, gait_, size_, current_step_;
@@ -671,6 +672,74 @@ class BipedWalkFootStepPlanner : public FootStepPlannerBase {
     return {Placement{p, p + 6}, Placement{p + 3, p + 15}};
   }
 };
+
+// jump_foot_step_planner.cpp:11-195 on a model of four point contacts (num_feet = 4) or of two contact surfaces (num_feet = 2,
+// is_biped_): one jump of jump_length and step_yaw, each instance's own.  init() also stores the q_ref of MPCJump::init
+// (mpc_jump.cpp:141-145) on the device; the plan has three steps until the feet leave the ground, two from then on.  plan() takes
+// any contact status of the model's contacts (:132, hasActiveContacts) and reads neither t nor planning_steps.  contactPositions and
+// contactSurfaces are the two parts of contactPlacements for every foot (the reference keeps feet 0 and 1 alone, :110-113); a
+// second init() starts over (the reference keeps the first init's centres of mass, :115-118).  The receding horizon of
+// MPCJump::updateSolution (mpc_jump.cpp:206-222) stays with the caller.
+class JumpFootStepPlanner : public FootStepPlannerBase {
+ public:
+  JumpFootStepPlanner(rtoc_ctx* ctx, const int batch, const int num_feet, const int projection = RTOC_PROJECT_AS_REFERENCE)
+      : FootStepPlannerBase(ctx, batch, projection, RTOC_GAIT_JUMP, "JumpFootStepPlanner", everyStatus(num_feet), num_feet == 2 ? 24 : 12),
+        num_feet_(num_feet) {}
+  // jump_length: 3 doubles for the batch or 3 per instance; step_yaw: one or one per instance (:43-49)
+  void setJumpPattern(const std::vector<double>& jump_length, const std::vector<double>& step_yaw) { setFixed(jump_length, step_yaw, false); }
+  bool plan(const double t, const unsigned contact_status, const int planning_steps = 0) {
+    return FootStepPlannerBase::plan(t, contact_status, planning_steps);
+  }
+  const double* jumpLength(const int b) { return stepLength(b); }
+  bool isBiped() const { return num_feet_ == 2; }
+  // of instance b: [num_feet][9] row-major; four point feet: identities (:99-105), which the plan does not store
+  const double* contactSurfaces(const int b, const int step) {
+    if (isBiped()) return contactPositions(b, step) + 6;
+    static const double eye[36] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+    return eye;
+  }
+  std::vector<BipedWalkFootStepPlanner::Placement> contactPlacements(const int b, const int step) {
+    const double* const p = contactPositions(b, step);
+    const double* const S = contactSurfaces(b, step);
+    std::vector<BipedWalkFootStepPlanner::Placement> out;
+    for (int k = 0; k < num_feet_; ++k) out.push_back({p + 3 * k, S + 9 * k});
+    return out;
+  }
+  // config_cost_->set_q_ref(q_ref) of MPCJump::init for every instance: the stored q_ref onto every row of the per-instance
+  // configuration reference of the grid in force (rtoc_foot_step_refs; needs no grid times, serves switching-time optimisation)
+  // nstages: the grid's (TimeDiscretization::size())
+  void setConfigurationRef(const int nstages) {
+    rtoc_foot_step_ref_params r = rtoc_foot_step_ref_params();
+    for (int k = 0; k < 4; ++k) r.foot_term[k] = -1;
+    r.com_term = -1, r.configuration = 1;
+    chk(rtoc_foot_step_refs(ctx(), &r, nullptr, nullptr, 0, nstages), "rtoc_foot_step_refs");
+  }
+  // the placing half of MPCJump::resetContactPlacements (mpc_jump.cpp:305-316): contact phase 0 <- contactPlacements(1) and, before
+  // the flight, phases 1 and 2 <- contactPlacements(2); after it every phase <- contactPlacements(1)
+  void place(const std::vector<int>& phase_of_grid_point) {
+    std::vector<int> ph(phase_of_grid_point);
+    const int last = size() - 2;
+    for (auto& e : ph) e = std::min(e, last);
+    FootStepPlannerBase::place(ph);
+  }
+
+ private:
+  static std::vector<unsigned> everyStatus(const int num_feet) {
+    if (num_feet != 2 && num_feet != 4) throw std::out_of_range("[JumpFootStepPlanner] invalid argument: robot is not a quadrupedal robot or a bipedal robot!");
+    std::vector<unsigned> out;
+    for (unsigned s = 0; s < (1u << num_feet); ++s) out.push_back(s);
+    return out;
+  }
+  int num_feet_;
+};
+
+// MPCJump::resetContactPlacements (mpc_jump.cpp:301-317) for every instance: plan at the q of rtoc_set_initial_state, then place
+inline bool resetContactPlacements(JumpFootStepPlanner& planner, const double t, const unsigned contact_status0,
+                                   const std::vector<int>& phase_of_grid_point) {
+  if (!planner.plan(t, contact_status0)) return false;
+  planner.place(phase_of_grid_point);
+  return true;
+}
 
 }  // namespace robotoc
 #endif  // ROBOTOC_HIP_PLANNER_HPP_

@@ -1,8 +1,9 @@
-"""TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner and BipedWalkFootStepPlanner over a
-capi.Context: the surface of the reference's classes (src/mpc/{trot,crawl,pace,flying_trot,biped_walk}_foot_step_planner.cpp) for a
+"""TrotFootStepPlanner, CrawlFootStepPlanner, PaceFootStepPlanner, FlyingTrotFootStepPlanner, BipedWalkFootStepPlanner and
+JumpFootStepPlanner over a
+capi.Context: the surface of the reference's classes (src/mpc/{trot,crawl,pace,flying_trot,biped_walk,jump}_foot_step_planner.cpp) for a
 batch, every instance with its own command.  The planning runs on the device (rtoc_foot_step_*, include/rtoc_robot.h); these shells
-hold no state of their own beyond the commands they were given.  The five share one body; a class names its gait, its legal contact statuses and what its setters
-check."""
+hold no state of their own beyond the commands they were given.  The five periodic gaits share one body; a class names its gait, its legal contact statuses and what its setters
+check.  The jump has its own setter, plans without a step count, and places by MPCJump's mapping."""
 import numpy as np
 
 from . import capi
@@ -200,3 +201,77 @@ class FlyingTrotFootStepPlanner(TrotFootStepPlanner):
             raise ValueError("'stance_time' must be positive")
         if gain <= 0.0:
             raise ValueError("'gain' must be positive")
+
+
+class JumpFootStepPlanner(TrotFootStepPlanner):
+    """src/mpc/jump_foot_step_planner.cpp on a robot model of four point contacts or of two contact surfaces: one jump of
+    jump_length and step_yaw, each instance's own.  init measures the feet, sets the goal placements, the goal centre of mass and
+    the q_ref of MPCJump::init (src/mpc/mpc_jump.cpp:141-145); the plan has three steps until the feet leave the ground and two
+    from then on.  The receding horizon of MPCJump::updateSolution stays with the caller."""
+    GAIT = capi.GAIT_JUMP
+
+    def set_jump_pattern(self, jump_length, step_yaw):
+        """setJumpPattern (:43-49): jump_length [3] or [batch, 3], step_yaw a scalar or [batch]"""
+        super().set_gait_pattern(jump_length, step_yaw, False)
+
+    def set_gait_pattern(self, *args):
+        raise TypeError("a jump has no gait pattern: set_jump_pattern")
+
+    def set_raibert_gait_pattern(self, *args):
+        raise TypeError("the reference has no Raibert form of a jump: set_jump_pattern")
+
+    def _feet(self):
+        return self.ctx._model_ncontacts
+
+    def plan(self, t, contact_status, planning_steps=0, x0=None):
+        """plan(t, q, v, contact_status, planning_steps) (:127-170); t and planning_steps are not read.  Any contact status of the
+        model's contacts is accepted, as in the reference; a bit beyond them raises."""
+        if x0 is not None:
+            self.ctx.set_initial_state(x0)
+        self.ctx.foot_step_plan(t, contact_status, planning_steps)
+        self._plan = None
+        return True
+
+    def current_step(self):
+        return self._get()["current_step"]
+
+    def contact_positions(self, step):
+        """[batch, feet, 3]: the translations of contactPlacements(step), every foot"""
+        return self._get()["positions"][:, step]
+
+    def contact_surfaces(self, step):
+        """[batch, feet, 3, 3]: the rotations of contactPlacements(step); identities for a quadruped (:99-105)"""
+        g = self._get()
+        if "surfaces" in g:
+            return g["surfaces"][:, step]
+        return np.broadcast_to(np.eye(3), (self.ctx.batch, self._feet(), 3, 3)).copy()
+
+    def contact_placements(self, step):
+        """(rotations [batch, feet, 3, 3], translations [batch, feet, 3]): contactPlacements(step) as SE3's two parts"""
+        return self.contact_surfaces(step), self.contact_positions(step)
+
+    def jump_length(self):
+        """[batch, 3]"""
+        return self._get()["step_length"]
+
+    def set_configuration_ref(self):
+        """config_cost_->set_q_ref(q_ref) of MPCJump::init for every instance: the q_ref stored by init onto every row of the
+        per-instance configuration reference of the grid in force"""
+        r = capi.FootStepRefs()
+        r.foot_term[:] = [-1] * 4
+        r.com_term, r.configuration = -1, 1
+        self.ctx.foot_step_refs(r)
+
+    def reset_contact_placements(self, t, contact_status, phase_of_grid_point, x0=None):
+        """MPCJump::resetContactPlacements (src/mpc/mpc_jump.cpp:301-317): plan, then contact phase 0 <- contactPlacements(1) and,
+        before the flight, phases 1 and 2 <- contactPlacements(2); after it every phase <- contactPlacements(1).
+        phase_of_grid_point: GridInfo::phase of every grid point relative to the first."""
+        self.plan(t, contact_status, 0, x0)
+        self.place(phase_of_grid_point)
+        return True
+
+    def place(self, phase_of_grid_point):
+        """the placing half of reset_contact_placements, from the plan as it stands: what a re-discretisation repeats"""
+        self._plan = None   # (the plan may have moved on through the context)
+        ph = np.minimum(np.asarray(phase_of_grid_point, dtype=np.int32), self.size() - 2)
+        self.ctx.foot_step_place(ph)

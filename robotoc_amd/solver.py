@@ -220,7 +220,7 @@ def interpolate_configuration(q1, q2, alpha, floating):
 class OCPSolver:
     def __init__(self, model, plan: ContactPlan, T, N, cost, joint_limits=None, friction_coefficients=None, barrier_param=1.0e-3,
                  fraction_to_boundary_rule=0.995, sto_constraints: Optional[STOConstraints] = None, options: Optional[SolverOptions] = None,
-                 batch=1, device=0, impact_cones=False, task_costs=None, force_cost=None, configuration_ref=None):
+                 batch=1, device=0, impact_cones=False, task_costs=None, force_cost=None, configuration_ref=None, contact_planner=None):
         """cost: keyword arguments of capi.Context.set_configuration_cost; joint_limits: (q_min, q_max, v_max, u_max) over the
         actuated joints or None; friction_coefficients: per contact or None; task_costs: robotoc_amd.costs.TaskSpace3DCost /
         CoMCost / TaskSpace6DCost components added to the configuration cost (a list shared by the batch) or None; force_cost: a
@@ -229,7 +229,12 @@ class OCPSolver:
         (ConfigurationSpaceCost::set_ref) -- shared by the batch, a list of `batch` of them (every instance its own), or None.  The
         object is asked once per grid point at every (re-)discretisation, mesh refinements included; with switching-time
         optimisation at the times of the structure the batch shares (those of the mean event times), not at every instance's own
-        -- the rule the task costs' user-object references follow."""
+        -- the rule the task costs' user-object references follow.  contact_planner: a robotoc_amd.planner.JumpFootStepPlanner (any
+        object with place(phase_of_grid_point) and set_configuration_ref()) or None.  With one, every (re-)discretisation, mesh
+        refinements included, ends with the planner writing every instance's placements and q_ref from its plan on the device onto
+        the grid just set, in place of the plan's shared placements and the cost's constant q_ref; a planner made without a context
+        is given this solver's.  The planner's init needs a grid on the context, so a planner that is not initialised yet is handed
+        over after the first discretize instead, through set_contact_planner."""
         self.model, self.plan, self.T, self.N = model, plan, float(T), int(N)
         self.options = options or SolverOptions()
         self.sto = sto_constraints
@@ -248,6 +253,10 @@ class OCPSolver:
         c.set_robot_model(model)
         c.set_configuration_cost(**cost)
         self.cost, self.configuration_ref = cost, configuration_ref
+        self.contact_planner = contact_planner
+        if contact_planner is not None and getattr(contact_planner, "ctx", None) is None:
+            contact_planner.ctx = c
+        self._phase = None
         if isinstance(configuration_ref, (list, tuple)) and len(configuration_ref) != batch:
             raise ValueError("a per-instance configuration_ref needs one object per instance")
         self.task_costs = list(task_costs) if task_costs else None
@@ -291,8 +300,10 @@ class OCPSolver:
         of the mean event times; every instance gets its own time steps from its own event times (rtoc_sto_set_problem)."""
         self.t0 = float(t)
         cs = self._sequence(self.event_times.mean(axis=0))
-        if self.task_costs or self.configuration_ref is not None:
+        self._phase = None
+        if self.task_costs or self.configuration_ref is not None or self.contact_planner is not None:
             grids, times, structure = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None, times=True, infos=True)
+            self._phase = [s[1] for s in structure]   # GridInfo::phase of every grid point
         else:
             grids = discretize(self.N, self.T, t, cs, phase_based=self.sto is not None)
         nev = sum(1 for g in grids if g.type in (GRID_IMPACT, GRID_LIFT))
@@ -324,6 +335,29 @@ class OCPSolver:
         if self.sto is not None and len(self.plan.events) > 0:
             c.sto_set_problem(self.t0, self.T, self.event_times, self.sto.minimum_dwell_times, self.sto.barrier_param,
                               self.sto.fraction_to_boundary_rule)
+        if self.contact_planner is not None:
+            # rtoc_set_grid has just forgotten the tables; the plan and the stored q_ref are still on the device
+            self._plan_onto_grid()
+
+    def _plan_onto_grid(self):
+        if self._phase is None:   # the grid in force was made without a planner: its structure once more
+            cs = self._sequence(self.event_times.mean(axis=0))
+            structure = discretize(self.N, self.T, self.t0, cs, phase_based=self.sto is not None, times=True, infos=True)[2]
+            self._phase = [s[1] for s in structure]
+        self.contact_planner.place(self._phase)
+        self.contact_planner.set_configuration_ref()
+
+    def set_contact_planner(self, contact_planner):
+        """the contact_planner of the constructor, handed over later: an initialised planner on this solver's context (one made
+        without a context is given it).  With a grid in force it places and sets q_ref at once; None takes the planner away (the
+        tables it wrote stay until the next discretize)."""
+        self.contact_planner = contact_planner
+        if contact_planner is None:
+            return
+        if getattr(contact_planner, "ctx", None) is None:
+            contact_planner.ctx = self.ctx
+        if self.grids is not None:
+            self._plan_onto_grid()
 
     def grid_times(self, b=0):
         """t of every grid point of instance b (TimeDiscretization::grid(i).t)"""
